@@ -20,13 +20,25 @@ Workload at N > 1: BASELINE.json configs[3] (4096 envs in total, sharded over th
 one RCCL all-gather of the episode returns closing the job).  --envs-per-gpu / --total-envs override either.
 Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, pre-warm, W warm-up steps, the K timed steps, the outputs (--dump-outputs) and the line
+(metric, value, unit, ms_per_step, ...; `roofline` where the timed steps' own HIP events give it: launch mode, the pilot loop).  --full adds
+everything that takes runs of its own: in resident mode the second pass of the K steps behind `roofline` and `value_incl_worker_launch`, the CPU
+baseline (`cpu_baseline`, unless --no-cpu-baseline) and the informational legs (`also`: the other BASELINE configs, the pilot loop, the image
+path, the hilly track; unless --no-also).
+
+--dump-outputs DIR writes what the timed path computed in its last step, right after the timed steps, as DIR/<name>.npy in float32 / float64
+(pose, speed, cte, indices, flags, returns; the frames (and depth frames) of a fixed, seeded sample of the envs, `img_env_idx.npy` naming them;
+with --pilot the controls the pilot produced).  The pre-warm is a fixed number of steps for given arguments and the synthetic controls are keyed
+by (seed, env id, step count), so the same arguments give the same inputs on every run and two builds can be compared output for output.
+At N > 1 every rank writes its own shard, as rank<r>_<name>.npy.
+
 Timing (round 3).  The metric is a steady-state rate.  An idle MI355X needs ~25-40 ms of work to raise its clocks, so untimed steps
-of the same workload run for PREWARM_S first, then the W warm-up steps.  In resident mode the worker stays on the GPU across the warm-up -> timed
-boundary: `value` is the host wall clock from the post of the first timed step to the completion flag of the last (env.sync() waits on the flags
-the worker writes once a step's frames are in memory); a device-wide synchronisation there would wait for the worker to leave, so torch's stream
-is synchronised instead.  `roofline.achieved` comes from a second pass of the same K steps bracketed by HIP events on the worker's own stream
-(= one whole worker launch: start-up, K steps, exit).  --profile-mode (scripts/profile.sh) runs the pre-warm by launches (a resident worker's
-pre-warm dispatch would be of no fixed length) and makes every worker dispatch of a trace serve exactly K steps.
+of the same workload run first (about PREWARM_S of work, prewarm_steps()), then the W warm-up steps.  In resident mode the worker stays on the GPU
+across the warm-up -> timed boundary: `value` is the host wall clock from the post of the first timed step to the completion flag of the last
+(env.sync() waits on the flags the worker writes once a step's frames are in memory); a device-wide synchronisation there would wait for the worker
+to leave, so torch's stream is synchronised instead.  With --full, `roofline.achieved` comes from a second pass of the same K steps bracketed by HIP
+events on the worker's own stream (= one whole worker launch: start-up, K steps, exit).  --profile-mode (scripts/profile.sh) runs the pre-warm by
+launches (a resident worker's pre-warm dispatch would be of no fixed length) and makes every worker dispatch of a trace serve exactly K steps.
 """
 import argparse
 import ctypes
@@ -40,6 +52,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PREWARM_S = 0.08               # untimed steps of the same workload before the W warm-up steps: GPU clocks at their loaded level
+DUMP_FRAME_BYTES = 48 << 20    # --dump-outputs: the frames of at most this many bytes (as float32) of sampled envs ...
+DUMP_ENV_BYTES = 12 << 20      # ... and the per-env values of every env up to this many bytes (64 MB in all at most)
 
 
 # What v_mfma_f32_32x32x16_f16 delivers on this chip when all 1,024 SIMDs stream it from registers (scripts/mfma_issue.hip, profiles/r04_mfma_issue.txt:
@@ -139,6 +153,47 @@ def pilot_weights(h, w):
         ws += [rng.uniform(-lim, lim, (a_, b_)).astype("float32"), np.zeros(b_, "float32")]
         macs += a_ * b_
     return ws, macs
+
+
+def prewarm_steps(n, h, w, render, depth, pilot_flops=None):
+    """The untimed steps before the W warm-up steps: about PREWARM_S of work at this build's per-step times (the camera step ~6 TB/s of
+    algorithmic bytes, 3 us at least; the pilot's forward ~0.7 PFLOP/s: 9.8 us and 168 us per step at 1024 envs x 120x160), in chunks of
+    400 steps (50 with the pilot).  A FIXED count for given arguments, not a time: the synthetic controls are keyed by the step count, so the
+    timed steps then start at the same step on every run (--dump-outputs).  Returns (chunks, steps per chunk)."""
+    step_s = max(3e-6, n * algorithmic_bytes(h, w, render, depth) / 6.0e12)
+    chunk = 400
+    if pilot_flops:
+        step_s += n * pilot_flops / 7.0e14
+        chunk = 50
+    return max(1, -(-int(PREWARM_S / step_s) // chunk)), chunk
+
+
+def dump_outputs(env, out_dir, prefix="", pilot=False):
+    """--dump-outputs: what the timed path computed in its last step, i.e. what a caller of that path receives (the telemetry of
+    trs_fetch_outputs plus yaw / returns / episode lengths; frames; with the pilot its controls), as float32 / float64 .npy files.  The
+    frames are those of a fixed, seeded sample of the envs (img_env_idx.npy), at most DUMP_FRAME_BYTES as float32; the per-env values are
+    those of every env up to DUMP_ENV_BYTES (beyond that of a seeded sample too, env_idx.npy), so that the files stay under 64 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sample = lambda k: np.sort(np.random.default_rng(0).choice(env.n, size=k, replace=False))
+    f32 = ("pos_x", "pos_y", "pos_z", "yaw", "speed", "cte", "ep_return", "last_return") + (("ctl_steer", "ctl_thr", "ctl_brk") if pilot else ())
+    f64 = ("seg_idx", "ep_len", "done")
+    per_env = 4 * len(f32) + 8 * len(f64)
+    sel = slice(None) if env.n * per_env <= DUMP_ENV_BYTES else sample(DUMP_ENV_BYTES // per_env)
+    out = {} if isinstance(sel, slice) else {"env_idx": sel.astype(np.float64)}
+    for name in f32:
+        out[name] = env.fetch(name)[sel].astype(np.float32)
+    for name in f64:
+        out[name] = env.fetch(name)[sel].astype(np.float64)
+    if env.cfg.render:
+        idx = sample(max(1, min(env.n, DUMP_FRAME_BYTES // (env.H * env.W * (3 + (1 if env.cfg.depth else 0)) * 4))))
+        out["img_env_idx"] = idx.astype(np.float64)
+        out["img"] = env.fetch("img")[idx].astype(np.float32)
+        if env.cfg.depth:
+            out["depth"] = env.fetch("depth")[idx].astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+    return sorted(out)
 
 
 def config1_car_loop(device, ticks=1500):
@@ -443,8 +498,11 @@ def main():
     ap.add_argument("--pilot", action="store_true", help="closed loop with cnn_2d_speed_control inference on the device frame each step (BASELINE configs[4] shape)")
     ap.add_argument("--depth", action="store_true", help="also write the binary32 depth frame (BASELINE configs[4] frame format)")
     ap.add_argument("--pilot-tuning", default="", help="with --pilot: kernel choices for measurements, e.g. dense=2,ksplit=32 (fields of trs_pilot_tuning, include/trsim.h)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the informational 8-steps-per-launch leg (profiling runs: only the timed kernel in the trace)")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own: in resident mode the second pass of the K steps behind roofline and "
+                                                         "value_incl_worker_launch, the CPU baseline and the informational legs (`also`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what their last step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the informational legs (profiling runs: only the timed kernel in the trace)")
     ap.add_argument("--profile-mode", action="store_true", help="for rocprofv3 runs (scripts/profile.sh): the clock pre-warm goes by launches (trs_step_kernel), and a resident worker is asked to leave after the "
                                                                   "warm-up, so that every trs_worker_kernel dispatch of the trace serves exactly --steps (or --warmup) steps")
     ap.add_argument("--force-dist", action="store_true", help="initialise the nccl process group even at world size 1 (path rehearsal)")
@@ -562,20 +620,20 @@ def main():
             sys.exit(f"rank {rank}: the warm-up all-gather returned contributions {seen[:16]}, expected one per rank 1..{world}")
     # An idle MI355X takes ~25-40 ms of work to raise its clocks: the first 2,000 steps of a fresh process run 12-14 % slower than the
     # steady state (profiles/r03_steady_state.txt: 10.85 us per step, then 9.46-9.58).  The metric is a steady-state rate, and
-    # the driver's --warmup 5 is 50 us, so the clocks are brought up first — with untimed steps of the same workload, for PREWARM_S
-    # seconds — and the W warm-up steps follow.  `config.prewarm_s` says so in the line.
-    t_pw = time.perf_counter()
+    # the driver's --warmup 5 is 50 us, so the clocks are brought up first — with untimed steps of the same workload, about PREWARM_S
+    # seconds of them (a fixed count: prewarm_steps) — and the W warm-up steps follow.  `config.prewarm_s` / `prewarm_steps` say so in the line.
+    pw_chunks, pw_chunk = prewarm_steps(n, args.img_h, args.img_w, render, args.depth, pilot_flops if args.pilot else None)
     if args.profile_mode and resident:
         # under the profiler the pre-warm steps go by LAUNCHES (trs_step_kernel: its own row of the stats table), so that every trs_worker_kernel
         # dispatch in the trace is one of the three equal ones below, and all three run at loaded clocks like the line's own (until round 5 the
         # profiled command had no pre-warm at all: its first dispatch ran 15-20 % slow and pulled the table's average off the line's figure)
         env.set_step_mode(False)
-        while time.perf_counter() - t_pw < PREWARM_S:
-            run(400)
+        for _ in range(pw_chunks):
+            run(pw_chunk)
             env.sync()
         env.set_step_mode(True)
-    while not args.profile_mode and time.perf_counter() - t_pw < PREWARM_S:
-        run(50 if args.pilot else 400)
+    for _ in range(0 if args.profile_mode else pw_chunks):
+        run(pw_chunk)
         env.sync()
     run(max(args.warmup, 1))
     if args.profile_mode and resident:
@@ -589,6 +647,9 @@ def main():
             env.event_record(1)
 
     wall = timed_steps(env, timed_run, args.steps, host_barrier, stream_sync)
+    if args.dump_outputs:
+        # what the LAST timed step computed, before anything else steps this env (a resident worker stays: the copies go on its side stream)
+        dump_outputs(env, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "", pilot=args.pilot)
     # the job's ONE exchange: an all-gather of the episode returns (4 B per env) per reporting interval — configs[3]: one per 1000 steps —
     # so it closes the job here, timed on its own, not inside the K timed steps (a resident worker is asked to leave first, outside the timing)
     gathered, allgather_s = None, None
@@ -602,24 +663,26 @@ def main():
         mine = torch.as_tensor(env.fetch("ep_return"))
         if not torch.equal(gathered.cpu()[shard.base:shard.base + n], mine):
             sys.exit(f"rank {rank}: the gathered returns do not hold this shard's values at [{shard.base}, {shard.base + n})")
-    if resident:
-        # the dominant kernel's launch duration by HIP events on its own stream: an event on that stream makes the worker leave, so this
-        # is a SECOND pass over the same K steps, bracketed by events = exactly one trs_worker_kernel launch (start-up, K steps, exit)
-        env.quiesce()
-        torch.cuda.synchronize()
-        env.event_record(0)
-        run(args.steps)
-        env.event_record(1)
-        env.sync()
-    kernel_ms = env.event_elapsed_ms(0, 1)
-    if dist is not None:
-        with phase("MAX of the event time over ranks (gloo)", PHASE_S):
-            kernel_ms = max_over_ranks(kernel_ms, host_group)        # (rank 0's own event time x world was not the job's)
+    kernel_ms = None
+    if args.full or not resident:                # launch mode: the timed steps' own HIP events; resident mode: a run of its own (--full)
+        if resident:
+            # the dominant kernel's launch duration by HIP events on its own stream: an event on that stream makes the worker leave, so this
+            # is a SECOND pass over the same K steps, bracketed by events = exactly one trs_worker_kernel launch (start-up, K steps, exit)
+            env.quiesce()
+            torch.cuda.synchronize()
+            env.event_record(0)
+            run(args.steps)
+            env.event_record(1)
+            env.sync()
+        kernel_ms = env.event_elapsed_ms(0, 1)
+        if dist is not None:
+            with phase("MAX of the event time over ranks (gloo)", PHASE_S):
+                kernel_ms = max_over_ranks(kernel_ms, host_group)        # (rank 0's own event time x world was not the job's)
     mode_after = env.step_mode()
 
     # informational only (never part of `value`): the same workload with 8 steps per launch, timed separately
     also = None
-    if render and not args.pilot and spl == 1 and world == 1 and not args.no_also:
+    if args.full and render and not args.pilot and spl == 1 and world == 1 and not args.no_also:
         env.set_step_mode(False)
         env.sync()
         # ... one kernel launch per step, controls from the in-kernel generator (round 1's headline path)
@@ -836,27 +899,6 @@ def main():
         total_env_steps = n * world * args.steps
         value = total_env_steps / wall
         B = algorithmic_bytes(args.img_h, args.img_w, render, args.depth)
-        # camera on: the library pipelines a call over ceil(steps/spl)+1 launches of trs_step_kernel (physics runs ahead of the
-        # raster inside and across launches); physics only: steps/spl launches of trs_physics_kernel
-        launches = ((args.steps + spl - 1) // spl + 1) if render else (args.steps + spl - 1) // spl
-        if resident:
-            launches = 1                                                # one trs_worker_kernel launch serves every posted step of the timed region
-        avg_launch_s = kernel_ms * 1e-3 / launches
-        per_launch = n * args.steps / launches                         # env-steps one launch completes
-        achieved = B * per_launch / avg_launch_s / 1e9                 # GB/s of algorithmic bytes, dominant (only) kernel
-        traffic = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        traffic_key = f"{n}x{args.img_h}x{args.img_w}" + ("+depth" if args.depth else "") + (":resident" if resident else f":spl{spl}")
-        if os.path.exists(pmc):
-            try:
-                # scripts/summarize_profile.py writes {"per_env_step": {"<envs>x<H>x<W>[+depth]:<resident|splK>": HBM bytes per env-step}} from the
-                # WRITE_SIZE / FETCH_SIZE passes of scripts/profile.sh (unit + gfx950 corrections of MI355X_MICROARCH.md applied); per launch = x the
-                # env-steps one launch completes, like `achieved`
-                with open(pmc) as f:
-                    per_step = json.load(f).get("per_env_step", {}).get(traffic_key)
-                traffic = None if per_step is None else per_step * per_launch
-            except Exception:
-                traffic = None
         line = {
             "metric": "env-steps/s (whole node) at N envs x 120x160 RGB",
             "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -869,34 +911,60 @@ def main():
                             + f" = {picked}" + (f": {n * world} envs in total over {world} GPUs, one RCCL all-gather of ep_return" if world > 1 else "")
                             + ", generated_track 1185 pts, synthetic controls seed 0x5EED, auto-reset",
                 "envs_total": n * world, "envs_per_gpu": n, "img_h": args.img_h, "img_w": args.img_w, "depth": bool(args.depth), "steps_per_launch": spl, "step_mode": "resident worker (posted steps)" if resident else "one launch per call", "prewarm_s": PREWARM_S if (resident or not args.profile_mode) else 0.0,
+                "prewarm_steps": pw_chunks * pw_chunk if (resident or not args.profile_mode) else 0,
                 "timing": ("host wall clock from the post of the first timed step to the completion flag of the last (worker resident across the warm-up -> timed boundary)"
-                           + ("; per rank between two host (gloo) barriers, MAX over ranks" if world > 1 else "") + "; "
-                           "roofline.achieved from a second pass of the same steps bracketed by HIP events = one whole worker launch") if resident else "host wall clock around the timed steps; HIP events on the env's stream for roofline.achieved", "sharding": f"{world} shard(s), no data-path collective; one all-gather of ep_return closes the job, timed separately (`allgather`)" if world > 1 else "1 shard",
+                           + ("; per rank between two host (gloo) barriers, MAX over ranks" if world > 1 else "")
+                           + ("; roofline.achieved from a second pass of the same steps bracketed by HIP events = one whole worker launch" if args.full else "")) if resident else
+                          "host wall clock around the timed steps; HIP events on the env's stream for roofline.achieved",
+                "sharding": f"{world} shard(s), no data-path collective; one all-gather of ep_return closes the job, timed separately (`allgather`)" if world > 1 else "1 shard",
             },
-            "roofline": {
+        }
+        if args.pilot:
+            line["config"]["workload"] += " + cnn_2d_speed_control inference in the loop (random-init weights, closed loop)"
+            line["dtype"] += " / fp16 MFMA convolutions, f32 accumulate"
+        if kernel_ms is not None:
+            # camera on: the library pipelines a call over ceil(steps/spl)+1 launches of trs_step_kernel (physics runs ahead of the
+            # raster inside and across launches); physics only: steps/spl launches of trs_physics_kernel
+            launches = ((args.steps + spl - 1) // spl + 1) if render else (args.steps + spl - 1) // spl
+            if resident:
+                launches = 1                                                # one trs_worker_kernel launch serves every posted step of the timed region
+            avg_launch_s = kernel_ms * 1e-3 / launches
+            per_launch = n * args.steps / launches                         # env-steps one launch completes
+            achieved = B * per_launch / avg_launch_s / 1e9                 # GB/s of algorithmic bytes, dominant (only) kernel
+            traffic = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            traffic_key = f"{n}x{args.img_h}x{args.img_w}" + ("+depth" if args.depth else "") + (":resident" if resident else f":spl{spl}")
+            if os.path.exists(pmc):
+                try:
+                    # scripts/summarize_profile.py writes {"per_env_step": {"<envs>x<H>x<W>[+depth]:<resident|splK>": HBM bytes per env-step}} from the
+                    # WRITE_SIZE / FETCH_SIZE passes of scripts/profile.sh (unit + gfx950 corrections of MI355X_MICROARCH.md applied); per launch = x the
+                    # env-steps one launch completes, like `achieved`
+                    with open(pmc) as f:
+                        per_step = json.load(f).get("per_env_step", {}).get(traffic_key)
+                    traffic = None if per_step is None else per_step * per_launch
+                except Exception:
+                    traffic = None
+            line["roofline"] = {
                 "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_key": traffic_key,
                 "frac_by_wall_clock": round(B * n * args.steps / wall / 1e9 / HBM_PEAK_GBS, 5),
                 "kernel": ("trs_worker_kernel" if render else "trs_physics_worker_kernel") if resident else ("trs_step_kernel" if render else "trs_physics_kernel"), "avg_launch_us": round(avg_launch_s * 1e6, 3),
                 "bytes_per_env_step": B, "env_steps_per_launch": round(per_launch, 2), "launches": launches,
-            },
-        }
+            }
         if also:
             line["also"] = also
-        if args.pilot:
+        if args.pilot and kernel_ms is not None:
             # closed loop with the CNN: the convolutions dominate (MFMA-bound class); the device time of a step spans
             # the env launch, the conv / dense launches and the tail, so the figure below is a whole-step rate, a lower bound
             # on the conv kernels' own rate
             tf = pilot_flops * n * args.steps / (kernel_ms * 1e-3) / 1e12
-            line["config"]["workload"] += " + cnn_2d_speed_control inference in the loop (random-init weights, closed loop)"
-            line["dtype"] += " / fp16 MFMA convolutions, f32 accumulate"
             line["roofline"] = {"bound": "mfma", "achieved": round(tf, 2), "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 5),
                                 "measured_ceiling": MEASURED_MFMA_TFLOPS, "frac_of_measured_ceiling": round(tf / MEASURED_MFMA_TFLOPS, 5),
                                 "traffic": None, "kernel": "per step: trs_step_kernel + trs_conv12_band_kernel (conv1 + conv2 fused) + trs_conv_frame5_kernel (conv3) + trs_conv_chain_kernel (conv4..7 in one launch) + trs_pilot_dense_kernel (dense1) + trs_pilot_tail_kernel at 120x160; frames too large for LDS: trs_conv_frame5_kernel on row bands (conv3) and one trs_conv_frame_kernel launch per 3x3 layer",
                                 "flops_per_frame": pilot_flops, "avg_step_us": round(kernel_ms * 1e3 / args.steps, 3),
                                 "note": "whole closed-loop step by HIP events; per-layer times in profiles/r04_pilot_layers.txt"}
         line["config"]["launcher"] = launcher          # "self": python bench.py --gpus N started the ranks (launch_ranks); "torch.distributed.run"; "external"
-        if resident:
+        if resident and args.full:
             # the same K steps with the worker's start-up and exit inside the clock (round 2's definition of `value`): one whole
             # trs_worker_kernel launch by HIP events — what a consumer that posts K steps and then stops sees.  `value` is the steady-state rate.
             line["value_incl_worker_launch"] = round(n * world * args.steps / avg_launch_s, 1)
@@ -915,7 +983,7 @@ def main():
         if args.share_gpu:
             line["config"]["rehearsal"] = (f"{world} ranks SHARING GPU 0 over gloo: a rehearsal of the N > 1 code path, not a measurement (resident mode selected on every rank; "
                                            "the library lets one worker at a time have the GPU: the ranks take turns of <= 50 ms or step by launches)")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(min(n, 1024), args.img_h, args.img_w) if render else None
             if cb:
                 line["cpu_baseline"] = cb

@@ -7,7 +7,7 @@ TAG=${1:-r01}; shift || true
 # the kernel-stats average over the two trs_worker_kernel dispatches is then the figure bench.py reports
 # (--profile-mode: the time-based pre-warm runs by launches (trs_step_kernel, its own row), the worker leaves after the warm-up: three dispatches of 1000 steps each — warm-up, the
 # wall-clock pass, the event-bracketed pass — so the stats table's average is a per-1000-steps figure like bench.py's avg_launch_us)
-ARGS="--steps 1000 --warmup 1000 --no-cpu-baseline --no-also --profile-mode $@"
+ARGS="--steps 1000 --warmup 1000 --full --no-cpu-baseline --no-also --profile-mode $@"
 cd "$(dirname "$0")/.."
 REPO=$PWD
 OUT=$REPO/gpurun_out/prof_$TAG

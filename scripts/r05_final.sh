@@ -4,17 +4,17 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out
 echo "[bench]"; date
-python bench.py > $O/r05f_bench_1gpu.json 2> $O/r05f_bench_1gpu.err
-python bench.py --steps 20 --warmup 5 > $O/r05f_bench_steps20.json 2>/dev/null
-python bench.py --gpus 1 --spawn --steps 20 --warmup 5 --no-also --no-cpu-baseline > $O/r05f_bench_spawn.json 2>/dev/null
-python bench.py --gpus 2 --share-gpu --steps 20 --warmup 5 > $O/r05f_bench_2ranks_rehearsal.json 2>/dev/null
+python bench.py --full > $O/r05f_bench_1gpu.json 2> $O/r05f_bench_1gpu.err
+python bench.py --full --steps 20 --warmup 5 > $O/r05f_bench_steps20.json 2>/dev/null
+python bench.py --full --gpus 1 --spawn --steps 20 --warmup 5 --no-also --no-cpu-baseline > $O/r05f_bench_spawn.json 2>/dev/null
+python bench.py --full --gpus 2 --share-gpu --steps 20 --warmup 5 > $O/r05f_bench_2ranks_rehearsal.json 2>/dev/null
 python bench.py --pilot --steps 200 --warmup 60 --no-cpu-baseline > $O/r05f_bench_pilot_1024x120x160.json 2>/dev/null
 python bench.py --pilot --steps 80 --warmup 30 --no-cpu-baseline --envs-per-gpu 512 --img-h 240 --img-w 320 --depth > $O/r05f_bench_pilot_512x240x320_depth.json 2>/dev/null
 echo "[profile of the bench command]"; date
 bash scripts/profile.sh r05f_resident > $O/r05f_profile_resident.log 2>&1
 echo "[sweep]"; date
 {
-B="python bench.py --no-cpu-baseline --no-also"
+B="python bench.py --full --no-cpu-baseline --no-also"
 for cfg in "--steps 20 --warmup 5" "" "--step-mode launch" "--envs-per-gpu 512" "--envs-per-gpu 256" "--envs-per-gpu 2048 --steps 1000" "--envs-per-gpu 4096 --steps 500" "--steps 600 --depth" "--envs-per-gpu 512 --steps 200 --img-h 240 --img-w 320 --depth" "--steps-per-launch 8 --step-mode launch" "--envs-per-gpu 256 --steps 4000 --no-render" "--envs-per-gpu 256 --steps 4000 --no-render --step-mode launch" "--envs-per-gpu 256 --steps 4000 --no-render --step-mode launch --steps-per-launch 16" "--envs-per-gpu 65536 --steps 256 --no-render --step-mode launch --steps-per-launch 16"; do
   echo "== $cfg"; timeout -k 10 120 $B $cfg 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], 'frac(events)', r['frac'], 'frac(wall)', r['frac_by_wall_clock'], 'launch_us', r['avg_launch_us'], d['config']['step_mode'])"
 done

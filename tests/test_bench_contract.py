@@ -1,9 +1,12 @@
-"""bench.py prints ONE JSON line with the driver's contract keys (plus the roofline / cpu_baseline objects)."""
+"""bench.py prints ONE JSON line with the driver's contract keys (plus, with --full, the roofline / cpu_baseline / also objects), and
+--dump-outputs writes what the timed path computed in its last step, the same on every run with the same arguments."""
+import ctypes
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -15,7 +18,7 @@ ROOFLINE = {"bound", "achieved", "peak", "unit", "frac", "traffic"}
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--envs-per-gpu", "256"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--envs-per-gpu", "256", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -54,6 +57,72 @@ def test_bench_line_has_the_contract_keys():
 
 def _json_lines(out):
     return [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+
+
+def _load_dump(d):
+    files = sorted(os.listdir(d))
+    assert files and all(f.endswith(".npy") for f in files), files
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()), {k: a.dtype.name for k, a in out.items()}
+    return out
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_lean_and_its_outputs_reproduce(tmp_path):
+    """A plain run: the headline keys, none of the --full extras, exactly --steps timed steps; --dump-outputs twice with the same arguments
+    gives the same arrays (the pre-warm is a fixed number of steps, the synthetic controls are keyed by the step count)."""
+    dumps = []
+    for tag in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5", "--envs-per-gpu", "256",
+                              "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = _json_lines(out)
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"} <= set(d)
+        assert not {"roofline", "also", "cpu_baseline", "value_incl_worker_launch"} & set(d)       # resident mode: the roofline takes a pass of its own
+        assert d["steps"] == 40 and d["warmup"] == 5 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["value"] > 1e6
+        assert abs(d["ms_per_step"] - 256 * 40 / d["value"] / 40 * 1e3) <= 1e-3 * d["ms_per_step"] + 1e-6
+        dumps.append(_load_dump(tmp_path / tag))
+    a, b = dumps
+    assert set(a) == set(b) and {"pos_x", "speed", "cte", "seg_idx", "done", "img", "img_env_idx"} <= set(a)
+    assert a["pos_x"].shape == (256,) and a["img"].shape[1:] == (120, 160, 3) and a["img"].shape[0] == a["img_env_idx"].shape[0]
+    assert a["img"].max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_dump_outputs_sizes_and_types(oracle_api, tmp_path, monkeypatch):
+    """bench.dump_outputs on the CPU oracle's env: float32 / float64 files only, frames of a seeded sample of the envs, the per-env values of a
+    seeded sample too once they outgrow their budget; the same env state gives the same files."""
+    import bench
+    from triton_racer_sim_amd.env import BatchedEnv
+    env = BatchedEnv(n_envs=40, auto_reset=True, depth=True, _api=oracle_api)
+    env.step_synthetic(12, 1)
+    monkeypatch.setattr(bench, "DUMP_FRAME_BYTES", 5 * 120 * 160 * 4 * 4)
+    bench.dump_outputs(env, str(tmp_path / "a"))
+    a = _load_dump(tmp_path / "a")
+    assert a["img"].shape == (5, 120, 160, 3) and a["depth"].shape == (5, 120, 160) and "env_idx" not in a
+    idx = a["img_env_idx"].astype(int)
+    assert np.array_equal(a["img"], env.fetch("img")[idx].astype(np.float32)) and np.array_equal(a["pos_x"], env.fetch("pos_x"))
+    assert np.array_equal(a["seg_idx"], env.fetch("seg_idx").astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_ENV_BYTES", 10 * (4 * 8 + 8 * 3))
+    bench.dump_outputs(env, str(tmp_path / "b"))
+    b = _load_dump(tmp_path / "b")
+    sel = b["env_idx"].astype(int)
+    assert sel.shape == (10,) and np.array_equal(b["speed"], env.fetch("speed")[sel]) and np.array_equal(b["img"], a["img"])
+    env.close()
+
+
+def test_prewarm_is_a_fixed_step_count():
+    """The untimed pre-warm is a number of steps fixed by the arguments (about PREWARM_S of work: ~8,400 steps of the default workload)."""
+    import bench
+    chunks, chunk = bench.prewarm_steps(1024, 120, 160, True, False)
+    assert (chunks, chunk) == bench.prewarm_steps(1024, 120, 160, True, False) and 7000 <= chunks * chunk <= 10000
+    _, macs = bench.pilot_weights(120, 160)
+    chunks, chunk = bench.prewarm_steps(1024, 120, 160, True, False, 2.0 * macs)
+    assert chunk == 50 and 300 <= chunks * chunk <= 700
 
 
 @pytest.mark.gpu
