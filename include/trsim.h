@@ -94,7 +94,10 @@ enum {
     TRS_F_CTL_STEER, /* float[n_envs]: the handle's own control arrays — what trs_step_host uploaded or the pilot of  */
     TRS_F_CTL_THR,   /*   trs_step_pilot produced last ('ai/steering', 'ai/throttle', 'ai/breaking' of KerasPilot.step, */
     TRS_F_CTL_BRK,   /*   keras_pilot.py:92-95)                                                                       */
-    TRS_F_DPITCH     /* float[n_points]: the view-pitch offset per raw track point of a track with elevation (include/trsim_spec.h, "tracks with elevation"); all zeros on a flat track */
+    TRS_F_DPITCH,    /* float[n_points]: the view-pitch offset per raw track point of a track with elevation (include/trsim_spec.h, "tracks with elevation"); all zeros on a flat track */
+    TRS_F_LENS_TABLE,   /* float[img_h][img_w][4] per pixel of the lens camera (include/trsim_spec.h, "lens camera"): F, L, depth (binary32) and the lens palette
+                           row as a uint32 bit pattern in word 3; the full frame, rebuilt from the host tables whatever the device keeps.  Only while a lens is set */
+    TRS_F_LENS_PALETTE  /* uint32[513][4] 0x00BBGGRR: the lens palette the kernels shade from (static frame filter applied).  Only while a lens is set */
 };
 
 typedef struct trs_map_info {
@@ -269,6 +272,26 @@ int trs_preprocess_host(trs_env* env, const trs_pre_config* cfg, const uint8_t* 
  * neighbourhood operator (use trs_preprocess).  cfg NULL = back to raw frames.  Takes effect from the next rendered
  * frame; survives trs_load_track. */
 int trs_set_frame_filter(trs_env* env, const trs_pre_config* cfg_or_null);
+
+/* ---- lens camera: the camera keys of the reference's gym_config that trs_config has no counterpart for ----
+ * fish_eye_x, fish_eye_y and offset_x of DEFAULT_GYM_CONFIG (components/gyminterface.py:16-45): a per-pixel ray model with two
+ * barrel strengths and a lateral camera mount, defined in include/trsim_spec.h ("lens camera"; parity with the simulator unpinned).
+ *   fish_eye_x, fish_eye_y in [0, 2] (0 = pinhole along that axis); offset_x in world units, + = right of the heading, |offset_x| <= 2.
+ * NULL or all zero selects the pinhole path: every frame then is byte for byte what a handle that never set a camera renders.
+ * Out-of-range values return TRS_ERR_ARG and leave the handle unchanged.  Flat tracks only: a lens on a track with elevation is refused
+ * (TRS_ERR_STATE), and so is trs_load_track of such a track while a lens is set; the dynamic-brightness frame filter and a lens exclude
+ * each other in either order (TRS_ERR_STATE).  trs_load_track of another flat track rebuilds the lens tables for its map.  Takes effect
+ * from the next step (a resident worker is quiesced and the next one starts with the new camera).  The image width must be a multiple of 8
+ * for a lens (the kernels store half of the mirror-symmetric per-pixel table). */
+typedef struct trs_camera {
+    uint32_t struct_size;            /* = sizeof(trs_camera), checked */
+    double   fish_eye_x, fish_eye_y; /* gym_config fish_eye_x / fish_eye_y */
+    double   offset_x;               /* gym_config offset_x, world units */
+} trs_camera;
+
+void trs_default_camera(trs_camera* cam);   /* the pinhole: all zero */
+int trs_set_camera(trs_env* env, const trs_camera* cam_or_null);
+int trs_get_camera(trs_env* env, trs_camera* out);
 
 /* Pilot-side normalisation (components/keras_pilot.py:49-55, keras_train.py:41-42): float32(img) / 255.
  * d_src NULL = latest frame; d_dst = float[n_images][H][W][3] device buffer. */

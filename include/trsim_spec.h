@@ -116,6 +116,31 @@
  *            fw = fog_f * (zd * inv_zfar_f);  colour[c][ch] = (int)((base[c][ch] * (1.0f - fw) + fog[ch] * fw) + 0.5f)
  *     pixels exactly as above with these row tables.  The depth frame is constant along a row of one frame, and now differs from env to env
  *     and from frame to frame with the slope ahead.
+ *
+ * ---- lens camera (trs_set_camera; flat tracks only; parity with the simulator UNPINNED) ----------------------------------------------
+ *   The reference's gym_config carries the donkey simulator's fish_eye_x, fish_eye_y and offset_x (gyminterface.py:16-45); the simulator is a
+ *   closed binary and the reference's cam_config send is commented out (:136-152), so this model, like everything above, is defined by this build.
+ *   kx = fish_eye_x, ky = fish_eye_y in [0, 2] (0 = pinhole); ox = offset_x in world units, + = right of the heading, |ox| <= 2.
+ *   f, pitch, cam_h, z_far and the map cell as in the flat camera paragraph.  kx = ky = ox = 0 selects the flat camera above (not this path).
+ *   per pixel (u, v), host, binary64:
+ *     xn = ((u + 0.5) - W/2) / f;  yn = (H/2 - (v + 0.5)) / f
+ *     rho2 = (((u + 0.5) - W/2)^2 + (H/2 - (v + 0.5))^2) / (H/2)^2
+ *     xr = xn * (1 + kx*rho2);  yr = yn * (1 + ky*rho2)                    (k > 0: edge rays bend outward = barrel / fish-eye)
+ *     dy = yr*cos(pitch) - sin(pitch);  dz = yr*sin(pitch) + cos(pitch)
+ *     dy >= -1e-6 -> SKY: g = clamp((H/2 - yr*f) / (H/2), 0, 1); row S(min((int)(g*256), 255)); F = L = 0, depth = (float)z_far
+ *     t = cam_h/(-dy); zd = t*dz;  zd > z_far -> FAR: row FAR; F = L = 0, depth = (float)z_far
+ *     else GROUND: F = (float)(zd/cell), L = (float)((t*xr)/cell), depth = (float)zd, row G(clamp((int)(zd/z_far*256), 0, 255))
+ *   lens palette, 513 rows of 4 class colours (host, binary64, the flat palette's rounding floor(x + 0.5)):
+ *     G(q), q < 256: fw = TRS_FOG_MAX * ((q + 0.5)/256), colour[c] = base[c]*(1 - fw) + fog*fw;  S(q): the flat sky blend at g = (q + 0.5)/256,
+ *     four equal colours;  FAR: the flat FAR colour.  A static frame filter applies to every entry, as to the flat palette.
+ *   per env and frame, binary32 (R1): (camx, camz, s, c) exactly as the flat camera (cam_fwd included);  oc = (float)(ox/cell) (host)
+ *     cx = fma(oc, c, camx);  cz = fma(oc, -s, camz)
+ *   per pixel: gx = fma(L, c, fma(F, s, cx));  gz = fma(L, -s, fma(F, c, cz));  ix = clamp((int)floor(gx), 0, GW-1), iz likewise
+ *     rgb = lens_palette[row][class(ix, iz)]  (SKY and FAR rows have four equal colours: their F = L = 0 lookup does not matter)
+ *   depth frame: depth per pixel.  The offset stays out of the table: pixels u and W-1-u have bit-identical F, depth and row and exactly negated L
+ *   (every binary64 operation sees identical or exactly negated operands), so a device may keep half of the table.
+ *   An independent numpy restatement checks the host tables (tests/test_lens_tables_cpu.py); a C restatement of the per-pixel pass checks the
+ *   frames (tests/test_lens_gpu.py).
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

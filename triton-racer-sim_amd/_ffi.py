@@ -65,7 +65,7 @@ FIELDS = {
     "img": 0, "pos_x": 1, "pos_y": 2, "pos_z": 3, "speed": 4, "cte": 5, "yaw": 6, "vel": 7,
     "seg_idx": 8, "ep_return": 9, "last_return": 10, "ep_len": 11, "done": 12,
     "map": 13, "rowtab": 14, "palette": 15, "tangent": 16, "steer_filt": 17, "stats": 18, "depth": 19, "rowdepth": 20,
-    "ctl_steer": 21, "ctl_thr": 22, "ctl_brk": 23, "dpitch": 24,
+    "ctl_steer": 21, "ctl_thr": 22, "ctl_brk": 23, "dpitch": 24, "lens_table": 25, "lens_palette": 26,
 }
 
 # every symbol include/trsim.h declares (suffix after the prefix)
@@ -79,6 +79,11 @@ SYMBOLS = [
     "comm_get_unique_id", "comm_init", "comm_destroy", "allgather_returns", "stream_wait_external", "stream_signal_external",
     "scratch", "upload", "counters",
 ]
+
+
+class TrsCamera(C.Structure):
+    """``trs_camera`` (include/trsim.h): the lens camera of ``trs_set_camera``."""
+    _fields_ = [("struct_size", C.c_uint32), ("fish_eye_x", C.c_double), ("fish_eye_y", C.c_double), ("offset_x", C.c_double)]
 
 
 class TrsMuxConfig(C.Structure):
@@ -120,9 +125,12 @@ PILOT_LAYERS = {
 PILOT_ARRAYS_OF_TYPE = {"cnn_2d_speed_control": 22, "cnn_2d": 22, "cnn_2d_speed_as_feature": 28, "cnn_2d_full_house": 42}
 
 
+# HIP library only: the lens camera (trs_set_camera) has no twin in the C oracle — its checker is the restatement of include/trsim_spec.h
+# ("lens camera") in tests/test_lens_tables_cpu.py and tests/test_lens_gpu.py, and oracle/ stays as it is
+LENS_SYMBOLS = ["default_camera", "set_camera", "get_camera"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"]
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -196,6 +204,11 @@ class Api:
             "default_pilot_tuning": (None, [C.POINTER(TrsPilotTuning)]),
             "pilot_set_tuning": (i32, [vp, C.POINTER(TrsPilotTuning)]),
         }
+        lens = {
+            "default_camera": (None, [C.POINTER(TrsCamera)]),
+            "set_camera": (i32, [vp, C.POINTER(TrsCamera)]),
+            "get_camera": (i32, [vp, C.POINTER(TrsCamera)]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -204,6 +217,12 @@ class Api:
         self.has_pilot = hasattr(cdll, prefix + "pilot_load")
         if self.has_pilot:
             for name, (res, args) in pilot.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_lens = hasattr(cdll, prefix + "set_camera")
+        if self.has_lens:
+            for name, (res, args) in lens.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -35,6 +35,14 @@ def _track_for(cfg):
     return cfg.get("track_data_file", "track_data/generated_track.json")
 
 
+def _camera_for(cfg):
+    """The lens camera of a gym_config: ``fish_eye_x``, ``fish_eye_y`` and ``offset_x`` (gyminterface.py:16-45; the reference sends
+    them as strings, :139-150, so strings are accepted).  Absent or zero keys: ``None``, the pinhole camera.  The other camera keys
+    (fov, offset_y, offset_z, rot_x, img_d, img_enc) stay ignored."""
+    vals = tuple(float(cfg.get(k, 0.0) or 0.0) for k in ("fish_eye_x", "fish_eye_y", "offset_x"))
+    return vals if any(v != 0.0 for v in vals) else None
+
+
 class HipGymInterface(Component):
     """One car (N = 1).  ``step(steering, throttle, breaking, reset) -> (img, x, y, z, speed, cte)``."""
 
@@ -49,7 +57,8 @@ class HipGymInterface(Component):
         self.latency_ticks = int(math.ceil(float(self.latency) * float(self.gym_config.get("loop_hz", 20)) / 1000.0)) if self.latency else 0
         self._delay = collections.deque()
         self.env = BatchedEnv(n_envs=1, track=_track_for(self.gym_config), device=self.gym_config.get("hip_device", 0),
-                              img_h=int(self.gym_config["img_h"]), img_w=int(self.gym_config["img_w"]), render=True, _api=_api)
+                              img_h=int(self.gym_config["img_h"]), img_w=int(self.gym_config["img_w"]), render=True,
+                              camera=_camera_for(self.gym_config), _api=_api)
         if self.gym_config.get("hip_resident"):
             self.env.set_step_mode(True, idle_us=int(self.gym_config.get("hip_resident_idle_us", 0)))
         self.last_image = None
@@ -101,7 +110,7 @@ class BatchedGymInterface(Component):
         self.sync = sync
         self.env = BatchedEnv(n_envs=n_envs, track=_track_for(self.gym_config), device=self.gym_config.get("hip_device", 0),
                               img_h=int(self.gym_config["img_h"]), img_w=int(self.gym_config["img_w"]), render=True,
-                              auto_reset=auto_reset, env_id_base=env_id_base, _api=_api)
+                              auto_reset=auto_reset, env_id_base=env_id_base, camera=_camera_for(self.gym_config), _api=_api)
 
     def step(self, *args):
         steering, throttle, breaking, reset = args

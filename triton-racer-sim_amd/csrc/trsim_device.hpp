@@ -72,6 +72,22 @@ struct RParams {                        // raster side of the step kernel
 };
 __host__ __device__ inline size_t hill_block_offset(int blob_bytes) { return ((size_t)blob_bytes + 63) & ~(size_t)63; }
 
+// What the LENS instantiations need (include/trsim_spec.h, "lens camera"): like HillBlock it lives in device memory behind the raster image, so the
+// flat kernels' arguments stay as they are.  The per-pixel table is stored for the RIGHT half of the frame only (u = W/2 + k, k in [0, W/2)): F, depth
+// and the palette row are even in u - W/2 and L is odd, so pixel W-1-u reads entry k with L negated.  Planes of [H][W/2], so that the 4 pixels of a
+// thread's column group are one 16-B load per plane (8 B for the rows).
+struct LensBlock {
+    const float* F;                     // [H][W/2] forward distance, cell units
+    const float* L;                     // [H][W/2] lateral distance, cell units (right half: + = right)
+    const float* D;                     // [H][W/2] z-depth (z_far for sky and far pixels)
+    const uint16_t* M;                  // [H][W/2] lens palette row: 0..255 ground G(q), 256..511 sky S(q), 512 FAR
+    const uint32_t* pal;                // [513][4] the lens palette (static frame filter applied), staged into LDS by the kernels
+    float oc;                           // (float)(offset_x / cell): the lateral mount, cell units
+    int wh;                             // W/2
+};
+__host__ __device__ inline size_t lens_block_offset(int blob_bytes) { return hill_block_offset(blob_bytes) + ((sizeof(HillBlock) + 63) & ~(size_t)63); }
+constexpr int kLensPalBytes = 513 * 16;
+
 struct FParams {                        // ImgPreprocessing with dynamic brightness, evaluated inside the step kernels (their DYN instantiations)
     double baseline;
     float contrast, offset;
@@ -781,6 +797,113 @@ __device__ __forceinline__ void raster_hill_frame(const RParams& p, const Raster
     raster_ground_rows<DEPTH, true>(p, t, f, cam);
 }
 
+// ---- the lens camera (include/trsim_spec.h, "lens camera") ------------------------------------------------------------------------------------
+// One env's whole frame.  The thread keeps its column group and rows (raster_thread); per row it needs the 4 table entries of its group from the
+// half-width planes (F, L and depth as 16 B, the palette rows as 8 B; the left half reads its mirror group reversed and negates L).  The table is the
+// same for every env, so the entries of a thread's first kLensRegRows rows are loaded into registers ONCE per kernel (lens_cache_load, in front of
+// the first frame) and every env's frame reuses them: no table traffic and no load behind the frame stores for them (loads count in vmcnt in issue
+// order with the stores, so a load between stores waits for their acknowledgements).  Rows beyond those (frames taller than the cache: 240x320)
+// are read from L2 per frame, the next row's entries before this row's store.  The camera is moved by the lateral mount once per frame, and every
+// pixel is shaded from the lens palette in LDS at `pal_off`: sky and far rows have four equal colours, so every pixel takes the same path (a map
+// lookup at F = L = 0 for them is harmless).
+template <bool DEPTH, int NR>
+struct LensCache {
+    static constexpr int R = NR;                                      // as many rows as fit the 168 VGPRs of 12 waves without a spill (tests/test_build_lint.py)
+    float4 F[R], L[R], D[DEPTH ? R : 1];
+    uint2 M[R];
+};
+template <bool DEPTH> using LensCacheStep = LensCache<DEPTH, DEPTH ? 3 : 8>;     // trs_step_kernel
+template <bool DEPTH> using LensCacheWorker = LensCache<DEPTH, DEPTH ? 3 : 4>;   // trs_worker_kernel (more state stays live across its loop)
+
+__device__ __forceinline__ int lens_col(const RParams& p, const RasterThread& t, bool& right)
+{
+    const int hg = p.gpr >> 1;
+    right = t.cg >= hg;
+    return (right ? t.cg - hg : hg - 1 - t.cg) << 2;
+}
+
+template <bool DEPTH, int NR>
+__device__ __forceinline__ void lens_cache_load(const RParams& p, const RasterThread& t, const trsim::LensBlock& lb, LensCache<DEPTH, NR>& k)
+{
+    bool right;
+    const size_t col = (size_t)lens_col(p, t, right);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const int v = t.vstart + i * p.rows_per_pass;
+        const size_t o = (size_t)(v < p.H ? v : 0) * lb.wh + col;
+        k.F[i] = *reinterpret_cast<const float4*>(lb.F + o);
+        k.L[i] = *reinterpret_cast<const float4*>(lb.L + o);
+        k.M[i] = *reinterpret_cast<const uint2*>(lb.M + o);
+        if constexpr (DEPTH) k.D[i] = *reinterpret_cast<const float4*>(lb.D + o);
+    }
+}
+
+template <bool DEPTH, int NR>
+__device__ __forceinline__ void raster_lens_frame(const RParams& p, const RasterThread& t, const trsim::LensBlock& lb, const LensCache<DEPTH, NR>& k, unsigned pal_off,
+                                                  const FrameDesc& f, const float4 cam)
+{
+    const float s = cam.z, c = cam.w, ns = -cam.z;
+    const float cx = __builtin_fmaf(lb.oc, c, cam.x), cz = __builtin_fmaf(lb.oc, ns, cam.y);
+    bool right;
+    const size_t col = (size_t)lens_col(p, t, right);
+    auto row = [&](int v, const float4 F4, const float4 L4, const uint2 M2, const float4 D4) {
+        // entries in pixel order of this group (the left half: mirrored, L negated)
+        float fe[4] = {F4.x, F4.y, F4.z, F4.w}, le[4] = {L4.x, L4.y, L4.z, L4.w};
+        unsigned me[4] = {M2.x & 0xFFFFu, M2.x >> 16, M2.y & 0xFFFFu, M2.y >> 16};
+        if (!right) {
+            float tf, tl; unsigned tm;
+            tf = fe[0]; fe[0] = fe[3]; fe[3] = tf; tf = fe[1]; fe[1] = fe[2]; fe[2] = tf;
+            tl = le[0]; le[0] = -le[3]; le[3] = -tl; tl = le[1]; le[1] = -le[2]; le[2] = -tl;
+            tm = me[0]; me[0] = me[3]; me[3] = tm; tm = me[1]; me[1] = me[2]; me[2] = tm;
+        }
+        uint32_t col4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float gx = __builtin_fmaf(le[i], c, __builtin_fmaf(fe[i], s, cx));
+            const float gz = __builtin_fmaf(le[i], ns, __builtin_fmaf(fe[i], c, cz));
+            const unsigned ix = min(cvt_u32_sat(gx), t.gwm1);
+            const unsigned iz = min(cvt_u32_sat(gz), t.ghm1);
+            const unsigned xoff = (ix >> 2) & ~3u;
+            unsigned waddr;
+            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(waddr) : "v"(iz), "s"(t.pitch), "v"(xoff));
+            const uint32_t w = *(lds_u32p)(uintptr_t)waddr;                 // map lives at LDS offset 0 (checked by the kernels)
+            const uint32_t cls = __builtin_amdgcn_ubfe(w, ix << 1, 2);
+            col4[i] = *(lds_u32p)(uintptr_t)(pal_off + (me[i] << 4) + (cls << 2));
+        }
+        const u3v px3 = {__builtin_amdgcn_perm(col4[1], col4[0], 0x04020100u), __builtin_amdgcn_perm(col4[2], col4[1], 0x05040201u),
+                         __builtin_amdgcn_perm(col4[3], col4[2], 0x06050402u)};
+        __builtin_amdgcn_raw_buffer_store_b96(px3, f.rgb, t.col_off + v * t.row_bytes, 0, TRS_STORE_AUX);
+        if constexpr (DEPTH) {
+            const u4v d4 = right ? u4v{__float_as_uint(D4.x), __float_as_uint(D4.y), __float_as_uint(D4.z), __float_as_uint(D4.w)}
+                                 : u4v{__float_as_uint(D4.w), __float_as_uint(D4.z), __float_as_uint(D4.y), __float_as_uint(D4.x)};
+            __builtin_amdgcn_raw_buffer_store_b128(d4, f.dep, (t.cg + v * p.gpr) * 16, 0, TRS_STORE_AUX);
+        }
+    };
+    constexpr int R = NR;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const int v = t.vstart + i * p.rows_per_pass;
+        if (v < p.H) row(v, k.F[i], k.L[i], k.M[i], DEPTH ? k.D[DEPTH ? i : 0] : k.F[i]);
+    }
+    const int vt = t.vstart + R * p.rows_per_pass;                    // rows beyond the cache: from L2, one row ahead
+    if (vt >= p.H) return;
+    auto ldF = [&](int v) { return *reinterpret_cast<const float4*>(lb.F + (size_t)v * lb.wh + col); };
+    auto ldL = [&](int v) { return *reinterpret_cast<const float4*>(lb.L + (size_t)v * lb.wh + col); };
+    auto ldM = [&](int v) { return *reinterpret_cast<const uint2*>(lb.M + (size_t)v * lb.wh + col); };
+    auto ldD = [&](int v) { return *reinterpret_cast<const float4*>(lb.D + (size_t)v * lb.wh + col); };
+    float4 Fn = ldF(vt), Ln = ldL(vt), Dn = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint2 Mn = ldM(vt);
+    if constexpr (DEPTH) Dn = ldD(vt);
+    for (int v = vt; v < p.H; v += p.rows_per_pass) {
+        const float4 F4 = Fn, L4 = Ln, D4 = Dn;
+        const uint2 M2 = Mn;
+        const int vn = v + p.rows_per_pass < p.H ? v + p.rows_per_pass : v;
+        Fn = ldF(vn); Ln = ldL(vn); Mn = ldM(vn);
+        if constexpr (DEPTH) Dn = ldD(vn);
+        row(v, F4, L4, M2, D4);
+    }
+}
+
 // The colour masks of one pixel (img_preprocessing.py:57-74; OpenCV's 8-bit RGB -> HSV with its fixed-point reciprocal tables, then inRange).
 // P = the TRIMMED pixel, bytes (r, g, b, x).  rngb[c * 256 + x] (range_byte_entry) has byte ch = 0xFF when value x of component c (h, s, v) lies
 // inside the range of the filter whose mask goes to channel ch, so the AND of three lookups is the pixel's masks in place; sel has 0xFF in the
@@ -1151,6 +1274,13 @@ __device__ __forceinline__ void stage_lds_dma(const unsigned char* blob, int byt
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + g),
                                              (__attribute__((address_space(3))) void*)(uintptr_t)(lds_byte_addr + g0 * 16), 16, 0, 0);
     }
+}
+
+// the lens palette global -> LDS (raster team, in front of the prologue's barrier)
+__device__ __forceinline__ void lens_stage_palette(const RParams& p, unsigned lds_off, int wave, int lane)
+{
+    const trsim::LensBlock* lb = reinterpret_cast<const trsim::LensBlock*>(p.blob + trsim::lens_block_offset(p.blob_bytes));
+    stage_lds_dma(reinterpret_cast<const unsigned char*>(lb->pal), trsim::kLensPalBytes, lds_off, wave, kRasterThreads / 64, lane);
 }
 
 }  // namespace

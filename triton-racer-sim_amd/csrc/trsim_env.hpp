@@ -31,6 +31,13 @@ struct trs_env {
     float* dpitch = nullptr;             // [n_points] view pitch per raw track point (device: (float)pitch + dpitch[i])
     bool hilly = false;                       // the loaded track has elevation (include/trsim_spec.h): the HILLS instantiations of the step kernels run
     trsim::HillBlock hill_host{};             // host copy of the block behind the raster image (trs_load_track fills the camera part, upload_palette the frame filter)
+    // the lens camera (trs_set_camera; include/trsim_spec.h, "lens camera"): the LENS instantiations of the step kernels run while lens_on
+    trs_camera camera{};                      // what trs_set_camera set (all zero: the pinhole)
+    bool lens_on = false;
+    trsim::LensTables lens;                   // host tables of the loaded map (full frame), built by lens_build
+    unsigned char* lens_dev = nullptr;        // device: half-width planes F | L | D | M, then the lens palette (LensBlock points into it)
+    size_t lens_pal_off = 0;                  // byte offset of the palette in lens_dev
+    int max_steps_lens = 1;                   // steps per launch that fit beside the lens palette in LDS
     unsigned long long* stats = nullptr;
     double* loc_q = nullptr; int32_t* loc_out = nullptr; int loc_cap = 0;
     uint8_t* pre = nullptr;              // processed frames of the env (trs_preprocess with d_dst == NULL)

@@ -113,8 +113,8 @@ __global__ __launch_bounds__(kPhysBlock) void trs_physics_kernel(const PParams p
 }
 
 
-template <bool DEPTH, bool DYN, bool HILLS = false>      // HILLS: a track with elevation (its own instantiations: the flat kernels' loops do not change for it)
-__global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)
+template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false>      // HILLS: a track with elevation (its own instantiations: the flat kernels' loops do not change for it);
+__global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)           // LENS: the lens camera on a flat track (likewise)
 {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -164,6 +164,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)
         } else if (sp.n_phys > 0) {
             stage_lds_dma(sp.ph.blob, sp.ph.blob_bytes, (unsigned)sp.lds_off_phys, pw, kPhysWaves, lane);
         }
+        if (LENS && raster_team && rendering) lens_stage_palette(p, (unsigned)lds_off_hill, wave, lane);   // the lens palette sits where a hilly track keeps its row tables
         if (has_c) lcam_prev[tid] = cv;
         if (raster_team && rendering && sp.r_first < 0)
             for (int j = tid + kRasterThreads; j < e_end - e_begin; j += kRasterThreads) lcam_prev[j] = cam_prev[e_begin + j];
@@ -231,6 +232,12 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)
     [[maybe_unused]] const int cg = rth.cg, vstart = rth.vstart, col_off = rth.col_off;
     [[maybe_unused]] const f2v ufa = rth.ufa, ufb = rth.ufb, ufc = rth.ufc, ufd = rth.ufd;
     [[maybe_unused]] const size_t row_bytes = (size_t)rth.row_bytes;
+    trsim::LensBlock lb{};
+    LensCacheStep<DEPTH> lcache;
+    if constexpr (LENS) {
+        lb = *reinterpret_cast<const trsim::LensBlock*>(p.blob + trsim::lens_block_offset(p.blob_bytes));   // (uniform address: scalar loads)
+        lens_cache_load(p, rth, lb, lcache);                   // this thread's table entries, once for every frame of the kernel
+    }
     for (int sidx = sp.r_first; sidx <= sp.r_last; ++sidx) {
     const unsigned abs_step = sp.step_base + (unsigned)sidx;                  // sidx = -1: the step before this launch
     uint8_t* const img = (abs_step & 1u) ? sp.img1 : sp.img0;
@@ -267,6 +274,18 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)
             for (int bi = 0; bi < kHillBatchMax; ++bi)
                 if (bi < nb)
                     raster_hill_frame<DEPTH>(p, rth, smem, (unsigned)lds_off_hill, bi, hbar, it * 2 * (kRasterThreads / 64), frame_desc<DEPTH>(p, img, dep, e + bi), cams[bi]);
+            continue;
+        }
+        if constexpr (LENS) {
+            // ---- the lens camera: every row of the frame from the per-pixel table (no uniform rows: sky and far pixels follow the lens per pixel)
+            float4 cam;
+            const int j = e - e_begin;
+            if (sidx < 0) cam = lcam_prev[j];
+            else {
+                while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
+                cam = lcam[sidx * sp.cam_stride + j];
+            }
+            raster_lens_frame(p, rth, lb, lcache, (unsigned)lds_off_hill, frame_desc<DEPTH>(p, img, dep, e), cam);
             continue;
         }
         if constexpr (DYN) {
@@ -1030,10 +1049,10 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.lds_off_cam = e->lds_step;                                                   // ring + counters sit behind the tables
     sp.lds_off_prog = sp.lds_off_cam + (std::max(n_phys, 1) + 1) * sp.cam_stride * 16;   // + one row: poses of the step before the launch
     int lds = sp.lds_off_prog + sp.cam_stride * 4 + 16;                            // + spare counters
-    if (e->hilly) {                                                                 // a track with elevation: view pitches behind the counters, the batch's row tables, a counter
+    if (e->hilly || e->lens_on) {                                                   // a track with elevation: view pitches behind the counters, the batch's row tables, a counter
         const int off_pitch = lds;                                                  // (= lds_off_prog + cam_stride * 4 + 16: the HILLS kernels compute the same offsets)
         const int off_hill = (off_pitch + (std::max(n_phys, 1) + 1) * sp.cam_stride * 4 + 15) & ~15;
-        lds = off_hill + hill_lds_bytes(e->H);
+        lds = off_hill + (e->hilly ? hill_lds_bytes(e->H) : trsim::kLensPalBytes);   // (the lens camera: its palette at the same offset)
     }
     const bool dyn = e->has_frame_filter && e->filter_dynamic;
     // Which frame buffers hold the CURRENT palette's uniform rows for every env (e->uniform_ok[b]): a launch that renders whole frames into a buffer makes it
@@ -1041,8 +1060,8 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.skip_uniform = 0;
     for (int r = r_first; r <= r_last; ++r) {
         const int b = (int)((step_base + (uint64_t)(int64_t)r) & 1u);
-        if (keep_uniform && r_first == r_last && e->uniform_ok[b] && !dyn) sp.skip_uniform = 1;
-        else e->uniform_ok[b] = !dyn;
+        if (keep_uniform && r_first == r_last && e->uniform_ok[b] && !dyn && !e->lens_on) sp.skip_uniform = 1;
+        else e->uniform_ok[b] = !dyn && !e->lens_on;                              // (the lens camera writes whole frames: no uniform rows)
     }
     std::memset(&sp.fp, 0, sizeof sp.fp);
     if (dyn) {
@@ -1063,6 +1082,9 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     if (e->hilly) {                                         // a track with elevation (its own instantiations; the dynamic-brightness filter is refused there)
         if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, true>), grid, block, lds, e->sP, sp);
         else hipLaunchKernelGGL((trs_step_kernel<false, false, true>), grid, block, lds, e->sP, sp);
+    } else if (e->lens_on) {                                // the lens camera (flat tracks; the dynamic-brightness filter is refused with it)
+        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, false, true>), grid, block, lds, e->sP, sp);
+        else hipLaunchKernelGGL((trs_step_kernel<false, false, false, true>), grid, block, lds, e->sP, sp);
     } else if (dyn) {
         if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, true>), grid, block, lds, e->sP, sp);
         else hipLaunchKernelGGL((trs_step_kernel<false, true>), grid, block, lds, e->sP, sp);
@@ -1085,7 +1107,7 @@ int run_camera_steps(trs_env* e, const float* st, const float* th, const float* 
 {
     const uint64_t s0 = e->step_count;
     const bool dyn_filter = e->has_frame_filter && e->filter_dynamic;
-    const int kmax = std::max(1, std::min(per_launch, dyn_filter ? e->max_steps_dyn : e->max_steps_per_launch));
+    const int kmax = std::max(1, std::min(per_launch, dyn_filter ? e->max_steps_dyn : (e->lens_on ? e->max_steps_lens : e->max_steps_per_launch)));
     int rc = TRS_OK;
     if (n == 1) {
         rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0, keep_uniform);
@@ -1249,7 +1271,7 @@ TRS_EXPORT int trs_destroy(trs_env* e)
     if (e->pilot) { trs_pilot_free(e->pilot); e->pilot = nullptr; }
     (void)hipFree(e->slab); (void)hipFree(e->img[0]); (void)hipFree(e->img[1]); (void)hipFree(e->depth[0]); (void)hipFree(e->depth[1]); (void)hipFree(e->blob_p); (void)hipFree(e->blob_r);
     (void)hipFree(e->tangent); (void)hipFree(e->start_yaw); (void)hipFree(e->cam); (void)hipFree(e->cam_pitch); (void)hipFree(e->dpitch);
-    (void)hipFree(e->stats); (void)hipFree(e->loc_q); (void)hipFree(e->loc_out);
+    (void)hipFree(e->stats); (void)hipFree(e->loc_q); (void)hipFree(e->loc_out); (void)hipFree(e->lens_dev);
     (void)hipFree(e->mux_state); (void)hipFree(e->edge_scratch); (void)hipFree(e->seq_buf); (void)hipFree(e->glue);
     for (void* sc : e->scratch) (void)hipFree(sc);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -1261,7 +1283,16 @@ TRS_EXPORT int trs_destroy(trs_env* e)
     return TRS_OK;
 }
 
-namespace { int upload_palette(trs_env* e); }
+namespace {
+int upload_palette(trs_env* e);
+struct LensStage {                                           // lens tables built for a map but not yet the handle's (lens_stage / lens_commit)
+    unsigned char* dev = nullptr; size_t pal_off = 0; int nmax = 0; trsim::LensTables T; bool block_written = false;
+    ~LensStage() { (void)hipFree(dev); }
+};
+int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S);
+void lens_commit(trs_env* e, LensStage& S);
+void lens_release(trs_env* e);
+}
 
 TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
 {
@@ -1276,6 +1307,8 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     trsim::TrackTables T;
     int rc = trsim::build_tables(e->cfg, h_xyz, n_points, T, err);
     if (rc) return fail(rc, err);
+    if (e->lens_on && T.hills)
+        return fail(TRS_ERR_STATE, "this track has elevation and a lens camera is set: the lens camera is built for flat tracks only (trs_set_camera(NULL) first); the handle keeps its track");
     PParams k = e->pp;
     RParams r = e->rp;
     struct Staged {                                          // device buffers of the new track; freed unless committed
@@ -1342,7 +1375,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     if (T.hills) std::memcpy(hr.data() + off_sky, T.sky.data(), (size_t)e->H * 4);
 
     HIPCHK(hipMalloc((void**)&nb.blob_p, off));
-    HIPCHK(hipMalloc((void**)&nb.blob_r, trsim::hill_block_offset((int)roff) + sizeof(trsim::HillBlock)));   // (+ the constants of a track with elevation, behind the image)
+    HIPCHK(hipMalloc((void**)&nb.blob_r, trsim::lens_block_offset((int)roff) + sizeof(trsim::LensBlock)));   // (+ the constants of a track with elevation and of the lens camera, behind the image)
     HIPCHK(hipMalloc((void**)&nb.tangent, (size_t)n_points * 8));
     HIPCHK(hipMalloc((void**)&nb.start_yaw, (size_t)n_points * 4));
     HIPCHK(hipMemcpy(nb.blob_p, hp.data(), off, hipMemcpyHostToDevice));
@@ -1377,10 +1410,20 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifndef TRS_SINGLE_VARIANT
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #endif
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_locate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k.blob_bytes));
+    // the lens camera, when one is set: its tables for the new map (its cell size) and its LensBlock behind the NEW raster image, before anything is committed —
+    // a track that leaves no LDS for the lens palette is refused like any other, and the handle keeps its track and its lens
+    LensStage ls;
+    {
+        trsim::LensBlock none{};                             // (the slot is never read while no lens is set; defined contents all the same)
+        HIPCHK(hipMemcpy(nb.blob_r + trsim::lens_block_offset(r.blob_bytes), &none, sizeof none, hipMemcpyHostToDevice));
+    }
+    if (e->lens_on) { int rl = lens_stage(e, e->camera, n_lds_step, T.info.cell, nb.blob_r, r.blob_bytes, ls); if (rl) return rl; }
     // ---- commit: nothing above has touched the handle ----
     e->track_loaded = false;                                 // (until the state arrays below are in place)
     (void)hipFree(e->blob_p); (void)hipFree(e->blob_r); (void)hipFree(e->tangent); (void)hipFree(e->start_yaw); (void)hipFree(e->dpitch);
@@ -1394,6 +1437,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
         HIPCHK(hipMemcpy(e->blob_r + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     }
     nb = Staged{};
+    if (e->lens_on) lens_commit(e, ls);
     e->tab = std::move(T);
     e->pp = k; e->rp = r;
     e->lds_r = n_lds_r; e->lds_p = n_lds_p; e->lds_step = n_lds_step; e->lds_off_phys = n_lds_off_phys; e->pts_bytes = n_pts_bytes;
@@ -1603,6 +1647,8 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     case TRS_F_PALETTE: if (e->track_loaded) { src = e->blob_r + e->rp.off_pal; need = (size_t)e->H * 16; } break;
     case TRS_F_TANGENT: if (e->track_loaded) { src = e->tangent; need = (size_t)k.np * 8; } break;
     case TRS_F_DPITCH: if (e->track_loaded) { src = e->tab.dpitch.data(); need = e->tab.dpitch.size() * 4; host_src = true; } break;
+    case TRS_F_LENS_TABLE: if (e->track_loaded && e->lens_on) { src = e->lens.pix.data(); need = e->lens.pix.size() * 4; host_src = true; } break;
+    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->lens_on && e->lens_dev) { src = e->lens_dev + e->lens_pal_off; need = (size_t)trsim::kLensPalBytes; } break;
     default: return fail(TRS_ERR_ARG, "unknown field");
     }
     if (!src) return fail(TRS_ERR_STATE, "field not available");
@@ -1818,10 +1864,16 @@ int upload_palette(trs_env* e)
     std::vector<uint32_t> pal(e->tab.palette);
     if (e->has_frame_filter && !e->filter_dynamic)             // dynamic brightness: the kernel filters a per-env palette itself
         for (auto& c : pal) c = filter_colour(e->frame_filter, c);
-    e->rp.uni_rows = e->hilly ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame)
-    e->uniform_ok[0] = e->uniform_ok[1] = false;               // (the closed pilot loop's steps skip rows an earlier step wrote: not across a palette change)
+    e->rp.uni_rows = (e->hilly || e->lens_on) ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame;
+    e->uniform_ok[0] = e->uniform_ok[1] = false;               //  the lens camera: on the pixel)  (the closed pilot loop's steps skip rows an earlier step wrote: not across a palette change)
     { int rq = sync_all(e); if (rq) return rq; }               // frames in flight keep the palette they were launched with
     HIPCHK(hipMemcpy(e->blob_r + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
+    if (e->lens_on && e->lens_dev) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
+        std::vector<uint32_t> lp(e->lens.palette);
+        if (e->has_frame_filter && !e->filter_dynamic)
+            for (auto& c : lp) c = filter_colour(e->frame_filter, c);
+        HIPCHK(hipMemcpy(e->lens_dev + e->lens_pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+    }
     if (e->hilly) {
         // a track with elevation: the kernels blend a row's ground colours per env and frame and run the static filter on each (hill_filter_colour); the sky colours and
         // the far colour are constants: filtered here
@@ -1847,6 +1899,73 @@ int upload_palette(trs_env* e)
         HIPCHK(hipMemcpy(e->blob_r + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     }
     return TRS_OK;
+}
+
+// The lens tables of a map for a camera (include/trsim_spec.h, "lens camera"), STAGED: host tables in binary64, the half-width planes and the palette
+// (static frame filter applied) in a device buffer of their own, and the LensBlock written into the raster image `blob_r` (the new track's, not yet committed,
+// in trs_load_track; the handle's own, with nothing in flight, in trs_set_camera).  Nothing of the handle changes here: lens_commit takes the result.
+// `lds_step` / `cell`: the step kernel's LDS image and the map cell of the track the tables are for.
+int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S)
+{
+    const int epw = e->pp.envs_per_wg;
+    // launch_step's layout with the lens palette where a hilly track keeps its row tables: lds_step + (n + 1) * epw * (16 + 4) + epw * 4 + 16 (+ 15 alignment) + the palette
+    const int room = 160 * 1024 - lds_step - epw * 4 - 16 - 15 - trsim::kLensPalBytes;
+    const int nmax = std::min(16, room / (epw * 20) - 1);
+    if (nmax < 1)
+        return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lens camera's palette (" + std::to_string(lds_step) + " B of tables at " +
+                                   std::to_string(epw) + " envs per workgroup): the lens camera needs a shorter track or fewer envs per GPU");
+    std::string err;
+    int rc = trsim::build_lens_tables(e->cfg, cell, cam.fish_eye_x, cam.fish_eye_y, S.T, err);
+    if (rc) return fail(rc, err);
+    const trsim::LensTables& T = S.T;
+    const int H = e->H, W = e->W, wh = W / 2;
+    const size_t plane = align_up((size_t)H * wh * 4, 256), mplane = align_up((size_t)H * wh * 2, 256);
+    const size_t off_L = plane, off_D = 2 * plane, off_M = 3 * plane, off_pal = 3 * plane + mplane;
+    const size_t bytes = off_pal + (size_t)trsim::kLensPalBytes;
+    std::vector<unsigned char> h(bytes, 0);
+    for (int v = 0; v < H; ++v)
+        for (int k = 0; k < wh; ++k) {
+            const float* px = &T.pix[((size_t)v * W + wh + k) * 4];
+            const size_t i = (size_t)v * wh + k;
+            uint32_t row;
+            std::memcpy(&row, &px[3], 4);
+            const uint16_t m = (uint16_t)row;
+            std::memcpy(h.data() + i * 4, &px[0], 4);
+            std::memcpy(h.data() + off_L + i * 4, &px[1], 4);
+            std::memcpy(h.data() + off_D + i * 4, &px[2], 4);
+            std::memcpy(h.data() + off_M + i * 2, &m, 2);
+        }
+    std::vector<uint32_t> lp(T.palette);
+    if (e->has_frame_filter && !e->filter_dynamic)
+        for (auto& c : lp) c = filter_colour(e->frame_filter, c);
+    std::memcpy(h.data() + off_pal, lp.data(), lp.size() * 4);
+    HIPCHK(hipMalloc((void**)&S.dev, bytes));
+    HIPCHK(hipMemcpy(S.dev, h.data(), bytes, hipMemcpyHostToDevice));
+    trsim::LensBlock lb{};
+    unsigned char* const d = S.dev;
+    lb.F = reinterpret_cast<const float*>(d); lb.L = reinterpret_cast<const float*>(d + off_L); lb.D = reinterpret_cast<const float*>(d + off_D);
+    lb.M = reinterpret_cast<const uint16_t*>(d + off_M); lb.pal = reinterpret_cast<const uint32_t*>(d + off_pal);
+    lb.oc = (float)(cam.offset_x / cell);
+    lb.wh = wh;
+    S.block_written = true;                                  // (from here on the slot in blob_r may hold a partial block when the copy fails)
+    HIPCHK(hipMemcpy(blob_r + trsim::lens_block_offset(blob_bytes), &lb, sizeof lb, hipMemcpyHostToDevice));
+    S.pal_off = off_pal; S.nmax = nmax;
+    return TRS_OK;
+}
+
+// the staged lens tables become the handle's (the old ones are freed)
+void lens_commit(trs_env* e, LensStage& S)
+{
+    (void)hipFree(e->lens_dev);
+    e->lens_dev = S.dev; S.dev = nullptr;
+    e->lens_pal_off = S.pal_off; e->lens = std::move(S.T); e->max_steps_lens = S.nmax;
+}
+
+// back to the pinhole camera: the lens tables are freed (nothing may be in flight)
+void lens_release(trs_env* e)
+{
+    (void)hipFree(e->lens_dev);
+    e->lens_dev = nullptr; e->lens_pal_off = 0; e->lens = trsim::LensTables{}; e->max_steps_lens = 1;
 }
 
 int ensure_tmp(trs_env* e, size_t frames)
@@ -1904,6 +2023,9 @@ TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
         if (c->dynamic_brightness && e->track_loaded && e->hilly)
             return fail(TRS_ERR_STATE, "the loaded track has elevation: a frame's palette is evaluated per env inside the kernels there, and the dynamic-brightness filter behind the "
                                        "rasteriser is not built for that; the static filter works, or use trs_preprocess on the rendered frames");
+        if (c->dynamic_brightness && e->lens_on)
+            return fail(TRS_ERR_STATE, "a lens camera is set: the dynamic-brightness filter behind the rasteriser is not built for the lens camera (trs_set_camera(NULL) first); "
+                                       "the static filter works, or use trs_preprocess on the rendered frames");
         if (c->dynamic_brightness) {
             const int rpp = kRasterThreads / (e->W / 4);
             if (rpp < 1 || (79 + rpp - 1) / rpp > 16) return fail(TRS_ERR_LIMIT, "image too wide for the in-kernel dynamic-brightness filter (class bits of the brightness rows live in 4 registers), use trs_preprocess");
@@ -1921,6 +2043,65 @@ TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
     }
     HIPCHK(hipSetDevice(e->device));
     return upload_palette(e);
+}
+
+TRS_EXPORT void trs_default_camera(trs_camera* c)
+{
+    if (!c) return;
+    std::memset(c, 0, sizeof *c);
+    c->struct_size = (uint32_t)sizeof *c;
+}
+
+TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    trs_camera nc;
+    trs_default_camera(&nc);
+    if (c) {
+        if (c->struct_size != sizeof(trs_camera)) return fail(TRS_ERR_ARG, "trs_camera.struct_size mismatch");
+        if (!(c->fish_eye_x >= 0.0 && c->fish_eye_x <= 2.0)) return fail(TRS_ERR_ARG, "fish_eye_x must lie in [0, 2]");
+        if (!(c->fish_eye_y >= 0.0 && c->fish_eye_y <= 2.0)) return fail(TRS_ERR_ARG, "fish_eye_y must lie in [0, 2]");
+        if (!(c->offset_x >= -2.0 && c->offset_x <= 2.0)) return fail(TRS_ERR_ARG, "offset_x must lie in [-2, 2] world units");
+        nc.fish_eye_x = c->fish_eye_x; nc.fish_eye_y = c->fish_eye_y; nc.offset_x = c->offset_x;
+    }
+    const bool on = nc.fish_eye_x != 0.0 || nc.fish_eye_y != 0.0 || nc.offset_x != 0.0;
+    if (on) {
+        if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
+        if (e->W % 8) return fail(TRS_ERR_LIMIT, "the lens camera needs an image width that is a multiple of 8 (the kernels store half of the mirror-symmetric table)");
+        if (e->track_loaded && e->hilly)
+            return fail(TRS_ERR_STATE, "the loaded track has elevation: the lens camera is built for flat tracks only (the ground plane of a hilly track tilts per env and frame)");
+        if (e->has_frame_filter && e->filter_dynamic)
+            return fail(TRS_ERR_STATE, "the dynamic-brightness frame filter is set: it is not built for the lens camera (trs_set_frame_filter without dynamic brightness, or NULL, first)");
+    }
+    HIPCHK(hipSetDevice(e->device));
+    // nothing may be in flight, and a resident worker leaves, BEFORE anything of the camera changes (the worker's quiesce can still launch for steps
+    // posted earlier: they run with the camera they were posted under)
+    { int rq = sync_all(e); if (rq) return rq; }
+    if (on && e->track_loaded) {
+        LensStage ls;
+        int rc = lens_stage(e, nc, e->lds_step, e->tab.info.cell, e->blob_r, e->rp.blob_bytes, ls);
+        if (rc) {
+            if (e->lens_on && ls.block_written) {            // the copy of the block failed: the handle's LensBlock may be half written, the old lens cannot stay
+                const std::string why = g_err;
+                lens_release(e); e->lens_on = false; trs_default_camera(&e->camera);
+                (void)upload_palette(e);
+                return fail(rc, why + " (the lens camera that was set has been removed: the pinhole camera renders)");
+            }
+            return rc;                                       // (the handle is unchanged: no lens before, whose block slot is never read, or the old block untouched)
+        }
+        lens_commit(e, ls);
+    }
+    e->camera = nc; e->lens_on = on;
+    if (!on) lens_release(e);                                // back to the pinhole: the tables are not kept
+    return upload_palette(e);                                // uni_rows, the lens palette with the frame filter
+}
+
+TRS_EXPORT int trs_get_camera(trs_env* e, trs_camera* out)
+{
+    if (!e || !out) return fail(TRS_ERR_ARG, "null argument");
+    *out = e->camera;
+    out->struct_size = (uint32_t)sizeof *out;
+    return TRS_OK;
 }
 
 TRS_EXPORT int trs_preprocess(trs_env* e, const trs_pre_config* c, const uint8_t* d_src, uint8_t* d_dst, int n_images, const uint8_t** d_out)

@@ -492,8 +492,8 @@ __device__ __forceinline__ int wait_lds_ge(const WParams& wp, const WLds& l, Dut
     }
 }
 
-template <bool DEPTH, bool DYN, bool HILLS = false>      // HILLS: a track with elevation (its own instantiations, see raster_hill_frame)
-__global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)
+template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false>      // HILLS: a track with elevation (its own instantiations, see raster_hill_frame);
+__global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)           // LENS: the lens camera on a flat track (raster_lens_frame)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool raster_team = tid < kRasterThreads;
@@ -517,6 +517,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)
     // ---- once per launch: tables by LDS-DMA, control block, env state ----
     if (raster_team) stage_lds_dma(p.blob, p.blob_bytes, 0u, wave, kRasterThreads / 64, lane);
     else stage_lds_dma(P.blob, P.blob_bytes, (unsigned)wp.lds_off_phys, pw, kPhysWaves, lane);
+    if (LENS && raster_team) lens_stage_palette(p, (unsigned)wp.lds_off_hill, wave, lane);   // the lens palette sits where a hilly track keeps its row tables
     if (tid == 0) { lds_store64(l.word, wp.start); lds_store64(l.fwd, wp.start); }
     if (tid < kSlots) l.arrive[tid] = 0;
     for (int j = tid; j < 2 * epw; j += kBlock) l.pprog[j] = 0;          // pprog | rread
@@ -633,6 +634,14 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)
     // more than the posts queued behind this step allow: a consumer that keeps two steps in
     // flight gets step s's completion after step s + 1's uniform rows, a lock-step consumer at once (drain, arrive).
     const RasterThread rth = raster_thread(p, smem, tid);
+    trsim::LensBlock lb{};
+    LensCacheWorker<DEPTH> lcache;
+    if constexpr (LENS) {
+        lb = *reinterpret_cast<const trsim::LensBlock*>(p.blob + trsim::lens_block_offset(p.blob_bytes));   // (uniform address: scalar loads)
+        lens_cache_load(p, rth, lb, lcache);                   // this thread's table entries, once for every frame of the kernel
+    }
+    // (the lens camera: the host sets uni_rows = 0, so the counts below are the lens frame's rows, one store instruction each (+1 with depth) as in the
+    // ground loop; its table loads sit between those stores in vmcnt and only make a counted wait below stricter, never looser)
     int nu = 0, ng = 0;
     for (int v = rth.vstart; v < p.uni_rows; v += p.rows_per_pass) ++nu;
     for (int v = rth.vground; v < p.H; v += p.rows_per_pass) ++ng;
@@ -806,7 +815,8 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)
             if (mine) tel = __float_as_uint(sl[4 + min(lane, 12)]);      // lanes 0..11 their word, lane 12 `done`
             asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(cam.x), "v"(cam.y), "v"(cam.z), "v"(cam.w), "v"(tel) : "memory");
             if (lane == 0) __hip_atomic_fetch_add(&l.rread[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            raster_ground_rows<DEPTH>(p, rth, fd, cam);
+            if constexpr (LENS) raster_lens_frame(p, rth, lb, lcache, (unsigned)wp.lds_off_hill, fd, cam);
+            else raster_ground_rows<DEPTH>(p, rth, fd, cam);
             if (mine && !(kDiag & 2)) {                     // the step's telemetry of env j: two wave instructions, written through
                 const size_t e = (size_t)(e_begin + j);
                 if (lane < 12) __hip_atomic_store((__attribute__((address_space(1))) unsigned*)(uintptr_t)optr + e, tel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1030,8 +1040,10 @@ int worker_fits(trs_env* e)
     if (e->has_frame_filter && e->filter_dynamic) { R->lds_off_dyn = (R->lds_bytes + 15) & ~15; R->lds_bytes = R->lds_off_dyn + dyn_lds_bytes(e->H); }
     R->lds_off_hill = (R->lds_bytes + 15) & ~15;
     if (e->hilly) R->lds_bytes = R->lds_off_hill + hill_lds_bytes(e->H);   // a track with elevation: the per-env row tables (trsim_device.hpp, hill_rows_build)
+    else if (e->lens_on) R->lds_bytes = R->lds_off_hill + trsim::kLensPalBytes;   // the lens camera: its palette (raster_lens_frame)
     if (R->lds_bytes > 160 * 1024)
         return trs_internal_fail(TRS_ERR_LIMIT, e->hilly ? "the resident worker's LDS state and the per-env row tables of a track with elevation do not fit beside this track's tables: use TRS_STEP_LAUNCH"
+                                                : e->lens_on ? "the resident worker's LDS state and the lens camera's palette do not fit beside this track's tables: use TRS_STEP_LAUNCH"
                                                             : "too many envs per workgroup for the resident worker's LDS state");
     return TRS_OK;
 }
@@ -1093,6 +1105,14 @@ int worker_launch(trs_env* e, uint64_t start)
     if (e->hilly) {                                       // a track with elevation (no frame filters there)
         if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
         else hipLaunchKernelGGL((trs_worker_kernel<false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+        RCHK(hipGetLastError());
+        R->running = true;
+        R->t_launch = std::chrono::steady_clock::now();
+        return TRS_OK;
+    }
+    if (e->lens_on) {                                     // the lens camera (flat tracks; the dynamic-brightness filter is refused with it)
+        if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+        else hipLaunchKernelGGL((trs_worker_kernel<false, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
         RCHK(hipGetLastError());
         R->running = true;
         R->t_launch = std::chrono::steady_clock::now();
@@ -1502,6 +1522,8 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_worker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (idle_us > 0) R->idle_us = (unsigned)std::min(idle_us, 1000000);
     if (!R->enabled) { R->base = R->seen_done = e->step_count; host_store(&R->mb->posted, e->step_count); }

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 #include "../../include/trsim_spec.h"
@@ -245,6 +246,74 @@ int build_tables(const trs_config& cfg, const double* xyz, int n_points, TrackTa
         for (int ch = 0; ch < 3; ++ch) T.far_rgb |= (uint32_t)round_colour((double)base[0][ch] * (1.0 - TRS_FOG_MAX) + (double)fog[ch] * TRS_FOG_MAX) << (8 * ch);
         T.inv_f = (float)(1.0 / f); T.hh = (float)half_h; T.pitch_f = (float)pitch;
         T.cam_h_f = (float)cfg.cam_h; T.z_far_f = (float)cfg.z_far; T.inv_zfar_f = (float)(1.0 / cfg.z_far); T.fog_f = (float)TRS_FOG_MAX;
+    }
+    return TRS_OK;
+}
+
+int build_lens_tables(const trs_config& cfg, double cell, double kx, double ky, LensTables& L, std::string& err)
+{
+    const int H = cfg.img_h, W = cfg.img_w;
+    if (H < 2 || W < 4 || !(cell > 0.0)) { err = "bad image size or map cell"; return TRS_ERR_ARG; }
+    L = LensTables{};
+    L.H = H; L.W = W;
+    const std::array<std::array<int, 3>, 4> base = {{TRS_RGB_GRASS, TRS_RGB_ROAD, TRS_RGB_EDGE, TRS_RGB_CENTRE}};
+    const std::array<int, 3> fog = TRS_RGB_FOG, sky_top = TRS_RGB_SKY_TOP, sky_hor = TRS_RGB_SKY_HOR;
+    // ---- palette: G(q) = the flat palette's fog blend at weight TRS_FOG_MAX * ((q + 0.5) / 256); S(q) = the flat sky blend at g = (q + 0.5) / 256; FAR
+    L.palette.assign((size_t)kLensPalRows * 4, 0u);
+    for (int q = 0; q < 256; ++q) {
+        const double fw = TRS_FOG_MAX * (((double)q + 0.5) / 256.0);
+        for (int c = 0; c < 4; ++c) {
+            uint32_t rgb = 0;
+            for (int ch = 0; ch < 3; ++ch) rgb |= (uint32_t)round_colour((double)base[c][ch] * (1.0 - fw) + (double)fog[ch] * fw) << (8 * ch);
+            L.palette[4 * (size_t)q + c] = rgb;
+        }
+        const double g = ((double)q + 0.5) / 256.0;
+        uint32_t sky = 0;
+        for (int ch = 0; ch < 3; ++ch) sky |= (uint32_t)round_colour((double)sky_top[ch] + ((double)sky_hor[ch] - (double)sky_top[ch]) * g) << (8 * ch);
+        for (int c = 0; c < 4; ++c) L.palette[4 * (size_t)(kLensSkyRow0 + q) + c] = sky;
+    }
+    uint32_t far = 0;
+    for (int ch = 0; ch < 3; ++ch) far |= (uint32_t)round_colour((double)base[0][ch] * (1.0 - TRS_FOG_MAX) + (double)fog[ch] * TRS_FOG_MAX) << (8 * ch);
+    for (int c = 0; c < 4; ++c) L.palette[4 * (size_t)kLensFarRow + c] = far;
+    // ---- per pixel
+    const double kPi = 3.14159265358979323846;
+    const double half_h = (double)H / 2.0, half_w = (double)W / 2.0;
+    const double f = half_h / std::tan(cfg.fov_v_deg * kPi / 180.0 / 2.0);
+    const double pitch = cfg.cam_pitch_deg * kPi / 180.0;
+    const double cp = std::cos(pitch), sp = std::sin(pitch);
+    const float zfar_f = (float)cfg.z_far;
+    L.pix.assign((size_t)H * W * 4, 0.0f);
+    for (int v = 0; v < H; ++v) {
+        const double py = half_h - ((double)v + 0.5);
+        const double yn = py / f;
+        for (int u = 0; u < W; ++u) {
+            const double px = ((double)u + 0.5) - half_w;
+            const double xn = px / f;
+            const double rho2 = (px * px + py * py) / (half_h * half_h);
+            const double xr = xn * (1.0 + kx * rho2), yr = yn * (1.0 + ky * rho2);
+            const double dy = yr * cp - sp, dz = yr * sp + cp;
+            float F = 0.0f, Lx = 0.0f, depth = zfar_f;
+            uint32_t row;
+            if (dy >= -1e-6) {
+                double g = (half_h - yr * f) / half_h;
+                g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g);
+                row = (uint32_t)(kLensSkyRow0 + std::min((int)(g * 256.0), 255));
+            } else {
+                const double t = cfg.cam_h / (-dy);
+                const double zd = t * dz;
+                if (zd > cfg.z_far) {
+                    row = (uint32_t)kLensFarRow;
+                } else {
+                    F = (float)(zd / cell);
+                    Lx = (float)((t * xr) / cell);
+                    depth = (float)zd;
+                    row = (uint32_t)std::min(std::max((int)(zd / cfg.z_far * 256.0), 0), 255);
+                }
+            }
+            float* const o = &L.pix[((size_t)v * W + u) * 4];
+            o[0] = F; o[1] = Lx; o[2] = depth;
+            std::memcpy(&o[3], &row, 4);
+        }
     }
     return TRS_OK;
 }

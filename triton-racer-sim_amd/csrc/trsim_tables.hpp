@@ -39,6 +39,18 @@ struct TrackTables {
     std::vector<uint16_t> grid_pts;        // [n_points]
 };
 
+// The lens camera (include/trsim_spec.h, "lens camera"): per pixel of the full frame F, L, depth and the lens palette row, and the lens palette,
+// in binary64 on the host.  The lateral offset is not in the table (the kernels move the camera by it), so the table depends on the config, the
+// map's cell size and the two fish-eye strengths only.
+constexpr int kLensPalRows = 513;          // 256 ground rows G(q) | 256 sky rows S(q) | FAR
+constexpr int kLensSkyRow0 = 256, kLensFarRow = 512;
+struct LensTables {
+    int H = 0, W = 0;
+    std::vector<float> pix;                // [H][W][4]: F, L, depth (binary32), palette row (uint32 bit pattern)
+    std::vector<uint32_t> palette;         // [kLensPalRows][4] 0x00BBGGRR, unfiltered
+};
+int build_lens_tables(const trs_config& cfg, double cell, double kx, double ky, LensTables& out, std::string& err);
+
 // returns TRS_OK or a negative trs_status, message in `err`
 int build_tables(const trs_config& cfg, const double* xyz, int n_points, TrackTables& out, std::string& err);
 

@@ -22,6 +22,7 @@ _FIELD_DTYPES = {
     "last_return": np.float32, "ep_len": np.int32, "done": np.uint8, "map": np.uint32, "rowtab": np.float32,
     "palette": np.uint32, "tangent": np.float32, "steer_filt": np.float32, "stats": np.uint64, "depth": np.float32, "rowdepth": np.float32,
     "ctl_steer": np.float32, "ctl_thr": np.float32, "ctl_brk": np.float32, "dpitch": np.float32,
+    "lens_table": np.float32, "lens_palette": np.uint32,
 }
 
 
@@ -91,7 +92,7 @@ def _stream_ptr(stream):
 
 class BatchedEnv:
     def __init__(self, n_envs=1, track="generated_track", device=0, img_h=120, img_w=160, render=True,
-                 auto_reset=False, env_id_base=0, seed=None, depth=False, _api=None, **overrides):
+                 auto_reset=False, env_id_base=0, seed=None, depth=False, camera=None, _api=None, **overrides):
         # `_api` exists for tests only (they pass the oracle's function table to diff both through one
         # wrapper); the product path always binds the HIP library and raises if it is not built.
         self.api = _api if _api is not None else _ffi.load_hip_library()
@@ -114,6 +115,11 @@ class BatchedEnv:
         self.map_info = None
         if track is not None:
             self.load_track(track)
+        if camera is not None:          # a dict of set_camera's keywords, or a (fish_eye_x, fish_eye_y, offset_x) triple
+            if isinstance(camera, dict):
+                self.set_camera(**camera)
+            else:
+                self.set_camera(*camera)
 
     # -- lifecycle ---------------------------------------------------------------------------
     def close(self):
@@ -223,7 +229,7 @@ class BatchedEnv:
         return {
             "img": (self.n, self.H, self.W, 3), "map": (mi.map_h, mi.map_words) if mi else None,
             "rowtab": (self.H, 2), "palette": (self.H, 4), "tangent": (self.n_points, 2), "stats": (64,), "depth": (self.n, self.H, self.W), "rowdepth": (self.H,),
-            "dpitch": (self.n_points,),
+            "dpitch": (self.n_points,), "lens_table": (self.H, self.W, 4), "lens_palette": (513, 4),
         }.get(name, (self.n,))
 
     def fetch(self, name):
@@ -321,6 +327,26 @@ class BatchedEnv:
         out = C.c_void_p()
         self.api.check(self.api.preprocess(self._h, C.byref(pc), None, None, self.n, C.byref(out)), "preprocess")
         return _DevicePtr(out.value, (self.n, self.H, self.W, 3), np.uint8, self)
+
+    def set_camera(self, fish_eye_x=0.0, fish_eye_y=0.0, offset_x=0.0):
+        """The lens camera (``trs_set_camera``; include/trsim_spec.h, "lens camera"): the ``fish_eye_x`` / ``fish_eye_y`` barrel strengths
+        (each in [0, 2]) and the lateral camera mount ``offset_x`` (world units, + = right of the heading, within +-2) of the reference's
+        gym_config.  ``set_camera(None)`` or all zero: the pinhole camera, byte for byte.  Flat tracks only; takes effect from the next step."""
+        if not getattr(self.api, "has_lens", False):
+            raise RuntimeError("this library has no lens camera (trs_set_camera)")
+        if fish_eye_x is None:
+            self.api.check(self.api.set_camera(self._h, None), "set_camera")
+            return
+        cam = _ffi.TrsCamera()
+        self.api.default_camera(C.byref(cam))
+        cam.fish_eye_x, cam.fish_eye_y, cam.offset_x = float(fish_eye_x), float(fish_eye_y), float(offset_x)
+        self.api.check(self.api.set_camera(self._h, C.byref(cam)), "set_camera")
+
+    def camera(self):
+        """``(fish_eye_x, fish_eye_y, offset_x)`` of the camera that is set (``trs_get_camera``; all zero = the pinhole)."""
+        cam = _ffi.TrsCamera()
+        self.api.check(self.api.get_camera(self._h, C.byref(cam)), "get_camera")
+        return cam.fish_eye_x, cam.fish_eye_y, cam.offset_x
 
     def set_frame_filter(self, cfg=None, enabled=True):
         """``ImgPreprocessing`` fused behind the rasteriser (``trs_set_frame_filter``): from the next frame on, the
