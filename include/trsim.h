@@ -293,6 +293,19 @@ void trs_default_camera(trs_camera* cam);   /* the pinhole: all zero */
 int trs_set_camera(trs_env* env, const trs_camera* cam_or_null);
 int trs_get_camera(trs_env* env, trs_camera* out);
 
+/* ---- scene lighting: a colour gain and bias per env, for domain randomisation (include/trsim_spec.h, "scene lighting") ----
+ * d_params: a caller-owned device array float[n_envs][8], {gR, gG, gB, 0, bR, bG, bB, 0} per env, read under the contract of trs_step's control
+ * arrays: every frame a call renders uses the values as they stand when that call starts (behind trs_stream_wait_external in launch mode, behind
+ * the post in resident mode), so values rewritten between steps need no new call (a running resident worker is not stopped for them).
+ * trs_set_lighting_host copies a host array into a device buffer the handle owns and registers that.  NULL (either call) returns to the unlit
+ * kernels: frames are then byte for byte what a handle that never set lighting renders.  Gain 1 and bias 0 are the identity.  Depth, state,
+ * indices and returns are not touched.  With a frame filter, frames are filter(lit raw frame) (dynamic brightness: the mean of the lit frame).
+ * Refused with TRS_ERR_STATE, the handle unchanged: a physics-only handle (cfg.render == 0), a lens camera (trs_set_camera) — in either order;
+ * TRS_ERR_LIMIT where the lit palettes do not fit in LDS beside the track's tables (or beside the resident worker's state in resident mode).
+ * Survives trs_load_track and trs_set_frame_filter.  The registering call itself synchronises the handle (and stops a resident worker). */
+int trs_set_lighting(trs_env* env, const float* d_params_or_null);
+int trs_set_lighting_host(trs_env* env, const float* h_params_or_null);
+
 /* Pilot-side normalisation (components/keras_pilot.py:49-55, keras_train.py:41-42): float32(img) / 255.
  * d_src NULL = latest frame; d_dst = float[n_images][H][W][3] device buffer. */
 int trs_normalize(trs_env* env, const uint8_t* d_src, float* d_dst, int n_images);

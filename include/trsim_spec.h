@@ -141,6 +141,16 @@
  *   (every binary64 operation sees identical or exactly negated operands), so a device may keep half of the table.
  *   An independent numpy restatement checks the host tables (tests/test_lens_tables_cpu.py); a C restatement of the per-pixel pass checks the
  *   frames (tests/test_lens_gpu.py).
+ *
+ * ---- scene lighting (trs_set_lighting; the pinhole camera on flat tracks and on tracks with elevation; not the lens camera) --------------------
+ *   Per env e, binary32 gain[e][ch] and bias[e][ch] for ch = R, G, B (frame channel order), laid out as float[n_envs][8] {gR gG gB 0 bR bG bB 0}.
+ *   Applied to the raw rendered colour of every pixel — after the fog blend and its rounding, before any frame filter — per channel x, binary32 (R1):
+ *     t = (float)x * gain;  t = t + bias;  t = t + 0.5f
+ *     out = !(t > 0.f) ? 0 : (t >= 255.f ? 255 : (int)t)                    (NaN -> 0)
+ *   gain = 1, bias = 0 is the identity, bit for bit.  A function of the colour alone: a lit frame equals L_e(raw frame) pixel for pixel, and with
+ *   a frame filter the frame equals filter(L_e(raw frame)) — with dynamic brightness, the frame's mean is the LIT frame's.  Depth, state, indices
+ *   and returns are untouched.  Not defined here (refused): the lens camera.  tests/test_lighting_cpu.py restates the rule in numpy against the product's
+ *   function (csrc/trsim_tables.hpp, light_channel); tests/test_lighting_gpu.py checks frames against the oracle's raw frames with the rule applied.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

@@ -128,9 +128,12 @@ PILOT_ARRAYS_OF_TYPE = {"cnn_2d_speed_control": 22, "cnn_2d": 22, "cnn_2d_speed_
 # HIP library only: the lens camera (trs_set_camera) has no twin in the C oracle — its checker is the restatement of include/trsim_spec.h
 # ("lens camera") in tests/test_lens_tables_cpu.py and tests/test_lens_gpu.py, and oracle/ stays as it is
 LENS_SYMBOLS = ["default_camera", "set_camera", "get_camera"]
+# HIP library only: scene lighting (trs_set_lighting) has no twin in the C oracle either — its checker is the oracle's unlit frame with the rule of
+# include/trsim_spec.h ("scene lighting") applied in numpy (tests/test_lighting_cpu.py, tests/test_lighting_gpu.py)
+LIGHT_SYMBOLS = ["set_lighting", "set_lighting_host"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -209,6 +212,10 @@ class Api:
             "set_camera": (i32, [vp, C.POINTER(TrsCamera)]),
             "get_camera": (i32, [vp, C.POINTER(TrsCamera)]),
         }
+        light = {
+            "set_lighting": (i32, [vp, vp]),
+            "set_lighting_host": (i32, [vp, C.POINTER(C.c_float)]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -223,6 +230,12 @@ class Api:
         self.has_lens = hasattr(cdll, prefix + "set_camera")
         if self.has_lens:
             for name, (res, args) in lens.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_lighting = hasattr(cdll, prefix + "set_lighting")
+        if self.has_lighting:
+            for name, (res, args) in light.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -43,6 +43,20 @@ def _camera_for(cfg):
     return vals if any(v != 0.0 for v in vals) else None
 
 
+def _lighting_for(cfg):
+    """The one car's scene lighting from the non-reference gym_config keys ``hip_lighting_gain`` and ``hip_lighting_bias``: a number or an
+    (R, G, B) triple each (strings accepted, as for the camera keys).  Both absent: ``None``, unlit frames."""
+    g, b = cfg.get("hip_lighting_gain"), cfg.get("hip_lighting_bias")
+    if g is None and b is None:
+        return None
+
+    def triple(v, default):
+        v = default if v is None else v
+        vals = [float(x) for x in (v if isinstance(v, (list, tuple, np.ndarray)) else [v])]
+        return np.broadcast_to(np.asarray(vals, np.float32), (3,)).reshape(1, 3)
+    return triple(g, 1.0), triple(b, 0.0)
+
+
 class HipGymInterface(Component):
     """One car (N = 1).  ``step(steering, throttle, breaking, reset) -> (img, x, y, z, speed, cte)``."""
 
@@ -59,6 +73,9 @@ class HipGymInterface(Component):
         self.env = BatchedEnv(n_envs=1, track=_track_for(self.gym_config), device=self.gym_config.get("hip_device", 0),
                               img_h=int(self.gym_config["img_h"]), img_w=int(self.gym_config["img_w"]), render=True,
                               camera=_camera_for(self.gym_config), _api=_api)
+        light = _lighting_for(self.gym_config)
+        if light is not None:
+            self.env.set_lighting(*light)
         if self.gym_config.get("hip_resident"):
             self.env.set_step_mode(True, idle_us=int(self.gym_config.get("hip_resident_idle_us", 0)))
         self.last_image = None
@@ -111,6 +128,10 @@ class BatchedGymInterface(Component):
         self.env = BatchedEnv(n_envs=n_envs, track=_track_for(self.gym_config), device=self.gym_config.get("hip_device", 0),
                               img_h=int(self.gym_config["img_h"]), img_w=int(self.gym_config["img_w"]), render=True,
                               auto_reset=auto_reset, env_id_base=env_id_base, camera=_camera_for(self.gym_config), _api=_api)
+
+    def set_lighting(self, params=None, bias=None):
+        """Scene lighting per env (``BatchedEnv.set_lighting``): redraw it at episode resets for domain randomisation."""
+        self.env.set_lighting(params, bias)
 
     def step(self, *args):
         steering, throttle, breaking, reset = args

@@ -9,6 +9,7 @@
 
 #include "../../include/trsim.h"
 #include "../../include/trsim_spec.h"
+#include "trsim_tables.hpp"
 
 #ifndef TRS_ABLATE
 #define TRS_ABLATE 0   /* 0 = product; 1/2 = timing-only diagnostic builds (scripts/ablate.sh), never shipped */
@@ -57,6 +58,9 @@ struct HillBlock {
     unsigned f_lo[4], f_hi[4];          // packed h | s << 8 | v << 16
     int f_dst[4];
     const int* hsv_tab;                 // [512] OpenCV's sdiv | hdiv fixed-point reciprocals (global)
+    // scene lighting (trs_set_lighting; the LIGHT instantiations only, flat tracks included): the caller's float[n_envs][8] {gR gG gB 0 bR bG bB 0}.  With lighting
+    // set, the host keeps the palette, the sky colours and the far colour RAW and fills the static frame filter above: the kernels light, then filter
+    const float* light;
 };
 
 struct RParams {                        // raster side of the step kernel
@@ -689,7 +693,8 @@ __device__ __forceinline__ uint32_t hill_filter_colour(const trsim::HillBlock& h
     return (uint32_t)o0 | ((uint32_t)o1 << 8) | ((uint32_t)o2 << 16);
 }
 
-__device__ __forceinline__ float hill_row_build(const RParams& p, unsigned char* lds, unsigned tab_off, float P, int v)   // returns the row's row_k (0: sky or beyond the far plane)
+// lg (LIGHT instantiations): the env's lighting parameters in LDS, applied to every colour of the row before the static filter (the sky and far colours are raw then)
+__device__ __forceinline__ float hill_row_build(const RParams& p, unsigned char* lds, unsigned tab_off, float P, int v, const float* lg = nullptr)   // returns the row's row_k (0: sky or beyond the far plane)
 {
     const trsim::HillBlock hb = *reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes));   // (uniform address: scalar loads)
     float sp, cp;
@@ -700,11 +705,13 @@ __device__ __forceinline__ float hill_row_build(const RParams& p, unsigned char*
     uint32_t c0, c1, c2, c3;
     if (dy >= -1e-6f) {
         c0 = c1 = c2 = c3 = *(lds_u32p)(uintptr_t)((unsigned)hb.off_sky + ((unsigned)v << 2));
+        if (lg) { c0 = trsim::light_colour(c0, lg); if (hb.filt) c0 = hill_filter_colour(hb, c0); c1 = c2 = c3 = c0; }
     } else {
         const float t = hb.cam_h_f / (-dy);
         const float zd = t * dz;
         if (zd > hb.z_far_f) {
             c0 = c1 = c2 = c3 = hb.far_rgb;
+            if (lg) { c0 = trsim::light_colour(c0, lg); if (hb.filt) c0 = hill_filter_colour(hb, c0); c1 = c2 = c3 = c0; }
         } else {
             lz = zd * hb.inv_cell_f; kk = (t * hb.inv_f) * hb.inv_cell_f; dep = zd;
             const float fw = hb.fog_f * (zd * hb.inv_zfar_f), om = 1.0f - fw;
@@ -720,6 +727,7 @@ __device__ __forceinline__ float hill_row_build(const RParams& p, unsigned char*
                     const float sum = a + b;
                     rgb |= (uint32_t)(int)(sum + 0.5f) << (8 * ch);
                 }
+                if (lg) rgb = trsim::light_colour(rgb, lg);
                 col[c] = hb.filt ? hill_filter_colour(hb, rgb) : rgb;
             }
             c0 = col[0]; c1 = col[1]; c2 = col[2]; c3 = col[3];
@@ -759,7 +767,7 @@ __device__ __forceinline__ bool team_barrier_wait(const int* dbar, int target, B
 // `done_before` = team barriers this kernel has passed so far x raster waves; returns false when a barrier gave up (resident worker: abort / safety).
 template <typename Bail>
 __device__ __forceinline__ bool hill_batch_build(const RParams& p, unsigned char* lds, unsigned tab0, const float (&P)[kHillBatchMax], int nb, int* hbar, int done_before,
-                                                 int tid, int lane, Bail& bail)
+                                                 int tid, int lane, Bail& bail, const float* lg0 = nullptr)   // lg0: the batch's lighting parameters in LDS, 8 floats per env (LIGHT)
 {
     constexpr int nrw = kRasterThreads / 64;
     // first_ground[parity of the batch][env]: the first row of the env's frame that sees the ground (row_k != 0).  The rows above it — sky, beyond the far plane — go
@@ -774,7 +782,7 @@ __device__ __forceinline__ bool hill_batch_build(const RParams& p, unsigned char
     for (int row = tid; row < nb * p.H; row += kRasterThreads) {
         const int bi = row / p.H, v = row - bi * p.H;
         const float Pv = bi == 0 ? P[0] : (bi == 1 ? P[1] : (bi == 2 ? P[2] : P[3]));
-        if (hill_row_build(p, lds, tab0 + (unsigned)bi * tb, Pv, v) != 0.0f) __hip_atomic_fetch_min(&fg[bi], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (hill_row_build(p, lds, tab0 + (unsigned)bi * tb, Pv, v, lg0 ? lg0 + 8 * bi : nullptr) != 0.0f) __hip_atomic_fetch_min(&fg[bi], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) __hip_atomic_fetch_add(hbar, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -795,6 +803,43 @@ __device__ __forceinline__ void raster_hill_frame(const RParams& p, const Raster
     if (vg < first_ground) vg += ((first_ground - vg + p.rows_per_pass - 1) / p.rows_per_pass) * p.rows_per_pass;
     t.vground = vg;
     raster_ground_rows<DEPTH, true>(p, t, f, cam);
+}
+
+// ---- scene lighting on a flat track (include/trsim_spec.h, "scene lighting"; the LIGHT instantiations) ------------------------------------------------
+// Every raster wave shades from its OWN lit copy of the palette: before an env's frame it lights (and, with the static frame filter, filters) the
+// palette entries of the rows its threads walk — rows v with v % rows_per_pass in the wave's range of r0 — into that copy, then shades the frame
+// from it through the unchanged row loops (RasterThread::pal_off).  No team barrier: a wave writes and reads only its own entries, and a wave's
+// LDS operations execute in order.  Waves w and w + light_copies(gpr) walk disjoint rows, so they share a copy.  LDS: behind the lighting
+// parameters, light_copies x uint32[H][4].  ~1-5 entries per lane and frame against ~40 shaded pixels.
+constexpr int kDynBatch = 4;                  // envs per batch of the dynamic-brightness filter behind the rasteriser (raster_dyn_batch)
+__host__ __device__ inline int light_copies(int gpr) { return (gpr + 63 + 63) / 64; }
+__host__ __device__ inline int light_pal_bytes(int H, int gpr) { return light_copies(gpr) * H * 16; }
+// The LDS of scene lighting behind the row tables (or where they would sit): the parameters of `slots` envs (the step kernel: the workgroup's envs; the
+// worker: a ring of kCamDepth steps of them), then on a flat track the waves' lit palettes — or, with the dynamic-brightness filter, the batch's lit
+// palettes by channel (raster_dyn_batch)
+__host__ __device__ inline int light_lds_extra(int H, int W, int slots, bool hilly, bool dyn)
+{
+    return slots * 32 + (hilly ? 0 : (dyn ? kDynBatch * H * 16 : light_pal_bytes(H, W / 4)));
+}
+// lg: the env's parameters in LDS; filt: the block's static-filter flag (read once per kernel); returns the LDS offset of the wave's lit palette
+__device__ __forceinline__ unsigned light_wave_palette(const RParams& p, unsigned pal0, const float* lg, int filt, int wave, int lane)
+{
+    const unsigned dst = pal0 + (unsigned)((wave % light_copies(p.gpr)) * p.H * 16);
+    const int lo = (64 * wave) / p.gpr, hi = min((64 * wave + 63) / p.gpr, p.rows_per_pass - 1);
+    const trsim::HillBlock& hb = *reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes));
+    float gb[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) gb[k] = lg[k];
+    asm volatile("" ::: "memory");                            // (the previous frame's palette reads of this wave are issued before these writes; LDS keeps a wave's order)
+    for (int r0 = lo; r0 <= hi; ++r0)
+        for (int i = lane; r0 + (i >> 2) * p.rows_per_pass < p.H; i += 64) {
+            const unsigned ent = ((unsigned)(r0 + (i >> 2) * p.rows_per_pass) << 4) + ((unsigned)(i & 3) << 2);
+            uint32_t c = trsim::light_colour(*(lds_u32p)(uintptr_t)((unsigned)p.off_pal + ent), gb);
+            if (filt) c = hill_filter_colour(hb, c);
+            *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)(dst + ent) = c;
+        }
+    asm volatile("" ::: "memory");                            // (the frame's palette reads stay behind these writes: a wave's LDS operations execute in order)
+    return dst;
 }
 
 // ---- the lens camera (include/trsim_spec.h, "lens camera") ------------------------------------------------------------------------------------
@@ -988,7 +1033,6 @@ __device__ __forceinline__ uint32_t filter_colour_dev(const FParams& f, const un
 #else
 #define DYN_STAMP(k) do { } while (0)
 #endif
-constexpr int kDynBatch = 4;
 __host__ __device__ inline int dyn_lds_bytes(int H) { return kDynBatch * H * 16 + 128 + ((kDynTabWords * 4 + 15) & ~15) + H * 16; }   // ... + rowch[H]: the raw palette by channel
 // the tables behind the batch's palettes and sums (staged by dyn_stage_tables before the launch's first barrier)
 __device__ __forceinline__ unsigned* dyn_tabs_lds(unsigned char* lds_base, const FParams& f, int H) { return reinterpret_cast<unsigned*>(lds_base + f.lds_off + kDynBatch * H * 16 + 128); }
@@ -1012,9 +1056,13 @@ __device__ __forceinline__ void dyn_stage_tables(unsigned char* lds_base, const 
 // answers from its abort bit and its safety deadline (a wave of the team that left at an aborted wait_posted never arrives here: ADVICE r03); a
 // launched kernel has no abort and passes a callable that says no.  false = gave up: the caller leaves the kernel.
 
-template <bool DEPTH, typename Bail>
+// LIGHT (scene lighting): lg0 = the batch's lighting parameters in LDS (8 floats per env), lrowch_off = LDS of the batch's LIT palettes by channel
+// (uint32 [kDynBatch][H][4], the layout of rowch): a third team barrier per batch, in front of phase A, closes (0) — every thread lights one row of one env's
+// palette — so phase A sums lit colours and phase B filters lit colours: the frame's mean is the lit frame's (filter(L_e(raw))).
+template <bool DEPTH, bool LIGHT = false, typename Bail>
 __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams& f, const RasterThread& rth, unsigned char* lds_base, const float4 (&cams)[kDynBatch],
-                                                 int nb, uint8_t* img, float* dep, int e, int it, int tid, int lane, Bail&& bail)
+                                                 int nb, uint8_t* img, float* dep, int e, int it, int tid, int lane, Bail&& bail,
+                                                 const float* lg0 = nullptr, unsigned lrowch_off = 0)
 {
     uint32_t* const penv = reinterpret_cast<uint32_t*>(lds_base + f.lds_off);                          // [kDynBatch][H][4]
 #ifdef TRS_DYN_STAMPS
@@ -1025,7 +1073,26 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
     int* const dbar = esum + 2 * kDynBatch * 3;
     const int par = it & 1;
     const int nrw = kRasterThreads / 64;
+    constexpr int kBars = LIGHT ? 3 : 2;                                  // team barriers per batch
     const f2v* const lrow = rth.lrow;
+    if constexpr (LIGHT) {
+        // (0) the batch's lit palettes by channel (an env past the batch's end takes the last env's parameters: computed, never read)
+        for (int item = tid; item < kDynBatch * p.H; item += kRasterThreads) {
+            const int bi = item / p.H, v = item - bi * p.H;
+            const float* const lg = lg0 + 8 * min(bi, nb - 1);
+            uint32_t c[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[k] = trsim::light_colour(*(lds_u32p)(uintptr_t)((unsigned)p.off_pal + ((unsigned)(4 * v + k) << 2)), lg);
+            uint32_t* const dst = reinterpret_cast<uint32_t*>(lds_base + lrowch_off) + 4 * item;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                dst[ch] = ((c[0] >> (8 * ch)) & 255u) | (((c[1] >> (8 * ch)) & 255u) << 8) | (((c[2] >> (8 * ch)) & 255u) << 16) | (((c[3] >> (8 * ch)) & 255u) << 24);
+            dst[3] = 0u;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(dbar, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (!team_barrier_wait(dbar, nrw * (kBars * it + 1), bail)) return false;
+    }
     unsigned cbits[kDynBatch][4];
 #pragma unroll
     for (int bi = 0; bi < kDynBatch; ++bi)
@@ -1091,10 +1158,11 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
         typedef unsigned lu4 __attribute__((ext_vector_type(4)));
         auto rowch_of = [&](int v) -> lu4 { return *(const __attribute__((address_space(3))) lu4*)(uintptr_t)(rowch_a + ((unsigned)v << 4)); };
         lu4 rc = rowch_of(max(vl, 0));                                   // this row's palette and row-table entry were requested one row earlier
+        typedef unsigned lu3 __attribute__((ext_vector_type(3)));   // (LIGHT: each env's own lit row, lrowch[bi][v] — its R, G, B words)
         f2v rt = lrow[max(vl, 0)];
         for (int v = vl; v >= vstop; v -= p.rows_per_pass) {
             const int vn = max(v - p.rows_per_pass, 0);
-            const lu4 rcn = rowch_of(vn);
+            const lu4 rcn = LIGHT ? rc : rowch_of(vn);
             const f2v rtn = lrow[vn];
             unsigned packs[kDynBatch];
 #pragma unroll
@@ -1111,6 +1179,12 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
             unsigned cnt[kDynBatch];
 #pragma unroll
             for (int bi = 0; bi < kDynBatch; ++bi) cnt[bi] = *(lds_u32p)(uintptr_t)(cnt_a + (packs[bi] << 2));   // (the four reads together, the pushes underneath)
+            lu3 rcl[kDynBatch];                                          // (LIGHT: the envs' lit rows, read with the counts — 12 registers, not a row ahead)
+            if constexpr (LIGHT) {
+#pragma unroll
+                for (int bi = 0; bi < kDynBatch; ++bi)
+                    rcl[bi] = *(const __attribute__((address_space(3))) lu3*)(uintptr_t)(lrowch_off + ((unsigned)(bi * p.H + v) << 4));
+            }
 #pragma unroll
             for (int bi = 0; bi < kDynBatch; ++bi) {
                 cbits[bi][3] = __builtin_amdgcn_alignbit(cbits[bi][3], cbits[bi][2], 24);
@@ -1121,9 +1195,10 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int bi = 0; bi < kDynBatch; ++bi) {
-                ssr[bi] = __builtin_amdgcn_udot4(cnt[bi], rc.x, ssr[bi], false);
-                ssg[bi] = __builtin_amdgcn_udot4(cnt[bi], rc.y, ssg[bi], false);
-                ssb[bi] = __builtin_amdgcn_udot4(cnt[bi], rc.z, ssb[bi], false);
+                const unsigned rx = LIGHT ? rcl[bi].x : rc.x, ry = LIGHT ? rcl[bi].y : rc.y, rz = LIGHT ? rcl[bi].z : rc.z;
+                ssr[bi] = __builtin_amdgcn_udot4(cnt[bi], rx, ssr[bi], false);
+                ssg[bi] = __builtin_amdgcn_udot4(cnt[bi], ry, ssg[bi], false);
+                ssb[bi] = __builtin_amdgcn_udot4(cnt[bi], rz, ssb[bi], false);
             }
             rc = rcn; rt = rtn;
         }
@@ -1141,7 +1216,7 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
     DYN_STAMP(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) __hip_atomic_fetch_add(dbar, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (!team_barrier_wait(dbar, nrw * (2 * it + 1), bail)) return false;
+    if (!team_barrier_wait(dbar, nrw * (kBars * it + kBars - 1), bail)) return false;
     DYN_STAMP(1);
     // (B) delta exactly as ImgPreprocessing computes it (binary64; img_preprocessing.py:88-91), then the palette entries
     {
@@ -1176,7 +1251,7 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
 #if TRS_DYN_ABLATE == 2   /* timing-only: phase B without the filter arithmetic */
                 c[bi] = raw + (unsigned)dlt[bi];
 #else
-                c[bi] = filter_colour_dev(f, ltabs, raw, dlt[bi]);
+                c[bi] = filter_colour_dev(f, ltabs, LIGHT ? trsim::light_colour(raw, lg0 + 8 * min(bi, nb - 1)) : raw, dlt[bi]);
 #endif
             }
 #pragma unroll
@@ -1191,7 +1266,7 @@ __device__ __forceinline__ bool raster_dyn_batch(const RParams& p, const FParams
     DYN_STAMP(2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) __hip_atomic_fetch_add(dbar, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (!team_barrier_wait(dbar, nrw * (2 * it + 2), bail)) return false;
+    if (!team_barrier_wait(dbar, nrw * (kBars * it + kBars), bail)) return false;
     DYN_STAMP(3);
     // (C) rows outside, envs inside (as phase A): the four envs' palette gathers of a row are sixteen independent LDS reads in flight; one env at a
     // time every row was its own round trip (6.9 of the step's 19 us by the stamps of scripts/dyn_stamps.sh, at 58 % of the vector-issue rate).

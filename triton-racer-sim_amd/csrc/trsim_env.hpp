@@ -38,6 +38,10 @@ struct trs_env {
     unsigned char* lens_dev = nullptr;        // device: half-width planes F | L | D | M, then the lens palette (LensBlock points into it)
     size_t lens_pal_off = 0;                  // byte offset of the palette in lens_dev
     int max_steps_lens = 1;                   // steps per launch that fit beside the lens palette in LDS
+    // scene lighting (trs_set_lighting; include/trsim_spec.h, "scene lighting"): the LIGHT instantiations of the step kernels run while light_on
+    bool light_on = false;
+    const float* light = nullptr;             // the registered float[n][8]: the caller's, or light_own
+    float* light_own = nullptr;               // trs_set_lighting_host's copy (owned by the handle)
     unsigned long long* stats = nullptr;
     double* loc_q = nullptr; int32_t* loc_out = nullptr; int loc_cap = 0;
     uint8_t* pre = nullptr;              // processed frames of the env (trs_preprocess with d_dst == NULL)
@@ -93,7 +97,8 @@ int sync_handle(trs_env* e);                               // the handle's strea
 int quiesce_handle(trs_env* e);                            // a resident worker has left; queued work may still be running
 void comm_destroy(trs_env* e);
 bool resident_running(const trs_env* e);
-bool resident_fits_dynamic_filter(const trs_env* e);      // the worker's LDS need WITH the dynamic-brightness palettes still fits a CU
+bool resident_fits_dynamic_filter(const trs_env* e);      // the worker's LDS need WITH the dynamic-brightness palettes still fits a CU (and the handle's scene lighting)
+bool resident_fits_lighting(const trs_env* e, bool dyn);  // the worker's LDS need WITH scene lighting (and the dynamic-brightness filter or not) still fits a CU
 void resident_clear_fault(trs_env* e);                     // trs_load_track puts every env on a defined state again
 int check_fault(trs_env* e);                               // TRS_ERR_DEVICE (sticky) once a kernel has reported a layout fault
 }  // namespace trsim

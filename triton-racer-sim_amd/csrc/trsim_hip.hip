@@ -113,8 +113,8 @@ __global__ __launch_bounds__(kPhysBlock) void trs_physics_kernel(const PParams p
 }
 
 
-template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false>      // HILLS: a track with elevation (its own instantiations: the flat kernels' loops do not change for it);
-__global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)           // LENS: the lens camera on a flat track (likewise)
+template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false, bool LIGHT = false>   // HILLS: a track with elevation (its own instantiations: the flat kernels' loops do not change for it);
+__global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)           // LENS: the lens camera on a flat track (likewise); LIGHT: scene lighting (flat or HILLS)
 {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -144,6 +144,12 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
     int* const hbar = reinterpret_cast<int*>(smem + lds_off_hill + hill_batch(p.H) * hill_table_bytes(p.H));
     const trsim::HillBlock* const hill = HILLS ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes)) : nullptr;
     if (HILLS && tid == 0) *hbar = 0;
+    // scene lighting (LIGHT): the workgroup's lighting parameters float[cam_stride][8], read once per launch (a call's frames all use the values as they stood when it
+    // started), then the raster waves' lit palettes (light_wave_palette) — behind the row tables of a track with elevation, else where those would sit
+    const int lds_off_light = (lds_off_hill + (HILLS ? hill_lds_bytes(p.H) : 0) + 15) & ~15;
+    float* const llight = reinterpret_cast<float*>(smem + lds_off_light);
+    const unsigned lds_off_lpal = (unsigned)lds_off_light + (unsigned)sp.cam_stride * 32u;
+    const int lfilt = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->filt : 0;   // (once per kernel)
     if constexpr (DYN) {
         if (tid < 32) reinterpret_cast<int*>(smem + sp.fp.lds_off + 4 * p.H * 16)[tid] = 0;   // esum[2][4][3], dbar
         dyn_stage_tables(smem, sp.fp, p.H, tid, kBlock, reinterpret_cast<const uint32_t*>(p.blob + p.off_pal));                   // OpenCV's reciprocals + the in-range byte masks (behind the prologue's barrier)
@@ -165,6 +171,10 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
             stage_lds_dma(sp.ph.blob, sp.ph.blob_bytes, (unsigned)sp.lds_off_phys, pw, kPhysWaves, lane);
         }
         if (LENS && raster_team && rendering) lens_stage_palette(p, (unsigned)lds_off_hill, wave, lane);   // the lens palette sits where a hilly track keeps its row tables
+        if (LIGHT && raster_team && rendering) {
+            const float* const lsrc = reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->light + (size_t)e_begin * 8;
+            for (int j = tid; j < (e_end - e_begin) * 8; j += kRasterThreads) llight[j] = lsrc[j];
+        }
         if (has_c) lcam_prev[tid] = cv;
         if (raster_team && rendering && sp.r_first < 0)
             for (int j = tid + kRasterThreads; j < e_end - e_begin; j += kRasterThreads) lcam_prev[j] = cam_prev[e_begin + j];
@@ -269,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
                 }
             }
             auto never = [](bool) { return false; };                          // (a launch has no abort: every raster wave arrives)
-            (void)hill_batch_build(p, smem, (unsigned)lds_off_hill, Pv, nb, hbar, it * 2 * (kRasterThreads / 64), tid, lane, never);
+            (void)hill_batch_build(p, smem, (unsigned)lds_off_hill, Pv, nb, hbar, it * 2 * (kRasterThreads / 64), tid, lane, never, LIGHT ? llight + (e - e_begin) * 8 : nullptr);
 #pragma unroll
             for (int bi = 0; bi < kHillBatchMax; ++bi)
                 if (bi < nb)
@@ -311,13 +321,16 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
                     }
                 }
             }
-            (void)raster_dyn_batch<DEPTH>(p, sp.fp, rth, smem, cams, min(kDynBatch, e_end - e), img, dep, e, it, tid, lane, [](bool) { return false; });   // a launch has no abort: every raster wave arrives
+            (void)raster_dyn_batch<DEPTH, LIGHT>(p, sp.fp, rth, smem, cams, min(kDynBatch, e_end - e), img, dep, e, it, tid, lane, [](bool) { return false; },   // a launch has no abort: every raster wave arrives
+                                                 LIGHT ? llight + (e - e_begin) * 8 : nullptr, lds_off_lpal);
             continue;
         }
         // rows with four equal class colours need no map lookup and no pose: they are written first, and in a single-step
         // call while the physics team still integrates
         const FrameDesc fd = frame_desc<DEPTH>(p, img, dep, e);
-        if (!sp.skip_uniform) raster_uniform_rows<DEPTH>(p, rth, fd);
+        RasterThread rl = rth;                                                // (LIGHT: shaded from this wave's lit copy of the palette)
+        if constexpr (LIGHT && !HILLS && !DYN) rl.pal_off = light_wave_palette(p, lds_off_lpal, llight + (e - e_begin) * 8, lfilt, wave, lane);
+        if (!sp.skip_uniform) raster_uniform_rows<DEPTH>(p, rl, fd);
         // -- rows that see the track
         float4 cam;
         const int j = e - e_begin;
@@ -327,7 +340,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
             while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
             cam = lcam[sidx * sp.cam_stride + j];
         }
-        raster_ground_rows<DEPTH>(p, rth, fd, cam);
+        raster_ground_rows<DEPTH>(p, rl, fd, cam);
     }
     }
     STAMP(5);
@@ -1015,6 +1028,29 @@ namespace {
 
 int grid_of(const trs_env* e) { return (e->n + e->pp.envs_per_wg - 1) / e->pp.envs_per_wg; }
 
+// The step kernel's dynamic LDS for n_phys physics steps per launch: launch_step's layout (which sets the offsets), for the handle's track and frame filter and
+// with scene lighting on or off
+int step_lds_need(const trs_env* e, int n_phys, bool light, bool dyn)
+{
+    const int epw = e->pp.envs_per_wg;
+    int lds = e->lds_step + (std::max(n_phys, 1) + 1) * epw * 16 + epw * 4 + 16;
+    if (e->hilly || e->lens_on || light) {
+        lds = ((lds + (std::max(n_phys, 1) + 1) * epw * 4 + 15) & ~15) + (e->hilly ? hill_lds_bytes(e->H) : (e->lens_on ? trsim::kLensPalBytes : 0));
+        if (light) lds = ((lds + 15) & ~15) + light_lds_extra(e->H, e->W, epw, e->hilly, dyn);
+    }
+    if (dyn) lds = ((lds + 15) & ~15) + dyn_lds_bytes(e->H);
+    return lds;
+}
+
+// steps per launch that fit with scene lighting (0: none) for the loaded track, with or without the dynamic-brightness filter
+int light_max_steps(const trs_env* e, bool dyn)
+{
+    int k = 0;
+    for (int n = 1; n <= 16; ++n)
+        if (step_lds_need(e, n, true, dyn) <= 160 * 1024) k = n;
+    return k;
+}
+
 // the handle's stream is idle: a resident worker (trs_set_step_mode) is asked to leave first — it owns the stream while it runs
 int sync_all(trs_env* e)
 {
@@ -1036,6 +1072,7 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
                 int n_phys, int r_first, int r_last, uint64_t step_base, bool keep_uniform = false)
 {
     SParams sp;
+    const bool dyn = e->has_frame_filter && e->filter_dynamic;
     sp.ph = e->pp;
     sp.ph.ctl_steer = st; sp.ph.ctl_thr = th; sp.ph.ctl_brk = br; sp.ph.ctl_reset = rs; sp.ph.ctl_stride = e->seq_stride;
     sp.ph.synth = synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
@@ -1049,19 +1086,19 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.lds_off_cam = e->lds_step;                                                   // ring + counters sit behind the tables
     sp.lds_off_prog = sp.lds_off_cam + (std::max(n_phys, 1) + 1) * sp.cam_stride * 16;   // + one row: poses of the step before the launch
     int lds = sp.lds_off_prog + sp.cam_stride * 4 + 16;                            // + spare counters
-    if (e->hilly || e->lens_on) {                                                   // a track with elevation: view pitches behind the counters, the batch's row tables, a counter
+    if (e->hilly || e->lens_on || e->light_on) {                                    // a track with elevation: view pitches behind the counters, the batch's row tables, a counter
         const int off_pitch = lds;                                                  // (= lds_off_prog + cam_stride * 4 + 16: the HILLS kernels compute the same offsets)
         const int off_hill = (off_pitch + (std::max(n_phys, 1) + 1) * sp.cam_stride * 4 + 15) & ~15;
-        lds = off_hill + (e->hilly ? hill_lds_bytes(e->H) : trsim::kLensPalBytes);   // (the lens camera: its palette at the same offset)
+        lds = off_hill + (e->hilly ? hill_lds_bytes(e->H) : (e->lens_on ? trsim::kLensPalBytes : 0));   // (the lens camera: its palette at the same offset)
+        if (e->light_on) lds = ((lds + 15) & ~15) + light_lds_extra(e->H, e->W, sp.cam_stride, e->hilly, dyn);   // scene lighting: the workgroup's parameters, the lit palettes
     }
-    const bool dyn = e->has_frame_filter && e->filter_dynamic;
     // Which frame buffers hold the CURRENT palette's uniform rows for every env (e->uniform_ok[b]): a launch that renders whole frames into a buffer makes it
     // so; a palette change (upload_palette: track, frame filter) or the dynamic-brightness filter (its uniform rows follow each frame's own mean) undoes it.
     sp.skip_uniform = 0;
     for (int r = r_first; r <= r_last; ++r) {
         const int b = (int)((step_base + (uint64_t)(int64_t)r) & 1u);
-        if (keep_uniform && r_first == r_last && e->uniform_ok[b] && !dyn && !e->lens_on) sp.skip_uniform = 1;
-        else e->uniform_ok[b] = !dyn && !e->lens_on;                              // (the lens camera writes whole frames: no uniform rows)
+        if (keep_uniform && r_first == r_last && e->uniform_ok[b] && !dyn && !e->lens_on && !e->light_on) sp.skip_uniform = 1;
+        else e->uniform_ok[b] = !dyn && !e->lens_on && !e->light_on;             // (the lens camera writes whole frames: no uniform rows; scene lighting: they follow the env's parameters)
     }
     std::memset(&sp.fp, 0, sizeof sp.fp);
     if (dyn) {
@@ -1079,7 +1116,18 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
         lds = sp.fp.lds_off + dyn_lds_bytes(e->H);                         // palettes of a batch of 4 envs + channel sums + barrier counter + the mask tables
     }
     const dim3 grid(grid_of(e)), block(kBlock);
-    if (e->hilly) {                                         // a track with elevation (its own instantiations; the dynamic-brightness filter is refused there)
+    if (e->light_on && dyn) {                               // scene lighting with the dynamic-brightness filter (flat tracks)
+        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, true, false, false, true>), grid, block, lds, e->sP, sp);
+        else hipLaunchKernelGGL((trs_step_kernel<false, true, false, false, true>), grid, block, lds, e->sP, sp);
+    } else if (e->light_on) {                               // scene lighting (flat or with elevation; no lens with it)
+        if (e->hilly) {
+            if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, true, false, true>), grid, block, lds, e->sP, sp);
+            else hipLaunchKernelGGL((trs_step_kernel<false, false, true, false, true>), grid, block, lds, e->sP, sp);
+        } else {
+            if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, false, false, true>), grid, block, lds, e->sP, sp);
+            else hipLaunchKernelGGL((trs_step_kernel<false, false, false, false, true>), grid, block, lds, e->sP, sp);
+        }
+    } else if (e->hilly) {                                         // a track with elevation (its own instantiations; the dynamic-brightness filter is refused there)
         if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, true>), grid, block, lds, e->sP, sp);
         else hipLaunchKernelGGL((trs_step_kernel<false, false, true>), grid, block, lds, e->sP, sp);
     } else if (e->lens_on) {                                // the lens camera (flat tracks; the dynamic-brightness filter is refused with it)
@@ -1107,7 +1155,8 @@ int run_camera_steps(trs_env* e, const float* st, const float* th, const float* 
 {
     const uint64_t s0 = e->step_count;
     const bool dyn_filter = e->has_frame_filter && e->filter_dynamic;
-    const int kmax = std::max(1, std::min(per_launch, dyn_filter ? e->max_steps_dyn : (e->lens_on ? e->max_steps_lens : e->max_steps_per_launch)));
+    const int kmax = std::max(1, std::min(per_launch, e->light_on ? light_max_steps(e, dyn_filter)
+                                                                  : (dyn_filter ? e->max_steps_dyn : (e->lens_on ? e->max_steps_lens : e->max_steps_per_launch))));
     int rc = TRS_OK;
     if (n == 1) {
         rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0, keep_uniform);
@@ -1271,7 +1320,7 @@ TRS_EXPORT int trs_destroy(trs_env* e)
     if (e->pilot) { trs_pilot_free(e->pilot); e->pilot = nullptr; }
     (void)hipFree(e->slab); (void)hipFree(e->img[0]); (void)hipFree(e->img[1]); (void)hipFree(e->depth[0]); (void)hipFree(e->depth[1]); (void)hipFree(e->blob_p); (void)hipFree(e->blob_r);
     (void)hipFree(e->tangent); (void)hipFree(e->start_yaw); (void)hipFree(e->cam); (void)hipFree(e->cam_pitch); (void)hipFree(e->dpitch);
-    (void)hipFree(e->stats); (void)hipFree(e->loc_q); (void)hipFree(e->loc_out); (void)hipFree(e->lens_dev);
+    (void)hipFree(e->stats); (void)hipFree(e->loc_q); (void)hipFree(e->loc_out); (void)hipFree(e->lens_dev); (void)hipFree(e->light_own);
     (void)hipFree(e->mux_state); (void)hipFree(e->edge_scratch); (void)hipFree(e->seq_buf); (void)hipFree(e->glue);
     for (void* sc : e->scratch) (void)hipFree(sc);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -1412,6 +1461,12 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifndef TRS_SINGLE_VARIANT
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #endif
@@ -1475,6 +1530,11 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
         e->has_frame_filter = false; e->filter_dynamic = false;
         (void)upload_palette(e);
         return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the dynamic-brightness frame filter that was set: the filter has been removed");
+    }
+    if (e->light_on && light_max_steps(e, e->has_frame_filter && e->filter_dynamic) < 1) {   // (e->hilly, e->lds_step: the new track's)
+        e->light_on = false; e->light = nullptr;
+        (void)upload_palette(e);
+        return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the scene lighting that was set: lighting has been removed");
     }
     return upload_palette(e);                 // also sets rp.uni_rows (and applies a frame filter that was set earlier)
 }
@@ -1862,7 +1922,7 @@ int upload_palette(trs_env* e)
 {
     if (!e->track_loaded || !e->cfg.render) return TRS_OK;
     std::vector<uint32_t> pal(e->tab.palette);
-    if (e->has_frame_filter && !e->filter_dynamic)             // dynamic brightness: the kernel filters a per-env palette itself
+    if (e->has_frame_filter && !e->filter_dynamic && !e->light_on)   // dynamic brightness: the kernel filters a per-env palette itself; scene lighting: lit, then filtered, in the kernel
         for (auto& c : pal) c = filter_colour(e->frame_filter, c);
     e->rp.uni_rows = (e->hilly || e->lens_on) ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame;
     e->uniform_ok[0] = e->uniform_ok[1] = false;               //  the lens camera: on the pixel)  (the closed pilot loop's steps skip rows an earlier step wrote: not across a palette change)
@@ -1874,18 +1934,22 @@ int upload_palette(trs_env* e)
             for (auto& c : lp) c = filter_colour(e->frame_filter, c);
         HIPCHK(hipMemcpy(e->lens_dev + e->lens_pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
     }
-    if (e->hilly) {
+    if (e->hilly || e->light_on) {
         // a track with elevation: the kernels blend a row's ground colours per env and frame and run the static filter on each (hill_filter_colour); the sky colours and
-        // the far colour are constants: filtered here
+        // the far colour are constants: filtered here — unless scene lighting is set, which comes first (the kernels light, then filter every colour; a flat track's
+        // LIGHT kernels read the filter from this block as well)
         const bool flt = e->has_frame_filter && !e->filter_dynamic;
         trsim::HillBlock& hb = e->hill_host;
         std::vector<uint32_t> sky(e->tab.sky);
         hb.far_rgb = e->tab.far_rgb;
         hb.filt = flt ? 1 : 0;
+        hb.light = e->light_on ? e->light : nullptr;
         if (flt) {
             const trs_pre_config& c = e->frame_filter;
-            for (auto& v : sky) v = filter_colour(c, v);
-            hb.far_rgb = filter_colour(c, hb.far_rgb);
+            if (!e->light_on) {
+                for (auto& v : sky) v = filter_colour(c, v);
+                hb.far_rgb = filter_colour(c, hb.far_rgb);
+            }
             { int rc = ensure_hsv_table(e); if (rc) return rc; }
             hb.f_color = c.color_filter_enabled; hb.f_nfilters = c.n_filters; hb.f_contrast = c.contrast_ratio; hb.f_offset = c.contrast_offset;
             for (int k = 0; k < 4; ++k) {
@@ -1895,7 +1959,7 @@ int upload_palette(trs_env* e)
             }
             hb.hsv_tab = e->hsv_tab;
         }
-        HIPCHK(hipMemcpy(e->blob_r + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
+        if (e->hilly) HIPCHK(hipMemcpy(e->blob_r + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->blob_r + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     }
     return TRS_OK;
@@ -2030,6 +2094,8 @@ TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
             const int rpp = kRasterThreads / (e->W / 4);
             if (rpp < 1 || (79 + rpp - 1) / rpp > 16) return fail(TRS_ERR_LIMIT, "image too wide for the in-kernel dynamic-brightness filter (class bits of the brightness rows live in 4 registers), use trs_preprocess");
             if (e->track_loaded && e->max_steps_dyn < 1) return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the in-kernel dynamic-brightness palette, use trs_preprocess");
+            if (e->track_loaded && e->light_on && light_max_steps(e, true) < 1)
+                return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the dynamic-brightness palettes with scene lighting, use trs_preprocess");
             // resident mode: the worker keeps its env state and hand-off ring in LDS as well — refuse HERE, with the reason, what every later
             // trs_step would otherwise refuse as "too many envs per workgroup" 
             if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits_dynamic_filter(e))
@@ -2072,6 +2138,8 @@ TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
             return fail(TRS_ERR_STATE, "the loaded track has elevation: the lens camera is built for flat tracks only (the ground plane of a hilly track tilts per env and frame)");
         if (e->has_frame_filter && e->filter_dynamic)
             return fail(TRS_ERR_STATE, "the dynamic-brightness frame filter is set: it is not built for the lens camera (trs_set_frame_filter without dynamic brightness, or NULL, first)");
+        if (e->light_on)
+            return fail(TRS_ERR_STATE, "scene lighting is set: it is not built for the lens camera (trs_set_lighting(NULL) first)");
     }
     HIPCHK(hipSetDevice(e->device));
     // nothing may be in flight, and a resident worker leaves, BEFORE anything of the camera changes (the worker's quiesce can still launch for steps
@@ -2094,6 +2162,54 @@ TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
     e->camera = nc; e->lens_on = on;
     if (!on) lens_release(e);                                // back to the pinhole: the tables are not kept
     return upload_palette(e);                                // uni_rows, the lens palette with the frame filter
+}
+
+// scene lighting (include/trsim_spec.h, "scene lighting"): register the caller's float[n_envs][8] (NULL: back to the unlit kernels)
+namespace {
+int set_lighting_impl(trs_env* e, const float* d_params, float* own)
+{
+    const bool on = d_params != nullptr;
+    if (on) {
+        const char* why = nullptr;
+        if (!e->cfg.render) why = "the env has no camera (cfg.render == 0)";
+        else if (e->lens_on) why = "a lens camera is set: scene lighting is not built for the lens camera (trs_set_camera(NULL) first)";
+        if (why) { if (own) (void)hipFree(own); return fail(TRS_ERR_STATE, why); }
+        if (e->track_loaded && light_max_steps(e, e->has_frame_filter && e->filter_dynamic) < 1) {
+            if (own) (void)hipFree(own);
+            return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lit palettes");
+        }
+        if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits_lighting(e, e->has_frame_filter && e->filter_dynamic)) {
+            if (own) (void)hipFree(own);
+            return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the lighting parameters and lit palettes: select TRS_STEP_LAUNCH");
+        }
+    }
+    // nothing may be in flight and a resident worker leaves before the kernels change (upload_palette quiesces too; the old host copy is freed after that)
+    { int rq = sync_all(e); if (rq) { if (own) (void)hipFree(own); return rq; } }
+    if (e->light_own && e->light_own != own) { (void)hipFree(e->light_own); e->light_own = nullptr; }
+    e->light_own = own;
+    e->light = d_params; e->light_on = on;
+    return upload_palette(e);                              // raw palette + the filter for the kernels, the parameters' address in the block behind the raster image
+}
+}  // namespace
+
+TRS_EXPORT int trs_set_lighting(trs_env* e, const float* d_params)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(e->device));
+    return set_lighting_impl(e, d_params, nullptr);
+}
+
+TRS_EXPORT int trs_set_lighting_host(trs_env* e, const float* h_params)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(e->device));
+    if (!h_params) return set_lighting_impl(e, nullptr, nullptr);
+    if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
+    float* own = nullptr;
+    const size_t bytes = (size_t)e->n * 8 * sizeof(float);
+    HIPCHK(hipMalloc((void**)&own, bytes));
+    if (hipMemcpy(own, h_params, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(own); return fail(TRS_ERR_DEVICE, "hipMemcpy of the lighting parameters failed"); }
+    return set_lighting_impl(e, own, own);
 }
 
 TRS_EXPORT int trs_get_camera(trs_env* e, trs_camera* out)

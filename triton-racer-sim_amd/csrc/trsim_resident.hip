@@ -492,8 +492,8 @@ __device__ __forceinline__ int wait_lds_ge(const WParams& wp, const WLds& l, Dut
     }
 }
 
-template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false>      // HILLS: a track with elevation (its own instantiations, see raster_hill_frame);
-__global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)           // LENS: the lens camera on a flat track (raster_lens_frame)
+template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false, bool LIGHT = false>   // HILLS: a track with elevation (its own instantiations, see raster_hill_frame);
+__global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)           // LENS: the lens camera on a flat track (raster_lens_frame); LIGHT: scene lighting
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool raster_team = tid < kRasterThreads;
@@ -523,6 +523,13 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
     for (int j = tid; j < 2 * epw; j += kBlock) l.pprog[j] = 0;          // pprog | rread
     int* const hbar = reinterpret_cast<int*>(smem + wp.lds_off_hill + hill_batch(p.H) * hill_table_bytes(p.H));   // (a track with elevation: the row tables' team-barrier counter)
     if (HILLS && tid == 0) *hbar = 0;
+    // scene lighting (LIGHT): a ring float[kCamDepth][epw][8] of the envs' lighting parameters beside the hand-off slots — the physics wave of an env reads them after
+    // the post (system scope) and writes them before the env's progress counter moves, so a frame uses the values of its post — then the raster waves' lit palettes
+    const int lds_off_light = (wp.lds_off_hill + (HILLS ? hill_lds_bytes(p.H) : 0) + 15) & ~15;
+    float* const lring = reinterpret_cast<float*>(smem + lds_off_light);
+    const unsigned lds_off_lpal = (unsigned)lds_off_light + (unsigned)(kCamDepth * epw * 32);
+    const float* const light_g = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->light : nullptr;
+    const int lfilt = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->filt : 0;   // (once per launch)
     if constexpr (DYN) {
         if (tid < 32) reinterpret_cast<int*>(smem + wp.fp.lds_off + kDynBatch * p.H * 16)[tid] = 0;   // channel sums, team-barrier counter
         dyn_stage_tables(smem, wp.fp, p.H, tid, kBlock, reinterpret_cast<const uint32_t*>(p.blob + p.off_pal));                   // the filter's tables, once per launch: the raster waves' steady state issues no loads
@@ -590,6 +597,10 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                                          HILLS ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes)) : nullptr);
                 if (n_loc <= TRS_PHYS_PRIO_MAX_ENVS) __builtin_amdgcn_s_setprio(0);
                 if (o.do_reset) lr = epr_before;
+                if constexpr (LIGHT) {                        // this step's lighting parameters of the env, in LDS before the counter moves (drain_lds below)
+                    const float lv = lane < 8 ? sys_load_val(&light_g[(size_t)e * 8 + lane]) : 0.f;
+                    if (lane < 8) lring[((size_t)(r & (kCamDepth - 1)) * epw + j) * 8 + lane] = lv;
+                }
                 if (lane == 0) {
                     q[0] = st.x; q[1] = st.y; q[2] = st.z; q[3] = st.yaw; q[4] = st.v; q[5] = st.sf; q[6] = st.epr;
                     q[7] = __int_as_float(st.seg); q[8] = __int_as_float(st.epl); q[9] = __int_as_float(st.done); q[10] = __int_as_float(st.pend);
@@ -720,7 +731,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                         cams[bi] = *reinterpret_cast<const float4*>(sl);
                         if ((j % (kRasterThreads / 64)) == wave) { mine_j = j; tel = __float_as_uint(sl[4 + min(lane, 12)]); }
                         asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(cams[bi].x), "v"(cams[bi].y), "v"(cams[bi].z), "v"(cams[bi].w), "v"(tel) : "memory");
-                        if (lane == 0) __hip_atomic_fetch_add(&l.rread[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (!LIGHT && lane == 0) __hip_atomic_fetch_add(&l.rread[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                 }
                 u64 t0_bar = 0;
@@ -732,7 +743,10 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     if (now - t0_bar > wp.safety_ticks) { worker_abort(wp, l, 5u); return true; }
                     return false;
                 };
-                if (!raster_dyn_batch<DEPTH>(p, wp.fp, rth, smem, cams, min(kDynBatch, n_loc - b0), img, dep, e_begin + b0, r * nbatch + b0 / kDynBatch, tid, lane, bail)) return;
+                if (!raster_dyn_batch<DEPTH, LIGHT>(p, wp.fp, rth, smem, cams, min(kDynBatch, n_loc - b0), img, dep, e_begin + b0, r * nbatch + b0 / kDynBatch, tid, lane, bail,
+                                                   LIGHT ? lring + ((size_t)(r & (kCamDepth - 1)) * epw + b0) * 8 : nullptr, lds_off_lpal)) return;
+                if (LIGHT && lane == 0)                               // (lighting: the batch's ring slots are read until its palettes are filtered)
+                    for (int bi = 0; bi < kDynBatch && b0 + bi < n_loc; ++bi) __hip_atomic_fetch_add(&l.rread[b0 + bi], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (mine_j >= 0 && !(kDiag & 2)) {                    // the step's telemetry of this wave's env of the batch (a wave owns at most one of four)
                     const size_t e = (size_t)(e_begin + mine_j);
                     if (lane < 12) __hip_atomic_store((__attribute__((address_space(1))) unsigned*)(uintptr_t)optr + e, tel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -767,7 +781,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                         Pv[bi] = sl[17];
                         if ((j % (kRasterThreads / 64)) == wave) { mine_j = j; tel = __float_as_uint(sl[4 + min(lane, 12)]); }
                         asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(cams[bi].x), "v"(cams[bi].y), "v"(cams[bi].z), "v"(cams[bi].w), "v"(tel), "v"(Pv[bi]) : "memory");
-                        if (lane == 0) __hip_atomic_fetch_add(&l.rread[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (!LIGHT && lane == 0) __hip_atomic_fetch_add(&l.rread[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                 }
                 u64 t0_bar = 0;
@@ -779,13 +793,47 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     return false;
                 };
                 const int done_before = (r * nbatch + b0 / HB) * 2 * (kRasterThreads / 64);
-                if (!hill_batch_build(p, smem, (unsigned)wp.lds_off_hill, Pv, nb, hbar, done_before, tid, lane, bail)) return;
+                if (!hill_batch_build(p, smem, (unsigned)wp.lds_off_hill, Pv, nb, hbar, done_before, tid, lane, bail,
+                                      LIGHT ? lring + ((size_t)(r & (kCamDepth - 1)) * epw + b0) * 8 : nullptr)) return;
+                if (LIGHT && lane == 0)                               // (lighting: the batch's ring slots are read until the tables are built)
+                    for (int bi = 0; bi < nb; ++bi) __hip_atomic_fetch_add(&l.rread[b0 + bi], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
                 for (int bi = 0; bi < kHillBatchMax; ++bi)
                     if (bi < nb)
                         raster_hill_frame<DEPTH>(p, rth, smem, (unsigned)wp.lds_off_hill, bi, hbar, done_before, frame_desc<DEPTH>(p, img, dep, e_begin + b0 + bi), cams[bi]);
                 if (mine_j >= 0 && !(kDiag & 2)) {                    // the step's telemetry of this wave's env of the batch (a wave owns at most one of a batch of <= 4 <= 8)
                     const size_t e = (size_t)(e_begin + mine_j);
+                    if (lane < 12) __hip_atomic_store((__attribute__((address_space(1))) unsigned*)(uintptr_t)optr + e, tel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    else if (lane < 14) __hip_atomic_store((__attribute__((address_space(1))) unsigned char*)(uintptr_t)optr + e, (unsigned char)(lane == 12 ? tel : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
+            continue;
+        }
+        if constexpr (LIGHT && !HILLS && !DYN) {
+            // Scene lighting on a flat track: an env's uniform rows need its lit palette, so the wave waits for the env's post first (the slot carries its
+            // parameters), lights its rows of the palette, then writes the frame as the non-sweep order below does — the same stores in the same order,
+            // so the counted waits of the arrivals are unchanged.
+            for (int j = 0; j < n_loc; ++j) {
+                const FrameDesc fd = frame_desc<DEPTH>(p, img, dep, e_begin + j);
+                if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, 3u, lane)) return;
+                const float* const sl = l.slot + ((size_t)(r & (kCamDepth - 1)) * epw + j) * kSlotWords;
+                const float4 cam = *reinterpret_cast<const float4*>(sl);
+                const bool mine = (j % (kRasterThreads / 64)) == wave;
+                unsigned tel = 0;
+                if (mine) tel = __float_as_uint(sl[4 + min(lane, 12)]);
+                RasterThread rl = rth;
+                rl.pal_off = light_wave_palette(p, lds_off_lpal, lring + ((size_t)(r & (kCamDepth - 1)) * epw + j) * 8, lfilt, wave, lane);
+                asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(cam.x), "v"(cam.y), "v"(cam.z), "v"(cam.w), "v"(tel) : "memory");
+                if (lane == 0) __hip_atomic_fetch_add(&l.rread[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                raster_uniform_rows<DEPTH>(p, rl, fd);
+                if (j == 0)
+                    while (s - owed >= keep) {
+                        wait_vmcnt_le((int)(s - owed - 1) * nstep + nu);
+                        raster_arrive(l, owed++, lane);
+                    }
+                raster_ground_rows<DEPTH>(p, rl, fd, cam);
+                if (mine && !(kDiag & 2)) {
+                    const size_t e = (size_t)(e_begin + j);
                     if (lane < 12) __hip_atomic_store((__attribute__((address_space(1))) unsigned*)(uintptr_t)optr + e, tel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     else if (lane < 14) __hip_atomic_store((__attribute__((address_space(1))) unsigned char*)(uintptr_t)optr + e, (unsigned char)(lane == 12 ? tel : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
@@ -1035,15 +1083,19 @@ int worker_fits(trs_env* e)
                                                         " envs): use TRS_STEP_LAUNCH with several steps per launch for shards of this size");
         return TRS_OK;
     }
-    R->lds_off_ctl = (e->lds_step + 15) & ~15;              // behind the tables
+    R->lds_off_ctl = (e->lds_step + 15) & ~15;              // behind the tables   (worker_lds_need mirrors this layout)
     R->lds_bytes = (int)(R->lds_off_ctl + wlds_bytes(e->pp.envs_per_wg) + 16);
     if (e->has_frame_filter && e->filter_dynamic) { R->lds_off_dyn = (R->lds_bytes + 15) & ~15; R->lds_bytes = R->lds_off_dyn + dyn_lds_bytes(e->H); }
     R->lds_off_hill = (R->lds_bytes + 15) & ~15;
     if (e->hilly) R->lds_bytes = R->lds_off_hill + hill_lds_bytes(e->H);   // a track with elevation: the per-env row tables (trsim_device.hpp, hill_rows_build)
     else if (e->lens_on) R->lds_bytes = R->lds_off_hill + trsim::kLensPalBytes;   // the lens camera: its palette (raster_lens_frame)
+    if (e->light_on)                                         // scene lighting: the parameter ring and (flat tracks) the lit palettes (trs_worker_kernel)
+        R->lds_bytes = ((std::max(R->lds_bytes, R->lds_off_hill) + 15) & ~15) +
+                       light_lds_extra(e->H, e->W, kCamDepth * e->pp.envs_per_wg, e->hilly, e->has_frame_filter && e->filter_dynamic);
     if (R->lds_bytes > 160 * 1024)
         return trs_internal_fail(TRS_ERR_LIMIT, e->hilly ? "the resident worker's LDS state and the per-env row tables of a track with elevation do not fit beside this track's tables: use TRS_STEP_LAUNCH"
                                                 : e->lens_on ? "the resident worker's LDS state and the lens camera's palette do not fit beside this track's tables: use TRS_STEP_LAUNCH"
+                                                : e->light_on ? "the resident worker's LDS state and the lit palettes of scene lighting do not fit beside this track's tables: use TRS_STEP_LAUNCH"
                                                             : "too many envs per workgroup for the resident worker's LDS state");
     return TRS_OK;
 }
@@ -1101,6 +1153,22 @@ int worker_launch(trs_env* e, uint64_t start)
         wp.fp.w0 = std::min(40, e->H); wp.fp.w1 = std::min(119, e->H);     // img[40:119] (img_preprocessing.py:88)
         wp.fp.tabs = e->dyn_tab;
         wp.fp.lds_off = R->lds_off_dyn;
+    }
+    if (e->light_on) {                                    // scene lighting (flat or with elevation, with the dynamic-brightness filter or not; no lens with it)
+        if (dyn) {
+            if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, true, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+            else hipLaunchKernelGGL((trs_worker_kernel<false, true, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+        } else if (e->hilly) {
+            if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+            else hipLaunchKernelGGL((trs_worker_kernel<false, false, true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+        } else {
+            if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+            else hipLaunchKernelGGL((trs_worker_kernel<false, false, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+        }
+        RCHK(hipGetLastError());
+        R->running = true;
+        R->t_launch = std::chrono::steady_clock::now();
+        return TRS_OK;
     }
     if (e->hilly) {                                       // a track with elevation (no frame filters there)
         if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
@@ -1297,12 +1365,21 @@ void resident_retry(trs_env* e)
 }
 bool resident_running(const trs_env* e) { return e && e->res && e->res->running; }
 void resident_clear_fault(trs_env* e) { if (e && e->res) e->res->broken = false; }
-bool resident_fits_dynamic_filter(const trs_env* e)
+// the render worker's LDS need (worker_fits' layout) with or without the dynamic-brightness palettes and scene lighting
+static int worker_lds_need(const trs_env* e, bool dyn, bool light)
 {
     const int off_ctl = (e->lds_step + 15) & ~15;
-    const int base = (int)(off_ctl + wlds_bytes(e->pp.envs_per_wg) + 16);
-    return ((base + 15) & ~15) + dyn_lds_bytes(e->H) <= 160 * 1024;
+    int lds = (int)(off_ctl + wlds_bytes(e->pp.envs_per_wg) + 16);
+    if (dyn) lds = ((lds + 15) & ~15) + dyn_lds_bytes(e->H);
+    const int off_hill = (lds + 15) & ~15;
+    if (e->hilly) lds = off_hill + hill_lds_bytes(e->H);
+    else if (e->lens_on) lds = off_hill + trsim::kLensPalBytes;
+    if (light) lds = ((std::max(lds, off_hill) + 15) & ~15) + light_lds_extra(e->H, e->W, kCamDepth * e->pp.envs_per_wg, e->hilly, dyn);
+    return lds;
 }
+
+bool resident_fits_dynamic_filter(const trs_env* e) { return worker_lds_need(e, true, e->light_on) <= 160 * 1024; }
+bool resident_fits_lighting(const trs_env* e, bool dyn) { return worker_lds_need(e, dyn, true) <= 160 * 1024; }
 
 int resident_post(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, size_t stride, int* n_done)
 {
@@ -1524,6 +1601,12 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_worker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (idle_us > 0) R->idle_us = (unsigned)std::min(idle_us, 1000000);
     if (!R->enabled) { R->base = R->seen_done = e->step_count; host_store(&R->mb->posted, e->step_count); }

@@ -51,6 +51,26 @@ struct LensTables {
 };
 int build_lens_tables(const trs_config& cfg, double cell, double kx, double ky, LensTables& out, std::string& err);
 
+// Scene lighting (include/trsim_spec.h, "scene lighting"): one channel value x of a raw rendered colour under gain g and bias b, binary32 with every operation
+// rounded (R1: the host and the kernels are built with -ffp-contract=off); NaN goes to 0.  gb = {gR, gG, gB, 0, bR, bG, bB, 0} (the per-env layout of
+// trs_set_lighting), colours 0x00BBGGRR.  Host and device share this code: the kernels light palette entries with it, tests/light_driver.cpp checks it.
+#if defined(__HIPCC__)
+#define TRS_HD __host__ __device__
+#else
+#define TRS_HD
+#endif
+TRS_HD inline uint32_t light_channel(uint32_t x, float g, float b)
+{
+    float t = (float)x * g;
+    t = t + b;
+    t = t + 0.5f;
+    return !(t > 0.0f) ? 0u : (t >= 255.0f ? 255u : (uint32_t)(int)t);
+}
+TRS_HD inline uint32_t light_colour(uint32_t bgr, const float* gb)
+{
+    return light_channel(bgr & 255u, gb[0], gb[4]) | (light_channel((bgr >> 8) & 255u, gb[1], gb[5]) << 8) | (light_channel((bgr >> 16) & 255u, gb[2], gb[6]) << 16);
+}
+
 // returns TRS_OK or a negative trs_status, message in `err`
 int build_tables(const trs_config& cfg, const double* xyz, int n_points, TrackTables& out, std::string& err);
 

@@ -90,6 +90,34 @@ def _stream_ptr(stream):
     return int(stream)
 
 
+def lighting_array(params, bias=None, n=None):
+    """Scene-lighting parameters as the library takes them: float32 ``[n, 8]`` = ``{gR, gG, gB, 0, bR, bG, bB, 0}`` per env, from an
+    ``[n, 8]`` array, or from gain ``[n, 3]`` and bias ``[n, 3]``."""
+    if bias is not None:
+        g, b = np.asarray(params, np.float32), np.asarray(bias, np.float32)
+        if g.ndim != 2 or g.shape[1] != 3 or b.shape != g.shape:
+            raise ValueError("gain and bias must both be [n_envs, 3]")
+        out = np.zeros((g.shape[0], 8), np.float32)
+        out[:, 0:3], out[:, 4:7] = g, b
+    else:
+        out = np.ascontiguousarray(params, np.float32)
+        if out.ndim != 2 or out.shape[1] != 8:
+            raise ValueError("lighting parameters must be [n_envs, 8] (or gain and bias [n_envs, 3] each)")
+    if n is not None and out.shape[0] != n:
+        raise ValueError(f"lighting parameters for {out.shape[0]} envs, the env has {n}")
+    return np.ascontiguousarray(out)
+
+
+def lighting_params(n, seed=0, gain=(0.6, 1.4), bias=(-30.0, 30.0), per_channel=True):
+    """Random scene lighting for domain randomisation: float32 ``[n, 8]`` with gains uniform in ``gain`` and biases uniform in ``bias``
+    (one draw per env and channel; ``per_channel=False``: one gain and one bias per env, the same on R, G and B), from ``seed``."""
+    rng = np.random.default_rng(seed)
+    k = 3 if per_channel else 1
+    g = np.broadcast_to(rng.uniform(gain[0], gain[1], (n, k)), (n, 3))
+    b = np.broadcast_to(rng.uniform(bias[0], bias[1], (n, k)), (n, 3))
+    return lighting_array(g.astype(np.float32), b.astype(np.float32))
+
+
 class BatchedEnv:
     def __init__(self, n_envs=1, track="generated_track", device=0, img_h=120, img_w=160, render=True,
                  auto_reset=False, env_id_base=0, seed=None, depth=False, camera=None, _api=None, **overrides):
@@ -347,6 +375,32 @@ class BatchedEnv:
         cam = _ffi.TrsCamera()
         self.api.check(self.api.get_camera(self._h, C.byref(cam)), "get_camera")
         return cam.fish_eye_x, cam.fish_eye_y, cam.offset_x
+
+    def set_lighting(self, params=None, bias=None):
+        """Scene lighting per env (``trs_set_lighting``; include/trsim_spec.h, "scene lighting"): a colour gain and bias per env and channel on
+        every rendered pixel, before any frame filter.  ``params``: ``None`` (unlit: frames byte for byte as before), a host array ``[n_envs, 8]``
+        (``{gR, gG, gB, 0, bR, bG, bB, 0}`` per env), or gain ``[n_envs, 3]`` with ``bias=[n_envs, 3]``, which the library copies — or a device
+        float32 ``[n_envs, 8]`` array (a torch CUDA tensor), registered zero-copy: the env keeps a reference, and values the caller rewrites
+        between steps (ordered before the step, e.g. through ``step_device(..., stream=)``) take effect at the next step without a new call.
+        Refused (``TRS_ERR_STATE``) without a camera and with a lens camera."""
+        if not getattr(self.api, "has_lighting", False):
+            raise RuntimeError("this library has no scene lighting (trs_set_lighting)")
+        if params is None:
+            self.api.check(self.api.set_lighting(self._h, None), "set_lighting")
+            self._light_ref = None
+            return
+        if is_device_array(params):
+            cai = params.__cuda_array_interface__
+            if bias is not None:
+                raise ValueError("a device array carries gain and bias together: float32 [n_envs, 8]")
+            if tuple(cai["shape"]) != (self.n, 8) or np.dtype(cai["typestr"]) != np.float32 or cai.get("strides") not in (None, (32, 4)):
+                raise ValueError(f"lighting parameters on the device must be a contiguous float32 [{self.n}, 8] array")
+            self.api.check(self.api.set_lighting(self._h, device_ptr(params)), "set_lighting")
+            self._light_ref = params
+            return
+        h = lighting_array(params, bias, self.n)
+        self.api.check(self.api.set_lighting_host(self._h, h.ctypes.data_as(C.POINTER(C.c_float))), "set_lighting_host")
+        self._light_ref = None
 
     def set_frame_filter(self, cfg=None, enabled=True):
         """``ImgPreprocessing`` fused behind the rasteriser (``trs_set_frame_filter``): from the next frame on, the
