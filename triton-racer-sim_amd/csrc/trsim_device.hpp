@@ -106,6 +106,16 @@ struct FParams {                        // ImgPreprocessing with dynamic brightn
 constexpr int kDynTabWords = 512 + 768 + 4 + 256;   // ... | cnt[256]: the class counts of a row's 4-pixel pack (n0 | n1 << 8 | n2 << 16 | n3 << 24; round 4, see raster_dyn_batch phase A)
 constexpr int kDynCntAt = 512 + 768 + 4;
 
+// Which instantiation of trs_step_kernel / trs_worker_kernel <DEPTH, DYN, HILLS, LENS, LIGHT> renders: one bit per template flag (variant_of in
+// trsim_env.hpp).  14 of the 32 are built, DEPTH x {plain, DYN, HILLS, LENS, LIGHT, LIGHT + HILLS, LIGHT + DYN}: the setters refuse the others first.
+using Variant = unsigned;
+constexpr Variant kVDepth = 1, kVDyn = 2, kVHills = 4, kVLens = 8, kVLight = 16, kVariants = 32;
+constexpr Variant variant_bits(bool depth, bool dyn, bool hills, bool lens, bool light)
+{
+    return (depth ? kVDepth : 0u) | (dyn ? kVDyn : 0u) | (hills ? kVHills : 0u) | (lens ? kVLens : 0u) | (light ? kVLight : 0u);
+}
+constexpr bool variant_built(Variant v) { return !((v & kVDyn) && (v & kVHills)) && !((v & kVLens) && (v & (kVDyn | kVHills | kVLight))); }
+
 }  // namespace trsim
 
 namespace {
@@ -128,6 +138,10 @@ using trsim::RParams;
 using trsim::FParams;
 using trsim::kDynTabWords;
 using trsim::kDynCntAt;
+using trsim::Variant;
+using trsim::kVDepth; using trsim::kVDyn; using trsim::kVHills; using trsim::kVLens; using trsim::kVLight; using trsim::kVariants;
+using trsim::variant_bits;
+using trsim::variant_built;
 
 // ---------------------------------------------------------------------------------------------
 // device pieces of the spec
@@ -1034,6 +1048,40 @@ __device__ __forceinline__ uint32_t filter_colour_dev(const FParams& f, const un
 #define DYN_STAMP(k) do { } while (0)
 #endif
 __host__ __device__ inline int dyn_lds_bytes(int H) { return kDynBatch * H * 16 + 128 + ((kDynTabWords * 4 + 15) & ~15) + H * 16; }   // ... + rowch[H]: the raw palette by channel
+
+// The step kernel's dynamic LDS behind its tables (lds_step bytes: raster image, physics image) for variant v and n_phys physics steps per launch: the one
+// layout launch_step sizes the launch and fills SParams / FParams from, and the kernel takes lds_off_pitch, lds_off_hill and lds_off_light from
+// (step_lds_behind, from SParams::lds_off_prog: the same arithmetic the kernels always did; the layout's size comes on top of it).
+//   cam:   float4 lcam[max(n_phys, 1) + 1][epw]   (the last row: the poses of the step before the launch)
+//   prog:  int pprog[epw] + 16 spare bytes
+//   pitch: float lpitch[max(n_phys, 1) + 1][epw]  (HILLS; LENS and LIGHT keep the region)
+//   hill:  (16-aligned) the batch's row tables and the raster team's barrier counter (HILLS) or the lens palette (LENS)
+//   light: (16-aligned, LIGHT) the workgroup's lighting parameters, then the lit palettes
+//   dyn:   (16-aligned, DYN) the dynamic-brightness filter's palettes, sums and tables (FParams::lds_off)
+struct StepLds { int cam, prog, pitch, hill, light, dyn, total; };
+// the region at `hill` of both kernels' layouts: the batch's row tables (HILLS) or the lens palette (LENS)
+__host__ __device__ inline int tabs_lds_bytes(int H, Variant v) { return (v & kVHills) ? hill_lds_bytes(H) : ((v & kVLens) ? trsim::kLensPalBytes : 0); }
+__host__ __device__ inline StepLds step_lds_behind(int prog, int epw, int H, Variant v, int n_phys)
+{
+    const int rows = max(n_phys, 1) + 1;
+    StepLds L;
+    L.prog = prog;
+    L.cam = prog - rows * epw * 16;
+    L.pitch = L.prog + epw * 4 + 16;
+    L.hill = (L.pitch + rows * epw * 4 + 15) & ~15;
+    L.light = (L.hill + tabs_lds_bytes(H, v) + 15) & ~15;
+    return L;
+}
+__host__ __device__ inline StepLds step_lds_layout(int lds_step, int epw, int H, int W, Variant v, int n_phys)
+{
+    StepLds L = step_lds_behind(lds_step + (max(n_phys, 1) + 1) * epw * 16, epw, H, v, n_phys);
+    int end = L.pitch;
+    if (v & (kVHills | kVLens | kVLight)) end = L.hill + tabs_lds_bytes(H, v);
+    if (v & kVLight) end = L.light + light_lds_extra(H, W, epw, (v & kVHills) != 0, (v & kVDyn) != 0);
+    L.dyn = (end + 15) & ~15;
+    L.total = (v & kVDyn) ? L.dyn + dyn_lds_bytes(H) : end;
+    return L;
+}
 // the tables behind the batch's palettes and sums (staged by dyn_stage_tables before the launch's first barrier)
 __device__ __forceinline__ unsigned* dyn_tabs_lds(unsigned char* lds_base, const FParams& f, int H) { return reinterpret_cast<unsigned*>(lds_base + f.lds_off + kDynBatch * H * 16 + 128); }
 // rowch[v] = the RAW palette of row v by channel: {R of classes 0..3, G of classes 0..3, B of classes 0..3, 0} as packed bytes (behind the tables)

@@ -3,7 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "../../include/trsim.h"
@@ -37,7 +39,6 @@ struct trs_env {
     trsim::LensTables lens;                   // host tables of the loaded map (full frame), built by lens_build
     unsigned char* lens_dev = nullptr;        // device: half-width planes F | L | D | M, then the lens palette (LensBlock points into it)
     size_t lens_pal_off = 0;                  // byte offset of the palette in lens_dev
-    int max_steps_lens = 1;                   // steps per launch that fit beside the lens palette in LDS
     // scene lighting (trs_set_lighting; include/trsim_spec.h, "scene lighting"): the LIGHT instantiations of the step kernels run while light_on
     bool light_on = false;
     const float* light = nullptr;             // the registered float[n][8]: the caller's, or light_own
@@ -61,10 +62,9 @@ struct trs_env {
     float *ctl_steer = nullptr, *ctl_thr = nullptr, *ctl_brk = nullptr;
     uint8_t* ctl_reset = nullptr;
     size_t img_bytes = 0;
-    int lds_step = 0, lds_off_phys = 0, max_steps_per_launch = 1;
+    int lds_step = 0, lds_off_phys = 0;
     float* seq_buf = nullptr; size_t seq_cap = 0;   // device copy of host control sequences (trs_step_sequence_host)
     int seq_stride = 0;                  // trs_step_sequence: n_envs while a sequence call is running, else 0
-    int max_steps_dyn = 0;               // steps per launch that still fit beside the dynamic-brightness palette (0 = it does not fit at all)
     void* pilot = nullptr;               // trsim_pilot.hip context (cnn_2d_speed_control weights + activations)
     trs_pilot_tuning pilot_tuning{}; bool has_pilot_tuning = false;   // trs_pilot_set_tuning: kernel choices of the next trs_pilot_load
     unsigned long long* fault = nullptr; // pinned host word the kernels set when they refuse to run (dynamic LDS not at offset 0)
@@ -97,8 +97,33 @@ int sync_handle(trs_env* e);                               // the handle's strea
 int quiesce_handle(trs_env* e);                            // a resident worker has left; queued work may still be running
 void comm_destroy(trs_env* e);
 bool resident_running(const trs_env* e);
-bool resident_fits_dynamic_filter(const trs_env* e);      // the worker's LDS need WITH the dynamic-brightness palettes still fits a CU (and the handle's scene lighting)
-bool resident_fits_lighting(const trs_env* e, bool dyn);  // the worker's LDS need WITH scene lighting (and the dynamic-brightness filter or not) still fits a CU
+bool resident_fits(const trs_env* e, Variant v);           // the render worker's LDS layout of variant v fits a CU beside the handle's tables
 void resident_clear_fault(trs_env* e);                     // trs_load_track puts every env on a defined state again
 int check_fault(trs_env* e);                               // TRS_ERR_DEVICE (sticky) once a kernel has reported a layout fault
+
+// the instantiation of the step kernel and of the resident worker that the handle's state selects (Variant, trsim_device.hpp)
+inline Variant variant_of(const trs_env* e)
+{
+    return variant_bits(e->rp.depth != 0, e->has_frame_filter && e->filter_dynamic, e->hilly, e->lens_on, e->light_on);
+}
+
+// the dynamic-brightness frame filter that is set, as the DYN instantiations take it (all zero without one); lds_off: its region in the kernel's LDS layout
+inline FParams fparams_of(const trs_env* e, int lds_off)
+{
+    FParams f;
+    std::memset(&f, 0, sizeof f);
+    if (!(e->has_frame_filter && e->filter_dynamic)) return f;
+    const trs_pre_config& c = e->frame_filter;
+    f.baseline = c.brightness_baseline; f.contrast = c.contrast_ratio; f.offset = c.contrast_offset;
+    f.color = c.color_filter_enabled; f.n_filters = c.n_filters;
+    for (int k = 0; k < 4; ++k) {
+        f.lo[k] = c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16);
+        f.hi[k] = c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16);
+        f.dst_ch[k] = c.dst_channel[k];
+    }
+    f.w0 = std::min(40, e->H); f.w1 = std::min(119, e->H);              // img[40:119] (img_preprocessing.py:88)
+    f.tabs = e->dyn_tab;
+    f.lds_off = lds_off;
+    return f;
+}
 }  // namespace trsim

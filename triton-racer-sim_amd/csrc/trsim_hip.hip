@@ -24,11 +24,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/trsim.h"
@@ -112,7 +114,6 @@ __global__ __launch_bounds__(kPhysBlock) void trs_physics_kernel(const PParams p
     env_store(p, e, st, lane);
 }
 
-
 template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false, bool LIGHT = false>   // HILLS: a track with elevation (its own instantiations: the flat kernels' loops do not change for it);
 __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)           // LENS: the lens camera on a flat track (likewise); LIGHT: scene lighting (flat or HILLS)
 {
@@ -136,17 +137,17 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
     int* const pprog = reinterpret_cast<int*>(smem + sp.lds_off_prog);         // [cam_stride] physics steps finished per env
     const bool rendering = sp.r_last >= sp.r_first;
     for (int j = tid; j < sp.cam_stride; j += kBlock) pprog[j] = 0;
-    // tracks with elevation (HILLS instantiations only; the host's launch_step lays the same regions out): behind the progress counters float lpitch[n_phys + 1][cam_stride]
+    // behind the progress counters (step_lds_layout, the layout the host's launch_step sized this launch by): tracks with elevation keep float lpitch[n_phys + 1][cam_stride]
     // (view pitch per step and env), then the batch's row tables and the raster team's barrier counter; the block of constants sits behind the raster image in memory
-    const int lds_off_pitch = sp.lds_off_prog + sp.cam_stride * 4 + 16;
-    const int lds_off_hill = (lds_off_pitch + (max(sp.n_phys, 1) + 1) * sp.cam_stride * 4 + 15) & ~15;
+    const StepLds lds = step_lds_behind(sp.lds_off_prog, sp.cam_stride, p.H, variant_bits(DEPTH, DYN, HILLS, LENS, LIGHT), sp.n_phys);
+    const int lds_off_pitch = lds.pitch, lds_off_hill = lds.hill;
     float* const lpitch = reinterpret_cast<float*>(smem + lds_off_pitch);
     int* const hbar = reinterpret_cast<int*>(smem + lds_off_hill + hill_batch(p.H) * hill_table_bytes(p.H));
     const trsim::HillBlock* const hill = HILLS ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes)) : nullptr;
     if (HILLS && tid == 0) *hbar = 0;
     // scene lighting (LIGHT): the workgroup's lighting parameters float[cam_stride][8], read once per launch (a call's frames all use the values as they stood when it
     // started), then the raster waves' lit palettes (light_wave_palette) — behind the row tables of a track with elevation, else where those would sit
-    const int lds_off_light = (lds_off_hill + (HILLS ? hill_lds_bytes(p.H) : 0) + 15) & ~15;
+    const int lds_off_light = lds.light;
     float* const llight = reinterpret_cast<float*>(smem + lds_off_light);
     const unsigned lds_off_lpal = (unsigned)lds_off_light + (unsigned)sp.cam_stride * 32u;
     const int lfilt = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->filt : 0;   // (once per kernel)
@@ -345,6 +346,16 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
     }
     STAMP(5);
 }
+
+// trs_step_kernel by variant bits, nullptr where none is built: the launch (launch_step) and the LDS attribute of every instantiation (trs_load_track) go through it
+using StepKernel = void (*)(SParams);
+template <Variant V> StepKernel step_kernel_of()
+{
+    if constexpr (variant_built(V)) return &trs_step_kernel<(V & kVDepth) != 0, (V & kVDyn) != 0, (V & kVHills) != 0, (V & kVLens) != 0, (V & kVLight) != 0>;
+    else return nullptr;
+}
+template <Variant... V> std::array<StepKernel, kVariants> step_kernel_table(std::integer_sequence<Variant, V...>) { return {step_kernel_of<V>()...}; }
+const std::array<StepKernel, kVariants> kStepKernels = step_kernel_table(std::make_integer_sequence<Variant, kVariants>{});
 
 #undef STAMP_STATS
 // ---------------------------------------------------------------------------------------------
@@ -1028,27 +1039,13 @@ namespace {
 
 int grid_of(const trs_env* e) { return (e->n + e->pp.envs_per_wg - 1) / e->pp.envs_per_wg; }
 
-// The step kernel's dynamic LDS for n_phys physics steps per launch: launch_step's layout (which sets the offsets), for the handle's track and frame filter and
-// with scene lighting on or off
-int step_lds_need(const trs_env* e, int n_phys, bool light, bool dyn)
+// Physics steps per launch of variant v beside lds_step bytes of tables: the largest n <= 16 whose step_lds_layout fits a CU's 160 KiB (0: not even one).
+// Every LDS refusal asks it about the variant the handle would run after the change.
+int steps_that_fit(const trs_env* e, Variant v, int lds_step)
 {
-    const int epw = e->pp.envs_per_wg;
-    int lds = e->lds_step + (std::max(n_phys, 1) + 1) * epw * 16 + epw * 4 + 16;
-    if (e->hilly || e->lens_on || light) {
-        lds = ((lds + (std::max(n_phys, 1) + 1) * epw * 4 + 15) & ~15) + (e->hilly ? hill_lds_bytes(e->H) : (e->lens_on ? trsim::kLensPalBytes : 0));
-        if (light) lds = ((lds + 15) & ~15) + light_lds_extra(e->H, e->W, epw, e->hilly, dyn);
-    }
-    if (dyn) lds = ((lds + 15) & ~15) + dyn_lds_bytes(e->H);
-    return lds;
-}
-
-// steps per launch that fit with scene lighting (0: none) for the loaded track, with or without the dynamic-brightness filter
-int light_max_steps(const trs_env* e, bool dyn)
-{
-    int k = 0;
-    for (int n = 1; n <= 16; ++n)
-        if (step_lds_need(e, n, true, dyn) <= 160 * 1024) k = n;
-    return k;
+    int n = 0;
+    while (n < 16 && step_lds_layout(lds_step, e->pp.envs_per_wg, e->H, e->W, v, n + 1).total <= 160 * 1024) ++n;
+    return n;
 }
 
 // the handle's stream is idle: a resident worker (trs_set_step_mode) is asked to leave first — it owns the stream while it runs
@@ -1071,8 +1068,11 @@ bool resident_steps(const trs_env* e) { return trsim::resident_on(e); }
 int launch_step(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth,
                 int n_phys, int r_first, int r_last, uint64_t step_base, bool keep_uniform = false)
 {
+    const Variant v = trsim::variant_of(e);
+    const StepKernel kernel = kStepKernels[v];
+    if (!kernel) return fail(TRS_ERR_STATE, "internal error: no step kernel is built for this combination of camera, track, frame filter and lighting");
     SParams sp;
-    const bool dyn = e->has_frame_filter && e->filter_dynamic;
+    const bool dyn = (v & kVDyn) != 0;
     sp.ph = e->pp;
     sp.ph.ctl_steer = st; sp.ph.ctl_thr = th; sp.ph.ctl_brk = br; sp.ph.ctl_reset = rs; sp.ph.ctl_stride = e->seq_stride;
     sp.ph.synth = synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
@@ -1083,15 +1083,8 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.step_base = (unsigned)step_base;
     sp.lds_off_phys = e->lds_off_phys;
     sp.cam_stride = e->pp.envs_per_wg;
-    sp.lds_off_cam = e->lds_step;                                                   // ring + counters sit behind the tables
-    sp.lds_off_prog = sp.lds_off_cam + (std::max(n_phys, 1) + 1) * sp.cam_stride * 16;   // + one row: poses of the step before the launch
-    int lds = sp.lds_off_prog + sp.cam_stride * 4 + 16;                            // + spare counters
-    if (e->hilly || e->lens_on || e->light_on) {                                    // a track with elevation: view pitches behind the counters, the batch's row tables, a counter
-        const int off_pitch = lds;                                                  // (= lds_off_prog + cam_stride * 4 + 16: the HILLS kernels compute the same offsets)
-        const int off_hill = (off_pitch + (std::max(n_phys, 1) + 1) * sp.cam_stride * 4 + 15) & ~15;
-        lds = off_hill + (e->hilly ? hill_lds_bytes(e->H) : (e->lens_on ? trsim::kLensPalBytes : 0));   // (the lens camera: its palette at the same offset)
-        if (e->light_on) lds = ((lds + 15) & ~15) + light_lds_extra(e->H, e->W, sp.cam_stride, e->hilly, dyn);   // scene lighting: the workgroup's parameters, the lit palettes
-    }
+    const StepLds lds = step_lds_layout(e->lds_step, sp.cam_stride, e->H, e->W, v, n_phys);   // ring + counters (+ the variant's regions) behind the tables
+    sp.lds_off_cam = lds.cam; sp.lds_off_prog = lds.prog;
     // Which frame buffers hold the CURRENT palette's uniform rows for every env (e->uniform_ok[b]): a launch that renders whole frames into a buffer makes it
     // so; a palette change (upload_palette: track, frame filter) or the dynamic-brightness filter (its uniform rows follow each frame's own mean) undoes it.
     sp.skip_uniform = 0;
@@ -1100,49 +1093,8 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
         if (keep_uniform && r_first == r_last && e->uniform_ok[b] && !dyn && !e->lens_on && !e->light_on) sp.skip_uniform = 1;
         else e->uniform_ok[b] = !dyn && !e->lens_on && !e->light_on;             // (the lens camera writes whole frames: no uniform rows; scene lighting: they follow the env's parameters)
     }
-    std::memset(&sp.fp, 0, sizeof sp.fp);
-    if (dyn) {
-        const trs_pre_config& c = e->frame_filter;
-        sp.fp.baseline = c.brightness_baseline; sp.fp.contrast = c.contrast_ratio; sp.fp.offset = c.contrast_offset;
-        sp.fp.color = c.color_filter_enabled; sp.fp.n_filters = c.n_filters;
-        for (int k = 0; k < 4; ++k) {
-            sp.fp.lo[k] = c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16);
-            sp.fp.hi[k] = c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16);
-            sp.fp.dst_ch[k] = c.dst_channel[k];
-        }
-        sp.fp.w0 = std::min(40, e->H); sp.fp.w1 = std::min(119, e->H);     // img[40:119] (img_preprocessing.py:88)
-        sp.fp.tabs = e->dyn_tab;
-        sp.fp.lds_off = (lds + 15) & ~15;
-        lds = sp.fp.lds_off + dyn_lds_bytes(e->H);                         // palettes of a batch of 4 envs + channel sums + barrier counter + the mask tables
-    }
-    const dim3 grid(grid_of(e)), block(kBlock);
-    if (e->light_on && dyn) {                               // scene lighting with the dynamic-brightness filter (flat tracks)
-        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, true, false, false, true>), grid, block, lds, e->sP, sp);
-        else hipLaunchKernelGGL((trs_step_kernel<false, true, false, false, true>), grid, block, lds, e->sP, sp);
-    } else if (e->light_on) {                               // scene lighting (flat or with elevation; no lens with it)
-        if (e->hilly) {
-            if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, true, false, true>), grid, block, lds, e->sP, sp);
-            else hipLaunchKernelGGL((trs_step_kernel<false, false, true, false, true>), grid, block, lds, e->sP, sp);
-        } else {
-            if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, false, false, true>), grid, block, lds, e->sP, sp);
-            else hipLaunchKernelGGL((trs_step_kernel<false, false, false, false, true>), grid, block, lds, e->sP, sp);
-        }
-    } else if (e->hilly) {                                         // a track with elevation (its own instantiations; the dynamic-brightness filter is refused there)
-        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, true>), grid, block, lds, e->sP, sp);
-        else hipLaunchKernelGGL((trs_step_kernel<false, false, true>), grid, block, lds, e->sP, sp);
-    } else if (e->lens_on) {                                // the lens camera (flat tracks; the dynamic-brightness filter is refused with it)
-        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false, false, true>), grid, block, lds, e->sP, sp);
-        else hipLaunchKernelGGL((trs_step_kernel<false, false, false, true>), grid, block, lds, e->sP, sp);
-    } else if (dyn) {
-        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, true>), grid, block, lds, e->sP, sp);
-        else hipLaunchKernelGGL((trs_step_kernel<false, true>), grid, block, lds, e->sP, sp);
-    } else {
-#ifndef TRS_SINGLE_VARIANT   /* A/B switch: build without the depth instantiation (HIP guide rule 19: co-compiled variants perturb each other) */
-        if (e->rp.depth) hipLaunchKernelGGL((trs_step_kernel<true, false>), grid, block, lds, e->sP, sp);
-        else
-#endif
-        hipLaunchKernelGGL((trs_step_kernel<false, false>), grid, block, lds, e->sP, sp);
-    }
+    sp.fp = trsim::fparams_of(e, lds.dyn);
+    hipLaunchKernelGGL(kernel, dim3(grid_of(e)), dim3(kBlock), lds.total, e->sP, sp);
     HIPCHK(hipGetLastError());
     return TRS_OK;
 }
@@ -1154,13 +1106,11 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
 int run_camera_steps(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, int per_launch, bool keep_uniform = false)
 {
     const uint64_t s0 = e->step_count;
-    const bool dyn_filter = e->has_frame_filter && e->filter_dynamic;
-    const int kmax = std::max(1, std::min(per_launch, e->light_on ? light_max_steps(e, dyn_filter)
-                                                                  : (dyn_filter ? e->max_steps_dyn : (e->lens_on ? e->max_steps_lens : e->max_steps_per_launch))));
     int rc = TRS_OK;
     if (n == 1) {
         rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0, keep_uniform);
     } else {
+        const int kmax = std::max(1, std::min(per_launch, steps_that_fit(e, trsim::variant_of(e), e->lds_step)));
         for (int done = 0; done < n && !rc;) {
             const int k = std::min(kmax, n - done);
             const size_t co = (size_t)done * (size_t)e->seq_stride;       // a sequence call hands each launch its own slice of controls
@@ -1335,7 +1285,7 @@ TRS_EXPORT int trs_destroy(trs_env* e)
 namespace {
 int upload_palette(trs_env* e);
 struct LensStage {                                           // lens tables built for a map but not yet the handle's (lens_stage / lens_commit)
-    unsigned char* dev = nullptr; size_t pal_off = 0; int nmax = 0; trsim::LensTables T; bool block_written = false;
+    unsigned char* dev = nullptr; size_t pal_off = 0; trsim::LensTables T; bool block_written = false;
     ~LensStage() { (void)hipFree(dev); }
 };
 int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S);
@@ -1364,7 +1314,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
         unsigned char *blob_p = nullptr, *blob_r = nullptr; float *tangent = nullptr, *start_yaw = nullptr, *dpitch = nullptr;
         ~Staged() { (void)hipFree(blob_p); (void)hipFree(blob_r); (void)hipFree(tangent); (void)hipFree(start_yaw); (void)hipFree(dpitch); }
     } nb;
-    int n_lds_r = 0, n_lds_p = 0, n_lds_step = 0, n_lds_off_phys = 0, n_pts_bytes = 0, n_max_spl = 1, n_max_dyn = 0;
+    int n_lds_r = 0, n_lds_p = 0, n_lds_step = 0, n_lds_off_phys = 0, n_pts_bytes = 0;
 
     // ---- physics LDS image: px | py | pz | tangent (when it fits) + scratch ----
     const size_t pts = align_up((size_t)n_points * 8, 16);
@@ -1442,34 +1392,12 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     k.np = n_points; r.map_w = T.info.map_w; r.map_h = T.info.map_h;
     k.map_x0f = T.map_x0f; k.map_z0f = T.map_z0f; k.inv_cellf = T.inv_cellf;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, n_lds_p));
-    {   // room left in the CU's 160 KiB for the in-launch camera ring: float4 per env per step + one counter per env
-        const int epw = k.envs_per_wg;
-        // (a track with elevation: + two per-env row tables and their counter, + 4 bytes of view pitch per env and step beside the 16 of the camera parameters)
-        const int hill_b = T.hills ? hill_lds_bytes(e->H) + 16 + epw * 4 : 0, per_step = epw * (T.hills ? 20 : 16);
-        const int free_b = 160 * 1024 - n_lds_step - epw * 4 - 16 - epw * 16 - hill_b;
-        n_max_spl = std::max(1, std::min(16, free_b / per_step));
-        const int free_dyn = free_b - (dyn_lds_bytes(e->H) + 32);
-        n_max_dyn = free_dyn >= epw * 16 ? std::min(16, free_dyn / (epw * 16)) : 0;
-        if (e->cfg.render && free_b < per_step) return fail(TRS_ERR_LIMIT, T.hills ? "no LDS left for the camera hand-off ring and the per-env row tables of a track with elevation"
-                                                                                                 : "no LDS left for the camera hand-off ring");
-        if (T.hills) n_max_dyn = 0;                              // (the dynamic-brightness filter is not available on a track with elevation)
-    }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<false, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#ifndef TRS_SINGLE_VARIANT
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_step_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
+    // room in the CU's 160 KiB for one step per launch of the camera hand-off ring (on a track with elevation: and the per-env row tables); the frame filter,
+    // the lens camera and scene lighting that are set are checked below, each with its own message
+    if (e->cfg.render && steps_that_fit(e, variant_bits(r.depth != 0, false, T.hills, false, false), n_lds_step) < 1)
+        return fail(TRS_ERR_LIMIT, T.hills ? "no LDS left for the camera hand-off ring and the per-env row tables of a track with elevation" : "no LDS left for the camera hand-off ring");
+    for (const StepKernel sk : kStepKernels)
+        if (sk) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_locate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k.blob_bytes));
     // the lens camera, when one is set: its tables for the new map (its cell size) and its LensBlock behind the NEW raster image, before anything is committed —
     // a track that leaves no LDS for the lens palette is refused like any other, and the handle keeps its track and its lens
@@ -1496,7 +1424,6 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     e->tab = std::move(T);
     e->pp = k; e->rp = r;
     e->lds_r = n_lds_r; e->lds_p = n_lds_p; e->lds_step = n_lds_step; e->lds_off_phys = n_lds_off_phys; e->pts_bytes = n_pts_bytes;
-    e->max_steps_per_launch = n_max_spl; e->max_steps_dyn = n_max_dyn;
     const trsim::TrackTables& TT = e->tab;
     // start poses (host mirror of the reset branch so that telemetry is meaningful before the first step)
     const size_t n = (size_t)e->n;
@@ -1526,12 +1453,12 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
         return fail(TRS_ERR_STATE, "this track has elevation: the dynamic-brightness frame filter that was set has been removed (a frame's palette is evaluated per env inside the kernels there; "
                                    "the static filter works, or use trs_preprocess on the rendered frames)");
     }
-    if (e->has_frame_filter && e->filter_dynamic && e->max_steps_dyn < 1) {
+    if (e->has_frame_filter && e->filter_dynamic && steps_that_fit(e, trsim::variant_of(e) & ~kVLight, e->lds_step) < 1) {   // (the filter alone; with lighting: below)
         e->has_frame_filter = false; e->filter_dynamic = false;
         (void)upload_palette(e);
         return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the dynamic-brightness frame filter that was set: the filter has been removed");
     }
-    if (e->light_on && light_max_steps(e, e->has_frame_filter && e->filter_dynamic) < 1) {   // (e->hilly, e->lds_step: the new track's)
+    if (e->light_on && steps_that_fit(e, trsim::variant_of(e), e->lds_step) < 1) {   // (e->hilly, e->lds_step: the new track's)
         e->light_on = false; e->light = nullptr;
         (void)upload_palette(e);
         return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the scene lighting that was set: lighting has been removed");
@@ -1971,13 +1898,9 @@ int upload_palette(trs_env* e)
 // `lds_step` / `cell`: the step kernel's LDS image and the map cell of the track the tables are for.
 int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S)
 {
-    const int epw = e->pp.envs_per_wg;
-    // launch_step's layout with the lens palette where a hilly track keeps its row tables: lds_step + (n + 1) * epw * (16 + 4) + epw * 4 + 16 (+ 15 alignment) + the palette
-    const int room = 160 * 1024 - lds_step - epw * 4 - 16 - 15 - trsim::kLensPalBytes;
-    const int nmax = std::min(16, room / (epw * 20) - 1);
-    if (nmax < 1)
+    if (steps_that_fit(e, variant_bits(e->rp.depth != 0, false, false, true, false), lds_step) < 1)   // (a lens excludes the other variants)
         return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lens camera's palette (" + std::to_string(lds_step) + " B of tables at " +
-                                   std::to_string(epw) + " envs per workgroup): the lens camera needs a shorter track or fewer envs per GPU");
+                                   std::to_string(e->pp.envs_per_wg) + " envs per workgroup): the lens camera needs a shorter track or fewer envs per GPU");
     std::string err;
     int rc = trsim::build_lens_tables(e->cfg, cell, cam.fish_eye_x, cam.fish_eye_y, S.T, err);
     if (rc) return fail(rc, err);
@@ -2013,7 +1936,7 @@ int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cel
     lb.wh = wh;
     S.block_written = true;                                  // (from here on the slot in blob_r may hold a partial block when the copy fails)
     HIPCHK(hipMemcpy(blob_r + trsim::lens_block_offset(blob_bytes), &lb, sizeof lb, hipMemcpyHostToDevice));
-    S.pal_off = off_pal; S.nmax = nmax;
+    S.pal_off = off_pal;
     return TRS_OK;
 }
 
@@ -2022,14 +1945,14 @@ void lens_commit(trs_env* e, LensStage& S)
 {
     (void)hipFree(e->lens_dev);
     e->lens_dev = S.dev; S.dev = nullptr;
-    e->lens_pal_off = S.pal_off; e->lens = std::move(S.T); e->max_steps_lens = S.nmax;
+    e->lens_pal_off = S.pal_off; e->lens = std::move(S.T);
 }
 
 // back to the pinhole camera: the lens tables are freed (nothing may be in flight)
 void lens_release(trs_env* e)
 {
     (void)hipFree(e->lens_dev);
-    e->lens_dev = nullptr; e->lens_pal_off = 0; e->lens = trsim::LensTables{}; e->max_steps_lens = 1;
+    e->lens_dev = nullptr; e->lens_pal_off = 0; e->lens = trsim::LensTables{};
 }
 
 int ensure_tmp(trs_env* e, size_t frames)
@@ -2093,12 +2016,14 @@ TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
         if (c->dynamic_brightness) {
             const int rpp = kRasterThreads / (e->W / 4);
             if (rpp < 1 || (79 + rpp - 1) / rpp > 16) return fail(TRS_ERR_LIMIT, "image too wide for the in-kernel dynamic-brightness filter (class bits of the brightness rows live in 4 registers), use trs_preprocess");
-            if (e->track_loaded && e->max_steps_dyn < 1) return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the in-kernel dynamic-brightness palette, use trs_preprocess");
-            if (e->track_loaded && e->light_on && light_max_steps(e, true) < 1)
+            const Variant v = trsim::variant_of(e) | kVDyn;       // what the handle runs with this filter: checked without, then with, its scene lighting
+            if (e->track_loaded && steps_that_fit(e, v & ~kVLight, e->lds_step) < 1)
+                return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the in-kernel dynamic-brightness palette, use trs_preprocess");
+            if (e->track_loaded && e->light_on && steps_that_fit(e, v, e->lds_step) < 1)
                 return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the dynamic-brightness palettes with scene lighting, use trs_preprocess");
             // resident mode: the worker keeps its env state and hand-off ring in LDS as well — refuse HERE, with the reason, what every later
             // trs_step would otherwise refuse as "too many envs per workgroup" 
-            if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits_dynamic_filter(e))
+            if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits(e, v))
                 return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the dynamic-brightness palettes of a batch: "
                                            "select TRS_STEP_LAUNCH for this filter, or use trs_preprocess");
         }
@@ -2174,11 +2099,12 @@ int set_lighting_impl(trs_env* e, const float* d_params, float* own)
         if (!e->cfg.render) why = "the env has no camera (cfg.render == 0)";
         else if (e->lens_on) why = "a lens camera is set: scene lighting is not built for the lens camera (trs_set_camera(NULL) first)";
         if (why) { if (own) (void)hipFree(own); return fail(TRS_ERR_STATE, why); }
-        if (e->track_loaded && light_max_steps(e, e->has_frame_filter && e->filter_dynamic) < 1) {
+        const Variant v = trsim::variant_of(e) | kVLight;     // what the handle runs with lighting
+        if (e->track_loaded && steps_that_fit(e, v, e->lds_step) < 1) {
             if (own) (void)hipFree(own);
             return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lit palettes");
         }
-        if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits_lighting(e, e->has_frame_filter && e->filter_dynamic)) {
+        if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits(e, v)) {
             if (own) (void)hipFree(own);
             return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the lighting parameters and lit palettes: select TRS_STEP_LAUNCH");
         }

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -35,6 +36,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
 
 #include "../../include/trsim.h"
 #include "../../include/trsim_spec.h"
@@ -231,6 +233,28 @@ __device__ __forceinline__ WLds wlds_of(unsigned char* base, int epw)
 __host__ __device__ inline size_t wlds_bytes(int epw)
 {
     return wlds_slot_off(epw) + (size_t)kCamDepth * epw * kSlotWords * 4 + (size_t)epw * 64;
+}
+
+// The render worker's dynamic LDS behind the tables (lds_step bytes) for variant v: the one layout worker_fits sizes the launch by and fills WParams
+// from; the kernel takes lds_off_light from its last step (worker_lds_light, from WParams::lds_off_hill).
+//   ctl:   the control block (WLds) + 16 spare bytes
+//   dyn:   (16-aligned, DYN) the dynamic-brightness filter's palettes, sums and tables (FParams::lds_off)
+//   hill:  (16-aligned) the batch's row tables and the raster team's barrier counter (HILLS) or the lens palette (LENS)
+//   light: (16-aligned, LIGHT) the ring of lighting parameters float[kCamDepth][epw][8], then the lit palettes
+struct WorkerLds { int ctl, dyn, hill, light, total; };
+__host__ __device__ inline int worker_lds_light(int hill, int H, Variant v) { return (hill + tabs_lds_bytes(H, v) + 15) & ~15; }
+__host__ __device__ inline WorkerLds worker_lds_layout(int lds_step, int epw, int H, int W, Variant v)
+{
+    WorkerLds L;
+    L.ctl = (lds_step + 15) & ~15;
+    int end = (int)(L.ctl + wlds_bytes(epw) + 16);
+    L.dyn = (end + 15) & ~15;
+    if (v & kVDyn) end = L.dyn + dyn_lds_bytes(H);
+    L.hill = (end + 15) & ~15;
+    if (v & (kVHills | kVLens)) end = L.hill + tabs_lds_bytes(H, v);
+    L.light = worker_lds_light(L.hill, H, v);
+    L.total = (v & kVLight) ? L.light + light_lds_extra(H, W, kCamDepth * epw, (v & kVHills) != 0, (v & kVDyn) != 0) : end;
+    return L;
 }
 
 // a bounded wait gave up: tell the host, every workgroup (device word) and this workgroup (LDS word)
@@ -525,7 +549,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
     if (HILLS && tid == 0) *hbar = 0;
     // scene lighting (LIGHT): a ring float[kCamDepth][epw][8] of the envs' lighting parameters beside the hand-off slots — the physics wave of an env reads them after
     // the post (system scope) and writes them before the env's progress counter moves, so a frame uses the values of its post — then the raster waves' lit palettes
-    const int lds_off_light = (wp.lds_off_hill + (HILLS ? hill_lds_bytes(p.H) : 0) + 15) & ~15;
+    const int lds_off_light = worker_lds_light(wp.lds_off_hill, p.H, variant_bits(DEPTH, DYN, HILLS, LENS, LIGHT));   // (worker_lds_layout)
     float* const lring = reinterpret_cast<float*>(smem + lds_off_light);
     const unsigned lds_off_lpal = (unsigned)lds_off_light + (unsigned)(kCamDepth * epw * 32);
     const float* const light_g = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->light : nullptr;
@@ -874,6 +898,16 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
     }
 }
 
+// trs_worker_kernel by variant bits, nullptr where none is built: the launch (worker_launch) and the LDS attribute of every instantiation (trs_set_step_mode) go through it
+using WorkerKernel = void (*)(WParams);
+template <Variant V> WorkerKernel worker_kernel_of()
+{
+    if constexpr (variant_built(V)) return &trs_worker_kernel<(V & kVDepth) != 0, (V & kVDyn) != 0, (V & kVHills) != 0, (V & kVLens) != 0, (V & kVLight) != 0>;
+    else return nullptr;
+}
+template <Variant... V> std::array<WorkerKernel, kVariants> worker_kernel_table(std::integer_sequence<Variant, V...>) { return {worker_kernel_of<V>()...}; }
+const std::array<WorkerKernel, kVariants> kWorkerKernels = worker_kernel_table(std::make_integer_sequence<Variant, kVariants>{});
+
 // ---- physics-only envs (cfg.render == 0, BASELINE configs[1]): the consumer-paced step without a launch per step -------------------
 // The same mailbox, device ring, arrival counters and exit protocol as trs_worker_kernel, on the geometry of trs_physics_kernel: one env
 // per wave, four envs per workgroup, the 38 KB track image staged once.  A workgroup has two more waves that own no env:
@@ -1083,15 +1117,8 @@ int worker_fits(trs_env* e)
                                                         " envs): use TRS_STEP_LAUNCH with several steps per launch for shards of this size");
         return TRS_OK;
     }
-    R->lds_off_ctl = (e->lds_step + 15) & ~15;              // behind the tables   (worker_lds_need mirrors this layout)
-    R->lds_bytes = (int)(R->lds_off_ctl + wlds_bytes(e->pp.envs_per_wg) + 16);
-    if (e->has_frame_filter && e->filter_dynamic) { R->lds_off_dyn = (R->lds_bytes + 15) & ~15; R->lds_bytes = R->lds_off_dyn + dyn_lds_bytes(e->H); }
-    R->lds_off_hill = (R->lds_bytes + 15) & ~15;
-    if (e->hilly) R->lds_bytes = R->lds_off_hill + hill_lds_bytes(e->H);   // a track with elevation: the per-env row tables (trsim_device.hpp, hill_rows_build)
-    else if (e->lens_on) R->lds_bytes = R->lds_off_hill + trsim::kLensPalBytes;   // the lens camera: its palette (raster_lens_frame)
-    if (e->light_on)                                         // scene lighting: the parameter ring and (flat tracks) the lit palettes (trs_worker_kernel)
-        R->lds_bytes = ((std::max(R->lds_bytes, R->lds_off_hill) + 15) & ~15) +
-                       light_lds_extra(e->H, e->W, kCamDepth * e->pp.envs_per_wg, e->hilly, e->has_frame_filter && e->filter_dynamic);
+    const WorkerLds L = worker_lds_layout(e->lds_step, e->pp.envs_per_wg, e->H, e->W, variant_of(e));   // behind the tables
+    R->lds_off_ctl = L.ctl; R->lds_off_dyn = L.dyn; R->lds_off_hill = L.hill; R->lds_bytes = L.total;
     if (R->lds_bytes > 160 * 1024)
         return trs_internal_fail(TRS_ERR_LIMIT, e->hilly ? "the resident worker's LDS state and the per-env row tables of a track with elevation do not fit beside this track's tables: use TRS_STEP_LAUNCH"
                                                 : e->lens_on ? "the resident worker's LDS state and the lens camera's palette do not fit beside this track's tables: use TRS_STEP_LAUNCH"
@@ -1107,6 +1134,9 @@ int worker_launch(trs_env* e, uint64_t start)
     Resident* R = e->res;
     Mailbox* mb = R->mb;
     { int rc = worker_fits(e); if (rc) return rc; }
+    const WorkerKernel kernel = e->cfg.render ? kWorkerKernels[variant_of(e)] : nullptr;
+    if (e->cfg.render && !kernel)
+        return trs_internal_fail(TRS_ERR_STATE, "internal error: no resident worker is built for this combination of camera, track, frame filter and lighting");
     {   // one worker per GPU: the worker of another handle of this process leaves first (the caller holds the device's lock)
         DeviceSlot& D = slot_of(e);
         trs_env* const other = D.owner;
@@ -1133,63 +1163,12 @@ int worker_launch(trs_env* e, uint64_t start)
     // (handle_exit): the set-up then sits in the stream's idle time instead of in front of every launch (~4 us per worker start)
     if (!(R->dc_ready && R->dc_ready_for == start)) hipLaunchKernelGGL(trs_worker_init_kernel, dim3(1), dim3(256), 0, e->sP, R->dc, (u64)start);
     R->dc_ready = false;
-    if (!e->cfg.render) {
+    if (e->cfg.render) {
+        wp.fp = fparams_of(e, R->lds_off_dyn);              // (the DYN instantiations: what trs_step_kernel's get, trsim_hip.hip launch_step)
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
+    } else {
         hipLaunchKernelGGL(trs_physics_worker_kernel, dim3(grid), dim3(kPwBlock), R->lds_bytes, e->sP, wp);
-        RCHK(hipGetLastError());
-        R->running = true;
-        R->t_launch = std::chrono::steady_clock::now();
-        return TRS_OK;
     }
-    const bool dyn = e->has_frame_filter && e->filter_dynamic;
-    if (dyn) {                                              // the fields trs_step_kernel's DYN instantiation gets (trsim_hip.hip, launch_step)
-        const trs_pre_config& c = e->frame_filter;
-        wp.fp.baseline = c.brightness_baseline; wp.fp.contrast = c.contrast_ratio; wp.fp.offset = c.contrast_offset;
-        wp.fp.color = c.color_filter_enabled; wp.fp.n_filters = c.n_filters;
-        for (int k = 0; k < 4; ++k) {
-            wp.fp.lo[k] = c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16);
-            wp.fp.hi[k] = c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16);
-            wp.fp.dst_ch[k] = c.dst_channel[k];
-        }
-        wp.fp.w0 = std::min(40, e->H); wp.fp.w1 = std::min(119, e->H);     // img[40:119] (img_preprocessing.py:88)
-        wp.fp.tabs = e->dyn_tab;
-        wp.fp.lds_off = R->lds_off_dyn;
-    }
-    if (e->light_on) {                                    // scene lighting (flat or with elevation, with the dynamic-brightness filter or not; no lens with it)
-        if (dyn) {
-            if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, true, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-            else hipLaunchKernelGGL((trs_worker_kernel<false, true, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        } else if (e->hilly) {
-            if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-            else hipLaunchKernelGGL((trs_worker_kernel<false, false, true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        } else {
-            if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-            else hipLaunchKernelGGL((trs_worker_kernel<false, false, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        }
-        RCHK(hipGetLastError());
-        R->running = true;
-        R->t_launch = std::chrono::steady_clock::now();
-        return TRS_OK;
-    }
-    if (e->hilly) {                                       // a track with elevation (no frame filters there)
-        if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        else hipLaunchKernelGGL((trs_worker_kernel<false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        RCHK(hipGetLastError());
-        R->running = true;
-        R->t_launch = std::chrono::steady_clock::now();
-        return TRS_OK;
-    }
-    if (e->lens_on) {                                     // the lens camera (flat tracks; the dynamic-brightness filter is refused with it)
-        if (e->rp.depth) hipLaunchKernelGGL((trs_worker_kernel<true, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        else hipLaunchKernelGGL((trs_worker_kernel<false, false, false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-        RCHK(hipGetLastError());
-        R->running = true;
-        R->t_launch = std::chrono::steady_clock::now();
-        return TRS_OK;
-    }
-    if (e->rp.depth) { if (dyn) hipLaunchKernelGGL((trs_worker_kernel<true, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-                       else hipLaunchKernelGGL((trs_worker_kernel<true, false>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp); }
-    else { if (dyn) hipLaunchKernelGGL((trs_worker_kernel<false, true>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp);
-           else hipLaunchKernelGGL((trs_worker_kernel<false, false>), dim3(grid), dim3(kBlock), R->lds_bytes, e->sP, wp); }
     RCHK(hipGetLastError());
     R->running = true;
     R->t_launch = std::chrono::steady_clock::now();
@@ -1365,21 +1344,7 @@ void resident_retry(trs_env* e)
 }
 bool resident_running(const trs_env* e) { return e && e->res && e->res->running; }
 void resident_clear_fault(trs_env* e) { if (e && e->res) e->res->broken = false; }
-// the render worker's LDS need (worker_fits' layout) with or without the dynamic-brightness palettes and scene lighting
-static int worker_lds_need(const trs_env* e, bool dyn, bool light)
-{
-    const int off_ctl = (e->lds_step + 15) & ~15;
-    int lds = (int)(off_ctl + wlds_bytes(e->pp.envs_per_wg) + 16);
-    if (dyn) lds = ((lds + 15) & ~15) + dyn_lds_bytes(e->H);
-    const int off_hill = (lds + 15) & ~15;
-    if (e->hilly) lds = off_hill + hill_lds_bytes(e->H);
-    else if (e->lens_on) lds = off_hill + trsim::kLensPalBytes;
-    if (light) lds = ((std::max(lds, off_hill) + 15) & ~15) + light_lds_extra(e->H, e->W, kCamDepth * e->pp.envs_per_wg, e->hilly, dyn);
-    return lds;
-}
-
-bool resident_fits_dynamic_filter(const trs_env* e) { return worker_lds_need(e, true, e->light_on) <= 160 * 1024; }
-bool resident_fits_lighting(const trs_env* e, bool dyn) { return worker_lds_need(e, dyn, true) <= 160 * 1024; }
+bool resident_fits(const trs_env* e, Variant v) { return worker_lds_layout(e->lds_step, e->pp.envs_per_wg, e->H, e->W, v).total <= 160 * 1024; }
 
 int resident_post(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, size_t stride, int* n_done)
 {
@@ -1593,20 +1558,8 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
     if (rc) return rc;
     Resident* R = e->res;
     { int rf = worker_fits(e); if (rf) return rf; }
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<false, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_worker_kernel<true, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const WorkerKernel wk : kWorkerKernels)
+        if (wk) RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_worker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (idle_us > 0) R->idle_us = (unsigned)std::min(idle_us, 1000000);
     if (!R->enabled) { R->base = R->seen_done = e->step_count; host_store(&R->mb->posted, e->step_count); }
