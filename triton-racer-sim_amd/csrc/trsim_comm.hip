@@ -43,7 +43,7 @@ struct RcclApi {
 struct Comm {
     int rank = 0, world = 1;
     void* nccl = nullptr;                // ncclComm_t; nullptr at world size 1 (the gather is a copy)
-    float* gathered = nullptr;           // device [world * n_envs]
+    DevBuf<float> gathered;              // device [world * n_envs]
 };
 
 }  // namespace trsim
@@ -109,8 +109,7 @@ void comm_destroy(trs_env* e)
     Comm* c = e->comm;
     if (!c) return;
     if (c->nccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->nccl);
-    (void)hipFree(c->gathered);
-    delete c;
+    delete c;                                                // (its buffer goes after the communicator that used it)
     e->comm = nullptr;
 }
 
@@ -139,7 +138,7 @@ TRS_EXPORT int trs_comm_init(trs_env* e, int rank, int world, const void* unique
     if (!c) return trs_internal_fail(TRS_ERR_NOMEM, "out of memory");
     e->comm = c;
     c->rank = rank; c->world = world;
-    if (hipMalloc((void**)&c->gathered, (size_t)world * e->n * sizeof(float)) != hipSuccess) { comm_destroy(e); return trs_internal_fail(TRS_ERR_NOMEM, "out of device memory"); }
+    if (c->gathered.alloc((size_t)world * e->n * sizeof(float)) != hipSuccess) { comm_destroy(e); return trs_internal_fail(TRS_ERR_NOMEM, "out of device memory"); }
     if (unique_id) {                                         // also at world size 1 when an id is given: the RCCL path itself is exercised
         if (!load_rccl()) { comm_destroy(e); return trs_internal_fail(TRS_ERR_DEVICE, g_rccl_err); }
         RcclId id;
@@ -168,14 +167,14 @@ TRS_EXPORT int trs_allgather_returns(trs_env* e, const float** d_out_all, float*
     Comm* c = e->comm;
     const size_t n = (size_t)e->n;
     if (c->nccl) {
-        const int rc = g_rccl.AllGather(e->pp.ep_return, c->gathered, n, kNcclFloat32, c->nccl, e->sP);
+        const int rc = g_rccl.AllGather(e->pp.ep_return, c->gathered.get(), n, kNcclFloat32, c->nccl, e->sP);
         if (rc) return rccl_fail("ncclAllGather", rc);
     } else {
-        CCHK(hipMemcpyAsync(c->gathered, e->pp.ep_return, n * sizeof(float), hipMemcpyDeviceToDevice, e->sP));
+        CCHK(hipMemcpyAsync(c->gathered.get(), e->pp.ep_return, n * sizeof(float), hipMemcpyDeviceToDevice, e->sP));
     }
-    if (d_out_all) *d_out_all = c->gathered;
+    if (d_out_all) *d_out_all = c->gathered.get();
     if (h_out_all) {
-        CCHK(hipMemcpyAsync(h_out_all, c->gathered, (size_t)c->world * n * sizeof(float), hipMemcpyDeviceToHost, e->sP));
+        CCHK(hipMemcpyAsync(h_out_all, c->gathered.get(), (size_t)c->world * n * sizeof(float), hipMemcpyDeviceToHost, e->sP));
         CCHK(hipStreamSynchronize(e->sP));
         return check_fault(e);
     }

@@ -10,6 +10,7 @@
 
 #include "../../include/trsim.h"
 #include "trsim_device.hpp"
+#include "trsim_mem.hpp"
 #include "trsim_tables.hpp"
 
 namespace trsim { struct Resident; struct Comm; }
@@ -19,57 +20,56 @@ struct trs_env {
     int device = 0, n = 0, H = 0, W = 0, cu_count = 0;
     hipStream_t sP = nullptr;            // the handle's stream: every launch, copy and timing event
     hipEvent_t ev[8] = {};
-    // device memory
-    unsigned char* slab = nullptr;       // state + controls
-    uint8_t* img[2] = {nullptr, nullptr};
+    // Memory the library allocates is held by DevBuf / PinnedBuf members (trsim_mem.hpp) and goes with the handle; raw pointers below are views.
+    trsim::DevBuf<> slab;                // state + controls
+    trsim::DevBuf<uint8_t> img[2];
     bool uniform_ok[2] = {false, false}; // frame buffer b holds the current palette's uniform rows (sky, beyond the far plane) of every env (launch_step)
-    float* depth[2] = {nullptr, nullptr};
-    unsigned char* blob_p = nullptr;     // physics LDS image
-    unsigned char* blob_r = nullptr;     // raster LDS image
-    float* tangent = nullptr;
-    float* start_yaw = nullptr;
-    float4* cam = nullptr;               // [kRing][n]
-    float* cam_pitch = nullptr;          // [kRing][n] the frames' view pitches (tracks with elevation)
-    float* dpitch = nullptr;             // [n_points] view pitch per raw track point (device: (float)pitch + dpitch[i])
+    trsim::DevBuf<float> depth[2];
+    trsim::DevBuf<> blob_p;              // physics LDS image
+    trsim::DevBuf<> blob_r;              // raster LDS image
+    trsim::DevBuf<float> tangent, start_yaw;
+    trsim::DevBuf<float4> cam;           // [kRing][n]
+    trsim::DevBuf<float> cam_pitch;      // [kRing][n] the frames' view pitches (tracks with elevation)
+    trsim::DevBuf<float> dpitch;         // [n_points] view pitch per raw track point (device: (float)pitch + dpitch[i])
     bool hilly = false;                       // the loaded track has elevation (include/trsim_spec.h): the HILLS instantiations of the step kernels run
     trsim::HillBlock hill_host{};             // host copy of the block behind the raster image (trs_load_track fills the camera part, upload_palette the frame filter)
     // the lens camera (trs_set_camera; include/trsim_spec.h, "lens camera"): the LENS instantiations of the step kernels run while lens_on
     trs_camera camera{};                      // what trs_set_camera set (all zero: the pinhole)
     bool lens_on = false;
     trsim::LensTables lens;                   // host tables of the loaded map (full frame), built by lens_build
-    unsigned char* lens_dev = nullptr;        // device: half-width planes F | L | D | M, then the lens palette (LensBlock points into it)
+    trsim::DevBuf<> lens_dev;                 // device: half-width planes F | L | D | M, then the lens palette (LensBlock points into it)
     size_t lens_pal_off = 0;                  // byte offset of the palette in lens_dev
     // scene lighting (trs_set_lighting; include/trsim_spec.h, "scene lighting"): the LIGHT instantiations of the step kernels run while light_on
     bool light_on = false;
-    const float* light = nullptr;             // the registered float[n][8]: the caller's, or light_own
-    float* light_own = nullptr;               // trs_set_lighting_host's copy (owned by the handle)
-    unsigned long long* stats = nullptr;
-    double* loc_q = nullptr; int32_t* loc_out = nullptr; int loc_cap = 0;
-    uint8_t* pre = nullptr;              // processed frames of the env (trs_preprocess with d_dst == NULL)
+    const float* light = nullptr;             // view: the registered float[n][8], the caller's or light_own's
+    trsim::DevBuf<float> light_own;           // trs_set_lighting_host's copy
+    trsim::DevBuf<unsigned long long> stats;
+    trsim::DevBuf<double> loc_q; trsim::DevBuf<int32_t> loc_out; int loc_cap = 0;   // trs_locate: room for loc_cap queries
+    trsim::DevBuf<uint8_t> pre;          // processed frames of the env (trs_preprocess with d_dst == NULL)
     trs_pre_config frame_filter{}; bool has_frame_filter = false, filter_dynamic = false;   // trs_set_frame_filter
-    unsigned char* pinned = nullptr; size_t pinned_bytes = 0;   // trs_fetch_outputs staging (hipHostMalloc)
-    int32_t* mux_state = nullptr; int mux_tick = 0;   // ControlMultiplexer state per car (trs_control_mux)
-    uint8_t *tmp_in = nullptr, *tmp_out = nullptr; float* tmp_f = nullptr; size_t tmp_cap = 0;   // host-frame staging
-    int* hsv_tab = nullptr;
-    unsigned* dyn_tab = nullptr;        // FParams::tabs of the dynamic-brightness frame filter that is set (hsv reciprocals | in-range byte masks | sel)
-    unsigned char* edge_scratch = nullptr; size_t edge_scratch_bytes = 0;   // work arrays of the Canny layer for frames beyond LDS
+    trsim::PinnedBuf<> pinned;           // trs_fetch_outputs staging
+    trsim::DevBuf<int32_t> mux_state; int mux_tick = 0;   // ControlMultiplexer state per car (trs_control_mux)
+    trsim::DevBuf<uint8_t> tmp_in, tmp_out; trsim::DevBuf<float> tmp_f; size_t tmp_cap = 0;   // host-frame staging with room for tmp_cap frames
+    trsim::DevBuf<int> hsv_tab;
+    trsim::DevBuf<unsigned> dyn_tab;    // FParams::tabs of the dynamic-brightness frame filter that is set (hsv reciprocals | in-range byte masks | sel)
+    trsim::DevBuf<> edge_scratch;        // work arrays of the Canny layer for frames beyond LDS
     trsim::PParams pp{};
     trsim::RParams rp{};
     trsim::TrackTables tab;
     bool track_loaded = false;
     int lds_p = 0, lds_r = 0, pts_bytes = 0;
     uint64_t step_count = 0;
-    float *ctl_steer = nullptr, *ctl_thr = nullptr, *ctl_brk = nullptr;
+    float *ctl_steer = nullptr, *ctl_thr = nullptr, *ctl_brk = nullptr;   // views into slab, like the state arrays in pp
     uint8_t* ctl_reset = nullptr;
     size_t img_bytes = 0;
     int lds_step = 0, lds_off_phys = 0;
-    float* seq_buf = nullptr; size_t seq_cap = 0;   // device copy of host control sequences (trs_step_sequence_host)
+    trsim::DevBuf<float> seq_buf;        // device copy of host control sequences (trs_step_sequence_host)
     int seq_stride = 0;                  // trs_step_sequence: n_envs while a sequence call is running, else 0
-    void* pilot = nullptr;               // trsim_pilot.hip context (cnn_2d_speed_control weights + activations)
+    void* pilot = nullptr;               // trsim_pilot.hip context (cnn_2d_speed_control weights + activations), released by trs_pilot_free
     trs_pilot_tuning pilot_tuning{}; bool has_pilot_tuning = false;   // trs_pilot_set_tuning: kernel choices of the next trs_pilot_load
-    unsigned long long* fault = nullptr; // pinned host word the kernels set when they refuse to run (dynamic LDS not at offset 0)
-    float* glue = nullptr; size_t glue_bytes = 0;   // device scratch of the *_host control glue (trs_driver_assist_host, trs_control_mux_host)
-    void* scratch[32] = {}; size_t scratch_bytes[32] = {};   // trs_scratch
+    trsim::PinnedBuf<unsigned long long> fault;   // pinned host word the kernels set when they refuse to run (dynamic LDS not at offset 0)
+    trsim::DevBuf<float> glue;           // device scratch of the *_host control glue (trs_driver_assist_host, trs_control_mux_host)
+    trsim::DevBuf<void> scratch[32];     // trs_scratch
     uint64_t d2h_bytes = 0, h2d_bytes = 0;                  // trs_counters: what the library itself copied
     trsim::Comm* comm = nullptr;         // trsim_comm.hip: the RCCL communicator of trs_comm_init, nullptr = none
     hipEvent_t ev_order = nullptr;       // trs_stream_wait_external / trs_stream_signal_external
@@ -122,7 +122,7 @@ inline FParams fparams_of(const trs_env* e, int lds_off)
         f.dst_ch[k] = c.dst_channel[k];
     }
     f.w0 = std::min(40, e->H); f.w1 = std::min(119, e->H);              // img[40:119] (img_preprocessing.py:88)
-    f.tabs = e->dyn_tab;
+    f.tabs = e->dyn_tab.get();
     f.lds_off = lds_off;
     return f;
 }

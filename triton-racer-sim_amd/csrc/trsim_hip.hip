@@ -1077,8 +1077,8 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.ph.ctl_steer = st; sp.ph.ctl_thr = th; sp.ph.ctl_brk = br; sp.ph.ctl_reset = rs; sp.ph.ctl_stride = e->seq_stride;
     sp.ph.synth = synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
     sp.ra = e->rp;
-    sp.img0 = e->img[0]; sp.img1 = e->img[1];
-    sp.dep0 = e->depth[0]; sp.dep1 = e->depth[1];
+    sp.img0 = e->img[0].get(); sp.img1 = e->img[1].get();
+    sp.dep0 = e->depth[0].get(); sp.dep1 = e->depth[1].get();
     sp.n_phys = n_phys; sp.r_first = r_first; sp.r_last = r_last;
     sp.step_base = (unsigned)step_base;
     sp.lds_off_phys = e->lds_off_phys;
@@ -1184,9 +1184,9 @@ int create_impl(const trs_config* cfg, int device, trs_env* e)
     // one slab for all per-env arrays: 10 float + 2 int32 state arrays, 3 float + 1 byte control arrays, 2 byte flags
     const size_t n = (size_t)e->n, fa = align_up(n * 4, 256), ba = align_up(n, 256);
     const size_t slab_bytes = fa * (10 + 2 + 3) + ba * 3;
-    HIPCHK(hipMalloc((void**)&e->slab, slab_bytes));
-    HIPCHK(hipMemsetAsync(e->slab, 0, slab_bytes, e->sP));
-    unsigned char* c = e->slab;
+    HIPCHK(e->slab.alloc(slab_bytes));
+    HIPCHK(hipMemsetAsync(e->slab.get(), 0, slab_bytes, e->sP));
+    unsigned char* c = e->slab.get();
     auto takef = [&](float*& ptr) { ptr = reinterpret_cast<float*>(c); c += fa; };
     PParams& k = e->pp;
     takef(k.x); takef(k.y); takef(k.z); takef(k.yaw); takef(k.v); takef(k.speed); takef(k.cte);
@@ -1195,23 +1195,23 @@ int create_impl(const trs_config* cfg, int device, trs_env* e)
     k.ep_len = reinterpret_cast<int32_t*>(c); c += fa;
     takef(e->ctl_steer); takef(e->ctl_thr); takef(e->ctl_brk);
     k.done = c; c += ba; k.pending = c; c += ba; e->ctl_reset = c; c += ba;
-    HIPCHK(hipMalloc((void**)&e->stats, 64 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(e->stats, 0, 64 * sizeof(unsigned long long), e->sP));
-    HIPCHK(hipMalloc((void**)&e->cam, (size_t)kRing * n * sizeof(float4)));
-    HIPCHK(hipMemsetAsync(e->cam, 0, (size_t)kRing * n * sizeof(float4), e->sP));
-    HIPCHK(hipMalloc((void**)&e->cam_pitch, (size_t)kRing * n * sizeof(float)));   // the frames' view pitches beside the camera ring (tracks with elevation)
-    HIPCHK(hipMemsetAsync(e->cam_pitch, 0, (size_t)kRing * n * sizeof(float), e->sP));
-    k.stats = e->stats; k.cam = e->cam;
+    HIPCHK(e->stats.alloc(64 * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(e->stats.get(), 0, e->stats.bytes(), e->sP));
+    HIPCHK(e->cam.alloc((size_t)kRing * n * sizeof(float4)));
+    HIPCHK(hipMemsetAsync(e->cam.get(), 0, e->cam.bytes(), e->sP));
+    HIPCHK(e->cam_pitch.alloc((size_t)kRing * n * sizeof(float)));   // the frames' view pitches beside the camera ring (tracks with elevation)
+    HIPCHK(hipMemsetAsync(e->cam_pitch.get(), 0, e->cam_pitch.bytes(), e->sP));
+    k.stats = e->stats.get(); k.cam = e->cam.get();
     RParams& r = e->rp;
-    r.stats = e->stats;
+    r.stats = e->stats.get();
     if (cfg->render) {
         e->img_bytes = n * (size_t)e->H * e->W * 3;
         for (int b = 0; b < 2; ++b) {
-            HIPCHK(hipMalloc((void**)&e->img[b], e->img_bytes));
-            HIPCHK(hipMemsetAsync(e->img[b], 0, e->img_bytes, e->sP));
+            HIPCHK(e->img[b].alloc(e->img_bytes));
+            HIPCHK(hipMemsetAsync(e->img[b].get(), 0, e->img_bytes, e->sP));
             if (cfg->depth) {
-                HIPCHK(hipMalloc((void**)&e->depth[b], n * (size_t)e->H * e->W * 4));
-                HIPCHK(hipMemsetAsync(e->depth[b], 0, n * (size_t)e->H * e->W * 4, e->sP));
+                HIPCHK(e->depth[b].alloc(n * (size_t)e->H * e->W * 4));
+                HIPCHK(hipMemsetAsync(e->depth[b].get(), 0, e->depth[b].bytes(), e->sP));
             }
         }
     }
@@ -1226,9 +1226,9 @@ int create_impl(const trs_config* cfg, int device, trs_env* e)
     if (r.gpr > kBlock) return fail(TRS_ERR_LIMIT, "img_w too large: more 4-pixel groups per row than threads per workgroup");
     if (r.gpr > kRasterThreads) return fail(TRS_ERR_LIMIT, "img_w too large: more 4-pixel groups per row than raster threads");
     r.rows_per_pass = kRasterThreads / r.gpr;   // raster threads beyond rows_per_pass * gpr idle (32 of 512 at W = 160)
-    HIPCHK(hipHostMalloc((void**)&e->fault, 64, hipHostMallocMapped | hipHostMallocCoherent));   // kernels report a layout fault here (checked at every synchronisation)
-    *e->fault = 0ull;
-    k.fault = e->fault; r.fault = e->fault;
+    HIPCHK(e->fault.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));   // kernels report a layout fault here (checked at every synchronisation)
+    *e->fault.get() = 0ull;
+    k.fault = e->fault.get(); r.fault = e->fault.get();
     HIPCHK(hipStreamSynchronize(e->sP));
     return TRS_OK;
 }
@@ -1268,25 +1268,16 @@ TRS_EXPORT int trs_destroy(trs_env* e)
     trsim::comm_destroy(e);
     if (e->ev_order) (void)hipEventDestroy(e->ev_order);
     if (e->pilot) { trs_pilot_free(e->pilot); e->pilot = nullptr; }
-    (void)hipFree(e->slab); (void)hipFree(e->img[0]); (void)hipFree(e->img[1]); (void)hipFree(e->depth[0]); (void)hipFree(e->depth[1]); (void)hipFree(e->blob_p); (void)hipFree(e->blob_r);
-    (void)hipFree(e->tangent); (void)hipFree(e->start_yaw); (void)hipFree(e->cam); (void)hipFree(e->cam_pitch); (void)hipFree(e->dpitch);
-    (void)hipFree(e->stats); (void)hipFree(e->loc_q); (void)hipFree(e->loc_out); (void)hipFree(e->lens_dev); (void)hipFree(e->light_own);
-    (void)hipFree(e->mux_state); (void)hipFree(e->edge_scratch); (void)hipFree(e->seq_buf); (void)hipFree(e->glue);
-    for (void* sc : e->scratch) (void)hipFree(sc);
-    if (e->pinned) (void)hipHostFree(e->pinned);
-    if (e->fault) (void)hipHostFree(e->fault);
-    (void)hipFree(e->pre); (void)hipFree(e->tmp_in); (void)hipFree(e->tmp_out); (void)hipFree(e->tmp_f); (void)hipFree(e->hsv_tab); (void)hipFree(e->dyn_tab);
     for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->sP) (void)hipStreamDestroy(e->sP);
-    delete e;
+    delete e;                                                // the handle's buffers go with it: the stream was idle above
     return TRS_OK;
 }
 
 namespace {
 int upload_palette(trs_env* e);
 struct LensStage {                                           // lens tables built for a map but not yet the handle's (lens_stage / lens_commit)
-    unsigned char* dev = nullptr; size_t pal_off = 0; trsim::LensTables T; bool block_written = false;
-    ~LensStage() { (void)hipFree(dev); }
+    trsim::DevBuf<> dev; size_t pal_off = 0; trsim::LensTables T; bool block_written = false;
 };
 int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S);
 void lens_commit(trs_env* e, LensStage& S);
@@ -1310,10 +1301,8 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
         return fail(TRS_ERR_STATE, "this track has elevation and a lens camera is set: the lens camera is built for flat tracks only (trs_set_camera(NULL) first); the handle keeps its track");
     PParams k = e->pp;
     RParams r = e->rp;
-    struct Staged {                                          // device buffers of the new track; freed unless committed
-        unsigned char *blob_p = nullptr, *blob_r = nullptr; float *tangent = nullptr, *start_yaw = nullptr, *dpitch = nullptr;
-        ~Staged() { (void)hipFree(blob_p); (void)hipFree(blob_r); (void)hipFree(tangent); (void)hipFree(start_yaw); (void)hipFree(dpitch); }
-    } nb;
+    trsim::DevBuf<> blob_p, blob_r;                          // device buffers of the new track; released unless moved into the handle
+    trsim::DevBuf<float> tangent, start_yaw, dpitch;
     int n_lds_r = 0, n_lds_p = 0, n_lds_step = 0, n_lds_off_phys = 0, n_pts_bytes = 0;
 
     // ---- physics LDS image: px | py | pz | tangent (when it fits) + scratch ----
@@ -1373,22 +1362,22 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     std::memcpy(hr.data() + r.off_depth, T.rowdepth.data(), (size_t)e->H * 4);
     if (T.hills) std::memcpy(hr.data() + off_sky, T.sky.data(), (size_t)e->H * 4);
 
-    HIPCHK(hipMalloc((void**)&nb.blob_p, off));
-    HIPCHK(hipMalloc((void**)&nb.blob_r, trsim::lens_block_offset((int)roff) + sizeof(trsim::LensBlock)));   // (+ the constants of a track with elevation and of the lens camera, behind the image)
-    HIPCHK(hipMalloc((void**)&nb.tangent, (size_t)n_points * 8));
-    HIPCHK(hipMalloc((void**)&nb.start_yaw, (size_t)n_points * 4));
-    HIPCHK(hipMemcpy(nb.blob_p, hp.data(), off, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(nb.blob_r, hr.data(), roff, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(nb.tangent, T.tangent.data(), (size_t)n_points * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(nb.start_yaw, T.start_yaw.data(), (size_t)n_points * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&nb.dpitch, (size_t)n_points * 4));
+    HIPCHK(blob_p.alloc(off));
+    HIPCHK(blob_r.alloc(trsim::lens_block_offset((int)roff) + sizeof(trsim::LensBlock)));   // (+ the constants of a track with elevation and of the lens camera, behind the image)
+    HIPCHK(tangent.alloc((size_t)n_points * 8));
+    HIPCHK(start_yaw.alloc((size_t)n_points * 4));
+    HIPCHK(hipMemcpy(blob_p.get(), hp.data(), off, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(blob_r.get(), hr.data(), roff, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(tangent.get(), T.tangent.data(), (size_t)n_points * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(start_yaw.get(), T.start_yaw.data(), (size_t)n_points * 4, hipMemcpyHostToDevice));
+    HIPCHK(dpitch.alloc((size_t)n_points * 4));
     {   // the view pitch of a frame whose nearest raw track point is idx: pitch_f + dpitch[idx], ONE binary32 addition as the spec has it
         std::vector<float> vp((size_t)n_points);
         for (int i = 0; i < n_points; ++i) vp[i] = T.pitch_f + T.dpitch[i];
-        HIPCHK(hipMemcpy(nb.dpitch, vp.data(), (size_t)n_points * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dpitch.get(), vp.data(), (size_t)n_points * 4, hipMemcpyHostToDevice));
     }
-    k.blob = nb.blob_p; k.start_yaw = nb.start_yaw; k.tangent_g = nb.tangent;
-    r.blob = nb.blob_r;
+    k.blob = blob_p.get(); k.start_yaw = start_yaw.get(); k.tangent_g = tangent.get();
+    r.blob = blob_r.get();
     k.np = n_points; r.map_w = T.info.map_w; r.map_h = T.info.map_h;
     k.map_x0f = T.map_x0f; k.map_z0f = T.map_z0f; k.inv_cellf = T.inv_cellf;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, n_lds_p));
@@ -1404,22 +1393,20 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     LensStage ls;
     {
         trsim::LensBlock none{};                             // (the slot is never read while no lens is set; defined contents all the same)
-        HIPCHK(hipMemcpy(nb.blob_r + trsim::lens_block_offset(r.blob_bytes), &none, sizeof none, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(blob_r.get() + trsim::lens_block_offset(r.blob_bytes), &none, sizeof none, hipMemcpyHostToDevice));
     }
-    if (e->lens_on) { int rl = lens_stage(e, e->camera, n_lds_step, T.info.cell, nb.blob_r, r.blob_bytes, ls); if (rl) return rl; }
+    if (e->lens_on) { int rl = lens_stage(e, e->camera, n_lds_step, T.info.cell, blob_r.get(), r.blob_bytes, ls); if (rl) return rl; }
     // ---- commit: nothing above has touched the handle ----
     e->track_loaded = false;                                 // (until the state arrays below are in place)
-    (void)hipFree(e->blob_p); (void)hipFree(e->blob_r); (void)hipFree(e->tangent); (void)hipFree(e->start_yaw); (void)hipFree(e->dpitch);
-    e->blob_p = nb.blob_p; e->blob_r = nb.blob_r; e->tangent = nb.tangent; e->start_yaw = nb.start_yaw; e->dpitch = nb.dpitch;
+    e->blob_p = std::move(blob_p); e->blob_r = std::move(blob_r); e->tangent = std::move(tangent); e->start_yaw = std::move(start_yaw); e->dpitch = std::move(dpitch);   // (the old track's are released)
     {
         trsim::HillBlock& hb = e->hill_host;                 // (host copy: upload_palette fills in the frame filter and sends the block again)
         hb = trsim::HillBlock{};
-        hb.vpitch = nb.dpitch; hb.cam_pitch = e->cam_pitch; hb.off_sky = off_sky; hb.far_rgb = T.far_rgb;
+        hb.vpitch = e->dpitch.get(); hb.cam_pitch = e->cam_pitch.get(); hb.off_sky = off_sky; hb.far_rgb = T.far_rgb;
         hb.inv_f = T.inv_f; hb.hh = T.hh; hb.cam_h_f = T.cam_h_f; hb.z_far_f = T.z_far_f; hb.inv_zfar_f = T.inv_zfar_f; hb.fog_f = T.fog_f; hb.inv_cell_f = T.inv_cellf;
         e->hilly = T.hills;
-        HIPCHK(hipMemcpy(e->blob_r + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->blob_r.get() + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     }
-    nb = Staged{};
     if (e->lens_on) lens_commit(e, ls);
     e->tab = std::move(T);
     e->pp = k; e->rp = r;
@@ -1443,7 +1430,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     HIPCHK(hipMemset(k.ep_len, 0, n * 4));
     HIPCHK(hipMemset(k.done, 0, n));
     HIPCHK(hipMemset(k.pending, 1, n));
-    HIPCHK(hipMemset(e->stats, 0, 64 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(e->stats.get(), 0, 64 * sizeof(unsigned long long)));
     e->step_count = 0;
     e->track_loaded = true;
     trsim::resident_clear_fault(e);
@@ -1556,13 +1543,11 @@ TRS_EXPORT int trs_step_sequence_host(trs_env* e, const float* h_st, const float
     HIPCHK(hipSetDevice(e->device));
     { int rq = quiesce(e); if (rq) return rq; }            // the sequence is copied through the handle's stream
     const size_t cnt = (size_t)n_steps * (size_t)e->n;
-    if (e->seq_cap < cnt) {
+    if (e->seq_buf.bytes() < cnt * 3 * sizeof(float)) {
         HIPCHK(hipStreamSynchronize(e->sP));
-        (void)hipFree(e->seq_buf); e->seq_buf = nullptr; e->seq_cap = 0;
-        HIPCHK(hipMalloc((void**)&e->seq_buf, cnt * 3 * sizeof(float)));
-        e->seq_cap = cnt;
+        HIPCHK(e->seq_buf.reserve(cnt * 3 * sizeof(float)));
     }
-    float *ds = e->seq_buf, *dt = ds + cnt, *db = dt + cnt;
+    float *ds = e->seq_buf.get(), *dt = ds + cnt, *db = dt + cnt;
     HIPCHK(hipMemcpyAsync(ds, h_st, cnt * 4, hipMemcpyHostToDevice, e->sP));
     HIPCHK(hipMemcpyAsync(dt, h_th, cnt * 4, hipMemcpyHostToDevice, e->sP));
     if (h_br) HIPCHK(hipMemcpyAsync(db, h_br, cnt * 4, hipMemcpyHostToDevice, e->sP));
@@ -1592,11 +1577,11 @@ TRS_EXPORT int trs_get_state(trs_env* e, trs_state_view* o)
     if (!e || !o) return fail(TRS_ERR_ARG, "null argument");
     const PParams& k = e->pp;
     o->n_envs = e->n; o->img_h = e->H; o->img_w = e->W; o->n_points = k.np;
-    o->img = e->cfg.render ? e->img[(e->step_count + 1) & 1] : nullptr;   // buffer written by the last step
+    o->img = e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr;   // buffer written by the last step
     o->pos_x = k.x; o->pos_y = k.y; o->pos_z = k.z; o->speed = k.speed; o->cte = k.cte; o->yaw = k.yaw; o->vel = k.v;
     o->seg_idx = k.seg_idx; o->ep_return = k.ep_return; o->last_return = k.last_return; o->ep_len = k.ep_len; o->done = k.done;
     o->step_count = e->step_count;
-    o->depth = (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1] : nullptr;
+    o->depth = (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1].get() : nullptr;
     return TRS_OK;
 }
 
@@ -1608,7 +1593,7 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     const void* src = nullptr; size_t need = 0; const size_t n = (size_t)e->n;
     bool host_src = false;
     switch (which) {
-    case TRS_F_IMG: src = e->cfg.render ? e->img[(e->step_count + 1) & 1] : nullptr; need = e->img_bytes; break;
+    case TRS_F_IMG: src = e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr; need = e->img_bytes; break;
     case TRS_F_POS_X: src = k.x; need = n * 4; break;
     case TRS_F_POS_Y: src = k.y; need = n * 4; break;
     case TRS_F_POS_Z: src = k.z; need = n * 4; break;
@@ -1625,17 +1610,17 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     case TRS_F_CTL_STEER: src = e->ctl_steer; need = n * 4; break;
     case TRS_F_CTL_THR: src = e->ctl_thr; need = n * 4; break;
     case TRS_F_CTL_BRK: src = e->ctl_brk; need = n * 4; break;
-    case TRS_F_STATS: src = e->stats; need = 64 * sizeof(unsigned long long); break;
-    case TRS_F_DEPTH: src = (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1] : nullptr; need = n * e->H * e->W * 4; break;
-    case TRS_F_ROWDEPTH: if (e->track_loaded) { src = e->blob_r + e->rp.off_depth; need = (size_t)e->H * 4; } break;
+    case TRS_F_STATS: src = e->stats.get(); need = 64 * sizeof(unsigned long long); break;
+    case TRS_F_DEPTH: src = (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1].get() : nullptr; need = n * e->H * e->W * 4; break;
+    case TRS_F_ROWDEPTH: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_depth; need = (size_t)e->H * 4; } break;
     // the tables live on the host exactly as built; their LDS images on the device are re-laid-out (pitched map)
     case TRS_F_MAP: if (e->track_loaded) { src = e->tab.map.data(); need = e->tab.map.size() * 4; host_src = true; } break;
-    case TRS_F_ROWTAB: if (e->track_loaded) { src = e->blob_r + e->rp.off_rowtab; need = (size_t)e->H * 8; } break;
-    case TRS_F_PALETTE: if (e->track_loaded) { src = e->blob_r + e->rp.off_pal; need = (size_t)e->H * 16; } break;
-    case TRS_F_TANGENT: if (e->track_loaded) { src = e->tangent; need = (size_t)k.np * 8; } break;
+    case TRS_F_ROWTAB: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_rowtab; need = (size_t)e->H * 8; } break;
+    case TRS_F_PALETTE: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_pal; need = (size_t)e->H * 16; } break;
+    case TRS_F_TANGENT: if (e->track_loaded) { src = e->tangent.get(); need = (size_t)k.np * 8; } break;
     case TRS_F_DPITCH: if (e->track_loaded) { src = e->tab.dpitch.data(); need = e->tab.dpitch.size() * 4; host_src = true; } break;
     case TRS_F_LENS_TABLE: if (e->track_loaded && e->lens_on) { src = e->lens.pix.data(); need = e->lens.pix.size() * 4; host_src = true; } break;
-    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->lens_on && e->lens_dev) { src = e->lens_dev + e->lens_pal_off; need = (size_t)trsim::kLensPalBytes; } break;
+    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->lens_on && e->lens_dev.get()) { src = e->lens_dev.get() + e->lens_pal_off; need = (size_t)trsim::kLensPalBytes; } break;
     default: return fail(TRS_ERR_ARG, "unknown field");
     }
     if (!src) return fail(TRS_ERR_STATE, "field not available");
@@ -1670,14 +1655,13 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
     const PParams& k = e->pp;
     const size_t n = (size_t)e->n, img_b = h_img ? e->img_bytes : 0;
     const size_t need = ((img_b + 15) & ~(size_t)15) + 7 * ((n * 4 + 15) & ~(size_t)15) + 16;   // every item starts 16-B aligned
-    if (e->pinned_bytes < need) {
-        if (e->pinned) { int rq = sync_all(e); if (rq) return rq; (void)hipHostFree(e->pinned); e->pinned = nullptr; e->pinned_bytes = 0; }
-        HIPCHK(hipHostMalloc((void**)&e->pinned, need, hipHostMallocDefault));
-        e->pinned_bytes = need;
+    if (e->pinned.bytes() < need) {
+        if (e->pinned.get()) { int rq = sync_all(e); if (rq) return rq; }
+        HIPCHK(e->pinned.reserve(need, hipHostMallocDefault));
     }
     struct Item { const void* src; void* dst; size_t bytes; };
     const Item items[8] = {
-        {h_img ? e->img[(e->step_count + 1) & 1] : nullptr, h_img, img_b},
+        {h_img ? e->img[(e->step_count + 1) & 1].get() : nullptr, h_img, img_b},
         {k.x, h_x, n * 4}, {k.y, h_y, n * 4}, {k.z, h_z, n * 4}, {k.speed, h_speed, n * 4}, {k.cte, h_cte, n * 4},
         {k.seg_idx, h_seg, n * 4}, {k.done, h_done, n},
     };
@@ -1687,7 +1671,7 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
     size_t off = 0;
     for (const Item& it : items) {
         if (!it.dst || !it.bytes) continue;
-        HIPCHK(hipMemcpyAsync(e->pinned + off, it.src, it.bytes, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(e->pinned.get() + off, it.src, it.bytes, hipMemcpyDeviceToHost, cs));
         e->d2h_bytes += it.bytes;
         off += (it.bytes + 15) & ~(size_t)15;
     }
@@ -1696,7 +1680,7 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
     off = 0;
     for (const Item& it : items) {
         if (!it.dst || !it.bytes) continue;
-        std::memcpy(it.dst, e->pinned + off, it.bytes);
+        std::memcpy(it.dst, e->pinned.get() + off, it.bytes);
         off += (it.bytes + 15) & ~(size_t)15;
     }
     return TRS_OK;
@@ -1729,21 +1713,21 @@ TRS_EXPORT int trs_locate(trs_env* e, const double* h_xyz, int nq, int32_t* h_id
     { int rq = quiesce(e); if (rq) return rq; }
     if (nq > e->loc_cap) {
         HIPCHK(hipStreamSynchronize(e->sP));
-        (void)hipFree(e->loc_q); (void)hipFree(e->loc_out); e->loc_q = nullptr; e->loc_out = nullptr; e->loc_cap = 0;
-        HIPCHK(hipMalloc((void**)&e->loc_q, (size_t)nq * 24));
-        HIPCHK(hipMalloc((void**)&e->loc_out, (size_t)nq * 4));
+        e->loc_cap = 0;
+        HIPCHK(e->loc_q.alloc((size_t)nq * 24));
+        HIPCHK(e->loc_out.alloc((size_t)nq * 4));
         e->loc_cap = nq;
     }
-    HIPCHK(hipMemcpyAsync(e->loc_q, h_xyz, (size_t)nq * 24, hipMemcpyHostToDevice, e->sP));
+    HIPCHK(hipMemcpyAsync(e->loc_q.get(), h_xyz, (size_t)nq * 24, hipMemcpyHostToDevice, e->sP));
     constexpr int kW = kLocBlock / 64;
     int grid = (nq + kW - 1) / kW;
     grid = std::min(grid, e->cu_count * 2);
     const PParams& pk = e->pp;
     const NearParams near{pk.np, pk.off_py, pk.off_pz, pk.off_gstart, pk.off_gpts, pk.grid_nx, pk.grid_nz, pk.grid_x0, pk.grid_z0};
     hipLaunchKernelGGL(trs_locate_kernel, dim3(grid), dim3(kLocBlock), pk.blob_bytes, e->sP,
-                       (const unsigned char*)e->blob_p, pk.blob_bytes, near, (const double*)e->loc_q, nq, e->loc_out);
+                       (const unsigned char*)e->blob_p.get(), pk.blob_bytes, near, (const double*)e->loc_q.get(), nq, e->loc_out.get());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_idx, e->loc_out, (size_t)nq * 4, hipMemcpyDeviceToHost, e->sP));
+    HIPCHK(hipMemcpyAsync(h_idx, e->loc_out.get(), (size_t)nq * 4, hipMemcpyDeviceToHost, e->sP));
     HIPCHK(hipStreamSynchronize(e->sP));
     return TRS_OK;
 }
@@ -1765,15 +1749,15 @@ int check_pre(const trs_pre_config* c)
 
 int ensure_hsv_table(trs_env* e)
 {
-    if (e->hsv_tab) return TRS_OK;
+    if (e->hsv_tab.get()) return TRS_OK;
     int tab[512];
     tab[0] = tab[256] = 0;
     for (int i = 1; i < 256; ++i) {          // OpenCV's sdiv_table / hdiv_table180, hsv_shift = 12
         tab[i] = (int)std::lrint((255 << 12) / (1.0 * i));
         tab[256 + i] = (int)std::lrint((180 << 12) / (6.0 * i));
     }
-    HIPCHK(hipMalloc((void**)&e->hsv_tab, sizeof tab));
-    HIPCHK(hipMemcpy(e->hsv_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+    HIPCHK(e->hsv_tab.alloc(sizeof tab));
+    HIPCHK(hipMemcpy(e->hsv_tab.get(), tab, sizeof tab, hipMemcpyHostToDevice));
     return TRS_OK;
 }
 
@@ -1783,7 +1767,7 @@ int upload_dyn_tables(trs_env* e, const trs_pre_config& c)
     int rc = ensure_hsv_table(e);
     if (rc) return rc;
     std::vector<unsigned> t(kDynTabWords, 0u);
-    HIPCHK(hipMemcpy(t.data(), e->hsv_tab, 512 * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t.data(), e->hsv_tab.get(), 512 * sizeof(int), hipMemcpyDeviceToHost));
     unsigned lo[4], hi[4]; int dc[4];
     for (int k = 0; k < 4; ++k) {
         lo[k] = c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16);
@@ -1799,8 +1783,8 @@ int upload_dyn_tables(trs_env* e, const trs_pre_config& c)
         t[trsim::kDynCntAt + i] = cnt;
     }
     { int rq = quiesce(e); if (rq) return rq; HIPCHK(hipStreamSynchronize(e->sP)); }   // a running kernel may still be staging the old tables
-    if (!e->dyn_tab) HIPCHK(hipMalloc((void**)&e->dyn_tab, kDynTabWords * sizeof(unsigned)));
-    HIPCHK(hipMemcpy(e->dyn_tab, t.data(), kDynTabWords * sizeof(unsigned), hipMemcpyHostToDevice));
+    HIPCHK(e->dyn_tab.reserve(kDynTabWords * sizeof(unsigned)));   // (allocated once: the size is fixed)
+    HIPCHK(hipMemcpy(e->dyn_tab.get(), t.data(), kDynTabWords * sizeof(unsigned), hipMemcpyHostToDevice));
     return TRS_OK;
 }
 
@@ -1854,12 +1838,12 @@ int upload_palette(trs_env* e)
     e->rp.uni_rows = (e->hilly || e->lens_on) ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame;
     e->uniform_ok[0] = e->uniform_ok[1] = false;               //  the lens camera: on the pixel)  (the closed pilot loop's steps skip rows an earlier step wrote: not across a palette change)
     { int rq = sync_all(e); if (rq) return rq; }               // frames in flight keep the palette they were launched with
-    HIPCHK(hipMemcpy(e->blob_r + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
-    if (e->lens_on && e->lens_dev) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
+    HIPCHK(hipMemcpy(e->blob_r.get() + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
+    if (e->lens_on && e->lens_dev.get()) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
         std::vector<uint32_t> lp(e->lens.palette);
         if (e->has_frame_filter && !e->filter_dynamic)
             for (auto& c : lp) c = filter_colour(e->frame_filter, c);
-        HIPCHK(hipMemcpy(e->lens_dev + e->lens_pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->lens_dev.get() + e->lens_pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
     }
     if (e->hilly || e->light_on) {
         // a track with elevation: the kernels blend a row's ground colours per env and frame and run the static filter on each (hill_filter_colour); the sky colours and
@@ -1884,10 +1868,10 @@ int upload_palette(trs_env* e)
                 hb.f_hi[k] = (unsigned)(c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16));
                 hb.f_dst[k] = c.dst_channel[k];
             }
-            hb.hsv_tab = e->hsv_tab;
+            hb.hsv_tab = e->hsv_tab.get();
         }
-        if (e->hilly) HIPCHK(hipMemcpy(e->blob_r + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->blob_r + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
+        if (e->hilly) HIPCHK(hipMemcpy(e->blob_r.get() + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->blob_r.get() + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     }
     return TRS_OK;
 }
@@ -1926,10 +1910,10 @@ int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cel
     if (e->has_frame_filter && !e->filter_dynamic)
         for (auto& c : lp) c = filter_colour(e->frame_filter, c);
     std::memcpy(h.data() + off_pal, lp.data(), lp.size() * 4);
-    HIPCHK(hipMalloc((void**)&S.dev, bytes));
-    HIPCHK(hipMemcpy(S.dev, h.data(), bytes, hipMemcpyHostToDevice));
+    HIPCHK(S.dev.alloc(bytes));
+    HIPCHK(hipMemcpy(S.dev.get(), h.data(), bytes, hipMemcpyHostToDevice));
     trsim::LensBlock lb{};
-    unsigned char* const d = S.dev;
+    unsigned char* const d = S.dev.get();
     lb.F = reinterpret_cast<const float*>(d); lb.L = reinterpret_cast<const float*>(d + off_L); lb.D = reinterpret_cast<const float*>(d + off_D);
     lb.M = reinterpret_cast<const uint16_t*>(d + off_M); lb.pal = reinterpret_cast<const uint32_t*>(d + off_pal);
     lb.oc = (float)(cam.offset_x / cell);
@@ -1943,28 +1927,26 @@ int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cel
 // the staged lens tables become the handle's (the old ones are freed)
 void lens_commit(trs_env* e, LensStage& S)
 {
-    (void)hipFree(e->lens_dev);
-    e->lens_dev = S.dev; S.dev = nullptr;
+    e->lens_dev = std::move(S.dev);
     e->lens_pal_off = S.pal_off; e->lens = std::move(S.T);
 }
 
 // back to the pinhole camera: the lens tables are freed (nothing may be in flight)
 void lens_release(trs_env* e)
 {
-    (void)hipFree(e->lens_dev);
-    e->lens_dev = nullptr; e->lens_pal_off = 0; e->lens = trsim::LensTables{};
+    (void)e->lens_dev.reset();
+    e->lens_pal_off = 0; e->lens = trsim::LensTables{};
 }
 
 int ensure_tmp(trs_env* e, size_t frames)
 {
     if (frames <= e->tmp_cap) return TRS_OK;
     HIPCHK(hipStreamSynchronize(e->sP));
-    (void)hipFree(e->tmp_in); (void)hipFree(e->tmp_out); (void)hipFree(e->tmp_f);
-    e->tmp_in = e->tmp_out = nullptr; e->tmp_f = nullptr; e->tmp_cap = 0;
+    e->tmp_cap = 0;
     const size_t fb = (size_t)e->H * e->W * 3;
-    HIPCHK(hipMalloc((void**)&e->tmp_in, frames * fb));
-    HIPCHK(hipMalloc((void**)&e->tmp_out, frames * fb));
-    HIPCHK(hipMalloc((void**)&e->tmp_f, frames * fb * sizeof(float)));
+    HIPCHK(e->tmp_in.alloc(frames * fb));
+    HIPCHK(e->tmp_out.alloc(frames * fb));
+    HIPCHK(e->tmp_f.alloc(frames * fb * sizeof(float)));
     e->tmp_cap = frames;
     return TRS_OK;
 }
@@ -1972,17 +1954,14 @@ int ensure_tmp(trs_env* e, size_t frames)
 // device scratch of the *_host control glue, owned by the handle (the N = 1 Car loop calls these every tick)
 int ensure_glue(trs_env* e, size_t bytes)
 {
-    if (bytes <= e->glue_bytes) return TRS_OK;
+    if (bytes <= e->glue.bytes()) return TRS_OK;
     int rc = sync_all(e);
     if (rc) return rc;
-    (void)hipFree(e->glue); e->glue = nullptr; e->glue_bytes = 0;
-    const size_t cap = std::max<size_t>(align_up(bytes, 256), 4096);
-    HIPCHK(hipMalloc((void**)&e->glue, cap));
-    e->glue_bytes = cap;
+    HIPCHK(e->glue.reserve(std::max<size_t>(align_up(bytes, 256), 4096)));
     return TRS_OK;
 }
 
-const uint8_t* latest_frame(const trs_env* e) { return e->cfg.render ? e->img[(e->step_count + 1) & 1] : nullptr; }
+const uint8_t* latest_frame(const trs_env* e) { return e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr; }
 
 }  // namespace
 
@@ -2072,7 +2051,7 @@ TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
     { int rq = sync_all(e); if (rq) return rq; }
     if (on && e->track_loaded) {
         LensStage ls;
-        int rc = lens_stage(e, nc, e->lds_step, e->tab.info.cell, e->blob_r, e->rp.blob_bytes, ls);
+        int rc = lens_stage(e, nc, e->lds_step, e->tab.info.cell, e->blob_r.get(), e->rp.blob_bytes, ls);
         if (rc) {
             if (e->lens_on && ls.block_written) {            // the copy of the block failed: the handle's LensBlock may be half written, the old lens cannot stay
                 const std::string why = g_err;
@@ -2091,28 +2070,23 @@ TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
 
 // scene lighting (include/trsim_spec.h, "scene lighting"): register the caller's float[n_envs][8] (NULL: back to the unlit kernels)
 namespace {
-int set_lighting_impl(trs_env* e, const float* d_params, float* own)
+int set_lighting_impl(trs_env* e, const float* d_params, trsim::DevBuf<float> own = {})   // own: the host entry point's copy behind d_params, released on a refusal
 {
     const bool on = d_params != nullptr;
     if (on) {
         const char* why = nullptr;
         if (!e->cfg.render) why = "the env has no camera (cfg.render == 0)";
         else if (e->lens_on) why = "a lens camera is set: scene lighting is not built for the lens camera (trs_set_camera(NULL) first)";
-        if (why) { if (own) (void)hipFree(own); return fail(TRS_ERR_STATE, why); }
+        if (why) return fail(TRS_ERR_STATE, why);
         const Variant v = trsim::variant_of(e) | kVLight;     // what the handle runs with lighting
-        if (e->track_loaded && steps_that_fit(e, v, e->lds_step) < 1) {
-            if (own) (void)hipFree(own);
+        if (e->track_loaded && steps_that_fit(e, v, e->lds_step) < 1)
             return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lit palettes");
-        }
-        if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits(e, v)) {
-            if (own) (void)hipFree(own);
+        if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits(e, v))
             return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the lighting parameters and lit palettes: select TRS_STEP_LAUNCH");
-        }
     }
     // nothing may be in flight and a resident worker leaves before the kernels change (upload_palette quiesces too; the old host copy is freed after that)
-    { int rq = sync_all(e); if (rq) { if (own) (void)hipFree(own); return rq; } }
-    if (e->light_own && e->light_own != own) { (void)hipFree(e->light_own); e->light_own = nullptr; }
-    e->light_own = own;
+    { int rq = sync_all(e); if (rq) return rq; }
+    e->light_own = std::move(own);                         // (the old host copy is released here, after the wait)
     e->light = d_params; e->light_on = on;
     return upload_palette(e);                              // raw palette + the filter for the kernels, the parameters' address in the block behind the raster image
 }
@@ -2122,20 +2096,21 @@ TRS_EXPORT int trs_set_lighting(trs_env* e, const float* d_params)
 {
     if (!e) return fail(TRS_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(e->device));
-    return set_lighting_impl(e, d_params, nullptr);
+    return set_lighting_impl(e, d_params);
 }
 
 TRS_EXPORT int trs_set_lighting_host(trs_env* e, const float* h_params)
 {
     if (!e) return fail(TRS_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(e->device));
-    if (!h_params) return set_lighting_impl(e, nullptr, nullptr);
+    if (!h_params) return set_lighting_impl(e, nullptr);
     if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
-    float* own = nullptr;
+    trsim::DevBuf<float> own;
     const size_t bytes = (size_t)e->n * 8 * sizeof(float);
-    HIPCHK(hipMalloc((void**)&own, bytes));
-    if (hipMemcpy(own, h_params, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(own); return fail(TRS_ERR_DEVICE, "hipMemcpy of the lighting parameters failed"); }
-    return set_lighting_impl(e, own, own);
+    HIPCHK(own.alloc(bytes));
+    if (hipMemcpy(own.get(), h_params, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(TRS_ERR_DEVICE, "hipMemcpy of the lighting parameters failed");
+    const float* d_params = own.get();
+    return set_lighting_impl(e, d_params, std::move(own));
 }
 
 TRS_EXPORT int trs_get_camera(trs_env* e, trs_camera* out)
@@ -2160,15 +2135,15 @@ TRS_EXPORT int trs_preprocess(trs_env* e, const trs_pre_config* c, const uint8_t
     }
     if (!d_dst) {
         if (n_images > e->n) return fail(TRS_ERR_ARG, "own buffer holds n_envs frames");
-        if (!e->pre) HIPCHK(hipMalloc((void**)&e->pre, (size_t)e->n * e->H * e->W * 3));
-        d_dst = e->pre;
+        HIPCHK(e->pre.reserve((size_t)e->n * e->H * e->W * 3));   // (allocated once: the size is fixed)
+        d_dst = e->pre.get();
     }
     if (d_out) *d_out = d_dst;
     if (n_images == 0) return TRS_OK;
     rc = ensure_hsv_table(e);
     if (rc) return rc;
     PreParams p{};
-    p.src = d_src; p.dst = d_dst; p.hsv_tab = e->hsv_tab;
+    p.src = d_src; p.dst = d_dst; p.hsv_tab = e->hsv_tab.get();
     p.n_img = n_images; p.H = e->H; p.W = e->W; p.gpr = e->W / 4; p.gpe = p.gpr * e->H;
     p.r0 = std::min(40, e->H); p.r1 = std::min(119, e->H);                 // img[40:119] (img_preprocessing.py:88)
     p.dynamic = c->dynamic_brightness; p.color = c->color_filter_enabled; p.n_filters = c->n_filters;
@@ -2197,13 +2172,11 @@ TRS_EXPORT int trs_preprocess(trs_env* e, const trs_pre_config* c, const uint8_t
             p.off_tab = 0;
             p.scratch_stride = align_up(work, 256);
             const size_t need = p.scratch_stride * (size_t)grid;
-            if (e->edge_scratch_bytes < need) {
+            if (e->edge_scratch.bytes() < need) {
                 HIPCHK(hipStreamSynchronize(e->sP));
-                (void)hipFree(e->edge_scratch); e->edge_scratch = nullptr; e->edge_scratch_bytes = 0;
-                HIPCHK(hipMalloc((void**)&e->edge_scratch, need));
-                e->edge_scratch_bytes = need;
+                HIPCHK(e->edge_scratch.reserve(need));
             }
-            p.scratch = e->edge_scratch;
+            p.scratch = e->edge_scratch.get();
             hipLaunchKernelGGL(trs_preprocess_edge_kernel<true>, dim3(grid), dim3(kEdgeBlock), tables, e->sP, p);
         }
         HIPCHK(hipGetLastError());
@@ -2226,10 +2199,10 @@ TRS_EXPORT int trs_preprocess_host(trs_env* e, const trs_pre_config* c, const ui
     int rc = ensure_tmp(e, (size_t)n_images);
     if (rc) return rc;
     const size_t bytes = (size_t)n_images * e->H * e->W * 3;
-    HIPCHK(hipMemcpyAsync(e->tmp_in, h_src, bytes, hipMemcpyHostToDevice, e->sP));
-    rc = trs_preprocess(e, c, e->tmp_in, e->tmp_out, n_images, nullptr);
+    HIPCHK(hipMemcpyAsync(e->tmp_in.get(), h_src, bytes, hipMemcpyHostToDevice, e->sP));
+    rc = trs_preprocess(e, c, e->tmp_in.get(), e->tmp_out.get(), n_images, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_dst, e->tmp_out, bytes, hipMemcpyDeviceToHost, e->sP));
+    HIPCHK(hipMemcpyAsync(h_dst, e->tmp_out.get(), bytes, hipMemcpyDeviceToHost, e->sP));
     e->d2h_bytes += bytes; e->h2d_bytes += bytes;
     HIPCHK(hipStreamSynchronize(e->sP));
     return TRS_OK;
@@ -2261,10 +2234,10 @@ TRS_EXPORT int trs_normalize_host(trs_env* e, const uint8_t* h_src, float* h_dst
     int rc = ensure_tmp(e, (size_t)n_images);
     if (rc) return rc;
     const size_t bytes = (size_t)n_images * e->H * e->W * 3;
-    HIPCHK(hipMemcpyAsync(e->tmp_in, h_src, bytes, hipMemcpyHostToDevice, e->sP));
-    rc = trs_normalize(e, e->tmp_in, e->tmp_f, n_images);
+    HIPCHK(hipMemcpyAsync(e->tmp_in.get(), h_src, bytes, hipMemcpyHostToDevice, e->sP));
+    rc = trs_normalize(e, e->tmp_in.get(), e->tmp_f.get(), n_images);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_dst, e->tmp_f, bytes * sizeof(float), hipMemcpyDeviceToHost, e->sP));
+    HIPCHK(hipMemcpyAsync(h_dst, e->tmp_f.get(), bytes * sizeof(float), hipMemcpyDeviceToHost, e->sP));
     e->d2h_bytes += bytes * sizeof(float); e->h2d_bytes += bytes;
     HIPCHK(hipStreamSynchronize(e->sP));
     return TRS_OK;
@@ -2290,7 +2263,7 @@ TRS_EXPORT int trs_driver_assist_host(trs_env* e, int mode, double k, float* h_s
     int rc = quiesce(e);
     if (!rc) rc = ensure_glue(e, (size_t)n * 16);
     if (rc) return rc;
-    float* d = e->glue;
+    float* d = e->glue.get();
     float *ds = d, *dt = d + n, *db = d + 2 * (size_t)n, *dp = d + 3 * (size_t)n;
     hipError_t err = hipSuccess;
     const float* srcs[4] = {h_st, h_th, h_br, h_sp};
@@ -2316,9 +2289,9 @@ TRS_EXPORT void trs_default_mux_config(trs_mux_config* c)
 static int mux_state_ready(trs_env* e)
 {
     { int rq = quiesce(e); if (rq) return rq; }
-    if (e->mux_state) return TRS_OK;
-    HIPCHK(hipMalloc((void**)&e->mux_state, (size_t)e->n * kMuxWords * sizeof(int32_t)));
-    hipLaunchKernelGGL(trs_control_mux_init_kernel, dim3((e->n + 255) / 256), dim3(256), 0, e->sP, e->mux_state, e->n);
+    if (e->mux_state.get()) return TRS_OK;
+    HIPCHK(e->mux_state.alloc((size_t)e->n * kMuxWords * sizeof(int32_t)));
+    hipLaunchKernelGGL(trs_control_mux_init_kernel, dim3((e->n + 255) / 256), dim3(256), 0, e->sP, e->mux_state.get(), e->n);
     HIPCHK(hipGetLastError());
     e->mux_tick = 0;
     return TRS_OK;
@@ -2329,7 +2302,7 @@ TRS_EXPORT int trs_control_mux_reset(trs_env* e)
     if (!e) return fail(TRS_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(e->device));
     { int rq = quiesce(e); if (rq) return rq; }
-    if (e->mux_state) { HIPCHK(hipFree(e->mux_state)); e->mux_state = nullptr; }
+    HIPCHK(e->mux_state.reset());
     return mux_state_ready(e);
 }
 
@@ -2346,7 +2319,7 @@ TRS_EXPORT int trs_control_mux(trs_env* e, const trs_mux_config* c, const uint8_
     if (rc) return rc;
     MuxParams p{};
     p.mode = d_mode; p.us = d_us; p.ut = d_ut; p.ub = d_ub; p.as = d_as; p.at = d_at; p.ab = d_ab; p.os = d_os; p.ot = d_ot; p.ob = d_ob;
-    p.state = e->mux_state; p.n = n; p.tick = e->mux_tick;
+    p.state = e->mux_state.get(); p.n = n; p.tick = e->mux_tick;
     p.en_t = c->throttle_lock_enabled != 0; p.ticks_t = c->throttle_lock_ticks; p.val_t = c->throttle_lock_value;
     p.en_s = c->steering_lock_enabled != 0; p.ticks_s = c->steering_lock_ticks; p.val_s = c->steering_lock_value;
     if (n > 0) {
@@ -2367,7 +2340,7 @@ TRS_EXPORT int trs_control_mux_host(trs_env* e, const trs_mux_config* c, const u
     int rc = quiesce(e);
     if (!rc) rc = ensure_glue(e, nn * 4 * 9 + nn);
     if (rc) return rc;
-    float* d = e->glue;
+    float* d = e->glue.get();
     uint8_t* dm = reinterpret_cast<uint8_t*>(d + 9 * nn);
     const float* srcs[9] = {h_us, h_ut, h_ub, h_as, h_at, h_ab, h_os, h_ot, h_ob};
     hipError_t err = hipMemcpyAsync(dm, h_mode, nn, hipMemcpyHostToDevice, e->sP);
@@ -2432,16 +2405,16 @@ TRS_EXPORT int trs_scratch(trs_env* e, int slot, size_t bytes, void** d_out)
 {
     if (!e || !d_out || slot < 0 || slot >= 32) return fail(TRS_ERR_ARG, "bad scratch slot (0..31) / null argument");
     HIPCHK(hipSetDevice(e->device));
-    if (bytes > e->scratch_bytes[slot]) {
+    if (bytes > e->scratch[slot].bytes()) {
         int rc = sync_all(e);                                // nothing in flight may still use the old buffer
         if (rc) return rc;
-        (void)hipFree(e->scratch[slot]); e->scratch[slot] = nullptr; e->scratch_bytes[slot] = 0;
-        const size_t cap = align_up(std::max<size_t>(bytes, 256), 256);
-        HIPCHK(hipMalloc(&e->scratch[slot], cap));
-        HIPCHK(hipMemset(e->scratch[slot], 0, cap));
-        e->scratch_bytes[slot] = cap;
+        (void)e->scratch[slot].reset();
+        trsim::DevBuf<void> nb;                              // (the slot takes it once it is zeroed)
+        HIPCHK(nb.alloc(align_up(std::max<size_t>(bytes, 256), 256)));
+        HIPCHK(hipMemset(nb.get(), 0, nb.bytes()));
+        e->scratch[slot] = std::move(nb);
     }
-    *d_out = e->scratch[slot];
+    *d_out = e->scratch[slot].get();
     return TRS_OK;
 }
 
@@ -2472,11 +2445,11 @@ bool trs_internal_view(trs_env* e, TrsEnvView* v)
     if (quiesce(e)) return false;                            // the pilot's kernels go onto the handle's stream
     v->device = e->device; v->n = e->n; v->H = e->H; v->W = e->W; v->render = e->cfg.render;
     v->stream = e->sP;
-    v->latest_frame = (e->cfg.render && e->step_count > 0) ? e->img[(e->step_count + 1) & 1] : nullptr;
+    v->latest_frame = (e->cfg.render && e->step_count > 0) ? e->img[(e->step_count + 1) & 1].get() : nullptr;
     v->speed = e->pp.speed; v->seg_idx = e->pp.seg_idx; v->n_points = e->pp.np;
     v->ctl_steer = e->ctl_steer; v->ctl_thr = e->ctl_thr; v->ctl_brk = e->ctl_brk;
     v->step_count = e->step_count;
-    v->stats = e->stats;
+    v->stats = e->stats.get();
     return true;
 }
 void** trs_internal_pilot_slot(trs_env* e) { return e ? &e->pilot : nullptr; }
@@ -2516,7 +2489,7 @@ int trsim::sync_handle(trs_env* e) { return sync_all(e); }
 int trsim::quiesce_handle(trs_env* e) { return quiesce(e); }
 int trsim::check_fault(trs_env* e)
 {
-    if (e->fault && __atomic_load_n(e->fault, __ATOMIC_ACQUIRE) != 0ull)
+    if (e->fault.get() && __atomic_load_n(e->fault.get(), __ATOMIC_ACQUIRE) != 0ull)
         return fail(TRS_ERR_DEVICE, "a step kernel found its dynamic LDS segment at a non-zero offset and refused to run: frames and state are stale");
     return TRS_OK;
 }

@@ -36,6 +36,7 @@
 
 #include "../../include/trsim.h"
 #include "trsim_internal.hpp"
+#include "trsim_mem.hpp"
 
 #define TRS_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -1666,30 +1667,30 @@ struct ConvLayer {
     bool frame = false; int frame_f = 1, frame_lds = 0, frame_bands = 1, frame_ohb = 0;   // trs_conv_frame_kernel (3x3 stride-1 layers: F frames' input activations in LDS)
     bool frame5 = false; int frame5_lds = 0, frame5_bands = 1, frame5_ohb = 0;   // trs_conv_frame5_kernel (conv3: 5x5 stride 2 over 32 channels, one input frame / band per workgroup in LDS)
     bool res_span = false; int span_nl = 0, run_pad = 0;   // trs_conv_span_kernel (stride-2 5x5 layers: per-row input spans staged in LDS)
-    u4v* w = nullptr; float* bias = nullptr; int* goff = nullptr;
+    trsim::DevBuf<u4v> w; trsim::DevBuf<float> bias; trsim::DevBuf<int> goff;
 };
 
 struct PilotCtx {
     int n_cap = 0, H = 0, W = 0, cu_count = 256;
     ConvLayer L[9];                       // conv1..7 + dense1 (1x1 "conv" over frames) [+ dense4: the second head of cnn_2d_full_house]
-    void* act[9] = {};                    // outputs of L[i] for n_cap frames (fp16; act[7], act[8] float)
+    trsim::DevBuf<void> act[9];           // outputs of L[i] for n_cap frames (fp16; act[7], act[8] float)
     size_t act_elems[9] = {};             // per frame
     int arch = 0;                         // TRS_PILOT_SPD_CTL / CNN_2D share Keras_2D_CNN(2 outputs); TRS_PILOT_SPD_FTR (+1 feature vector); TRS_PILOT_FULL_HOUSE
     int n_layers = 8;
-    float* xblob = nullptr;               // small fp32 weights of the extra dense branches (TailExParams offsets)
+    trsim::DevBuf<float> xblob;           // small fp32 weights of the extra dense branches (TailExParams offsets)
     int xo[32] = {};                      // offsets (floats) into xblob
-    void* slab2 = nullptr; size_t slab2_bytes = 0; int last_slices2 = 1;   // dense4 partial sums
-    float *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr, *w4 = nullptr, *b4 = nullptr;
-    float* raw = nullptr;                 // [n_cap][2]
-    uint8_t* tmp_frames = nullptr; size_t tmp_cap = 0;
+    trsim::DevBuf<void> slab2; int last_slices2 = 1;   // dense4 partial sums
+    trsim::DevBuf<float> w2, b2, w3, b3, w4, b4;
+    trsim::DevBuf<float> raw;             // [n_cap][2]
+    trsim::DevBuf<uint8_t> tmp_frames; size_t tmp_cap = 0;   // room for tmp_cap bytes of frames and side inputs (+ the callers' padding)
     int last_n = 0, last_slices = 1;
     bool no_fuse = false;
     bool fuse12 = false; int fuse_r2 = 0, fuse_lds = 0; Fuse12Params fuse{};   // conv1 -> conv2 in one kernel, band form (conv1's activation stays in LDS)
     const uint8_t* last_frames = nullptr; bool act0_valid = false;           // conv1's activation is only materialised on demand (debug getter)
-    void* slab = nullptr; size_t slab_bytes = 0;   // dense1 partial sums [slices][n][100] fp32
+    trsim::DevBuf<void> slab;             // dense1 partial sums [slices][n][100] fp32
     int chain_first = -1, chain_lds = 0; ChainParams chain{};   // conv(chain_first + 1) .. conv7 in one launch (trs_conv_chain_kernel); -1: layer by layer
     bool chain_mid_valid = true;          // act[chain_first .. 5] hold the last pass (the chain never writes them; the debug getter runs the single layers on demand)
-    u4v* w2_parity = nullptr;             // conv2's granules in the band kernel's order: per kernel row the even conv1 columns (kw 0, 2, 4), then the odd (1, 3)
+    trsim::DevBuf<u4v> w2_parity;         // conv2's granules in the band kernel's order: per kernel row the even conv1 columns (kw 0, 2, 4), then the odd (1, 3)
     trs_pilot_tuning tun{};               // the kernel choices this context was loaded with (trs_pilot_set_tuning, else the defaults)
 };
 
@@ -1701,28 +1702,18 @@ unsigned short host_f2h(float f)
 }
 float host_h2f(unsigned short u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; }
 
-void free_ctx(PilotCtx* c)
-{
-    if (!c) return;
-    for (auto& l : c->L) { (void)hipFree(l.w); (void)hipFree(l.bias); (void)hipFree(l.goff); }
-    for (auto& a : c->act) (void)hipFree(a);
-    (void)hipFree(c->w2); (void)hipFree(c->b2); (void)hipFree(c->w3); (void)hipFree(c->b3); (void)hipFree(c->w4); (void)hipFree(c->b4);
-    (void)hipFree(c->raw); (void)hipFree(c->tmp_frames); (void)hipFree(c->slab); (void)hipFree(c->slab2); (void)hipFree(c->xblob); (void)hipFree(c->w2_parity);
-    delete c;
-}
-
 template <typename T>
-int upload(T** dst, const std::vector<T>& v)
+int upload(trsim::DevBuf<T>& dst, const std::vector<T>& v)
 {
-    HIPCHK(hipMalloc((void**)dst, v.size() * sizeof(T)));
-    HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    HIPCHK(dst.alloc(v.size() * sizeof(T)));
+    HIPCHK(hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return TRS_OK;
 }
 
 int launch_conv(const ConvLayer& l, const void* in, size_t in_bytes, void* out, int n_img, hipStream_t s, int cu_count)
 {
     ConvParams p{};
-    p.in = in; p.w = l.w; p.bias = l.bias; p.goff = l.goff; p.out = out;
+    p.in = in; p.w = l.w.get(); p.bias = l.bias.get(); p.goff = l.goff.get(); p.out = out;
     if (in_bytes > 0x7FFFFFFFull) return trs_internal_fail(TRS_ERR_LIMIT, "activation larger than 2 GiB: lower the batch");
     p.in_bytes = (int)in_bytes;
     p.N = n_img; p.IH = l.IH; p.IW = l.IW; p.CIN = l.CIN; p.OH = l.OH; p.OW = l.OW; p.COUT = l.COUT; p.COUT_PAD = l.COUT_PAD; p.S = l.S;
@@ -1734,7 +1725,7 @@ int launch_conv(const ConvLayer& l, const void* in, size_t in_bytes, void* out, 
     p.KH = l.KH; p.KW = l.KW; p.run_pad = l.run_pad; p.cg = l.u8in ? 0 : l.CIN / 8; p.span_nl = l.span_nl;
     if (l.frame5) {                                                         // one persistent 8-wave workgroup per CU: a unit (frame or row band) computed from one LDS buffer, the next staged into the other
         Frame5Params q{};
-        q.in = static_cast<const u4v*>(in); q.w = l.w; q.bias = l.bias; q.out = static_cast<unsigned short*>(out);
+        q.in = static_cast<const u4v*>(in); q.w = l.w.get(); q.bias = l.bias.get(); q.out = static_cast<unsigned short*>(out);
         q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.F = 1; q.ev = (l.IW + 1) / 2; q.COUT = l.COUT;
         q.bands = l.frame5_bands; q.ohb = l.frame5_ohb; q.ihb = l.frame5_bands == 1 ? l.IH : 2 * l.frame5_ohb + 3;
         q.magic_ow = (unsigned)((0x100000000ull + (unsigned)l.OW - 1u) / (unsigned)l.OW);
@@ -1745,7 +1736,7 @@ int launch_conv(const ConvLayer& l, const void* in, size_t in_bytes, void* out, 
     }
     if (l.frame) {
         FrameConvParams q{};
-        q.in = static_cast<const u4v*>(in); q.w = l.w; q.bias = l.bias; q.out = static_cast<unsigned short*>(out);
+        q.in = static_cast<const u4v*>(in); q.w = l.w.get(); q.bias = l.bias.get(); q.out = static_cast<unsigned short*>(out);
         q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.COUT = l.COUT; q.COUT_PAD = l.COUT_PAD; q.KH = l.KH; q.KW = l.KW;
         q.F = l.frame_f; q.cg = l.CIN / 8; q.cgs = q.cg == 8 ? 3 : 4; q.relu = l.relu;
         q.bands = l.frame_bands; q.ohb = l.frame_ohb; q.ihb = l.frame_ohb + l.KH - 1;
@@ -1805,7 +1796,7 @@ void dense_plan(const ConvLayer& l, int n, int cu_count, const trs_pilot_tuning&
 int launch_dense(PilotCtx* c, const ConvLayer& l, const void* in, int n, void* slab, hipStream_t s)
 {
     DenseParams q{};
-    q.act = static_cast<const u4v*>(in); q.w = l.w; q.bias = l.bias; q.slab = static_cast<float*>(slab);
+    q.act = static_cast<const u4v*>(in); q.w = l.w.get(); q.bias = l.bias.get(); q.slab = static_cast<float*>(slab);
     int nf = 1;
     q.n = n; q.G = l.G;
     dense_plan(l, n, c->cu_count, c->tun, &q.gps, &q.KS, &nf);
@@ -1832,7 +1823,7 @@ int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n)
         if (in_bytes > 0x7FFFFFFFull) return trs_internal_fail(TRS_ERR_LIMIT, "frames larger than 2 GiB: lower the batch");
         Fuse12Params q = c->fuse;
         q.frames = d_frames; q.frames_bytes = (int)in_bytes; q.N = n;
-        q.c2.out = c->act[1]; q.c2.M = n * c->L[1].OH * c->L[1].OW;
+        q.c2.out = c->act[1].get(); q.c2.M = n * c->L[1].OH * c->L[1].OW;
         q.c2.nt_out = 0;
         int grid = std::max(1, std::min(n * q.bands * std::max(1, q.wsplit), c->cu_count));
         // rolling bands when there are enough (frame, part) streams for every CU (a small batch keeps one band per workgroup: more parallelism)
@@ -1846,7 +1837,7 @@ int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n)
             hipLaunchKernelGGL(trs_conv12_band_kernel<false>, dim3(grid), dim3(1024), c->fuse_lds, v.stream, q);
         }
         HIPCHK(hipGetLastError());
-        in = c->act[1];
+        in = c->act[1].get();
         in_bytes = (size_t)n * c->act_elems[1] * 2;
         first = 2;
     }
@@ -1854,43 +1845,39 @@ int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n)
     for (int i = first; i < 8; ++i) {
         if (i == c->chain_first) {                                          // conv(i + 1) .. conv7 in one launch, activations in LDS
             ChainParams q = c->chain;
-            q.in = static_cast<const u4v*>(in); q.out = static_cast<unsigned short*>(c->act[6]); q.N = n;
+            q.in = static_cast<const u4v*>(in); q.out = static_cast<unsigned short*>(c->act[6].get()); q.N = n;
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_conv_chain_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, c->chain_lds));
             hipLaunchKernelGGL(trs_conv_chain_kernel<512>, dim3((n + q.F - 1) / q.F), dim3(512), c->chain_lds, v.stream, q);
             HIPCHK(hipGetLastError());
-            in = c->act[6];
+            in = c->act[6].get();
             in_bytes = (size_t)n * c->act_elems[6] * 2;
             i = 6;
             continue;
         }
-        void* out = c->act[i];
+        void* out = c->act[i].get();
         if (i == 7) {                                                       // dense1: one fp32 slab per K slice, added in order by the tail kernel
             { int gps; dense_plan(c->L[7], n, c->cu_count, c->tun, &gps, &c->last_slices); }
             const size_t need = (size_t)c->last_slices * n * c->act_elems[7] * sizeof(float);
-            if (c->slab_bytes < need) {
+            if (c->slab.bytes() < need) {
                 HIPCHK(hipStreamSynchronize(v.stream));
-                (void)hipFree(c->slab); c->slab = nullptr; c->slab_bytes = 0;
-                HIPCHK(hipMalloc(&c->slab, need));
-                c->slab_bytes = need;
+                HIPCHK(c->slab.reserve(need));
             }
-            out = c->slab;
+            out = c->slab.get();
         }
         int rc = i == 7 ? launch_dense(c, c->L[7], in, n, out, v.stream) : launch_conv(c->L[i], in, in_bytes, out, n, v.stream, c->cu_count);
         if (rc) return rc;
         if (i == 0) c->act0_valid = true;
-        in = c->act[i];
+        in = c->act[i].get();
         in_bytes = (size_t)n * c->act_elems[i] * (c->L[i].out_f32 ? 4 : 2);
     }
     if (c->arch == TRS_PILOT_FULL_HOUSE) {                                 // the steering head's dense4 reads conv7's output as well
         { int gps; dense_plan(c->L[8], n, c->cu_count, c->tun, &gps, &c->last_slices2); }
         const size_t need = (size_t)c->last_slices2 * n * c->act_elems[8] * sizeof(float);
-        if (c->slab2_bytes < need) {
+        if (c->slab2.bytes() < need) {
             HIPCHK(hipStreamSynchronize(v.stream));
-            (void)hipFree(c->slab2); c->slab2 = nullptr; c->slab2_bytes = 0;
-            HIPCHK(hipMalloc(&c->slab2, need));
-            c->slab2_bytes = need;
+            HIPCHK(c->slab2.reserve(need));
         }
-        int rc = launch_dense(c, c->L[8], c->act[6], n, c->slab2, v.stream);
+        int rc = launch_dense(c, c->L[8], c->act[6].get(), n, c->slab2.get(), v.stream);
         if (rc) return rc;
     }
     c->last_n = n;
@@ -1911,7 +1898,7 @@ int check_model_type(const PilotCtx* c, const trs_pilot_config* cfg)
 TailParams make_tail(const PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io)
 {
     TailParams t{};
-    t.w2 = c->w2; t.b2 = c->b2; t.w3 = c->w3; t.b3 = c->b3; t.w4 = c->w4; t.b4 = c->b4;
+    t.w2 = c->w2.get(); t.b2 = c->b2.get(); t.w3 = c->w3.get(); t.b3 = c->b3.get(); t.w4 = c->w4.get(); t.b4 = c->b4.get();
     t.raw_out = raw_out; t.n = n; t.act = act ? 1 : 0;
     if (act) {
         t.speed = v.speed; t.steer = v.ctl_steer; t.thr = v.ctl_thr; t.brk = v.ctl_brk;
@@ -1927,9 +1914,9 @@ int run_tail(PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_
 {
     if (c->arch != TRS_PILOT_SPD_CTL) {
         TailExParams t{};
-        t.h1 = static_cast<const float*>(c->slab); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->act_elems[7];
-        t.h4 = static_cast<const float*>(c->slab2); t.h4_slices = c->last_slices2; t.h4_stride = (size_t)n * c->act_elems[8];
-        t.blob = c->xblob; std::memcpy(t.xo, c->xo, sizeof t.xo);
+        t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->act_elems[7];
+        t.h4 = static_cast<const float*>(c->slab2.get()); t.h4_slices = c->last_slices2; t.h4_stride = (size_t)n * c->act_elems[8];
+        t.blob = c->xblob.get(); std::memcpy(t.xo, c->xo, sizeof t.xo);
         t.arch = c->arch; t.f1 = c->arch == TRS_PILOT_SPD_FTR ? 4 : 16; t.f2 = 2 * t.f1; t.f3 = 4 * t.f1;
         t.speed = (io && io->speed) ? io->speed : v.speed; t.segment = io ? io->segment : nullptr; t.seg_idx = v.seg_idx; t.np = v.n_points > 0 ? v.n_points : 1;
         t.raw_out = raw_out; t.n = n; t.act = act ? 1 : 0;
@@ -1944,7 +1931,7 @@ int run_tail(PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_
         return TRS_OK;
     }
     TailParams t = make_tail(c, v, n, raw_out, cfg, act, io);
-    t.h1 = static_cast<const float*>(c->slab); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->act_elems[7];
+    t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->act_elems[7];
     hipLaunchKernelGGL(trs_pilot_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, v.stream, t);
     HIPCHK(hipGetLastError());
     return TRS_OK;
@@ -1960,7 +1947,7 @@ int forward_and_tail(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, 
 
 }  // namespace
 
-void trs_pilot_free(void* ctx) { free_ctx(static_cast<PilotCtx*>(ctx)); }
+void trs_pilot_free(void* ctx) { delete static_cast<PilotCtx*>(ctx); }
 
 TRS_EXPORT void trs_default_pilot_config(trs_pilot_config* c)
 {
@@ -1998,9 +1985,9 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
     for (int i = 0; i < n_arrays; ++i) if (!arr[i]) return trs_internal_fail(TRS_ERR_ARG, "null weight array");
     HIPCHK(hipSetDevice(v.device));
     void** slot = trs_internal_pilot_slot(e);
-    if (*slot) { HIPCHK(hipStreamSynchronize(v.stream)); free_ctx(static_cast<PilotCtx*>(*slot)); *slot = nullptr; }
+    if (*slot) { HIPCHK(hipStreamSynchronize(v.stream)); delete static_cast<PilotCtx*>(*slot); *slot = nullptr; }
     // the context under construction is freed on EVERY early return below (HIPCHK included); released into the handle at the end
-    std::unique_ptr<PilotCtx, void (*)(PilotCtx*)> guard(new PilotCtx(), free_ctx);
+    std::unique_ptr<PilotCtx> guard(new PilotCtx());
     PilotCtx* const c = guard.get();
     c->n_cap = v.n; c->H = v.H; c->W = v.W;
     trs_default_pilot_tuning(&c->tun);
@@ -2134,17 +2121,17 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
         for (int co = 0; co < l.COUT; ++co) bias[co] = B[co];
         std::vector<u4v> wv(wp.size() / 8);
         std::memcpy(wv.data(), wp.data(), wp.size() * 2);
-        int rc = upload(&l.w, wv); if (!rc) rc = upload(&l.bias, bias); if (!rc) rc = upload(&l.goff, goff);
+        int rc = upload(l.w, wv); if (!rc) rc = upload(l.bias, bias); if (!rc) rc = upload(l.goff, goff);
         if (rc) return rc;
         c->act_elems[i] = (size_t)l.OH * l.OW * l.COUT;
-        HIPCHK(hipMalloc(&c->act[i], (size_t)c->n_cap * c->act_elems[i] * (l.out_f32 ? 4 : 2) + 64));
+        HIPCHK(c->act[i].alloc((size_t)c->n_cap * c->act_elems[i] * (l.out_f32 ? 4 : 2) + 64));
         if (i < 7) { ih = l.OH; iw = l.OW; }
     }
-    auto up = [&](float** dst, const float* src, size_t n) -> int { std::vector<float> t(src, src + n); return upload(dst, t); };
+    auto up = [&](trsim::DevBuf<float>& dst, const float* src, size_t n) -> int { std::vector<float> t(src, src + n); return upload(dst, t); };
     const int nz = c->arch == TRS_PILOT_FULL_HOUSE ? 1 : 2;                // outputs of the first head
-    int rc = up(&c->w2, arr[16], 100 * 50); if (!rc) rc = up(&c->b2, arr[17], 50);
-    if (!rc) rc = up(&c->w3, arr[18], 50 * 25); if (!rc) rc = up(&c->b3, arr[19], 25);
-    if (!rc) rc = up(&c->w4, arr[20], 25 * nz); if (!rc) rc = up(&c->b4, arr[21], nz);
+    int rc = up(c->w2, arr[16], 100 * 50); if (!rc) rc = up(c->b2, arr[17], 50);
+    if (!rc) rc = up(c->w3, arr[18], 50 * 25); if (!rc) rc = up(c->b3, arr[19], 25);
+    if (!rc) rc = up(c->w4, arr[20], 25 * nz); if (!rc) rc = up(c->b4, arr[21], nz);
     if (rc) return rc;
     if (c->arch != TRS_PILOT_SPD_CTL) {        // the small fp32 branches of the tail: one blob, offsets by XO_*
         const int F = (int)c->L[7].CIN;
@@ -2163,16 +2150,16 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
             put(XO_W5, arr[36], 100 * 50); put(XO_B5, arr[37], 50); put(XO_W6, arr[38], 50 * 25); put(XO_B6, arr[39], 25);
             put(XO_W7, arr[40], 25); put(XO_B7, arr[41], 1);
         }
-        rc = upload(&c->xblob, blob);
+        rc = upload(c->xblob, blob);
         if (rc) return rc;
     }
     {   // conv1 -> conv2 fusion: needs the 5x5/2 + 5x5/2 head of Keras_2D_CNN and an LDS tile of 2 R2 + 3 conv1 rows
         const ConvLayer& l0 = c->L[0]; const ConvLayer& l1 = c->L[1];
         Fuse12Params& q = c->fuse;
         q = Fuse12Params{};
-        q.w1 = l0.w; q.b1 = l0.bias; q.w2 = l1.w;
+        q.w1 = l0.w.get(); q.b1 = l0.bias.get(); q.w2 = l1.w.get();
         q.c2 = ConvParams{};
-        q.c2.bias = l1.bias; q.c2.COUT = l1.COUT; q.c2.COUT_PAD = l1.COUT_PAD; q.c2.relu = 1; q.c2.oscale = 1.0f;
+        q.c2.bias = l1.bias.get(); q.c2.COUT = l1.COUT; q.c2.COUT_PAD = l1.COUT_PAD; q.c2.relu = 1; q.c2.oscale = 1.0f;
         q.IH = l0.IH; q.IW = l0.IW; q.OH1 = l0.OH; q.OW1 = l0.OW; q.OH2 = l1.OH; q.OW2 = l1.OW;
         {   // can conv1 leave binary16's range?  Its inputs are pixels / 256 <= 1, so |output| <= |bias| + sum |w| (x 256 / 255 and the binary16 rounding of the
             // weights: 1.01 covers both).  Below 65504 for every output channel the fused head's conv1 epilogue needs no saturation step.
@@ -2229,15 +2216,15 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
     if (c->fuse12) {                            // the band kernel reads conv1 columns by parity: conv2's granules in that order
         const ConvLayer& l1 = c->L[1];
         std::vector<u4v> orig((size_t)l1.G_pad * l1.COUT_PAD), perm(orig.size());
-        HIPCHK(hipMemcpy(orig.data(), l1.w, orig.size() * sizeof(u4v), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(orig.data(), l1.w.get(), orig.size() * sizeof(u4v), hipMemcpyDeviceToHost));
         for (int kh = 0; kh < 5; ++kh)
             for (int sl = 0; sl < 16; ++sl) {
                 const int src = sl < 9 ? (2 * (sl / 3)) * 3 + sl % 3 : (sl < 15 ? (2 * ((sl - 9) / 3) + 1) * 3 + (sl - 9) % 3 : 15);   // granule kw * 3 + c8 of the kernel row
                 std::memcpy(&perm[(size_t)(kh * 16 + sl) * l1.COUT_PAD], &orig[(size_t)(kh * 16 + src) * l1.COUT_PAD], (size_t)l1.COUT_PAD * sizeof(u4v));
             }
-        int rcw = upload(&c->w2_parity, perm);
+        int rcw = upload(c->w2_parity, perm);
         if (rcw) return rcw;
-        c->fuse.w2 = c->w2_parity;
+        c->fuse.w2 = c->w2_parity.get();
     }
     {   // conv4..conv7 (or conv5..conv7) as one launch when F frames of all their activations fit LDS; TRS_PILOT_CHAIN = 0: off, 3 / 4: layers
         const int want = T.chain_layers;
@@ -2292,13 +2279,13 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
                         if (m < best || (m == best && wv > best_waves)) { best = m; best_waves = wv; nt = cnt; }
                     }
                     auto magic = [](int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1u) / (unsigned)d); };
-                    q.L[j] = ChainLayer{l.w, l.bias, l.IH, l.IW, l.OH, l.OW, l.COUT, l.CIN / 8, l.CIN / 8 == 8 ? 3 : 4, nt, 2, magic(l.OH * l.OW), magic(l.OW)};
+                    q.L[j] = ChainLayer{l.w.get(), l.bias.get(), l.IH, l.IW, l.OH, l.OW, l.COUT, l.CIN / 8, l.CIN / 8 == 8 ? 3 : 4, nt, 2, magic(l.OH * l.OW), magic(l.OW)};
                 }
                 c->chain_first = first; c->chain_lds = (int)total;
             }
         }
     }
-    HIPCHK(hipMalloc((void**)&c->raw, (size_t)c->n_cap * 2 * sizeof(float)));
+    HIPCHK(c->raw.alloc((size_t)c->n_cap * 2 * sizeof(float)));
     *slot = guard.release();
     return TRS_OK;
 }
@@ -2317,7 +2304,7 @@ TRS_EXPORT int trs_pilot_forward(trs_env* e, const uint8_t* d_frames, int n_imag
     }
     if (c->arch != TRS_PILOT_SPD_CTL && n_images != v.n)
         return trs_internal_fail(TRS_ERR_ARG, "this model type also reads speed (and segment): use trs_pilot_forward_ex, or n_images == n_envs for the env's own");
-    return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw, nullptr, false);
+    return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw.get(), nullptr, false);
 }
 
 TRS_EXPORT int trs_pilot_forward_ex(trs_env* e, const uint8_t* d_frames, const float* d_speed, const float* d_segment, int n_images, float* d_out)
@@ -2334,7 +2321,7 @@ TRS_EXPORT int trs_pilot_forward_ex(trs_env* e, const uint8_t* d_frames, const f
         d_frames = v.latest_frame;
     }
     const ActIo io{d_speed, d_segment, nullptr, nullptr, nullptr, nullptr};
-    return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw, nullptr, false, &io);
+    return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw.get(), nullptr, false, &io);
 }
 
 TRS_EXPORT int trs_pilot_forward_host_ex(trs_env* e, const uint8_t* h_frames, const float* h_speed, const float* h_segment, int n_images, float* h_out)
@@ -2349,19 +2336,19 @@ TRS_EXPORT int trs_pilot_forward_host_ex(trs_env* e, const uint8_t* h_frames, co
     const size_t bytes = (size_t)n_images * c->H * c->W * 3, extra = (size_t)n_images * 8;
     if (bytes + extra > c->tmp_cap) {
         HIPCHK(hipStreamSynchronize(v.stream));
-        (void)hipFree(c->tmp_frames); c->tmp_frames = nullptr; c->tmp_cap = 0;
-        HIPCHK(hipMalloc((void**)&c->tmp_frames, bytes + extra + 128));
+        c->tmp_cap = 0;
+        HIPCHK(c->tmp_frames.alloc(bytes + extra + 128));
         c->tmp_cap = bytes + extra;
     }
-    float* d_spd = reinterpret_cast<float*>(c->tmp_frames + ((bytes + 63) & ~(size_t)63));
+    float* d_spd = reinterpret_cast<float*>(c->tmp_frames.get() + ((bytes + 63) & ~(size_t)63));
     float* d_seg = d_spd + n_images;
-    HIPCHK(hipMemcpyAsync(c->tmp_frames, h_frames, bytes, hipMemcpyHostToDevice, v.stream));
+    HIPCHK(hipMemcpyAsync(c->tmp_frames.get(), h_frames, bytes, hipMemcpyHostToDevice, v.stream));
     if (h_speed) HIPCHK(hipMemcpyAsync(d_spd, h_speed, (size_t)n_images * 4, hipMemcpyHostToDevice, v.stream));
     if (h_segment) HIPCHK(hipMemcpyAsync(d_seg, h_segment, (size_t)n_images * 4, hipMemcpyHostToDevice, v.stream));
-    int rc = c->arch == TRS_PILOT_SPD_CTL ? trs_pilot_forward(e, c->tmp_frames, n_images, c->raw)
-                                          : trs_pilot_forward_ex(e, c->tmp_frames, h_speed ? d_spd : nullptr, h_segment ? d_seg : nullptr, n_images, c->raw);
+    int rc = c->arch == TRS_PILOT_SPD_CTL ? trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get())
+                                          : trs_pilot_forward_ex(e, c->tmp_frames.get(), h_speed ? d_spd : nullptr, h_segment ? d_seg : nullptr, n_images, c->raw.get());
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_out, c->raw, (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
     trs_internal_count(e, (uint64_t)n_images * 2 * sizeof(float), (uint64_t)bytes);
     HIPCHK(hipStreamSynchronize(v.stream));
     return TRS_OK;
@@ -2378,14 +2365,14 @@ TRS_EXPORT int trs_pilot_forward_host(trs_env* e, const uint8_t* h_frames, int n
     const size_t bytes = (size_t)n_images * c->H * c->W * 3;
     if (bytes > c->tmp_cap) {
         HIPCHK(hipStreamSynchronize(v.stream));
-        (void)hipFree(c->tmp_frames); c->tmp_frames = nullptr; c->tmp_cap = 0;
-        HIPCHK(hipMalloc((void**)&c->tmp_frames, bytes + 64));
+        c->tmp_cap = 0;
+        HIPCHK(c->tmp_frames.alloc(bytes + 64));
         c->tmp_cap = bytes;
     }
-    HIPCHK(hipMemcpyAsync(c->tmp_frames, h_frames, bytes, hipMemcpyHostToDevice, v.stream));
-    int rc = trs_pilot_forward(e, c->tmp_frames, n_images, c->raw);
+    HIPCHK(hipMemcpyAsync(c->tmp_frames.get(), h_frames, bytes, hipMemcpyHostToDevice, v.stream));
+    int rc = trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get());
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_out, c->raw, (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
     trs_internal_count(e, (uint64_t)n_images * 2 * sizeof(float), (uint64_t)n_images * c->H * c->W * 3);
     HIPCHK(hipStreamSynchronize(v.stream));
     return TRS_OK;
@@ -2402,14 +2389,14 @@ TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t
     if (n_floats != total) return trs_internal_fail(TRS_ERR_ARG, "size mismatch");
     HIPCHK(hipSetDevice(v.device));
     if (layer == 0 && !c->act0_valid) {                                     // the fused head never wrote conv1's activation: run the unfused conv1 now
-        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * c->H * c->W * 3, c->act[0], c->last_n, v.stream, c->cu_count);
+        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * c->H * c->W * 3, c->act[0].get(), c->last_n, v.stream, c->cu_count);
         if (rc) return rc;
         c->act0_valid = true;
     }
     if (c->chain_first >= 0 && layer >= c->chain_first && layer < 6 && !c->chain_mid_valid) {   // the chain kept these activations in LDS: run the single layers now
         for (int j = c->chain_first; j < 6; ++j) {
-            const void* src = j == 0 ? (const void*)c->last_frames : c->act[j - 1];
-            int rc = launch_conv(c->L[j], src, (size_t)c->last_n * c->act_elems[j - 1] * 2, c->act[j], c->last_n, v.stream, c->cu_count);
+            const void* src = j == 0 ? (const void*)c->last_frames : c->act[j - 1].get();
+            int rc = launch_conv(c->L[j], src, (size_t)c->last_n * c->act_elems[j - 1] * 2, c->act[j].get(), c->last_n, v.stream, c->cu_count);
             if (rc) return rc;
         }
         c->chain_mid_valid = true;
@@ -2419,14 +2406,14 @@ TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t
         std::vector<float> part(total);
         for (size_t i = 0; i < total; ++i) h_dst[i] = 0.0f;
         for (int sl = 0; sl < c->last_slices; ++sl) {
-            HIPCHK(hipMemcpy(part.data(), static_cast<const float*>(c->slab) + (size_t)sl * total, total * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(part.data(), static_cast<const float*>(c->slab.get()) + (size_t)sl * total, total * 4, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < total; ++i) h_dst[i] += part[i];
         }
         for (size_t i = 0; i < total; ++i) h_dst[i] = h_dst[i] > 0.0f ? h_dst[i] : 0.0f;
         return TRS_OK;
     }
     std::vector<unsigned short> tmp(total);
-    HIPCHK(hipMemcpy(tmp.data(), c->act[layer], total * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), c->act[layer].get(), total * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < total; ++i) h_dst[i] = host_h2f(tmp[i]);
     return TRS_OK;
 }
@@ -2435,13 +2422,13 @@ TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t
 static int materialise_layers(PilotCtx* c, const TrsEnvView& v, int upto)
 {
     if (!c->act0_valid) {
-        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * c->H * c->W * 3, c->act[0], c->last_n, v.stream, c->cu_count);
+        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * c->H * c->W * 3, c->act[0].get(), c->last_n, v.stream, c->cu_count);
         if (rc) return rc;
         c->act0_valid = true;
     }
     if (c->chain_first >= 0 && upto >= c->chain_first && !c->chain_mid_valid) {
         for (int j = c->chain_first; j < 6; ++j) {
-            int rc = launch_conv(c->L[j], c->act[j - 1], (size_t)c->last_n * c->act_elems[j - 1] * 2, c->act[j], c->last_n, v.stream, c->cu_count);
+            int rc = launch_conv(c->L[j], c->act[j - 1].get(), (size_t)c->last_n * c->act_elems[j - 1] * 2, c->act[j].get(), c->last_n, v.stream, c->cu_count);
             if (rc) return rc;
         }
         c->chain_mid_valid = true;
@@ -2463,7 +2450,7 @@ TRS_EXPORT int trs_pilot_range_check(trs_env* e, uint64_t h_out[8])
     for (int i = 0; i < 7; ++i) {
         const size_t n = (size_t)c->last_n * c->act_elems[i];
         const int grid = (int)std::min<size_t>(4096, (n + 255) / 256);
-        hipLaunchKernelGGL(trs_pilot_count_sat_kernel, dim3(grid), dim3(256), 0, v.stream, static_cast<const unsigned short*>(c->act[i]), n, scratch + i, v.stats + 3);
+        hipLaunchKernelGGL(trs_pilot_count_sat_kernel, dim3(grid), dim3(256), 0, v.stream, static_cast<const unsigned short*>(c->act[i].get()), n, scratch + i, v.stats + 3);
     }
     HIPCHK(hipGetLastError());
     unsigned long long host[8] = {};
@@ -2498,7 +2485,7 @@ TRS_EXPORT int trs_pilot_act(trs_env* e, const trs_pilot_config* cfg, const uint
         return TRS_OK;
     }
     const ActIo io{d_speed, d_segment, d_mode, d_steer, d_thr, d_brk};
-    return forward_and_tail(c, v, d_frames, n, c->raw, cfg, true, &io);
+    return forward_and_tail(c, v, d_frames, n, c->raw.get(), cfg, true, &io);
 }
 
 TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_steps)
@@ -2515,7 +2502,7 @@ TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_ste
     for (int k = 0; k < n_steps; ++k) {
         trs_internal_view(e, &v);
         if (v.latest_frame) {                       // KerasPilot.step on the frame of the previous tick
-            int rc = forward_and_tail(c, v, v.latest_frame, v.n, c->raw, cfg, true);
+            int rc = forward_and_tail(c, v, v.latest_frame, v.n, c->raw.get(), cfg, true);
             if (rc) return rc;
         } else {                                    // args[0] is None -> (0.0, 0.0, 0.0) (keras_pilot.py:46-47)
             hipLaunchKernelGGL(trs_zero_controls_kernel, dim3((v.n + 255) / 256), dim3(256), 0, v.stream, v.ctl_steer, v.ctl_thr, v.ctl_brk, v.n);

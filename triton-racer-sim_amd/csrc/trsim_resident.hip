@@ -115,8 +115,8 @@ struct Resident {
     bool enabled = false, running = false;
     bool broken = false;                 // a worker gave up (bounded wait): some workgroups may have taken a step others did not — the env
                                          // state is undefined until the track is loaded again; every resident call fails meanwhile
-    Mailbox* mb = nullptr;
-    DevCtl* dc = nullptr;
+    PinnedBuf<Mailbox> mb;               // (mapped, coherent: the worker and the host talk through it)
+    DevBuf<DevCtl> dc;
     hipStream_t sC = nullptr;            // copies while the worker owns the handle's stream
     uint64_t base = 0;                   // steps [base, step_count) were handed to the worker since the last quiesce
     uint64_t seen_done = 0;              // every step below this index has been observed complete
@@ -134,7 +134,7 @@ struct Resident {
                                          // between two generations is where ANOTHER process's kernels get CUs — its launches, or its own worker,
                                          // which then holds the GPU for its 50 ms: processes that share a GPU take turns at the reference's tick
                                          // rate (20 Hz, car_templates/manage.py:38) or better, and a worker restart (~35 us) per 50 ms costs 0.1 %
-    unsigned char* hctl = nullptr;       // pinned staging for host-array controls: [kSlots] x (3 float[n] + uint8[n])
+    PinnedBuf<> hctl;                    // pinned staging for host-array controls: [kSlots] x (3 float[n] + uint8[n])
     size_t hctl_slot = 0;
     int lds_bytes = 0, lds_off_ctl = 0, lds_off_dyn = 0, lds_off_hill = 0;
     long long pw_capacity_envs = 0;      // physics-only handles: envs whose workgroups the GPU holds at once (worker_fits)
@@ -1132,7 +1132,7 @@ int evict(trs_env* other);
 int worker_launch(trs_env* e, uint64_t start)
 {
     Resident* R = e->res;
-    Mailbox* mb = R->mb;
+    Mailbox* mb = R->mb.get();
     { int rc = worker_fits(e); if (rc) return rc; }
     const WorkerKernel kernel = e->cfg.render ? kWorkerKernels[variant_of(e)] : nullptr;
     if (e->cfg.render && !kernel)
@@ -1148,9 +1148,9 @@ int worker_launch(trs_env* e, uint64_t start)
     WParams wp{};
     wp.ph = e->pp; wp.ph.synth = 0; wp.ph.write_cam = 0; wp.ph.n_steps = 0; wp.ph.step_off = 0; wp.ph.ctl_stride = 0;
     wp.ra = e->rp;
-    wp.img0 = e->img[0]; wp.img1 = e->img[1]; wp.dep0 = e->depth[0]; wp.dep1 = e->depth[1];
+    wp.img0 = e->img[0].get(); wp.img1 = e->img[1].get(); wp.dep0 = e->depth[0].get(); wp.dep1 = e->depth[1].get();
     e->uniform_ok[0] = e->uniform_ok[1] = false;            // (launch_step's bookkeeping of which buffer holds whole frames of the current palette: not kept across a worker)
-    wp.mb = mb; wp.dc = R->dc;
+    wp.mb = mb; wp.dc = R->dc.get();
     wp.start = start;
     wp.idle_ticks = (unsigned long long)R->idle_us * 100ull;
     wp.life_ticks = (unsigned long long)R->life_us * 100ull;   // 50 ms by default: then the dispatcher leaves and the host starts a new worker at its next post
@@ -1161,7 +1161,7 @@ int worker_launch(trs_env* e, uint64_t start)
     wp.n_blocks = grid;
     // the control block is set up by a one-workgroup kernel in front of the worker — unless the previous worker's normal exit already did that for exactly this start
     // (handle_exit): the set-up then sits in the stream's idle time instead of in front of every launch (~4 us per worker start)
-    if (!(R->dc_ready && R->dc_ready_for == start)) hipLaunchKernelGGL(trs_worker_init_kernel, dim3(1), dim3(256), 0, e->sP, R->dc, (u64)start);
+    if (!(R->dc_ready && R->dc_ready_for == start)) hipLaunchKernelGGL(trs_worker_init_kernel, dim3(1), dim3(256), 0, e->sP, R->dc.get(), (u64)start);
     R->dc_ready = false;
     if (e->cfg.render) {
         wp.fp = fparams_of(e, R->lds_off_dyn);              // (the DYN instantiations: what trs_step_kernel's get, trsim_hip.hip launch_step)
@@ -1231,7 +1231,7 @@ int handle_exit(trs_env* e, bool relaunch = true)
     if (host_load(&R->mb->started)) R->retry_ms = kRetryMs0;   // this launch had the GPU: the sharing that caused an earlier fallback is over
     if (consumed < posted && relaunch) return worker_launch(e, consumed);
     if (consumed == posted) {                               // nothing left to serve: the next launch of this handle starts here — its control block is set up now
-        hipLaunchKernelGGL(trs_worker_init_kernel, dim3(1), dim3(256), 0, e->sP, R->dc, (u64)consumed);
+        hipLaunchKernelGGL(trs_worker_init_kernel, dim3(1), dim3(256), 0, e->sP, R->dc.get(), (u64)consumed);
         if (hipGetLastError() == hipSuccess) { R->dc_ready = true; R->dc_ready_for = consumed; }
     }
     return TRS_OK;
@@ -1266,7 +1266,7 @@ int wait_done(trs_env* e, uint64_t s)
 {
     Resident* R = e->res;
     if (s < R->seen_done) return TRS_OK;
-    Mailbox* mb = R->mb;
+    Mailbox* mb = R->mb.get();
     const auto t0 = std::chrono::steady_clock::now();
     auto fell_back = [&]() -> int {                           // the posted steps went onto the stream as launches: wait for the stream
         RCHK(hipStreamSynchronize(e->sP));
@@ -1301,10 +1301,10 @@ int wait_done(trs_env* e, uint64_t s)
 int ensure_resident(trs_env* e)
 {
     Resident* R = e->res;
-    if (R->mb) return TRS_OK;
-    RCHK(hipHostMalloc((void**)&R->mb, sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(R->mb, 0, sizeof(Mailbox));
-    RCHK(hipMalloc((void**)&R->dc, sizeof(DevCtl)));
+    if (R->mb.get()) return TRS_OK;
+    RCHK(R->mb.alloc(sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(R->mb.get(), 0, sizeof(Mailbox));
+    RCHK(R->dc.alloc(sizeof(DevCtl)));
     // The copy stream must not share a hardware queue with the handle's stream: a copy queued behind the worker kernel on the same queue would
     // wait until the worker leaves (seen in round 4: 100 ms = idle_us per trs_fetch_outputs in a process that had created many streams, where
     // the runtime's least-used-queue choice put both streams on one queue).  The runtime keeps a separate pool of hardware queues per stream
@@ -1315,7 +1315,7 @@ int ensure_resident(trs_env* e)
         RCHK(hipStreamCreateWithPriority(&R->sC, hipStreamNonBlocking, greatest));
     }
     R->hctl_slot = ((size_t)e->n * 13 + 63) & ~(size_t)63;
-    RCHK(hipHostMalloc((void**)&R->hctl, R->hctl_slot * kSlots, hipHostMallocMapped | hipHostMallocCoherent));
+    RCHK(R->hctl.alloc(R->hctl_slot * kSlots, hipHostMallocMapped | hipHostMallocCoherent));
     return TRS_OK;
 }
 
@@ -1331,7 +1331,7 @@ bool resident_on(const trs_env* e) { return e && e->res && e->res->enabled; }
 void resident_retry(trs_env* e)
 {
     Resident* R = e ? e->res : nullptr;
-    if (!R || R->enabled || !R->fell_back || R->broken || !R->mb) return;
+    if (!R || R->enabled || !R->fell_back || R->broken || !R->mb.get()) return;
     DevLock lock(e);
     if (std::chrono::steady_clock::now() - R->t_fallback < std::chrono::milliseconds(R->retry_ms)) return;
     if (worker_fits(e) != TRS_OK) return;
@@ -1350,7 +1350,7 @@ int resident_post(trs_env* e, const float* st, const float* th, const float* br,
 {
     DevLock lock(e);
     Resident* R = e->res;
-    Mailbox* mb = R->mb;
+    Mailbox* mb = R->mb.get();
     *n_done = 0;
     if (R->broken) return trs_internal_fail(TRS_ERR_DEVICE, "a resident worker gave up earlier: the env state is undefined, load the track again (trs_load_track)");
     for (int k = 0; k < n; ++k) {
@@ -1420,7 +1420,7 @@ void resident_note_launch(trs_env* e)
 int resident_quiesce(trs_env* e)
 {
     Resident* R = e->res;
-    if (!R || !R->mb) return TRS_OK;
+    if (!R || !R->mb.get()) return TRS_OK;
     DevLock lock(e);
     int rc = TRS_OK;
     if (!R->running && R->enabled && !R->broken && host_load(&R->mb->posted) > R->seen_done && host_load(&R->mb->posted) == e->step_count)
@@ -1444,11 +1444,8 @@ void resident_destroy(trs_env* e)
     DevLock lock(e);
     if (slot_of(e).owner == e) slot_of(e).owner = nullptr;
     if (R->running) { host_store(&R->mb->close, kCloseLeave); (void)hipStreamSynchronize(e->sP); }
-    if (R->mb) (void)hipHostFree(R->mb);
-    if (R->hctl) (void)hipHostFree(R->hctl);
-    (void)hipFree(R->dc);
     if (R->sC) (void)hipStreamDestroy(R->sC);
-    delete R;
+    delete R;                                                // (the worker has left: the mailbox, the staging and the control block go)
     e->res = nullptr;
 }
 
@@ -1467,7 +1464,7 @@ int resident_post_host(trs_env* e, const float* h_st, const float* h_th, const f
         if (rc) return rc;
         if (!R->enabled) return kFellBack;
     }
-    unsigned char* slot = R->hctl + (s & (kSlots - 1)) * R->hctl_slot;
+    unsigned char* slot = R->hctl.get() + (s & (kSlots - 1)) * R->hctl_slot;
     const size_t n = (size_t)e->n;
     float* f = reinterpret_cast<float*>(slot);
     std::memcpy(f, h_st, n * 4); std::memcpy(f + n, h_th, n * 4);
@@ -1484,7 +1481,7 @@ int resident_post_host(trs_env* e, const float* h_st, const float* h_th, const f
                 if (rc) return rc;
                 if (!R->enabled) { *n_done = k; return kFellBack; }
             }
-            unsigned char* sl = R->hctl + (sk & (kSlots - 1)) * R->hctl_slot;
+            unsigned char* sl = R->hctl.get() + (sk & (kSlots - 1)) * R->hctl_slot;
             if (sl != slot) std::memcpy(sl, slot, n * 12);
             slot = sl; f = reinterpret_cast<float*>(slot); rsb = slot + n * 12;
         }
@@ -1523,7 +1520,7 @@ TRS_EXPORT int trs_resident_debug_abort(trs_env* e)
     DevLock lock(e);
     if (!e->res || !e->res->running) return trs_internal_fail(TRS_ERR_STATE, "no resident worker is running on this handle");
     RCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(trs_worker_debug_abort_kernel, dim3(1), dim3(1), 0, e->res->sC, e->res->mb, e->res->dc);
+    hipLaunchKernelGGL(trs_worker_debug_abort_kernel, dim3(1), dim3(1), 0, e->res->sC, e->res->mb.get(), e->res->dc.get());
     RCHK(hipGetLastError());
     RCHK(hipStreamSynchronize(e->res->sC));
     return TRS_OK;
