@@ -1,5 +1,6 @@
 """The product's host-side table builder (csrc/trsim_tables.cpp: class map, row table, palette, tangents) on the CPU, built
-with AddressSanitizer + UBSan, against the oracle's tables bit for bit — the host logic of `trs_load_track` without a GPU."""
+with AddressSanitizer + UBSan, against the oracle's tables bit for bit; the layout and packing of a track's two LDS images, the refusals by policy and the LDS fit arithmetic
+(csrc/trsim_plan.hpp) against fixtures computed with the arithmetic `trs_load_track` and the setters had — their host logic without a GPU."""
 import ctypes as C
 import os
 import shutil
@@ -8,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import track_points
+from conftest import load_golden, track_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -44,3 +45,157 @@ def test_host_tables_equal_the_oracle(driver, make_env, oracle_api, tmp_path, tr
         got = np.fromfile(tmp_path / f"t.{name}", dtype=dtype)
         want = env.fetch(name).reshape(-1)
         assert got.size == want.size and np.array_equal(got.view(np.uint32), want.view(np.uint32)), name
+
+
+# ---- the layout of a track's two LDS images and the refusals (csrc/trsim_plan.hpp), on the CPU ---------------------------------------------
+
+LDS_BYTES = 160 * 1024
+V_DEPTH, V_DYN, V_HILLS, V_LENS, V_LIGHT = 1, 2, 4, 8, 16
+FEATURE_BITS = {"DYN": V_DYN, "HILLS": V_HILLS, "LENS": V_LENS, "LIGHT": V_LIGHT}
+
+
+def built(v):
+    """variant_built as DESIGN.md states it: no DYN with HILLS, no LENS with DYN, HILLS or LIGHT."""
+    return not (v & V_DYN and v & V_HILLS) and not (v & V_LENS and v & (V_DYN | V_HILLS | V_LIGHT))
+
+
+def layout_track(name, resampled_to=None, scaled_by=None):
+    """The fixture's tracks: the two golden tracks, the mountain track without its heights (`long_flat_track` of tests/test_lens_gpu.py), a
+    track resampled to n points (point i at arc index i * len / n of the closed lap, linear between its two neighbours) or scaled about the origin."""
+    pts = track_points("mountain" if name == "long_flat" else name).copy()
+    if name == "long_flat":
+        pts[:, 1] = 0.0
+    if resampled_to:
+        t = np.arange(resampled_to) * (len(pts) / resampled_to)
+        i0 = np.floor(t).astype(int)
+        f = (t - i0)[:, None]
+        pts = pts[i0] * (1.0 - f) + pts[(i0 + 1) % len(pts)] * f
+    return pts if scaled_by is None else pts * scaled_by
+
+
+def run_layout(driver, oracle_api, tmp_path, pts, h, w, envs_per_wg):
+    from triton_racer_sim_amd import _ffi
+    cfg = _ffi.TrsConfig()
+    oracle_api.default_config(C.byref(cfg))
+    cfg.n_envs, cfg.img_h, cfg.img_w = 2, h, w
+    (tmp_path / "cfg.bin").write_bytes(bytes(cfg))
+    (tmp_path / "pts.bin").write_bytes(np.ascontiguousarray(pts, dtype=np.float64).tobytes())
+    out = subprocess.run([driver, str(tmp_path / "cfg.bin"), str(tmp_path / "pts.bin"), str(tmp_path / "t"), str(envs_per_wg)], capture_output=True, text=True,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-2000:]
+    return out.stdout.splitlines()
+
+
+LAYOUT_CASES = load_golden("track_layouts.json")
+
+
+@pytest.mark.parametrize("case", LAYOUT_CASES["cases"], ids=lambda c: f"{c['track']}-{c['img_h']}x{c['img_w']}-{c['envs_per_wg']}")
+def test_track_layout_and_packed_images(driver, oracle_api, tmp_path, case):
+    h, w = case["img_h"], case["img_w"]
+    lines = run_layout(driver, oracle_api, tmp_path, layout_track(case["track"]), h, w, case["envs_per_wg"])
+    n_points, map_w, map_h, map_words = (int(x) for x in lines[0].split())
+    assert lines[1].startswith("layout "), lines[1]
+    L = {k: int(v) for k, v in (kv.split("=") for kv in lines[1].split()[1:])}
+    hills = lines[2] == "hills 1"
+    # (a) every field is what the arithmetic of trs_load_track gave before it moved (the fixture was computed with those lines)
+    assert L == case["layout"]
+    # (b) regions: 16-byte aligned, in order, disjoint, inside the image; the map pitch is an odd number of words
+    pts_b, grid_start_b, grid_pts_b = n_points * 8, os.path.getsize(tmp_path / "t.grid_start"), os.path.getsize(tmp_path / "t.grid_pts")
+    phys = [("px", 0, pts_b), ("py", L["p.off_py"], pts_b), ("pz", L["p.off_pz"], pts_b)]
+    if L["p.tan_in_lds"]:
+        phys.append(("tangent", L["p.off_tan"], n_points * 8))
+    phys += [("grid_start", L["p.off_gstart"], grid_start_b), ("grid_pts", L["p.off_gpts"], grid_pts_b)]
+    raster = [("map", 0, L["r.map_pitch_b"] * map_h), ("rowtab", L["r.off_rowtab"], h * 8), ("palette", L["r.off_pal"], h * 16), ("rowdepth", L["r.off_depth"], h * 4)]
+    if hills:
+        raster.append(("sky", L["r.off_sky"], h * 4))
+    for regions, blob_bytes in ((phys, L["p.blob_bytes"]), (raster, L["r.blob_bytes"])):
+        end = 0
+        for name, off, size in regions:
+            assert off % 16 == 0 and off >= end, (name, off, end)
+            end = off + size
+        assert end <= blob_bytes, (regions[-1][0], end, blob_bytes)
+    assert L["r.map_pitch_b"] % 4 == 0 and (L["r.map_pitch_b"] // 4) % 2 == 1 and L["r.map_pitch_b"] // 4 >= map_words
+    assert L["p.pts_bytes"] == L["p.off_tan"] and L["p.off_scratch"] == L["p.blob_bytes"] and L["p.lds_p"] >= L["p.blob_bytes"] and L["p.lds_p"] % 16 == 0
+    assert L["lds_off_phys"] == L["r.lds_r"] >= L["r.blob_bytes"] and L["lds_off_phys"] % 16 == 0
+    assert L["lds_step"] == L["lds_off_phys"] + L["p.blob_bytes"] <= LDS_BYTES and L["p.lds_p"] <= LDS_BYTES
+    # (c) every region of a packed image is, byte for byte, the table it holds; the map rows are the unpitched map's
+    img_p, img_r = (tmp_path / "t.phys").read_bytes(), (tmp_path / "t.raster").read_bytes()
+    assert len(img_p) == L["p.blob_bytes"] and len(img_r) == L["r.blob_bytes"]
+    for name, off, size in phys:
+        assert img_p[off:off + size] == (tmp_path / f"t.{name}").read_bytes(), name
+    for name, off, size in raster[1:]:
+        assert img_r[off:off + size] == (tmp_path / f"t.{name}").read_bytes(), name
+    unpitched = (tmp_path / "t.map").read_bytes()
+    assert len(unpitched) == map_words * 4 * map_h
+    for row in range(map_h):
+        assert img_r[row * L["r.map_pitch_b"]:row * L["r.map_pitch_b"] + map_words * 4] == unpitched[row * map_words * 4:(row + 1) * map_words * 4], row
+
+
+@pytest.mark.parametrize("case", LAYOUT_CASES["refusals"], ids=lambda c: f"{c['track']}-{c['resampled_to'] or c['scaled_by']}-{c['img_h']}x{c['img_w']}")
+def test_track_layout_refusals(driver, oracle_api, tmp_path, case):
+    lines = run_layout(driver, oracle_api, tmp_path, layout_track(case["track"], case["resampled_to"], case["scaled_by"]), case["img_h"], case["img_w"], case["envs_per_wg"])
+    assert lines[1] == f"refused {case['code']} {case['text']}"
+
+
+@pytest.fixture(scope="module")
+def plan_driver(tmp_path_factory):
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    exe = tmp_path_factory.mktemp("plan") / "driver"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"),
+                           "-o", str(exe), os.path.join(ROOT, "tests", "plan_driver.cpp")])
+    return str(exe)
+
+
+def run_plan(plan_driver, *args):
+    out = subprocess.run([plan_driver, *[str(a) for a in args]], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-2000:]
+    return [line.split(" ") for line in out.stdout.splitlines()]
+
+
+def test_refusal_policy_is_variant_built(plan_driver):
+    """For each of the 14 built variants as the handle's state and each feature bit a caller can add: refused exactly when the result is not built,
+    naming a set bit that is not built together with the added one, with a message; the eight messages are the ones the setters had."""
+    rows = run_plan(plan_driver, "policy")
+    states = [v for v in range(32) if built(v)]
+    assert len(states) == 14 and len(rows) == 14 * 4
+    seen = {}
+    for (tag, state, add, result_built, set_bit, pair_built, *text), (want_state, want_add) in zip(rows, [(s, a) for s in states for a in FEATURE_BITS.values()]):
+        state, add, set_bit, text = int(state), int(add), int(set_bit), " ".join(text)
+        assert tag == "clash" and (state, add) == (want_state, want_add)
+        assert int(result_built) == built(state | add)
+        if built(state | add):
+            assert set_bit == 0 and text == ""
+        else:
+            assert set_bit in FEATURE_BITS.values() and state & set_bit and not built(add | set_bit) and int(pair_built) == 0 and text != ""
+            assert seen.setdefault((add, set_bit), text) == text
+    want = {(FEATURE_BITS[r["added"]], FEATURE_BITS[r["set"]]): r["text"] for r in load_golden("variant_refusals.json")}
+    assert len(want) == 8 and seen == want
+    # a lens camera asked for while two set features clash with it: the order of the setter's checks (HILLS, DYN, LIGHT) picks the message
+    by_case = {(int(r[1]), int(r[2])): int(r[4]) for r in rows}
+    assert by_case[(V_DYN | V_LIGHT, V_LENS)] == V_DYN and by_case[(V_HILLS | V_LIGHT, V_LENS)] == V_HILLS
+
+
+def test_lds_fit_is_the_two_layouts(plan_driver):
+    """lds_fit over the fixture's lds_step values, every built variant and 1 to 64 envs per workgroup: 'one step per launch fits' and 'the worker fits'
+    as the two layout functions give them; each feature must be seen fitting and not fitting."""
+    by_size = {}
+    for c in LAYOUT_CASES["cases"]:
+        by_size.setdefault((c["img_h"], c["img_w"]), set()).add(c["layout"]["lds_step"])
+    answers = {(name, mode): set() for name in FEATURE_BITS for mode in ("launch", "resident")}
+    n = 0
+    for (h, w), steps in sorted(by_size.items()):
+        for tag, lds_step, v, epw, total1, fit_steps, worker_total, fit_launch, fit_resident in run_plan(plan_driver, "fit", h, w, *sorted(steps)):
+            v, launch_ok, worker_ok = int(v), int(total1) <= LDS_BYTES, int(worker_total) <= LDS_BYTES
+            assert tag == "fit" and built(v) and (int(fit_steps) >= 1) == launch_ok
+            assert int(fit_launch) == (0 if launch_ok else 1)                                # LdsFit: ok, no_launch, no_worker
+            assert int(fit_resident) == (1 if not launch_ok else (0 if worker_ok else 2))
+            for name, bit in FEATURE_BITS.items():
+                if v & bit:
+                    answers[(name, "launch")].add(int(fit_launch) == 0)
+                    answers[(name, "resident")].add(int(fit_resident) == 0)
+            n += 1
+    assert n == sum(len(s) for s in by_size.values()) * 14 * 64
+    assert all(a == {True, False} for a in answers.values()), answers

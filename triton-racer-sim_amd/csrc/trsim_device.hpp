@@ -9,6 +9,7 @@
 
 #include "../../include/trsim.h"
 #include "../../include/trsim_spec.h"
+#include "trsim_plan.hpp"
 #include "trsim_tables.hpp"
 
 #ifndef TRS_ABLATE
@@ -90,7 +91,6 @@ struct LensBlock {
     int wh;                             // W/2
 };
 __host__ __device__ inline size_t lens_block_offset(int blob_bytes) { return hill_block_offset(blob_bytes) + ((sizeof(HillBlock) + 63) & ~(size_t)63); }
-constexpr int kLensPalBytes = 513 * 16;
 
 struct FParams {                        // ImgPreprocessing with dynamic brightness, evaluated inside the step kernels (their DYN instantiations)
     double baseline;
@@ -103,26 +103,13 @@ struct FParams {                        // ImgPreprocessing with dynamic brightn
                                         // in-range tests per component value, range_byte_entry) | sel — staged into LDS once per launch (round 4: the
                                         // resident worker's raster waves then issue NO loads in their steady state)
 };
-constexpr int kDynTabWords = 512 + 768 + 4 + 256;   // ... | cnt[256]: the class counts of a row's 4-pixel pack (n0 | n1 << 8 | n2 << 16 | n3 << 24; round 4, see raster_dyn_batch phase A)
 constexpr int kDynCntAt = 512 + 768 + 4;
-
-// Which instantiation of trs_step_kernel / trs_worker_kernel <DEPTH, DYN, HILLS, LENS, LIGHT> renders: one bit per template flag (variant_of in
-// trsim_env.hpp).  14 of the 32 are built, DEPTH x {plain, DYN, HILLS, LENS, LIGHT, LIGHT + HILLS, LIGHT + DYN}: the setters refuse the others first.
-using Variant = unsigned;
-constexpr Variant kVDepth = 1, kVDyn = 2, kVHills = 4, kVLens = 8, kVLight = 16, kVariants = 32;
-constexpr Variant variant_bits(bool depth, bool dyn, bool hills, bool lens, bool light)
-{
-    return (depth ? kVDepth : 0u) | (dyn ? kVDyn : 0u) | (hills ? kVHills : 0u) | (lens ? kVLens : 0u) | (light ? kVLight : 0u);
-}
-constexpr bool variant_built(Variant v) { return !((v & kVDyn) && (v & kVHills)) && !((v & kVLens) && (v & (kVDyn | kVHills | kVLight))); }
 
 }  // namespace trsim
 
 namespace {
 
-#ifndef TRS_RASTER_WAVES
-#define TRS_RASTER_WAVES 8    /* raster waves per workgroup: 512 threads = 12 full rows of 40 groups per pass, 10 passes exactly at 120x160, and 12 waves balance over the 4 SIMDs (10 + 5 waves: 72.5 M env-steps/s, 8 + 4: 77.0 M; profiles/r01_step_kernel_waves_ab.txt) */
-#endif
+using trsim::kRasterThreads;
 #ifndef TRS_PHYS_WAVES
 #define TRS_PHYS_WAVES 4      /* physics waves per workgroup: one env per wave at 1024 envs */
 #endif
@@ -130,7 +117,6 @@ constexpr int kBlock = 64 * (TRS_RASTER_WAVES + TRS_PHYS_WAVES);   // 12 waves
 constexpr int kLocBlock = 1024;        // locate kernel: 16 waves = 16 queries in flight per workgroup
 constexpr int kRing = 4;               // global camera-parameter ring: the last step of launch i is the first frame of launch i+1
 [[maybe_unused]] constexpr int kRasterStampThread = 64 * TRS_RASTER_WAVES;  // diagnostic stamps: wave 0 and the first physics wave
-constexpr int kRasterThreads = 64 * TRS_RASTER_WAVES;
 constexpr int kPhysWaves = (kBlock - kRasterThreads) / 64;
 
 using trsim::PParams;
@@ -142,6 +128,10 @@ using trsim::Variant;
 using trsim::kVDepth; using trsim::kVDyn; using trsim::kVHills; using trsim::kVLens; using trsim::kVLight; using trsim::kVariants;
 using trsim::variant_bits;
 using trsim::variant_built;
+using trsim::kPhysBlock; using trsim::kDynBatch;
+using trsim::kHillRowBytes; using trsim::kHillBatchMax; using trsim::hill_table_bytes; using trsim::hill_batch; using trsim::hill_lds_bytes;
+using trsim::light_copies; using trsim::light_pal_bytes; using trsim::light_lds_extra; using trsim::dyn_lds_bytes;
+using trsim::StepLds; using trsim::tabs_lds_bytes; using trsim::step_lds_behind; using trsim::step_lds_layout;
 
 // ---------------------------------------------------------------------------------------------
 // device pieces of the spec
@@ -666,11 +656,6 @@ __device__ __forceinline__ void raster_ground_rows(const RParams& p, const Raste
 // threads fill in one pass, at most 4): team barrier (the previous batch's tables have been read by every wave) - build - team barrier - shade the
 // batch's envs.  (First form: one table per env frame behind its own barrier, two tables alternating: 14.7 us per step at 1024 envs x 120x160 against
 // 9.45 flat — the waves of the flat kernels never meet; profiles/r05_hills.txt.)
-constexpr int kHillRowBytes = 28;
-constexpr int kHillBatchMax = 4;
-__host__ __device__ inline int hill_table_bytes(int H) { return (kHillRowBytes * H + 15) & ~15; }
-__host__ __device__ inline int hill_batch(int H) { const int b = kRasterThreads / (H > 0 ? H : 1); return b < 1 ? 1 : (b > kHillBatchMax ? kHillBatchMax : b); }
-__host__ __device__ inline int hill_lds_bytes(int H) { return hill_batch(H) * hill_table_bytes(H) + 48; }   // the batch's tables + the team-barrier counter (4 B) + 12 B spare + int first_ground[2][4]: an env's first row that sees the ground, by batch parity
 
 // ImgPreprocessing.__process of ONE colour without dynamic brightness and Canny (img_preprocessing.py:37-74,92-99): the device twin of the host's filter_colour —
 // the same binary32 trim, OpenCV's 8-bit fixed-point HSV with its reciprocal tables, the masks written over their destination channels in filter order.
@@ -825,16 +810,6 @@ __device__ __forceinline__ void raster_hill_frame(const RParams& p, const Raster
 // from it through the unchanged row loops (RasterThread::pal_off).  No team barrier: a wave writes and reads only its own entries, and a wave's
 // LDS operations execute in order.  Waves w and w + light_copies(gpr) walk disjoint rows, so they share a copy.  LDS: behind the lighting
 // parameters, light_copies x uint32[H][4].  ~1-5 entries per lane and frame against ~40 shaded pixels.
-constexpr int kDynBatch = 4;                  // envs per batch of the dynamic-brightness filter behind the rasteriser (raster_dyn_batch)
-__host__ __device__ inline int light_copies(int gpr) { return (gpr + 63 + 63) / 64; }
-__host__ __device__ inline int light_pal_bytes(int H, int gpr) { return light_copies(gpr) * H * 16; }
-// The LDS of scene lighting behind the row tables (or where they would sit): the parameters of `slots` envs (the step kernel: the workgroup's envs; the
-// worker: a ring of kCamDepth steps of them), then on a flat track the waves' lit palettes — or, with the dynamic-brightness filter, the batch's lit
-// palettes by channel (raster_dyn_batch)
-__host__ __device__ inline int light_lds_extra(int H, int W, int slots, bool hilly, bool dyn)
-{
-    return slots * 32 + (hilly ? 0 : (dyn ? kDynBatch * H * 16 : light_pal_bytes(H, W / 4)));
-}
 // lg: the env's parameters in LDS; filt: the block's static-filter flag (read once per kernel); returns the LDS offset of the wave's lit palette
 __device__ __forceinline__ unsigned light_wave_palette(const RParams& p, unsigned pal0, const float* lg, int filt, int wave, int lane)
 {
@@ -1047,41 +1022,6 @@ __device__ __forceinline__ uint32_t filter_colour_dev(const FParams& f, const un
 #else
 #define DYN_STAMP(k) do { } while (0)
 #endif
-__host__ __device__ inline int dyn_lds_bytes(int H) { return kDynBatch * H * 16 + 128 + ((kDynTabWords * 4 + 15) & ~15) + H * 16; }   // ... + rowch[H]: the raw palette by channel
-
-// The step kernel's dynamic LDS behind its tables (lds_step bytes: raster image, physics image) for variant v and n_phys physics steps per launch: the one
-// layout launch_step sizes the launch and fills SParams / FParams from, and the kernel takes lds_off_pitch, lds_off_hill and lds_off_light from
-// (step_lds_behind, from SParams::lds_off_prog: the same arithmetic the kernels always did; the layout's size comes on top of it).
-//   cam:   float4 lcam[max(n_phys, 1) + 1][epw]   (the last row: the poses of the step before the launch)
-//   prog:  int pprog[epw] + 16 spare bytes
-//   pitch: float lpitch[max(n_phys, 1) + 1][epw]  (HILLS; LENS and LIGHT keep the region)
-//   hill:  (16-aligned) the batch's row tables and the raster team's barrier counter (HILLS) or the lens palette (LENS)
-//   light: (16-aligned, LIGHT) the workgroup's lighting parameters, then the lit palettes
-//   dyn:   (16-aligned, DYN) the dynamic-brightness filter's palettes, sums and tables (FParams::lds_off)
-struct StepLds { int cam, prog, pitch, hill, light, dyn, total; };
-// the region at `hill` of both kernels' layouts: the batch's row tables (HILLS) or the lens palette (LENS)
-__host__ __device__ inline int tabs_lds_bytes(int H, Variant v) { return (v & kVHills) ? hill_lds_bytes(H) : ((v & kVLens) ? trsim::kLensPalBytes : 0); }
-__host__ __device__ inline StepLds step_lds_behind(int prog, int epw, int H, Variant v, int n_phys)
-{
-    const int rows = max(n_phys, 1) + 1;
-    StepLds L;
-    L.prog = prog;
-    L.cam = prog - rows * epw * 16;
-    L.pitch = L.prog + epw * 4 + 16;
-    L.hill = (L.pitch + rows * epw * 4 + 15) & ~15;
-    L.light = (L.hill + tabs_lds_bytes(H, v) + 15) & ~15;
-    return L;
-}
-__host__ __device__ inline StepLds step_lds_layout(int lds_step, int epw, int H, int W, Variant v, int n_phys)
-{
-    StepLds L = step_lds_behind(lds_step + (max(n_phys, 1) + 1) * epw * 16, epw, H, v, n_phys);
-    int end = L.pitch;
-    if (v & (kVHills | kVLens | kVLight)) end = L.hill + tabs_lds_bytes(H, v);
-    if (v & kVLight) end = L.light + light_lds_extra(H, W, epw, (v & kVHills) != 0, (v & kVDyn) != 0);
-    L.dyn = (end + 15) & ~15;
-    L.total = (v & kVDyn) ? L.dyn + dyn_lds_bytes(H) : end;
-    return L;
-}
 // the tables behind the batch's palettes and sums (staged by dyn_stage_tables before the launch's first barrier)
 __device__ __forceinline__ unsigned* dyn_tabs_lds(unsigned char* lds_base, const FParams& f, int H) { return reinterpret_cast<unsigned*>(lds_base + f.lds_off + kDynBatch * H * 16 + 128); }
 // rowch[v] = the RAW palette of row v by channel: {R of classes 0..3, G of classes 0..3, B of classes 0..3, 0} as packed bytes (behind the tables)

@@ -97,7 +97,6 @@ int sync_handle(trs_env* e);                               // the handle's strea
 int quiesce_handle(trs_env* e);                            // a resident worker has left; queued work may still be running
 void comm_destroy(trs_env* e);
 bool resident_running(const trs_env* e);
-bool resident_fits(const trs_env* e, Variant v);           // the render worker's LDS layout of variant v fits a CU beside the handle's tables
 void resident_clear_fault(trs_env* e);                     // trs_load_track puts every env on a defined state again
 int check_fault(trs_env* e);                               // TRS_ERR_DEVICE (sticky) once a kernel has reported a layout fault
 
@@ -106,6 +105,9 @@ inline Variant variant_of(const trs_env* e)
 {
     return variant_bits(e->rp.depth != 0, e->has_frame_filter && e->filter_dynamic, e->hilly, e->lens_on, e->light_on);
 }
+
+// one HSV bound of a colour filter (trs_pre_config::hsv_lo / hsv_hi) as the kernels take it: h | s << 8 | v << 16
+inline int pack_hsv(const uint8_t (&b)[3]) { return b[0] | (b[1] << 8) | (b[2] << 16); }
 
 // the dynamic-brightness frame filter that is set, as the DYN instantiations take it (all zero without one); lds_off: its region in the kernel's LDS layout
 inline FParams fparams_of(const trs_env* e, int lds_off)
@@ -117,8 +119,8 @@ inline FParams fparams_of(const trs_env* e, int lds_off)
     f.baseline = c.brightness_baseline; f.contrast = c.contrast_ratio; f.offset = c.contrast_offset;
     f.color = c.color_filter_enabled; f.n_filters = c.n_filters;
     for (int k = 0; k < 4; ++k) {
-        f.lo[k] = c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16);
-        f.hi[k] = c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16);
+        f.lo[k] = pack_hsv(c.hsv_lo[k]);
+        f.hi[k] = pack_hsv(c.hsv_hi[k]);
         f.dst_ch[k] = c.dst_channel[k];
     }
     f.w0 = std::min(40, e->H); f.w1 = std::min(119, e->H);              // img[40:119] (img_preprocessing.py:88)

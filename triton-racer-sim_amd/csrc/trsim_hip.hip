@@ -94,7 +94,6 @@ struct SParams {
 
 // Physics-only envs (BASELINE config 2): the same barrier-free wave-per-env routine, 4 envs per 256-thread workgroup,
 // K steps per launch.  The track image is staged once per launch; nothing is synchronised after that.
-constexpr int kPhysBlock = 256;
 
 __global__ __launch_bounds__(kPhysBlock) void trs_physics_kernel(const PParams p)
 {
@@ -1037,16 +1036,17 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 namespace {
 
+// the frame buffers written by the last step (nullptr without a camera / without cfg.depth)
+const uint8_t* latest_frame(const trs_env* e) { return e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr; }
+const float* latest_depth(const trs_env* e) { return (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1].get() : nullptr; }
+
 int grid_of(const trs_env* e) { return (e->n + e->pp.envs_per_wg - 1) / e->pp.envs_per_wg; }
 
-// Physics steps per launch of variant v beside lds_step bytes of tables: the largest n <= 16 whose step_lds_layout fits a CU's 160 KiB (0: not even one).
-// Every LDS refusal asks it about the variant the handle would run after the change.
-int steps_that_fit(const trs_env* e, Variant v, int lds_step)
-{
-    int n = 0;
-    while (n < 16 && step_lds_layout(lds_step, e->pp.envs_per_wg, e->H, e->W, v, n + 1).total <= 160 * 1024) ++n;
-    return n;
-}
+// The two LDS questions of every refusal, about the variant v the handle would run after the change beside lds_step bytes of tables (trsim_plan.hpp)
+trsim::LdsFit handle_fit(const trs_env* e, Variant v, int lds_step) { return trsim::lds_fit(lds_step, e->pp.envs_per_wg, e->H, e->W, v, trsim::resident_on(e)); }
+int steps_that_fit(const trs_env* e, Variant v, int lds_step) { return trsim::steps_that_fit(lds_step, e->pp.envs_per_wg, e->H, e->W, v); }
+// The variant the handle runs now, for the refusals by policy (variant_clash): a handle without a track has no HILLS bit, whatever a failed reload left behind
+Variant variant_now(const trs_env* e) { return trsim::variant_of(e) & (e->track_loaded ? ~0u : ~kVHills); }
 
 // the handle's stream is idle: a resident worker (trs_set_step_mode) is asked to leave first — it owns the stream while it runs
 int sync_all(trs_env* e)
@@ -1284,141 +1284,99 @@ void lens_commit(trs_env* e, LensStage& S);
 void lens_release(trs_env* e);
 }
 
-TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    HIPCHK(hipSetDevice(e->device));
-    int rc0 = sync_all(e);
-    if (rc0) return rc0;
-    // Transactional: everything is built into copies (tables, parameter blocks, layout numbers, device buffers) and
-    // committed only after every check, allocation and copy has succeeded — a failed reload leaves the handle with the
-    // track it had (or with none), never with new offsets against old blobs.
-    std::string err;
-    trsim::TrackTables T;
-    int rc = trsim::build_tables(e->cfg, h_xyz, n_points, T, err);
-    if (rc) return fail(rc, err);
-    if (e->lens_on && T.hills)
-        return fail(TRS_ERR_STATE, "this track has elevation and a lens camera is set: the lens camera is built for flat tracks only (trs_set_camera(NULL) first); the handle keeps its track");
-    PParams k = e->pp;
-    RParams r = e->rp;
-    trsim::DevBuf<> blob_p, blob_r;                          // device buffers of the new track; released unless moved into the handle
+namespace {
+// ---- trs_load_track, step by step.  Transactional: everything is built into copies (tables, layout, parameter blocks, device buffers) and committed only
+// after every check, allocation and copy has succeeded — a failed reload leaves the handle with the track it had (or with none), never with new offsets
+// against old blobs.
+struct TrackStage {                                          // device buffers of the new track; released unless moved into the handle
+    trsim::DevBuf<> blob_p, blob_r;
     trsim::DevBuf<float> tangent, start_yaw, dpitch;
-    int n_lds_r = 0, n_lds_p = 0, n_lds_step = 0, n_lds_off_phys = 0, n_pts_bytes = 0;
+};
 
-    // ---- physics LDS image: px | py | pz | tangent (when it fits) + scratch ----
-    const size_t pts = align_up((size_t)n_points * 8, 16);
-    const size_t scratch = (size_t)(kPhysBlock / 64) * (16 + 4) + 16;     // physics-only kernel: per-wave sinks
-    size_t off = 0;
-    k.off_py = (int)(off += pts); k.off_pz = (int)(off += pts); off += pts;
-    n_pts_bytes = (int)off;
-    k.off_tan = (int)off;
-    const size_t tan_bytes = align_up((size_t)n_points * 8, 16);
-    // ---- raster LDS image: map (rows pitched to an odd number of words) @0 | rowtab | palette ----
-    const int pitch_words = T.info.map_words | 1;          // odd pitch: rows of the map start on different LDS banks
-    r.map_pitch_b = pitch_words * 4;
-    if (r.map_pitch_b >= (1 << 24) || T.info.map_h >= (1 << 24)) return fail(TRS_ERR_LIMIT, "map exceeds the 24-bit multiply of the rasteriser");
-    const size_t map_bytes = (size_t)r.map_pitch_b * T.info.map_h;
-    size_t roff = align_up(map_bytes, 16);
-    r.off_rowtab = (int)roff; roff += align_up((size_t)e->H * 8, 16);
-    r.off_pal = (int)roff; roff += (size_t)e->H * 16;
-    r.off_depth = (int)roff; roff += align_up((size_t)e->H * 4, 16);
-    const int off_sky = (int)roff;
-    if (T.hills) roff += align_up((size_t)e->H * 4, 16);     // a track with elevation: the sky colour of every row rides in the raster image (hill_rows_build)
-    r.blob_bytes = (int)roff;
-    n_lds_r = (int)align_up(roff, 16);
-    if ((size_t)r.blob_bytes > (size_t)100 * 1024)
-        return fail(TRS_ERR_LIMIT, "map + camera tables exceed the step kernel's LDS staging capacity");
-    // tangents ride in LDS when the fused kernel's image (raster tables + points + tangents) still fits a CU's 160 KiB
-    n_lds_off_phys = n_lds_r;
-    const size_t grid_bytes = align_up(T.grid_start.size() * 2, 16) + align_up(T.grid_pts.size() * 2, 16);
-    // (... and leaves room for what the kernels keep behind the tables: the camera hand-off ring of a few steps, and on a track with elevation the two per-env
-    // row tables + the view pitches — the mountain track's points + tangents fill the CU to within 150 bytes on their own)
-    const size_t behind = (size_t)k.envs_per_wg * 4 + 16 + (size_t)k.envs_per_wg * 20 * 3 + (T.hills ? (size_t)hill_lds_bytes(e->H) + 64 : 0);
-    k.tan_in_lds = ((size_t)n_lds_off_phys + off + grid_bytes + tan_bytes + behind <= 160 * 1024) ? 1 : 0;
-    if (k.tan_in_lds) off += tan_bytes;
-    // nearest-point accelerator tables ride behind the points (uint16 cell starts + point lists)
+int track_upload(const trsim::TrackTables& T, const std::vector<unsigned char>& hp, const std::vector<unsigned char>& hr, TrackStage& S)
+{
+    const size_t n_points = (size_t)T.n_points;
+    HIPCHK(S.blob_p.alloc(hp.size()));
+    HIPCHK(S.blob_r.alloc(trsim::lens_block_offset((int)hr.size()) + sizeof(trsim::LensBlock)));   // (+ the constants of a track with elevation and of the lens camera, behind the image)
+    HIPCHK(S.tangent.alloc(n_points * 8));
+    HIPCHK(S.start_yaw.alloc(n_points * 4));
+    HIPCHK(hipMemcpy(S.blob_p.get(), hp.data(), hp.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.blob_r.get(), hr.data(), hr.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.tangent.get(), T.tangent.data(), n_points * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.start_yaw.get(), T.start_yaw.data(), n_points * 4, hipMemcpyHostToDevice));
+    HIPCHK(S.dpitch.alloc(n_points * 4));
+    // the view pitch of a frame whose nearest raw track point is idx: pitch_f + dpitch[idx], ONE binary32 addition as the spec has it
+    std::vector<float> vp(n_points);
+    for (size_t i = 0; i < n_points; ++i) vp[i] = T.pitch_f + T.dpitch[i];
+    HIPCHK(hipMemcpy(S.dpitch.get(), vp.data(), n_points * 4, hipMemcpyHostToDevice));
+    return TRS_OK;
+}
+
+// the kernels' parameter blocks for the new track: copies of the handle's with the layout, the tables' constants and the staged buffers
+void track_params(const trsim::TrackTables& T, const trsim::TrackLayout& L, const TrackStage& S, PParams& k, RParams& r)
+{
+    k.off_py = L.p.off_py; k.off_pz = L.p.off_pz; k.off_tan = L.p.off_tan; k.tan_in_lds = L.p.tan_in_lds;
     k.grid_nx = T.grid_nx; k.grid_nz = T.grid_nz; k.grid_x0 = T.grid_x0; k.grid_z0 = T.grid_z0;
-    k.off_gstart = (int)off; off += align_up(T.grid_start.size() * 2, 16);
-    k.off_gpts = (int)off; off += align_up(T.grid_pts.size() * 2, 16);
-    k.blob_bytes = (int)off;
-    k.off_scratch = (int)off;
-    n_lds_p = (int)align_up(off + scratch, 16);
-    n_lds_step = (int)align_up((size_t)n_lds_off_phys + off, 16);
-    if (n_lds_p > 160 * 1024 || (e->cfg.render && n_lds_step > 160 * 1024))
-        return fail(TRS_ERR_LIMIT, "track too long for the LDS-resident nearest-point search");
-    std::vector<unsigned char> hp(off, 0);
-    std::memcpy(hp.data(), T.px.data(), (size_t)n_points * 8);
-    std::memcpy(hp.data() + k.off_py, T.py.data(), (size_t)n_points * 8);
-    std::memcpy(hp.data() + k.off_pz, T.pz.data(), (size_t)n_points * 8);
-    if (k.tan_in_lds) std::memcpy(hp.data() + k.off_tan, T.tangent.data(), (size_t)n_points * 8);
-    if (!T.grid_start.empty()) std::memcpy(hp.data() + k.off_gstart, T.grid_start.data(), T.grid_start.size() * 2);
-    if (!T.grid_pts.empty()) std::memcpy(hp.data() + k.off_gpts, T.grid_pts.data(), T.grid_pts.size() * 2);
-
-    std::vector<unsigned char> hr(roff, 0);
-    for (int row = 0; row < T.info.map_h; ++row)
-        std::memcpy(hr.data() + (size_t)row * r.map_pitch_b, T.map.data() + (size_t)row * T.info.map_words, (size_t)T.info.map_words * 4);
-    std::memcpy(hr.data() + r.off_rowtab, T.rowtab.data(), (size_t)e->H * 8);
-    std::memcpy(hr.data() + r.off_pal, T.palette.data(), (size_t)e->H * 16);
-    std::memcpy(hr.data() + r.off_depth, T.rowdepth.data(), (size_t)e->H * 4);
-    if (T.hills) std::memcpy(hr.data() + off_sky, T.sky.data(), (size_t)e->H * 4);
-
-    HIPCHK(blob_p.alloc(off));
-    HIPCHK(blob_r.alloc(trsim::lens_block_offset((int)roff) + sizeof(trsim::LensBlock)));   // (+ the constants of a track with elevation and of the lens camera, behind the image)
-    HIPCHK(tangent.alloc((size_t)n_points * 8));
-    HIPCHK(start_yaw.alloc((size_t)n_points * 4));
-    HIPCHK(hipMemcpy(blob_p.get(), hp.data(), off, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(blob_r.get(), hr.data(), roff, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(tangent.get(), T.tangent.data(), (size_t)n_points * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(start_yaw.get(), T.start_yaw.data(), (size_t)n_points * 4, hipMemcpyHostToDevice));
-    HIPCHK(dpitch.alloc((size_t)n_points * 4));
-    {   // the view pitch of a frame whose nearest raw track point is idx: pitch_f + dpitch[idx], ONE binary32 addition as the spec has it
-        std::vector<float> vp((size_t)n_points);
-        for (int i = 0; i < n_points; ++i) vp[i] = T.pitch_f + T.dpitch[i];
-        HIPCHK(hipMemcpy(dpitch.get(), vp.data(), (size_t)n_points * 4, hipMemcpyHostToDevice));
-    }
-    k.blob = blob_p.get(); k.start_yaw = start_yaw.get(); k.tangent_g = tangent.get();
-    r.blob = blob_r.get();
-    k.np = n_points; r.map_w = T.info.map_w; r.map_h = T.info.map_h;
+    k.off_gstart = L.p.off_gstart; k.off_gpts = L.p.off_gpts; k.blob_bytes = L.p.blob_bytes; k.off_scratch = L.p.off_scratch;
+    r.map_pitch_b = L.r.map_pitch_b; r.off_rowtab = L.r.off_rowtab; r.off_pal = L.r.off_pal; r.off_depth = L.r.off_depth; r.blob_bytes = L.r.blob_bytes;
+    k.blob = S.blob_p.get(); k.start_yaw = S.start_yaw.get(); k.tangent_g = S.tangent.get();
+    r.blob = S.blob_r.get();
+    k.np = T.n_points; r.map_w = T.info.map_w; r.map_h = T.info.map_h;
     k.map_x0f = T.map_x0f; k.map_z0f = T.map_z0f; k.inv_cellf = T.inv_cellf;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, n_lds_p));
+}
+
+// the kernels may use the LDS the new track needs — and the fused kernel has room for one step per launch beside it
+int track_kernel_attributes(const trs_env* e, const trsim::TrackLayout& L, bool hills)
+{
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L.p.lds_p));
     // room in the CU's 160 KiB for one step per launch of the camera hand-off ring (on a track with elevation: and the per-env row tables); the frame filter,
-    // the lens camera and scene lighting that are set are checked below, each with its own message
-    if (e->cfg.render && steps_that_fit(e, variant_bits(r.depth != 0, false, T.hills, false, false), n_lds_step) < 1)
-        return fail(TRS_ERR_LIMIT, T.hills ? "no LDS left for the camera hand-off ring and the per-env row tables of a track with elevation" : "no LDS left for the camera hand-off ring");
+    // the lens camera and scene lighting that are set are checked later, each with its own message
+    if (e->cfg.render && handle_fit(e, variant_bits(e->rp.depth != 0, false, hills, false, false), L.lds_step) == trsim::LdsFit::no_launch)
+        return fail(TRS_ERR_LIMIT, hills ? "no LDS left for the camera hand-off ring and the per-env row tables of a track with elevation" : "no LDS left for the camera hand-off ring");
     for (const StepKernel sk : kStepKernels)
         if (sk) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_locate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k.blob_bytes));
-    // the lens camera, when one is set: its tables for the new map (its cell size) and its LensBlock behind the NEW raster image, before anything is committed —
-    // a track that leaves no LDS for the lens palette is refused like any other, and the handle keeps its track and its lens
-    LensStage ls;
-    {
-        trsim::LensBlock none{};                             // (the slot is never read while no lens is set; defined contents all the same)
-        HIPCHK(hipMemcpy(blob_r.get() + trsim::lens_block_offset(r.blob_bytes), &none, sizeof none, hipMemcpyHostToDevice));
-    }
-    if (e->lens_on) { int rl = lens_stage(e, e->camera, n_lds_step, T.info.cell, blob_r.get(), r.blob_bytes, ls); if (rl) return rl; }
-    // ---- commit: nothing above has touched the handle ----
-    e->track_loaded = false;                                 // (until the state arrays below are in place)
-    e->blob_p = std::move(blob_p); e->blob_r = std::move(blob_r); e->tangent = std::move(tangent); e->start_yaw = std::move(start_yaw); e->dpitch = std::move(dpitch);   // (the old track's are released)
-    {
-        trsim::HillBlock& hb = e->hill_host;                 // (host copy: upload_palette fills in the frame filter and sends the block again)
-        hb = trsim::HillBlock{};
-        hb.vpitch = e->dpitch.get(); hb.cam_pitch = e->cam_pitch.get(); hb.off_sky = off_sky; hb.far_rgb = T.far_rgb;
-        hb.inv_f = T.inv_f; hb.hh = T.hh; hb.cam_h_f = T.cam_h_f; hb.z_far_f = T.z_far_f; hb.inv_zfar_f = T.inv_zfar_f; hb.fog_f = T.fog_f; hb.inv_cell_f = T.inv_cellf;
-        e->hilly = T.hills;
-        HIPCHK(hipMemcpy(e->blob_r.get() + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
-    }
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_locate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L.p.blob_bytes));
+    return TRS_OK;
+}
+
+// the lens camera, when one is set: its tables for the new map (its cell size) and its LensBlock behind the NEW raster image, before anything is committed —
+// a track that leaves no LDS for the lens palette is refused like any other, and the handle keeps its track and its lens
+int track_lens_stage(const trs_env* e, const trsim::TrackTables& T, const trsim::TrackLayout& L, TrackStage& S, LensStage& ls)
+{
+    trsim::LensBlock none{};                                 // (the slot is never read while no lens is set; defined contents all the same)
+    HIPCHK(hipMemcpy(S.blob_r.get() + trsim::lens_block_offset(L.r.blob_bytes), &none, sizeof none, hipMemcpyHostToDevice));
+    return e->lens_on ? lens_stage(e, e->camera, L.lds_step, T.info.cell, S.blob_r.get(), L.r.blob_bytes, ls) : TRS_OK;
+}
+
+// ---- commit: nothing before this has touched the handle ----
+int track_commit(trs_env* e, trsim::TrackTables& T, const trsim::TrackLayout& L, TrackStage& S, const PParams& k, const RParams& r, LensStage& ls)
+{
+    e->track_loaded = false;                                 // (until the state arrays are in place: track_start_poses)
+    e->blob_p = std::move(S.blob_p); e->blob_r = std::move(S.blob_r); e->tangent = std::move(S.tangent); e->start_yaw = std::move(S.start_yaw); e->dpitch = std::move(S.dpitch);   // (the old track's are released)
+    trsim::HillBlock& hb = e->hill_host;                     // (host copy: upload_palette fills in the frame filter and sends the block again)
+    hb = trsim::HillBlock{};
+    hb.vpitch = e->dpitch.get(); hb.cam_pitch = e->cam_pitch.get(); hb.off_sky = L.r.off_sky; hb.far_rgb = T.far_rgb;
+    hb.inv_f = T.inv_f; hb.hh = T.hh; hb.cam_h_f = T.cam_h_f; hb.z_far_f = T.z_far_f; hb.inv_zfar_f = T.inv_zfar_f; hb.fog_f = T.fog_f; hb.inv_cell_f = T.inv_cellf;
+    e->hilly = T.hills;
+    HIPCHK(hipMemcpy(e->blob_r.get() + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     if (e->lens_on) lens_commit(e, ls);
     e->tab = std::move(T);
     e->pp = k; e->rp = r;
-    e->lds_r = n_lds_r; e->lds_p = n_lds_p; e->lds_step = n_lds_step; e->lds_off_phys = n_lds_off_phys; e->pts_bytes = n_pts_bytes;
+    e->lds_r = L.r.lds_r; e->lds_p = L.p.lds_p; e->lds_step = L.lds_step; e->lds_off_phys = L.lds_off_phys; e->pts_bytes = L.p.pts_bytes;
+    return TRS_OK;
+}
+
+// start poses (host mirror of the reset branch so that telemetry is meaningful before the first step)
+int track_start_poses(trs_env* e)
+{
     const trsim::TrackTables& TT = e->tab;
-    // start poses (host mirror of the reset branch so that telemetry is meaningful before the first step)
+    const PParams& k = e->pp;
     const size_t n = (size_t)e->n;
     std::vector<float> sx(n), sy(n), sz(n), syaw(n);
     std::vector<int32_t> sidx(n);
     for (size_t i = 0; i < n; ++i) {
         const int gid = e->cfg.env_id_base + (int)i;
-        const int si = (int)(((long long)TRS_START_STRIDE * gid) % n_points);
+        const int si = (int)(((long long)TRS_START_STRIDE * gid) % TT.n_points);
         sx[i] = (float)TT.px[si]; sy[i] = (float)TT.py[si]; sz[i] = (float)TT.pz[si]; syaw[i] = TT.start_yaw[si]; sidx[i] = si;
     }
     HIPCHK(hipMemcpy(k.x, sx.data(), n * 4, hipMemcpyHostToDevice));
@@ -1434,23 +1392,60 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     e->step_count = 0;
     e->track_loaded = true;
     trsim::resident_clear_fault(e);
-    if (e->has_frame_filter && e->filter_dynamic && e->hilly) {   // (the dynamic-brightness filter is not built for tracks with elevation, see trs_set_frame_filter)
+    return TRS_OK;
+}
+
+// The features that were set and that the committed track has no kernel (`clash`: the dynamic-brightness filter on a track with elevation, see
+// variant_refusal) or no LDS for are removed, with an error return; otherwise the palette of the new track goes up
+int track_drop_misfits(trs_env* e, Variant clash)
+{
+    auto drop_filter = [&](int code, const char* why) {
         e->has_frame_filter = false; e->filter_dynamic = false;
         (void)upload_palette(e);
-        return fail(TRS_ERR_STATE, "this track has elevation: the dynamic-brightness frame filter that was set has been removed (a frame's palette is evaluated per env inside the kernels there; "
-                                   "the static filter works, or use trs_preprocess on the rendered frames)");
-    }
-    if (e->has_frame_filter && e->filter_dynamic && steps_that_fit(e, trsim::variant_of(e) & ~kVLight, e->lds_step) < 1) {   // (the filter alone; with lighting: below)
-        e->has_frame_filter = false; e->filter_dynamic = false;
-        (void)upload_palette(e);
-        return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the dynamic-brightness frame filter that was set: the filter has been removed");
-    }
-    if (e->light_on && steps_that_fit(e, trsim::variant_of(e), e->lds_step) < 1) {   // (e->hilly, e->lds_step: the new track's)
+        return fail(code, why);
+    };
+    const Variant v = trsim::variant_of(e);                  // (HILLS, e->lds_step: the new track's)
+    if (clash == kVDyn) return drop_filter(TRS_ERR_STATE, trsim::variant_refusal(kVHills, kVDyn));
+    if ((v & kVDyn) && handle_fit(e, v & ~kVLight, e->lds_step) == trsim::LdsFit::no_launch)   // (the filter alone; with lighting: below)
+        return drop_filter(TRS_ERR_LIMIT, "this track leaves no LDS for the dynamic-brightness frame filter that was set: the filter has been removed");
+    if ((v & kVLight) && handle_fit(e, v, e->lds_step) == trsim::LdsFit::no_launch) {
         e->light_on = false; e->light = nullptr;
         (void)upload_palette(e);
         return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the scene lighting that was set: lighting has been removed");
     }
     return upload_palette(e);                 // also sets rp.uni_rows (and applies a frame filter that was set earlier)
+}
+}  // namespace
+
+TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(e->device));
+    int rc = sync_all(e);
+    if (rc) return rc;
+    std::string err;
+    trsim::TrackTables T;
+    rc = trsim::build_tables(e->cfg, h_xyz, n_points, T, err);
+    if (rc) return fail(rc, err);
+    // the new track's HILLS bit against what is set: a lens camera refuses the track now, the dynamic-brightness filter is removed after the commit
+    const Variant clash = trsim::variant_clash(trsim::variant_of(e) & ~kVHills, T.hills ? kVHills : 0u);
+    if (clash == kVLens) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVHills, clash));
+    trsim::TrackLayout L;
+    rc = trsim::track_layout(T, e->H, e->cfg.render != 0, e->pp.envs_per_wg, L, err);
+    if (rc) return fail(rc, err);
+    std::vector<unsigned char> hp, hr;
+    trsim::pack_track_images(T, e->H, L, hp, hr);
+    TrackStage S;
+    if ((rc = track_upload(T, hp, hr, S))) return rc;
+    PParams k = e->pp;
+    RParams r = e->rp;
+    track_params(T, L, S, k, r);
+    if ((rc = track_kernel_attributes(e, L, T.hills))) return rc;
+    LensStage ls;
+    if ((rc = track_lens_stage(e, T, L, S, ls))) return rc;
+    if ((rc = track_commit(e, T, L, S, k, r, ls))) return rc;
+    if ((rc = track_start_poses(e))) return rc;
+    return track_drop_misfits(e, clash);
 }
 
 TRS_EXPORT int trs_reset(trs_env* e, const uint8_t* h_mask)
@@ -1577,11 +1572,11 @@ TRS_EXPORT int trs_get_state(trs_env* e, trs_state_view* o)
     if (!e || !o) return fail(TRS_ERR_ARG, "null argument");
     const PParams& k = e->pp;
     o->n_envs = e->n; o->img_h = e->H; o->img_w = e->W; o->n_points = k.np;
-    o->img = e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr;   // buffer written by the last step
+    o->img = latest_frame(e);
     o->pos_x = k.x; o->pos_y = k.y; o->pos_z = k.z; o->speed = k.speed; o->cte = k.cte; o->yaw = k.yaw; o->vel = k.v;
     o->seg_idx = k.seg_idx; o->ep_return = k.ep_return; o->last_return = k.last_return; o->ep_len = k.ep_len; o->done = k.done;
     o->step_count = e->step_count;
-    o->depth = (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1].get() : nullptr;
+    o->depth = latest_depth(e);
     return TRS_OK;
 }
 
@@ -1593,7 +1588,7 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     const void* src = nullptr; size_t need = 0; const size_t n = (size_t)e->n;
     bool host_src = false;
     switch (which) {
-    case TRS_F_IMG: src = e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr; need = e->img_bytes; break;
+    case TRS_F_IMG: src = latest_frame(e); need = e->img_bytes; break;
     case TRS_F_POS_X: src = k.x; need = n * 4; break;
     case TRS_F_POS_Y: src = k.y; need = n * 4; break;
     case TRS_F_POS_Z: src = k.z; need = n * 4; break;
@@ -1611,7 +1606,7 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     case TRS_F_CTL_THR: src = e->ctl_thr; need = n * 4; break;
     case TRS_F_CTL_BRK: src = e->ctl_brk; need = n * 4; break;
     case TRS_F_STATS: src = e->stats.get(); need = 64 * sizeof(unsigned long long); break;
-    case TRS_F_DEPTH: src = (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1].get() : nullptr; need = n * e->H * e->W * 4; break;
+    case TRS_F_DEPTH: src = latest_depth(e); need = n * e->H * e->W * 4; break;
     case TRS_F_ROWDEPTH: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_depth; need = (size_t)e->H * 4; } break;
     // the tables live on the host exactly as built; their LDS images on the device are re-laid-out (pitched map)
     case TRS_F_MAP: if (e->track_loaded) { src = e->tab.map.data(); need = e->tab.map.size() * 4; host_src = true; } break;
@@ -1661,7 +1656,7 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
     }
     struct Item { const void* src; void* dst; size_t bytes; };
     const Item items[8] = {
-        {h_img ? e->img[(e->step_count + 1) & 1].get() : nullptr, h_img, img_b},
+        {h_img ? latest_frame(e) : nullptr, h_img, img_b},
         {k.x, h_x, n * 4}, {k.y, h_y, n * 4}, {k.z, h_z, n * 4}, {k.speed, h_speed, n * 4}, {k.cte, h_cte, n * 4},
         {k.seg_idx, h_seg, n * 4}, {k.done, h_done, n},
     };
@@ -1770,8 +1765,8 @@ int upload_dyn_tables(trs_env* e, const trs_pre_config& c)
     HIPCHK(hipMemcpy(t.data(), e->hsv_tab.get(), 512 * sizeof(int), hipMemcpyDeviceToHost));
     unsigned lo[4], hi[4]; int dc[4];
     for (int k = 0; k < 4; ++k) {
-        lo[k] = c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16);
-        hi[k] = c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16);
+        lo[k] = (unsigned)trsim::pack_hsv(c.hsv_lo[k]);
+        hi[k] = (unsigned)trsim::pack_hsv(c.hsv_hi[k]);
         dc[k] = c.dst_channel[k];
     }
     unsigned sel = 0;
@@ -1864,8 +1859,8 @@ int upload_palette(trs_env* e)
             { int rc = ensure_hsv_table(e); if (rc) return rc; }
             hb.f_color = c.color_filter_enabled; hb.f_nfilters = c.n_filters; hb.f_contrast = c.contrast_ratio; hb.f_offset = c.contrast_offset;
             for (int k = 0; k < 4; ++k) {
-                hb.f_lo[k] = (unsigned)(c.hsv_lo[k][0] | (c.hsv_lo[k][1] << 8) | (c.hsv_lo[k][2] << 16));
-                hb.f_hi[k] = (unsigned)(c.hsv_hi[k][0] | (c.hsv_hi[k][1] << 8) | (c.hsv_hi[k][2] << 16));
+                hb.f_lo[k] = (unsigned)trsim::pack_hsv(c.hsv_lo[k]);
+                hb.f_hi[k] = (unsigned)trsim::pack_hsv(c.hsv_hi[k]);
                 hb.f_dst[k] = c.dst_channel[k];
             }
             hb.hsv_tab = e->hsv_tab.get();
@@ -1882,7 +1877,7 @@ int upload_palette(trs_env* e)
 // `lds_step` / `cell`: the step kernel's LDS image and the map cell of the track the tables are for.
 int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S)
 {
-    if (steps_that_fit(e, variant_bits(e->rp.depth != 0, false, false, true, false), lds_step) < 1)   // (a lens excludes the other variants)
+    if (handle_fit(e, variant_bits(e->rp.depth != 0, false, false, true, false), lds_step) == trsim::LdsFit::no_launch)   // (a lens excludes the other variants)
         return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lens camera's palette (" + std::to_string(lds_step) + " B of tables at " +
                                    std::to_string(e->pp.envs_per_wg) + " envs per workgroup): the lens camera needs a shorter track or fewer envs per GPU");
     std::string err;
@@ -1961,8 +1956,6 @@ int ensure_glue(trs_env* e, size_t bytes)
     return TRS_OK;
 }
 
-const uint8_t* latest_frame(const trs_env* e) { return e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr; }
-
 }  // namespace
 
 TRS_EXPORT void trs_default_pre_config(trs_pre_config* c)
@@ -1986,23 +1979,20 @@ TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
         int rc = check_pre(c);
         if (rc) return rc;
         if (c->edge_detection_enabled) return fail(TRS_ERR_ARG, "the Canny layer is a neighbourhood operator: not a palette filter, use trs_preprocess");
-        if (c->dynamic_brightness && e->track_loaded && e->hilly)
-            return fail(TRS_ERR_STATE, "the loaded track has elevation: a frame's palette is evaluated per env inside the kernels there, and the dynamic-brightness filter behind the "
-                                       "rasteriser is not built for that; the static filter works, or use trs_preprocess on the rendered frames");
-        if (c->dynamic_brightness && e->lens_on)
-            return fail(TRS_ERR_STATE, "a lens camera is set: the dynamic-brightness filter behind the rasteriser is not built for the lens camera (trs_set_camera(NULL) first); "
-                                       "the static filter works, or use trs_preprocess on the rendered frames");
+        if (c->dynamic_brightness)
+            if (const Variant set = trsim::variant_clash(variant_now(e), kVDyn)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVDyn, set));
         if (c->dynamic_brightness) {
             const int rpp = kRasterThreads / (e->W / 4);
             if (rpp < 1 || (79 + rpp - 1) / rpp > 16) return fail(TRS_ERR_LIMIT, "image too wide for the in-kernel dynamic-brightness filter (class bits of the brightness rows live in 4 registers), use trs_preprocess");
             const Variant v = trsim::variant_of(e) | kVDyn;       // what the handle runs with this filter: checked without, then with, its scene lighting
-            if (e->track_loaded && steps_that_fit(e, v & ~kVLight, e->lds_step) < 1)
+            if (e->track_loaded && handle_fit(e, v & ~kVLight, e->lds_step) == trsim::LdsFit::no_launch)
                 return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the in-kernel dynamic-brightness palette, use trs_preprocess");
-            if (e->track_loaded && e->light_on && steps_that_fit(e, v, e->lds_step) < 1)
+            const trsim::LdsFit fit = e->track_loaded ? handle_fit(e, v, e->lds_step) : trsim::LdsFit::ok;
+            if (fit == trsim::LdsFit::no_launch)             // (only with scene lighting: the filter alone fits)
                 return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the dynamic-brightness palettes with scene lighting, use trs_preprocess");
             // resident mode: the worker keeps its env state and hand-off ring in LDS as well — refuse HERE, with the reason, what every later
             // trs_step would otherwise refuse as "too many envs per workgroup" 
-            if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits(e, v))
+            if (fit == trsim::LdsFit::no_worker)
                 return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the dynamic-brightness palettes of a batch: "
                                            "select TRS_STEP_LAUNCH for this filter, or use trs_preprocess");
         }
@@ -2038,12 +2028,7 @@ TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
     if (on) {
         if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
         if (e->W % 8) return fail(TRS_ERR_LIMIT, "the lens camera needs an image width that is a multiple of 8 (the kernels store half of the mirror-symmetric table)");
-        if (e->track_loaded && e->hilly)
-            return fail(TRS_ERR_STATE, "the loaded track has elevation: the lens camera is built for flat tracks only (the ground plane of a hilly track tilts per env and frame)");
-        if (e->has_frame_filter && e->filter_dynamic)
-            return fail(TRS_ERR_STATE, "the dynamic-brightness frame filter is set: it is not built for the lens camera (trs_set_frame_filter without dynamic brightness, or NULL, first)");
-        if (e->light_on)
-            return fail(TRS_ERR_STATE, "scene lighting is set: it is not built for the lens camera (trs_set_lighting(NULL) first)");
+        if (const Variant set = trsim::variant_clash(variant_now(e), kVLens)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVLens, set));
     }
     HIPCHK(hipSetDevice(e->device));
     // nothing may be in flight, and a resident worker leaves, BEFORE anything of the camera changes (the worker's quiesce can still launch for steps
@@ -2074,14 +2059,12 @@ int set_lighting_impl(trs_env* e, const float* d_params, trsim::DevBuf<float> ow
 {
     const bool on = d_params != nullptr;
     if (on) {
-        const char* why = nullptr;
-        if (!e->cfg.render) why = "the env has no camera (cfg.render == 0)";
-        else if (e->lens_on) why = "a lens camera is set: scene lighting is not built for the lens camera (trs_set_camera(NULL) first)";
-        if (why) return fail(TRS_ERR_STATE, why);
-        const Variant v = trsim::variant_of(e) | kVLight;     // what the handle runs with lighting
-        if (e->track_loaded && steps_that_fit(e, v, e->lds_step) < 1)
+        if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
+        if (const Variant set = trsim::variant_clash(variant_now(e), kVLight)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVLight, set));
+        const trsim::LdsFit fit = e->track_loaded ? handle_fit(e, trsim::variant_of(e) | kVLight, e->lds_step) : trsim::LdsFit::ok;   // what the handle runs with lighting
+        if (fit == trsim::LdsFit::no_launch)
             return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lit palettes");
-        if (e->track_loaded && trsim::resident_on(e) && !trsim::resident_fits(e, v))
+        if (fit == trsim::LdsFit::no_worker)
             return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the lighting parameters and lit palettes: select TRS_STEP_LAUNCH");
     }
     // nothing may be in flight and a resident worker leaves before the kernels change (upload_palette quiesces too; the old host copy is freed after that)
@@ -2149,8 +2132,8 @@ TRS_EXPORT int trs_preprocess(trs_env* e, const trs_pre_config* c, const uint8_t
     p.dynamic = c->dynamic_brightness; p.color = c->color_filter_enabled; p.n_filters = c->n_filters;
     p.contrast = c->contrast_ratio; p.offset = c->contrast_offset; p.baseline = c->brightness_baseline;
     for (int f = 0; f < 4; ++f) {
-        p.lo[f] = c->hsv_lo[f][0] | (c->hsv_lo[f][1] << 8) | (c->hsv_lo[f][2] << 16);
-        p.hi[f] = c->hsv_hi[f][0] | (c->hsv_hi[f][1] << 8) | (c->hsv_hi[f][2] << 16);
+        p.lo[f] = trsim::pack_hsv(c->hsv_lo[f]);
+        p.hi[f] = trsim::pack_hsv(c->hsv_hi[f]);
         p.dst_ch[f] = c->dst_channel[f];
     }
     if (c->edge_detection_enabled) {
@@ -2445,7 +2428,7 @@ bool trs_internal_view(trs_env* e, TrsEnvView* v)
     if (quiesce(e)) return false;                            // the pilot's kernels go onto the handle's stream
     v->device = e->device; v->n = e->n; v->H = e->H; v->W = e->W; v->render = e->cfg.render;
     v->stream = e->sP;
-    v->latest_frame = (e->cfg.render && e->step_count > 0) ? e->img[(e->step_count + 1) & 1].get() : nullptr;
+    v->latest_frame = e->step_count > 0 ? latest_frame(e) : nullptr;
     v->speed = e->pp.speed; v->seg_idx = e->pp.seg_idx; v->n_points = e->pp.np;
     v->ctl_steer = e->ctl_steer; v->ctl_thr = e->ctl_thr; v->ctl_brk = e->ctl_brk;
     v->step_count = e->step_count;

@@ -49,7 +49,6 @@
 namespace trsim {
 
 constexpr int kSlots = 8;       // posts in flight: ring entries, arrival counters, done flags
-constexpr int kCamDepth = 4;    // steps the physics team may run ahead of the raster team
 
 struct WEntry {                 // one posted step: ONE 64-B line, so the dispatcher learns of a post and gets it in one PCIe read
     uint64_t seq_lo;            // step index + 1: the tag of the line's FIRST 32-byte half, written by the host after steer / thr / brk
@@ -204,7 +203,6 @@ __device__ __forceinline__ T sys_load_val(const T* p)
 }
 
 // what a workgroup shares in LDS (behind the tables)
-constexpr int kSlotWords = 20;  // one hand-off slot: camera parameters (4) | x y z yaw v speed cte seg epr epl sf last_return (12) | done | view pitch (a track with elevation) | 2 spare
 struct WLds {
     u64* word;          // posted count | flags as last seen by this workgroup's leader
     u64* fwd;           // steps this workgroup has completely passed on (the forwarder's count; the dispatcher's idle clock reads it)
@@ -214,8 +212,6 @@ struct WLds {
     float* slot;        // [kCamDepth][epw][kSlotWords] physics -> raster: the pose to render AND the telemetry to write out
     float* lst;         // [epw][16] env state carried from step to step
 };
-
-__host__ __device__ inline size_t wlds_slot_off(int epw) { return (64 + (size_t)epw * 8 + 15) & ~(size_t)15; }
 
 __device__ __forceinline__ WLds wlds_of(unsigned char* base, int epw)
 {
@@ -228,33 +224,6 @@ __device__ __forceinline__ WLds wlds_of(unsigned char* base, int epw)
     l.slot = reinterpret_cast<float*>(base + wlds_slot_off(epw));
     l.lst = l.slot + (size_t)kCamDepth * epw * kSlotWords;
     return l;
-}
-
-__host__ __device__ inline size_t wlds_bytes(int epw)
-{
-    return wlds_slot_off(epw) + (size_t)kCamDepth * epw * kSlotWords * 4 + (size_t)epw * 64;
-}
-
-// The render worker's dynamic LDS behind the tables (lds_step bytes) for variant v: the one layout worker_fits sizes the launch by and fills WParams
-// from; the kernel takes lds_off_light from its last step (worker_lds_light, from WParams::lds_off_hill).
-//   ctl:   the control block (WLds) + 16 spare bytes
-//   dyn:   (16-aligned, DYN) the dynamic-brightness filter's palettes, sums and tables (FParams::lds_off)
-//   hill:  (16-aligned) the batch's row tables and the raster team's barrier counter (HILLS) or the lens palette (LENS)
-//   light: (16-aligned, LIGHT) the ring of lighting parameters float[kCamDepth][epw][8], then the lit palettes
-struct WorkerLds { int ctl, dyn, hill, light, total; };
-__host__ __device__ inline int worker_lds_light(int hill, int H, Variant v) { return (hill + tabs_lds_bytes(H, v) + 15) & ~15; }
-__host__ __device__ inline WorkerLds worker_lds_layout(int lds_step, int epw, int H, int W, Variant v)
-{
-    WorkerLds L;
-    L.ctl = (lds_step + 15) & ~15;
-    int end = (int)(L.ctl + wlds_bytes(epw) + 16);
-    L.dyn = (end + 15) & ~15;
-    if (v & kVDyn) end = L.dyn + dyn_lds_bytes(H);
-    L.hill = (end + 15) & ~15;
-    if (v & (kVHills | kVLens)) end = L.hill + tabs_lds_bytes(H, v);
-    L.light = worker_lds_light(L.hill, H, v);
-    L.total = (v & kVLight) ? L.light + light_lds_extra(H, W, kCamDepth * epw, (v & kVHills) != 0, (v & kVDyn) != 0) : end;
-    return L;
 }
 
 // a bounded wait gave up: tell the host, every workgroup (device word) and this workgroup (LDS word)
@@ -1344,7 +1313,6 @@ void resident_retry(trs_env* e)
 }
 bool resident_running(const trs_env* e) { return e && e->res && e->res->running; }
 void resident_clear_fault(trs_env* e) { if (e && e->res) e->res->broken = false; }
-bool resident_fits(const trs_env* e, Variant v) { return worker_lds_layout(e->lds_step, e->pp.envs_per_wg, e->H, e->W, v).total <= 160 * 1024; }
 
 int resident_post(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, size_t stride, int* n_done)
 {

@@ -1,5 +1,6 @@
 // trsim_tables.cpp — see trsim_tables.hpp.  Product code: independent of oracle/.
 #include "trsim_tables.hpp"
+#include "trsim_plan.hpp"
 
 #include <algorithm>
 #include <array>
@@ -316,6 +317,75 @@ int build_lens_tables(const trs_config& cfg, double cell, double kx, double ky, 
         }
     }
     return TRS_OK;
+}
+
+namespace {
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+}
+
+int track_layout(const TrackTables& T, int H, bool render, int envs_per_wg, TrackLayout& L, std::string& err)
+{
+    L = TrackLayout{};
+    const size_t n_points = (size_t)T.n_points;
+    // ---- physics LDS image: px | py | pz | tangent (when it fits) + scratch ----
+    const size_t pts = align_up(n_points * 8, 16);
+    const size_t scratch = (size_t)(kPhysBlock / 64) * (16 + 4) + 16;     // physics-only kernel: per-wave sinks
+    size_t off = 0;
+    L.p.off_py = (int)(off += pts); L.p.off_pz = (int)(off += pts); off += pts;
+    L.p.pts_bytes = (int)off;
+    L.p.off_tan = (int)off;
+    const size_t tan_bytes = align_up(n_points * 8, 16);
+    // ---- raster LDS image: map (rows pitched to an odd number of words) @0 | rowtab | palette ----
+    const int pitch_words = T.info.map_words | 1;          // odd pitch: rows of the map start on different LDS banks
+    L.r.map_pitch_b = pitch_words * 4;
+    if (L.r.map_pitch_b >= (1 << 24) || T.info.map_h >= (1 << 24)) { err = "map exceeds the 24-bit multiply of the rasteriser"; return TRS_ERR_LIMIT; }
+    const size_t map_bytes = (size_t)L.r.map_pitch_b * T.info.map_h;
+    size_t roff = align_up(map_bytes, 16);
+    L.r.off_rowtab = (int)roff; roff += align_up((size_t)H * 8, 16);
+    L.r.off_pal = (int)roff; roff += (size_t)H * 16;
+    L.r.off_depth = (int)roff; roff += align_up((size_t)H * 4, 16);
+    L.r.off_sky = (int)roff;
+    if (T.hills) roff += align_up((size_t)H * 4, 16);     // a track with elevation: the sky colour of every row rides in the raster image (hill_rows_build)
+    L.r.blob_bytes = (int)roff;
+    L.r.lds_r = (int)align_up(roff, 16);
+    if ((size_t)L.r.blob_bytes > (size_t)100 * 1024) { err = "map + camera tables exceed the step kernel's LDS staging capacity"; return TRS_ERR_LIMIT; }
+    // tangents ride in LDS when the fused kernel's image (raster tables + points + tangents) still fits a CU's 160 KiB
+    L.lds_off_phys = L.r.lds_r;
+    const size_t grid_bytes = align_up(T.grid_start.size() * 2, 16) + align_up(T.grid_pts.size() * 2, 16);
+    // (... and leaves room for what the kernels keep behind the tables: the camera hand-off ring of a few steps, and on a track with elevation the two per-env
+    // row tables + the view pitches — the mountain track's points + tangents fill the CU to within 150 bytes on their own)
+    const size_t behind = (size_t)envs_per_wg * 4 + 16 + (size_t)envs_per_wg * 20 * 3 + (T.hills ? (size_t)hill_lds_bytes(H) + 64 : 0);
+    L.p.tan_in_lds = ((size_t)L.lds_off_phys + off + grid_bytes + tan_bytes + behind <= 160 * 1024) ? 1 : 0;
+    if (L.p.tan_in_lds) off += tan_bytes;
+    // nearest-point accelerator tables ride behind the points (uint16 cell starts + point lists)
+    L.p.off_gstart = (int)off; off += align_up(T.grid_start.size() * 2, 16);
+    L.p.off_gpts = (int)off; off += align_up(T.grid_pts.size() * 2, 16);
+    L.p.blob_bytes = (int)off;
+    L.p.off_scratch = (int)off;
+    L.p.lds_p = (int)align_up(off + scratch, 16);
+    L.lds_step = (int)align_up((size_t)L.lds_off_phys + off, 16);
+    if (L.p.lds_p > 160 * 1024 || (render && L.lds_step > 160 * 1024)) { err = "track too long for the LDS-resident nearest-point search"; return TRS_ERR_LIMIT; }
+    return TRS_OK;
+}
+
+void pack_track_images(const TrackTables& T, int H, const TrackLayout& L, std::vector<unsigned char>& phys, std::vector<unsigned char>& raster)
+{
+    const size_t n_points = (size_t)T.n_points;
+    phys.assign((size_t)L.p.blob_bytes, 0);
+    std::memcpy(phys.data(), T.px.data(), n_points * 8);
+    std::memcpy(phys.data() + L.p.off_py, T.py.data(), n_points * 8);
+    std::memcpy(phys.data() + L.p.off_pz, T.pz.data(), n_points * 8);
+    if (L.p.tan_in_lds) std::memcpy(phys.data() + L.p.off_tan, T.tangent.data(), n_points * 8);
+    if (!T.grid_start.empty()) std::memcpy(phys.data() + L.p.off_gstart, T.grid_start.data(), T.grid_start.size() * 2);
+    if (!T.grid_pts.empty()) std::memcpy(phys.data() + L.p.off_gpts, T.grid_pts.data(), T.grid_pts.size() * 2);
+
+    raster.assign((size_t)L.r.blob_bytes, 0);
+    for (int row = 0; row < T.info.map_h; ++row)
+        std::memcpy(raster.data() + (size_t)row * L.r.map_pitch_b, T.map.data() + (size_t)row * T.info.map_words, (size_t)T.info.map_words * 4);
+    std::memcpy(raster.data() + L.r.off_rowtab, T.rowtab.data(), (size_t)H * 8);
+    std::memcpy(raster.data() + L.r.off_pal, T.palette.data(), (size_t)H * 16);
+    std::memcpy(raster.data() + L.r.off_depth, T.rowdepth.data(), (size_t)H * 4);
+    if (T.hills) std::memcpy(raster.data() + L.r.off_sky, T.sky.data(), (size_t)H * 4);
 }
 
 }  // namespace trsim
