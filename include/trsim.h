@@ -156,7 +156,9 @@ int trs_step_sequence_host(trs_env* env, const float* h_steering, const float* h
  *   TRS_STEP_RESIDENT a worker kernel stays on the GPU (tables staged once, env state in LDS, one workgroup per CU) and a
  *     call only POSTS the step: control pointers into a ring in pinned host memory that the worker polls.  No kernel launch,
  *     no kernel boundary, no table re-staging per step; the physics team runs ahead of the raster team as far as posted
- *     steps allow; up to 8 steps may be in flight, a post beyond that waits.  The worker leaves by itself after `idle_us`
+ *     steps allow; up to 8 steps may be in flight, a post beyond that waits.  Like every step path it stores the rows of a frame
+ *     that do not depend on the pose once per frame buffer and palette, not every step: the frame buffers are read-only for the
+ *     consumer (trs_get_state).  The worker leaves by itself after `idle_us`
  *     (<= 0: 2000) without a post and is started again by the next one.  While it is resident it owns the handle's stream:
  *     trs_sync waits for the posted steps only (completion flags in host memory), trs_copy_to_host / trs_fetch_outputs copy
  *     on a side stream, and every OTHER call that needs the stream (reset, set_pose, load_track, image path, control glue,
@@ -207,7 +209,11 @@ int trs_resident_debug_lifetime(trs_env* env, int life_us);
 int trs_resident_debug_abort(trs_env* env);
 #endif
 
-/* Telemetry of the last step (components/gyminterface.py:76,95-104) as device pointers. */
+/* Telemetry of the last step (components/gyminterface.py:76,95-104) as device pointers.
+ * The frame buffers behind `img` and `depth` (two each, alternating by step) are READ-ONLY for the consumer, in every step mode: rows of a frame that do
+ * not depend on the pose (sky, ground beyond the far plane: the leading rows of a flat track's frame) are stored once per buffer and palette, and later
+ * steps into that buffer store only the rows that see the track.  After trs_sync the view is always a whole frame; a consumer that wrote into it would
+ * find its bytes in those rows two steps later.  Copy a frame before changing it (trs_preprocess writes to a buffer of its own). */
 int trs_get_state(trs_env* env, trs_state_view* out);
 
 /* Synchronising copy of one field to host memory (`which` = TRS_F_*). `bytes` must match. */

@@ -23,7 +23,7 @@ struct trs_env {
     // Memory the library allocates is held by DevBuf / PinnedBuf members (trsim_mem.hpp) and goes with the handle; raw pointers below are views.
     trsim::DevBuf<> slab;                // state + controls
     trsim::DevBuf<uint8_t> img[2];
-    bool uniform_ok[2] = {false, false}; // frame buffer b holds the current palette's uniform rows (sky, beyond the far plane) of every env (launch_step)
+    trsim::UniformRows uniform_ok;       // which frame buffer holds the present palette's uniform rows (sky, beyond the far plane) of every env: every step path asks it (trsim_plan.hpp)
     trsim::DevBuf<float> depth[2];
     trsim::DevBuf<> blob_p;              // physics LDS image
     trsim::DevBuf<> blob_r;              // raster LDS image

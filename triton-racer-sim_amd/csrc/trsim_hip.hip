@@ -86,9 +86,9 @@ struct SParams {
                                         // launch (camera parameters from the global ring, written by the previous launch)
     unsigned step_base;                 // absolute index of this launch's physics step 0
     int lds_off_phys, lds_off_cam, lds_off_prog, cam_stride;   // LDS: physics image, float4 lcam[n_phys][cam_stride], int pprog[cam_stride]
-    int skip_uniform;                   // 1: the target frame buffer already holds this palette's uniform rows (sky, beyond the far plane: they depend on neither the
-                                        // pose nor the step) of every env — an earlier step wrote them and nothing has touched them since: only the rows that see the
-                                        // track are written.  Set by the closed pilot loop only (trs_internal_step_launch); every other step path writes whole frames.
+    int skip_uniform;                   // bit b: frame buffer b (steps with index & 1 == b) already holds this palette's uniform rows (sky, beyond the far plane: they
+                                        // depend on neither the pose nor the step) of every env — an earlier step wrote them and nothing has touched them since: only the
+                                        // rows that see the track are written.  Every step path gets it from the handle's UniformRows (trsim_plan.hpp), launch_step here.
     FParams fp;
 };
 
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
         const FrameDesc fd = frame_desc<DEPTH>(p, img, dep, e);
         RasterThread rl = rth;                                                // (LIGHT: shaded from this wave's lit copy of the palette)
         if constexpr (LIGHT && !HILLS && !DYN) rl.pal_off = light_wave_palette(p, lds_off_lpal, llight + (e - e_begin) * 8, lfilt, wave, lane);
-        if (!sp.skip_uniform) raster_uniform_rows<DEPTH>(p, rl, fd);
+        if (!((sp.skip_uniform >> (abs_step & 1u)) & 1)) raster_uniform_rows<DEPTH>(p, rl, fd);
         // -- rows that see the track
         float4 cam;
         const int j = e - e_begin;
@@ -1066,13 +1066,12 @@ bool resident_steps(const trs_env* e) { return trsim::resident_on(e); }
 // one launch of the fused step kernel: physics steps [step_base, step_base + n_phys) and the frames of launch-local
 // steps r_first..r_last (-1 = step_base - 1, whose camera parameters the previous launch left in the global ring)
 int launch_step(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth,
-                int n_phys, int r_first, int r_last, uint64_t step_base, bool keep_uniform = false)
+                int n_phys, int r_first, int r_last, uint64_t step_base)
 {
     const Variant v = trsim::variant_of(e);
     const StepKernel kernel = kStepKernels[v];
     if (!kernel) return fail(TRS_ERR_STATE, "internal error: no step kernel is built for this combination of camera, track, frame filter and lighting");
     SParams sp;
-    const bool dyn = (v & kVDyn) != 0;
     sp.ph = e->pp;
     sp.ph.ctl_steer = st; sp.ph.ctl_thr = th; sp.ph.ctl_brk = br; sp.ph.ctl_reset = rs; sp.ph.ctl_stride = e->seq_stride;
     sp.ph.synth = synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
@@ -1085,14 +1084,10 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.cam_stride = e->pp.envs_per_wg;
     const StepLds lds = step_lds_layout(e->lds_step, sp.cam_stride, e->H, e->W, v, n_phys);   // ring + counters (+ the variant's regions) behind the tables
     sp.lds_off_cam = lds.cam; sp.lds_off_prog = lds.prog;
-    // Which frame buffers hold the CURRENT palette's uniform rows for every env (e->uniform_ok[b]): a launch that renders whole frames into a buffer makes it
-    // so; a palette change (upload_palette: track, frame filter) or the dynamic-brightness filter (its uniform rows follow each frame's own mean) undoes it.
-    sp.skip_uniform = 0;
-    for (int r = r_first; r <= r_last; ++r) {
-        const int b = (int)((step_base + (uint64_t)(int64_t)r) & 1u);
-        if (keep_uniform && r_first == r_last && e->uniform_ok[b] && !dyn && !e->lens_on && !e->light_on) sp.skip_uniform = 1;
-        else e->uniform_ok[b] = !dyn && !e->lens_on && !e->light_on;             // (the lens camera writes whole frames: no uniform rows; scene lighting: they follow the env's parameters)
-    }
+    // Which frame buffers hold the CURRENT palette's uniform rows for every env (e->uniform_ok, trsim_plan.hpp): the launch skips them there, and the buffers
+    // it renders into hold them afterwards — or no longer, after a DYN, LENS or LIGHT frame.
+    sp.skip_uniform = (int)e->uniform_ok.skip_mask(v);
+    if (r_first <= r_last) e->uniform_ok.rendered(v, step_base + (uint64_t)(int64_t)r_first, (uint64_t)(r_last - r_first + 1));
     sp.fp = trsim::fparams_of(e, lds.dyn);
     hipLaunchKernelGGL(kernel, dim3(grid_of(e)), dim3(kBlock), lds.total, e->sP, sp);
     HIPCHK(hipGetLastError());
@@ -1103,12 +1098,12 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
 // through the LDS progress counters.  Otherwise a software pipeline over launches: a launch advances K physics steps
 // and renders the previous launch's last step plus its own steps 0..K-2; a raster-only launch closes the call, so on
 // return state and image both belong to step s0+n-1.
-int run_camera_steps(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, int per_launch, bool keep_uniform = false)
+int run_camera_steps(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, int per_launch)
 {
     const uint64_t s0 = e->step_count;
     int rc = TRS_OK;
     if (n == 1) {
-        rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0, keep_uniform);
+        rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0);
     } else {
         const int kmax = std::max(1, std::min(per_launch, steps_that_fit(e, trsim::variant_of(e), e->lds_step)));
         for (int done = 0; done < n && !rc;) {
@@ -1206,6 +1201,7 @@ int create_impl(const trs_config* cfg, int device, trs_env* e)
     r.stats = e->stats.get();
     if (cfg->render) {
         e->img_bytes = n * (size_t)e->H * e->W * 3;
+        e->uniform_ok.invalidate();                         // fresh buffers hold no frame
         for (int b = 0; b < 2; ++b) {
             HIPCHK(e->img[b].alloc(e->img_bytes));
             HIPCHK(hipMemsetAsync(e->img[b].get(), 0, e->img_bytes, e->sP));
@@ -1830,9 +1826,9 @@ int upload_palette(trs_env* e)
     std::vector<uint32_t> pal(e->tab.palette);
     if (e->has_frame_filter && !e->filter_dynamic && !e->light_on)   // dynamic brightness: the kernel filters a per-env palette itself; scene lighting: lit, then filtered, in the kernel
         for (auto& c : pal) c = filter_colour(e->frame_filter, c);
+    { int rq = sync_all(e); if (rq) return rq; }               // frames in flight keep the palette they were launched with (a resident worker leaves here and reports what it rendered)
     e->rp.uni_rows = (e->hilly || e->lens_on) ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame;
-    e->uniform_ok[0] = e->uniform_ok[1] = false;               //  the lens camera: on the pixel)  (the closed pilot loop's steps skip rows an earlier step wrote: not across a palette change)
-    { int rq = sync_all(e); if (rq) return rq; }               // frames in flight keep the palette they were launched with
+    e->uniform_ok.invalidate();                                //  the lens camera: on the pixel)  (steps skip uniform rows an earlier step wrote: not across a palette change)
     HIPCHK(hipMemcpy(e->blob_r.get() + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
     if (e->lens_on && e->lens_dev.get()) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
         std::vector<uint32_t> lp(e->lens.palette);
@@ -2451,9 +2447,9 @@ int trs_internal_step_launch(trs_env* e, const float* d_st, const float* d_th, c
 {
     if (!e || !e->track_loaded) return fail(TRS_ERR_STATE, "no track loaded");
     { int rq = quiesce(e); if (rq) return rq; }
-    // (the loop's own steps: the uniform rows of a frame buffer — sky, beyond the far plane — are written by the first step that renders into it and kept after that:
+    // (like every step path: the uniform rows of a frame buffer — sky, beyond the far plane — are written by the first step that renders into it and kept after that:
     // 41 % of a frame's bytes at the default camera, 4.8 of the 16.5 us of this step at 1024 x 120x160, ~20 of 48 us at 512 x 240x320 + depth)
-    const int rc = e->cfg.render ? run_camera_steps(e, d_st, d_th, d_br, nullptr, 0, 1, 1, true) : run_physics_steps(e, d_st, d_th, d_br, nullptr, 0, 1, 1);
+    const int rc = e->cfg.render ? run_camera_steps(e, d_st, d_th, d_br, nullptr, 0, 1, 1) : run_physics_steps(e, d_st, d_th, d_br, nullptr, 0, 1, 1);
     if (!rc) trsim::resident_note_launch(e);               // resident mode selected: this step has no completion flag, trs_sync / the copies wait for the stream
     return rc;
 }

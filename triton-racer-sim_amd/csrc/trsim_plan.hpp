@@ -167,6 +167,46 @@ inline LdsFit lds_fit(int lds_step, int epw, int H, int W, Variant v, bool resid
     return resident && !resident_fits(lds_step, epw, H, W, v) ? LdsFit::no_worker : LdsFit::ok;
 }
 
+// ---- uniform rows: which frame buffers already hold them, and what a raster wave of the worker then stores ---------------------------
+// The leading RParams::uni_rows rows of a frame (sky, ground beyond the far plane) are the palette's rows: they depend on neither the pose, the env
+// nor the step.  A frame buffer that a step has rendered into with the present palette holds them for every env, and later steps into that buffer
+// store only the rows that see the track; the consumer still finds a whole frame.  This is the one owner of "does buffer b hold them":
+//   launch_step, worker_launch ask skip_mask();  launch_step and the worker's exit (handle_exit) report what was rendered with rendered();
+//   upload_palette (track, frame filter, camera, lens, lighting), the buffers' allocation and a worker that ended by its abort bit call invalidate().
+// DYN, LENS and LIGHT frames have no such rows (the filter follows each frame's mean, the lens decides per pixel, the palette is lit per env): a step
+// of those variants skips nothing and leaves its buffer without them.  HILLS has uni_rows == 0: skipping is a no-op there.
+constexpr bool variant_keeps_uniform(Variant v) { return !(v & (kVDyn | kVLens | kVLight)); }
+struct UniformRows {
+    bool ok[2] = {false, false};                // frame buffer b (= step index & 1) holds the present palette's uniform rows of every env
+    void invalidate() { ok[0] = ok[1] = false; }
+    // bit b: steps of variant v that render into buffer b need not store their uniform rows
+    unsigned skip_mask(Variant v) const { return variant_keeps_uniform(v) ? (ok[0] ? 1u : 0u) | (ok[1] ? 2u : 0u) : 0u; }
+    // steps [first, first + n) of variant v have rendered (whole frames, or all but rows the buffer held already)
+    void rendered(Variant v, unsigned long long first, unsigned long long n)
+    {
+        for (unsigned long long k = 0; k < n && k < 2; ++k) ok[(first + k) & 1ull] = variant_keeps_uniform(v);
+    }
+};
+
+// The resident worker's raster waves (trs_worker_kernel, the plain path) skip the uniform rows of step s when the host's mask says buffer s & 1 holds them,
+// or when this launch of the worker (it began at step `start`) has itself rendered step s - 2: every thread then skips exactly the bytes it stored two steps ago.
+TRS_HD inline bool worker_skips_uniform(unsigned mask, unsigned long long start, unsigned long long s) { return ((mask >> (s & 1ull)) & 1u) != 0 || s - start >= 2; }
+// Store instructions a raster wave issues for one step: nstep with its uniform rows (nuni of them), nstep - nuni without.
+TRS_HD inline int worker_step_stores(int nstep, int nuni, bool skips) { return skips ? nstep - nuni : nstep; }
+// The count of the lagged arrival for step `owed`, taken inside step s (owed < s) behind `uni_now` store instructions of step s's uniform rows: exactly what
+// the wave has issued since the end of step `owed` — the whole steps between, each with or without its uniform rows, and uni_now.  (A count that is too
+// small only waits longer; one that is too large would publish a frame before it is in memory.)
+TRS_HD inline int worker_wait_count(unsigned mask, unsigned long long start, unsigned long long owed, unsigned long long s, int nstep, int nuni, int uni_now)
+{
+    int n = uni_now;
+    for (unsigned long long q = owed + 1; q < s; ++q) n += worker_step_stores(nstep, nuni, worker_skips_uniform(mask, start, q));
+    return n;
+}
+// Steps of lag between a wave's stores and its arrival: two always, three where two whole steps and the uniform rows in front of the wait still fit the
+// 6-bit counter — sized by the steps a launch of the worker spends its life on: without their uniform rows where the variant skips them (from its third
+// step on; the first two may be longer, their counts are then clamped to 63, which only waits for more).
+TRS_HD inline int worker_lag(int nstep, int nuni, bool skipping) { return (2 * worker_step_stores(nstep, nuni, skipping) + (skipping ? 0 : nuni) <= 63) ? 3 : 2; }
+
 // ---- the two LDS images of a track ------------------------------------------------------------------------------------------
 // physics image:  px | py | pz | tangent (tan_in_lds) | grid starts | grid points, and behind it the physics-only kernel's scratch (lds_p bytes of LDS)
 // raster image:   map (rows pitched to an odd number of words) @0 | rowtab | palette | depth | sky (a track with elevation)

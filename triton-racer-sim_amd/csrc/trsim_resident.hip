@@ -13,7 +13,8 @@
 //         scope), camera parameters into an LDS ring kCamDepth deep; it runs ahead of the raster team as far as posts and
 //         the ring allow (back-pressure: a slot is reused once all raster waves have read it)
 //   raster team: per step: the uniform rows of ALL the workgroup's envs first (they need no pose), then per env the rows
-//         that see the track; every store write-through (sc0 sc1)
+//         that see the track; every store write-through (sc0 sc1).  The uniform rows are stored only while the step's frame
+//         buffer does not hold them yet (UniformRows, trsim_plan.hpp): from its third step on a launch stores the other rows alone
 //   completion: every wave drains its stores (s_waitcnt vmcnt(0)) and arrives on an LDS counter; the workgroup's last wave
 //         arrives on a device counter sharded by blockIdx % 8, the last shard on a top counter, and the last of all stores
 //         done[step % 8] = step + 1 into the mailbox (system scope).  One writer per flag and step, so the host never sees
@@ -97,6 +98,7 @@ struct WParams {
     unsigned long long checkin_ticks;                       // how long the dispatcher waits for every workgroup of the launch to report in
     int lds_off_phys, lds_off_ctl, n_blocks;
     int lds_off_hill;                                       // a track with elevation: two per-env row tables (hill_table_bytes each) + the raster team's barrier counter
+    unsigned uni_mask;                                      // bit b: frame buffer b holds the palette's uniform rows of every env already (UniformRows::skip_mask at the launch)
     FParams fp;                                             // DYN instantiation: ImgPreprocessing with dynamic brightness behind the rasteriser (trs_set_frame_filter)
 };
 #ifndef TRS_RESIDENT_DIAG
@@ -123,6 +125,7 @@ struct Resident {
                                          // completion flag will ever be written for them — the stream is what to wait for
     bool fell_back = false;              // a launch of the worker was found not co-resident (another process's worker on the GPU): the handle went
                                          // back to TRS_STEP_LAUNCH by itself (trs_last_error() says so); trs_set_step_mode selects resident mode again
+    uint64_t gen_start = 0; Variant gen_variant = 0;    // the running (or last) launch of the worker: its first step and its kernel variant (what it rendered: worker_rendered)
     bool dc_ready = false; uint64_t dc_ready_for = 0;   // the device control block has been zeroed and set up for a launch that starts at this step (handle_exit does it for the NEXT launch)
     std::chrono::steady_clock::time_point t_launch{};   // when the running worker was launched (the host gives up on a launch that never reports in)
     std::chrono::steady_clock::time_point t_fallback{}; // when the handle went back to launches; resident mode is tried again retry_ms later
@@ -655,10 +658,14 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
     int own = 0;                                              // envs whose telemetry this wave writes out (2 store instructions each)
     for (int j = wave; j < n_loc; j += kRasterThreads / 64) ++own;
     const int nuni = nu * n_loc, nstep = (nu + ng) * n_loc + 2 * own;
+    // The plain path below does not store the uniform rows of a step whose frame buffer holds them already (worker_skips_uniform, trsim_plan.hpp: the host's
+    // mask, or this launch's own step two steps earlier): such a step issues nstep - nuni store instructions, and the counted waits follow what each step
+    // really issued (worker_wait_count).  The DYN, HILLS, LIGHT and LENS paths write whole frames: nstep every step.
+    constexpr bool kSkipUniform = !DYN && !HILLS && !LIGHT && !LENS;
     // two steps of lag always: what the wave then waits for was issued a whole step ago (a count beyond 63 is clamped, which only
     // asks for what the 6-bit counter enforces anyway); three where a step is so short that even that is younger than a store's
-    // round trip (small shards: 2 * nstep + nuni still fits the counter)
-    const int lag = (2 * nstep + nuni <= 63) ? 3 : 2;
+    // round trip (two whole steps and the uniform rows in front of the wait still fit the counter: worker_lag)
+    const int lag = worker_lag(nstep, nuni, kSkipUniform);
     // this lane's telemetry array (lanes 0..11: 4-byte arrays in slot-word order, lanes 12, 13: the byte arrays done, pending)
     unsigned char* optr = nullptr;
     {
@@ -833,16 +840,20 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
             }
             continue;
         }
-        const bool sweep = ahead == 0;
+        // this step's uniform rows are in its frame buffer already: only the rows that see the track are stored (the sweep order only applies to steps that write them)
+        const bool skipu = kSkipUniform && worker_skips_uniform(wp.uni_mask, wp.start, s);
+        const bool sweep = ahead == 0 && !skipu;
         if (sweep)
             for (int j = 0; j < n_loc; ++j) raster_uniform_rows<DEPTH>(p, rth, frame_desc<DEPTH>(p, img, dep, e_begin + j));
         for (int j = 0; j < n_loc; ++j) {
             const FrameDesc fd = frame_desc<DEPTH>(p, img, dep, e_begin + j);
-            if (!sweep) raster_uniform_rows<DEPTH>(p, rth, fd);
+            if (!sweep && !skipu) raster_uniform_rows<DEPTH>(p, rth, fd);
             if (j == 0)                                       // arrivals owed: everything this wave has issued since the end of step `owed`
-                while (s - owed >= keep) {                    // is (s - owed - 1) whole steps + this step's uniform rows so far
+                while (s - owed >= keep) {                    // is the whole steps between (with or without their uniform rows) + this step's uniform rows so far
                     const u64 tv0 = probe ? now_clk() : 0;
-                    if (!(kDiag & 1)) wait_vmcnt_le((int)(s - owed - 1) * nstep + (sweep ? nuni : nu));
+                    if (!(kDiag & 1))
+                        wait_vmcnt_le(kSkipUniform ? worker_wait_count(wp.uni_mask, wp.start, owed, s, nstep, nuni, skipu ? 0 : (sweep ? nuni : nu))
+                                                   : (int)(s - owed - 1) * nstep + (sweep ? nuni : nu));
                     if (probe) t_vm += now_clk() - tv0;
                     raster_arrive(l, owed++, lane);
                 }
@@ -1118,7 +1129,8 @@ int worker_launch(trs_env* e, uint64_t start)
     wp.ph = e->pp; wp.ph.synth = 0; wp.ph.write_cam = 0; wp.ph.n_steps = 0; wp.ph.step_off = 0; wp.ph.ctl_stride = 0;
     wp.ra = e->rp;
     wp.img0 = e->img[0].get(); wp.img1 = e->img[1].get(); wp.dep0 = e->depth[0].get(); wp.dep1 = e->depth[1].get();
-    e->uniform_ok[0] = e->uniform_ok[1] = false;            // (launch_step's bookkeeping of which buffer holds whole frames of the current palette: not kept across a worker)
+    wp.uni_mask = e->cfg.render ? e->uniform_ok.skip_mask(variant_of(e)) : 0u;   // buffers that hold the uniform rows already; the launch's own steps are reported when it has ended (worker_rendered)
+    R->gen_start = start; R->gen_variant = e->cfg.render ? variant_of(e) : 0u;
     wp.mb = mb; wp.dc = R->dc.get();
     wp.start = start;
     wp.idle_ticks = (unsigned long long)R->idle_us * 100ull;
@@ -1144,11 +1156,21 @@ int worker_launch(trs_env* e, uint64_t start)
     return TRS_OK;
 }
 
+// the worker's kernel has ended normally having processed the steps below `consumed`: the frame buffers it rendered into hold the uniform rows now (or, after
+// DYN / LENS / LIGHT frames, no longer); a launch that was called off (consumed == its first step) changes nothing
+void worker_rendered(trs_env* e, uint64_t consumed)
+{
+    Resident* R = e->res;
+    if (e->cfg.render && consumed > R->gen_start) e->uniform_ok.rendered(R->gen_variant, R->gen_start, consumed - R->gen_start);
+    R->gen_start = std::max(R->gen_start, consumed);         // (reported once)
+}
+
 int worker_error(trs_env* e)
 {
     const uint64_t err = host_load(&e->res->mb->error);
     if (!err) return TRS_OK;
     e->res->broken = true;
+    e->uniform_ok.invalidate();                              // waves left in the middle of frames
     static const char* const what[] = {"", "waiting for a post", "camera ring back-pressure", "waiting for the physics team", "forwarding the last arrivals",
                                        "team barrier of the dynamic-brightness batch", "", "abort injected by trs_resident_debug_abort (test hook)", "",
                                        "dynamic LDS segment not at offset 0"};
@@ -1194,6 +1216,7 @@ int handle_exit(trs_env* e, bool relaunch = true)
     int rc = worker_error(e);
     if (rc) return rc;
     const uint64_t consumed = host_load(&R->mb->consumed), posted = host_load(&R->mb->posted);
+    worker_rendered(e, consumed);
     if (host_load(&R->mb->exited) == kExitNotCoresident)
         return fall_back_to_launches(e, consumed, "the launch did not get every CU within 2 ms");
     if (consumed > R->seen_done) R->seen_done = consumed;   // the kernel has ended: everything it consumed is complete
@@ -1228,6 +1251,7 @@ int give_up_on_launch(trs_env* e)
     R->running = false;
     int rc = worker_error(e);
     if (rc) return rc;
+    worker_rendered(e, host_load(&R->mb->consumed));
     return fall_back_to_launches(e, host_load(&R->mb->consumed), "the launch had not started after 250 ms");
 }
 

@@ -288,7 +288,10 @@ class BatchedEnv:
         ``torch.as_tensor(env.device_array('ep_return'), device='cuda')``.  The env's steps run on the env's own stream, so
         the view is ordered first: with ``stream=`` (the CONSUMER's stream) that stream is made to wait for the env's work
         queued so far (``trs_stream_signal_external``), otherwise the host waits (``sync=False`` skips even that: the caller
-        orders).  ``'img'`` / ``'depth'`` alternate between two buffers: the frame of step s is overwritten by step s + 2."""
+        orders).  ``'img'`` / ``'depth'`` alternate between two buffers: the frame of step s is overwritten by step s + 2.
+        The frame buffers are READ-ONLY for the consumer: rows that do not depend on the pose (sky, ground beyond the far plane) are
+        written once per buffer and palette, later steps store only the rows that see the track — bytes written into a view would
+        show up in those rows two steps later.  Clone a frame before changing it."""
         if stream is not None:
             self.api.check(self.api.stream_signal_external(self._h, _stream_ptr(stream) or None), "stream_signal_external")
         elif sync:
