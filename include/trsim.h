@@ -225,6 +225,36 @@ int trs_copy_to_host(trs_env* env, int which, void* h_dst, size_t bytes);
 int trs_fetch_outputs(trs_env* env, uint8_t* h_img, float* h_x, float* h_y, float* h_z, float* h_speed, float* h_cte,
                       int32_t* h_seg_idx, uint8_t* h_done);
 
+/* ---- observation latency: what the car is told, `sim_latency` of the reference's gym_config per env (include/trsim_spec.h, "observation latency") ----
+ * The reference delays every telemetry packet by sim_latency ms (components/gyminterface.py:96).  Here an env's delay is L_e ticks: after step T of the
+ * history its observation is the truth record of step T - L_e (frame, depth frame, x, y, z, speed, cte, index), or the constructor's state (zeros,
+ * arrived = 0) while T - L_e < 1.  The history begins at trs_set_latency and at trs_load_track; resets do not restart it.  Everything that shows what the
+ * simulator did (trs_get_state, trs_fetch_outputs, trs_copy_to_host, rewards, done, returns) stays the truth, bit for bit; trs_pilot_act,
+ * trs_pilot_forward*, trs_preprocess and trs_normalize with NULL sources keep meaning the newest rendered frame (pass the view's pointers for the
+ * delayed one); trs_step_pilot alone switches: the controls of tick T + 1 are KerasPilot.step(observation after T) where it has arrived, else (0, 0, 0).
+ *   h_ticks: int32[n_envs], each in [0, max_ticks]; 1 <= max_ticks <= 30.  NULL: off — from the next step on every byte any call shows is what a
+ *   handle that never set a latency shows.  TRS_ERR_ARG for values out of range; TRS_ERR_NOMEM (the message names the bytes it wanted) when the ring
+ *   of max_ticks + 2 frame slots does not fit; TRS_ERR_STATE while resident mode is selected — trs_set_step_mode(TRS_STEP_RESIDENT) is refused
+ *   likewise while a latency is set.  A refused call leaves the handle unchanged.  The call synchronises the handle.
+ * With a latency set every step is one launch (n_steps > 1, sequences and steps_per_launch > 1 loop single-step launches: the results do not change),
+ * followed by one launch of trs_obs_kernel.  One delay for all envs moves no frame byte: the view's `img` points into the ring slot of step T - L.
+ * The view handed out after step T stays intact while step T + 1 runs, like the frames of trs_get_state.  Physics-only handles: img == NULL. */
+typedef struct trs_obs_view {
+    uint32_t struct_size;
+    int32_t  n_envs, img_h, img_w;
+    const uint8_t* img;              /* uint8[n_envs][H][W][3], NULL without a camera */
+    const float*   depth;            /* float[n_envs][H][W], NULL unless cfg.depth */
+    const float *pos_x, *pos_y, *pos_z, *speed, *cte;
+    const int32_t* seg_idx;
+    const uint8_t* arrived;          /* uint8[n_envs]: 1 once T - L_e >= 1 */
+} trs_obs_view;
+int trs_set_latency(trs_env* env, const int32_t* h_ticks_or_null, int max_ticks);
+int trs_get_latency(trs_env* env, int32_t* h_ticks_out_or_null, int* max_ticks_out);   /* *max_ticks_out == 0: off (ticks then all 0) */
+int trs_get_observation(trs_env* env, trs_obs_view* out);   /* device pointers; TRS_ERR_STATE while latency is off */
+/* like trs_fetch_outputs: the observation of all envs in one synchronisation, any pointer NULL */
+int trs_fetch_observation(trs_env* env, uint8_t* h_img, float* h_x, float* h_y, float* h_z, float* h_speed, float* h_cte,
+                          int32_t* h_seg_idx, uint8_t* h_arrived);
+
 /* Overwrite env pose (x, y, z, yaw, v) from host arrays of n_envs floats — test hook. */
 int trs_set_pose(trs_env* env, const float* h_x, const float* h_y, const float* h_z,
                  const float* h_yaw, const float* h_v);

@@ -151,6 +151,22 @@
  *   a frame filter the frame equals filter(L_e(raw frame)) — with dynamic brightness, the frame's mean is the LIT frame's.  Depth, state, indices
  *   and returns are untouched.  Not defined here (refused): the lens camera.  tests/test_lighting_cpu.py restates the rule in numpy against the product's
  *   function (csrc/trsim_tables.hpp, light_channel); tests/test_lighting_gpu.py checks frames against the oracle's raw frames with the rule applied.
+ *
+ * ---- observation latency (trs_set_latency; sim_latency of the reference's gym_config, per env; HIP library only) --------------------------------
+ *   The reference accepts a telemetry packet sim_latency ms after it was sent (components/gyminterface.py:96); with the fixed tick that is a delay of
+ *   L ticks, L = ceil(ms * loop_hz / 1000).  Per env e a delay L_e in [0, max_ticks], max_ticks <= 30.
+ *   T: the number of env steps taken since the later of trs_set_latency and trs_load_track — both begin the history.  trs_reset, a d_reset byte,
+ *   auto_reset and trs_set_pose do NOT: the reference's pipeline keeps delivering the old episode's packets after reset_car.
+ *   After step T the truth record is R_T = (frame, depth frame if cfg.depth, x, y, z, speed, cte, seg_idx), exactly as trs_get_state shows it.
+ *     observation of env e after step T = R_{T - L_e}[e]                          when T - L_e >= 1
+ *                                       = all frame bytes 0, depth 0.0f, telemetry 0, index 0   otherwise (the constructor's state, gyminterface.py:56,60-64)
+ *     arrived[e] = (T - L_e >= 1)
+ *   which is the delay line of HipGymInterface (it returns R_{t-L} from tick L + 1 on).  Nothing else is delayed: state, frames, rewards, done and
+ *   returns of every existing call are the truth, bit for bit, whatever the delays.
+ *   Closed loop (trs_step_pilot): the controls of tick T + 1 are KerasPilot.step(observation after T) for envs with arrived[e], and (0, 0, 0) for the
+ *   others (keras_pilot.py:46-47: no frame yet); the speed (every model type that reads it) and 'loc/segment' (full house) are the observation's.
+ *   The observation handed out after step T stays intact while step T + 1 runs.  tests/test_latency_cpu.py checks the ring arithmetic against a deque;
+ *   tests/test_latency_gpu.py checks observations against the oracle's records kept in a list.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

@@ -41,6 +41,16 @@ class TrsStateView(C.Structure):
     ]
 
 
+class TrsObsView(C.Structure):
+    """``trs_obs_view`` (include/trsim.h): what the cars are told after the last step, as device pointers (``trs_get_observation``)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_envs", C.c_int32), ("img_h", C.c_int32), ("img_w", C.c_int32),
+        ("img", C.c_void_p), ("depth", C.c_void_p),
+        ("pos_x", C.c_void_p), ("pos_y", C.c_void_p), ("pos_z", C.c_void_p), ("speed", C.c_void_p), ("cte", C.c_void_p),
+        ("seg_idx", C.c_void_p), ("arrived", C.c_void_p),
+    ]
+
+
 class TrsMapInfo(C.Structure):
     _fields_ = [
         ("map_w", C.c_int32), ("map_h", C.c_int32), ("map_words", C.c_int32),
@@ -131,9 +141,12 @@ LENS_SYMBOLS = ["default_camera", "set_camera", "get_camera"]
 # HIP library only: scene lighting (trs_set_lighting) has no twin in the C oracle either — its checker is the oracle's unlit frame with the rule of
 # include/trsim_spec.h ("scene lighting") applied in numpy (tests/test_lighting_cpu.py, tests/test_lighting_gpu.py)
 LIGHT_SYMBOLS = ["set_lighting", "set_lighting_host"]
+# HIP library only: observation latency (trs_set_latency) is a view on the truth the oracle already checks — its checker is the history of oracle records
+# with the rule of include/trsim_spec.h ("observation latency") applied in Python (tests/test_latency_cpu.py, tests/test_latency_gpu.py)
+LATENCY_SYMBOLS = ["set_latency", "get_latency", "get_observation", "fetch_observation"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -216,6 +229,12 @@ class Api:
             "set_lighting": (i32, [vp, vp]),
             "set_lighting_host": (i32, [vp, C.POINTER(C.c_float)]),
         }
+        latency = {
+            "set_latency": (i32, [vp, vp, i32]),
+            "get_latency": (i32, [vp, vp, C.POINTER(i32)]),
+            "get_observation": (i32, [vp, C.POINTER(TrsObsView)]),
+            "fetch_observation": (i32, [vp] + [vp] * 8),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -236,6 +255,12 @@ class Api:
         self.has_lighting = hasattr(cdll, prefix + "set_lighting")
         if self.has_lighting:
             for name, (res, args) in light.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_latency = hasattr(cdll, prefix + "set_latency")
+        if self.has_latency:
+            for name, (res, args) in latency.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

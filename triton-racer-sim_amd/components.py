@@ -57,6 +57,21 @@ def _lighting_for(cfg):
     return triple(g, 1.0), triple(b, 0.0)
 
 
+def sim_latency_ticks(sim_latency, loop_hz=20, n=None):
+    """``sim_latency`` of a gym_config (ms; gyminterface.py:96 sleeps that long before a telemetry frame is accepted) as ticks of the fixed-step
+    env, by ``HipGymInterface``'s rule ``ceil(ms * loop_hz / 1000)``: a number, or one value per env -> int32 array (``n`` given: broadcast to it)."""
+    import math
+    ms = np.atleast_1d(np.asarray(0 if sim_latency is None else sim_latency, dtype=np.float64))
+    if np.any(ms < 0):
+        raise ValueError("sim_latency must not be negative")
+    ticks = np.asarray([int(math.ceil(float(v) * float(loop_hz) / 1000.0)) for v in ms.ravel()], dtype=np.int32)
+    if n is not None:
+        if ticks.size not in (1, int(n)):
+            raise ValueError(f"sim_latency has {ticks.size} values, the interface has {n} envs")
+        ticks = np.ascontiguousarray(np.broadcast_to(ticks, (int(n),)))
+    return ticks
+
+
 class HipGymInterface(Component):
     """One car (N = 1).  ``step(steering, throttle, breaking, reset) -> (img, x, y, z, speed, cte)``."""
 
@@ -128,6 +143,13 @@ class BatchedGymInterface(Component):
         self.env = BatchedEnv(n_envs=n_envs, track=_track_for(self.gym_config), device=self.gym_config.get("hip_device", 0),
                               img_h=int(self.gym_config["img_h"]), img_w=int(self.gym_config["img_w"]), render=True,
                               auto_reset=auto_reset, env_id_base=env_id_base, camera=_camera_for(self.gym_config), _api=_api)
+        # sim_latency (ms; a number or one value per env): the observation ports carry what each car is told, that many ticks late
+        # (BatchedEnv.set_latency); all zero: nothing is set and the code path is the one without the key
+        sl = self.gym_config["sim_latency"]
+        self.latency_ticks = sim_latency_ticks(sl, self.gym_config.get("loop_hz", 20), n_envs)
+        self.delayed = bool(np.any(self.latency_ticks > 0))
+        if self.delayed:
+            self.env.set_latency(self.latency_ticks)
 
     def set_lighting(self, params=None, bias=None):
         """Scene lighting per env (``BatchedEnv.set_lighting``): redraw it at episode resets for domain randomisation."""
@@ -147,6 +169,12 @@ class BatchedGymInterface(Component):
         else:
             self.env.step(steering, throttle, breaking, reset=None if reset is None else reset)
         names = ["img", "pos_x", "pos_y", "pos_z", "speed", "cte", "seg_idx", "done"]
+        if self.delayed:                                       # the observation, sim_latency late; 'gym/done' stays the truth
+            if self.to_host:
+                return (*self.env.observation()[:7], self.env.fetch("done"))
+            if self.sync:
+                self.env.sync()
+            return (*(self.env.device_observation(n, sync=False) for n in names[:7]), self.env.device_array("done", sync=False))
         if self.to_host:
             return self.env.fetch_outputs()
         # device handles: the step ran on the env's own stream, so order it before anyone looks (one wait for the tuple).

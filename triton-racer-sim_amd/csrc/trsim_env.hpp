@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/trsim.h"
 #include "trsim_device.hpp"
@@ -43,6 +44,18 @@ struct trs_env {
     bool light_on = false;
     const float* light = nullptr;             // view: the registered float[n][8], the caller's or light_own's
     trsim::DevBuf<float> light_own;           // trs_set_lighting_host's copy
+    // observation latency (trs_set_latency; include/trsim_spec.h, "observation latency"): while lat.on() every step renders into a slot of ring_img /
+    // ring_dep, trs_obs_kernel files its telemetry in ring_tel and gathers every env's delayed record; img[] / depth[] then hold the gathered frames
+    // (envs with different delays) or lie idle (one delay for all: the view points into the ring)
+    trsim::ObsRing lat;                       // slot arithmetic (trsim_plan.hpp)
+    uint64_t lat_base = 0;                    // step_count when the history began: T = step_count - lat_base
+    bool lat_uniform = true; int lat_all = 0; // every env has the delay lat_all
+    trsim::DevBuf<int32_t> lat_ticks; std::vector<int32_t> lat_host;   // int32[n]: L_e, device and host
+    trsim::DevBuf<uint8_t> ring_img; size_t ring_img_stride = 0;   // [slots] frames of all envs, stride bytes apart (a multiple of 256)
+    trsim::DevBuf<float> ring_dep; size_t ring_dep_stride = 0;     // [slots] depth frames (cfg.depth), stride bytes apart
+    trsim::DevBuf<float> ring_tel;            // [slots][6][n]: x y z speed cte | seg_idx (int32)
+    trsim::DevBuf<float> obs_tel[2];          // [6][n] the gathered telemetry, by T & 1
+    trsim::DevBuf<uint8_t> obs_flag[2];       // arrived[n] | mode[n] (TRS_MODE_AI where arrived, else TRS_MODE_HUMAN: the pilot tail's mask), by T & 1
     trsim::DevBuf<unsigned long long> stats;
     trsim::DevBuf<double> loc_q; trsim::DevBuf<int32_t> loc_out; int loc_cap = 0;   // trs_locate: room for loc_cap queries
     trsim::DevBuf<uint8_t> pre;          // processed frames of the env (trs_preprocess with d_dst == NULL)
@@ -79,6 +92,7 @@ struct trs_env {
 // ---- trsim_resident.hip (the resident worker: one step per trs_step call without a launch per step) ----
 namespace trsim {
 bool resident_on(const trs_env* e);                       // resident mode selected for this handle
+bool resident_selected(const trs_env* e);                 // ... or selected and gone back to launches for now (the GPU is shared): it comes back by itself
 void resident_retry(trs_env* e);                          // a handle that fell back to launches (GPU shared with another process) tries resident mode again when due
 // hand n steps to the worker; controls as in trs_step (device pointers, or host-pinned pointers the device can read);
 // stride: elements between consecutive steps' control arrays (0 = held), synth: controls from the spec's generator

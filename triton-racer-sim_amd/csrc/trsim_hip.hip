@@ -920,6 +920,93 @@ __global__ __launch_bounds__(256) void trs_normalize_kernel(const uint32_t* src,
     }
 }
 
+// ---- observation latency (include/trsim_spec.h, "observation latency"): one launch behind every step while a latency is set ----------------------
+// Workgroups [0, tel_blocks): one thread per env files the step's telemetry in ring slot `slot_now` and gathers the env's delayed record (zeros and
+// arrived = 0 until it exists).  The other workgroups (only when the envs' delays differ) move every env's delayed frame, then depth frame, from its ring
+// slot into the gathered frame: a copy, 16 B per lane, kObsVecs loads in flight per thread, the source slot uniform per workgroup, no LDS.  Source and
+// destination lie at the same offset from a 256-aligned base, so one split serves both: up to three 4-byte pieces in front of the 16-aligned middle
+// (an env's frame is a multiple of 4 bytes, of 16 only for some sizes) and up to three behind it.  Envs that have not arrived get zeros without a read.
+constexpr int kObsBlock = 256, kObsVecs = 4;
+struct ObsFrames { const uint8_t* ring; size_t stride; uint8_t* out; unsigned env_bytes; int blocks_per_env; };
+struct ObsParams {
+    const float* truth[5]; const int32_t* seg;                // x y z speed cte | seg_idx as the step left them
+    float* ring_tel;                                          // [slots][6][n]
+    const int32_t* ticks;                                     // L_e
+    float* out_tel; uint8_t* out_flag;                        // [6][n] | arrived[n], mode[n]
+    int n, slots, slot_now;
+    long long T;                                              // steps of the history so far, this one included
+    int tel_blocks;
+    ObsFrames img, dep;                                       // blocks_per_env == 0: nothing to gather
+};
+// workgroups per env frame: 16 KiB of the middle each, at least one (it also moves the 4-byte pieces)
+inline int obs_blocks_per_env(unsigned env_bytes) { const unsigned per = kObsBlock * kObsVecs; return (int)std::max(1u, (env_bytes / 16u + per - 1) / per); }
+
+__device__ __forceinline__ void obs_move_env(const ObsFrames& f, const ObsParams& p, int env, int blk, int tid)
+{
+    const int L = p.ticks[env];
+    const bool arrived = p.T - (long long)L >= 1;
+    int slot = p.slot_now - L;
+    if (slot < 0) slot += p.slots;
+    const size_t off = (size_t)env * f.env_bytes;
+    const unsigned head = min((16u - (unsigned)(off & 15u)) & 15u, f.env_bytes);
+    const unsigned vecs = (f.env_bytes - head) >> 4, tail = f.env_bytes - head - (vecs << 4);
+    const uint8_t* const src = f.ring + (size_t)slot * f.stride + off;
+    uint8_t* const dst = f.out + off;
+    const uint4* const s4 = reinterpret_cast<const uint4*>(src + head);
+    uint4* const d4 = reinterpret_cast<uint4*>(dst + head);
+    const unsigned v0 = (unsigned)blk * (kObsBlock * kObsVecs) + (unsigned)tid;
+    uint4 r[kObsVecs];
+#pragma unroll
+    for (int k = 0; k < kObsVecs; ++k) {
+        const unsigned i = v0 + k * kObsBlock;
+        r[k] = make_uint4(0u, 0u, 0u, 0u);
+        if (arrived && i < vecs) r[k] = s4[i];
+    }
+#pragma unroll
+    for (int k = 0; k < kObsVecs; ++k) {
+        const unsigned i = v0 + k * kObsBlock;
+        if (i < vecs) d4[i] = r[k];
+    }
+    if (blk == 0) {                                           // the 4-byte pieces: threads 0..2 in front, 64..66 behind
+        const unsigned t = (unsigned)tid;
+        if (t < head / 4u) reinterpret_cast<uint32_t*>(dst)[t] = arrived ? reinterpret_cast<const uint32_t*>(src)[t] : 0u;
+        const unsigned tb = head + (vecs << 4);
+        if (t >= 64u && t - 64u < tail / 4u)
+            reinterpret_cast<uint32_t*>(dst + tb)[t - 64u] = arrived ? reinterpret_cast<const uint32_t*>(src + tb)[t - 64u] : 0u;
+    }
+}
+
+__global__ __launch_bounds__(kObsBlock) void trs_obs_kernel(const ObsParams p)
+{
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    if (b < p.tel_blocks) {
+        const int i = b * kObsBlock + tid;
+        if (i >= p.n) return;
+        const size_t n = (size_t)p.n;
+        float* const now = p.ring_tel + (size_t)p.slot_now * 6 * n;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) now[k * n + i] = p.truth[k][i];
+        reinterpret_cast<int32_t*>(now)[5 * n + i] = p.seg[i];
+        const int L = p.ticks[i];
+        const bool arrived = p.T - (long long)L >= 1;
+        int slot = p.slot_now - L;
+        if (slot < 0) slot += p.slots;
+        const float* const then = p.ring_tel + (size_t)slot * 6 * n;      // (L == 0: what this thread has just stored)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) p.out_tel[k * n + i] = arrived ? (L == 0 ? p.truth[k][i] : then[k * n + i]) : 0.0f;
+        reinterpret_cast<int32_t*>(p.out_tel)[5 * n + i] = arrived ? (L == 0 ? p.seg[i] : reinterpret_cast<const int32_t*>(then)[5 * n + i]) : 0;
+        p.out_flag[i] = arrived ? 1 : 0;
+        p.out_flag[n + i] = arrived ? (uint8_t)TRS_MODE_AI : (uint8_t)TRS_MODE_HUMAN;
+        return;
+    }
+    b -= p.tel_blocks;
+    const int img_blocks = p.n * p.img.blocks_per_env;
+    if (b < img_blocks) { obs_move_env(p.img, p, b / p.img.blocks_per_env, b % p.img.blocks_per_env, tid); return; }
+    b -= img_blocks;
+    if (p.dep.blocks_per_env > 0 && b < p.n * p.dep.blocks_per_env) obs_move_env(p.dep, p, b / p.dep.blocks_per_env, b % p.dep.blocks_per_env, tid);
+}
+
 // DriverAssistance.step for N cars (components/driver_assistance.py:13-31), in place; binary64 like the reference's Python floats
 __global__ void trs_driver_assist_kernel(int mode, double k, float* st, float* th, float* br, const float* sp, int n)
 {
@@ -1037,8 +1124,20 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 namespace {
 
 // the frame buffers written by the last step (nullptr without a camera / without cfg.depth)
-const uint8_t* latest_frame(const trs_env* e) { return e->cfg.render ? e->img[(e->step_count + 1) & 1].get() : nullptr; }
-const float* latest_depth(const trs_env* e) { return (e->cfg.render && e->cfg.depth) ? e->depth[(e->step_count + 1) & 1].get() : nullptr; }
+// (with an observation latency set: the ring slot of the last step — every step then renders into the ring, trsim_plan.hpp, ObsRing)
+long long history_steps(const trs_env* e) { return (long long)(e->step_count - e->lat_base); }   // T of "observation latency": steps since the history began
+uint8_t* ring_frame(const trs_env* e, int slot) { return e->ring_img.get() + (size_t)slot * e->ring_img_stride; }
+float* ring_depth(const trs_env* e, int slot) { return reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(e->ring_dep.get()) + (size_t)slot * e->ring_dep_stride); }
+const uint8_t* latest_frame(const trs_env* e)
+{
+    if (!e->cfg.render) return nullptr;
+    return e->lat.on() ? ring_frame(e, e->lat.slot_of_step(history_steps(e))) : e->img[(e->step_count + 1) & 1].get();
+}
+const float* latest_depth(const trs_env* e)
+{
+    if (!(e->cfg.render && e->cfg.depth)) return nullptr;
+    return e->lat.on() ? ring_depth(e, e->lat.slot_of_step(history_steps(e))) : e->depth[(e->step_count + 1) & 1].get();
+}
 
 int grid_of(const trs_env* e) { return (e->n + e->pp.envs_per_wg - 1) / e->pp.envs_per_wg; }
 
@@ -1076,8 +1175,16 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.ph.ctl_steer = st; sp.ph.ctl_thr = th; sp.ph.ctl_brk = br; sp.ph.ctl_reset = rs; sp.ph.ctl_stride = e->seq_stride;
     sp.ph.synth = synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
     sp.ra = e->rp;
-    sp.img0 = e->img[0].get(); sp.img1 = e->img[1].get();
-    sp.dep0 = e->depth[0].get(); sp.dep1 = e->depth[1].get();
+    const bool ring = e->lat.on();                                // an observation latency is set: the one frame of this launch goes to its ring slot
+    if (ring) {
+        if (n_phys != 1 || r_first != 0 || r_last != 0) return fail(TRS_ERR_STATE, "internal error: a step with an observation latency set is one launch that renders its own frame");
+        const int slot = e->lat.slot_of_step((long long)(step_base - e->lat_base) + 1);
+        sp.img0 = sp.img1 = ring_frame(e, slot);
+        sp.dep0 = sp.dep1 = e->cfg.depth ? ring_depth(e, slot) : nullptr;
+    } else {
+        sp.img0 = e->img[0].get(); sp.img1 = e->img[1].get();
+        sp.dep0 = e->depth[0].get(); sp.dep1 = e->depth[1].get();
+    }
     sp.n_phys = n_phys; sp.r_first = r_first; sp.r_last = r_last;
     sp.step_base = (unsigned)step_base;
     sp.lds_off_phys = e->lds_off_phys;
@@ -1086,10 +1193,41 @@ int launch_step(trs_env* e, const float* st, const float* th, const float* br, c
     sp.lds_off_cam = lds.cam; sp.lds_off_prog = lds.prog;
     // Which frame buffers hold the CURRENT palette's uniform rows for every env (e->uniform_ok, trsim_plan.hpp): the launch skips them there, and the buffers
     // it renders into hold them afterwards — or no longer, after a DYN, LENS or LIGHT frame.
-    sp.skip_uniform = (int)e->uniform_ok.skip_mask(v);
-    if (r_first <= r_last) e->uniform_ok.rendered(v, step_base + (uint64_t)(int64_t)r_first, (uint64_t)(r_last - r_first + 1));
+    // A ring slot is never claimed: every step into the ring stores whole frames (the uniform-row skip does not carry over to ring slots).
+    sp.skip_uniform = ring ? 0 : (int)e->uniform_ok.skip_mask(v);
+    if (!ring && r_first <= r_last) e->uniform_ok.rendered(v, step_base + (uint64_t)(int64_t)r_first, (uint64_t)(r_last - r_first + 1));
     sp.fp = trsim::fparams_of(e, lds.dyn);
     hipLaunchKernelGGL(kernel, dim3(grid_of(e)), dim3(kBlock), lds.total, e->sP, sp);
+    HIPCHK(hipGetLastError());
+    return TRS_OK;
+}
+
+// The launch behind every step while an observation latency is set (trs_obs_kernel): the step that has just been counted is filed in the ring and every
+// env's delayed record gathered.  One delay for all envs: the frame view points into the ring (obs_view) and only the telemetry part runs.
+int launch_obs(trs_env* e)
+{
+    const long long T = history_steps(e);
+    const PParams& k = e->pp;
+    ObsParams p;
+    std::memset(&p, 0, sizeof p);
+    p.truth[0] = k.x; p.truth[1] = k.y; p.truth[2] = k.z; p.truth[3] = k.speed; p.truth[4] = k.cte; p.seg = k.seg_idx;
+    p.ring_tel = e->ring_tel.get(); p.ticks = e->lat_ticks.get();
+    const int b = trsim::ObsRing::gather_buf(T);
+    p.out_tel = e->obs_tel[b].get(); p.out_flag = e->obs_flag[b].get();
+    p.n = e->n; p.slots = e->lat.slots(); p.slot_now = e->lat.slot_of_step(T); p.T = T;
+    p.tel_blocks = (e->n + kObsBlock - 1) / kObsBlock;
+    int grid = p.tel_blocks;
+    if (e->cfg.render && !e->lat_uniform) {
+        p.img = ObsFrames{e->ring_img.get(), e->ring_img_stride, e->img[b].get(), (unsigned)((size_t)e->H * e->W * 3), 0};
+        p.img.blocks_per_env = obs_blocks_per_env(p.img.env_bytes);
+        grid += e->n * p.img.blocks_per_env;
+        if (e->cfg.depth) {
+            p.dep = ObsFrames{reinterpret_cast<const uint8_t*>(e->ring_dep.get()), e->ring_dep_stride, reinterpret_cast<uint8_t*>(e->depth[b].get()), (unsigned)((size_t)e->H * e->W * 4), 0};
+            p.dep.blocks_per_env = obs_blocks_per_env(p.dep.env_bytes);
+            grid += e->n * p.dep.blocks_per_env;
+        }
+    }
+    hipLaunchKernelGGL(trs_obs_kernel, dim3(grid), dim3(kObsBlock), 0, e->sP, p);
     HIPCHK(hipGetLastError());
     return TRS_OK;
 }
@@ -1102,6 +1240,15 @@ int run_camera_steps(trs_env* e, const float* st, const float* th, const float* 
 {
     const uint64_t s0 = e->step_count;
     int rc = TRS_OK;
+    if (e->lat.on()) {                                       // an observation latency is set: every step is one launch into its ring slot, and trs_obs_kernel behind it
+        for (int i = 0; i < n; ++i) {
+            const size_t co = (size_t)i * (size_t)e->seq_stride;
+            if ((rc = launch_step(e, st ? st + co : st, th ? th + co : th, br ? br + co : br, i == 0 ? rs : nullptr, synth, 1, 0, 0, s0 + (uint64_t)i))) return rc;
+            e->step_count += 1;
+            if ((rc = launch_obs(e))) return rc;
+        }
+        return TRS_OK;
+    }
     if (n == 1) {
         rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0);
     } else {
@@ -1122,6 +1269,7 @@ int run_camera_steps(trs_env* e, const float* st, const float* th, const float* 
 // physics-only envs: K steps inside one launch of the physics kernel
 int run_physics_steps(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, int per_launch)
 {
+    if (e->lat.on()) per_launch = 1;                         // an observation latency is set: trs_obs_kernel files every step's telemetry
     for (int done = 0; done < n;) {
         const int now = std::min(per_launch, n - done);
         PParams p = e->pp;
@@ -1133,8 +1281,47 @@ int run_physics_steps(trs_env* e, const float* st, const float* th, const float*
         HIPCHK(hipGetLastError());
         e->step_count += (uint64_t)now;
         done += now;
+        if (e->lat.on()) { const int rc = launch_obs(e); if (rc) return rc; }
     }
     return TRS_OK;
+}
+
+// The history of observations begins (trs_set_latency, trs_load_track): nothing has arrived, and every slot an observation can point into before a step
+// has written it holds the constructor's state.  The handle's stream is idle when this is called.
+int latency_restart(trs_env* e)
+{
+    e->lat_base = e->step_count;
+    if (e->ring_img.get()) HIPCHK(hipMemsetAsync(e->ring_img.get(), 0, e->ring_img.bytes(), e->sP));
+    if (e->ring_dep.get()) HIPCHK(hipMemsetAsync(e->ring_dep.get(), 0, e->ring_dep.bytes(), e->sP));
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(hipMemsetAsync(e->obs_tel[b].get(), 0, e->obs_tel[b].bytes(), e->sP));
+        HIPCHK(hipMemsetAsync(e->obs_flag[b].get(), 0, e->obs_flag[b].bytes(), e->sP));
+        if (!e->lat_uniform && e->img[b].get()) HIPCHK(hipMemsetAsync(e->img[b].get(), 0, e->img[b].bytes(), e->sP));        // the gathered frames
+        if (!e->lat_uniform && e->depth[b].get()) HIPCHK(hipMemsetAsync(e->depth[b].get(), 0, e->depth[b].bytes(), e->sP));
+    }
+    HIPCHK(hipStreamSynchronize(e->sP));
+    return TRS_OK;
+}
+
+// what the car is told after the last step (trs_get_observation): device pointers into the gathered telemetry and, for the frames, into the ring (one
+// delay for all envs: no frame byte is moved) or the gathered frames
+void obs_view(const trs_env* e, trs_obs_view* o)
+{
+    const long long T = history_steps(e);
+    const int b = trsim::ObsRing::gather_buf(T);
+    const size_t n = (size_t)e->n;
+    const float* t = e->obs_tel[b].get();
+    o->struct_size = (uint32_t)sizeof *o;
+    o->n_envs = e->n; o->img_h = e->H; o->img_w = e->W;
+    o->img = nullptr; o->depth = nullptr;
+    if (e->cfg.render) {
+        const int slot = e->lat.slot_of_obs(T, e->lat_all);
+        o->img = e->lat_uniform ? ring_frame(e, slot) : e->img[b].get();
+        if (e->cfg.depth) o->depth = e->lat_uniform ? ring_depth(e, slot) : e->depth[b].get();
+    }
+    o->pos_x = t; o->pos_y = t + n; o->pos_z = t + 2 * n; o->speed = t + 3 * n; o->cte = t + 4 * n;
+    o->seg_idx = reinterpret_cast<const int32_t*>(t + 5 * n);
+    o->arrived = e->obs_flag[b].get();
 }
 
 }  // namespace
@@ -1441,6 +1628,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     if ((rc = track_lens_stage(e, T, L, S, ls))) return rc;
     if ((rc = track_commit(e, T, L, S, k, r, ls))) return rc;
     if ((rc = track_start_poses(e))) return rc;
+    if (e->lat.on() && (rc = latency_restart(e))) return rc;  // the observations of the old track's steps do not reach the new one
     return track_drop_misfits(e, clash);
 }
 
@@ -1667,6 +1855,118 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
         off += (it.bytes + 15) & ~(size_t)15;
     }
     HIPCHK(hipStreamSynchronize(cs));
+    { int rf = trsim::check_fault(e); if (rf) return rf; }
+    off = 0;
+    for (const Item& it : items) {
+        if (!it.dst || !it.bytes) continue;
+        std::memcpy(it.dst, e->pinned.get() + off, it.bytes);
+        off += (it.bytes + 15) & ~(size_t)15;
+    }
+    return TRS_OK;
+}
+
+// ---- observation latency (include/trsim_spec.h, "observation latency") ---------------------------------------------------------------
+TRS_EXPORT int trs_set_latency(trs_env* e, const int32_t* h_ticks, int max_ticks)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    if (h_ticks) {
+        if (max_ticks < 1 || max_ticks > trsim::kMaxLatencyTicks) return fail(TRS_ERR_ARG, "max_ticks must be in [1, " + std::to_string(trsim::kMaxLatencyTicks) + "]");
+        for (int i = 0; i < e->n; ++i)
+            if (h_ticks[i] < 0 || h_ticks[i] > max_ticks) return fail(TRS_ERR_ARG, "the latency of env " + std::to_string(i) + " is " + std::to_string(h_ticks[i]) + " ticks: outside [0, max_ticks = " + std::to_string(max_ticks) + "]");
+        if (trsim::resident_selected(e))
+            return fail(TRS_ERR_STATE, "resident mode is selected (trs_set_step_mode): the worker's frame hand-off is built on two buffers by step parity, an observation latency needs "
+                                       "steps by launches (TRS_STEP_LAUNCH first)");
+    }
+    HIPCHK(hipSetDevice(e->device));
+    int rc = sync_all(e);
+    if (rc) return rc;
+    if (!h_ticks) {                                          // off: back to the two frame buffers; the next step into each stores a whole frame
+        if (!e->lat.on()) return TRS_OK;
+        e->lat = trsim::ObsRing{};
+        e->lat_uniform = true; e->lat_all = 0; e->lat_base = 0; e->lat_host.clear();
+        (void)e->ring_img.reset(); (void)e->ring_dep.reset(); (void)e->ring_tel.reset(); (void)e->lat_ticks.reset();
+        for (int b = 0; b < 2; ++b) { (void)e->obs_tel[b].reset(); (void)e->obs_flag[b].reset(); }
+        e->ring_img_stride = e->ring_dep_stride = 0;
+        e->uniform_ok.invalidate();
+        return TRS_OK;
+    }
+    // everything the new setting needs is allocated first: a failure leaves the handle as it was
+    trsim::ObsRing ring; ring.max_ticks = max_ticks;
+    const size_t n = (size_t)e->n, slots = (size_t)ring.slots();
+    const size_t img_stride = e->cfg.render ? align_up(e->img_bytes, 256) : 0;
+    const size_t dep_stride = (e->cfg.render && e->cfg.depth) ? align_up(n * (size_t)e->H * e->W * 4, 256) : 0;
+    trsim::DevBuf<uint8_t> r_img, flag[2]; trsim::DevBuf<float> r_dep, r_tel, tel[2]; trsim::DevBuf<int32_t> ticks;
+    auto want = [&](auto& buf, size_t bytes) -> int {
+        if (!bytes) return TRS_OK;
+        const hipError_t rh = buf.alloc(bytes);
+        if (rh == hipSuccess) return TRS_OK;
+        (void)hipGetLastError();
+        return fail(rh == hipErrorOutOfMemory ? TRS_ERR_NOMEM : TRS_ERR_DEVICE,
+                    "trs_set_latency: the observation ring of " + std::to_string(slots) + " slots wanted " + std::to_string(bytes) + " bytes of device memory (" + hipGetErrorString(rh) + "); the handle is unchanged");
+    };
+    if ((rc = want(r_img, slots * img_stride)) || (rc = want(r_dep, slots * dep_stride)) || (rc = want(r_tel, slots * 6 * n * 4)) || (rc = want(ticks, n * 4))) return rc;
+    for (int b = 0; b < 2; ++b)
+        if ((rc = want(tel[b], 6 * n * 4)) || (rc = want(flag[b], 2 * n))) return rc;
+    HIPCHK(hipMemcpy(ticks.get(), h_ticks, n * 4, hipMemcpyHostToDevice));
+    e->h2d_bytes += n * 4;
+    // commit
+    e->ring_img = std::move(r_img); e->ring_dep = std::move(r_dep); e->ring_tel = std::move(r_tel); e->lat_ticks = std::move(ticks);
+    for (int b = 0; b < 2; ++b) { e->obs_tel[b] = std::move(tel[b]); e->obs_flag[b] = std::move(flag[b]); }
+    e->ring_img_stride = img_stride; e->ring_dep_stride = dep_stride;
+    e->lat = ring;
+    e->lat_host.assign(h_ticks, h_ticks + n);
+    e->lat_all = h_ticks[0];
+    e->lat_uniform = std::all_of(h_ticks, h_ticks + n, [&](int32_t t) { return t == h_ticks[0]; });
+    e->uniform_ok.invalidate();                              // img[] / depth[] become the gathered frames (or lie idle): no step has claimed them when the latency goes off again
+    return latency_restart(e);
+}
+
+TRS_EXPORT int trs_get_latency(trs_env* e, int32_t* h_ticks_out, int* max_ticks_out)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    if (max_ticks_out) *max_ticks_out = e->lat.max_ticks;
+    if (h_ticks_out)
+        for (int i = 0; i < e->n; ++i) h_ticks_out[i] = e->lat.on() ? e->lat_host[(size_t)i] : 0;
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_get_observation(trs_env* e, trs_obs_view* out)
+{
+    if (!e || !out) return fail(TRS_ERR_ARG, "null argument");
+    if (!e->lat.on()) return fail(TRS_ERR_STATE, "no observation latency is set (trs_set_latency): the observation is the state, trs_get_state");
+    obs_view(e, out);
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_fetch_observation(trs_env* e, uint8_t* h_img, float* h_x, float* h_y, float* h_z, float* h_speed, float* h_cte,
+                                     int32_t* h_seg, uint8_t* h_arrived)
+{
+    if (!e) return fail(TRS_ERR_ARG, "null handle");
+    if (!e->lat.on()) return fail(TRS_ERR_STATE, "no observation latency is set (trs_set_latency): the observation is the state, trs_fetch_outputs");
+    if (h_img && !e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
+    HIPCHK(hipSetDevice(e->device));
+    const size_t n = (size_t)e->n, img_b = h_img ? e->img_bytes : 0;
+    const size_t need = ((img_b + 15) & ~(size_t)15) + 7 * ((n * 4 + 15) & ~(size_t)15) + 16;   // every item starts 16-B aligned
+    if (e->pinned.bytes() < need) {
+        if (e->pinned.get()) { int rq = sync_all(e); if (rq) return rq; }
+        HIPCHK(e->pinned.reserve(need, hipHostMallocDefault));
+    }
+    trs_obs_view v;
+    obs_view(e, &v);
+    struct Item { const void* src; void* dst; size_t bytes; };
+    const Item items[8] = {
+        {h_img ? v.img : nullptr, h_img, img_b},
+        {v.pos_x, h_x, n * 4}, {v.pos_y, h_y, n * 4}, {v.pos_z, h_z, n * 4}, {v.speed, h_speed, n * 4}, {v.cte, h_cte, n * 4},
+        {v.seg_idx, h_seg, n * 4}, {v.arrived, h_arrived, n},
+    };
+    size_t off = 0;
+    for (const Item& it : items) {
+        if (!it.dst || !it.bytes) continue;
+        HIPCHK(hipMemcpyAsync(e->pinned.get() + off, it.src, it.bytes, hipMemcpyDeviceToHost, e->sP));
+        e->d2h_bytes += it.bytes;
+        off += (it.bytes + 15) & ~(size_t)15;
+    }
+    HIPCHK(hipStreamSynchronize(e->sP));
     { int rf = trsim::check_fault(e); if (rf) return rf; }
     off = 0;
     for (const Item& it : items) {
@@ -2429,6 +2729,13 @@ bool trs_internal_view(trs_env* e, TrsEnvView* v)
     v->ctl_steer = e->ctl_steer; v->ctl_thr = e->ctl_thr; v->ctl_brk = e->ctl_brk;
     v->step_count = e->step_count;
     v->stats = e->stats.get();
+    v->obs_on = e->lat.on();
+    v->obs_frame = nullptr; v->obs_speed = nullptr; v->obs_seg_idx = nullptr; v->obs_mode = nullptr;
+    if (v->obs_on && history_steps(e) > 0) {                 // what the car is told (trs_get_observation); before the first step of the history: nothing
+        trs_obs_view o;
+        obs_view(e, &o);
+        v->obs_frame = o.img; v->obs_speed = o.speed; v->obs_seg_idx = o.seg_idx; v->obs_mode = o.arrived + e->n;
+    }
     return true;
 }
 void** trs_internal_pilot_slot(trs_env* e) { return e ? &e->pilot : nullptr; }

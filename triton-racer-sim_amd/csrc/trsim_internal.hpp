@@ -16,6 +16,11 @@ struct TrsEnvView {
     float *ctl_steer, *ctl_thr, *ctl_brk;   // the handle's own control staging arrays (device)
     uint64_t step_count;
     unsigned long long* stats;        // TRS_F_STATS (device, uint64[64])
+    // an observation latency is set (trs_set_latency): what the cars are told after the last step (nullptr before the first step of the history) —
+    // trs_step_pilot reads these instead of latest_frame / speed / seg_idx, and masks the cars whose first observation has not arrived
+    bool obs_on;
+    const uint8_t* obs_frame; const float* obs_speed; const int32_t* obs_seg_idx;
+    const uint8_t* obs_mode;          // uint8[n]: TRS_MODE_AI where the env's observation has arrived, else TRS_MODE_HUMAN
 };
 
 bool trs_internal_view(trs_env* e, TrsEnvView* out);

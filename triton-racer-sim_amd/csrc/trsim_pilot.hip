@@ -2501,7 +2501,13 @@ TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_ste
     HIPCHK(hipSetDevice(v.device));
     for (int k = 0; k < n_steps; ++k) {
         trs_internal_view(e, &v);
-        if (v.latest_frame) {                       // KerasPilot.step on the frame of the previous tick
+        if (v.obs_on && v.obs_frame) {              // an observation latency is set: KerasPilot.step on what each car has been told (frame, speed, segment), and
+            TrsEnvView o = v;                       // (0, 0, 0) for the cars nothing has reached yet (keras_pilot.py:46-47) through the tail's mode mask
+            o.speed = v.obs_speed; o.seg_idx = v.obs_seg_idx;
+            const ActIo io{nullptr, nullptr, v.obs_mode, v.ctl_steer, v.ctl_thr, v.ctl_brk};
+            int rc = forward_and_tail(c, o, v.obs_frame, v.n, c->raw.get(), cfg, true, &io);
+            if (rc) return rc;
+        } else if (!v.obs_on && v.latest_frame) {   // KerasPilot.step on the frame of the previous tick
             int rc = forward_and_tail(c, v, v.latest_frame, v.n, c->raw.get(), cfg, true);
             if (rc) return rc;
         } else {                                    // args[0] is None -> (0.0, 0.0, 0.0) (keras_pilot.py:46-47)

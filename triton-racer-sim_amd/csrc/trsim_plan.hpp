@@ -207,6 +207,25 @@ TRS_HD inline int worker_wait_count(unsigned mask, unsigned long long start, uns
 // step on; the first two may be longer, their counts are then clamped to 63, which only waits for more).
 TRS_HD inline int worker_lag(int nstep, int nuni, bool skipping) { return (2 * worker_step_stores(nstep, nuni, skipping) + (skipping ? 0 : nuni) <= 63) ? 3 : 2; }
 
+// ---- observation latency: the ring of truth records and where an env's observation lies in it ----------------------------------------
+// With a latency set (trs_set_latency; include/trsim_spec.h, "observation latency") step T of the history (T = 1 for the first step since the history
+// began) renders into ring slot slot_of_step(T) and trs_obs_kernel files its telemetry there.  The observation of an env with delay L after step T is
+// the record of step T - L; it must stay intact while step T + 1 renders, so the ring has max_ticks + 2 slots: the records T - max_ticks .. T that
+// observations after T may point into, and the one step T + 1 writes.  A step index <= 0 names a slot that no step of the history has written yet
+// (T - L > -slots()): the ring is zeroed when the history begins, so such a slot holds the constructor's state, all zeros.
+// The one owner of this arithmetic: launch_step, trs_obs_kernel's parameters and the views (trs_get_state, trs_get_observation) ask here.
+constexpr int kMaxLatencyTicks = 30;
+struct ObsRing {
+    int max_ticks = 0;                                       // 0: latency is off
+    bool on() const { return max_ticks > 0; }
+    int slots() const { return max_ticks + 2; }
+    int slot_of_step(long long T) const { const int S = slots(); return (int)(((T % S) + S) % S); }
+    static bool arrived(long long T, int L) { return T - L >= 1; }
+    int slot_of_obs(long long T, int L) const { return slot_of_step(T - (long long)L); }
+    // the gathered observation (telemetry always; frames when the envs' delays differ) is double buffered like the frames of a handle without latency
+    static int gather_buf(long long T) { return (int)(T & 1ll); }
+};
+
 // ---- the two LDS images of a track ------------------------------------------------------------------------------------------
 // physics image:  px | py | pz | tangent (tan_in_lds) | grid starts | grid points, and behind it the physics-only kernel's scratch (lds_p bytes of LDS)
 // raster image:   map (rows pitched to an odd number of words) @0 | rowtab | palette | depth | sky (a track with elevation)

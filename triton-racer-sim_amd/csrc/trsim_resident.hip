@@ -1317,6 +1317,7 @@ int ensure_resident(trs_env* e)
 namespace trsim {
 
 bool resident_on(const trs_env* e) { return e && e->res && e->res->enabled; }
+bool resident_selected(const trs_env* e) { return e && e->res && (e->res->enabled || e->res->fell_back); }   // (fell back: resident_retry selects it again by itself)
 
 // A handle that went back to launches because the GPU was shared with another process's worker tries resident mode again by itself:
 // called in front of every step call.  The step that follows starts a worker; if the GPU is still shared the launch is called off
@@ -1541,6 +1542,9 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
         return rc;
     }
     if (!e->track_loaded) return trs_internal_fail(TRS_ERR_STATE, "no track loaded");
+    if (e->lat.on())                                         // (refused before anything of the handle changes)
+        return trs_internal_fail(TRS_ERR_STATE, "an observation latency is set (trs_set_latency): its ring of frames is filled by launches, one per step, and the resident worker hands "
+                                                "frames over by step parity (trs_set_latency(NULL) first)");
     if (!e->res) e->res = new (std::nothrow) Resident();
     if (!e->res) return trs_internal_fail(TRS_ERR_NOMEM, "out of memory");
     int rc = ensure_resident(e);

@@ -405,6 +405,67 @@ class BatchedEnv:
         self.api.check(self.api.set_lighting_host(self._h, h.ctypes.data_as(C.POINTER(C.c_float))), "set_lighting_host")
         self._light_ref = None
 
+    # -- observation latency (trs_set_latency; include/trsim_spec.h, "observation latency") ----------------------------------
+    _OBS_DTYPES = {"img": np.uint8, "depth": np.float32, "pos_x": np.float32, "pos_y": np.float32, "pos_z": np.float32, "speed": np.float32,
+                   "cte": np.float32, "seg_idx": np.int32, "arrived": np.uint8}
+
+    def set_latency(self, ticks=None, max_ticks=None):
+        """Per-env observation latency in ticks (``trs_set_latency``): ``ticks`` is a scalar or one value per env, each in ``[0, max_ticks]``
+        (``max_ticks`` defaults to the largest value, at least 1; at most 30).  ``None``: off.  ``fetch``, ``fetch_outputs`` and ``device_array`` keep
+        showing what the simulator did; ``observation()`` / ``device_observation()`` show what each car is told, ``ticks`` steps late, and
+        ``step_pilot`` drives on that.  The history restarts here and at ``load_track``, not at resets.  Launch mode only."""
+        if not getattr(self.api, "has_latency", False):
+            raise RuntimeError("the oracle has no observation latency (trs_set_latency): it is a view on the truth the oracle checks, HIP library only")
+        if ticks is None:
+            self.api.check(self.api.set_latency(self._h, None, 0), "set_latency")
+            return
+        t = np.asarray(ticks)
+        if t.dtype.kind not in "iu" and not np.all(t == np.round(t)):
+            raise ValueError("latency ticks must be whole numbers")
+        t = np.ascontiguousarray(np.broadcast_to(t.astype(np.int64), (self.n,)))
+        if np.any(t < -2**31) or np.any(t >= 2**31):
+            raise ValueError("latency ticks out of range")
+        t = np.ascontiguousarray(t, dtype=np.int32)
+        m = max(1, int(t.max())) if max_ticks is None else int(max_ticks)
+        self.api.check(self.api.set_latency(self._h, t.ctypes.data, m), "set_latency")
+
+    def latency(self):
+        """``(ticks int32[n_envs], max_ticks)`` (``trs_get_latency``); ``max_ticks == 0``: off."""
+        if not getattr(self.api, "has_latency", False):
+            raise RuntimeError("the oracle has no observation latency (trs_get_latency)")
+        t, m = np.zeros(self.n, np.int32), C.c_int(0)
+        self.api.check(self.api.get_latency(self._h, t.ctypes.data, C.byref(m)), "get_latency")
+        return t, int(m.value)
+
+    def observation(self, image=True):
+        """``(img, x, y, z, speed, cte, seg_idx, arrived)`` of all envs as fresh numpy arrays in one synchronisation (``trs_fetch_observation``):
+        ``fetch_outputs`` as the cars are told it; zeros and ``arrived == 0`` for an env whose first observation is still under way."""
+        n = self.n
+        img = np.empty((n, self.H, self.W, 3), np.uint8) if image else None
+        f = [np.empty(n, np.float32) for _ in range(5)]
+        seg, arrived = np.empty(n, np.int32), np.empty(n, np.uint8)
+        self.api.check(self.api.fetch_observation(self._h, img.ctypes.data if image else None, *[a.ctypes.data for a in f],
+                                                  seg.ctypes.data, arrived.ctypes.data), "fetch_observation")
+        return (img, *f, seg, arrived)
+
+    def observation_view(self):
+        ov = _ffi.TrsObsView()
+        self.api.check(self.api.get_observation(self._h, C.byref(ov)), "get_observation")
+        return ov
+
+    def device_observation(self, name, stream=None, sync=True):
+        """Zero-copy handle on one field of the observation (``trs_get_observation``): ``img``, ``depth``, ``pos_x``, ``pos_y``, ``pos_z``,
+        ``speed``, ``cte``, ``seg_idx`` or ``arrived``; ordered like ``device_array``.  Read-only, and valid while the NEXT step runs, not beyond.
+        With one latency for all envs ``img`` points into the ring slot of the delayed step: no frame byte has been moved."""
+        if stream is not None:
+            self.api.check(self.api.stream_signal_external(self._h, _stream_ptr(stream) or None), "stream_signal_external")
+        elif sync:
+            self.sync()
+        ptr = getattr(self.observation_view(), name)
+        if not ptr:
+            raise RuntimeError(f"{name} is not part of this env's observation")
+        return _DevicePtr(ptr, self._shape(name), self._OBS_DTYPES[name], self)
+
     def set_frame_filter(self, cfg=None, enabled=True):
         """``ImgPreprocessing`` fused behind the rasteriser (``trs_set_frame_filter``): from the next frame on, the
         env's ``img`` IS ``cam/processed_img`` at no extra cost (the palette is filtered, not the pixels).  Trim and
@@ -570,7 +631,8 @@ class BatchedEnv:
         return out
 
     def step_pilot(self, n_steps=1, cfg=None):
-        """Closed loop: controls = KerasPilot.step(previous frame, speed), then one env step; all on the device."""
+        """Closed loop: controls = KerasPilot.step(previous frame, speed), then one env step; all on the device.  With ``set_latency`` the pilot
+        sees each car's observation (frame, speed, segment) instead, and cars nothing has reached yet get (0, 0, 0)."""
         pc = cfg if isinstance(cfg, _ffi.TrsPilotConfig) else self.pilot_config(cfg)
         self.api.check(self.api.step_pilot(self._h, C.byref(pc), int(n_steps)), "step_pilot")
 
