@@ -111,7 +111,8 @@ def test_host_controls_and_reset_semantics(make_env):
 
 
 def test_set_pose_offtrack_and_lost(make_env):
-    """Cars placed off the road / farther than L1 = 100 from every point: done flag, index 0, penalty."""
+    """Cars placed off the road / farther than L1 = 100 from every point: done flag, index 0, penalty.  (Physics only, by launches; the rendered
+    counterpart — cars on rings outside the class map, every raster implementation and step path — is tests/test_step_branches_gpu.py, part B.)"""
     n = 8
     pts = track_points("generated")
     x = np.array([pts[5, 0], pts[5, 0] + 2.9, pts[5, 0] + 3.5, 1000.0, -400.0, pts[600, 0], pts[600, 0] - 3.2, pts[0, 0]], np.float32)
