@@ -2,9 +2,13 @@
 // tests/test_host_tables.py, which builds it with AddressSanitizer + UBSan.
 //   plan_driver policy                         every built variant as the handle's state x every feature bit a caller can add
 //   plan_driver fit <H> <W> <lds_step>...      every built variant x 1..64 envs per workgroup beside each lds_step
+//   plan_driver slices <n_envs>                the controls of a step call (Controls) after k = 0..16 steps: strides 0 and n_envs x brk / reset given or not, and the
+//                                              synthetic call; then the same for after(a).after(b), a, b = 0..8.  Offsets in floats from each array's base, -1 = null
+//   plan_driver fetch                          fetch_layout / fetch_reserve for every subset of the eight items, n_envs in {1, 5, 70}, with and without a 64x64 frame
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "../triton-racer-sim_amd/csrc/trsim_plan.hpp"
 
@@ -34,6 +38,39 @@ int main(int argc, char** argv)
                                 worker_lds_layout(lds_step, epw, H, W, v).total, (int)lds_fit(lds_step, epw, H, W, v, false), (int)lds_fit(lds_step, epw, H, W, v, true));
             }
         }
+        return 0;
+    }
+    if (argc >= 3 && !std::strcmp(argv[1], "slices")) {
+        const int n = std::atoi(argv[2]);
+        std::vector<float> st((size_t)17 * n), th(st.size()), br(st.size());
+        std::vector<uint8_t> rs((size_t)n);
+        auto off = [](const float* p, const std::vector<float>& base) { return p ? (long)(p - base.data()) : -1l; };
+        auto show = [&](const char* tag, const Controls& c, int a, int b, const Controls& r) {
+            std::printf("%s %d %d %d %d %d %d %ld %ld %ld %d %d %d\n", tag, c.stride, c.brk ? 1 : 0, c.reset ? 1 : 0, c.synth, a, b, off(r.steer, st), off(r.thr, th), off(r.brk, br),
+                        r.reset ? (r.reset == rs.data() ? 1 : -1) : 0, r.synth, r.stride);
+        };
+        std::vector<Controls> calls;
+        for (const int stride : {0, n})
+            for (int m = 0; m < 4; ++m) calls.push_back(Controls{st.data(), th.data(), (m & 1) ? br.data() : nullptr, (m & 2) ? rs.data() : nullptr, 0, stride});
+        for (const int stride : {0, n}) calls.push_back(Controls{nullptr, nullptr, nullptr, nullptr, 1, stride});
+        for (const Controls& c : calls) {
+            for (int k = 0; k <= 16; ++k) show("slice", c, k, 0, c.after(k));
+            for (int a = 0; a <= 8; ++a)
+                for (int b = 0; b <= 8; ++b) show("compose", c, a, b, c.after(a).after(b));
+        }
+        return 0;
+    }
+    if (argc >= 2 && !std::strcmp(argv[1], "fetch")) {
+        for (const size_t n : {(size_t)1, (size_t)5, (size_t)70})
+            for (const size_t img : {(size_t)0, (size_t)64 * 64 * 3 * n})
+                for (unsigned mask = 0; mask < (1u << kFetchItems); ++mask) {
+                    size_t bytes[kFetchItems];
+                    for (int i = 0; i < kFetchItems; ++i) bytes[i] = ((mask >> i) & 1u) ? (i == 0 ? img : (i == kFetchItems - 1 ? n : n * 4)) : 0;
+                    const FetchLayout L = fetch_layout(bytes);
+                    std::printf("fetch %zu %zu %u %zu %zu", n, img, mask, fetch_reserve(bytes[0], n), L.end);
+                    for (int i = 0; i < kFetchItems; ++i) std::printf(" %zu:%zu", L.off[i], bytes[i]);
+                    std::printf("\n");
+                }
         return 0;
     }
     return 2;

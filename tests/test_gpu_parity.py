@@ -326,3 +326,37 @@ def test_step_sequence_equals_single_steps(make_env, render):
     for name in ("pos_x", "pos_z", "speed", "cte", "yaw", "ep_return"):
         assert np.array_equal(seq.fetch(name), one.fetch(name)), name
         assert np.max(np.abs(seq.fetch(name) - ora.fetch(name))) <= 1e-5, name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["launch", "resident"])
+@pytest.mark.parametrize("render", [True, False])
+def test_step_sequence_with_reset_mask(make_env, render, mode):
+    """trs_step_sequence with a reset mask, by launches (slices of 5 + 5 + 3 steps) and posted to the resident worker: the mask belongs to the first
+    step of the call alone and every step reads its own control set == the oracle making the same call == a second HIP handle fed one trs_step at
+    a time with the mask on its first step.  A reset applied to every slice or to none, or a slice offset by one step, fails here."""
+    n, k = 70, 13
+    rng = np.random.default_rng(6)
+    st = rng.uniform(-1, 1, (k, n)).astype(np.float32)
+    th = rng.uniform(-0.2, 1, (k, n)).astype(np.float32)
+    br = (rng.uniform(0, 1, (k, n)) * (rng.uniform(0, 1, (k, n)) < 0.2)).astype(np.float32)
+    mask = (np.arange(n) % 3 == 0).astype(np.uint8)
+    kw = dict(n_envs=n, render=render, auto_reset=True, img_h=64, img_w=64)
+    seq, one, ora = make_env("hip", **kw), make_env("hip", **kw), make_env("oracle", **kw)
+    if mode == "resident":
+        seq.set_step_mode(True)
+    for env in (seq, one, ora):
+        env.step_synthetic(3, 1)
+    seq.step_sequence(st, th, br, reset=mask, steps_per_launch=5)
+    ora.step_sequence(st, th, br, reset=mask, steps_per_launch=5)
+    for t in range(k):
+        one.step(st[t], th[t], br[t], reset=mask if t == 0 else None)
+    ep = ora.fetch("ep_len")                                                # (a reset step opens the episode without counting)
+    assert int(ep[mask == 1].max()) <= k - 1 < int(ep[mask == 0].max()), "the reference itself did not reset the masked envs inside the call"
+    for name in list(INTS) + (["img"] if render else []):
+        assert np.array_equal(seq.fetch(name), one.fetch(name)), name
+        assert np.array_equal(seq.fetch(name), ora.fetch(name)), name
+    for name in FLOATS:
+        a, b, c = seq.fetch(name), one.fetch(name), ora.fetch(name)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), name
+        assert np.max(np.abs(a.astype(np.float64) - c.astype(np.float64))) <= TOL, name

@@ -199,3 +199,51 @@ def test_lds_fit_is_the_two_layouts(plan_driver):
             n += 1
     assert n == sum(len(s) for s in by_size.values()) * 14 * 64
     assert all(a == {True, False} for a in answers.values()), answers
+
+
+def test_control_slices_of_a_step_call(plan_driver):
+    """Controls::after, the one owner of 'which controls does step k of a call read' (launch loops, the worker's post loop, the remainder after a
+    fall-back): strides 0 and n_envs, brk / reset given or not, the synthetic call, k = 0..16, against a three-line model; and after(a).after(b) is
+    after(a + b), which a fall-back followed by launch slices relies on."""
+    n = 70
+
+    def model(present, stride, k):                             # offsets in floats of steer, thr, brk (-1: null) and whether the reset mask survives
+        return [k * stride if p else -1 for p in present], k == 0
+
+    rows = [[r[0]] + [int(x) for x in r[1:]] for r in run_plan(plan_driver, "slices", n)]
+    calls = set()
+    for tag, stride, has_brk, has_reset, synth, a, b, o_st, o_th, o_br, reset_kept, synth_out, stride_out in rows:
+        assert tag in ("slice", "compose") and stride in (0, n) and (b == 0 or tag == "compose")
+        calls.add((stride, has_brk, has_reset, synth))
+        offs, keeps = model([not synth, not synth, bool(has_brk)], stride, a + b)
+        where = (tag, stride, has_brk, has_reset, synth, a, b)
+        assert [o_st, o_th, o_br] == offs, where
+        assert reset_kept == (1 if has_reset and keeps else 0), where          # (-1: a reset pointer that is not the call's)
+        assert (synth_out, stride_out) == (synth, stride), where
+    assert calls == {(s, br, rs, 0) for s in (0, n) for br in (0, 1) for rs in (0, 1)} | {(0, 0, 0, 1), (n, 0, 0, 1)}
+    assert len(rows) == len(calls) * (17 + 81)
+
+
+def test_fetch_layout_every_subset(plan_driver):
+    """fetch_layout / fetch_reserve (the pinned staging of trs_fetch_outputs and trs_fetch_observation): for every subset of the eight items, n_envs in
+    {1, 5, 70}, with and without a 64 x 64 frame: the items asked for start 16-byte aligned, in table order, without overlap, inside the reserve;
+    and the reserve is the formula the staging has always been sized by."""
+    rows = run_plan(plan_driver, "fetch")
+    assert len(rows) == 3 * 2 * 256
+    seen = set()
+    for tag, n, img, mask, reserve, end, *items in rows:
+        n, img, mask, reserve, end = int(n), int(img), int(mask), int(reserve), int(end)
+        assert tag == "fetch" and n in (1, 5, 70) and img in (0, 64 * 64 * 3 * n) and len(items) == 8
+        seen.add((n, img, mask))
+        items = [tuple(int(x) for x in it.split(":")) for it in items]
+        want = [(img if i == 0 else (n if i == 7 else 4 * n)) if mask >> i & 1 else 0 for i in range(8)]
+        assert [b for _, b in items] == want
+        assert reserve == ((want[0] + 15) & ~15) + 7 * ((4 * n + 15) & ~15) + 16
+        at = 0
+        for off, size in items:
+            if not size:
+                continue
+            assert off % 16 == 0 and off >= at, (n, img, mask, items)        # aligned, ascending, behind the end of the item before
+            at = off + size
+        assert at <= end <= reserve, (n, img, mask, at, end, reserve)
+    assert len(seen) == len(rows)

@@ -77,7 +77,6 @@ struct trs_env {
     size_t img_bytes = 0;
     int lds_step = 0, lds_off_phys = 0;
     trsim::DevBuf<float> seq_buf;        // device copy of host control sequences (trs_step_sequence_host)
-    int seq_stride = 0;                  // trs_step_sequence: n_envs while a sequence call is running, else 0
     void* pilot = nullptr;               // trsim_pilot.hip context (cnn_2d_speed_control weights + activations), released by trs_pilot_free
     trs_pilot_tuning pilot_tuning{}; bool has_pilot_tuning = false;   // trs_pilot_set_tuning: kernel choices of the next trs_pilot_load
     trsim::PinnedBuf<unsigned long long> fault;   // pinned host word the kernels set when they refuse to run (dynamic LDS not at offset 0)
@@ -94,14 +93,14 @@ namespace trsim {
 bool resident_on(const trs_env* e);                       // resident mode selected for this handle
 bool resident_selected(const trs_env* e);                 // ... or selected and gone back to launches for now (the GPU is shared): it comes back by itself
 void resident_retry(trs_env* e);                          // a handle that fell back to launches (GPU shared with another process) tries resident mode again when due
-// hand n steps to the worker; controls as in trs_step (device pointers, or host-pinned pointers the device can read);
-// stride: elements between consecutive steps' control arrays (0 = held), synth: controls from the spec's generator
+// hand n steps to the worker; c: the controls of the call (Controls, trsim_plan.hpp) as device pointers or host-pinned pointers the device can read;
+// step k of the call is posted with c.after(k).  resident_post_host: c holds host arrays, held controls, staged per step in pinned memory.
 // Both return TRS_OK, an error (< 0) or kResidentFellBack (> 0, not an error): the worker's launch was found not co-resident (another process's
 // worker on the GPU), the handle is back in TRS_STEP_LAUNCH, the first *n_done steps of the call are on the stream as launches and the caller
 // launches the rest itself.
 constexpr int kResidentFellBack = 1;
-int resident_post(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, size_t stride, int* n_done);
-int resident_post_host(trs_env* e, const float* h_st, const float* h_th, const float* h_br, const uint8_t* h_rs, int n_steps, int* n_done);
+int resident_post(trs_env* e, const Controls& c, int n, int* n_done);
+int resident_post_host(trs_env* e, const Controls& h, int n_steps, int* n_done);
 hipStream_t resident_copy_stream(trs_env* e);             // a stream that is not blocked by the worker (the handle's own when none runs)
 int resident_wait(trs_env* e);                            // every posted step complete (the worker stays resident)
 int resident_quiesce(trs_env* e);                         // ... and the worker has left the GPU: the stream is free again

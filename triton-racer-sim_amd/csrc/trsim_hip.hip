@@ -43,6 +43,7 @@
 
 #define TRS_EXPORT extern "C" __attribute__((visibility("default")))
 
+using trsim::Controls;   // the controls of a step call and their slices (trsim_plan.hpp)
 namespace {
 
 
@@ -1158,22 +1159,17 @@ int sync_all(trs_env* e)
 // anything about to be queued on the handle's stream must not end up behind a resident worker
 int quiesce(trs_env* e) { return e->res ? trsim::resident_quiesce(e) : TRS_OK; }
 
-// steps go to the resident worker: resident mode is on (physics-only handles have their own worker kernel since round 4); the dynamic-brightness frame filter has its own worker
-// instantiation since round 3 (it used to fall back to launches)
-bool resident_steps(const trs_env* e) { return trsim::resident_on(e); }
-
 // one launch of the fused step kernel: physics steps [step_base, step_base + n_phys) and the frames of launch-local
 // steps r_first..r_last (-1 = step_base - 1, whose camera parameters the previous launch left in the global ring)
-int launch_step(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth,
-                int n_phys, int r_first, int r_last, uint64_t step_base)
+int launch_step(trs_env* e, const Controls& c, int n_phys, int r_first, int r_last, uint64_t step_base)
 {
     const Variant v = trsim::variant_of(e);
     const StepKernel kernel = kStepKernels[v];
     if (!kernel) return fail(TRS_ERR_STATE, "internal error: no step kernel is built for this combination of camera, track, frame filter and lighting");
     SParams sp;
     sp.ph = e->pp;
-    sp.ph.ctl_steer = st; sp.ph.ctl_thr = th; sp.ph.ctl_brk = br; sp.ph.ctl_reset = rs; sp.ph.ctl_stride = e->seq_stride;
-    sp.ph.synth = synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
+    sp.ph.ctl_steer = c.steer; sp.ph.ctl_thr = c.thr; sp.ph.ctl_brk = c.brk; sp.ph.ctl_reset = c.reset; sp.ph.ctl_stride = c.stride;
+    sp.ph.synth = c.synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
     sp.ra = e->rp;
     const bool ring = e->lat.on();                                // an observation latency is set: the one frame of this launch goes to its ring slot
     if (ring) {
@@ -1235,55 +1231,89 @@ int launch_obs(trs_env* e)
 // n env steps with a camera, K = steps per launch.  n == 1: one launch, the raster team waits for the physics team
 // through the LDS progress counters.  Otherwise a software pipeline over launches: a launch advances K physics steps
 // and renders the previous launch's last step plus its own steps 0..K-2; a raster-only launch closes the call, so on
-// return state and image both belong to step s0+n-1.
-int run_camera_steps(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, int per_launch)
+// return state and image both belong to step s0+n-1.  Every launch reads its own slice of the call's controls (Controls::after).
+int run_camera_steps(trs_env* e, const Controls& c, int n, int per_launch)
 {
     const uint64_t s0 = e->step_count;
     int rc = TRS_OK;
     if (e->lat.on()) {                                       // an observation latency is set: every step is one launch into its ring slot, and trs_obs_kernel behind it
         for (int i = 0; i < n; ++i) {
-            const size_t co = (size_t)i * (size_t)e->seq_stride;
-            if ((rc = launch_step(e, st ? st + co : st, th ? th + co : th, br ? br + co : br, i == 0 ? rs : nullptr, synth, 1, 0, 0, s0 + (uint64_t)i))) return rc;
+            if ((rc = launch_step(e, c.after(i), 1, 0, 0, s0 + (uint64_t)i))) return rc;
             e->step_count += 1;
             if ((rc = launch_obs(e))) return rc;
         }
         return TRS_OK;
     }
     if (n == 1) {
-        rc = launch_step(e, st, th, br, rs, synth, 1, 0, 0, s0);
+        rc = launch_step(e, c, 1, 0, 0, s0);
     } else {
         const int kmax = std::max(1, std::min(per_launch, steps_that_fit(e, trsim::variant_of(e), e->lds_step)));
         for (int done = 0; done < n && !rc;) {
             const int k = std::min(kmax, n - done);
-            const size_t co = (size_t)done * (size_t)e->seq_stride;       // a sequence call hands each launch its own slice of controls
-            rc = launch_step(e, st ? st + co : st, th ? th + co : th, br ? br + co : br, done == 0 ? rs : nullptr, synth, k, done == 0 ? 0 : -1, k - 2, s0 + done);
+            rc = launch_step(e, c.after(done), k, done == 0 ? 0 : -1, k - 2, s0 + done);
             done += k;
         }
-        if (!rc) rc = launch_step(e, st, th, br, nullptr, synth, 0, -1, -1, s0 + n);
+        if (!rc) rc = launch_step(e, Controls{c.steer, c.thr, c.brk, nullptr, c.synth, c.stride}, 0, -1, -1, s0 + n);   // (no physics step: it reads no controls)
     }
     if (rc) return rc;
     e->step_count += (uint64_t)n;
     return TRS_OK;
 }
 
+// one launch of the physics-only kernel: n_steps steps from step index step_off, every step k reading c.after(k) (the kernel strides by itself)
+int launch_physics(trs_env* e, const Controls& c, int n_steps, uint64_t step_off)
+{
+    PParams p = e->pp;
+    p.ctl_steer = c.steer; p.ctl_thr = c.thr; p.ctl_brk = c.brk; p.ctl_reset = c.reset; p.ctl_stride = c.stride;
+    p.synth = c.synth; p.n_steps = n_steps; p.write_cam = 0; p.step_off = (uint32_t)step_off;
+    hipLaunchKernelGGL(trs_physics_kernel, dim3((e->n + kPhysBlock / 64 - 1) / (kPhysBlock / 64)), dim3(kPhysBlock), e->lds_p, e->sP, p);
+    HIPCHK(hipGetLastError());
+    return TRS_OK;
+}
+
 // physics-only envs: K steps inside one launch of the physics kernel
-int run_physics_steps(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, int per_launch)
+int run_physics_steps(trs_env* e, const Controls& c, int n, int per_launch)
 {
     if (e->lat.on()) per_launch = 1;                         // an observation latency is set: trs_obs_kernel files every step's telemetry
     for (int done = 0; done < n;) {
         const int now = std::min(per_launch, n - done);
-        PParams p = e->pp;
-        const size_t co = (size_t)done * (size_t)e->seq_stride;
-        p.ctl_steer = st ? st + co : st; p.ctl_thr = th ? th + co : th; p.ctl_brk = br ? br + co : br; p.ctl_reset = done == 0 ? rs : nullptr;
-        p.ctl_stride = e->seq_stride;
-        p.synth = synth; p.n_steps = now; p.write_cam = 0; p.step_off = (uint32_t)e->step_count;
-        hipLaunchKernelGGL(trs_physics_kernel, dim3((e->n + kPhysBlock / 64 - 1) / (kPhysBlock / 64)), dim3(kPhysBlock), e->lds_p, e->sP, p);
-        HIPCHK(hipGetLastError());
+        int rc = launch_physics(e, c.after(done), now, e->step_count);
+        if (rc) return rc;
         e->step_count += (uint64_t)now;
         done += now;
-        if (e->lat.on()) { const int rc = launch_obs(e); if (rc) return rc; }
+        if (e->lat.on() && (rc = launch_obs(e))) return rc;
     }
     return TRS_OK;
+}
+
+// The launch half of every step call, and the whole of the pilot loop's step: n steps by launches on the handle's stream, which the caller has quiesced.
+struct PerLaunch { int camera, physics; };                   // steps per launch with a camera / physics-only (trs_step: the whole call / 1)
+int launch_steps(trs_env* e, const Controls& c, int n, PerLaunch per) { return e->cfg.render ? run_camera_steps(e, c, n, per.camera) : run_physics_steps(e, c, n, per.physics); }
+
+// The path of every step call behind its argument checks.  In resident mode (tried again when due after a fall-back) the steps are posted to the worker; where
+// it falls back in the middle of the call (kResidentFellBack: the first `done` steps are on the stream as launches) the remainder, c.after(done), goes on by launches.
+// host (trs_step_host): c holds host arrays; the worker reads them from its pinned staging, launches from the handle's control arrays after an upload.
+int step_call(trs_env* e, Controls c, int n_steps, PerLaunch per, bool host = false)
+{
+    trsim::resident_retry(e);
+    if (trsim::resident_on(e)) {
+        int done = 0;
+        const int rc = host ? trsim::resident_post_host(e, c, n_steps, &done) : trsim::resident_post(e, c, n_steps, &done);
+        if (rc != trsim::kResidentFellBack || done == n_steps) return rc < 0 ? rc : TRS_OK;
+        c = c.after(done);                                   // the handle went back to launch mode (trs_last_error() says why): the rest of the call by launches
+        n_steps -= done;
+    }
+    { int rq = quiesce(e); if (rq) return rq; }
+    if (host) {
+        const size_t n = (size_t)e->n;
+        e->h2d_bytes += n * 8 + (c.brk ? n * 4 : 0) + (c.reset ? n : 0);
+        HIPCHK(hipMemcpyAsync(e->ctl_steer, c.steer, n * 4, hipMemcpyHostToDevice, e->sP));
+        HIPCHK(hipMemcpyAsync(e->ctl_thr, c.thr, n * 4, hipMemcpyHostToDevice, e->sP));
+        if (c.brk) HIPCHK(hipMemcpyAsync(e->ctl_brk, c.brk, n * 4, hipMemcpyHostToDevice, e->sP));
+        if (c.reset) HIPCHK(hipMemcpyAsync(e->ctl_reset, c.reset, n, hipMemcpyHostToDevice, e->sP));
+        c = Controls{e->ctl_steer, e->ctl_thr, c.brk ? e->ctl_brk : nullptr, c.reset ? e->ctl_reset : nullptr, 0, 0};
+    }
+    return launch_steps(e, c, n_steps, per);
 }
 
 // The history of observations begins (trs_set_latency, trs_load_track): nothing has arrived, and every slot an observation can point into before a step
@@ -1322,6 +1352,34 @@ void obs_view(const trs_env* e, trs_obs_view* o)
     o->pos_x = t; o->pos_y = t + n; o->pos_z = t + 2 * n; o->speed = t + 3 * n; o->cte = t + 4 * n;
     o->seg_idx = reinterpret_cast<const int32_t*>(t + 5 * n);
     o->arrived = e->obs_flag[b].get();
+}
+
+// The staged fetch behind trs_fetch_outputs and trs_fetch_observation: the items asked for (dst non-null) into the pinned staging by copies on stream
+// cs, one synchronisation, then out to the caller's arrays (fetch_layout, trsim_plan.hpp).  fetch_staging comes first: it may have to idle the handle.
+struct FetchItem { const void* src; void* dst; size_t bytes; };
+int fetch_staging(trs_env* e, size_t img_bytes)
+{
+    const size_t need = trsim::fetch_reserve(img_bytes, (size_t)e->n);
+    if (e->pinned.bytes() >= need) return TRS_OK;
+    if (e->pinned.get()) { int rq = sync_all(e); if (rq) return rq; }
+    HIPCHK(e->pinned.reserve(need, hipHostMallocDefault));
+    return TRS_OK;
+}
+int staged_fetch(trs_env* e, const FetchItem (&items)[trsim::kFetchItems], hipStream_t cs)
+{
+    size_t bytes[trsim::kFetchItems];
+    for (int i = 0; i < trsim::kFetchItems; ++i) bytes[i] = items[i].dst ? items[i].bytes : 0;
+    const trsim::FetchLayout L = trsim::fetch_layout(bytes);
+    for (int i = 0; i < trsim::kFetchItems; ++i) {
+        if (!bytes[i]) continue;
+        HIPCHK(hipMemcpyAsync(e->pinned.get() + L.off[i], items[i].src, bytes[i], hipMemcpyDeviceToHost, cs));
+        e->d2h_bytes += bytes[i];
+    }
+    HIPCHK(hipStreamSynchronize(cs));
+    { int rf = trsim::check_fault(e); if (rf) return rf; }
+    for (int i = 0; i < trsim::kFetchItems; ++i)
+        if (bytes[i]) std::memcpy(items[i].dst, e->pinned.get() + L.off[i], bytes[i]);
+    return TRS_OK;
 }
 
 }  // namespace
@@ -1652,18 +1710,7 @@ TRS_EXPORT int trs_step(trs_env* e, const float* d_st, const float* d_th, const 
     if (n_steps < 1) return fail(TRS_ERR_ARG, "n_steps < 1");
     if (!d_st || !d_th) return fail(TRS_ERR_ARG, "null controls");
     HIPCHK(hipSetDevice(e->device));
-    trsim::resident_retry(e);
-    if (resident_steps(e)) {
-        int done = 0;
-        const int rc = trsim::resident_post(e, d_st, d_th, d_br, d_rs, 0, n_steps, 0, &done);
-        if (rc != trsim::kResidentFellBack || done == n_steps) return rc < 0 ? rc : TRS_OK;
-        n_steps -= done;                                     // the handle went back to launch mode (trs_last_error() says why): the rest of the call by launches
-        if (done) d_rs = nullptr;
-    }
-    { int rq = quiesce(e); if (rq) return rq; }
-    // held controls; the reset request applies to the first step only
-    return e->cfg.render ? run_camera_steps(e, d_st, d_th, d_br, d_rs, 0, n_steps, n_steps)
-                         : run_physics_steps(e, d_st, d_th, d_br, d_rs, 0, n_steps, 1);
+    return step_call(e, Controls{d_st, d_th, d_br, d_rs, 0, 0}, n_steps, PerLaunch{n_steps, 1});   // held controls; the reset request applies to the first step only
 }
 
 TRS_EXPORT int trs_step_host(trs_env* e, const float* h_st, const float* h_th, const float* h_br, const uint8_t* h_rs, int n_steps)
@@ -1672,22 +1719,7 @@ TRS_EXPORT int trs_step_host(trs_env* e, const float* h_st, const float* h_th, c
     if (n_steps < 1) return fail(TRS_ERR_ARG, "n_steps < 1");
     if (!h_st || !h_th) return fail(TRS_ERR_ARG, "null controls");
     HIPCHK(hipSetDevice(e->device));
-    trsim::resident_retry(e);
-    if (resident_steps(e)) {
-        int done = 0;
-        const int rc = trsim::resident_post_host(e, h_st, h_th, h_br, h_rs, n_steps, &done);
-        if (rc != trsim::kResidentFellBack || done == n_steps) return rc < 0 ? rc : TRS_OK;
-        n_steps -= done;
-        if (done) h_rs = nullptr;
-    }
-    { int rq = quiesce(e); if (rq) return rq; }
-    const size_t n = (size_t)e->n;
-    e->h2d_bytes += n * 8 + (h_br ? n * 4 : 0) + (h_rs ? n : 0);
-    HIPCHK(hipMemcpyAsync(e->ctl_steer, h_st, n * 4, hipMemcpyHostToDevice, e->sP));
-    HIPCHK(hipMemcpyAsync(e->ctl_thr, h_th, n * 4, hipMemcpyHostToDevice, e->sP));
-    if (h_br) HIPCHK(hipMemcpyAsync(e->ctl_brk, h_br, n * 4, hipMemcpyHostToDevice, e->sP));
-    if (h_rs) HIPCHK(hipMemcpyAsync(e->ctl_reset, h_rs, n, hipMemcpyHostToDevice, e->sP));
-    return trs_step(e, e->ctl_steer, e->ctl_thr, h_br ? e->ctl_brk : nullptr, h_rs ? e->ctl_reset : nullptr, n_steps);
+    return step_call(e, Controls{h_st, h_th, h_br, h_rs, 0, 0}, n_steps, PerLaunch{n_steps, 1}, true);
 }
 
 TRS_EXPORT int trs_step_sequence(trs_env* e, const float* d_st, const float* d_th, const float* d_br, const uint8_t* d_rs, int n_steps, int steps_per_launch)
@@ -1696,22 +1728,7 @@ TRS_EXPORT int trs_step_sequence(trs_env* e, const float* d_st, const float* d_t
     if (n_steps < 1 || steps_per_launch < 1) return fail(TRS_ERR_ARG, "n_steps / steps_per_launch < 1");
     if (!d_st || !d_th) return fail(TRS_ERR_ARG, "null controls");
     HIPCHK(hipSetDevice(e->device));
-    trsim::resident_retry(e);
-    if (resident_steps(e)) {
-        int done = 0;
-        const int rc = trsim::resident_post(e, d_st, d_th, d_br, d_rs, 0, n_steps, (size_t)e->n, &done);
-        if (rc != trsim::kResidentFellBack || done == n_steps) return rc < 0 ? rc : TRS_OK;
-        const size_t co = (size_t)done * (size_t)e->n;
-        d_st += co; d_th += co; if (d_br) d_br += co;
-        n_steps -= done;
-        if (done) d_rs = nullptr;
-    }
-    { int rq = quiesce(e); if (rq) return rq; }
-    e->seq_stride = e->n;
-    const int rc = e->cfg.render ? run_camera_steps(e, d_st, d_th, d_br, d_rs, 0, n_steps, steps_per_launch)
-                                 : run_physics_steps(e, d_st, d_th, d_br, d_rs, 0, n_steps, steps_per_launch);
-    e->seq_stride = 0;
-    return rc;
+    return step_call(e, Controls{d_st, d_th, d_br, d_rs, 0, e->n}, n_steps, PerLaunch{steps_per_launch, steps_per_launch});
 }
 
 TRS_EXPORT int trs_step_sequence_host(trs_env* e, const float* h_st, const float* h_th, const float* h_br, const uint8_t* h_rs, int n_steps, int steps_per_launch)
@@ -1731,7 +1748,7 @@ TRS_EXPORT int trs_step_sequence_host(trs_env* e, const float* h_st, const float
     HIPCHK(hipMemcpyAsync(dt, h_th, cnt * 4, hipMemcpyHostToDevice, e->sP));
     if (h_br) HIPCHK(hipMemcpyAsync(db, h_br, cnt * 4, hipMemcpyHostToDevice, e->sP));
     if (h_rs) HIPCHK(hipMemcpyAsync(e->ctl_reset, h_rs, (size_t)e->n, hipMemcpyHostToDevice, e->sP));
-    return trs_step_sequence(e, ds, dt, h_br ? db : nullptr, h_rs ? e->ctl_reset : nullptr, n_steps, steps_per_launch);
+    return step_call(e, Controls{ds, dt, h_br ? db : nullptr, h_rs ? e->ctl_reset : nullptr, 0, e->n}, n_steps, PerLaunch{steps_per_launch, steps_per_launch});
 }
 
 TRS_EXPORT int trs_step_synthetic(trs_env* e, int n_steps, int steps_per_launch)
@@ -1739,16 +1756,7 @@ TRS_EXPORT int trs_step_synthetic(trs_env* e, int n_steps, int steps_per_launch)
     if (!e || !e->track_loaded) return fail(TRS_ERR_STATE, "no track loaded");
     if (n_steps < 1 || steps_per_launch < 1) return fail(TRS_ERR_ARG, "n_steps / steps_per_launch < 1");
     HIPCHK(hipSetDevice(e->device));
-    trsim::resident_retry(e);
-    if (resident_steps(e)) {
-        int done = 0;
-        const int rc = trsim::resident_post(e, nullptr, nullptr, nullptr, nullptr, 1, n_steps, 0, &done);
-        if (rc != trsim::kResidentFellBack || done == n_steps) return rc < 0 ? rc : TRS_OK;
-        n_steps -= done;
-    }
-    { int rq = quiesce(e); if (rq) return rq; }
-    return e->cfg.render ? run_camera_steps(e, nullptr, nullptr, nullptr, nullptr, 1, n_steps, steps_per_launch)
-                         : run_physics_steps(e, nullptr, nullptr, nullptr, nullptr, 1, n_steps, steps_per_launch);
+    return step_call(e, Controls{nullptr, nullptr, nullptr, nullptr, 1, 0}, n_steps, PerLaunch{steps_per_launch, steps_per_launch});
 }
 
 TRS_EXPORT int trs_get_state(trs_env* e, trs_state_view* o)
@@ -1805,7 +1813,7 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     if (!src) return fail(TRS_ERR_STATE, "field not available");
     if (bytes != need) return fail(TRS_ERR_ARG, "byte count mismatch");
     if (host_src) { std::memcpy(dst, src, need); return TRS_OK; }
-    if (resident_steps(e) && which != TRS_F_STATS) {
+    if (trsim::resident_on(e) && which != TRS_F_STATS) {
         // the worker keeps the handle's stream: wait for its posted steps (their bytes are written through to memory before
         // the completion flag), then copy on the side stream
         int rw = trsim::resident_wait(e);
@@ -1833,36 +1841,16 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
     HIPCHK(hipSetDevice(e->device));
     const PParams& k = e->pp;
     const size_t n = (size_t)e->n, img_b = h_img ? e->img_bytes : 0;
-    const size_t need = ((img_b + 15) & ~(size_t)15) + 7 * ((n * 4 + 15) & ~(size_t)15) + 16;   // every item starts 16-B aligned
-    if (e->pinned.bytes() < need) {
-        if (e->pinned.get()) { int rq = sync_all(e); if (rq) return rq; }
-        HIPCHK(e->pinned.reserve(need, hipHostMallocDefault));
-    }
-    struct Item { const void* src; void* dst; size_t bytes; };
-    const Item items[8] = {
+    { int rs = fetch_staging(e, img_b); if (rs) return rs; }
+    const FetchItem items[trsim::kFetchItems] = {
         {h_img ? latest_frame(e) : nullptr, h_img, img_b},
         {k.x, h_x, n * 4}, {k.y, h_y, n * 4}, {k.z, h_z, n * 4}, {k.speed, h_speed, n * 4}, {k.cte, h_cte, n * 4},
         {k.seg_idx, h_seg, n * 4}, {k.done, h_done, n},
     };
     hipStream_t cs = e->sP;
-    if (resident_steps(e)) { int rw = trsim::resident_wait(e); if (rw) return rw; cs = trsim::resident_copy_stream(e); }
+    if (trsim::resident_on(e)) { int rw = trsim::resident_wait(e); if (rw) return rw; cs = trsim::resident_copy_stream(e); }
     else { int rq = quiesce(e); if (rq) return rq; }
-    size_t off = 0;
-    for (const Item& it : items) {
-        if (!it.dst || !it.bytes) continue;
-        HIPCHK(hipMemcpyAsync(e->pinned.get() + off, it.src, it.bytes, hipMemcpyDeviceToHost, cs));
-        e->d2h_bytes += it.bytes;
-        off += (it.bytes + 15) & ~(size_t)15;
-    }
-    HIPCHK(hipStreamSynchronize(cs));
-    { int rf = trsim::check_fault(e); if (rf) return rf; }
-    off = 0;
-    for (const Item& it : items) {
-        if (!it.dst || !it.bytes) continue;
-        std::memcpy(it.dst, e->pinned.get() + off, it.bytes);
-        off += (it.bytes + 15) & ~(size_t)15;
-    }
-    return TRS_OK;
+    return staged_fetch(e, items, cs);
 }
 
 // ---- observation latency (include/trsim_spec.h, "observation latency") ---------------------------------------------------------------
@@ -1946,35 +1934,15 @@ TRS_EXPORT int trs_fetch_observation(trs_env* e, uint8_t* h_img, float* h_x, flo
     if (h_img && !e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
     HIPCHK(hipSetDevice(e->device));
     const size_t n = (size_t)e->n, img_b = h_img ? e->img_bytes : 0;
-    const size_t need = ((img_b + 15) & ~(size_t)15) + 7 * ((n * 4 + 15) & ~(size_t)15) + 16;   // every item starts 16-B aligned
-    if (e->pinned.bytes() < need) {
-        if (e->pinned.get()) { int rq = sync_all(e); if (rq) return rq; }
-        HIPCHK(e->pinned.reserve(need, hipHostMallocDefault));
-    }
+    { int rs = fetch_staging(e, img_b); if (rs) return rs; }
     trs_obs_view v;
     obs_view(e, &v);
-    struct Item { const void* src; void* dst; size_t bytes; };
-    const Item items[8] = {
+    const FetchItem items[trsim::kFetchItems] = {
         {h_img ? v.img : nullptr, h_img, img_b},
         {v.pos_x, h_x, n * 4}, {v.pos_y, h_y, n * 4}, {v.pos_z, h_z, n * 4}, {v.speed, h_speed, n * 4}, {v.cte, h_cte, n * 4},
         {v.seg_idx, h_seg, n * 4}, {v.arrived, h_arrived, n},
     };
-    size_t off = 0;
-    for (const Item& it : items) {
-        if (!it.dst || !it.bytes) continue;
-        HIPCHK(hipMemcpyAsync(e->pinned.get() + off, it.src, it.bytes, hipMemcpyDeviceToHost, e->sP));
-        e->d2h_bytes += it.bytes;
-        off += (it.bytes + 15) & ~(size_t)15;
-    }
-    HIPCHK(hipStreamSynchronize(e->sP));
-    { int rf = trsim::check_fault(e); if (rf) return rf; }
-    off = 0;
-    for (const Item& it : items) {
-        if (!it.dst || !it.bytes) continue;
-        std::memcpy(it.dst, e->pinned.get() + off, it.bytes);
-        off += (it.bytes + 15) & ~(size_t)15;
-    }
-    return TRS_OK;
+    return staged_fetch(e, items, e->sP);
 }
 
 TRS_EXPORT int trs_set_pose(trs_env* e, const float* x, const float* y, const float* z, const float* yaw, const float* v)
@@ -2645,7 +2613,7 @@ TRS_EXPORT int trs_sync(trs_env* e)
 {
     if (!e) return fail(TRS_ERR_ARG, "null handle");
     HIPCHK(hipSetDevice(e->device));
-    if (resident_steps(e)) { int rw = trsim::resident_wait(e); return rw ? rw : trsim::check_fault(e); }   // posted steps complete; the worker stays
+    if (trsim::resident_on(e)) { int rw = trsim::resident_wait(e); return rw ? rw : trsim::check_fault(e); }   // posted steps complete; the worker stays
     return sync_all(e);
 }
 
@@ -2756,19 +2724,13 @@ int trs_internal_step_launch(trs_env* e, const float* d_st, const float* d_th, c
     { int rq = quiesce(e); if (rq) return rq; }
     // (like every step path: the uniform rows of a frame buffer — sky, beyond the far plane — are written by the first step that renders into it and kept after that:
     // 41 % of a frame's bytes at the default camera, 4.8 of the 16.5 us of this step at 1024 x 120x160, ~20 of 48 us at 512 x 240x320 + depth)
-    const int rc = e->cfg.render ? run_camera_steps(e, d_st, d_th, d_br, nullptr, 0, 1, 1) : run_physics_steps(e, d_st, d_th, d_br, nullptr, 0, 1, 1);
+    const int rc = launch_steps(e, Controls{d_st, d_th, d_br, nullptr, 0, 0}, 1, PerLaunch{1, 1});
     if (!rc) trsim::resident_note_launch(e);               // resident mode selected: this step has no completion flag, trs_sync / the copies wait for the stream
     return rc;
 }
-int trs_internal_replay_launch(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, uint64_t step)
+int trs_internal_replay_launch(trs_env* e, const trsim::Controls& c, uint64_t step)
 {
-    if (e->cfg.render) return launch_step(e, st, th, br, rs, synth, 1, 0, 0, step);
-    PParams p = e->pp;
-    p.ctl_steer = st; p.ctl_thr = th; p.ctl_brk = br; p.ctl_reset = rs; p.ctl_stride = 0;
-    p.synth = synth; p.n_steps = 1; p.write_cam = 0; p.step_off = (uint32_t)step;
-    hipLaunchKernelGGL(trs_physics_kernel, dim3((e->n + kPhysBlock / 64 - 1) / (kPhysBlock / 64)), dim3(kPhysBlock), e->lds_p, e->sP, p);
-    HIPCHK(hipGetLastError());
-    return TRS_OK;
+    return e->cfg.render ? launch_step(e, c, 1, 0, 0, step) : launch_physics(e, c, 1, step);
 }
 void trs_internal_note(const std::string& msg) { g_err = msg; }
 int trsim::sync_handle(trs_env* e) { return sync_all(e); }

@@ -1,9 +1,11 @@
-// trsim_plan.hpp — what a handle is allowed to become, as integer arithmetic and string selection a host compiler builds without HIP:
+// trsim_plan.hpp — what a handle is allowed to become and how a call is cut up, as integer arithmetic and string selection a host compiler builds without HIP:
 // the kernel variants and which of them exist, the LDS the kernels keep behind a track's tables (the layouts the hosts size their launches by
-// and the kernels take their offsets from), the layout of a track's two LDS images, and the refusals that follow from all three.
+// and the kernels take their offsets from), the layout of a track's two LDS images, the refusals that follow from all three, the frame buffers that hold their
+// uniform rows (UniformRows), the observation ring (ObsRing), the controls of a step call and their slices (Controls) and a fetch's staging (fetch_layout).
 // Functions that the kernels call as well carry TRS_HD (trsim_tables.hpp).  tests/plan_driver.cpp and tests/host_tables_driver.cpp run it on the CPU.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -225,6 +227,36 @@ struct ObsRing {
     // the gathered observation (telemetry always; frames when the envs' delays differ) is double buffered like the frames of a handle without latency
     static int gather_buf(long long T) { return (int)(T & 1ll); }
 };
+
+// ---- the controls of a step call, and the slice of them a launch or a post reads ----------------------------------------------------------
+// Control arrays (device pointers, or host arrays on their way to the device; brk and reset optional), or synth: the spec's generator and no arrays.
+// stride: floats between the control sets of consecutive steps, 0 = held controls, n_envs = a sequence.  The reset mask belongs to the first step alone.
+// The one owner of "which controls does step k of the call read": the launch loops (run_camera_steps, run_physics_steps), the worker's post loop
+// (resident_post) and the remainder of a call whose worker fell back to launches all ask after().  after(a).after(b) == after(a + b).
+struct Controls {
+    const float *steer = nullptr, *thr = nullptr, *brk = nullptr;
+    const uint8_t* reset = nullptr;
+    int synth = 0, stride = 0;
+    Controls after(int k) const                              // the controls of the call's remainder after k steps
+    {
+        const size_t off = (size_t)k * (size_t)stride;
+        return {steer ? steer + off : nullptr, thr ? thr + off : nullptr, brk ? brk + off : nullptr, k == 0 ? reset : nullptr, synth, stride};
+    }
+};
+
+// ---- the pinned staging of a fetch (trs_fetch_outputs, trs_fetch_observation) ----------------------------------------------------------------
+// Up to eight optional items (the frame, six words per env, a byte per env) go through one pinned block behind one synchronisation; bytes[i] == 0: item i is
+// not asked for.  Every present item starts 16-byte aligned, in table order.  The block is reserved for the frame asked for and all seven per-env items.
+constexpr int kFetchItems = 8;
+constexpr size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+constexpr size_t fetch_reserve(size_t img_bytes, size_t n_envs) { return align16(img_bytes) + 7 * align16(n_envs * 4) + 16; }
+struct FetchLayout { size_t off[kFetchItems], end; };
+inline FetchLayout fetch_layout(const size_t (&bytes)[kFetchItems])
+{
+    FetchLayout L{};
+    for (int i = 0; i < kFetchItems; ++i) { L.off[i] = L.end; L.end += align16(bytes[i]); }
+    return L;
+}
 
 // ---- the two LDS images of a track ------------------------------------------------------------------------------------------
 // physics image:  px | py | pz | tangent (tan_in_lds) | grid starts | grid points, and behind it the physics-only kernel's scratch (lds_p bytes of LDS)

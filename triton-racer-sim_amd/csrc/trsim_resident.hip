@@ -1195,7 +1195,7 @@ int fall_back_to_launches(trs_env* e, uint64_t consumed, const char* why)
         const WEntry& en = R->mb->ring[s & (kSlots - 1)];
         if (en.seq != s + 1 || en.seq_lo != s + 1)
             return trs_internal_fail(TRS_ERR_DEVICE, "resident worker: the post of step " + std::to_string(s) + " is no longer in the ring");
-        int rc = trs_internal_replay_launch(e, en.steer, en.thr, en.brk, en.reset, (int)en.synth, s);
+        int rc = trs_internal_replay_launch(e, Controls{en.steer, en.thr, en.brk, en.reset, (int)en.synth, 0}, s);
         if (rc) return rc;
     }
     R->launched = true;                                      // these steps have no completion flag: the stream is what to wait for
@@ -1339,7 +1339,7 @@ void resident_retry(trs_env* e)
 bool resident_running(const trs_env* e) { return e && e->res && e->res->running; }
 void resident_clear_fault(trs_env* e) { if (e && e->res) e->res->broken = false; }
 
-int resident_post(trs_env* e, const float* st, const float* th, const float* br, const uint8_t* rs, int synth, int n, size_t stride, int* n_done)
+int resident_post(trs_env* e, const Controls& c, int n, int* n_done)
 {
     DevLock lock(e);
     Resident* R = e->res;
@@ -1360,15 +1360,12 @@ int resident_post(trs_env* e, const float* st, const float* th, const float* br,
             if (rc) return rc;
             if (!R->enabled) { *n_done = k; return kFellBack; }       // the handle went back to launch mode: the caller launches steps k.. itself
         }
-        WEntry en{};
-        const size_t off = (size_t)k * stride;
-        en.steer = st ? st + off : nullptr; en.thr = th ? th + off : nullptr; en.brk = br ? br + off : nullptr;
-        en.reset = k == 0 ? rs : nullptr; en.synth = synth ? 1u : 0u;
+        const Controls ck = c.after(k);                           // what step k of the call reads
         if (!R->running) { int rc = worker_fits(e); if (rc) return rc; }   // nothing is published for a worker that could not be launched
         WEntry* slot = &mb->ring[s & (kSlots - 1)];
-        slot->steer = en.steer; slot->thr = en.thr; slot->brk = en.brk;
+        slot->steer = ck.steer; slot->thr = ck.thr; slot->brk = ck.brk;
         host_store(&slot->seq_lo, s + 1);                         // first half: payload, then its tag (x86 keeps the store order)
-        slot->reset = en.reset; slot->synth = en.synth;
+        slot->reset = ck.reset; slot->synth = ck.synth ? 1u : 0u;
         host_store(&slot->seq, s + 1);                            // second half likewise; this tag last: the line is now a valid post
         host_store(&mb->posted, s + 1);
         std::atomic_thread_fence(std::memory_order_seq_cst);     // the post is visible before `exited` is read
@@ -1445,7 +1442,7 @@ void resident_destroy(trs_env* e)
 hipStream_t resident_copy_stream(trs_env* e) { return (e->res && e->res->running) ? e->res->sC : e->sP; }
 
 // controls handed over as host arrays: into this step's slot of the pinned staging buffer, which the device reads over PCIe
-int resident_post_host(trs_env* e, const float* h_st, const float* h_th, const float* h_br, const uint8_t* h_rs, int n_steps, int* n_done)
+int resident_post_host(trs_env* e, const Controls& h, int n_steps, int* n_done)
 {
     DevLock lock(e);
     Resident* R = e->res;
@@ -1460,10 +1457,10 @@ int resident_post_host(trs_env* e, const float* h_st, const float* h_th, const f
     unsigned char* slot = R->hctl.get() + (s & (kSlots - 1)) * R->hctl_slot;
     const size_t n = (size_t)e->n;
     float* f = reinterpret_cast<float*>(slot);
-    std::memcpy(f, h_st, n * 4); std::memcpy(f + n, h_th, n * 4);
-    if (h_br) std::memcpy(f + 2 * n, h_br, n * 4);
+    std::memcpy(f, h.steer, n * 4); std::memcpy(f + n, h.thr, n * 4);
+    if (h.brk) std::memcpy(f + 2 * n, h.brk, n * 4);
     uint8_t* rsb = slot + n * 12;
-    if (h_rs) std::memcpy(rsb, h_rs, n);
+    if (h.reset) std::memcpy(rsb, h.reset, n);
     // held controls: every step of the call reads the same slot, so the slot must outlive them — post them one by one and
     // keep the slot until the last is done (n_steps > kSlots would wrap onto it: copy again per step instead)
     for (int k = 0; k < n_steps; ++k) {
@@ -1479,7 +1476,7 @@ int resident_post_host(trs_env* e, const float* h_st, const float* h_th, const f
             slot = sl; f = reinterpret_cast<float*>(slot); rsb = slot + n * 12;
         }
         int one = 0;
-        int rc = resident_post(e, f, f + n, h_br ? f + 2 * n : nullptr, (k == 0 && h_rs) ? rsb : nullptr, 0, 1, 0, &one);
+        int rc = resident_post(e, Controls{f, f + n, h.brk ? f + 2 * n : nullptr, (k == 0 && h.reset) ? rsb : nullptr, 0, 0}, 1, &one);
         if (rc == kFellBack) { *n_done = k + one; return kFellBack; }
         if (rc) return rc;
     }
