@@ -147,7 +147,9 @@ def test_component_handoff_semantics(oracle_api):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("size", [(120, 160), (240, 320), (64, 64)])
+# 120x200: the trim kernel's two passes over memory on 256 threads (20+ groups per thread), the Canny kernel's LDS arrays in two chunks;
+# 136x200: the smallest frame whose Canny work arrays go to the global scratch; 244x320: the two passes over memory on 1024 threads
+@pytest.mark.parametrize("size", [(120, 160), (240, 320), (64, 64), (120, 200), (136, 200), (244, 320)])
 def test_gpu_preprocess_and_normalize_equal_oracle(make_env, size):
     h, w = size
     g = make_env("hip", n_envs=1, track=None, render=False, img_h=h, img_w=w)

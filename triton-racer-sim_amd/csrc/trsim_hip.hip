@@ -694,9 +694,10 @@ __global__ __launch_bounds__(kEdgeBlock) void trs_preprocess_edge_kernel(const P
         }
         // ---- the frame: kEdgeGpt groups per thread in registers, every load issued before the first is used (a thread that loaded and used
         // its groups one after the other paid one memory round trip per group: the two passes over the frame were 29 % of the kernel).
-        // A frame of up to 1024 x kEdgeGpt groups (every frame whose work arrays fit LDS) is read from memory ONCE — both passes work
-        // on the registers — and the next frame's loads are issued as soon as the registers are free, in front of the Sobel phase.
-        // Larger frames take the passes in chunks of 1024 x kEdgeGpt groups (the second pass reads L2). ----
+        // A frame of up to 1024 x kEdgeGpt groups (20,480 pixels: 120x160, not every frame whose work arrays fit LDS - 120x200 fits with
+        // 6,000 groups) is read from memory ONCE — both passes work on the registers — and the next frame's loads are issued as soon as the
+        // registers are free, in front of the Sobel phase.  Larger frames, in LDS or in the scratch, take the passes in chunks of
+        // 1024 x kEdgeGpt groups (the second pass reads L2) and have no prefetch, no early sums and no early table. ----
         if (!one_chunk) fetch(rs, 0, R);                                    // (one-chunk frames: the first was requested at the kernel's start, the others during the previous frame)
         // ---- channel sums over the brightness rows -> delta (as trs_preprocess_kernel) ----
         // (one-chunk frames after the first: the sums were taken from the prefetched registers in the middle of the previous frame, see below -
