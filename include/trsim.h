@@ -255,6 +255,29 @@ int trs_get_observation(trs_env* env, trs_obs_view* out);   /* device pointers; 
 int trs_fetch_observation(trs_env* env, uint8_t* h_img, float* h_x, float* h_y, float* h_z, float* h_speed, float* h_cte,
                           int32_t* h_seg_idx, uint8_t* h_arrived);
 
+/* ---- tub images: frames on the device -> the img_k.jpg files of the reference's tubs (include/trsim_spec.h, "tub image (JPEG)") ----
+ * The reference writes a record's image with Image.fromarray(img).save(path) (components/datastorage.py:78): baseline JPEG, quality 75, 4:2:0.
+ * trs_encode_jpeg writes the same bytes, for quality in 1..100, from frames that never leave the device.
+ *   d_src: uint8[n_images][H][W][3] of the handle's size, 4-byte aligned; NULL = the latest frames, as trs_normalize resolves them (n_images ==
+ *     n_envs; behind every step mode, frame filter, lens, lighting and latency: the call reads whole frames after the step).
+ *   d_dst: n_images slots of `cap` bytes; frame i's file starts at d_dst + i * cap.  d_len[i]: the file's length when it fits in the slot, the
+ *     NEGATED length when it does not (the slot's content is then undefined).  No byte at or beyond d_dst + (i + 1) * cap and no byte of another
+ *     slot is ever written; bytes of a slot beyond the file's end are left untouched.  Asynchronous, on the handle's stream.
+ *   trs_jpeg_header_bytes: the length of SOI..SOS for the handle's H x W (the same for every quality).  A cap of header + 2 + H * W * 3 / 4 holds
+ *     every rendered frame seen so far at quality 75 many times over; noise at quality 100 can take more than H * W * 3.
+ *   trs_encode_jpeg_host: the same into handle-owned slots, then the fitting files packed back to back: h_blob[h_off[i] .. h_off[i + 1]) is
+ *     frame i's file, h_off has n_images + 1 entries, h_len (optional) is d_len.  A frame that did not fit has h_off[i + 1] == h_off[i] and
+ *     h_len[i] < 0.  One synchronisation, two device-to-host copies (offsets and lengths; min(blob_cap, n_images * cap) bytes of files).
+ *     TRS_ERR_LIMIT when the files need more than blob_cap: h_off and h_len are valid, nothing is written past h_blob + blob_cap.
+ *   TRS_ERR_ARG: quality outside 1..100, cap < header + 2, n_images < 1 (or != n_envs with d_src NULL), a NULL destination.  TRS_ERR_STATE: d_src
+ *     NULL on a handle without a camera.  TRS_ERR_LIMIT: img_w > 672 (the kernel gives every 8 x 8 block of a 16-row stripe a lane of its 256).
+ *   The kernel runs min(n_images, 4 x CU count) workgroups, each looping over frames.  Resident mode: the worker leaves the GPU first, as for
+ *   trs_normalize, and trs_sync then waits for the encoder like for a launched step. */
+int trs_jpeg_header_bytes(trs_env* env, int quality);   /* > 0: bytes of SOI..SOS; < 0: trs_status */
+int trs_encode_jpeg(trs_env* env, const uint8_t* d_src_or_null, int n_images, int quality, uint8_t* d_dst, int cap, int32_t* d_len);
+int trs_encode_jpeg_host(trs_env* env, const uint8_t* d_src_or_null, int n_images, int quality, int cap,
+                         uint8_t* h_blob, size_t blob_cap, int64_t* h_off, int32_t* h_len_or_null);
+
 /* Overwrite env pose (x, y, z, yaw, v) from host arrays of n_envs floats — test hook. */
 int trs_set_pose(trs_env* env, const float* h_x, const float* h_y, const float* h_z,
                  const float* h_yaw, const float* h_v);

@@ -167,6 +167,42 @@
  *   others (keras_pilot.py:46-47: no frame yet); the speed (every model type that reads it) and 'loc/segment' (full house) are the observation's.
  *   The observation handed out after step T stays intact while step T + 1 runs.  tests/test_latency_cpu.py checks the ring arithmetic against a deque;
  *   tests/test_latency_gpu.py checks observations against the oracle's records kept in a list.
+ *
+ * ---- tub image (JPEG) (trs_encode_jpeg; the img_k.jpg of a tub record, components/datastorage.py:78; HIP library only) ---------------------------
+ *   One uint8[H][W][3] RGB frame -> one baseline JPEG file: quality q in 1..100 (default 75), 4:2:0, one interleaved scan, the standard's tables.
+ *   Integer arithmetic only; >> is an arithmetic shift, / truncates.  The file is a function of the frame's bytes, H, W and q alone.
+ *   Quantisation tables: the luminance and chrominance bases of the JPEG standard's Annex K;  scale = q < 50 ? 5000 / q : 200 - 2 q;
+ *     entry = clamp((base * scale + 50) / 100, 1, 255).
+ *   Colour, per pixel, FIX(x) = (int)(x * 65536 + 0.5):
+ *     Y  = ( FIX(.299) R   + FIX(.587) G   + FIX(.114) B   + 32768) >> 16
+ *     Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B     + (128 << 16) + 32767) >> 16
+ *     Cr = ( FIX(.5) R     - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16
+ *   MCU = 16 x 16 pixels = blocks Y00 Y01 Y10 Y11 Cb Cr of 8 x 8 samples; ceil(H / 16) x ceil(W / 16) MCUs in raster order.
+ *   Edges.  The Y plane is padded to multiples of 8 by replicating its last column and row.  A full-resolution chroma plane is padded to an even
+ *     height and to the width 16 ceil(W / 16) by replicating its last row and column, then downsampled; the DOWNSAMPLED plane is padded to a
+ *     multiple of 8 rows by replicating ITS last row.  A Y block of an MCU that lies wholly beyond the ceil(H / 8) block rows or the ceil(W / 8)
+ *     block columns is a dummy block: all AC coefficients 0, and its quantised DC is the quantised DC of the block before it in the MCU.
+ *   Downsampling 2 x 2: (a + b + c + d + bias) >> 2, bias = 1 in even output columns and 2 in odd ones.
+ *   DCT of a block of samples - 128: the integer forward transform with 13 constant bits and 2 extra bits after the first pass,
+ *     DESCALE(x, n) = (x + (1 << (n - 1))) >> n.  One pass over d0..d7:
+ *       t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4
+ *       t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *       rows (first):    o0 = (t10 + t11) << 2,  o4 = (t10 - t11) << 2,  n = 11;      columns (second): o0 = DESCALE(t10 + t11, 2),  o4 = DESCALE(t10 - t11, 2),  n = 15
+ *       e = (t12 + t13) * 4433;  o2 = DESCALE(e + t13 * 6270, n);  o6 = DESCALE(e - t12 * 15137, n)
+ *       z5 = (t4 + t5 + t6 + t7) * 9633;  z1 = -(t4 + t7) * 7373;  z2 = -(t5 + t6) * 20995;  z3 = -(t4 + t6) * 16069 + z5;  z4 = -(t5 + t7) * 3196 + z5
+ *       o7 = DESCALE(t4 * 2446 + z1 + z3, n);  o5 = DESCALE(t5 * 16819 + z2 + z4, n);  o3 = DESCALE(t6 * 25172 + z2 + z3, n);  o1 = DESCALE(t7 * 12299 + z1 + z4, n)
+ *     over the 8 rows, then over the 8 columns: the coefficients come out scaled by 8.
+ *   Quantiser, coefficient c, table entry Q:  qv = Q << 3;  a = |c| + (qv >> 1);  v = a >= qv ? a / qv : 0, with the sign of c.
+ *   Entropy coding: the four Huffman tables of Annex K (codes of one length count up in symbol order and double when the length grows).  Per block in
+ *     zig-zag order: the DC difference to the previous block of the same component (0 before the first; over the whole scan, no restart intervals) as
+ *     its size s = bits of |d| and s extra bits (d, or d - 1 when negative); per non-zero AC coefficient 0xF0 (ZRL) while the run of zeros before it
+ *     exceeds 15, then (run << 4 | s) and the s extra bits; 0x00 (EOB) when the block ends in zeros.  Bits fill bytes from the most significant one; a
+ *     byte 0x00 follows every byte 0xFF; the last partial byte is filled with 1-bits; then FF D9.
+ *   Header, in this order: SOI | APP0 "JFIF" 1.01, units 0, density 1 x 1, no thumbnail | DQT table 0, DQT table 1 (two segments, 8-bit, zig-zag) |
+ *     SOF0 precision 8, H, W, components (1, 0x22, table 0) (2, 0x11, table 1) (3, 0x11, table 1) | DHT DC0, AC0, DC1, AC1 (four segments) |
+ *     SOS components (1, 0x00) (2, 0x11) (3, 0x11), then 0, 63, 0.  623 bytes.
+ *   This is what Pillow (libjpeg) writes for Image.fromarray(frame).save(path, quality=q): tests/test_jpeg_cpu.py restates the paragraph in numpy and
+ *   compares files byte for byte; csrc/trsim_jpeg_tables.hpp is the one place the library's host and kernel take the rules from.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

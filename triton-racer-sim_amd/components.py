@@ -252,6 +252,28 @@ class HipImgPreprocessing(Component):
         return "Image Preprocessing"
 
 
+class HipJpegEncoder(Component):
+    """``cam/img -> cam/img_jpg``: the tick's frames as the ``img_k.jpg`` files of the reference's tubs (``components/datastorage.py:78``:
+    Pillow's defaults — baseline JPEG, quality 75, 4:2:0), encoded on the GPU by ``env`` (``BatchedEnv.encode_jpeg``; include/trsim_spec.h,
+    "tub image (JPEG)") and brought to the host in one copy.  The output is a sequence of ``bytes``, one per car: feed it to
+    ``BatchedDataStorage(..., image_port='cam/img_jpg')``.  ``cam/img`` may be the env's device handle (no raw frame leaves the GPU) or a host
+    array ``uint8[N,H,W,3]``."""
+
+    def __init__(self, env, quality=75):
+        Component.__init__(self, inputs=["cam/img"], outputs=["cam/img_jpg"], threaded=False)
+        self.env = env
+        self.quality = int(quality)
+
+    def step(self, *args):
+        img = args[0]
+        if img is None:
+            return None,
+        return self.env.encode_jpeg(img, quality=self.quality),
+
+    def getName(self):
+        return "JPEG Encoder"
+
+
 MUX_INPUTS = ["usr/mode", "usr/steering", "usr/throttle", "usr/breaking", "ai/steering", "ai/throttle", "ai/breaking"]   # controlmultiplexer.py:9
 MUX_OUTPUTS = ["mux/steering", "mux/throttle", "mux/breaking"]
 

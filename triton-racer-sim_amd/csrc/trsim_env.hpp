@@ -82,6 +82,10 @@ struct trs_env {
     trsim::PinnedBuf<unsigned long long> fault;   // pinned host word the kernels set when they refuse to run (dynamic LDS not at offset 0)
     trsim::DevBuf<float> glue;           // device scratch of the *_host control glue (trs_driver_assist_host, trs_control_mux_host)
     trsim::DevBuf<void> scratch[32];     // trs_scratch
+    // the tub image encoder (trs_encode_jpeg; include/trsim_spec.h, "tub image (JPEG)")
+    trsim::DevBuf<> jpg_tab; int jpg_quality = 0;   // device copy of jpeg::Tables (trsim_jpeg_tables.hpp) for jpg_quality; 0: none yet
+    trsim::DevBuf<uint8_t> jpg_slots, jpg_blob; trsim::DevBuf<int32_t> jpg_len; trsim::DevBuf<long long> jpg_off;   // trs_encode_jpeg_host: slots, lengths, packed files, offsets
+    trsim::PinnedBuf<> jpg_pin;          // ... and the staging of its offsets and lengths
     uint64_t d2h_bytes = 0, h2d_bytes = 0;                  // trs_counters: what the library itself copied
     trsim::Comm* comm = nullptr;         // trsim_comm.hip: the RCCL communicator of trs_comm_init, nullptr = none
     hipEvent_t ev_order = nullptr;       // trs_stream_wait_external / trs_stream_signal_external

@@ -2716,6 +2716,7 @@ void trs_internal_set_pilot_tuning(trs_env* e, const trs_pilot_tuning* t)
     if (t) e->pilot_tuning = *t;
 }
 int trs_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+const uint8_t* trs_internal_latest_frame(const trs_env* e) { return e ? latest_frame(e) : nullptr; }
 void trs_internal_count(trs_env* e, uint64_t d2h, uint64_t h2d) { if (e) { e->d2h_bytes += d2h; e->h2d_bytes += h2d; } }
 // one env step by LAUNCH whatever the handle's step mode: the pilot loop's kernels need the CUs' LDS, which a resident worker
 // would hold, and its controls are produced on the handle's stream right in front of the step

@@ -30,6 +30,7 @@ void** trs_internal_pilot_slot(trs_env* e);
 const trs_pilot_tuning* trs_internal_pilot_tuning(trs_env* e);   // what trs_pilot_set_tuning stored, or nullptr (defaults)
 void trs_internal_set_pilot_tuning(trs_env* e, const trs_pilot_tuning* t);
 int trs_internal_fail(int code, const std::string& msg);
+const uint8_t* trs_internal_latest_frame(const trs_env* e);   // what a NULL frame source means to trs_normalize, trs_preprocess and trs_encode_jpeg (nullptr: no camera)
 int trs_internal_step_launch(trs_env* e, const float* d_st, const float* d_th, const float* d_br);   // one env step by launch, whatever the step mode
 // one env step with index `step` by launch, on the handle's stream, WITHOUT moving the step counter: a step that was posted to a resident worker
 // (the counter moved at the post) and has to run as a launch after all (trsim_resident.hip, fall_back_to_launches)

@@ -79,6 +79,7 @@ SLOT_MODE = 3                  # 'usr/mode' as uint8 codes                      
 SLOT_USR = (4, 5, 6)           # 'usr/steering', 'usr/throttle', 'usr/breaking'   (uploaded joystick values)
 SLOT_MUX = (7, 8, 9)           # 'mux/steering', 'mux/throttle', 'mux/breaking'   (BatchedControlMultiplexer)
 SLOT_PILOT_IN = (10, 11)       # 'gym/speed', 'loc/segment' that reached HipKerasPilot as HOST values beside a device frame
+SLOT_JPEG_IN = 12              # host frames handed to BatchedEnv.encode_jpeg                        (uploaded before the encoder reads them)
 
 
 def _stream_ptr(stream):
@@ -116,6 +117,31 @@ def lighting_params(n, seed=0, gain=(0.6, 1.4), bias=(-30.0, 30.0), per_channel=
     g = np.broadcast_to(rng.uniform(gain[0], gain[1], (n, k)), (n, 3))
     b = np.broadcast_to(rng.uniform(bias[0], bias[1], (n, k)), (n, 3))
     return lighting_array(g.astype(np.float32), b.astype(np.float32))
+
+
+class JpegFrames:
+    """The JPEG files of one ``BatchedEnv.encode_jpeg`` call: ``len()``, ``[i] -> bytes``, iteration; ``.blob`` (uint8, the files that fitted back to
+    back), ``.offsets`` (int64[n + 1] into ``.blob``) and ``.lengths`` (int32[n]; negative: the file did not fit and was encoded on the host)."""
+
+    def __init__(self, blob, offsets, lengths, late=None):
+        self.blob, self.offsets, self.lengths = blob, offsets, lengths
+        self._late = late or {}
+
+    def __len__(self):
+        return int(self.lengths.shape[0])
+
+    def __getitem__(self, i):
+        n = len(self)
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(n))]
+        i = int(i)
+        if i < 0:
+            i += n
+        if not 0 <= i < n:
+            raise IndexError(i)
+        if i in self._late:
+            return self._late[i]
+        return self.blob[int(self.offsets[i]):int(self.offsets[i + 1])].tobytes()
 
 
 class BatchedEnv:
@@ -482,6 +508,80 @@ class BatchedEnv:
         dst = np.empty(src.shape, dtype=np.float32)
         self.api.check(self.api.normalize_host(self._h, src.ctypes.data, dst.ctypes.data, int(src.shape[0])), "normalize_host")
         return dst
+
+    # -- tub images (include/trsim_spec.h, "tub image (JPEG)") ------------------------------------
+    def jpeg_header_bytes(self, quality=75):
+        if not getattr(self.api, "has_jpeg", False):
+            raise RuntimeError("this library has no JPEG encoder (trs_encode_jpeg)")
+        n = self.api.jpeg_header_bytes(self._h, int(quality))
+        if n < 0:
+            self.api.check(n, "jpeg_header_bytes")
+        return int(n)
+
+    def jpeg_default_cap(self, quality=75):
+        """Bytes per frame ``encode_jpeg`` reserves unless told otherwise: the header, the end marker and a quarter of the raw frame."""
+        return self.jpeg_header_bytes(quality) + 2 + self.H * self.W * 3 // 4
+
+    def device_encode_jpeg(self, d_dst, d_len, frames=None, n_images=None, quality=75, cap=None):
+        """``trs_encode_jpeg``, device to device and asynchronous on the env's stream: ``d_dst`` takes ``n_images`` slots of ``cap`` bytes, ``d_len``
+        int32 lengths (negated where a file did not fit).  ``frames``: ``None`` = the latest frames, else a device ``uint8[n,H,W,3]``; pointers are
+        integers or anything with ``__cuda_array_interface__`` (torch tensors)."""
+        src = device_ptr(frames)
+        n = self.n if n_images is None else int(n_images)
+        cap = self.jpeg_default_cap(quality) if cap is None else int(cap)
+        if not getattr(self.api, "has_jpeg", False):
+            raise RuntimeError("this library has no JPEG encoder (trs_encode_jpeg)")
+        self.api.check(self.api.encode_jpeg(self._h, src, n, int(quality), device_ptr(d_dst), cap, device_ptr(d_len)), "encode_jpeg")
+        return cap
+
+    def encode_jpeg(self, frames=None, quality=75, cap=None):
+        """The ``img_k.jpg`` bytes of N frames in one call (``trs_encode_jpeg_host``) as a ``JpegFrames`` sequence — byte for byte what
+        ``Image.fromarray(frame).save(path, quality=quality)`` writes.  ``frames``: ``None`` = the env's latest frames, a device array, or a host
+        ``uint8[n,H,W,3]`` (uploaded first).  A frame whose file exceeds ``cap`` bytes (default: header + 2 + H*W*3/4) is encoded with Pillow from
+        the fetched frame when Pillow imports; otherwise the call raises and names the frame."""
+        if not getattr(self.api, "has_jpeg", False):
+            raise RuntimeError("this library has no JPEG encoder (trs_encode_jpeg)")
+        host = None
+        if frames is None:
+            src, n = None, self.n
+        elif is_device_array(frames):
+            shape = tuple(frames.__cuda_array_interface__["shape"])
+            if shape[-3:] != (self.H, self.W, 3):
+                raise ValueError(f"frames must be uint8[n, {self.H}, {self.W}, 3]")
+            src, n = device_ptr(frames), int(np.prod(shape[:-3], dtype=np.int64))
+        else:
+            host = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, self.H, self.W, 3)
+            n = int(host.shape[0])
+            d = C.c_void_p()
+            self.api.check(self.api.scratch(self._h, SLOT_JPEG_IN, host.nbytes, C.byref(d)), "scratch")
+            self.api.check(self.api.upload(self._h, d, host.ctypes.data, host.nbytes), "upload")
+            src = d.value
+        cap = self.jpeg_default_cap(quality) if cap is None else int(cap)
+        blob = np.empty(max(n, 0) * max(cap, 0), np.uint8)
+        off, ln = np.zeros(max(n, 0) + 1, np.int64), np.zeros(max(n, 0), np.int32)
+        self.api.check(self.api.encode_jpeg_host(self._h, src, n, int(quality), cap, blob.ctypes.data, blob.nbytes, off.ctypes.data, ln.ctypes.data),
+                       "encode_jpeg_host")
+        late = {}
+        over = np.flatnonzero(ln < 0)
+        if over.size:
+            try:
+                from PIL import Image
+            except ImportError:
+                raise RuntimeError(f"the JPEG file of env {int(over[0])} takes {-int(ln[over[0]])} bytes, more than cap = {cap}, and Pillow is not "
+                                   "there to encode it on the host: pass a larger cap") from None
+            import io
+            if host is None:
+                host = self.fetch("img") if frames is None else None
+            for i in over:
+                if host is not None:
+                    img = host[i]
+                else:                                            # a caller's device array: fetch the one frame
+                    import torch
+                    img = torch.as_tensor(frames, device=f"cuda:{self.device}").reshape(-1, self.H, self.W, 3)[int(i)].cpu().numpy()
+                buf = io.BytesIO()
+                Image.fromarray(img).save(buf, format="JPEG", quality=int(quality))
+                late[int(i)] = buf.getvalue()
+        return JpegFrames(blob[:int(off[-1])], off, ln, late)
 
     def driver_assist_host(self, steering, throttle, brake, speed, mode="steering", k=5):
         """``DriverAssistance.step`` (``components/driver_assistance.py:13-31``) for N cars on the device; returns new float32 arrays."""

@@ -58,7 +58,11 @@ class DataStorage(Component):
     def _store(self, k, record):
         key = "cam/img" if "cam/img" in record else "cam/processed_img"
         img = record.get(key)
-        if img is not None:
+        if isinstance(img, (bytes, bytearray, memoryview)):      # an encoded file (HipJpegEncoder, BatchedEnv.encode_jpeg): written as it is
+            with open(os.path.join(self.storage_path, f"img_{k}.jpg"), "wb") as f:
+                f.write(img)
+            record[key] = f"img_{k}.jpg"
+        elif img is not None:
             from PIL import Image
             Image.fromarray(np.asarray(img)).save(os.path.join(self.storage_path, f"img_{k}.jpg"))
             record[key] = f"img_{k}.jpg"
@@ -98,16 +102,24 @@ class BatchedDataStorage(Component):
     """N cars per tick -> N tubs ``<root>/records_{i}/`` (``i`` from 1 like the reference's folder numbering,
     ``datastorage.py:60-65``), each with the single-car layout above, so every tub loads with the reference's
     ``DataLoader`` classes.  Ports carry arrays of length N (``cam/img``: ``uint8[N,H,W,3]``; ``None`` allowed);
-    ``usr/del_record`` / ``usr/toggle_record`` are scalars or per-car arrays."""
+    ``usr/del_record`` / ``usr/toggle_record`` are scalars or per-car arrays.  ``image_port``: read the image from that port instead (e.g.
+    ``cam/img_jpg``, the files ``HipJpegEncoder`` made on the device: a sequence of ``bytes`` per tick) — it is still recorded under the
+    stored image name, so the JSON does not change."""
 
-    def __init__(self, n_cars, to_store=None, storage_root=None):
+    def __init__(self, n_cars, to_store=None, storage_root=None, image_port=None):
         Component.__init__(self, inputs=list(DEFAULT_TO_STORE if to_store is None else to_store), threaded=False)
         self.step_inputs += ["usr/del_record", "usr/toggle_record"]
+        stored = self.step_inputs[:-2]
+        if image_port is not None:
+            key = "cam/img" if "cam/img" in stored else "cam/processed_img"
+            if key not in stored:
+                raise ValueError("image_port needs 'cam/img' or 'cam/processed_img' among the stored ports")
+            self.step_inputs[self.step_inputs.index(key)] = image_port
         if storage_root is None:
             raise ValueError("storage_root is required")
         os.makedirs(storage_root, exist_ok=True)
         self.n = int(n_cars)
-        self.tubs = [DataStorage(to_store=self.step_inputs[:-2], storage_path=os.path.join(storage_root, f"records_{i + 1}")) for i in range(self.n)]
+        self.tubs = [DataStorage(to_store=stored, storage_path=os.path.join(storage_root, f"records_{i + 1}")) for i in range(self.n)]
 
     def step(self, *args):
         def car(v, i):
