@@ -278,6 +278,29 @@ int trs_encode_jpeg(trs_env* env, const uint8_t* d_src_or_null, int n_images, in
 int trs_encode_jpeg_host(trs_env* env, const uint8_t* d_src_or_null, int n_images, int quality, int cap,
                          uint8_t* h_blob, size_t blob_cap, int64_t* h_off, int32_t* h_len_or_null);
 
+/* ---- tub images, read back: img_k.jpg files on the device -> frames on the device (include/trsim_spec.h, "tub image (JPEG), decoding") ----
+ * The reference's loaders open every img_i.jpg with Pillow (components/keras_train.py:33-57).  trs_decode_jpeg gives the same bytes, for files that
+ * are already on the device (the encoder's slots, an uploaded tub) and frames that stay there (trs_pilot_forward, trs_pilot_act).
+ *   File i is d_files[d_off[i] .. d_off[i] + d_len[i]); files may start at any byte offset.  That covers the slots of trs_encode_jpeg
+ *     (d_off[i] = i * cap, d_len = the encoder's d_len) and a packed blob (d_off = the blob's offsets, d_len[i] = d_off[i + 1] - d_off[i]).
+ *   d_dst: uint8[n_images][H][W][3] of the handle's size (rows are stored by dwords when img_w is a multiple of 4 and d_dst is 4-byte aligned).
+ *   d_status[i]:  0 decoded, frame i written | 1 skipped: d_len[i] <= 0 (e.g. the encoder's overflow report), frame i untouched |
+ *     2 unsupported: a JPEG file outside the accepted kind (progressive, grayscale, other sampling than 4:2:0, restart intervals, 16-bit tables,
+ *       an Adobe segment, img_w <= 4, ...), frame i untouched: decode it on the host | 3 the file's size is not the handle's, frame i untouched |
+ *     4 corrupt (truncated, a code no table holds, a marker inside the scan), frame i undefined.
+ *   No byte outside frame i is written for file i, and no byte outside [d_off[i], d_off[i] + d_len[i]) is read, whatever the file holds.
+ *   Asynchronous, on the handle's stream; needs no camera (cfg.render == 0 handles with a size work).  Resident mode: as for trs_encode_jpeg.
+ *   trs_decode_jpeg_host: files packed in host memory (h_off has n_images + 1 entries, as trs_encode_jpeg_host fills it) -> h_dst, h_status;
+ *     frames with status 1..3 are left as the caller had them.  Uploads the files, one synchronisation.
+ *   TRS_ERR_ARG: n_images < 1, a NULL pointer (a refused call writes nothing).  TRS_ERR_LIMIT: the image is wider than the kernel's plan holds: a
+ *     workgroup keeps the sample rows of 4 files (one per wave) in LDS, 40.25 KiB + 3.5 KiB per 16 columns; with 160 KiB per workgroup: img_w > 544
+ *     (the error text gives the limit for the device's LDS, which is queried).
+ *   The kernel runs min(ceil(n_images / 4), 2 x CU count) workgroups of 4 waves, each wave looping over files. */
+int trs_decode_jpeg(trs_env* env, const uint8_t* d_files, const int64_t* d_off, const int32_t* d_len, int n_images,
+                    uint8_t* d_dst /* uint8[n][H][W][3] */, int32_t* d_status);
+int trs_decode_jpeg_host(trs_env* env, const uint8_t* h_blob, const int64_t* h_off /* n + 1 */, int n_images,
+                         uint8_t* h_dst, int32_t* h_status);
+
 /* Overwrite env pose (x, y, z, yaw, v) from host arrays of n_envs floats — test hook. */
 int trs_set_pose(trs_env* env, const float* h_x, const float* h_y, const float* h_z,
                  const float* h_yaw, const float* h_v);

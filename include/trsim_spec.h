@@ -203,6 +203,42 @@
  *     SOS components (1, 0x00) (2, 0x11) (3, 0x11), then 0, 63, 0.  623 bytes.
  *   This is what Pillow (libjpeg) writes for Image.fromarray(frame).save(path, quality=q): tests/test_jpeg_cpu.py restates the paragraph in numpy and
  *   compares files byte for byte; csrc/trsim_jpeg_tables.hpp is the one place the library's host and kernel take the rules from.
+ *
+ * ---- tub image (JPEG), decoding (trs_decode_jpeg; what the reference's loaders read back, components/keras_train.py:33-57; HIP library only) ------
+ *   One baseline JPEG file -> one uint8[H][W][3] RGB frame and a status.  Integer arithmetic only; >> is an arithmetic shift.
+ *   Accepted files: SOI; any APPn / COM segments (skipped); DQT and DHT taken FROM THE FILE (any number of 8-bit quantisation tables per segment,
+ *     any quality; up to two DC and two AC Huffman tables in one or several segments, so files written with optimised tables decode); SOF0 with
+ *     precision 8 and components (1, 0x22) (2, 0x11) (3, 0x11); one interleaved scan of components 1, 2, 3 with Ss = 0, Se = 63, Ah/Al = 0.
+ *   Status, decided segment by segment in file order:  4 (corrupt): no SOI, a byte other than 0xFF where a marker must stand, a segment that runs
+ *     past the file's end, a marker without a segment (0x00, 0x01, RSTn, SOI, EOI) before the scan, a table index > 3, a DHT with more codes of a
+ *     length than that length has or more than 256 symbols, a second SOF0, SOS before SOF0 or naming a table the file did not define, segment
+ *     lengths that contradict their counts.  2 (unsupported): fill bytes (0xFF 0xFF), 16-bit quantisation tables, Huffman table 2 or 3, APP14
+ *     "Adobe", any other precision, component count, ids or sampling, any other frame type (SOF1..SOF15), DRI, any other scan parameters, any
+ *     other marker, and a width <= 4 (a chroma plane <= 2 samples wide: libjpeg-turbo leaves the triangle filter there).  3: at SOS, H x W is not
+ *     the expected size.  Then the scan: 4 when a bit at or beyond the end of the file is needed, when the next bits are no code of the table, when
+ *     a marker (0xFF followed by anything but 0x00) stands before the last MCU is complete, when a DC size exceeds 11 or an AC size 10, or when a
+ *     run leaves the block.  Otherwise 0; what follows the last MCU (padding, EOI) is not looked at.
+ *   Entropy decoding is the inverse of the paragraph above: DC predictors per component over the whole scan, ZRL (16 zeros) and EOB, a 0x00 behind
+ *     a 0xFF dropped; an extra-bits value v of size s stands for v if v >= 1 << (s - 1), else v - (1 << s) + 1.
+ *   Dequantiser: coefficient k (zig-zag) times Q[k] of the component's table.
+ *   Inverse DCT: 13 constant bits, 2 extra bits after the first pass, COLUMNS FIRST.  One pass over i0..i7:
+ *       z1 = (i2 + i6) * 4433;  t2 = z1 - i6 * 15137;  t3 = z1 + i2 * 6270;  t0 = (i0 + i4) << 13;  t1 = (i0 - i4) << 13
+ *       t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *       a0 = i7, a1 = i5, a2 = i3, a3 = i1;  z1 = a0 + a3, z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3, z5 = (z3 + z4) * 9633
+ *       a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299;  z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5
+ *       a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4
+ *       o0..o7 = DESCALE(t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3; n)
+ *     with n = 11 over the 8 columns, then n = 18 over the 8 rows; sample = clamp(o + 128, 0, 255).  (libjpeg's range table wraps for coefficients
+ *     far outside what an image produces; that is not part of this paragraph: the arithmetic here wraps modulo 2^32 and then clamps.)
+ *   Chroma upsampling: the 2 x 2 triangle filter over the ceil(H / 2) x ceil(W / 2) REAL samples of a chroma plane (the padding rows and columns
+ *     the transform also produced are not read).  Image row y has the chroma row c = y >> 1 and the neighbour nb = the row above c when y is even,
+ *     the row below when y is odd; above the first row and below the last stands that row itself.  s = 3 c + nb per chroma column.  Image column x
+ *     has s of column x >> 1 and s' of the column to its left (x even) or right (x odd), which is that column itself at the plane's two ends:
+ *     even x: (3 s + s' + 8) >> 4,  odd x: (3 s + s' + 7) >> 4.
+ *   Colour, with cb, cr minus 128 and every result clamped to 0..255:
+ *     R = Y + ((FIX(1.402) cr + 32768) >> 16);  G = Y + ((-FIX(0.34414) cb + 32768 - FIX(0.71414) cr) >> 16);  B = Y + ((FIX(1.772) cb + 32768) >> 16)
+ *   This is what Pillow 12 on libjpeg-turbo gives for np.asarray(Image.open(path)): tests/test_jpeg_decode_cpu.py restates the paragraph in numpy
+ *   and compares frames byte for byte; csrc/trsim_jpeg_decode.hpp is the one place the library's kernel and the host test driver take the rules from.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

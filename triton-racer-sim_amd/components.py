@@ -274,6 +274,25 @@ class HipJpegEncoder(Component):
         return "JPEG Encoder"
 
 
+class HipJpegDecoder(Component):
+    """``cam/img_jpg -> cam/img``: the twin of ``HipJpegEncoder`` — a tick's ``img_k.jpg`` files (a sequence of ``bytes`` or a ``JpegFrames``, one per
+    car) back to frames ``uint8[N,H,W,3]``, decoded on the GPU by ``env`` (``BatchedEnv.decode_jpeg``; include/trsim_spec.h, "tub image (JPEG),
+    decoding"): byte for byte what Pillow's ``Image.open`` gives, e.g. to replay a recorded tub through a pilot."""
+
+    def __init__(self, env):
+        Component.__init__(self, inputs=["cam/img_jpg"], outputs=["cam/img"], threaded=False)
+        self.env = env
+
+    def step(self, *args):
+        files = args[0]
+        if files is None:
+            return None,
+        return self.env.decode_jpeg(files)[0],
+
+    def getName(self):
+        return "JPEG Decoder"
+
+
 MUX_INPUTS = ["usr/mode", "usr/steering", "usr/throttle", "usr/breaking", "ai/steering", "ai/throttle", "ai/breaking"]   # controlmultiplexer.py:9
 MUX_OUTPUTS = ["mux/steering", "mux/throttle", "mux/breaking"]
 

@@ -86,6 +86,9 @@ struct trs_env {
     trsim::DevBuf<> jpg_tab; int jpg_quality = 0;   // device copy of jpeg::Tables (trsim_jpeg_tables.hpp) for jpg_quality; 0: none yet
     trsim::DevBuf<uint8_t> jpg_slots, jpg_blob; trsim::DevBuf<int32_t> jpg_len; trsim::DevBuf<long long> jpg_off;   // trs_encode_jpeg_host: slots, lengths, packed files, offsets
     trsim::PinnedBuf<> jpg_pin;          // ... and the staging of its offsets and lengths
+    // the tub image decoder (trs_decode_jpeg; include/trsim_spec.h, "tub image (JPEG), decoding")
+    int jpd_lds_max = 0;                 // LDS a workgroup may take on the handle's device, queried at the first call; 0: not yet
+    trsim::DevBuf<uint8_t> jpd_files, jpd_dst; trsim::DevBuf<> jpd_meta;   // trs_decode_jpeg_host: the files, the frames, offsets | lengths | statuses
     uint64_t d2h_bytes = 0, h2d_bytes = 0;                  // trs_counters: what the library itself copied
     trsim::Comm* comm = nullptr;         // trsim_comm.hip: the RCCL communicator of trs_comm_init, nullptr = none
     hipEvent_t ev_order = nullptr;       // trs_stream_wait_external / trs_stream_signal_external

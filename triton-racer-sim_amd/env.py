@@ -583,6 +583,52 @@ class BatchedEnv:
                 late[int(i)] = buf.getvalue()
         return JpegFrames(blob[:int(off[-1])], off, ln, late)
 
+    # -- tub images, read back (include/trsim_spec.h, "tub image (JPEG), decoding") ----------------
+    JPEG_STATUS = {0: "decoded", 1: "skipped", 2: "unsupported", 3: "size differs", 4: "corrupt"}
+
+    def device_decode_jpeg(self, d_files, d_off, d_len, d_dst, d_status, n_images=None):
+        """``trs_decode_jpeg``, device to device and asynchronous on the env's stream: file ``i`` is ``d_files[d_off[i] : d_off[i] + d_len[i]]``
+        (``d_off`` int64, ``d_len`` int32 — the encoder's slots with ``d_off[i] = i * cap`` and its ``d_len``, or a packed blob), ``d_dst`` takes
+        ``uint8[n,H,W,3]``, ``d_status`` int32 per file (``JPEG_STATUS``).  Pointers are integers or anything with ``__cuda_array_interface__``."""
+        if not getattr(self.api, "has_jpeg_decode", False):
+            raise RuntimeError("this library has no JPEG decoder (trs_decode_jpeg)")
+        n = self.n if n_images is None else int(n_images)
+        self.api.check(self.api.decode_jpeg(self._h, device_ptr(d_files), device_ptr(d_off), device_ptr(d_len), n, device_ptr(d_dst), device_ptr(d_status)),
+                       "decode_jpeg")
+
+    def decode_jpeg(self, files):
+        """The frames of N ``img_k.jpg`` files in one call (``trs_decode_jpeg_host``) -> ``(uint8[n,H,W,3], int32 status[n])`` — byte for byte what
+        ``np.asarray(Image.open(path))`` gives.  ``files``: a sequence of ``bytes`` or a ``JpegFrames``.  A file the device reports as unsupported
+        (status 2: progressive, grayscale, other sampling, ...) is decoded with Pillow on the host when its result has the shape (H, W, 3); otherwise,
+        and for a file of another size (3) or a corrupt one (4), the call raises and names the index."""
+        if not getattr(self.api, "has_jpeg_decode", False):
+            raise RuntimeError("this library has no JPEG decoder (trs_decode_jpeg)")
+        files = [bytes(f) for f in files]
+        n = len(files)
+        out = np.zeros((n, self.H, self.W, 3), np.uint8)
+        status = np.zeros(n, np.int32)
+        if n == 0:
+            return out, status
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(f) for f in files], out=off[1:])
+        blob = np.frombuffer(b"".join(files) or b"\0", np.uint8)
+        self.api.check(self.api.decode_jpeg_host(self._h, blob.ctypes.data, off.ctypes.data, n, out.ctypes.data, status.ctypes.data), "decode_jpeg_host")
+        for i in np.flatnonzero(status != 0):
+            i, st = int(i), int(status[i])
+            img = None
+            if st == 2:
+                try:
+                    import io
+                    from PIL import Image
+                    img = np.asarray(Image.open(io.BytesIO(files[i])))
+                except Exception:
+                    img = None
+            if img is None or img.shape != (self.H, self.W, 3) or img.dtype != np.uint8:
+                raise RuntimeError(f"the JPEG file of index {i} is {self.JPEG_STATUS.get(st, st)} (status {st}, {len(files[i])} bytes) and cannot be decoded "
+                                   f"to uint8[{self.H}, {self.W}, 3]" + (" on the host either" if st == 2 else ""))
+            out[i] = img
+        return out, status
+
     def driver_assist_host(self, steering, throttle, brake, speed, mode="steering", k=5):
         """``DriverAssistance.step`` (``components/driver_assistance.py:13-31``) for N cars on the device; returns new float32 arrays."""
         arrs = [np.array(a, dtype=np.float32, copy=True).reshape(-1) for a in (steering, throttle, brake, speed)]

@@ -149,32 +149,52 @@ LOADERS = {
 }
 
 
-def load_records(paths, loader="speed_ctl"):
+def load_records(paths, loader="speed_ctl", env=None, batch=1024):
     """What ``DataLoader.load`` collects before its train/validation split (``keras_train.py:33-57``): for every tub,
     records ``i = 1, 2, ...`` until ``img_{i}.jpg`` or ``record_{i}.json`` is missing — the walk starts at 1, so the
     writer's record 0 is never read (reference quirk, kept).  Returns ``(images float32[n,H,W,3] in [0,1],
-    features float32[n,F] (F = 0 without features), labels float32[n,L])``."""
-    from PIL import Image
+    features float32[n,F] (F = 0 without features), labels float32[n,L])``.  ``env``: a ``BatchedEnv`` of the images' size — the same walk, but the
+    files are decoded on its GPU, ``batch`` at a time (``BatchedEnv.decode_jpeg``), instead of one by one with Pillow; the arrays are equal."""
     labels_of, features_of = LOADERS[loader]
     paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
     for p in paths:
         if not os.path.exists(p):
             raise FileNotFoundError(f"Folder does not exists: {p}")                    # keras_train.py:26-28
-    imgs, feats, labels = [], [], []
+    if env is None:
+        from PIL import Image
+    imgs, feats, labels, pending = [], [], [], []
+
+    def decode_pending():
+        if pending:
+            frames, _ = env.decode_jpeg(pending)
+            imgs.extend(frames.astype(np.float32) / np.float32(255))
+            pending.clear()
+
     for p in paths:
         i = 1
         while True:
             try:
-                img = np.asarray(Image.open(os.path.join(p, f"img_{i}.jpg")), dtype=np.float32)
-                img /= 255
+                if env is None:
+                    img = np.asarray(Image.open(os.path.join(p, f"img_{i}.jpg")), dtype=np.float32)
+                    img /= 255
+                else:
+                    with open(os.path.join(p, f"img_{i}.jpg"), "rb") as f:
+                        img = f.read()
                 with open(os.path.join(p, f"record_{i}.json")) as f:
                     record = json.load(f)
             except FileNotFoundError:
                 break
-            imgs.append(img)
+            if env is None:
+                imgs.append(img)
+            else:
+                pending.append(img)
+                if len(pending) >= max(int(batch), 1):
+                    decode_pending()
             labels.append(np.asarray(labels_of(record), dtype=np.float32))
             feats.append(np.asarray(features_of(record) if features_of else (), dtype=np.float32))
             i += 1
+    if env is not None:
+        decode_pending()
     if not imgs:
         return np.zeros((0, 0, 0, 3), np.float32), np.zeros((0, 0), np.float32), np.zeros((0, 2), np.float32)
     return np.stack(imgs), np.stack(feats), np.stack(labels)
