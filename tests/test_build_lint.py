@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+import __graft_entry__
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "triton-racer-sim_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -103,7 +105,7 @@ def device_asm(src, tmp_path_factory):
     return _ASM[src]
 
 
-SOURCES = ["trsim_hip.hip", "trsim_resident.hip", "trsim_pilot.hip"]
+SOURCES = [s for s in __graft_entry__.HIP_SOURCES if s.endswith(".hip")]
 
 
 @pytest.mark.parametrize("src", SOURCES)

@@ -19,14 +19,6 @@
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
 
-#define TRS_EXPORT extern "C" __attribute__((visibility("default")))
-
-#define CCHK(call)                                                                                \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) return trs_internal_fail(TRS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 namespace trsim {
 
 // the five entry points of rccl.h this file uses (signatures of /opt/rocm/include/rccl/rccl.h:187,220,260,339,678)
@@ -131,7 +123,7 @@ TRS_EXPORT int trs_comm_init(trs_env* e, int rank, int world, const void* unique
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     if (world < 1 || rank < 0 || rank >= world) return trs_internal_fail(TRS_ERR_ARG, "bad rank / world size");
     if (world > 1 && !unique_id) return trs_internal_fail(TRS_ERR_ARG, "a communicator of more than one rank needs rank 0's unique id (trs_comm_get_unique_id)");
-    CCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     { int rq = sync_handle(e); if (rq) return rq; }
     comm_destroy(e);
     Comm* c = new (std::nothrow) Comm();
@@ -152,7 +144,7 @@ TRS_EXPORT int trs_comm_init(trs_env* e, int rank, int world, const void* unique
 TRS_EXPORT int trs_comm_destroy(trs_env* e)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    CCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     { int rq = sync_handle(e); if (rq) return rq; }
     comm_destroy(e);
     return TRS_OK;
@@ -162,7 +154,7 @@ TRS_EXPORT int trs_allgather_returns(trs_env* e, const float** d_out_all, float*
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     if (!e->comm) return trs_internal_fail(TRS_ERR_STATE, "no communicator: call trs_comm_init first");
-    CCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     { int rq = quiesce_handle(e); if (rq) return rq; }       // the collective is queued on the handle's stream, behind the steps
     Comm* c = e->comm;
     const size_t n = (size_t)e->n;
@@ -170,12 +162,12 @@ TRS_EXPORT int trs_allgather_returns(trs_env* e, const float** d_out_all, float*
         const int rc = g_rccl.AllGather(e->pp.ep_return, c->gathered.get(), n, kNcclFloat32, c->nccl, e->sP);
         if (rc) return rccl_fail("ncclAllGather", rc);
     } else {
-        CCHK(hipMemcpyAsync(c->gathered.get(), e->pp.ep_return, n * sizeof(float), hipMemcpyDeviceToDevice, e->sP));
+        HIPCHK(hipMemcpyAsync(c->gathered.get(), e->pp.ep_return, n * sizeof(float), hipMemcpyDeviceToDevice, e->sP));
     }
     if (d_out_all) *d_out_all = c->gathered.get();
     if (h_out_all) {
-        CCHK(hipMemcpyAsync(h_out_all, c->gathered.get(), (size_t)c->world * n * sizeof(float), hipMemcpyDeviceToHost, e->sP));
-        CCHK(hipStreamSynchronize(e->sP));
+        HIPCHK(hipMemcpyAsync(h_out_all, c->gathered.get(), (size_t)c->world * n * sizeof(float), hipMemcpyDeviceToHost, e->sP));
+        HIPCHK(hipStreamSynchronize(e->sP));
         return check_fault(e);
     }
     return TRS_OK;
@@ -188,21 +180,21 @@ TRS_EXPORT int trs_allgather_returns(trs_env* e, const float** d_out_all, float*
 TRS_EXPORT int trs_stream_wait_external(trs_env* e, void* hip_stream)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    CCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     hipStream_t ext = static_cast<hipStream_t>(hip_stream);
-    if (resident_on(e) || resident_running(e)) { CCHK(hipStreamSynchronize(ext)); return TRS_OK; }   // a posted step reads its controls as soon as the worker sees the post
-    CCHK(hipEventRecord(e->ev_order, ext));
-    CCHK(hipStreamWaitEvent(e->sP, e->ev_order, 0));
+    if (resident_on(e) || resident_running(e)) { HIPCHK(hipStreamSynchronize(ext)); return TRS_OK; }   // a posted step reads its controls as soon as the worker sees the post
+    HIPCHK(hipEventRecord(e->ev_order, ext));
+    HIPCHK(hipStreamWaitEvent(e->sP, e->ev_order, 0));
     return TRS_OK;
 }
 
 TRS_EXPORT int trs_stream_signal_external(trs_env* e, void* hip_stream)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    CCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     hipStream_t ext = static_cast<hipStream_t>(hip_stream);
     if (resident_running(e)) { int rw = resident_wait(e); if (rw) return rw; return check_fault(e); }   // completion flags: the frames are in memory; an event would wait for the worker to leave
-    CCHK(hipEventRecord(e->ev_order, e->sP));
-    CCHK(hipStreamWaitEvent(ext, e->ev_order, 0));
+    HIPCHK(hipEventRecord(e->ev_order, e->sP));
+    HIPCHK(hipStreamWaitEvent(ext, e->ev_order, 0));
     return TRS_OK;
 }

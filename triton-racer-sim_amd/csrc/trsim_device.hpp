@@ -1,7 +1,8 @@
-// trsim_device.hpp — device-side pieces shared by the step kernels (trsim_hip.hip) and the resident worker
-// (trsim_resident.hip): the spec's arithmetic (include/trsim_spec.h), the wave-parallel nearest-point search
-// (= reference LocationTracker.__find_closest, components/track_data_process.py:89-104), one env step on registers, and the
-// per-thread raster walk.  Everything is force-inlined; both translation units compile their own copy.
+// trsim_device.hpp — device-side pieces shared by the step kernels (trsim_hip.hip), the resident worker (trsim_resident.hip)
+// and the image path (trsim_image.hip): the spec's arithmetic (include/trsim_spec.h), the wave-parallel nearest-point search
+// (= reference LocationTracker.__find_closest, components/track_data_process.py:89-104), one env step on registers, the
+// per-thread raster walk, and the colour-mask lookups and wave reductions the frame filters use.  Everything is force-inlined;
+// every translation unit compiles its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -119,6 +119,7 @@ void comm_destroy(trs_env* e);
 bool resident_running(const trs_env* e);
 void resident_clear_fault(trs_env* e);                     // trs_load_track puts every env on a defined state again
 int check_fault(trs_env* e);                               // TRS_ERR_DEVICE (sticky) once a kernel has reported a layout fault
+int ensure_hsv_table(trs_env* e);                          // e->hsv_tab holds OpenCV's reciprocal tables (hsv_reciprocals, trsim_filter.hpp); uploaded once (trsim_hip.hip)
 
 // the instantiation of the step kernel and of the resident worker that the handle's state selects (Variant, trsim_device.hpp)
 inline Variant variant_of(const trs_env* e)

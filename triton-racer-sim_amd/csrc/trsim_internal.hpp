@@ -1,11 +1,26 @@
-// trsim_internal.hpp — what trsim_pilot.hip needs from the env handle defined in trsim_hip.hip (not part of the ABI).
+// trsim_internal.hpp — what the translation units of libtrsim.so share besides the handle (trsim_env.hpp): the accessors trsim_hip.hip defines for the
+// others, and the macros every unit exports and checks HIP calls with (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 
 #include "../../include/trsim.h"
+
+#define TRS_EXPORT extern "C" __attribute__((visibility("default")))
+
+// a failed HIP call ends the entry point with TRS_ERR_DEVICE and "<call>: <hipGetErrorString>" as trs_last_error()
+#define HIPCHK(call)                                                                                             \
+    do {                                                                                                         \
+        hipError_t _e = (call);                                                                                  \
+        if (_e != hipSuccess) return trs_internal_fail(TRS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+namespace trsim {
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+}
 
 namespace trsim { struct Controls; }   // trsim_plan.hpp
 

@@ -15,16 +15,8 @@
 #include "trsim_internal.hpp"
 #include "trsim_jpeg_tables.hpp"
 
-#define TRS_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 namespace jpeg = trsim::jpeg;
-
-#define HIPCHK(call)                                                                                             \
-    do {                                                                                                         \
-        hipError_t _e = (call);                                                                                  \
-        if (_e != hipSuccess) return trs_internal_fail(TRS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 struct JpegParams {
     const uint8_t* src;          // uint8[n][H][W][3], 4-byte aligned

@@ -17,16 +17,8 @@
 #include "trsim_internal.hpp"
 #include "trsim_jpeg_decode.hpp"
 
-#define TRS_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 namespace jpeg = trsim::jpeg;
-
-#define HIPCHK(call)                                                                                             \
-    do {                                                                                                         \
-        hipError_t _e = (call);                                                                                  \
-        if (_e != hipSuccess) return trs_internal_fail(TRS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 struct DecodeParams {
     const uint8_t* files; const int64_t* off; const int32_t* len;

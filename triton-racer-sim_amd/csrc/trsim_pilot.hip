@@ -38,8 +38,6 @@
 #include "trsim_internal.hpp"
 #include "trsim_mem.hpp"
 
-#define TRS_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;   // 8 binary16 values: one MFMA operand fragment per lane (round 3: binary16 instead of bfloat16 —
@@ -1651,12 +1649,6 @@ __global__ void trs_zero_controls_kernel(float* a, float* b, float* c, int n)
 }
 
 // ---------------------------------------------------------------------------------------------
-
-#define HIPCHK(call)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) return trs_internal_fail(TRS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 struct ConvLayer {
     int KH, KW, S, CIN, COUT, COUT_PAD, IH, IW, OH, OW, G, G_pad;

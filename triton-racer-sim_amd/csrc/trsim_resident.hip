@@ -45,8 +45,6 @@
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
 
-#define TRS_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace trsim {
 
 constexpr int kSlots = 8;       // posts in flight: ring entries, arrival counters, done flags
@@ -1062,12 +1060,6 @@ __global__ void trs_worker_init_kernel(DevCtl* dc, u64 start)
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-#define RCHK(call)                                                                                \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) return trs_internal_fail(TRS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 inline uint64_t host_load(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
 inline void host_store(uint64_t* p, uint64_t v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
 
@@ -1085,7 +1077,7 @@ int worker_fits(trs_env* e)
         // beyond it the workgroups that found no room never arrive — a step would complete only when the others idle out).
         if (R->pw_capacity_lds != R->lds_bytes) {            // (asked once per LDS need: this runs in front of every worker start)
             int per_cu = 0;
-            RCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(trs_physics_worker_kernel), kPwBlock, (size_t)R->lds_bytes));
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(trs_physics_worker_kernel), kPwBlock, (size_t)R->lds_bytes));
             R->pw_capacity_envs = (long long)per_cu * (long long)std::max(e->cu_count, 1) * kPwEnvs;
             R->pw_capacity_lds = R->lds_bytes;
         }
@@ -1150,7 +1142,7 @@ int worker_launch(trs_env* e, uint64_t start)
     } else {
         hipLaunchKernelGGL(trs_physics_worker_kernel, dim3(grid), dim3(kPwBlock), R->lds_bytes, e->sP, wp);
     }
-    RCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     R->running = true;
     R->t_launch = std::chrono::steady_clock::now();
     return TRS_OK;
@@ -1211,7 +1203,7 @@ int fall_back_to_launches(trs_env* e, uint64_t consumed, const char* why)
 int handle_exit(trs_env* e, bool relaunch = true)
 {
     Resident* R = e->res;
-    RCHK(hipStreamSynchronize(e->sP));
+    HIPCHK(hipStreamSynchronize(e->sP));
     R->running = false;
     int rc = worker_error(e);
     if (rc) return rc;
@@ -1247,7 +1239,7 @@ int give_up_on_launch(trs_env* e)
 {
     Resident* R = e->res;
     host_store(&R->mb->close, kCloseCancel);
-    RCHK(hipStreamSynchronize(e->sP));                       // bounded by the other worker's lifetime (50 ms) or idle time
+    HIPCHK(hipStreamSynchronize(e->sP));                       // bounded by the other worker's lifetime (50 ms) or idle time
     R->running = false;
     int rc = worker_error(e);
     if (rc) return rc;
@@ -1262,7 +1254,7 @@ int wait_done(trs_env* e, uint64_t s)
     Mailbox* mb = R->mb.get();
     const auto t0 = std::chrono::steady_clock::now();
     auto fell_back = [&]() -> int {                           // the posted steps went onto the stream as launches: wait for the stream
-        RCHK(hipStreamSynchronize(e->sP));
+        HIPCHK(hipStreamSynchronize(e->sP));
         R->launched = false;
         R->base = R->seen_done = e->step_count;
         return TRS_OK;
@@ -1295,20 +1287,20 @@ int ensure_resident(trs_env* e)
 {
     Resident* R = e->res;
     if (R->mb.get()) return TRS_OK;
-    RCHK(R->mb.alloc(sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(R->mb.alloc(sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(R->mb.get(), 0, sizeof(Mailbox));
-    RCHK(R->dc.alloc(sizeof(DevCtl)));
+    HIPCHK(R->dc.alloc(sizeof(DevCtl)));
     // The copy stream must not share a hardware queue with the handle's stream: a copy queued behind the worker kernel on the same queue would
     // wait until the worker leaves (seen in round 4: 100 ms = idle_us per trs_fetch_outputs in a process that had created many streams, where
     // the runtime's least-used-queue choice put both streams on one queue).  The runtime keeps a separate pool of hardware queues per stream
     // priority, so the copy stream takes the HIGHEST priority and the handle's stream (default priority) can never alias it.
     {
         int least = 0, greatest = 0;
-        RCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        RCHK(hipStreamCreateWithPriority(&R->sC, hipStreamNonBlocking, greatest));
+        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(hipStreamCreateWithPriority(&R->sC, hipStreamNonBlocking, greatest));
     }
     R->hctl_slot = ((size_t)e->n * 13 + 63) & ~(size_t)63;
-    RCHK(R->hctl.alloc(R->hctl_slot * kSlots, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(R->hctl.alloc(R->hctl_slot * kSlots, hipHostMallocMapped | hipHostMallocCoherent));
     return TRS_OK;
 }
 
@@ -1387,7 +1379,7 @@ int resident_wait(trs_env* e)
     if (!R) return TRS_OK;
     DevLock lock(e);
     if (R->launched && !R->running) {                        // the newest steps went through launches (resident_note_launch): wait for the stream
-        RCHK(hipStreamSynchronize(e->sP));
+        HIPCHK(hipStreamSynchronize(e->sP));
         R->launched = false;
         R->base = R->seen_done = e->step_count;
         return TRS_OK;
@@ -1509,10 +1501,10 @@ TRS_EXPORT int trs_resident_debug_abort(trs_env* e)
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     DevLock lock(e);
     if (!e->res || !e->res->running) return trs_internal_fail(TRS_ERR_STATE, "no resident worker is running on this handle");
-    RCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(trs_worker_debug_abort_kernel, dim3(1), dim3(1), 0, e->res->sC, e->res->mb.get(), e->res->dc.get());
-    RCHK(hipGetLastError());
-    RCHK(hipStreamSynchronize(e->res->sC));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->res->sC));
     return TRS_OK;
 }
 #endif
@@ -1530,7 +1522,7 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     if (mode != TRS_STEP_LAUNCH && mode != TRS_STEP_RESIDENT) return trs_internal_fail(TRS_ERR_ARG, "mode must be TRS_STEP_LAUNCH or TRS_STEP_RESIDENT");
-    RCHK(hipSetDevice(e->device));
+    HIPCHK(hipSetDevice(e->device));
     DevLock lock(e);
     if (mode == TRS_STEP_LAUNCH) {
         if (!e->res) return TRS_OK;
@@ -1549,8 +1541,8 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
     Resident* R = e->res;
     { int rf = worker_fits(e); if (rf) return rf; }
     for (const WorkerKernel wk : kWorkerKernels)
-        if (wk) RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    RCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_worker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (wk) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_worker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (idle_us > 0) R->idle_us = (unsigned)std::min(idle_us, 1000000);
     if (!R->enabled) { R->base = R->seen_done = e->step_count; host_store(&R->mb->posted, e->step_count); }
     R->enabled = true;
