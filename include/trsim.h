@@ -301,6 +301,37 @@ int trs_decode_jpeg(trs_env* env, const uint8_t* d_files, const int64_t* d_off, 
 int trs_decode_jpeg_host(trs_env* env, const uint8_t* h_blob, const int64_t* h_off /* n + 1 */, int n_images,
                          uint8_t* h_dst, int32_t* h_status);
 
+/* ---- camera codec: the JPEG round trip every frame of the reference's pilot has been through (include/trsim_spec.h, "camera codec (JPEG round trip)") ----
+ * The simulator sends 'cam/img' as a JPEG and GymInterface.on_msg_recv decodes it (components/gyminterface.py:97-99); DataStorage saves it as JPEG
+ * again (components/datastorage.py:78): the reference's pilot trains and drives on lossy frames.  codec(frame, q) is what trs_decode_jpeg gives for
+ * the file trs_encode_jpeg writes for `frame` at quality q — what Pillow gives for save(quality = q), then open — computed in one kernel without
+ * the file: entropy coding is lossless, so the quantised coefficients go straight to the dequantiser.  Parity with the closed simulator's own
+ * encoder is unpinned: its quality is not known.
+ *   trs_jpeg_roundtrip: d_src uint8[n_images][H][W][3] of the handle's size, 4-byte aligned; NULL = the latest frames, as trs_encode_jpeg resolves
+ *     them (n_images == n_envs; behind every step mode, lens, lighting, hills and latency: the call reads whole frames after the step).  d_dst: the
+ *     same shape, 4-byte aligned; NULL = the handle's own codec buffer (n_images <= n_envs), returned through *d_out (may be NULL).  No byte outside
+ *     frame i of d_dst is written for frame i, and d_src is only read.  Asynchronous, on the handle's stream.  Resident mode: the worker leaves the
+ *     GPU first, as for trs_encode_jpeg, and trs_sync then waits for the kernel like for a launched step.
+ *   trs_jpeg_roundtrip_host: host frames in (NULL = the latest frames) and out, synchronous (the N = 1 Component path).
+ *   TRS_ERR_ARG: quality outside 1..100, n_images < 1 (or != n_envs with a NULL source, or > n_envs with a NULL destination), a misaligned pointer,
+ *     a destination range that overlaps the source (a pixel is made from its neighbours' blocks: the call does not work in place).  TRS_ERR_STATE: a
+ *     NULL source on a handle without a camera.  TRS_ERR_LIMIT: img_w <= 4 (the triangle filter needs more than two chroma columns), or img_w beyond
+ *     what the kernel's plan holds: a workgroup keeps a 16-row stripe (raw rows, sample planes before and after the transform) in LDS, 9.5 KiB +
+ *     2 KiB per 16 columns; with 160 KiB: img_w > 1200 (the error text gives the limit).  A refused call writes nothing.
+ *   The kernel runs min(n_images, 4 x CU count) workgroups, each looping over frames.
+ *   trs_set_camera_codec(quality): while a quality in 1..100 is set, trs_step_pilot feeds the pilot codec(frame, quality) of whichever frame it reads
+ *     — the latest frame, or the delayed observation frame while a latency is set (cars nothing has reached yet stay masked) — by one pre-pass per
+ *     step into the handle's codec buffer.  Everything that shows what the simulator did stays the truth, bit for bit: trs_get_state,
+ *     trs_fetch_outputs, trs_copy_to_host, trs_get_observation, trs_encode_jpeg with a NULL source, depth.  0: off — from the next step on every byte
+ *     and control is what a handle that never set a codec gives.  TRS_ERR_STATE: no camera; a frame filter is set (trs_set_frame_filter: the fused
+ *     filter would run in FRONT of the codec, the reference's ImgPreprocessing runs behind the decoded frame — trs_preprocess on the codec's frames
+ *     gives that order); trs_set_frame_filter with a filter is refused likewise while a codec is set.  A refused call leaves the handle unchanged.
+ *   trs_get_camera_codec: the quality that is set, 0: none. */
+int trs_jpeg_roundtrip(trs_env* env, const uint8_t* d_src_or_null, int n_images, int quality, uint8_t* d_dst_or_null, const uint8_t** d_out);
+int trs_jpeg_roundtrip_host(trs_env* env, const uint8_t* h_src_or_null, int n_images, int quality, uint8_t* h_dst);
+int trs_set_camera_codec(trs_env* env, int quality);
+int trs_get_camera_codec(trs_env* env, int* quality);
+
 /* Overwrite env pose (x, y, z, yaw, v) from host arrays of n_envs floats — test hook. */
 int trs_set_pose(trs_env* env, const float* h_x, const float* h_y, const float* h_z,
                  const float* h_yaw, const float* h_v);

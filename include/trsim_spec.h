@@ -239,6 +239,18 @@
  *     R = Y + ((FIX(1.402) cr + 32768) >> 16);  G = Y + ((-FIX(0.34414) cb + 32768 - FIX(0.71414) cr) >> 16);  B = Y + ((FIX(1.772) cb + 32768) >> 16)
  *   This is what Pillow 12 on libjpeg-turbo gives for np.asarray(Image.open(path)): tests/test_jpeg_decode_cpu.py restates the paragraph in numpy
  *   and compares frames byte for byte; csrc/trsim_jpeg_decode.hpp is the one place the library's kernel and the host test driver take the rules from.
+ *
+ * ---- camera codec (JPEG round trip) (trs_jpeg_roundtrip, trs_set_camera_codec; the decoded 'cam/img' of components/gyminterface.py:97-99; HIP library only)
+ *   codec(frame, q) of one uint8[H][W][3] RGB frame, W > 4, q in 1..100: the frame "tub image (JPEG), decoding" gives for the file "tub image
+ *   (JPEG)" defines for `frame` at quality q.  Entropy coding is lossless, so no file is made; step by step, each as the paragraph named defines it:
+ *     colour, edges, 2 x 2 downsampling, forward DCT (rows, then columns), quantiser                 ("tub image (JPEG)")
+ *     dequantiser, inverse DCT (columns, then rows), clamp, triangle upsampling, colour              ("tub image (JPEG), decoding")
+ *   The quantised coefficient v goes straight to the dequantiser: v times the table entry Q it was quantised with.
+ *   Dummy Y blocks are never output: they hold no image sample, and what the file carries in them (the DC of the block before) does not reach a pixel.
+ *   The padding rows and columns of the chroma planes take part in their blocks' transforms and are not read by the upsampler.
+ *   The result equals what Pillow gives for save(quality = q), then open.  Parity with the closed simulator's own encoder is unpinned: its quality
+ *   is unknown.  tests/test_jpeg_codec_cpu.py restates the paragraph in numpy and compares it with decode(encode()) of the two paragraphs above and with
+ *   Pillow, byte for byte; csrc/trsim_jpeg_codec.hpp composes the two headers' rules for the kernel and for the host test driver.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

@@ -150,9 +150,12 @@ JPEG_SYMBOLS = ["jpeg_header_bytes", "encode_jpeg", "encode_jpeg_host"]
 # HIP library only: the tub image decoder (trs_decode_jpeg) — its checker is the restatement of include/trsim_spec.h ("tub image (JPEG), decoding") in
 # tests/test_jpeg_decode_cpu.py, itself pinned to Pillow's decoder byte for byte (tests/test_jpeg_decode_gpu.py compares the kernel's frames with it)
 JPEG_DECODE_SYMBOLS = ["decode_jpeg", "decode_jpeg_host"]
+# HIP library only: the camera codec (trs_jpeg_roundtrip, trs_set_camera_codec) — its checker is the restatement of include/trsim_spec.h ("camera codec
+# (JPEG round trip)") in tests/test_jpeg_codec_cpu.py, itself pinned to decode(encode()) of the two restatements above and to Pillow's save and open
+JPEG_CODEC_SYMBOLS = ["jpeg_roundtrip", "jpeg_roundtrip_host", "set_camera_codec", "get_camera_codec"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -250,6 +253,12 @@ class Api:
             "decode_jpeg": (i32, [vp, vp, vp, vp, i32, vp, vp]),
             "decode_jpeg_host": (i32, [vp, vp, vp, i32, vp, vp]),
         }
+        jpeg_codec = {
+            "jpeg_roundtrip": (i32, [vp, vp, i32, i32, vp, C.POINTER(vp)]),
+            "jpeg_roundtrip_host": (i32, [vp, vp, i32, i32, vp]),
+            "set_camera_codec": (i32, [vp, i32]),
+            "get_camera_codec": (i32, [vp, C.POINTER(i32)]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -288,6 +297,12 @@ class Api:
         self.has_jpeg_decode = hasattr(cdll, prefix + "decode_jpeg")
         if self.has_jpeg_decode:
             for name, (res, args) in jpeg_decode.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_jpeg_codec = hasattr(cdll, prefix + "jpeg_roundtrip")
+        if self.has_jpeg_codec:
+            for name, (res, args) in jpeg_codec.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

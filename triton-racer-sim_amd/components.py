@@ -23,6 +23,8 @@ DEFAULT_GYM_CONFIG = {
     "img_w": 160, "img_h": 120, "scene_name": "generated_track", "sim_latency": 0,
     "track_data_file": "track_data/generated_track.json", "hip_device": 0,
     "hip_resident": False,      # True: trs_set_step_mode(TRS_STEP_RESIDENT) - the per-tick step is POSTED to a worker kernel that stays on the GPU
+    "img_jpeg_quality": 0,      # 1..100: 'cam/img' is the frame after a JPEG save at this quality and open (the reference's 'cam/img' is a decoded JPEG,
+                                # gyminterface.py:97-99; BatchedEnv.jpeg_roundtrip); 0: the rendered frame.  img_enc stays ignored
 }
 
 _SCENE_TRACKS = {"generated_track": "generated_track.json", "mountain_track": "mountain_track.json"}
@@ -38,7 +40,7 @@ def _track_for(cfg):
 def _camera_for(cfg):
     """The lens camera of a gym_config: ``fish_eye_x``, ``fish_eye_y`` and ``offset_x`` (gyminterface.py:16-45; the reference sends
     them as strings, :139-150, so strings are accepted).  Absent or zero keys: ``None``, the pinhole camera.  The other camera keys
-    (fov, offset_y, offset_z, rot_x, img_d, img_enc) stay ignored."""
+    (fov, offset_y, offset_z, rot_x, img_d, img_enc) stay ignored (``img_jpeg_quality`` is the key that puts 'cam/img' through a JPEG)."""
     vals = tuple(float(cfg.get(k, 0.0) or 0.0) for k in ("fish_eye_x", "fish_eye_y", "offset_x"))
     return vals if any(v != 0.0 for v in vals) else None
 
@@ -55,6 +57,14 @@ def _lighting_for(cfg):
         vals = [float(x) for x in (v if isinstance(v, (list, tuple, np.ndarray)) else [v])]
         return np.broadcast_to(np.asarray(vals, np.float32), (3,)).reshape(1, 3)
     return triple(g, 1.0), triple(b, 0.0)
+
+
+def _jpeg_quality_for(cfg):
+    """``img_jpeg_quality`` of a gym_config (a number or a string, as the reference sends its camera keys): 0 or absent = off, else 1..100."""
+    q = int(float(cfg.get("img_jpeg_quality", 0) or 0))
+    if not 0 <= q <= 100:
+        raise ValueError("img_jpeg_quality must be in 1..100, or 0 for the rendered frame")
+    return q
 
 
 def sim_latency_ticks(sim_latency, loop_hz=20, n=None):
@@ -93,6 +103,7 @@ class HipGymInterface(Component):
             self.env.set_lighting(*light)
         if self.gym_config.get("hip_resident"):
             self.env.set_step_mode(True, idle_us=int(self.gym_config.get("hip_resident_idle_us", 0)))
+        self.jpeg_quality = _jpeg_quality_for(self.gym_config)
         self.last_image = None
         self.pos_x = self.pos_y = self.pos_z = self.speed = self.cte = 0.0
         self.seg_idx = 0
@@ -106,7 +117,9 @@ class HipGymInterface(Component):
         self.env.step(float(steering), float(throttle), float(breaking), reset=bool(reset))
         # a fresh ndarray per frame, never overwritten by later steps (ownership rule of gyminterface.py:99); Python floats
         # because json.dump needs them (gyminterface.py:100-104); one synchronisation for the whole tuple
-        img, x, y, z, speed, cte, seg, _ = self.env.fetch_outputs()
+        img, x, y, z, speed, cte, seg, _ = self.env.fetch_outputs(image=not self.jpeg_quality)
+        if self.jpeg_quality:                                 # the frame as the reference's car sees it: through a JPEG (gyminterface.py:97-99)
+            img = self.env.jpeg_roundtrip(None, self.jpeg_quality)
         self.last_image = img[0]
         self.pos_x, self.pos_y, self.pos_z, self.speed, self.cte = float(x[0]), float(y[0]), float(z[0]), float(speed[0]), float(cte[0])
         self.seg_idx = int(seg[0])
@@ -150,6 +163,18 @@ class BatchedGymInterface(Component):
         self.delayed = bool(np.any(self.latency_ticks > 0))
         if self.delayed:
             self.env.set_latency(self.latency_ticks)
+        # img_jpeg_quality: 'cam/img' is the codec's frame of what the port would carry without the key (the latest frame, or the delayed one)
+        self.jpeg_quality = _jpeg_quality_for(self.gym_config)
+
+    def _codec_img(self, frames, out):
+        """``out`` with its first entry replaced by the codec's frame of ``frames``: host frames (``to_host``), or a device handle / ``None`` (the
+        latest frames), whose codec frame lies in the env's codec buffer until the next call."""
+        if self.to_host:
+            return (self.env.jpeg_roundtrip(frames, self.jpeg_quality), *out[1:])
+        img = self.env.device_jpeg_roundtrip(frames, self.jpeg_quality)
+        if self.sync:
+            self.env.sync()
+        return (img, *out[1:])
 
     def set_lighting(self, params=None, bias=None):
         """Scene lighting per env (``BatchedEnv.set_lighting``): redraw it at episode resets for domain randomisation."""
@@ -171,17 +196,22 @@ class BatchedGymInterface(Component):
         names = ["img", "pos_x", "pos_y", "pos_z", "speed", "cte", "seg_idx", "done"]
         if self.delayed:                                       # the observation, sim_latency late; 'gym/done' stays the truth
             if self.to_host:
-                return (*self.env.observation()[:7], self.env.fetch("done"))
+                out = (*self.env.observation()[:7], self.env.fetch("done"))
+                return self._codec_img(out[0], out) if self.jpeg_quality else out
             if self.sync:
                 self.env.sync()
-            return (*(self.env.device_observation(n, sync=False) for n in names[:7]), self.env.device_array("done", sync=False))
+            out = (*(self.env.device_observation(n, sync=False) for n in names[:7]), self.env.device_array("done", sync=False))
+            return self._codec_img(out[0], out) if self.jpeg_quality else out
         if self.to_host:
+            if self.jpeg_quality:
+                return self._codec_img(None, self.env.fetch_outputs(image=False))
             return self.env.fetch_outputs()
         # device handles: the step ran on the env's own stream, so order it before anyone looks (one wait for the tuple).
         # 'cam/img' alternates between two buffers: a handle stays valid while the NEXT step renders, not beyond.
         if self.sync:
             self.env.sync()
-        return tuple(self.env.device_array(n, sync=False) for n in names)
+        out = tuple(self.env.device_array(n, sync=False) for n in names)
+        return self._codec_img(None, out) if self.jpeg_quality else out
 
     def onShutdown(self):
         self.env.close()

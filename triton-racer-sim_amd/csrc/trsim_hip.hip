@@ -13,6 +13,7 @@
 //   trsim_control.hip  trs_driver_assist and trs_control_mux, kernels and host
 //   trsim_resident.hip the resident worker (trs_set_step_mode)            trsim_pilot.hip  the pilot network and trs_step_pilot
 //   trsim_jpeg.hip / trsim_jpeg_decode.hip  the tub image codec           trsim_comm.hip   the RCCL communicator
+//   trsim_jpeg_codec.hip  the camera codec (trs_jpeg_roundtrip, trs_set_camera_codec)
 //   trsim_filter.hpp   host only: the static colour filter of ONE colour, OpenCV's reciprocal tables, the check of a trs_pre_config
 //
 // Inside a multi-step call the raster team renders step t-1 while the physics team computes step t; the host opens the call with a physics-only launch
@@ -1500,6 +1501,9 @@ TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
         const char* why = nullptr;
         int rc = trsim::check_pre(c, &why);
         if (rc) return fail(rc, why);
+        if (e->codec_quality)
+            return fail(TRS_ERR_STATE, "a camera codec is set (trs_set_camera_codec): the fused filter would run in front of it, the reference filters the decoded frame: "
+                                       "use trs_preprocess on the codec's frames");
         if (c->edge_detection_enabled) return fail(TRS_ERR_ARG, "the Canny layer is a neighbourhood operator: not a palette filter, use trs_preprocess");
         if (c->dynamic_brightness)
             if (const Variant set = trsim::variant_clash(variant_now(e), kVDyn)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVDyn, set));
@@ -1723,6 +1727,7 @@ bool trs_internal_view(trs_env* e, TrsEnvView* v)
     v->step_count = e->step_count;
     v->stats = e->stats.get();
     v->obs_on = e->lat.on();
+    v->codec_quality = e->codec_quality;
     v->obs_frame = nullptr; v->obs_speed = nullptr; v->obs_seg_idx = nullptr; v->obs_mode = nullptr;
     if (v->obs_on && history_steps(e) > 0) {                 // what the car is told (trs_get_observation); before the first step of the history: nothing
         trs_obs_view o;

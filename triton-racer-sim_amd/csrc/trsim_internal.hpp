@@ -38,6 +38,7 @@ struct TrsEnvView {
     bool obs_on;
     const uint8_t* obs_frame; const float* obs_speed; const int32_t* obs_seg_idx;
     const uint8_t* obs_mode;          // uint8[n]: TRS_MODE_AI where the env's observation has arrived, else TRS_MODE_HUMAN
+    int codec_quality;                // trs_set_camera_codec: trs_step_pilot feeds the pilot codec(frame) of the frame it reads (0: the frame itself)
 };
 
 bool trs_internal_view(trs_env* e, TrsEnvView* out);
@@ -46,6 +47,7 @@ const trs_pilot_tuning* trs_internal_pilot_tuning(trs_env* e);   // what trs_pil
 void trs_internal_set_pilot_tuning(trs_env* e, const trs_pilot_tuning* t);
 int trs_internal_fail(int code, const std::string& msg);
 const uint8_t* trs_internal_latest_frame(const trs_env* e);   // what a NULL frame source means to trs_normalize, trs_preprocess and trs_encode_jpeg (nullptr: no camera)
+int trs_internal_camera_codec(trs_env* e, const uint8_t* d_frames, const uint8_t** d_out);   // codec(n_envs frames, the quality that is set) into the handle's codec buffer, on the stream (trsim_jpeg_codec.hip)
 int trs_internal_step_launch(trs_env* e, const float* d_st, const float* d_th, const float* d_br);   // one env step by launch, whatever the step mode
 // one env step with index `step` by launch, on the handle's stream, WITHOUT moving the step counter: a step that was posted to a resident worker
 // (the counter moved at the post) and has to run as a launch after all (trsim_resident.hip, fall_back_to_launches)

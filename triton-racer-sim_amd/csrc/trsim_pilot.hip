@@ -2493,14 +2493,19 @@ TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_ste
     HIPCHK(hipSetDevice(v.device));
     for (int k = 0; k < n_steps; ++k) {
         trs_internal_view(e, &v);
-        if (v.obs_on && v.obs_frame) {              // an observation latency is set: KerasPilot.step on what each car has been told (frame, speed, segment), and
+        const uint8_t* seen = v.obs_on ? v.obs_frame : v.latest_frame;      // the frame the pilot reads today (nullptr: none yet)
+        if (seen && v.codec_quality) {              // a camera codec is set: the pilot reads codec(that frame), as the reference's pilot reads decoded JPEGs
+            int rc = trs_internal_camera_codec(e, seen, &seen);
+            if (rc) return rc;
+        }
+        if (v.obs_on && seen) {                     // an observation latency is set: KerasPilot.step on what each car has been told (frame, speed, segment), and
             TrsEnvView o = v;                       // (0, 0, 0) for the cars nothing has reached yet (keras_pilot.py:46-47) through the tail's mode mask
             o.speed = v.obs_speed; o.seg_idx = v.obs_seg_idx;
             const ActIo io{nullptr, nullptr, v.obs_mode, v.ctl_steer, v.ctl_thr, v.ctl_brk};
-            int rc = forward_and_tail(c, o, v.obs_frame, v.n, c->raw.get(), cfg, true, &io);
+            int rc = forward_and_tail(c, o, seen, v.n, c->raw.get(), cfg, true, &io);
             if (rc) return rc;
-        } else if (!v.obs_on && v.latest_frame) {   // KerasPilot.step on the frame of the previous tick
-            int rc = forward_and_tail(c, v, v.latest_frame, v.n, c->raw.get(), cfg, true);
+        } else if (!v.obs_on && seen) {             // KerasPilot.step on the frame of the previous tick
+            int rc = forward_and_tail(c, v, seen, v.n, c->raw.get(), cfg, true);
             if (rc) return rc;
         } else {                                    // args[0] is None -> (0.0, 0.0, 0.0) (keras_pilot.py:46-47)
             hipLaunchKernelGGL(trs_zero_controls_kernel, dim3((v.n + 255) / 256), dim3(256), 0, v.stream, v.ctl_steer, v.ctl_thr, v.ctl_brk, v.n);

@@ -629,6 +629,57 @@ class BatchedEnv:
             out[i] = img
         return out, status
 
+    # -- camera codec (include/trsim_spec.h, "camera codec (JPEG round trip)") ---------------------
+    def _need_codec(self):
+        if not getattr(self.api, "has_jpeg_codec", False):
+            raise RuntimeError("this library has no camera codec (trs_jpeg_roundtrip)")
+
+    def device_jpeg_roundtrip(self, frames=None, quality=75, d_dst=None, n_images=None):
+        """``trs_jpeg_roundtrip``, device to device and asynchronous on the env's stream: ``frames`` (``None`` = the latest frames, else a device
+        ``uint8[n,H,W,3]``) as a JPEG save at ``quality`` and open would give them back.  ``d_dst``: ``None`` = the env's own codec buffer (which
+        ``step_pilot`` also writes while a camera codec is set), else a device ``uint8[n,H,W,3]`` that does not overlap ``frames``.  Returns a
+        zero-copy handle on the result."""
+        self._need_codec()
+        if frames is not None and n_images is None and is_device_array(frames):
+            shape = tuple(frames.__cuda_array_interface__["shape"])
+            if shape[-3:] != (self.H, self.W, 3):
+                raise ValueError(f"frames must be uint8[n, {self.H}, {self.W}, 3]")
+            n_images = int(np.prod(shape[:-3], dtype=np.int64))
+        n = self.n if n_images is None else int(n_images)
+        out = C.c_void_p()
+        self.api.check(self.api.jpeg_roundtrip(self._h, device_ptr(frames), n, int(quality), device_ptr(d_dst), C.byref(out)), "jpeg_roundtrip")
+        return _DevicePtr(out.value, (n, self.H, self.W, 3), np.uint8, self if d_dst is None else d_dst)
+
+    def jpeg_roundtrip(self, frames=None, quality=75):
+        """``codec(frame, quality)`` of N frames as a fresh ``uint8[n,H,W,3]`` (``trs_jpeg_roundtrip_host``) — byte for byte what saving each frame
+        with Pillow at ``quality`` and opening the file gives, the lossy frame the reference's pilot sees.  ``frames``: ``None`` = the env's latest
+        frames, a device array, or a host ``uint8[n,H,W,3]``."""
+        self._need_codec()
+        if frames is not None and is_device_array(frames):
+            d = self.device_jpeg_roundtrip(frames, quality)
+            import torch
+            self.sync()
+            return torch.as_tensor(d, device=f"cuda:{self.device}").cpu().numpy()
+        src = None if frames is None else np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, self.H, self.W, 3)
+        n = self.n if src is None else int(src.shape[0])
+        dst = np.empty((n, self.H, self.W, 3), np.uint8)
+        self.api.check(self.api.jpeg_roundtrip_host(self._h, None if src is None else src.ctypes.data, n, int(quality), dst.ctypes.data), "jpeg_roundtrip_host")
+        return dst
+
+    def set_camera_codec(self, quality=75):
+        """While set (``trs_set_camera_codec``), ``step_pilot`` feeds the pilot ``codec(frame, quality)`` of the frame it reads — the latest one, or
+        the delayed observation while a latency is set; ``fetch``, ``fetch_outputs``, ``observation`` and ``encode_jpeg`` keep showing the rendered
+        truth.  ``0`` or ``None``: off.  Refused while a frame filter is set, and ``set_frame_filter`` is refused while a codec is set."""
+        self._need_codec()
+        self.api.check(self.api.set_camera_codec(self._h, int(quality or 0)), "set_camera_codec")
+
+    def camera_codec(self):
+        """The quality ``set_camera_codec`` set (``trs_get_camera_codec``); 0: none."""
+        self._need_codec()
+        q = C.c_int(0)
+        self.api.check(self.api.get_camera_codec(self._h, C.byref(q)), "get_camera_codec")
+        return int(q.value)
+
     def driver_assist_host(self, steering, throttle, brake, speed, mode="steering", k=5):
         """``DriverAssistance.step`` (``components/driver_assistance.py:13-31``) for N cars on the device; returns new float32 arrays."""
         arrs = [np.array(a, dtype=np.float32, copy=True).reshape(-1) for a in (steering, throttle, brake, speed)]
@@ -778,7 +829,8 @@ class BatchedEnv:
 
     def step_pilot(self, n_steps=1, cfg=None):
         """Closed loop: controls = KerasPilot.step(previous frame, speed), then one env step; all on the device.  With ``set_latency`` the pilot
-        sees each car's observation (frame, speed, segment) instead, and cars nothing has reached yet get (0, 0, 0)."""
+        sees each car's observation (frame, speed, segment) instead, and cars nothing has reached yet get (0, 0, 0).  With ``set_camera_codec`` the
+        frame it sees has been through the JPEG round trip first."""
         pc = cfg if isinstance(cfg, _ffi.TrsPilotConfig) else self.pilot_config(cfg)
         self.api.check(self.api.step_pilot(self._h, C.byref(pc), int(n_steps)), "step_pilot")
 
