@@ -5,6 +5,10 @@
 //   plan_driver slices <n_envs>                the controls of a step call (Controls) after k = 0..16 steps: strides 0 and n_envs x brk / reset given or not, and the
 //                                              synthetic call; then the same for after(a).after(b), a, b = 0..8.  Offsets in floats from each array's base, -1 = null
 //   plan_driver fetch                          fetch_layout / fetch_reserve for every subset of the eight items, n_envs in {1, 5, 70}, with and without a 64x64 frame
+//   plan_driver lds <W> <lds_step> <epw> <n_phys>   for H = 2..600 and every built variant: every region offset of step_lds_layout and worker_lds_layout, where the
+//                                              lit palettes and the worker's hand-off slots begin, and for each of the hill_batch(H) row tables of a HILLS
+//                                              variant the offsets of its three planes (in the step kernel's layout and in the worker's) and its end
+//   plan_driver geometry <H> <W>               rows per pass, idle raster threads, passes and the last pass's rows, hill_batch, light_copies, the dynamic filter's window
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +42,34 @@ int main(int argc, char** argv)
                                 worker_lds_layout(lds_step, epw, H, W, v).total, (int)lds_fit(lds_step, epw, H, W, v, false), (int)lds_fit(lds_step, epw, H, W, v, true));
             }
         }
+        return 0;
+    }
+    if (argc >= 6 && !std::strcmp(argv[1], "lds")) {
+        const int W = std::atoi(argv[2]), lds_step = std::atoi(argv[3]), epw = std::atoi(argv[4]), n_phys = std::atoi(argv[5]);
+        for (int H = 2; H <= 600; ++H)
+            for (Variant v = 0; v < kVariants; ++v) {
+                if (!variant_built(v)) continue;
+                const bool hilly = (v & kVHills) != 0, dyn = (v & kVDyn) != 0;
+                const StepLds S = step_lds_layout(lds_step, epw, H, W, v, n_phys);
+                const WorkerLds K = worker_lds_layout(lds_step, epw, H, W, v);
+                std::printf("step %d %u %d %d %d %d %d %d %d %d\n", H, v, S.cam, S.prog, S.pitch, S.hill, S.light, S.light + epw * 32, S.dyn, S.total);
+                std::printf("worker %d %u %d %d %d %d %d %d %d\n", H, v, K.ctl, K.ctl + (int)wlds_slot_off(epw), K.dyn, K.hill, K.light, K.light + kCamDepth * epw * 32, K.total);
+                std::printf("sizes %d %u %d %d %d %d\n", H, v, tabs_lds_bytes(H, v), light_lds_extra(H, W, epw, hilly, dyn), light_lds_extra(H, W, kCamDepth * epw, hilly, dyn), dyn_lds_bytes(H));
+                if (!hilly) continue;
+                for (int k = 0; k < hill_batch(H); ++k)
+                    for (const int base : {S.hill, K.hill}) {
+                        const int tab = base + k * hill_table_bytes(H);
+                        std::printf("table %d %u %d %s %d %d %d %d\n", H, v, k, base == S.hill ? "step" : "worker", tab, tab + hill_table_pal_off(H), tab + hill_table_depth_off(H),
+                                    tab + hill_table_bytes(H));
+                    }
+                std::printf("hbar %d %u %d %d %d\n", H, v, hill_batch(H), S.hill + hill_batch(H) * hill_table_bytes(H), K.hill + hill_batch(H) * hill_table_bytes(H));
+            }
+        return 0;
+    }
+    if (argc >= 4 && !std::strcmp(argv[1], "geometry")) {
+        const int H = std::atoi(argv[2]), W = std::atoi(argv[3]), gpr = W / 4, rpp = raster_rows_per_pass(gpr);
+        std::printf("geometry %d %d %d %d %d %d %d %d %d %d %d\n", H, W, gpr, rpp, kRasterThreads - rpp * gpr, (H + rpp - 1) / rpp, H - ((H - 1) / rpp) * rpp, hill_batch(H),
+                    light_copies(gpr), dyn_window_lo(H), dyn_window_hi(H));
         return 0;
     }
     if (argc >= 3 && !std::strcmp(argv[1], "slices")) {

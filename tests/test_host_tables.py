@@ -247,3 +247,112 @@ def test_fetch_layout_every_subset(plan_driver):
             at = off + size
         assert at <= end <= reserve, (n, img, mask, at, end, reserve)
     assert len(seen) == len(rows)
+
+
+# ---- every LDS region and row-table plane over H = 2..600 (csrc/trsim_plan.hpp), on the CPU ------------------------------------------------
+
+K_CAM_DEPTH, K_DYN_BATCH, K_SLOT_WORDS, K_LENS_PAL_BYTES, K_DYN_TAB_WORDS, K_RASTER_THREADS = 4, 4, 20, 513 * 16, 512 + 768 + 4 + 256, 512
+
+
+def a16(x):
+    return (x + 15) & ~15
+
+
+def old_layouts(H, W, lds_step, epw, n_phys, v):
+    """step_lds_layout, worker_lds_layout and the row tables' planes as the header computed them while a row table was 8 H | 16 H | 4 H without padding."""
+    hilly, dyn, lens, light = bool(v & V_HILLS), bool(v & V_DYN), bool(v & V_LENS), bool(v & V_LIGHT)
+    hb = max(1, min(4, K_RASTER_THREADS // H))
+    tab = a16(28 * H)
+    tabs = hb * tab + 48 if hilly else (K_LENS_PAL_BYTES if lens else 0)
+    dyn_b = K_DYN_BATCH * H * 16 + 128 + a16(K_DYN_TAB_WORDS * 4) + H * 16
+
+    def light_extra(slots):
+        return slots * 32 + (0 if hilly else (K_DYN_BATCH * H * 16 if dyn else ((W // 4 + 126) // 64) * H * 16))
+
+    rows = max(n_phys, 1) + 1
+    cam = lds_step
+    prog = cam + rows * epw * 16
+    pitch = prog + epw * 4 + 16
+    hill = a16(pitch + rows * epw * 4)
+    lightoff = a16(hill + tabs)
+    end = pitch
+    if hilly or lens or light:
+        end = hill + tabs
+    if light:
+        end = lightoff + light_extra(epw)
+    dynoff = a16(end)
+    step = dict(cam=cam, prog=prog, pitch=pitch, hill=hill, light=lightoff, lit=lightoff + epw * 32, dyn=dynoff, total=dynoff + dyn_b if dyn else end)
+    ctl = a16(lds_step)
+    slot = a16(64 + epw * 8)
+    end = ctl + slot + K_CAM_DEPTH * epw * K_SLOT_WORDS * 4 + epw * 64 + 16
+    wdyn = a16(end)
+    if dyn:
+        end = wdyn + dyn_b
+    whill = a16(end)
+    if hilly or lens:
+        end = whill + tabs
+    wlight = a16(whill + tabs)
+    worker = dict(ctl=ctl, slots=ctl + slot, dyn=wdyn, hill=whill, light=wlight, lit=wlight + K_CAM_DEPTH * epw * 32,
+                  total=wlight + light_extra(K_CAM_DEPTH * epw) if light else end)
+    tables = {(k, name): (base + k * tab, base + k * tab + 8 * H, base + k * tab + 24 * H, base + (k + 1) * tab)
+              for k in range(hb) for name, base in (("step", hill), ("worker", whill))} if hilly else {}
+    return step, worker, tables, hb
+
+
+@pytest.mark.parametrize("W,lds_step,epw,n_phys", [(160, 142240, 1, 1), (8, 117616, 5, 3), (12, 146656, 2, 16), (520, 114880, 3, 1), (2048, 159824, 64, 2)])
+def test_lds_regions_and_row_table_planes_are_aligned(plan_driver, W, lds_step, epw, n_phys):
+    """For H = 2..600 and every built variant, both kernels' layouts and each of the hill_batch(H) row tables.  What the kernels access 16 bytes at a
+    time starts on a multiple of 16: the camera rows (float4), the tables' region, each row table and its palette plane (hill_row_build stores uint4,
+    the row loops load them), the lighting parameters and the lit palettes behind them, the dynamic filter's region, the worker's control block and its
+    hand-off slots (float4 camera parameters, 80 bytes each).  The rowtab plane (float2) needs 8, the depth plane, prog and pitch 4.  Planes and tables
+    lie in order without overlap inside their region.  For even H every value is what the unpadded layout gave."""
+    rows = run_plan(plan_driver, "lds", W, lds_step, epw, n_phys)
+    n_rows = {"step": 0, "worker": 0, "table": 0}
+    seen_odd_hilly = False
+    got = {}
+    for r in rows:
+        got.setdefault((int(r[1]), int(r[2])), []).append(r)
+    assert sorted(got) == [(H, v) for H in range(2, 601) for v in range(32) if built(v)]
+    for (H, v), group in got.items():
+        step_old, worker_old, tables_old, hb = old_layouts(H, W, lds_step, epw, n_phys, v)
+        tables = {}
+        for r in group:
+            tag, vals = r[0], r[3:]
+            if tag == "step":
+                step = dict(zip(("cam", "prog", "pitch", "hill", "light", "lit", "dyn", "total"), map(int, vals)))
+            elif tag == "worker":
+                worker = dict(zip(("ctl", "slots", "dyn", "hill", "light", "lit", "total"), map(int, vals)))
+            elif tag == "sizes":
+                tabs_b, light_b, light_ring_b, dyn_b = map(int, vals)
+            elif tag == "table":
+                tables[(int(vals[0]), vals[1])] = tuple(int(x) for x in vals[2:])
+            else:
+                assert tag == "hbar" and int(vals[0]) == hb
+                hbar = (int(vals[1]), int(vals[2]))
+        for name in ("cam", "hill", "light", "lit", "dyn"):
+            assert step[name] % 16 == 0, (H, v, name, step)
+        for name in ("ctl", "slots", "dyn", "hill", "light", "lit"):
+            assert worker[name] % 16 == 0, (H, v, name, worker)
+        assert step["prog"] % 4 == 0 and step["pitch"] % 4 == 0 and dyn_b % 16 == 0
+        assert lds_step == step["cam"] < step["prog"] < step["pitch"] <= step["hill"] <= step["light"] <= step["lit"] and step["hill"] + tabs_b <= step["light"]
+        assert worker["ctl"] < worker["slots"] < worker["dyn"] <= worker["hill"] <= worker["light"] <= worker["lit"] and worker["hill"] + tabs_b <= worker["light"]
+        if v & V_LIGHT:
+            assert step["light"] + light_b <= step["dyn"] and step["light"] + light_b <= step["total"] and worker["light"] + light_ring_b == worker["total"]
+        if v & V_DYN:
+            assert step["dyn"] + dyn_b == step["total"] and worker["dyn"] + dyn_b <= worker["hill"]
+        assert set(tables) == ({(k, name) for k in range(hb) for name in ("step", "worker")} if v & V_HILLS else set())
+        for name, base, bar in (("step", step["hill"], 0), ("worker", worker["hill"], 1)):
+            at = base
+            for k in range(hb if v & V_HILLS else 0):
+                tab, pal, dep, end = tables[(k, name)]
+                assert tab == at and tab % 16 == 0 and pal % 16 == 0 and dep % 4 == 0, (H, v, k, name, tables[(k, name)])
+                assert tab + 8 * H <= pal and pal + 16 * H == dep and dep + 4 * H <= end and end % 16 == 0, (H, v, k, name, tables[(k, name)])
+                at = end
+                n_rows["table"] += 1
+                seen_odd_hilly |= H % 2 == 1
+            if v & V_HILLS:
+                assert hbar[bar] == at and at + 48 == base + tabs_b               # the barrier counter and the first-ground rows behind the last table
+        if H % 2 == 0:
+            assert (step, worker, tables) == (step_old, worker_old, tables_old), (H, v)
+        n_rows["step"] += 1; n_rows["worker"] += 1
+    assert n_rows["step"] == n_rows["worker"] == 599 * 14 and n_rows["table"] > 0 and seen_odd_hilly

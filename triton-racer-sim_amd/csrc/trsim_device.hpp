@@ -651,7 +651,7 @@ __device__ __forceinline__ void raster_ground_rows(const RParams& p, const Raste
 // ---- tracks with elevation (include/trsim_spec.h, "tracks with elevation") ------------------------------------------------------
 // On a hilly track a frame's row tables depend on the env and the step: the view pitch P = pitch + dpitch[nearest track point] (the slope ahead against
 // the slope here) comes from the physics wave with the camera parameters, and the raster team evaluates the rows into tables of its own in LDS —
-// float2 rowtab[H] | uint32 palette[H][4] | float depth[H], the layout of the host's tables, so the row loops above only get another base
+// float2 rowtab[H] | uint32 palette[H][4] (16-aligned: hill_table_pal_off) | float depth[H], the planes of the host's tables, so the row loops above only get another base
 // (raster_use_table).  One thread computes one row: binary32, the spec's operation order (no contraction: the kernels are built with
 // -ffp-contract=off; the division is IEEE).  The envs of a workgroup go through in BATCHES of hill_batch(H) (as many whole tables as the 512 raster
 // threads fill in one pass, at most 4): team barrier (the previous batch's tables have been read by every wave) - build - team barrier - shade the
@@ -735,8 +735,8 @@ __device__ __forceinline__ float hill_row_build(const RParams& p, unsigned char*
     }
     unsigned char* const tab = lds + tab_off;
     reinterpret_cast<f2v*>(tab)[v] = f2v{lz, kk};
-    reinterpret_cast<u4v*>(tab + 8 * p.H)[v] = u4v{c0, c1, c2, c3};
-    reinterpret_cast<float*>(tab + 24 * p.H)[v] = dep;
+    reinterpret_cast<u4v*>(tab + trsim::hill_table_pal_off(p.H))[v] = u4v{c0, c1, c2, c3};
+    reinterpret_cast<float*>(tab + trsim::hill_table_depth_off(p.H))[v] = dep;
     return kk;
 }
 
@@ -745,8 +745,8 @@ __device__ __forceinline__ RasterThread raster_use_table(const RasterThread& t, 
 {
     RasterThread r = t;
     r.lrow = reinterpret_cast<const f2v*>(lds + tab_off);
-    r.pal_off = tab_off + 8u * (unsigned)H;
-    r.lrowdepth = reinterpret_cast<const float*>(lds + tab_off + 24u * (unsigned)H);
+    r.pal_off = tab_off + (unsigned)trsim::hill_table_pal_off(H);
+    r.lrowdepth = reinterpret_cast<const float*>(lds + tab_off + (unsigned)trsim::hill_table_depth_off(H));
     return r;
 }
 

@@ -149,7 +149,7 @@ inline FParams fparams_of(const trs_env* e, int lds_off)
         f.hi[k] = pack_hsv(c.hsv_hi[k]);
         f.dst_ch[k] = c.dst_channel[k];
     }
-    f.w0 = std::min(40, e->H); f.w1 = std::min(119, e->H);              // img[40:119] (img_preprocessing.py:88)
+    f.w0 = dyn_window_lo(e->H); f.w1 = dyn_window_hi(e->H);             // img[40:119] (img_preprocessing.py:88)
     f.tabs = e->dyn_tab.get();
     f.lds_off = lds_off;
     return f;

@@ -815,7 +815,7 @@ int create_impl(const trs_config* cfg, int device, trs_env* e)
     k.cam_fwd = cfg->cam_fwd; k.auto_reset = cfg->auto_reset; k.seed = cfg->seed;
     if (r.gpr > kBlock) return fail(TRS_ERR_LIMIT, "img_w too large: more 4-pixel groups per row than threads per workgroup");
     if (r.gpr > kRasterThreads) return fail(TRS_ERR_LIMIT, "img_w too large: more 4-pixel groups per row than raster threads");
-    r.rows_per_pass = kRasterThreads / r.gpr;   // raster threads beyond rows_per_pass * gpr idle (32 of 512 at W = 160)
+    r.rows_per_pass = trsim::raster_rows_per_pass(r.gpr);   // raster threads beyond rows_per_pass * gpr idle (32 of 512 at W = 160)
     HIPCHK(e->fault.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));   // kernels report a layout fault here (checked at every synchronisation)
     *e->fault.get() = 0ull;
     k.fault = e->fault.get(); r.fault = e->fault.get();

@@ -24,6 +24,13 @@ constexpr int kSlotWords = 20;              // resident worker, one hand-off slo
 constexpr int kLensPalBytes = 513 * 16;
 constexpr int kDynTabWords = 512 + 768 + 4 + 256;   // ... | cnt[256]: the class counts of a row's 4-pixel pack (n0 | n1 << 8 | n2 << 16 | n3 << 24; round 4, see raster_dyn_batch phase A)
 
+// A raster thread owns one 4-pixel column group (gpr = W / 4 of them per row) of every rows_per_pass-th row: the threads beyond rows_per_pass * gpr idle
+// (32 of 512 at W = 160), and a frame takes ceil(H / rows_per_pass) passes, the last of them ragged where H is no multiple.
+TRS_HD inline int raster_rows_per_pass(int gpr) { return kRasterThreads / (gpr > 0 ? gpr : 1); }
+// the dynamic-brightness filter's brightness window: image rows [lo, hi) = img[40:119] (img_preprocessing.py:88), cut to the frame; empty for H <= 40
+TRS_HD inline int dyn_window_lo(int H) { return H < 40 ? H : 40; }
+TRS_HD inline int dyn_window_hi(int H) { return H < 119 ? H : 119; }
+
 // Which instantiation of trs_step_kernel / trs_worker_kernel <DEPTH, DYN, HILLS, LENS, LIGHT> renders: one bit per template flag (variant_of in
 // trsim_env.hpp).  14 of the 32 are built, DEPTH x {plain, DYN, HILLS, LENS, LIGHT, LIGHT + HILLS, LIGHT + DYN}: the setters refuse the others first
 // (variant_clash).
@@ -71,7 +78,12 @@ inline const char* variant_refusal(Variant add, Variant set)
 // tracks with elevation: the batch's row tables (trsim_device.hpp, hill_batch_build)
 constexpr int kHillRowBytes = 28;
 constexpr int kHillBatchMax = 4;
-TRS_HD inline int hill_table_bytes(int H) { return (kHillRowBytes * H + 15) & ~15; }
+// One row table: float2 rowtab[H] | (16-aligned) uint32 palette[H][4] | float depth[H].  The palette plane is written and read 16 bytes at a time, so it starts
+// on a multiple of 16 for every H: behind an odd H's rowtab come 8 bytes of padding (an even H has none: 8 H | 16 H | 4 H = kHillRowBytes * H as before).
+// hill_row_build, raster_use_table and hill_table_bytes all take the plane offsets from here.
+TRS_HD inline int hill_table_pal_off(int H) { return (8 * H + 15) & ~15; }
+TRS_HD inline int hill_table_depth_off(int H) { return hill_table_pal_off(H) + 16 * H; }
+TRS_HD inline int hill_table_bytes(int H) { return (hill_table_depth_off(H) + 4 * H + 15) & ~15; }
 TRS_HD inline int hill_batch(int H) { const int b = kRasterThreads / (H > 0 ? H : 1); return b < 1 ? 1 : (b > kHillBatchMax ? kHillBatchMax : b); }
 TRS_HD inline int hill_lds_bytes(int H) { return hill_batch(H) * hill_table_bytes(H) + 48; }   // the batch's tables + the team-barrier counter (4 B) + 12 B spare + int first_ground[2][4]: an env's first row that sees the ground, by batch parity
 
