@@ -54,18 +54,7 @@ static int decode_file(const uint8_t* bytes, int len, int H, int W, std::vector<
                 }
         if (st == kDecoded) {
             frame->assign((size_t)H * W * 3, 0);
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x) {
-                    const int r0 = y >> 1, r1 = chroma_nb_row(g, y), c0 = x >> 1, c1 = chroma_nb_col(W, x);
-                    int cc[2];
-                    for (int p = 0; p < 2; ++p) {
-                        const uint8_t* pl = cp[p].data();
-                        cc[p] = tri_h(tri_v(pl[r0 * cs + c0], pl[r1 * cs + c0]), tri_v(pl[r0 * cs + c1], pl[r1 * cs + c1]), x);
-                    }
-                    const uint32_t rgb = ycc_to_rgb(yp[(size_t)y * ys + x], cc[0], cc[1]);
-                    uint8_t* px = &(*frame)[((size_t)y * W + x) * 3];
-                    px[0] = (uint8_t)rgb; px[1] = (uint8_t)(rgb >> 8); px[2] = (uint8_t)(rgb >> 16);
-                }
+            planes_to_frame(g, yp.data(), ys, cp[0].data(), cp[1].data(), cs, frame->data());
         }
     }
     std::free(exact);

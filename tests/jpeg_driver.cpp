@@ -69,7 +69,7 @@ int main(int argc, char** argv)
         std::printf("\n");
     } else if (!std::strcmp(cmd, "blocks")) {
         // jpeg_driver blocks <H> <W> <quality> <raw RGB file>: the quantised blocks of every MCU in zig-zag order, one line per block, from the
-        // header's sample rules and arithmetic alone (the dummy blocks' DC is left to the caller: it is a rule about neighbours, checked on the GPU)
+        // header's sample_planes and arithmetic alone (the dummy blocks' DC is left to the caller: it is a rule about neighbours, checked on the GPU)
         const int H = arg(2), W = arg(3);
         const Geometry g = geometry(H, W);
         build_tables(H, W, arg(4), t.get());
@@ -77,27 +77,18 @@ int main(int argc, char** argv)
         FILE* f = argc > 5 ? std::fopen(argv[5], "rb") : nullptr;
         if (!f || std::fread(px.data(), 1, px.size(), f) != px.size()) return 4;
         std::fclose(f);
-        auto at = [&](int r, int c, int ch) { return (int)px[((size_t)r * W + c) * 3 + ch]; };
+        const int ys = 16 * g.mcu_cols, cs = 8 * g.mcu_cols;
+        std::vector<uint8_t> yp((size_t)16 * g.mcu_rows * ys), cp[2];
+        cp[0].resize((size_t)8 * g.mcu_rows * cs); cp[1].resize(cp[0].size());
+        sample_planes(g, px.data(), yp.data(), cp[0].data(), cp[1].data());
         for (int my = 0; my < g.mcu_rows; ++my)
             for (int mx = 0; mx < g.mcu_cols; ++mx)
                 for (int k = 0; k < kBlocksPerMcu; ++k) {
                     int ws[64], out[64];
                     for (int r = 0; r < 8; ++r) {
+                        const uint8_t* sp = k < 4 ? &yp[(size_t)(16 * my + 8 * (k >> 1) + r) * ys + 16 * mx + 8 * (k & 1)] : &cp[k - 4][(size_t)(8 * my + r) * cs + 8 * mx];
                         int d[8];
-                        for (int c = 0; c < 8; ++c) {
-                            int s;
-                            if (k < 4) {
-                                const int sr = y_src_row(g, 16 * my + 8 * (k >> 1) + r), sc = y_src_col(g, 16 * mx + 8 * (k & 1) + c);
-                                s = luma(at(sr, sc, 0), at(sr, sc, 1), at(sr, sc, 2));
-                            } else {
-                                int r0, r1, c0, c1;
-                                c_src_rows(g, 8 * my + r, &r0, &r1);
-                                c_src_cols(g, 8 * mx + c, &c0, &c1);
-                                auto cc = [&](int rr, int cl) { return k == 4 ? chroma_b(at(rr, cl, 0), at(rr, cl, 1), at(rr, cl, 2)) : chroma_r(at(rr, cl, 0), at(rr, cl, 1), at(rr, cl, 2)); };
-                                s = downsample(cc(r0, c0), cc(r0, c1), cc(r1, c0), cc(r1, c1), 8 * mx + c);
-                            }
-                            d[c] = s - 128;
-                        }
+                        for (int c = 0; c < 8; ++c) d[c] = sp[c] - 128;
                         fdct_pass<true>(d);
                         for (int c = 0; c < 8; ++c) ws[r * 8 + c] = d[c];
                     }

@@ -1,7 +1,7 @@
 """trs_decode_jpeg on the GPU against the restatement of include/trsim_spec.h ("tub image (JPEG), decoding") in tests/test_jpeg_decode_cpu.py — which is
 pinned to Pillow's decoder there — byte for byte: five sizes with every entropy path (stuffed 0xFF, ZRL, every AC size, DC + EOB only blocks, 1..7 pad
-bits) and optimised tables, the encoder's slots decoded in place behind both step modes, files at odd offsets with more files than waves, every kind
-of bad file between good ones, the refusals, and the Python layer up to a tub read back.
+bits) and optimised tables, the encoder's slots decoded in place behind both step modes, files at odd offsets with more files than waves, frames that
+start one byte past a dword boundary (the byte stores), every kind of bad file between good ones, the refusals, and the Python layer up to a tub read back.
 Every device buffer of files ends in 4 KiB of sentinel bytes the test owns, and the frames lie between two sentinel frames."""
 import numpy as np
 import pytest
@@ -40,17 +40,23 @@ def pack(files, odd=False):
     return blob, np.asarray(off, np.int64), np.asarray([len(f) for f in files], np.int32)
 
 
-def device_decode(torch, env, blob, off, ln, expect_rc=0):
-    """trs_decode_jpeg from device copies into sentinel-filled frames between two sentinel guard frames -> (uint8[n][H][W][3], int32 status[n])"""
+def device_decode(torch, env, blob, off, ln, expect_rc=0, misalign=0):
+    """trs_decode_jpeg from device copies into sentinel-filled frames between two sentinel guard frames -> (uint8[n][H][W][3], int32 status[n]).
+    misalign: the guard frames start that many bytes past a dword boundary (and so does every frame, where a frame's bytes are a multiple of 4)"""
     n = len(off)
     d_blob, d_off, d_len = (torch.as_tensor(a).cuda() for a in (blob, off, ln))
-    dst = torch.full((n + 2, env.H, env.W, 3), SENTINEL, dtype=torch.uint8, device="cuda")
+    flat = torch.full(((n + 2) * env.H * env.W * 3 + 4,), SENTINEL, dtype=torch.uint8, device="cuda")
+    lead = (misalign - flat.data_ptr()) % 4
+    dst = flat[lead:lead + flat.numel() - 4].view(n + 2, env.H, env.W, 3)
+    assert misalign == 0 or dst[1:].data_ptr() % 4 == misalign
     status = torch.full((n + 2,), -7, dtype=torch.int32, device="cuda")
     torch.cuda.current_stream().synchronize()                        # the env works on its own stream
     env.device_decode_jpeg(d_blob, d_off, d_len, dst[1:], status[1:], n_images=n)
     env.sync()
     out, st = dst.cpu().numpy(), status.cpu().numpy()
     assert (out[0] == SENTINEL).all() and (out[-1] == SENTINEL).all(), "a guard frame was written"
+    edge = flat.cpu().numpy()
+    assert (edge[:lead] == SENTINEL).all() and (edge[lead + dst.numel():] == SENTINEL).all()
     assert st[0] == -7 and st[-1] == -7
     assert np.array_equal(d_blob.cpu().numpy(), blob)
     return out[1:-1], st[1:-1]
@@ -151,7 +157,8 @@ def test_device_round_trip(make_env, resident):
 
 
 def test_odd_offsets_and_more_files_than_waves(make_env):
-    """files at odd byte offsets with odd lengths; n = 1, and one more than twice the waves the library launches: every wave loops"""
+    """files at odd byte offsets with odd lengths; n = 1, two files into frames one byte past a dword boundary (stored by bytes: the same frames as the
+    aligned call's dword stores), and one more than twice the waves the library launches: every wave loops"""
     torch = pytest.importorskip("torch")
     h, w = 24, 40
     env = plain_env(make_env, h, w)
@@ -160,6 +167,10 @@ def test_odd_offsets_and_more_files_than_waves(make_env):
     seven = [f if len(f) % 2 else f + b"\x00" for f in seven]        # (a byte behind EOI: the decoder stops at the last MCU)
     frames, status = device_decode(torch, env, *pack(seven[:1], odd=True))
     assert_frames(frames, status, seven[:1], h, w, "one file")
+    aligned, status = device_decode(torch, env, *pack(seven[:2]))
+    shifted, status1 = device_decode(torch, env, *pack(seven[:2]), misalign=1)
+    assert (status == DECODED).all() and (status1 == DECODED).all() and np.array_equal(shifted, aligned)
+    assert_frames(shifted, status1, seven[:2], h, w, "frames one byte past a dword boundary")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     n = 2 * WAVES_PER_WG * WGS_PER_CU * cus + 1
     order = np.arange(n) % len(seven)

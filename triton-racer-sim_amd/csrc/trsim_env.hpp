@@ -91,7 +91,7 @@ struct trs_env {
     trsim::DevBuf<uint8_t> jpd_files, jpd_dst; trsim::DevBuf<> jpd_meta;   // trs_decode_jpeg_host: the files, the frames, offsets | lengths | statuses
     // the camera codec (trs_jpeg_roundtrip, trs_set_camera_codec; include/trsim_spec.h, "camera codec (JPEG round trip)")
     int codec_quality = 0;               // trs_set_camera_codec: trs_step_pilot feeds the pilot codec(frame, codec_quality); 0: off
-    trsim::DevBuf<int32_t> jpc_steps; int jpc_quality = 0;   // device copy of jpeg::codec_steps (trsim_jpeg_codec.hpp) for jpc_quality; 0: none yet
+    trsim::DevBuf<int32_t> jpc_steps; int jpc_quality = 0;   // device copy of jpeg::quant_steps (trsim_jpeg_tables.hpp) for jpc_quality; 0: none yet
     trsim::DevBuf<uint8_t> jpc_dst;      // the handle's codec buffer: n_envs frames (d_dst NULL, and the pre-pass of trs_step_pilot)
     trsim::DevBuf<uint8_t> jpc_in, jpc_out;   // trs_jpeg_roundtrip_host: the frames up and down
     uint64_t d2h_bytes = 0, h2d_bytes = 0;                  // trs_counters: what the library itself copied

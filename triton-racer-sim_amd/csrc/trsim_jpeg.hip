@@ -1,6 +1,7 @@
 // trsim_jpeg.hip — the tub image encoder: uint8[n][H][W][3] frames on the device -> baseline JPEG files (quality q, 4:2:0, the standard's Huffman
 // tables), byte for byte what include/trsim_spec.h ("tub image (JPEG)") defines.  Every table and every arithmetic rule comes from
-// trsim_jpeg_tables.hpp; this file holds the data movement: trs_jpeg_kernel (frames -> one slot of `cap` bytes per frame + its length) and
+// trsim_jpeg_tables.hpp, the stage from raw rows to sample planes from trsim_jpeg_device.hpp; this file holds the rest of the data movement:
+// trs_jpeg_kernel (frames -> one slot of `cap` bytes per frame + its length) and
 // trs_jpeg_pack_kernel (slots -> the files back to back + their offsets, for the one device-to-host copy of trs_encode_jpeg_host).
 #include <hip/hip_runtime.h>
 
@@ -13,7 +14,8 @@
 #include "../../include/trsim.h"
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
-#include "trsim_jpeg_tables.hpp"
+#include "trsim_jpeg_device.hpp"
+#include "trsim_jpeg_host.hpp"
 
 namespace {
 namespace jpeg = trsim::jpeg;
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(jpeg::kThreads) void trs_jpeg_kernel(JpegParams p)
     uint32_t* ws = reinterpret_cast<uint32_t*>(jsmem + p.lds.off_ws);    // raw rows, then int32[nb][8][8] between the DCT passes, then the bit stream
     int16_t* coef = reinterpret_cast<int16_t*>(jsmem + p.lds.off_coef);  // [nb][kCoefStride], zig-zag order
     int* scan = reinterpret_cast<int*>(jsmem + p.lds.off_scan);
-    const int ws_dwords = nb * 64 + 4, ystride = 16 * mw, cstride = 8 * mw, row_bytes = p.W * 3, row_dw = row_bytes / 4;
+    const int ws_dwords = nb * 64 + 4, ystride = 16 * mw, cstride = 8 * mw, row_bytes = p.W * 3;
     {
         const uint32_t* s = reinterpret_cast<const uint32_t*>(p.tab);
         uint32_t* d = reinterpret_cast<uint32_t*>(T);
@@ -83,35 +85,7 @@ __global__ __launch_bounds__(jpeg::kThreads) void trs_jpeg_kernel(JpegParams p)
         int out = jpeg::kHeaderBytes, carry_bits = 0, dcp0 = 0, dcp1 = 0, dcp2 = 0;
         uint32_t carry_byte = 0;
         for (int my = 0; my < g.mcu_rows; ++my) {
-            const int r_lo = 16 * my, nrows = min(16, p.H - r_lo);
-            {   // the MCU row's image rows, as they lie in memory
-                const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src + (size_t)r_lo * row_bytes);
-                for (int i = tid; i < nrows * row_dw; i += jpeg::kThreads) ws[i] = s4[i];
-            }
-            __syncthreads();
-            {   // colour and downsampling, one 2 x 2 quad of the padded planes per thread and turn
-                const uint8_t* raw = reinterpret_cast<const uint8_t*>(ws);
-                for (int q = tid; q < 8 * cstride; q += jpeg::kThreads) {
-                    const int qr = q / cstride, qc = q - qr * cstride;
-                    for (int dy = 0; dy < 2; ++dy)
-                        for (int dx = 0; dx < 2; ++dx) {
-                            const uint8_t* px = raw + (jpeg::y_src_row(g, r_lo + 2 * qr + dy) - r_lo) * row_bytes + jpeg::y_src_col(g, 2 * qc + dx) * 3;
-                            ys[(2 * qr + dy) * ystride + 2 * qc + dx] = (uint8_t)jpeg::luma(px[0], px[1], px[2]);
-                        }
-                    int r0, r1, c0, c1;
-                    jpeg::c_src_rows(g, 8 * my + qr, &r0, &r1);
-                    jpeg::c_src_cols(g, qc, &c0, &c1);
-                    const uint8_t* a = raw + (r0 - r_lo) * row_bytes + c0 * 3;
-                    const uint8_t* b = raw + (r0 - r_lo) * row_bytes + c1 * 3;
-                    const uint8_t* c = raw + (r1 - r_lo) * row_bytes + c0 * 3;
-                    const uint8_t* d = raw + (r1 - r_lo) * row_bytes + c1 * 3;
-                    cs[qr * cstride + qc] = (uint8_t)jpeg::downsample(jpeg::chroma_b(a[0], a[1], a[2]), jpeg::chroma_b(b[0], b[1], b[2]),
-                                                                      jpeg::chroma_b(c[0], c[1], c[2]), jpeg::chroma_b(d[0], d[1], d[2]), qc);
-                    cs[(8 + qr) * cstride + qc] = (uint8_t)jpeg::downsample(jpeg::chroma_r(a[0], a[1], a[2]), jpeg::chroma_r(b[0], b[1], b[2]),
-                                                                            jpeg::chroma_r(c[0], c[1], c[2]), jpeg::chroma_r(d[0], d[1], d[2]), qc);
-                }
-            }
-            __syncthreads();
+            jpeg::sample_stripe<jpeg::kThreads>(g, my, src, ws, ys, cs);   // (the raw rows alias the workspace)
             for (int t = tid; t < nb * 8; t += jpeg::kThreads) {          // DCT over the rows of every block
                 const int b = t >> 3, r = t & 7, mx = b / jpeg::kBlocksPerMcu, k = b - mx * jpeg::kBlocksPerMcu;
                 const uint8_t* sp = k < 4 ? ys + ((k >> 1) * 8 + r) * ystride + mx * 16 + (k & 1) * 8 : cs + ((k - 4) * 8 + r) * cstride + mx * 8;
@@ -257,9 +231,8 @@ __global__ __launch_bounds__(256) void trs_jpeg_pack_kernel(const uint8_t* slots
 
 int check_args(trs_env* e, int n_images, int quality, int cap)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    if (quality < 1 || quality > 100) return trs_internal_fail(TRS_ERR_ARG, "quality must be in [1, 100]");
-    if (n_images < 1) return trs_internal_fail(TRS_ERR_ARG, "n_images < 1");
+    const int rc = jpeg::check_call(e, n_images, quality);
+    if (rc) return rc;
     if (cap < jpeg::kHeaderBytes + 2) return trs_internal_fail(TRS_ERR_ARG, "cap is below the header's " + std::to_string(jpeg::kHeaderBytes) + " bytes plus the end marker's 2");
     return TRS_OK;
 }
@@ -283,9 +256,8 @@ int ensure_tables(trs_env* e, int quality)
 
 TRS_EXPORT int trs_jpeg_header_bytes(trs_env* e, int quality)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    if (quality < 1 || quality > 100) return trs_internal_fail(TRS_ERR_ARG, "quality must be in [1, 100]");
-    return jpeg::kHeaderBytes;
+    const int rc = jpeg::check_call(e, 1, quality);       // (the header's length does not depend on the number of images)
+    return rc ? rc : jpeg::kHeaderBytes;
 }
 
 TRS_EXPORT int trs_encode_jpeg(trs_env* e, const uint8_t* d_src, int n_images, int quality, uint8_t* d_dst, int cap, int32_t* d_len)
@@ -297,11 +269,8 @@ TRS_EXPORT int trs_encode_jpeg(trs_env* e, const uint8_t* d_src, int n_images, i
     HIPCHK(hipSetDevice(e->device));
     rc = trsim::quiesce_handle(e);
     if (rc) return rc;
-    if (!d_src) {
-        d_src = trs_internal_latest_frame(e);
-        if (!d_src) return trs_internal_fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0): there is no latest frame to encode");
-        if (n_images != e->n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs n_images == n_envs");
-    }
+    rc = jpeg::latest_frame_source(e, n_images, "to encode", &d_src);
+    if (rc) return rc;
     const jpeg::Geometry g = jpeg::geometry(e->H, e->W);
     const jpeg::StripeLds lds = jpeg::stripe_lds(e->W);
     if (jpeg::blocks_per_stripe(g) > jpeg::kThreads || lds.total > jpeg::kMaxLdsBytes || e->H > 65535 || e->W > 65535)
@@ -335,8 +304,7 @@ TRS_EXPORT int trs_encode_jpeg_host(trs_env* e, const uint8_t* d_src, int n_imag
         if (rh == hipSuccess) rh = e->jpg_len.reserve(n * sizeof(int32_t));
         if (rh == hipSuccess) rh = e->jpg_off.reserve(pin_bytes);
         if (rh == hipSuccess) rh = e->jpg_pin.reserve(pin_bytes);
-        if (rh != hipSuccess)
-            return trs_internal_fail(rh == hipErrorOutOfMemory ? TRS_ERR_NOMEM : TRS_ERR_DEVICE, "no memory for " + std::to_string(2 * slot_bytes) + " bytes of encoder scratch");
+        if (rh != hipSuccess) return jpeg::no_memory(rh, 2 * slot_bytes, "encoder scratch");
     }
     rc = trs_encode_jpeg(e, d_src, n_images, quality, e->jpg_slots.get(), cap, e->jpg_len.get());
     if (rc) return rc;

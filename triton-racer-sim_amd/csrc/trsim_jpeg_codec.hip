@@ -1,7 +1,8 @@
 // trsim_jpeg_codec.hip — the camera codec: uint8[n][H][W][3] frames on the device -> the frames a JPEG save and open would give back, byte for byte
 // what include/trsim_spec.h ("camera codec (JPEG round trip)") defines: decode(encode(frame, q)) without a file in between.  Every rule comes from
-// trsim_jpeg_tables.hpp and trsim_jpeg_decode.hpp through the block steps of trsim_jpeg_codec.hpp; this file holds the data movement of
-// trs_jpeg_codec_kernel, the entry points, and the pre-pass trs_step_pilot runs while trs_set_camera_codec is set.
+// trsim_jpeg_tables.hpp and trsim_jpeg_decode.hpp through the block steps of trsim_jpeg_codec.hpp, the first and the last stage from trsim_jpeg_device.hpp
+// (shared with the encoder and with the decoder); this file holds the data movement of trs_jpeg_codec_kernel between them, the entry points, and the
+// pre-pass trs_step_pilot runs while trs_set_camera_codec is set.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,59 +13,22 @@
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
 #include "trsim_jpeg_codec.hpp"
+#include "trsim_jpeg_device.hpp"
+#include "trsim_jpeg_host.hpp"
 
 namespace {
 namespace jpeg = trsim::jpeg;
+using jpeg::wave_sync;
 
 struct CodecParams {
     const uint8_t* src;          // uint8[n][H][W][3], 4-byte aligned, W % 4 == 0
     uint8_t* dst;                // the same shape, no byte shared with src
-    const int32_t* qv;           // codec_steps: int32[2][64]
+    const int32_t* qv;           // quant_steps: int32[2][64]
     int n, H, W;
     jpeg::CodecLds lds;
 };
 
 extern __shared__ __attribute__((aligned(16))) unsigned char csmem[];
-
-// what one lane of the wave wrote to LDS is visible to the others behind this
-__device__ inline void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// image rows [16 my, 16 my + 16) of the frame from the Y samples of MCU row my and the chroma ring: 4 pixels (3 dwords) per thread and turn
-__device__ void output_mcu_row(const CodecParams& p, const jpeg::Geometry& g, int my, const uint8_t* yout, const uint8_t* cring, uint8_t* dst)
-{
-    const int mw = g.mcu_cols, ys = 16 * mw, cs = 8 * mw, units = p.W >> 2, rows = min(16, p.H - 16 * my);
-    const uint8_t* yrow0 = yout + (my & 1) * 256 * mw;
-    auto crow = [&](int plane, int r) { return cring + ((r >> 3) % jpeg::kChromaRing) * 128 * mw + plane * 64 * mw + (r & 7) * cs; };
-    for (int t = threadIdx.x; t < rows * units; t += jpeg::kCodecThreads) {
-        const int ry = t / units, u = t - ry * units, y = 16 * my + ry, x0 = 4 * u;
-        const int r0 = y >> 1, r1 = jpeg::chroma_nb_row(g, y);
-        // the vertical sums of the chroma columns 2u - 1 .. 2u + 2 (clamped to the plane), both planes
-        int s[2][4];
-        for (int pl = 0; pl < 2; ++pl) {
-            const uint8_t* a = crow(pl, r0);
-            const uint8_t* b = crow(pl, r1);
-            for (int j = 0; j < 4; ++j) {
-                const int c = min(max(2 * u - 1 + j, 0), jpeg::chroma_cols(p.W) - 1);
-                s[pl][j] = jpeg::tri_v(a[c], b[c]);
-            }
-        }
-        const uint32_t y4 = *reinterpret_cast<const uint32_t*>(yrow0 + ry * ys + x0);
-        uint32_t px[4];
-        for (int k = 0; k < 4; ++k) {
-            const int x = x0 + k, own = 1 + (k >> 1), nb = (k & 1) ? own + 1 : own - 1;      // (s[][0] and s[][3] are the clamped neighbours)
-            px[k] = jpeg::ycc_to_rgb((int)((y4 >> (8 * k)) & 255u), jpeg::tri_h(s[0][own], s[0][nb], x), jpeg::tri_h(s[1][own], s[1][nb], x));
-        }
-        uint32_t* o4 = reinterpret_cast<uint32_t*>(dst + ((size_t)y * p.W + x0) * 3);
-        o4[0] = px[0] | px[1] << 24;
-        o4[1] = px[1] >> 8 | px[2] << 16;
-        o4[2] = px[2] >> 16 | px[3] << 8;
-    }
-}
 
 // One workgroup per frame at a time, one MCU row (16 image rows) at a time:
 //   raw RGB rows -> LDS | colour + 2x2 downsampling -> sample planes | per wave, 8 blocks at a time: rows in, columns (quantiser and dequantiser), rows out
@@ -80,43 +44,14 @@ __global__ __launch_bounds__(jpeg::kCodecThreads) void trs_jpeg_codec_kernel(Cod
     uint8_t* ys = csmem + p.lds.off_y;                                      // [16][16 mw]
     uint8_t* cs = csmem + p.lds.off_c;                                      // [2][8][8 mw]
     int32_t* w = reinterpret_cast<int32_t*>(csmem + p.lds.off_ws) + (wave * 8 + (lane >> 3)) * jpeg::kWsBlockStride;   // this lane's block of the wave's 8
-    uint8_t* yout = csmem + p.lds.off_yout;                                 // [2][16][16 mw]
-    uint8_t* cring = csmem + p.lds.off_cring;                               // [kChromaRing][Cb | Cr][8][8 mw]
-    const int ystride = 16 * mw, cstride = 8 * mw, row_bytes = p.W * 3, row_dw = row_bytes / 4, j = lane & 7;
+    const jpeg::SampleBuffers sb{csmem + p.lds.off_yout, csmem + p.lds.off_cring, mw};
+    const int ystride = 16 * mw, cstride = 8 * mw, row_bytes = p.W * 3, j = lane & 7;
     if (tid < 128) Q[tid] = p.qv[tid];
     for (int f = blockIdx.x; f < p.n; f += gridDim.x) {
         const uint8_t* src = p.src + (size_t)f * p.H * row_bytes;
         uint8_t* dst = p.dst + (size_t)f * p.H * row_bytes;
         for (int my = 0; my < g.mcu_rows; ++my) {
-            const int r_lo = 16 * my, nrows = min(16, p.H - r_lo);
-            {
-                const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src + (size_t)r_lo * row_bytes);
-                for (int i = tid; i < nrows * row_dw; i += jpeg::kCodecThreads) raw4[i] = s4[i];
-            }
-            __syncthreads();
-            {   // colour and downsampling, one 2 x 2 quad of the padded planes per thread and turn
-                const uint8_t* raw = reinterpret_cast<const uint8_t*>(raw4);
-                for (int q = tid; q < 8 * cstride; q += jpeg::kCodecThreads) {
-                    const int qr = q / cstride, qc = q - qr * cstride;
-                    for (int dy = 0; dy < 2; ++dy)
-                        for (int dx = 0; dx < 2; ++dx) {
-                            const uint8_t* px = raw + (jpeg::y_src_row(g, r_lo + 2 * qr + dy) - r_lo) * row_bytes + jpeg::y_src_col(g, 2 * qc + dx) * 3;
-                            ys[(2 * qr + dy) * ystride + 2 * qc + dx] = (uint8_t)jpeg::luma(px[0], px[1], px[2]);
-                        }
-                    int r0, r1, c0, c1;
-                    jpeg::c_src_rows(g, 8 * my + qr, &r0, &r1);
-                    jpeg::c_src_cols(g, qc, &c0, &c1);
-                    const uint8_t* a = raw + (r0 - r_lo) * row_bytes + c0 * 3;
-                    const uint8_t* b = raw + (r0 - r_lo) * row_bytes + c1 * 3;
-                    const uint8_t* c = raw + (r1 - r_lo) * row_bytes + c0 * 3;
-                    const uint8_t* d = raw + (r1 - r_lo) * row_bytes + c1 * 3;
-                    cs[qr * cstride + qc] = (uint8_t)jpeg::downsample(jpeg::chroma_b(a[0], a[1], a[2]), jpeg::chroma_b(b[0], b[1], b[2]),
-                                                                      jpeg::chroma_b(c[0], c[1], c[2]), jpeg::chroma_b(d[0], d[1], d[2]), qc);
-                    cs[(8 + qr) * cstride + qc] = (uint8_t)jpeg::downsample(jpeg::chroma_r(a[0], a[1], a[2]), jpeg::chroma_r(b[0], b[1], b[2]),
-                                                                            jpeg::chroma_r(c[0], c[1], c[2]), jpeg::chroma_r(d[0], d[1], d[2]), qc);
-                }
-            }
-            __syncthreads();
+            jpeg::sample_stripe<jpeg::kCodecThreads>(g, my, src, raw4, ys, cs);
             for (int b0 = wave * 8; b0 < nb; b0 += (jpeg::kCodecThreads / 64) * 8) {      // 8 blocks per wave and turn: a row, a column, a row per lane
                 const int b = b0 + (lane >> 3), mx = b / jpeg::kBlocksPerMcu, k = b - mx * jpeg::kBlocksPerMcu;
                 const bool live = b < nb && !(k < 4 && jpeg::y_dummy(g, my, mx, k));
@@ -146,27 +81,24 @@ __global__ __launch_bounds__(jpeg::kCodecThreads) void trs_jpeg_codec_kernel(Cod
                         lo4 |= (uint32_t)d[c] << (8 * c);
                         hi4 |= (uint32_t)d[c + 4] << (8 * c);
                     }
-                    uint8_t* out = k < 4 ? yout + (my & 1) * 256 * mw + (8 * (k >> 1) + j) * ystride + 16 * mx + 8 * (k & 1)
-                                         : cring + (my % jpeg::kChromaRing) * 128 * mw + (k - 4) * 64 * mw + j * cstride + 8 * mx;
-                    reinterpret_cast<uint32_t*>(out)[0] = lo4;
-                    reinterpret_cast<uint32_t*>(out)[1] = hi4;
+                    sb.store_block_row(my, mx, k, j, lo4, hi4);
                 }
                 wave_sync();                                                                  // the wave's intermediates are free for its next 8 blocks
             }
             __syncthreads();
-            if (my > 0) output_mcu_row(p, g, my - 1, yout, cring, dst);
+            if (my > 0) jpeg::output_mcu_row<jpeg::kCodecThreads>(g, my - 1, sb, dst, tid, true);   // (dwords: the host refuses a d_dst that is not 4-byte aligned, and img_w % 4 == 0)
             // (what the next MCU row overwrites of the samples read here lies behind its two barriers)
         }
-        output_mcu_row(p, g, g.mcu_rows - 1, yout, cring, dst);
+        jpeg::output_mcu_row<jpeg::kCodecThreads>(g, g.mcu_rows - 1, sb, dst, tid, true);
     }
 }
 
-// the device copy of codec_steps(quality): rebuilt when the quality changes (the stream is drained first: a kernel in flight reads the old copy)
+// the device copy of quant_steps(quality): rebuilt when the quality changes (the stream is drained first: a kernel in flight reads the old copy)
 int ensure_steps(trs_env* e, int quality)
 {
     if (e->jpc_quality == quality && e->jpc_steps.get()) return TRS_OK;
-    int32_t qv[128];
-    jpeg::codec_steps(quality, qv);
+    int32_t qv[2][64];
+    jpeg::quant_steps(quality, qv);
     HIPCHK(hipStreamSynchronize(e->sP));
     e->jpc_quality = 0;
     HIPCHK(e->jpc_steps.reserve(sizeof qv));
@@ -186,34 +118,25 @@ int check_size(const trs_env* e)
                                                     " bytes of LDS allows img_w <= " + std::to_string(jpeg::codec_max_width(jpeg::kMaxLdsBytes)));
     return TRS_OK;
 }
-
-int no_memory(hipError_t rh, size_t bytes)
-{
-    return trs_internal_fail(rh == hipErrorOutOfMemory ? TRS_ERR_NOMEM : TRS_ERR_DEVICE, "no memory for " + std::to_string(bytes) + " bytes of camera codec frames");
-}
 }  // namespace
 
 TRS_EXPORT int trs_jpeg_roundtrip(trs_env* e, const uint8_t* d_src, int n_images, int quality, uint8_t* d_dst, const uint8_t** d_out)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    if (quality < 1 || quality > 100) return trs_internal_fail(TRS_ERR_ARG, "quality must be in [1, 100]");
-    if (n_images < 1) return trs_internal_fail(TRS_ERR_ARG, "n_images < 1");
+    int rc = jpeg::check_call(e, n_images, quality);
+    if (rc) return rc;
     if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 3) return trs_internal_fail(TRS_ERR_ARG, "d_src and d_dst must be 4-byte aligned");
-    int rc = check_size(e);
+    rc = check_size(e);
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device));
     rc = trsim::quiesce_handle(e);
     if (rc) return rc;
-    if (!d_src) {
-        d_src = trs_internal_latest_frame(e);
-        if (!d_src) return trs_internal_fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0): there is no latest frame for the codec");
-        if (n_images != e->n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs n_images == n_envs");
-    }
+    rc = jpeg::latest_frame_source(e, n_images, "for the codec", &d_src);
+    if (rc) return rc;
     const size_t frame_bytes = (size_t)e->H * e->W * 3, bytes = (size_t)n_images * frame_bytes;
     if (!d_dst) {
         if (n_images > e->n) return trs_internal_fail(TRS_ERR_ARG, "own buffer holds n_envs frames");
         const hipError_t rh = e->jpc_dst.reserve((size_t)e->n * frame_bytes);      // (allocated once: the size is fixed)
-        if (rh != hipSuccess) return no_memory(rh, (size_t)e->n * frame_bytes);
+        if (rh != hipSuccess) return jpeg::no_memory(rh, (size_t)e->n * frame_bytes, "camera codec frames");
         d_dst = e->jpc_dst.get();
     }
     if (d_dst < d_src + bytes && d_src < d_dst + bytes)
@@ -234,11 +157,10 @@ TRS_EXPORT int trs_jpeg_roundtrip(trs_env* e, const uint8_t* d_src, int n_images
 
 TRS_EXPORT int trs_jpeg_roundtrip_host(trs_env* e, const uint8_t* h_src, int n_images, int quality, uint8_t* h_dst)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    if (quality < 1 || quality > 100) return trs_internal_fail(TRS_ERR_ARG, "quality must be in [1, 100]");
-    if (n_images < 1) return trs_internal_fail(TRS_ERR_ARG, "n_images < 1");
+    int rc = jpeg::check_call(e, n_images, quality);
+    if (rc) return rc;
     if (!h_dst) return trs_internal_fail(TRS_ERR_ARG, "null destination");
-    int rc = check_size(e);
+    rc = check_size(e);
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device));
     rc = trsim::quiesce_handle(e);
@@ -248,7 +170,7 @@ TRS_EXPORT int trs_jpeg_roundtrip_host(trs_env* e, const uint8_t* h_src, int n_i
         HIPCHK(hipStreamSynchronize(e->sP));                              // what is replaced may still be in use
         hipError_t rh = h_src ? e->jpc_in.reserve(bytes) : hipSuccess;
         if (rh == hipSuccess) rh = e->jpc_out.reserve(bytes);
-        if (rh != hipSuccess) return no_memory(rh, 2 * bytes);
+        if (rh != hipSuccess) return jpeg::no_memory(rh, 2 * bytes, "camera codec frames");
     }
     if (h_src) HIPCHK(hipMemcpyAsync(e->jpc_in.get(), h_src, bytes, hipMemcpyHostToDevice, e->sP));
     rc = trs_jpeg_roundtrip(e, h_src ? e->jpc_in.get() : nullptr, n_images, quality, e->jpc_out.get(), nullptr);
@@ -275,7 +197,7 @@ TRS_EXPORT int trs_set_camera_codec(trs_env* e, int quality)
     if (rc) return rc;
     const size_t bytes = (size_t)e->n * e->H * e->W * 3;
     const hipError_t rh = e->jpc_dst.reserve(bytes);
-    if (rh != hipSuccess) return no_memory(rh, bytes);
+    if (rh != hipSuccess) return jpeg::no_memory(rh, bytes, "camera codec frames");
     rc = ensure_steps(e, quality);
     if (rc) return rc;
     e->codec_quality = quality;

@@ -1,8 +1,9 @@
 // trsim_jpeg_codec.hpp — the camera codec (include/trsim_spec.h, "camera codec (JPEG round trip)"): codec(frame, q) = decode(encode(frame, q)) without
 // the entropy stage between the quantiser and the dequantiser.  Every rule is a function of trsim_jpeg_tables.hpp (colour, edges, downsampling, forward
 // DCT, quantiser) or of trsim_jpeg_decode.hpp (inverse DCT, clamp, triangle upsampling, colour back); what is new here is their composition over one
-// block, a plain host loop over a whole frame (tests/jpeg_codec_driver.cpp drives it under the sanitizers) and the LDS plan of trs_jpeg_codec_kernel
-// (csrc/trsim_jpeg_codec.hip), which takes the block steps from here.
+// block, a whole frame on the host as sample_planes, the blocks, planes_to_frame (tests/jpeg_codec_driver.cpp drives it under the sanitizers) and the
+// LDS plan of trs_jpeg_codec_kernel (csrc/trsim_jpeg_codec.hip), which takes the block steps from here and its first and last stage from
+// trsim_jpeg_device.hpp (sample_stripe, output_mcu_row).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -58,16 +59,6 @@ inline void codec_block(const uint8_t* in, int in_stride, const int32_t* qv, uin
     }
 }
 
-// the quantisation steps << 3 of a quality as the block steps take them: [luminance | chrominance][64], natural order
-inline void codec_steps(int quality, int32_t qv[128])
-{
-    for (int c = 0; c < 2; ++c) {
-        uint8_t q[64];
-        quant_table(quality, c, q);
-        for (int i = 0; i < 64; ++i) qv[c * 64 + i] = (int32_t)q[i] << 3;
-    }
-}
-
 // the triangle filter needs a chroma plane of more than two columns, as the decoder does (parse_header)
 TRS_JPEG_HD bool codec_size_ok(int H, int W) { return H >= 1 && W > 4; }
 
@@ -77,47 +68,22 @@ inline bool codec_frame(int H, int W, int quality, const uint8_t* src, uint8_t* 
     if (!codec_size_ok(H, W) || quality < 1 || quality > 100) return false;
     const Geometry g = geometry(H, W);
     const int ys = 16 * g.mcu_cols, cs = 8 * g.mcu_cols, yr = 16 * g.mcu_rows, cr = 8 * g.mcu_rows;
-    int32_t qv[128];
-    codec_steps(quality, qv);
+    int32_t qv[2][64];
+    quant_steps(quality, qv);
     std::vector<uint8_t> yp((size_t)yr * ys), cp[2], yo((size_t)yr * ys), co[2];
     for (int p = 0; p < 2; ++p) { cp[p].resize((size_t)cr * cs); co[p].resize((size_t)cr * cs); }
-    auto px = [&](int r, int c) { return src + ((size_t)r * W + c) * 3; };
-    for (int r = 0; r < yr; ++r)
-        for (int c = 0; c < ys; ++c) {
-            const uint8_t* s = px(y_src_row(g, r), y_src_col(g, c));
-            yp[(size_t)r * ys + c] = (uint8_t)luma(s[0], s[1], s[2]);
-        }
-    for (int r = 0; r < cr; ++r)
-        for (int c = 0; c < cs; ++c) {
-            int r0, r1, c0, c1;
-            c_src_rows(g, r, &r0, &r1);
-            c_src_cols(g, c, &c0, &c1);
-            const uint8_t *a = px(r0, c0), *b = px(r0, c1), *e = px(r1, c0), *f = px(r1, c1);
-            cp[0][(size_t)r * cs + c] = (uint8_t)downsample(chroma_b(a[0], a[1], a[2]), chroma_b(b[0], b[1], b[2]), chroma_b(e[0], e[1], e[2]), chroma_b(f[0], f[1], f[2]), c);
-            cp[1][(size_t)r * cs + c] = (uint8_t)downsample(chroma_r(a[0], a[1], a[2]), chroma_r(b[0], b[1], b[2]), chroma_r(e[0], e[1], e[2]), chroma_r(f[0], f[1], f[2]), c);
-        }
+    sample_planes(g, src, yp.data(), cp[0].data(), cp[1].data());
     for (int my = 0; my < g.mcu_rows; ++my)
         for (int mx = 0; mx < g.mcu_cols; ++mx) {
             for (int k = 0; k < 4; ++k) {
                 if (y_dummy(g, my, mx, k)) continue;                              // a dummy block holds no image sample: it is never output
                 const size_t at = (size_t)(16 * my + 8 * (k >> 1)) * ys + 16 * mx + 8 * (k & 1);
-                codec_block(&yp[at], ys, qv, &yo[at], ys);
+                codec_block(&yp[at], ys, qv[0], &yo[at], ys);
             }
             const size_t at = (size_t)8 * my * cs + 8 * mx;
-            for (int p = 0; p < 2; ++p) codec_block(&cp[p][at], cs, qv + 64, &co[p][at], cs);
+            for (int p = 0; p < 2; ++p) codec_block(&cp[p][at], cs, qv[1], &co[p][at], cs);
         }
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            const int r0 = y >> 1, r1 = chroma_nb_row(g, y), c0 = x >> 1, c1 = chroma_nb_col(W, x);
-            int cc[2];
-            for (int p = 0; p < 2; ++p) {
-                const uint8_t* pl = co[p].data();
-                cc[p] = tri_h(tri_v(pl[r0 * cs + c0], pl[r1 * cs + c0]), tri_v(pl[r0 * cs + c1], pl[r1 * cs + c1]), x);
-            }
-            const uint32_t rgb = ycc_to_rgb(yo[(size_t)y * ys + x], cc[0], cc[1]);
-            uint8_t* o = dst + ((size_t)y * W + x) * 3;
-            o[0] = (uint8_t)rgb; o[1] = (uint8_t)(rgb >> 8); o[2] = (uint8_t)(rgb >> 16);
-        }
+    planes_to_frame(g, yo.data(), ys, co[0].data(), co[1].data(), cs, dst);
     return true;
 }
 

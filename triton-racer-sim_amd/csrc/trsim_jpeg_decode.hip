@@ -1,6 +1,7 @@
 // trsim_jpeg_decode.hip — the tub image decoder: baseline JPEG files on the device -> uint8[n][H][W][3] frames, byte for byte what include/trsim_spec.h
 // ("tub image (JPEG), decoding") defines, which is what Pillow's decoder gives.  Every rule comes from trsim_jpeg_decode.hpp; this file holds the data
-// movement of trs_jpeg_decode_kernel and the two entry points.
+// movement of trs_jpeg_decode_kernel up to the sample buffers and the two entry points; the buffers' layout and the way from them to the frame are
+// trsim_jpeg_device.hpp's, shared with the camera codec.
 // One wave per file, kDecodeWaves independent waves per workgroup, no workgroup barrier.  A file's Huffman decoding is a serial chain: the wave runs it
 // as wave-uniform code (every lane computes the same values from the same LDS words), so that the 64 lanes are at hand, without a branch, for what is
 // parallel: refilling the window of file bytes, clearing and transforming blocks, upsampling, colour and the stores.
@@ -15,10 +16,12 @@
 #include "../../include/trsim.h"
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
-#include "trsim_jpeg_decode.hpp"
+#include "trsim_jpeg_device.hpp"
+#include "trsim_jpeg_host.hpp"
 
 namespace {
 namespace jpeg = trsim::jpeg;
+using jpeg::wave_sync;
 
 struct DecodeParams {
     const uint8_t* files; const int64_t* off; const int32_t* len;
@@ -28,14 +31,6 @@ struct DecodeParams {
 };
 
 extern __shared__ __attribute__((aligned(16))) unsigned char dsmem[];
-
-// what one lane of the wave wrote to LDS is visible to the others behind this
-__device__ inline void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The file type of the shared rules on the device: kWindowBytes of the file in the wave's LDS, refilled by all lanes when a byte outside it is asked
 // for.  at() must be called by all 64 lanes with the same index.  Global memory is read by aligned dwords that lie wholly inside the file and by bytes
@@ -69,44 +64,6 @@ struct WindowFile {
     }
 };
 
-// image rows [16 my, 16 my + 16) of the frame from the Y samples of MCU row my and the chroma ring: 4 pixels (3 dwords) per lane and turn
-__device__ void output_mcu_row(const DecodeParams& p, const jpeg::Geometry& g, int my, const uint8_t* ybuf, const uint8_t* cring, uint8_t* dst, int lane, bool dwords)
-{
-    const int mw = g.mcu_cols, ys = 16 * mw, cs = 8 * mw, units = (p.W + 3) >> 2, rows = min(16, p.H - 16 * my);
-    const uint8_t* yrow0 = ybuf + (my & 1) * 256 * mw;
-    auto crow = [&](int plane, int r) { return cring + ((r >> 3) % jpeg::kChromaRing) * 128 * mw + plane * 64 * mw + (r & 7) * cs; };
-    for (int t = lane; t < rows * units; t += 64) {
-        const int ry = t / units, u = t - ry * units, y = 16 * my + ry, x0 = 4 * u;
-        const int r0 = y >> 1, r1 = jpeg::chroma_nb_row(g, y);
-        // the vertical sums of the chroma columns 2u - 1 .. 2u + 2 (clamped to the plane), both planes
-        int s[2][4];
-        for (int pl = 0; pl < 2; ++pl) {
-            const uint8_t* a = crow(pl, r0);
-            const uint8_t* b = crow(pl, r1);
-            for (int j = 0; j < 4; ++j) {
-                const int c = min(max(2 * u - 1 + j, 0), jpeg::chroma_cols(p.W) - 1);
-                s[pl][j] = jpeg::tri_v(a[c], b[c]);
-            }
-        }
-        uint32_t px[4];
-        for (int k = 0; k < 4; ++k) {
-            const int x = x0 + k, own = 1 + (k >> 1), nb = (k & 1) ? own + 1 : own - 1;      // (s[][0] and s[][3] are the clamped neighbours)
-            px[k] = jpeg::ycc_to_rgb(yrow0[ry * ys + min(x, ys - 1)], jpeg::tri_h(s[0][own], s[0][nb], x), jpeg::tri_h(s[1][own], s[1][nb], x));
-        }
-        uint8_t* o = dst + ((size_t)y * p.W + x0) * 3;
-        if (dwords && x0 + 4 <= p.W) {
-            uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
-            o4[0] = px[0] | px[1] << 24;
-            o4[1] = px[1] >> 8 | px[2] << 16;
-            o4[2] = px[2] >> 16 | px[3] << 8;
-        } else {
-            for (int k = 0; k < 4 && x0 + k < p.W; ++k) {
-                o[3 * k] = (uint8_t)px[k]; o[3 * k + 1] = (uint8_t)(px[k] >> 8); o[3 * k + 2] = (uint8_t)(px[k] >> 16);
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(64 * jpeg::kDecodeWaves) void trs_jpeg_decode_kernel(DecodeParams p)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -114,10 +71,9 @@ __global__ __launch_bounds__(64 * jpeg::kDecodeWaves) void trs_jpeg_decode_kerne
     jpeg::DecodeTables* T = reinterpret_cast<jpeg::DecodeTables*>(base + p.lds.off_tab);
     int16_t* coef = reinterpret_cast<int16_t*>(base + p.lds.off_coef);
     int32_t* ws = reinterpret_cast<int32_t*>(base + p.lds.off_ws);
-    uint8_t* ybuf = base + p.lds.off_y;                                // [2][16][16 mw]
-    uint8_t* cring = base + p.lds.off_c;                               // [kChromaRing][Cb | Cr][8][8 mw]
     const jpeg::Geometry g = jpeg::geometry(p.H, p.W);
-    const int mw = g.mcu_cols, ys = 16 * mw, cs = 8 * mw;
+    const int mw = g.mcu_cols;
+    const jpeg::SampleBuffers sb{base + p.lds.off_y, base + p.lds.off_c, mw};
     const size_t frame_bytes = (size_t)p.H * p.W * 3;
     const bool dwords = (p.W & 3) == 0 && (reinterpret_cast<uintptr_t>(p.dst) & 3) == 0;
     for (int i = blockIdx.x * jpeg::kDecodeWaves + wave; i < p.n; i += gridDim.x * jpeg::kDecodeWaves) {
@@ -170,18 +126,14 @@ __global__ __launch_bounds__(64 * jpeg::kDecodeWaves) void trs_jpeg_decode_kerne
                                     lo4 |= (uint32_t)jpeg::sample_of(d[col]) << (8 * col);
                                     hi4 |= (uint32_t)jpeg::sample_of(d[col + 4]) << (8 * col);
                                 }
-                                const int mx = mx0 + b / jpeg::kBlocksPerMcu;
-                                uint8_t* out = k < 4 ? ybuf + (my & 1) * 256 * mw + (8 * (k >> 1) + j) * ys + 16 * mx + 8 * (k & 1)
-                                                     : cring + (my % jpeg::kChromaRing) * 128 * mw + (k - 4) * 64 * mw + j * cs + 8 * mx;
-                                reinterpret_cast<uint32_t*>(out)[0] = lo4;
-                                reinterpret_cast<uint32_t*>(out)[1] = hi4;
+                                sb.store_block_row(my, mx0 + b / jpeg::kBlocksPerMcu, k, j, lo4, hi4);
                             }
                             wave_sync();
                         }
                     }
-                    if (st == jpeg::kDecoded && my > 0) output_mcu_row(p, g, my - 1, ybuf, cring, dst, lane, dwords);   // (the triangle filter reads the first chroma row of MCU row my)
+                    if (st == jpeg::kDecoded && my > 0) jpeg::output_mcu_row<64>(g, my - 1, sb, dst, lane, dwords);   // (the triangle filter reads the first chroma row of MCU row my)
                 }
-                if (st == jpeg::kDecoded) output_mcu_row(p, g, g.mcu_rows - 1, ybuf, cring, dst, lane, dwords);
+                if (st == jpeg::kDecoded) jpeg::output_mcu_row<64>(g, g.mcu_rows - 1, sb, dst, lane, dwords);
                 wave_sync();                                           // the sample buffers are free for the next file
             }
         }
@@ -255,8 +207,7 @@ TRS_EXPORT int trs_decode_jpeg_host(trs_env* e, const uint8_t* h_blob, const int
         hipError_t rh = e->jpd_files.reserve(blob_bytes);
         if (rh == hipSuccess) rh = e->jpd_meta.reserve(off_bytes + 2 * len_bytes);
         if (rh == hipSuccess) rh = e->jpd_dst.reserve(std::max<size_t>(dst_bytes, 4));
-        if (rh != hipSuccess)
-            return trs_internal_fail(rh == hipErrorOutOfMemory ? TRS_ERR_NOMEM : TRS_ERR_DEVICE, "no memory for " + std::to_string(blob_bytes + dst_bytes) + " bytes of decoder scratch");
+        if (rh != hipSuccess) return jpeg::no_memory(rh, blob_bytes + dst_bytes, "decoder scratch");
     }
     unsigned char* meta = e->jpd_meta.get();                              // offsets | lengths | statuses
     int64_t* d_off = reinterpret_cast<int64_t*>(meta);

@@ -1,11 +1,13 @@
 // trsim_jpeg_decode.hpp — reading a tub image (include/trsim_spec.h, "tub image (JPEG), decoding") as rules that compile for host and device: the
 // marker walk with its status decision, the Huffman tables taken from the file, the bit reader, symbol and block decoding, the inverse DCT pass,
-// the triangle upsampling and the colour formulas, and the LDS plan of the kernel.  csrc/trsim_jpeg_decode.hip holds the kernel's data movement and
-// tests/jpeg_decode_driver.cpp a plain host loop; both take every rule from here.
+// the triangle upsampling and the colour formulas, sample planes to a whole frame on the host (planes_to_frame), and the LDS plan of the kernel.
+// csrc/trsim_jpeg_decode.hip holds the kernel's data movement and tests/jpeg_decode_driver.cpp a plain host loop; both take every rule from here.  The
+// kernel's form of planes_to_frame, four pixels a lane, is output_mcu_row (trsim_jpeg_device.hpp), which the camera codec's kernel shares.
 // Every read of a file byte goes through the `at(i)` of a file type F that knows the file's length (SpanFile here, the kernel's LDS window there): it
 // answers 0 beyond the end and never reads there.  Every loop over file bytes is bounded: the marker walk moves forward by >= 2 bytes a turn and
 // stops at the length, the bit reader refills at most 8 bytes a call and stops at the length or at a marker, a block decodes at most 64 symbols.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "trsim_jpeg_tables.hpp"
@@ -303,6 +305,21 @@ TRS_JPEG_HD uint32_t ycc_to_rgb(int y, int cb, int cr)
     const int g = y + ((-fix16(0.34414) * cb + 32768 - fix16(0.71414) * cr) >> 16);
     const int b = y + ((fix16(1.772) * cb + 32768) >> 16);
     return (uint32_t)clamp255(r) | (uint32_t)clamp255(g) << 8 | (uint32_t)clamp255(b) << 16;
+}
+
+// the frame uint8[H][W][3] at dst from the sample planes: yp (rows ystride bytes apart), cb and cr (rows cstride apart; the ceil(H / 2) x ceil(W / 2) real samples are read)
+inline void planes_to_frame(const Geometry& g, const uint8_t* yp, int ystride, const uint8_t* cb, const uint8_t* cr, int cstride, uint8_t* dst)
+{
+    for (int y = 0; y < g.H; ++y)
+        for (int x = 0; x < g.W; ++x) {
+            const size_t r0 = (size_t)(y >> 1) * cstride, r1 = (size_t)chroma_nb_row(g, y) * cstride;
+            const int c0 = x >> 1, c1 = chroma_nb_col(g.W, x);
+            const int b = tri_h(tri_v(cb[r0 + c0], cb[r1 + c0]), tri_v(cb[r0 + c1], cb[r1 + c1]), x);
+            const int r = tri_h(tri_v(cr[r0 + c0], cr[r1 + c0]), tri_v(cr[r0 + c1], cr[r1 + c1]), x);
+            const uint32_t rgb = ycc_to_rgb(yp[(size_t)y * ystride + x], b, r);
+            uint8_t* o = dst + ((size_t)y * g.W + x) * 3;
+            o[0] = (uint8_t)rgb; o[1] = (uint8_t)(rgb >> 8); o[2] = (uint8_t)(rgb >> 16);
+        }
 }
 
 // ---- the kernel's LDS, per wave and per workgroup (csrc/trsim_jpeg_decode.hip lays it out in this order) -----------------------------------------

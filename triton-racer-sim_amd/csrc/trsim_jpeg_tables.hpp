@@ -1,7 +1,8 @@
 // trsim_jpeg_tables.hpp — the tub image format (include/trsim_spec.h, "tub image (JPEG)") as tables and integer arithmetic: quantisation tables
 // for a quality, the header bytes SOI..SOS, the Huffman tables in the form the kernel reads, the MCU geometry with its edge and dummy-block rules,
-// and the per-sample arithmetic (colour, downsampling, the two DCT passes, the quantiser).  Compiles without HIP (tests/jpeg_driver.cpp drives it
-// under the sanitizers); csrc/trsim_jpeg.hip takes every rule from here — none of them is written a second time in the kernel.
+// the per-sample arithmetic (colour, downsampling, the two DCT passes, the quantiser) and the forward sample rule of a 2 x 2 quad (sample_quad; over a
+// whole frame on the host: sample_planes).  Compiles without HIP (tests/jpeg_driver.cpp drives it under the sanitizers).  trs_jpeg_kernel and
+// trs_jpeg_codec_kernel take every rule from here, and apply sample_quad through the one stage both share (sample_stripe, trsim_jpeg_device.hpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -113,15 +114,21 @@ inline std::vector<uint8_t> header_bytes(int H, int W, int quality)
     return o;
 }
 
+// the quantisation steps << 3 of a quality, as the quantiser takes them (Tables::qv, and the camera codec's block steps)
+inline void quant_steps(int quality, int32_t qv[2][64])
+{
+    for (int c = 0; c < 2; ++c) {
+        uint8_t q[64];
+        quant_table(quality, c, q);
+        for (int i = 0; i < 64; ++i) qv[c][i] = (int32_t)q[i] << 3;
+    }
+}
+
 inline void build_tables(int H, int W, int quality, Tables* t)
 {
     huff_codes(kHuff[0], t->dc[0], 16); huff_codes(kHuff[1], t->ac[0], 256);
     huff_codes(kHuff[2], t->dc[1], 16); huff_codes(kHuff[3], t->ac[1], 256);
-    for (int c = 0; c < 2; ++c) {
-        uint8_t q[64];
-        quant_table(quality, c, q);
-        for (int i = 0; i < 64; ++i) t->qv[c][i] = (int32_t)q[i] << 3;
-    }
+    quant_steps(quality, t->qv);
     for (int k = 0; k < 64; ++k) t->zz_pos[kZigzag[k]] = (uint8_t)k;
     const std::vector<uint8_t> h = header_bytes(H, W, quality);
     for (int i = 0; i <= kHeaderBytes; ++i) t->header[i] = i < (int)h.size() ? h[i] : 0;
@@ -164,6 +171,40 @@ TRS_JPEG_HD int luma(int r, int g, int b) { return (fix16(.299) * r + fix16(.587
 TRS_JPEG_HD int chroma_b(int r, int g, int b) { return (-fix16(.16874) * r - fix16(.33126) * g + fix16(.5) * b + (128 << 16) + 32767) >> 16; }
 TRS_JPEG_HD int chroma_r(int r, int g, int b) { return (fix16(.5) * r - fix16(.41869) * g - fix16(.08131) * b + (128 << 16) + 32767) >> 16; }
 TRS_JPEG_HD int downsample(int a, int b, int c, int d, int out_col) { return (a + b + c + d + 1 + (out_col & 1)) >> 2; }
+
+// the forward sample rule: the samples of the 2 x 2 quad (qr, qc) of the padded planes — Y rows 2 qr, 2 qr + 1 and columns 2 qc, 2 qc + 1, and the
+// one sample (qr, qc) of either downsampled chroma plane.  px(r, c): the three RGB bytes of image pixel (r, c)
+struct QuadSamples { uint8_t y[2][2], cb, cr; };
+template <class Px>
+TRS_JPEG_HD QuadSamples sample_quad(const Geometry& g, int qr, int qc, Px px)
+{
+    QuadSamples s;
+    for (int dy = 0; dy < 2; ++dy)
+        for (int dx = 0; dx < 2; ++dx) {
+            const uint8_t* p = px(y_src_row(g, 2 * qr + dy), y_src_col(g, 2 * qc + dx));
+            s.y[dy][dx] = (uint8_t)luma(p[0], p[1], p[2]);
+        }
+    int r0, r1, c0, c1;
+    c_src_rows(g, qr, &r0, &r1);
+    c_src_cols(g, qc, &c0, &c1);
+    const uint8_t *a = px(r0, c0), *b = px(r0, c1), *c = px(r1, c0), *d = px(r1, c1);
+    s.cb = (uint8_t)downsample(chroma_b(a[0], a[1], a[2]), chroma_b(b[0], b[1], b[2]), chroma_b(c[0], c[1], c[2]), chroma_b(d[0], d[1], d[2]), qc);
+    s.cr = (uint8_t)downsample(chroma_r(a[0], a[1], a[2]), chroma_r(b[0], b[1], b[2]), chroma_r(c[0], c[1], c[2]), chroma_r(d[0], d[1], d[2]), qc);
+    return s;
+}
+// ... over a whole uint8[H][W][3] frame: yp[16 mcu_rows][16 mcu_cols], cb and cr [8 mcu_rows][8 mcu_cols]
+inline void sample_planes(const Geometry& g, const uint8_t* src, uint8_t* yp, uint8_t* cb, uint8_t* cr)
+{
+    const int ys = 16 * g.mcu_cols, cs = 8 * g.mcu_cols;
+    for (int qr = 0; qr < 8 * g.mcu_rows; ++qr)
+        for (int qc = 0; qc < cs; ++qc) {
+            const QuadSamples s = sample_quad(g, qr, qc, [&](int r, int c) { return src + ((size_t)r * g.W + c) * 3; });
+            for (int dy = 0; dy < 2; ++dy)
+                for (int dx = 0; dx < 2; ++dx) yp[(size_t)(2 * qr + dy) * ys + 2 * qc + dx] = s.y[dy][dx];
+            cb[(size_t)qr * cs + qc] = s.cb;
+            cr[(size_t)qr * cs + qc] = s.cr;
+        }
+}
 
 TRS_JPEG_HD int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 // one pass of the integer forward DCT over d[0..7] in place.  FIRST (rows, samples - 128): output scaled by 4 beyond the DCT's own factor; the
