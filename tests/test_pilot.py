@@ -10,13 +10,36 @@ stores activations as fp16 (round 3; bfloat16 until round 2 — the same MFMA ra
   * "pure": fp32 everywhere (what TensorFlow would compute): tolerance 4e-4 on the two outputs — measured: max |HIP - fp32| 4.4e-5 over
     288 frames x 3 weight sets at both frame sizes (scripts/pilot_precision.py, profiles/r03_pilot_precision.txt; 5.0e-4 with bfloat16)."""
 import math
+import types
 
 import numpy as np
 import pytest
 
+from test_pilot_plan_cpu import build_driver, call_of, plan_of
+
 pytestmark = pytest.mark.gpu
 
 SPEC = [(5, 2, 3, 24), (5, 2, 24, 32), (5, 2, 32, 64), (3, 1, 64, 64), (3, 1, 64, 64), (3, 1, 64, 128), (3, 1, 128, 128)]
+
+
+@pytest.fixture(scope="module")
+def planner(tmp_path_factory):
+    """What trs_pilot_load plans on this device (csrc/trsim_pilot_plan.hpp through tests/pilot_plan_driver.cpp, a host program): a comparison test asks it
+    which kernels its two runs reach.  plan(h, w, n_cap, **tuning) and call(h, w, n_cap, n, **tuning) as in tests/test_pilot_plan_cpu.py.
+    The plan is made for this device's CU count, as the library makes it; the values the tests expect of it (64 frames per dense workgroup at 150 frames of
+    240x320, 4 frames per chain workgroup at 1027 only, rolling bands at 300 / 150 / 131 frames) are those of the MI355X's 256 CUs: on a part with another
+    count they fail, which says that the cases no longer reach the kernels their docstrings name and want choosing anew."""
+    import torch
+    exe = build_driver(tmp_path_factory.mktemp("pilot_plan"), sanitize=False)
+    assert exe, "the plan driver needs g++"
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return types.SimpleNamespace(cus=cus, plan=lambda h, w, n_cap, **t: plan_of(exe, h, w, n_cap, cus=cus, **t),
+                                 call=lambda h, w, n_cap, n, **t: call_of(exe, h, w, n_cap, n, cus=cus, **t))
+
+
+def served(plan):
+    """the kernel that serves conv1..conv7 in a forward pass"""
+    return [l["served_by"] for l in plan["layers"][:7]]
 
 
 def make_weights(h, w, seed=0):
@@ -338,9 +361,10 @@ def test_closed_loop_is_unaffected_by_another_stream(make_env):
 
 
 @pytest.mark.parametrize("size,wsplit", [((120, 160), None), ((240, 320), None), ((240, 320), 1), ((100, 132), None), ((130, 300), None)])
-def test_fused_head_equals_the_two_layers(make_env, size, wsplit):
+def test_fused_head_equals_the_two_layers(make_env, planner, size, wsplit):
     """conv1 -> conv2 fused (conv1's activation stays in LDS; trs_conv12_band_kernel) against the two separate kernels (trs_pilot_tuning.no_fuse).
-    The band form (120x160; 240x320 and 130x300 cut in two parts of conv2 columns of equal width, the last one overlapping its neighbour) keeps the conv1 tile
+    The band form (120x160 at its whole width; 240x320, 130x300 and 100x132 — whose frame row of 396 bytes is no multiple of 16 — cut in two parts of conv2
+    columns of equal width, the last one overlapping its neighbour; the plan is asserted) keeps the conv1 tile
     split by column parity and takes conv2's k dimension in that order (even columns, then odd): the same products in another
     summation order, so an output can land on the neighbouring fp16 value — at most one ulp (2^-10 relative), on a small fraction
     of the elements.  240x320 with fuse_wsplit_max = 1 (a band may not be cut in width, and a whole-width band does not fit LDS): the
@@ -351,6 +375,13 @@ def test_fused_head_equals_the_two_layers(make_env, size, wsplit):
     ws = make_weights(h, w, seed=3)
     env = make_env("hip", n_envs=n, img_h=h, img_w=w, auto_reset=True)
     tune = {} if wsplit is None else {"fuse_wsplit_max": wsplit}
+    fused_plan, plain_plan = planner.plan(h, w, n, **tune), planner.plan(h, w, n, no_fuse=1, **tune)
+    assert served(plain_plan)[:2] == ["u8", "span<1>"]
+    if wsplit == 1:
+        assert fused_plan["head"]["on"] == 0 and served(fused_plan)[:2] == ["u8", "span<1>"]      # the documented fallback: both runs are the two layers
+    else:
+        parts = {(120, 160): 1, (240, 320): 2, (100, 132): 2, (130, 300): 2}[size]
+        assert fused_plan["head"]["wsplit"] == parts and served(fused_plan)[:2] == ["band<whole>" if parts == 1 else "band<split>"] * 2
     if tune:
         env.pilot_tuning(**tune)
     env.pilot_load(ws)
@@ -407,7 +438,7 @@ def test_fused_head_conv1_beyond_the_fp16_range(make_env):
 
 
 @pytest.mark.parametrize("size,n", [((120, 160), 300), ((240, 320), 150), ((130, 300), 131)])
-def test_fused_head_rolling_bands_are_bit_identical_to_one_band_per_item(make_env, size, n):
+def test_fused_head_rolling_bands_are_bit_identical_to_one_band_per_item(make_env, planner, size, n):
     """Round 3: with a (frame, part) stream per CU or more, a workgroup of the band-form head walks a frame's bands top to bottom and keeps
     the three conv1 rows two neighbouring bands share in a ring (trs_pilot_tuning.fuse_roll, the default) instead of computing them
     twice.  Same values into the same MFMAs: conv2's activation and the model's outputs must equal the one-band-per-item order bit for
@@ -417,6 +448,9 @@ def test_fused_head_rolling_bands_are_bit_identical_to_one_band_per_item(make_en
     rng = np.random.default_rng(12)
     frames = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
     oh2, ow2 = ((h - 5) // 2 + 1 - 5) // 2 + 1, ((w - 5) // 2 + 1 - 5) // 2 + 1
+    for roll in (1, 0):                                                # the batch is large enough for the default to roll, and the tuning field turns it off
+        call = planner.call(h, w, n, n, fuse_roll=roll)
+        assert (call["head_runs"], call["roll"]) == (1, roll), call
     res = {}
     for roll in (1, 0):
         env = make_env("hip", n_envs=n, img_h=h, img_w=w, auto_reset=True)
@@ -429,13 +463,15 @@ def test_fused_head_rolling_bands_are_bit_identical_to_one_band_per_item(make_en
     assert np.array_equal(res[1][0], res[0][0])
 
 
-@pytest.mark.parametrize("size,n", [((120, 160), 77), ((240, 320), 40), ((240, 320), 77), ((100, 132), 5), ((120, 160), 1)])
-def test_dense_kernel_against_torch_in_both_frame_groupings(make_env, size, n):
+@pytest.mark.parametrize("size,n", [((120, 160), 77), ((240, 320), 40), ((240, 320), 77), ((100, 132), 5), ((120, 160), 1), ((240, 320), 150)])
+def test_dense_kernel_against_torch_in_both_frame_groupings(make_env, planner, size, n):
     """dense1 on trs_pilot_dense_kernel against fp32 PyTorch on the kernel's own conv7 activation (the chunked 1x1-convolution kernel it
-    was compared with until round 3 is gone), in both of its forms: 64 frames per workgroup where K is long (the default at 240x320 with
-    n >= 64) and 32 frames per workgroup (trs_pilot_tuning.dense = 2) — the same fp16 products, K and frames split differently: fp32
-    summation order only.  n is not a multiple of 32 / 64 (ragged last frame group) and spans several groups; 240x320 needs several LDS
-    chunks per slice and a ragged last one."""
+    was compared with until round 3 is gone), in both of its forms: 64 frames per workgroup where K is long enough that every workgroup keeps two
+    LDS chunks or more (240x320 on 256 CUs: 129 frames or more — of these cases only 150) and 32 frames per workgroup (trs_pilot_tuning.dense = 2, and
+    the default everywhere else) — the same fp16 products, K and frames split differently: fp32 summation order only.  The plan is asserted: at
+    240x320 with 150 frames the two runs are trs_pilot_dense_kernel<2> and <1>; in every other case both runs are <1>, so the comparison between
+    the runs says nothing there and the check is the one against PyTorch.  n is not a multiple of 32 / 64 (ragged last frame group) and spans
+    several groups; 240x320 needs several LDS chunks per slice and a ragged last one."""
     h, w = size
     ws = make_weights(h, w, seed=5)
     rng = np.random.default_rng(11)
@@ -444,7 +480,9 @@ def test_dense_kernel_against_torch_in_both_frame_groupings(make_env, size, n):
     oh, ow = h, w
     for k, s_, _, _ in SPEC:
         oh, ow = (oh - k) // s_ + 1, (ow - k) // s_ + 1
-    for mode in ("1", "2"):                                           # 2: always 32 frames per workgroup (1 takes 64 where K is long: 240x320 with n >= 64)
+    nf = {mode: planner.call(h, w, n, n, dense=int(mode))["nf"] for mode in ("1", "2")}
+    assert nf == {"1": 2 if (size, n) == ((240, 320), 150) else 1, "2": 1}
+    for mode in ("1", "2"):                                           # 2: always 32 frames per workgroup (1 takes 64 where K is long: 240x320 with n >= 129)
         env = make_env("hip", n_envs=n, img_h=h, img_w=w, auto_reset=True)
         env.pilot_tuning(dense=int(mode))
         env.pilot_load(ws)
@@ -462,11 +500,12 @@ def test_dense_kernel_against_torch_in_both_frame_groupings(make_env, size, n):
 
 @pytest.mark.parametrize("size,n", [((120, 160), 37), ((120, 160), 1027), ((100, 132), 9), ((240, 320), 6), ((120, 160), 1)])
 @pytest.mark.parametrize("layers", ["4", "3"])
-def test_conv_chain_is_bit_identical_to_the_single_layers(make_env, size, n, layers):
+def test_conv_chain_is_bit_identical_to_the_single_layers(make_env, planner, size, n, layers):
     """conv4..conv7 (or conv5..conv7) in one launch with the activations in LDS (trs_conv_chain_kernel) against one launch per
     layer (trs_pilot_tuning.chain_layers = 0): the same MFMA order on the same fp16 values, so every activation — the interior ones are
     recomputed by the debug getter — and the outputs agree bit for bit.  37 frames: 2 frames per workgroup, odd tail; 1027: 4 per
-    workgroup with a ragged last one (3 frames: the second conv4 pass has one frame); 240x320 does not fit LDS: no chain."""
+    workgroup with a ragged last one (3 frames: the second conv4 pass has one frame); 100x132 and one frame: 2 per workgroup; 240x320 does not fit
+    LDS: no chain, both runs go layer by layer (the plan is asserted)."""
     h, w = size
     ws = make_weights(h, w, seed=9)
     rng = np.random.default_rng(21)
@@ -475,6 +514,13 @@ def test_conv_chain_is_bit_identical_to_the_single_layers(make_env, size, n, lay
     for k, s_, _, cout in SPEC:
         ih, iw = (ih - k) // s_ + 1, (iw - k) // s_ + 1
         shapes.append((n, ih, iw, cout))
+    on, off = planner.plan(h, w, n, chain_layers=int(layers)), planner.plan(h, w, n, chain_layers=0)
+    assert off["chain"]["first"] == -1 and "chain" not in served(off)
+    if size == (240, 320):
+        assert on["chain"]["first"] == -1 and served(on) == served(off)
+    else:
+        assert (on["chain"]["nl"], on["chain"]["F"]) == (int(layers), 4 if n == 1027 else 2)
+        assert served(on)[3:] == ["frame"] * (4 - int(layers)) + ["chain"] * int(layers) and served(off)[3:] == ["frame"] * 4
     res = {}
     for mode in ("0", layers):
         env = make_env("hip", n_envs=n, img_h=h, img_w=w, auto_reset=True)
@@ -489,7 +535,7 @@ def test_conv_chain_is_bit_identical_to_the_single_layers(make_env, size, n, lay
 
 
 @pytest.mark.parametrize("size,n", [((120, 160), 37), ((120, 160), 1027), ((100, 132), 9), ((240, 320), 11)])
-def test_conv3_with_frames_in_lds_is_bit_identical_to_the_span_kernel(make_env, size, n):
+def test_conv3_with_frames_in_lds_is_bit_identical_to_the_span_kernel(make_env, planner, size, n):
     """conv3 on trs_conv_frame5_kernel (input frames in LDS, even / odd column planes, weights from L2) against the span kernel
     (trs_pilot_tuning.frame5 = 0): the same k order on the same fp16 values — conv3's activation and the outputs agree bit for bit.  240x320: the input frame (281 KB)
     is cut into 5 bands of 6 output rows (the last has 3)."""
@@ -500,6 +546,9 @@ def test_conv3_with_frames_in_lds_is_bit_identical_to_the_span_kernel(make_env, 
     (ih, iw) = (h, w)
     for k, s_, _, cout in SPEC[:3]:
         ih, iw = (ih - k) // s_ + 1, (iw - k) // s_ + 1
+    on, off = planner.plan(h, w, n, frame5=2), planner.plan(h, w, n, frame5=0)
+    assert served(on)[2] == "frame5" and served(off)[2] == "span<2>"
+    assert on["layers"][2]["frame5_bands"] == (5 if size == (240, 320) else 1)
     res = {}
     for mode in ("0", "2"):                                          # 2: also when the frame has to be cut into row bands
         env = make_env("hip", n_envs=n, img_h=h, img_w=w, auto_reset=True)

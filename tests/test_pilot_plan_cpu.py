@@ -1,0 +1,262 @@
+"""The pilot's plan and weight packing (csrc/trsim_pilot_plan.hpp) on the CPU: tests/pilot_plan_driver.cpp built with AddressSanitizer + UBSan and run as
+a subprocess.  (a) Which kernel serves which layer, and with what LDS, at the sizes the GPU tests and the benchmark use — the table of DESIGN.md, computed
+with the arithmetic trs_pilot_load had before it moved here (256 CUs, default tuning).  (b) Properties of every plan over a sweep of frame sizes and batch
+capacities.  (c) The packing of the Keras arrays into fp16 granules against a numpy restatement written here."""
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LDS_BYTES = 160 * 1024
+REFUSALS = ("image too small for Keras_2D_CNN", "dense1's shape does not suit trs_pilot_dense_kernel", "a convolution's weight slice does not fit LDS")
+SPEC = [(5, 2, 3, 24), (5, 2, 24, 32), (5, 2, 32, 64), (3, 1, 64, 64), (3, 1, 64, 64), (3, 1, 64, 128), (3, 1, 128, 128)]
+
+
+def build_driver(directory, sanitize=True):
+    """The driver's executable, or None where there is no host compiler.  tests/test_pilot.py asks the same program for the plan of its cases, without the sanitizers."""
+    if not shutil.which("g++"):
+        return None
+    exe = os.path.join(str(directory), "pilot_plan_driver")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17"] + (["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else [])
+                          + ["-o", exe, os.path.join(ROOT, "tests", "pilot_plan_driver.cpp")])
+    return exe
+
+
+def run_driver(exe, *args):
+    out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, (args, out.stderr[-2000:])
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-2000:]
+    return out.stdout.splitlines()
+
+
+def parse(line):
+    """'kind a=1 b=x text=the rest' -> (kind, {a: 1, b: 'x', text: 'the rest'})"""
+    kind, _, rest = line.partition(" ")
+    rest, _, text = rest.partition(" text=")
+    rec = {k: (int(v) if re.fullmatch(r"-?\d+", v) else v) for k, v in (kv.split("=", 1) for kv in rest.split())}
+    if text:
+        rec["text"] = text
+    return kind, rec
+
+
+def plan_of(exe, h, w, n_cap, cus=256, arrays=22, **tuning):
+    """{'layers': [...], 'head': {...}, 'chain': {...}} or {'refuse': {...}} for one frame size."""
+    plan = {"layers": []}
+    for kind, rec in map(parse, run_driver(exe, "plan", h, w, n_cap, cus, arrays, *[f"{k}={v}" for k, v in tuning.items()])):
+        if kind == "layer":
+            plan["layers"].append(rec)
+        else:
+            plan[kind] = rec
+    return plan
+
+
+def call_of(exe, h, w, n_cap, n, cus=256, arrays=22, **tuning):
+    (line,) = run_driver(exe, "call", h, w, n_cap, cus, arrays, n, *[f"{k}={v}" for k, v in tuning.items()])
+    return parse(line)[1]
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = build_driver(tmp_path_factory.mktemp("pilot_plan"))
+    if not exe:
+        pytest.skip("g++ not available")
+    return exe
+
+
+# ---- (a) the table -------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n_cap,f,lds", [(1, 2, 67072), (37, 2, 67072), (77, 2, 67072), (1024, 4, 132096), (1027, 4, 132096)])
+def test_plan_at_120x160(driver, n_cap, f, lds):
+    p = plan_of(driver, 120, 160, n_cap)
+    head = p["head"]
+    assert (head["on"], head["wsplit"], head["R2"], head["bands"], head["lds"]) == (1, 1, 6, 5, 135392)
+    assert [l["served_by"] for l in p["layers"]] == ["band<whole>", "band<whole>", "frame5", "chain", "chain", "chain", "chain", "dense"]
+    c3 = p["layers"][2]
+    assert (c3["frame5"], c3["frame5_bands"], c3["frame5_lds"]) == (1, 1, 128128)
+    assert [(l["frame"], l["frame_bands"]) for l in p["layers"][3:7]] == [(1, 1)] * 4
+    chain = p["chain"]
+    assert (chain["first"], chain["nl"], chain["F"], chain["lds"]) == (3, 4, f, lds)
+    d = call_of(driver, 120, 160, n_cap, n_cap)
+    assert (d["nf"], d["KS"]) == (1, 4 if n_cap == 1027 else 8)
+
+
+def test_plan_at_240x320(driver):
+    p = plan_of(driver, 240, 320, 512)
+    head = p["head"]
+    assert (head["on"], head["wsplit"], head["w2p"], head["cpr"], head["R2"], head["bands"], head["lds"]) == (1, 2, 39, 31, 6, 10, 139328)
+    c3 = p["layers"][2]
+    assert (c3["frame5"], c3["frame5_bands"], c3["frame5_ohb"], c3["frame5_lds"]) == (1, 5, 6, 148096)
+    assert [(l["frame"], l["frame_bands"]) for l in p["layers"][3:7]] == [(1, 2), (1, 2), (1, 3), (1, 3)]
+    assert p["chain"]["first"] == -1
+    assert [l["served_by"] for l in p["layers"]] == ["band<split>", "band<split>", "frame5", "frame", "frame", "frame", "frame", "dense"]
+    unsplit = plan_of(driver, 240, 320, 512, fuse_wsplit_max=1)
+    assert unsplit["head"]["on"] == 0 and [l["served_by"] for l in unsplit["layers"][:2]] == ["u8", "span<1>"]
+    for n, nf, ks in [(6, 1, None), (40, 1, None), (77, 1, None), (150, 2, 62), (512, 2, 31)]:
+        d = call_of(driver, 240, 320, 512, n)
+        assert d["nf"] == nf and (ks is None or d["KS"] == ks), (n, d)
+        assert call_of(driver, 240, 320, 512, n, dense=2)["nf"] == 1
+
+
+def test_plan_at_100x132_and_130x300(driver):
+    p = plan_of(driver, 100, 132, 9)
+    head = p["head"]
+    assert (head["on"], head["wsplit"], head["w2p"], head["bands"], head["lds"]) == (1, 2, 15, 4, 85760)     # a frame row of 396 bytes is no multiple of 16
+    assert (p["chain"]["first"], p["chain"]["F"]) == (3, 2)
+    p = plan_of(driver, 130, 300, 131)
+    head = p["head"]
+    assert (head["on"], head["wsplit"], head["w2p"], head["lds"]) == (1, 2, 36, 132896)
+    c3 = p["layers"][2]
+    assert (c3["frame5"], c3["frame5_bands"], c3["frame5_lds"]) == (1, 2, 156928) and 158 * 1024 - c3["frame5_lds"] == 4864
+    assert p["chain"]["first"] == -1
+
+
+def test_refusals_come_back_through_the_plan(driver):
+    small = plan_of(driver, 28, 160, 4)
+    assert small["refuse"] == {"H": 28, "W": 160, "n_cap": 4, "code": -5, "text": REFUSALS[0]} and not small["layers"]
+
+
+# ---- (b) properties of every plan ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("w", [64, 132, 160, 300, 320])
+@pytest.mark.parametrize("n_cap", [1, 37, 1027])
+def test_every_plan_fits_and_is_aligned(driver, w, n_cap):
+    seen, planned = set(), 0
+    for kind, r in map(parse, run_driver(driver, "plan", "29:260", w, n_cap, 256, 22)):
+        seen.add(r["H"])
+        where = (kind, r["H"], w, n_cap, r.get("i"))
+        if kind == "refuse":
+            assert r["code"] == -5 and r["text"] in REFUSALS, where
+        elif kind == "layer":
+            planned += r["i"] == 0
+            assert r["i"] == 7 or 0 < r["res_lds"] <= LDS_BYTES, where
+            for tag in ("frame", "frame5"):
+                if r[tag]:
+                    bands, ohb = r[tag + "_bands"], r[tag + "_ohb"]
+                    assert 0 < r[tag + "_lds"] <= LDS_BYTES, where
+                    assert bands * ohb >= r["OH"] > (bands - 1) * ohb, where
+        elif kind == "head" and r["on"]:
+            assert r["lds"] <= LDS_BYTES, where
+            for off in ("off_w2", "off_b", "off_tile", "off_band"):
+                assert r[off] % 16 == 0 and 0 < r[off] < r["lds"], (where, off)
+            assert r["off_w2"] < r["off_b"] < r["off_tile"] and r["off_tile"] + r["tile_bytes"] <= r["off_band"] and r["off_band"] + r["band_bytes"] == r["lds"], where
+        elif kind == "chain" and r["first"] >= 0:
+            assert r["lds"] <= LDS_BYTES, where
+            for off in ("offA", "offB", "off_bias"):
+                assert r[off] % 16 == 0 and 0 <= r[off] < r["lds"], (where, off)
+            assert r["offA"] < r["offB"] < r["off_bias"], where
+    assert seen == set(range(29, 261))                                       # every size answered: a plan or a refusal
+    assert planned > 100 if w > 64 else planned == 0                         # (a frame 64 wide is too small for the seven convolutions)
+
+
+@pytest.mark.parametrize("w", [64, 132, 160, 300, 320])
+def test_dense1_slices_cover_k_and_frame_groups_cover_the_batch(driver, w):
+    pat = re.compile(r" n=(\d+) G=(\d+) nf=(\d+) gps=(\d+) KS=(\d+) groups=(\d+) dense_grid=(\d+) dense_lds=(\d+) ")
+    lines = 0
+    for line in run_driver(driver, "call", "29:260", w, 1027, 256, 22, "1:300"):
+        if not line.startswith("call "):
+            assert line.startswith("refuse "), line
+            continue
+        n, g, nf, gps, ks, groups, grid, lds = map(int, pat.search(line).groups())
+        lines += 1
+        assert ks * gps >= g > (ks - 1) * gps, line
+        assert grid % 8 == 0 and grid >= groups * ks, line
+        assert groups * 32 * nf >= n and nf in (1, 2) and lds <= LDS_BYTES, line
+    assert lines > 100 * 300 if w > 64 else lines == 0
+
+
+# ---- (c) packing ---------------------------------------------------------------------------------------------------------------------------
+
+def fp16_bits(x):
+    return np.clip(x.astype(np.float32), -65504.0, 65504.0).astype(np.float16).view(np.uint16)
+
+
+def numpy_pack(i, ih, iw, kernel):
+    """The granule layout as the kernels' comments state it: [g][cout padded to 32][8 input values] of fp16 and, per granule, the byte offset of its
+    8 values from the output pixel's first input byte.  A kernel row is one run of KW x CIN input values in NHWC order, padded with zero granules to
+    a multiple of 4; conv1's run is the 15 bytes of 5 RGB pixels + 1, in two granules, its weights x 256 / 255; dense1 is one run."""
+    if i == 7:
+        cin, cout = kernel.shape
+        rows = [kernel]
+        px_bytes, row_bytes, cout_pad = 2, 0, 128
+    else:
+        kh, kw, cin, cout = kernel.shape
+        rows = [kernel[r].reshape(kw * cin, cout) for r in range(kh)]
+        px_bytes, row_bytes, cout_pad = (1, iw * 3, 32) if i == 0 else (2, iw * cin * 2, (cout + 31) // 32 * 32)
+    if i == 0:
+        rows = [np.concatenate([r * (np.float32(256.0) / np.float32(255.0)), np.zeros((1, cout), np.float32)]) for r in rows]
+    run = rows[0].shape[0] // 8
+    run_pad = run if i == 0 else (run + 3) // 4 * 4
+    g_real = len(rows) * run_pad
+    g_pad = (g_real + 3) // 4 * 4
+    w = np.zeros((g_pad, cout_pad, 8), np.uint16)
+    goff = np.zeros(g_pad, np.int32)
+    is_padding = np.ones(g_pad, bool)
+    for r, row in enumerate(rows):
+        for gi in range(run_pad):
+            g = r * run_pad + gi
+            goff[g] = r * row_bytes + gi * 8 * px_bytes
+            if gi < run:
+                w[g, :cout, :] = fp16_bits(row[gi * 8:gi * 8 + 8]).T
+                is_padding[g] = False
+    goff[g_real:] = goff[g_real - 1]
+    return w, goff, is_padding, cout_pad
+
+
+def glorot(rng, shape):
+    fan = (shape[0] * shape[1] * (shape[2] + shape[3])) if len(shape) == 4 else sum(shape)
+    lim = math.sqrt(6.0 / fan)
+    return rng.uniform(-lim, lim, shape).astype(np.float32)
+
+
+def pack(driver, tmp_path, i, ih, iw, kernel, bias):
+    (tmp_path / "k.bin").write_bytes(np.ascontiguousarray(kernel, np.float32).tobytes())
+    (tmp_path / "b.bin").write_bytes(np.ascontiguousarray(bias, np.float32).tobytes())
+    lines = run_driver(driver, "pack", i, ih, iw, tmp_path / "k.bin", tmp_path / "b.bin", tmp_path / "out")
+    return lines, {ext: np.fromfile(tmp_path / f"out.{ext}", dtype) for ext, dtype in (("w", np.uint16), ("goff", np.int32), ("bias", np.float32))}
+
+
+@pytest.mark.parametrize("i,ih,iw", [(0, 16, 16), (1, 16, 16), (3, 16, 16), (7, 1, 5)], ids=["conv1", "conv2", "conv4", "dense1-G80"])
+def test_packing_equals_the_numpy_restatement(driver, tmp_path, i, ih, iw):
+    rng = np.random.default_rng(40 + i)
+    shape = (ih * iw * 128, 100) if i == 7 else (SPEC[i][0], SPEC[i][0], SPEC[i][2], SPEC[i][3])
+    kernel = glorot(rng, shape)
+    kernel.reshape(-1)[:4] = [7.0e4, -7.0e4, 3.0e-6, 1.0e-9]                 # beyond the range (saturates), a binary16 subnormal, below the smallest one
+    bias = rng.uniform(-0.05, 0.05, shape[-1]).astype(np.float32)
+    lines, got = pack(driver, tmp_path, i, ih, iw, kernel, bias)
+    head = parse(lines[0])[1]
+    want_w, want_goff, is_padding, cout_pad = numpy_pack(i, ih, iw, kernel)
+    assert (head["G_pad"], head["COUT_PAD"]) == (len(want_goff), cout_pad) and (i != 7 or head["G"] == 80) and (i != 1 or (head["run"], head["run_pad"]) == (15, 16))
+    assert np.array_equal(got["w"].reshape(want_w.shape), want_w)
+    assert np.array_equal(got["goff"], want_goff)
+    assert np.array_equal(got["bias"], np.concatenate([bias, np.zeros(cout_pad - len(bias), np.float32)]))
+    # the padding granules: zero weights on an address inside the input of the first output pixel's frame
+    assert is_padding.sum() == {0: 2, 1: 5, 3: 0, 7: 0}[i]
+    assert not got["w"].reshape(want_w.shape)[is_padding].any()
+    assert (got["goff"] >= 0).all() and (got["goff"] + 16 <= head["in_bytes"]).all()
+    if i == 1:
+        # trs_conv12_band_kernel reads a window as two runs, the even conv1 columns (3 pixels = 9 granules of 8 channels) then the odd (2 pixels = 6): conv2's
+        # granules are packed in that order for it, the row's padding granule last
+        order = [kw * 3 + c8 for kw in (0, 2, 4) for c8 in range(3)] + [kw * 3 + c8 for kw in (1, 3) for c8 in range(3)] + [15]
+        assert [int(x) for x in lines[1].split()[1:]] == order
+        parity = np.fromfile(tmp_path / "out.parity", np.uint16).reshape(5, 16, cout_pad, 8)
+        assert np.array_equal(parity, want_w.reshape(5, 16, cout_pad, 8)[:, order])
+
+
+def test_conv1_bound_for_the_fused_heads_epilogue(driver, tmp_path):
+    rng = np.random.default_rng(7)
+    kernel, bias = glorot(rng, (5, 5, 3, 24)), rng.uniform(-0.05, 0.05, 24).astype(np.float32)
+
+    def bounded(k):
+        lines, _ = pack(driver, tmp_path, 0, 16, 16, k, bias)
+        return int(lines[1].split()[1])
+
+    assert bounded(kernel) == 1
+    assert bounded(kernel * np.float32(3e5)) == 0
+    with_nan = kernel.copy()
+    with_nan[2, 3, 1, 17] = np.nan
+    assert bounded(with_nan) == 0

@@ -25,11 +25,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
-#include <string>
 #include <type_traits>
 #include <memory>
 #include <vector>
@@ -37,6 +34,7 @@
 #include "../../include/trsim.h"
 #include "trsim_internal.hpp"
 #include "trsim_mem.hpp"
+#include "trsim_pilot_plan.hpp"   // the plan: which kernel serves which layer, the constants shared with the kernels, the weight packing (host-only)
 
 namespace {
 
@@ -45,6 +43,7 @@ typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;   // 8 binary16 valu
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
+using namespace trsim;   // (trsim_pilot_plan.hpp, trsim_mem.hpp)
 constexpr int kLayers = 11;               // conv1..7, dense1..3, output
 #ifndef TRS_CONV_ABLATE
 #define TRS_CONV_ABLATE 0   /* diagnostic builds of trs_conv_lt_kernel, never shipped: 1 = no steady-state global loads, 2 = no LDS transpose, 3 = no MFMA, 4 = no stores */
@@ -169,9 +168,6 @@ struct FrameConvParams {
 
 #ifndef TRS_FRAME_STAMPS
 #define TRS_FRAME_STAMPS 0   /* diagnostic build, never shipped: workgroup 7 prints the s_memtime ticks of its staging, work and waits */
-#endif
-#ifndef TRS_FRAME_LOADERS
-#define TRS_FRAME_LOADERS 4   /* loader waves of trs_conv_frame_kernel beside its 8 compute waves */
 #endif
 #ifndef TRS_FRAME_R
 #define TRS_FRAME_R 4   /* weight ring depth of trs_conv_frame_kernel in k-steps */
@@ -593,7 +589,6 @@ __global__ __launch_bounds__(BLOCK, 2) void trs_conv_chain_kernel(const ChainPar
 #endif
 #ifndef TRS_F5_NB
 #define TRS_F5_NB 2        /* 32-channel blocks per wave item */
-#define TRS_F5_COMPUTE 4   /* compute waves (+ 4 loader waves); 1 x 8 and 2 x 8 measured: see the kernel */
 #endif
 #ifndef TRS_F5_STAMPS
 #define TRS_F5_STAMPS 0   /* diagnostic build, never shipped: workgroup 7 prints the s_memtime ticks of its first staging, its work and its waits */
@@ -822,8 +817,6 @@ struct Fuse12Params {
 // thread, requested one item ahead so that its latency hides behind conv1 of the current item), unpacks them once into a fp16
 // image in LDS, and conv1 reads its k-steps (8 consecutive values, 4-byte aligned) from there with two ds_read2_b32.
 // Same fp16 values as the separate layers; conv2's k dimension runs in column-parity order (see the tile layout below).
-constexpr int kBandPf = 2;                                                  // 16-byte chunks of the band per loader thread (waves 8..15: 512 threads; 4 until round 2:
-                                                                            // the 8 registers now hold conv1's bias)
 template <bool SPLIT>
 __global__ __launch_bounds__(1024) void trs_conv12_band_kernel(const Fuse12Params q)
 {
@@ -1361,11 +1354,8 @@ struct DenseParams {
 #ifndef TRS_DENSE_ABLATE
 #define TRS_DENSE_ABLATE 0   /* timing-only diagnostic builds (scripts/r04_dense_ablate.sh), never shipped */
 #endif
-constexpr int kDenseChunk = 72;            // granules per LDS chunk = 36 k-steps
-constexpr int kDensePitch = 73;            // LDS row pitch in granules (odd: 16 lanes cover all 64 banks)
 constexpr int kDenseSteps = kDenseChunk / 2;
 constexpr int kDenseStage = 9;             // granules a thread stages per chunk and per 32 frames (32 x 72 / 256)
-constexpr int kDenseLds = 2 * 32 * kDensePitch * 16;   // per 32 frames (NF = 2: twice that)
 
 // NF = frame blocks of 32 per workgroup.  NF = 2 (round 4, long K: 240x320): every weight fragment feeds TWO MFMAs (frames 0..31 and 32..63), so the
 // weight stream — per-lane 16-byte loads straight from L2, 1.18 MB per workgroup at 512 x 240x320, measured as 15 of the kernel's 37 us by a
@@ -1648,27 +1638,16 @@ __global__ void trs_zero_controls_kernel(float* a, float* b, float* c, int n)
     if (i < n) { a[i] = 0.f; b[i] = 0.f; c[i] = 0.f; }
 }
 
-// ---------------------------------------------------------------------------------------------
-
+// ---- the host side: the device buffers, the kernels' parameter blocks filled from the plan (trsim_pilot_plan.hpp), and the launches ----
 struct ConvLayer {
-    int KH, KW, S, CIN, COUT, COUT_PAD, IH, IW, OH, OW, G, G_pad;
-    bool u8in, out_f32, relu;
-    // conv1..7 on the single-layer kernels (trs_conv_u8_kernel, trs_conv_lt_kernel, trs_conv_span_kernel): the weights (or a 64-channel
-    // slice) live in LDS, persistent workgroups
-    int res_nb = 1, res_ysplit = 1, res_lds = 0, res_block = 512, res_wg_per_cu = 1;
-    bool frame = false; int frame_f = 1, frame_lds = 0, frame_bands = 1, frame_ohb = 0;   // trs_conv_frame_kernel (3x3 stride-1 layers: F frames' input activations in LDS)
-    bool frame5 = false; int frame5_lds = 0, frame5_bands = 1, frame5_ohb = 0;   // trs_conv_frame5_kernel (conv3: 5x5 stride 2 over 32 channels, one input frame / band per workgroup in LDS)
-    bool res_span = false; int span_nl = 0, run_pad = 0;   // trs_conv_span_kernel (stride-2 5x5 layers: per-row input spans staged in LDS)
+    const PilotLayer* p = nullptr;        // its row of PilotCtx::plan
     trsim::DevBuf<u4v> w; trsim::DevBuf<float> bias; trsim::DevBuf<int> goff;
 };
 
 struct PilotCtx {
-    int n_cap = 0, H = 0, W = 0, cu_count = 256;
+    PilotPlan plan;                       // what trs_pilot_load decided for this frame size, batch capacity, device and tuning
     ConvLayer L[9];                       // conv1..7 + dense1 (1x1 "conv" over frames) [+ dense4: the second head of cnn_2d_full_house]
     trsim::DevBuf<void> act[9];           // outputs of L[i] for n_cap frames (fp16; act[7], act[8] float)
-    size_t act_elems[9] = {};             // per frame
-    int arch = 0;                         // TRS_PILOT_SPD_CTL / CNN_2D share Keras_2D_CNN(2 outputs); TRS_PILOT_SPD_FTR (+1 feature vector); TRS_PILOT_FULL_HOUSE
-    int n_layers = 8;
     trsim::DevBuf<float> xblob;           // small fp32 weights of the extra dense branches (TailExParams offsets)
     int xo[32] = {};                      // offsets (floats) into xblob
     trsim::DevBuf<void> slab2; int last_slices2 = 1;   // dense4 partial sums
@@ -1676,37 +1655,60 @@ struct PilotCtx {
     trsim::DevBuf<float> raw;             // [n_cap][2]
     trsim::DevBuf<uint8_t> tmp_frames; size_t tmp_cap = 0;   // room for tmp_cap bytes of frames and side inputs (+ the callers' padding)
     int last_n = 0, last_slices = 1;
-    bool no_fuse = false;
-    bool fuse12 = false; int fuse_r2 = 0, fuse_lds = 0; Fuse12Params fuse{};   // conv1 -> conv2 in one kernel, band form (conv1's activation stays in LDS)
+    Fuse12Params fuse{};                  // conv1 -> conv2 in one kernel, band form (plan.head): all but the per-call fields
     const uint8_t* last_frames = nullptr; bool act0_valid = false;           // conv1's activation is only materialised on demand (debug getter)
     trsim::DevBuf<void> slab;             // dense1 partial sums [slices][n][100] fp32
-    int chain_first = -1, chain_lds = 0; ChainParams chain{};   // conv(chain_first + 1) .. conv7 in one launch (trs_conv_chain_kernel); -1: layer by layer
-    bool chain_mid_valid = true;          // act[chain_first .. 5] hold the last pass (the chain never writes them; the debug getter runs the single layers on demand)
-    trsim::DevBuf<u4v> w2_parity;         // conv2's granules in the band kernel's order: per kernel row the even conv1 columns (kw 0, 2, 4), then the odd (1, 3)
-    trs_pilot_tuning tun{};               // the kernel choices this context was loaded with (trs_pilot_set_tuning, else the defaults)
+    ChainParams chain{};                  // conv(plan.chain.first + 1) .. conv7 in one launch (trs_conv_chain_kernel): all but the per-call fields
+    bool chain_mid_valid = true;          // act[chain.first .. 5] hold the last pass (the chain never writes them; the debug getter runs the single layers on demand)
+    trsim::DevBuf<u4v> w2_parity;         // conv2's granules in the band kernel's order (conv2_parity_order)
 };
 
-unsigned short host_f2h(float f)
-{   // round to nearest even; weights beyond binary16's range saturate (|w| > 65504 does not occur in a trained network)
-    const _Float16 h = (_Float16)std::min(std::max(f, -65504.0f), 65504.0f);
-    unsigned short u; std::memcpy(&u, &h, 2);
-    return u;
-}
-float host_h2f(unsigned short u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; }
+float host_h2f(unsigned short u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; }   // (the debug getter's; packing needs host_f2h only)
 
-template <typename T>
-int upload(trsim::DevBuf<T>& dst, const std::vector<T>& v)
+template <typename D, typename T>
+int upload(trsim::DevBuf<D>& dst, const std::vector<T>& v)
 {
     HIPCHK(dst.alloc(v.size() * sizeof(T)));
     HIPCHK(hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return TRS_OK;
 }
 
-int launch_conv(const ConvLayer& l, const void* in, size_t in_bytes, void* out, int n_img, hipStream_t s, int cu_count)
+// one launch with dynamic LDS: the kernel may use up to lds_max, this launch gets lds
+template <typename P>
+int launch_lds(void (*kernel)(P), dim3 grid, dim3 block, int lds, int lds_max, hipStream_t s, const P& p)
 {
-    ConvParams p{};
-    p.in = in; p.w = l.w.get(); p.bias = l.bias.get(); p.goff = l.goff.get(); p.out = out;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, p);
+    HIPCHK(hipGetLastError());
+    return TRS_OK;
+}
+
+int launch_conv(const ConvLayer& cl, const void* in, size_t in_bytes, void* out, int n_img, hipStream_t s, int cu_count)
+{
+    const PilotLayer& l = *cl.p;
     if (in_bytes > 0x7FFFFFFFull) return trs_internal_fail(TRS_ERR_LIMIT, "activation larger than 2 GiB: lower the batch");
+    const PilotKernel kernel = pilot_kernel_of(l);
+    if (kernel == kKernFrame5) {                                            // one persistent 8-wave workgroup per CU: a unit (frame or row band) computed from one LDS buffer, the next staged into the other
+        Frame5Params q{};
+        q.in = static_cast<const u4v*>(in); q.w = cl.w.get(); q.bias = cl.bias.get(); q.out = static_cast<unsigned short*>(out);
+        q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.F = 1; q.ev = (l.IW + 1) / 2; q.COUT = l.COUT;
+        q.bands = l.frame5_bands; q.ohb = l.frame5_ohb; q.ihb = l.frame5_bands == 1 ? l.IH : 2 * l.frame5_ohb + 3; q.magic_ow = pilot_magic(l.OW);
+        return launch_lds(trs_conv_frame5_kernel<2, TRS_F5_NB, TRS_F5_R, kFrame5Block, TRS_F5_COMPUTE>, dim3(frame5_grid(l, n_img, cu_count)), dim3(kFrame5Block), l.frame5_lds, kPilotLds, s, q);
+    }
+    if (kernel == kKernFrame) {
+        FrameConvParams q{};
+        q.in = static_cast<const u4v*>(in); q.w = cl.w.get(); q.bias = cl.bias.get(); q.out = static_cast<unsigned short*>(out);
+        q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.COUT = l.COUT; q.COUT_PAD = l.COUT_PAD; q.KH = l.KH; q.KW = l.KW;
+        q.F = l.frame_f; q.cg = l.CIN / 8; q.cgs = q.cg == 8 ? 3 : 4; q.relu = l.relu;
+        q.bands = l.frame_bands; q.ohb = l.frame_ohb; q.ihb = l.frame_ohb + l.KH - 1;
+        q.magic_uout = pilot_magic(q.ohb * q.OW); q.magic_ow = pilot_magic(q.OW); q.magic_bands = q.bands == 1 ? 0u : pilot_magic(q.bands);
+        // (wave items of 2 x 32 pixels x 64 channels: the plan cuts the frames into bands so that a group has about 8 of them — items of 3 tiles need
+        // more than the 168 registers that 12 waves leave each)
+        return launch_lds(q.cg == 8 ? trs_conv_frame_kernel<2, 2, 4, TRS_FRAME_R, 8, TRS_FRAME_LOADERS> : trs_conv_frame_kernel<2, 2, 8, TRS_FRAME_R, 8, TRS_FRAME_LOADERS>,
+                          dim3(frame_grid(l, n_img, cu_count)), dim3(kFrameBlock), l.frame_lds, kPilotLds, s, q);   // one persistent workgroup per CU
+    }
+    ConvParams p{};
+    p.in = in; p.w = cl.w.get(); p.bias = cl.bias.get(); p.goff = cl.goff.get(); p.out = out;
     p.in_bytes = (int)in_bytes;
     p.N = n_img; p.IH = l.IH; p.IW = l.IW; p.CIN = l.CIN; p.OH = l.OH; p.OW = l.OW; p.COUT = l.COUT; p.COUT_PAD = l.COUT_PAD; p.S = l.S;
     p.G = l.G; p.G_pad = l.G_pad; p.M = n_img * l.OH * l.OW;
@@ -1715,164 +1717,85 @@ int launch_conv(const ConvLayer& l, const void* in, size_t in_bytes, void* out, 
     // outputs above 128 MB leave non-temporally (measured: conv1's 222 MB -> conv1 88 -> 81 us, conv2 85 -> 82; at 48 MB conv3 loses)
     p.nt_out = (!l.out_f32 && (size_t)p.M * l.COUT * 2 > ((size_t)128 << 20)) ? 1 : 0;
     p.KH = l.KH; p.KW = l.KW; p.run_pad = l.run_pad; p.cg = l.u8in ? 0 : l.CIN / 8; p.span_nl = l.span_nl;
-    if (l.frame5) {                                                         // one persistent 8-wave workgroup per CU: a unit (frame or row band) computed from one LDS buffer, the next staged into the other
-        Frame5Params q{};
-        q.in = static_cast<const u4v*>(in); q.w = l.w.get(); q.bias = l.bias.get(); q.out = static_cast<unsigned short*>(out);
-        q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.F = 1; q.ev = (l.IW + 1) / 2; q.COUT = l.COUT;
-        q.bands = l.frame5_bands; q.ohb = l.frame5_ohb; q.ihb = l.frame5_bands == 1 ? l.IH : 2 * l.frame5_ohb + 3;
-        q.magic_ow = (unsigned)((0x100000000ull + (unsigned)l.OW - 1u) / (unsigned)l.OW);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_conv_frame5_kernel<2, TRS_F5_NB, TRS_F5_R, 64 * (TRS_F5_COMPUTE + 4), TRS_F5_COMPUTE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((trs_conv_frame5_kernel<2, TRS_F5_NB, TRS_F5_R, 64 * (TRS_F5_COMPUTE + 4), TRS_F5_COMPUTE>), dim3(std::min(n_img * q.bands, cu_count)), dim3(64 * (TRS_F5_COMPUTE + 4)), l.frame5_lds, s, q);
-        HIPCHK(hipGetLastError());
-        return TRS_OK;
-    }
-    if (l.frame) {
-        FrameConvParams q{};
-        q.in = static_cast<const u4v*>(in); q.w = l.w.get(); q.bias = l.bias.get(); q.out = static_cast<unsigned short*>(out);
-        q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.COUT = l.COUT; q.COUT_PAD = l.COUT_PAD; q.KH = l.KH; q.KW = l.KW;
-        q.F = l.frame_f; q.cg = l.CIN / 8; q.cgs = q.cg == 8 ? 3 : 4; q.relu = l.relu;
-        q.bands = l.frame_bands; q.ohb = l.frame_ohb; q.ihb = l.frame_ohb + l.KH - 1;
-        { auto magic = [](int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1u) / (unsigned)d); };
-          q.magic_uout = magic(q.ohb * q.OW); q.magic_ow = magic(q.OW); q.magic_bands = q.bands == 1 ? 0u : magic(q.bands); }
-        const int groups = (n_img * q.bands + q.F - 1) / q.F, grid = std::min(groups, cu_count);   // one persistent workgroup per CU
-#define LAUNCH_FRAME(NT_, HALF_)                                                                                              \
-    do {                                                                                                                      \
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_conv_frame_kernel<NT_, 2, HALF_, TRS_FRAME_R, 8, TRS_FRAME_LOADERS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL((trs_conv_frame_kernel<NT_, 2, HALF_, TRS_FRAME_R, 8, TRS_FRAME_LOADERS>), dim3(grid), dim3(64 * (8 + TRS_FRAME_LOADERS)), l.frame_lds, s, q);   \
-    } while (0)
-        // (wave items of 2 x 32 pixels x 64 channels: the host cuts the frames into bands so that a group has about 8 of them — items of 3 tiles need
-        // more than the 168 registers that 12 waves leave each)
-        if (q.cg == 8) LAUNCH_FRAME(2, 4); else LAUNCH_FRAME(2, 8);
-#undef LAUNCH_FRAME
-        HIPCHK(hipGetLastError());
-        return TRS_OK;
-    }
-    const int waves = l.res_block / 64, ntiles = (p.M + 31) / 32;
-    const int grid_x = std::max(1, std::min((ntiles + waves - 1) / waves, cu_count * l.res_wg_per_cu));
-#define LAUNCH_K(KERNEL)                                                                                                     \
-    do {                                                                                                                     \
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, l.res_lds)); \
-        hipLaunchKernelGGL((KERNEL), dim3(grid_x, l.res_ysplit), dim3(l.res_block), l.res_lds, s, p);                        \
-    } while (0)
-    if (l.u8in) LAUNCH_K(trs_conv_u8_kernel);                               // conv1 as its own layer
-    else if (l.res_span && l.res_nb == 1) LAUNCH_K((trs_conv_span_kernel<1, false>));   // conv2 unfused (24 input channels: 6 granules per pixel pair, no swizzle)
-    else if (l.res_span) LAUNCH_K((trs_conv_span_kernel<2, true>));         // conv3 where its frames do not fit LDS (240x320)
-    else if (l.res_nb == 1) LAUNCH_K(trs_conv_lt_kernel<1>);                // the fallback of every other (layer, shape)
-    else LAUNCH_K(trs_conv_lt_kernel<2>);
-#undef LAUNCH_K
-    HIPCHK(hipGetLastError());
-    return TRS_OK;
+    void (*const single[])(ConvParams) = {trs_conv_u8_kernel, trs_conv_span_kernel<1, false>, trs_conv_span_kernel<2, true>, trs_conv_lt_kernel<1>, trs_conv_lt_kernel<2>};   // in PilotKernel's order
+    return launch_lds(single[kernel], dim3(single_grid_x(l, n_img, cu_count), l.res_ysplit), dim3(l.res_block), l.res_lds, l.res_lds, s, p);
 }
 
-// K slices of trs_pilot_dense_kernel: whole LDS chunks, as many slices as give every CU a workgroup (groups of 32 NF frames x slices).
-// NF = 2 (64 frames per workgroup share every weight fragment) where the K dimension is long enough that every workgroup still gets two
-// chunks or more (240x320: 8,816 granules; at 120x160 a slice is one chunk and the kernel is launch-bound: NF = 1).
-void dense_plan(const ConvLayer& l, int n, int cu_count, const trs_pilot_tuning& T, int* gps, int* ks, int* nf_out = nullptr)
+// dense1 / dense4 as forward planned it for this batch (d): one fp32 slab per K slice, added in order by the tail kernel
+int launch_dense(const ConvLayer& cl, const DenseCall& d, const void* in, int n, trsim::DevBuf<void>& slab, hipStream_t s)
 {
-    const int G = l.G, chunks = (G + kDenseChunk - 1) / kDenseChunk;
-    int nf = 1;
-    {
-        const int groups2 = (n + 63) / 64, want2 = std::max(1, cu_count / groups2);
-        if (n >= 64 && (chunks + want2 - 1) / want2 >= 2) nf = 2;
-        if (T.dense == 2) nf = 1;                                           // tuning: dense = 2 keeps 32 frames per workgroup (A/B)
+    const size_t need = (size_t)d.KS * n * cl.p->act_elems() * sizeof(float);
+    if (slab.bytes() < need) {
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(slab.reserve(need));
     }
-    const int groups = (n + 32 * nf - 1) / (32 * nf);
-    int want = std::max(1, cu_count / groups);
-    if (T.ksplit > 0) want = T.ksplit;
-    const int cps = std::max(1, (chunks + want - 1) / want);
-    *gps = cps * kDenseChunk;
-    *ks = (G + *gps - 1) / *gps;
-    if (nf_out) *nf_out = nf;
-}
-
-int launch_dense(PilotCtx* c, const ConvLayer& l, const void* in, int n, void* slab, hipStream_t s)
-{
     DenseParams q{};
-    q.act = static_cast<const u4v*>(in); q.w = l.w.get(); q.bias = l.bias.get(); q.slab = static_cast<float*>(slab);
-    int nf = 1;
-    q.n = n; q.G = l.G;
-    dense_plan(l, n, c->cu_count, c->tun, &q.gps, &q.KS, &nf);
-    q.groups = (n + 32 * nf - 1) / (32 * nf);
-    const int grid = q.groups * ((q.KS + 7) / 8) * 8;
-    if (nf == 2) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_pilot_dense_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kDenseLds));
-        hipLaunchKernelGGL(trs_pilot_dense_kernel<2>, dim3(grid), dim3(256), 2 * kDenseLds, s, q);
-    } else {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_pilot_dense_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kDenseLds));
-        hipLaunchKernelGGL(trs_pilot_dense_kernel<1>, dim3(grid), dim3(256), kDenseLds, s, q);
-    }
-    HIPCHK(hipGetLastError());
-    return TRS_OK;
+    q.act = static_cast<const u4v*>(in); q.w = cl.w.get(); q.bias = cl.bias.get(); q.slab = static_cast<float*>(slab.get());
+    q.n = n; q.G = cl.p->G; q.gps = d.gps; q.KS = d.KS; q.groups = d.groups;
+    return launch_lds(d.nf == 2 ? trs_pilot_dense_kernel<2> : trs_pilot_dense_kernel<1>, dim3(d.grid), dim3(256), d.lds, d.lds, s, q);
 }
 
 int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n)
 {
+    const PilotPlan& P = c->plan;
     const void* in = d_frames;
-    size_t in_bytes = (size_t)n * c->H * c->W * 3;
+    size_t in_bytes = (size_t)n * P.H * P.W * 3;
     int first = 0;
     c->last_frames = d_frames; c->act0_valid = false;
-    if (c->fuse12 && !c->no_fuse) {
+    if (pilot_head_runs(P)) {
         if (in_bytes > 0x7FFFFFFFull) return trs_internal_fail(TRS_ERR_LIMIT, "frames larger than 2 GiB: lower the batch");
+        const HeadCall hc = head_call(P, n);
         Fuse12Params q = c->fuse;
         q.frames = d_frames; q.frames_bytes = (int)in_bytes; q.N = n;
-        q.c2.out = c->act[1].get(); q.c2.M = n * c->L[1].OH * c->L[1].OW;
-        q.c2.nt_out = 0;
-        int grid = std::max(1, std::min(n * q.bands * std::max(1, q.wsplit), c->cu_count));
-        // rolling bands when there are enough (frame, part) streams for every CU (a small batch keeps one band per workgroup: more parallelism)
-        q.roll = (c->tun.fuse_roll && n * std::max(1, q.wsplit) >= c->cu_count && q.bands > 1) ? 1 : 0;
-        if (q.roll) grid = std::min(n * std::max(1, q.wsplit), c->cu_count);
-        if (q.wsplit > 1) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_conv12_band_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, c->fuse_lds));
-            hipLaunchKernelGGL(trs_conv12_band_kernel<true>, dim3(grid), dim3(1024), c->fuse_lds, v.stream, q);
-        } else {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_conv12_band_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, c->fuse_lds));
-            hipLaunchKernelGGL(trs_conv12_band_kernel<false>, dim3(grid), dim3(1024), c->fuse_lds, v.stream, q);
-        }
-        HIPCHK(hipGetLastError());
+        q.c2.out = c->act[1].get(); q.c2.M = n * P.L[1].OH * P.L[1].OW; q.c2.nt_out = 0;
+        q.roll = hc.roll;
+        int rc = launch_lds(q.wsplit > 1 ? trs_conv12_band_kernel<true> : trs_conv12_band_kernel<false>, dim3(hc.grid), dim3(1024), P.head.lds, P.head.lds, v.stream, q);
+        if (rc) return rc;
         in = c->act[1].get();
-        in_bytes = (size_t)n * c->act_elems[1] * 2;
+        in_bytes = (size_t)n * P.L[1].act_elems() * 2;
         first = 2;
     }
-    c->chain_mid_valid = c->chain_first < 0;
-    for (int i = first; i < 8; ++i) {
-        if (i == c->chain_first) {                                          // conv(i + 1) .. conv7 in one launch, activations in LDS
+    c->chain_mid_valid = P.chain.first < 0;
+    for (int i = first; i < 7; ++i) {
+        if (i == P.chain.first) {                                           // conv(i + 1) .. conv7 in one launch, activations in LDS
             ChainParams q = c->chain;
             q.in = static_cast<const u4v*>(in); q.out = static_cast<unsigned short*>(c->act[6].get()); q.N = n;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_conv_chain_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, c->chain_lds));
-            hipLaunchKernelGGL(trs_conv_chain_kernel<512>, dim3((n + q.F - 1) / q.F), dim3(512), c->chain_lds, v.stream, q);
-            HIPCHK(hipGetLastError());
-            in = c->act[6].get();
-            in_bytes = (size_t)n * c->act_elems[6] * 2;
-            i = 6;
-            continue;
+            int rc = launch_lds(trs_conv_chain_kernel<kChainBlock>, dim3(chain_grid(P.chain, n)), dim3(kChainBlock), P.chain.lds, P.chain.lds, v.stream, q);
+            if (rc) return rc;
+            break;
         }
-        void* out = c->act[i].get();
-        if (i == 7) {                                                       // dense1: one fp32 slab per K slice, added in order by the tail kernel
-            { int gps; dense_plan(c->L[7], n, c->cu_count, c->tun, &gps, &c->last_slices); }
-            const size_t need = (size_t)c->last_slices * n * c->act_elems[7] * sizeof(float);
-            if (c->slab.bytes() < need) {
-                HIPCHK(hipStreamSynchronize(v.stream));
-                HIPCHK(c->slab.reserve(need));
-            }
-            out = c->slab.get();
-        }
-        int rc = i == 7 ? launch_dense(c, c->L[7], in, n, out, v.stream) : launch_conv(c->L[i], in, in_bytes, out, n, v.stream, c->cu_count);
+        int rc = launch_conv(c->L[i], in, in_bytes, c->act[i].get(), n, v.stream, P.cu_count);
         if (rc) return rc;
         if (i == 0) c->act0_valid = true;
         in = c->act[i].get();
-        in_bytes = (size_t)n * c->act_elems[i] * (c->L[i].out_f32 ? 4 : 2);
+        in_bytes = (size_t)n * P.L[i].act_elems() * 2;
     }
-    if (c->arch == TRS_PILOT_FULL_HOUSE) {                                 // the steering head's dense4 reads conv7's output as well
-        { int gps; dense_plan(c->L[8], n, c->cu_count, c->tun, &gps, &c->last_slices2); }
-        const size_t need = (size_t)c->last_slices2 * n * c->act_elems[8] * sizeof(float);
-        if (c->slab2.bytes() < need) {
-            HIPCHK(hipStreamSynchronize(v.stream));
-            HIPCHK(c->slab2.reserve(need));
-        }
-        int rc = launch_dense(c, c->L[8], c->act[6].get(), n, c->slab2.get(), v.stream);
-        if (rc) return rc;
-    }
+    const DenseCall d = dense_call(P.L[7], n, P.cu_count, P.tun);             // dense4 has dense1's shape: one plan for both
+    c->last_slices = d.KS;
+    int rc = launch_dense(c->L[7], d, c->act[6].get(), n, c->slab, v.stream);
+    if (!rc && P.arch == TRS_PILOT_FULL_HOUSE) { c->last_slices2 = d.KS; rc = launch_dense(c->L[8], d, c->act[6].get(), n, c->slab2, v.stream); }   // the steering head's dense4 reads conv7's output as well
+    if (rc) return rc;
     c->last_n = n;
+    return TRS_OK;
+}
+
+// materialise what the fused kernels of the last forward pass kept in LDS, as far as layers lo..hi need it: conv1 behind the fused head (layer 0),
+// the chain's interior layers
+int materialise_layers(PilotCtx* c, const TrsEnvView& v, int lo, int hi)
+{
+    const PilotPlan& P = c->plan;
+    if (lo == 0 && !c->act0_valid) {
+        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * P.H * P.W * 3, c->act[0].get(), c->last_n, v.stream, P.cu_count);
+        if (rc) return rc;
+        c->act0_valid = true;
+    }
+    if (P.chain.first >= 0 && hi >= P.chain.first && lo < 6 && !c->chain_mid_valid) {
+        for (int j = P.chain.first; j < 6; ++j) {
+            int rc = launch_conv(c->L[j], c->act[j - 1].get(), (size_t)c->last_n * P.L[j - 1].act_elems() * 2, c->act[j].get(), c->last_n, v.stream, P.cu_count);
+            if (rc) return rc;
+        }
+        c->chain_mid_valid = true;
+    }
     return TRS_OK;
 }
 
@@ -1882,7 +1805,7 @@ struct ActIo { const float* speed; const float* segment; const uint8_t* mode; fl
 int check_model_type(const PilotCtx* c, const trs_pilot_config* cfg)
 {
     const int mt = cfg->model_type;
-    const bool ok = c->arch == TRS_PILOT_SPD_CTL ? (mt == TRS_PILOT_SPD_CTL || mt == TRS_PILOT_CNN_2D) : mt == c->arch;
+    const bool ok = c->plan.arch == TRS_PILOT_SPD_CTL ? (mt == TRS_PILOT_SPD_CTL || mt == TRS_PILOT_CNN_2D) : mt == c->plan.arch;
     if (!ok) return trs_internal_fail(TRS_ERR_ARG, "trs_pilot_config.model_type does not match the loaded weights (22 arrays: cnn_2d_speed_control / cnn_2d; 28: cnn_2d_speed_as_feature; 42: cnn_2d_full_house)");
     return TRS_OK;
 }
@@ -1904,12 +1827,12 @@ TailParams make_tail(const PilotCtx* c, const TrsEnvView& v, int n, float* raw_o
 
 int run_tail(PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io = nullptr)
 {
-    if (c->arch != TRS_PILOT_SPD_CTL) {
+    if (c->plan.arch != TRS_PILOT_SPD_CTL) {
         TailExParams t{};
-        t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->act_elems[7];
-        t.h4 = static_cast<const float*>(c->slab2.get()); t.h4_slices = c->last_slices2; t.h4_stride = (size_t)n * c->act_elems[8];
+        t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->plan.L[7].act_elems();
+        t.h4 = static_cast<const float*>(c->slab2.get()); t.h4_slices = c->last_slices2; t.h4_stride = (size_t)n * c->plan.L[8].act_elems();
         t.blob = c->xblob.get(); std::memcpy(t.xo, c->xo, sizeof t.xo);
-        t.arch = c->arch; t.f1 = c->arch == TRS_PILOT_SPD_FTR ? 4 : 16; t.f2 = 2 * t.f1; t.f3 = 4 * t.f1;
+        t.arch = c->plan.arch; t.f1 = c->plan.arch == TRS_PILOT_SPD_FTR ? 4 : 16; t.f2 = 2 * t.f1; t.f3 = 4 * t.f1;
         t.speed = (io && io->speed) ? io->speed : v.speed; t.segment = io ? io->segment : nullptr; t.seg_idx = v.seg_idx; t.np = v.n_points > 0 ? v.n_points : 1;
         t.raw_out = raw_out; t.n = n; t.act = act ? 1 : 0;
         if (act) {
@@ -1923,7 +1846,7 @@ int run_tail(PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_
         return TRS_OK;
     }
     TailParams t = make_tail(c, v, n, raw_out, cfg, act, io);
-    t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->act_elems[7];
+    t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->plan.L[7].act_elems();
     hipLaunchKernelGGL(trs_pilot_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, v.stream, t);
     HIPCHK(hipGetLastError());
     return TRS_OK;
@@ -1950,14 +1873,7 @@ TRS_EXPORT void trs_default_pilot_config(trs_pilot_config* c)
     c->smooth_steering_enabled = 0; c->smooth_steering_threshold = 0.9f;
 }
 
-TRS_EXPORT void trs_default_pilot_tuning(trs_pilot_tuning* t)
-{
-    if (!t) return;
-    std::memset(t, 0, sizeof *t);
-    t->struct_size = (uint32_t)sizeof *t;
-    t->fuse_band_r2 = 6; t->fuse_wsplit_max = 4; t->span_layers_mask = 0x6;
-    t->fuse_roll = 1; t->frame5 = 1; t->frame_layers_mask = 0x78; t->chain_layers = 4; t->dense = 1;
-}
+TRS_EXPORT void trs_default_pilot_tuning(trs_pilot_tuning* t) { if (t) *t = pilot_default_tuning(); }
 
 TRS_EXPORT int trs_pilot_set_tuning(trs_env* e, const trs_pilot_tuning* t)
 {
@@ -1981,153 +1897,33 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
     // the context under construction is freed on EVERY early return below (HIPCHK included); released into the handle at the end
     std::unique_ptr<PilotCtx> guard(new PilotCtx());
     PilotCtx* const c = guard.get();
-    c->n_cap = v.n; c->H = v.H; c->W = v.W;
-    trs_default_pilot_tuning(&c->tun);
-    if (const trs_pilot_tuning* user = trs_internal_pilot_tuning(e)) c->tun = *user;
-    const trs_pilot_tuning& T = c->tun;
-    c->arch = n_arrays == 28 ? TRS_PILOT_SPD_FTR : (n_arrays == 42 ? TRS_PILOT_FULL_HOUSE : TRS_PILOT_SPD_CTL);
-    c->n_layers = c->arch == TRS_PILOT_FULL_HOUSE ? 9 : 8;
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, v.device) == hipSuccess && prop.multiProcessorCount > 0) c->cu_count = prop.multiProcessorCount; }
-    static const int spec[7][4] = {{5, 2, 3, 24}, {5, 2, 24, 32}, {5, 2, 32, 64}, {3, 1, 64, 64}, {3, 1, 64, 64}, {3, 1, 64, 128}, {3, 1, 128, 128}};
-    int ih = v.H, iw = v.W;
-    for (int i = 0; i < c->n_layers; ++i) {
-        ConvLayer& l = c->L[i];
-        if (i < 7) { l.KH = l.KW = spec[i][0]; l.S = spec[i][1]; l.CIN = spec[i][2]; l.COUT = spec[i][3]; l.IH = ih; l.IW = iw; }
-        else { l.KH = l.KW = 1; l.S = 1; l.CIN = ih * iw * 128; l.COUT = 100; l.IH = 1; l.IW = 1; }     // dense1 (and dense4) over the NHWC flatten:
-                                                                                                          // the kernel's first CIN rows; the rows of the small branches go to the tail
-        l.OH = (l.IH - l.KH) / l.S + 1; l.OW = (l.IW - l.KW) / l.S + 1;
-        if (l.OH < 1 || l.OW < 1) { return trs_internal_fail(TRS_ERR_LIMIT, "image too small for Keras_2D_CNN"); }
-        l.COUT_PAD = (l.COUT + 31) / 32 * 32;
-        l.u8in = (i == 0); l.relu = true; l.out_f32 = (i >= 7);
-        // granules: a kernel row is one contiguous run of KW * CIN / 8 granules in NHWC; runs are padded to whole trips of 4
-        // (zero weights) so that a trip is always 64 contiguous bytes (trs_conv_lt_kernel); dense1 is one long run
-        const int run = l.u8in ? 2 : l.KW * l.CIN / 8, run_pad = l.u8in ? 2 : (run + 3) & ~3;
-        l.G = l.KH * run_pad;
-        l.G_pad = (l.G + 3) & ~3;
-        if (i >= 7 && (l.COUT_PAD != 128 || l.G % 16 != 0)) return trs_internal_fail(TRS_ERR_LIMIT, "dense1's shape does not suit trs_pilot_dense_kernel");   // (never for Keras_2D_CNN: 100 outputs, 16 granules per pixel of conv7's output)
-        if (i < 7) {       // conv layers on their single-layer kernels: resident weights, at most 64 output channels per slice (NB <= 2 keeps 16 waves per CU in registers)
-            l.res_nb = std::min(2, l.COUT_PAD / 32);
-            l.res_ysplit = l.COUT_PAD / (32 * l.res_nb);
-            l.run_pad = run_pad;
-            // stride-2 layers with wide kernels re-fetch every byte ~2.5x through overlapping windows: span staging instead
-            const int cgr = l.CIN / 8, pix_gran = l.S * cgr;
-            const int nseg_max = 30 / l.OW + 2;
-            const int span_mask = T.span_layers_mask;                         // bit i = conv(i+1) uses the span kernel: conv2 and conv3 (0x6)
-            l.res_span = !l.u8in && l.S == 2 && l.KW >= 5 && nseg_max <= 4 && ((span_mask >> i) & 1) && l.COUT % 32 == 0;   // (whole 32-channel blocks: its epilogue stores 16 channels per lane)
-            if (l.res_span) {
-                l.span_nl = ((32 - nseg_max) * pix_gran + nseg_max * run_pad + 63) / 64;
-                if (l.span_nl > 5) l.res_span = false;
-            }
-            const int stage_per_wave = l.res_span ? l.span_nl * 1024 : 2048;  // input transpose / span stage; output transpose (all kernels)
-            auto lds_for = [&](int nb, int waves) { return l.G_pad * nb * 32 * 16 + ((l.G_pad * 4 + 15) & ~15) + nb * 32 * 4 + waves * stage_per_wave; };
-            // conv7's 64-channel slices at 7 waves beat 32-channel slices at 16 (240x320: 199 -> 143 us; the pixels are read twice instead of four times)
-            if (lds_for(l.res_nb, 7) > 160 * 1024) { l.res_nb = 1; l.res_ysplit = l.COUT_PAD / 32; }    // 32-channel slices
-            if (lds_for(l.res_nb, 4) > 160 * 1024) return trs_internal_fail(TRS_ERR_LIMIT, "a convolution's weight slice does not fit LDS");   // (never for Keras_2D_CNN)
-            // workgroups per CU and waves per workgroup: about 16 waves per CU when LDS allows
-            l.res_wg_per_cu = 1;
-            for (int wg = 4; wg >= 1; --wg) {
-                const int waves = std::max(4, 16 / wg);
-                if (wg * (lds_for(l.res_nb, waves) + 512) <= 160 * 1024) { l.res_wg_per_cu = wg; break; }
-            }
-            int waves = std::max(4, 16 / l.res_wg_per_cu);
-            if (l.res_span) waves = std::min(waves, 12);                      // trs_conv_span_kernel is built for <= 768 threads
-            while (waves > 4 && l.res_wg_per_cu * (lds_for(l.res_nb, waves) + 512) > 160 * 1024) --waves;
-            l.res_block = 64 * waves;
-            l.res_lds = lds_for(l.res_nb, waves);
-        }
-        if (i >= 3 && i < 7) {   // conv4..7: frames in LDS when they fit (240x320: conv7's 167 KB frame does not: the quad-load kernel stays)
-            const int mask = T.frame_layers_mask;                             // bit i = conv(i+1) (0x78)
-            const int cg = l.CIN / 8;
-            const bool shape_ok = l.S == 1 && l.KH == 3 && l.KW == 3 && (cg == 8 || cg == 16) && l.COUT_PAD % 64 == 0 && l.COUT == l.COUT_PAD && run_pad == l.KW * cg;
-            if (((mask >> i) & 1) && shape_ok) {
-                // Two LDS buffers (the group being computed and the next one), F units each, a unit = a frame or one of `bands` row bands of it (240x320:
-                // conv4 128 KB, conv6 97 KB, conv7 167 KB per frame).  Among the (bands, F) that fit, take the one with the fewest MFMA rounds: a group is
-                // ceil(tiles / 2) x (COUT / 64) wave items for 8 compute waves; bands re-stage KH - 1 rows each (a small penalty), every CU should get
-                // at least two groups (one to compute, one on its way).
-                int bands = 1, f = 1; double best = 1e30;
-                for (int bnd = 1; bnd <= l.OH && bnd <= 8; ++bnd) {
-                    const int ohb_ = (l.OH + bnd - 1) / bnd;
-                    const size_t unit_ = (size_t)(ohb_ + l.KH - 1) * l.IW * l.CIN * 2;
-                    for (int f_ = 1; f_ <= 8; ++f_) {
-                        if (2 * unit_ * f_ + l.COUT_PAD * 4 > 158 * 1024) break;
-                        const long groups = ((long)c->n_cap * bnd + f_ - 1) / f_;
-                        if (f_ > 1 && groups < 2 * c->cu_count) break;
-                        const int tiles = (f_ * ohb_ * l.OW + 31) / 32, items = ((tiles + 1) / 2) * (l.COUT_PAD / 64);
-                        const double rounds = (double)((items + 7) / 8), per_cu = std::ceil((double)groups / c->cu_count);
-                        const double cost = per_cu * (rounds + 0.15) * (1.0 + 0.1 * (double)(bnd - 1) * (l.KH - 1) / l.OH);   // + a barrier and a hand-over per group
-                        if (cost < best - 1e-9) { best = cost; bands = bnd; f = f_; }
-                    }
-                }
-                const int ohb = (l.OH + bands - 1) / bands;
-                const int ihb = ohb + l.KH - 1;
-                const size_t unit_bytes = (size_t)ihb * l.IW * l.CIN * 2;
-                l.frame = best < 1e29;
-                l.frame_f = f; l.frame_bands = bands; l.frame_ohb = ohb; l.frame_lds = (int)(2 * f * unit_bytes) + l.COUT_PAD * 4;
-            }
-        }
-        if (i == 2) {            // conv3: frames in LDS when two fit (120x160: 2 x 64 KB); TRS_PILOT_FRAME5 = 0: the span kernel
-            const int on = T.frame5;
-            const bool shape_ok = l.KH == 5 && l.KW == 5 && l.S == 2 && l.CIN == 32 && l.COUT == 64 && l.COUT_PAD == 64 && run_pad == 20 && l.G_pad == 100;
-            // a frame larger than ~78 KB is cut into row bands (240x320: 57 x 77 x 32 = 281 KB -> 5 bands of 6 output rows = 15 input rows, 74 KB:
-            // two workgroups of one band per CU)
-            int bands = 1;
-            while (bands < l.OH && (size_t)(bands == 1 ? l.IH : 2 * ((l.OH + bands - 1) / bands) + 3) * l.IW * 64 > 78 * 1024) ++bands;
-            const int ohb = (l.OH + bands - 1) / bands, ihb = bands == 1 ? l.IH : 2 * ohb + 3;
-            const size_t unit = (size_t)ihb * l.IW * 64;
-            // (round 3: one unit per 4-wave workgroup, two workgroups per CU; round 4: one persistent double-buffered workgroup per CU — see the kernel)
-            // (row bands at 240x320: 89 us against the span kernel's 86 in round 3, one unit per workgroup; 72.0 against 83.1 on the persistent double-buffered
-            // workgroup of round 4: bands by default where a frame does not fit)
-            if (on && shape_ok && 2 * unit + 256 <= 158 * 1024) {           // two buffers: the unit being computed and the next one
-                l.frame5 = true; l.frame5_lds = (int)(2 * unit) + 64 * 4; l.frame5_bands = bands; l.frame5_ohb = ohb;
-            }
-        }
-        // ---- pack the kernel into granules [g][cout_pad][8] of fp16 and the per-granule input offsets ----
+    // ---- plan: which kernel serves which layer, every LDS layout (trsim_pilot_plan.hpp) ----
+    const trs_pilot_tuning* const user = trs_internal_pilot_tuning(e);
+    int cu_count = 256;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, v.device) == hipSuccess && prop.multiProcessorCount > 0) cu_count = prop.multiProcessorCount; }
+    c->plan = pilot_plan(v.H, v.W, v.n, cu_count, n_arrays, user ? *user : pilot_default_tuning());
+    const PilotPlan& P = c->plan;
+    if (P.err) return trs_internal_fail(P.err, P.err_text);
+    // ---- pack the Keras arrays, allocate and upload ----
+    for (int i = 0; i < P.n_layers; ++i) {
+        const PilotLayer& l = P.L[i];
+        ConvLayer& cl = c->L[i]; cl.p = &l;
         const int ai = i == 8 ? 34 : 2 * i;                               // dense4 of the full-house model
-        const float* K = arr[ai];
-        const float* B = arr[ai + 1];
-        std::vector<unsigned short> wp((size_t)l.G_pad * l.COUT_PAD * 8, 0);
-        std::vector<int> goff(l.G_pad, 0);
-        for (int g = 0; g < l.G; ++g) {
-            if (l.u8in) {
-                const int kh = g >> 1, half = g & 1;
-                goff[g] = kh * l.IW * 3 + 8 * half;
-                for (int j = 0; j < 8; ++j) {
-                    const int f = 8 * half + j;                       // byte f of the 16-byte row window = (kw, c), 15 is padding
-                    if (f >= 15) continue;
-                    const int kw = f / 3, ch = f % 3;
-                    for (int co = 0; co < l.COUT; ++co)
-                        wp[((size_t)g * l.COUT_PAD + co) * 8 + j] = host_f2h(K[((kh * l.KW + kw) * l.CIN + ch) * l.COUT + co] * (256.0f / 255.0f));   // x 2^-8 in the epilogue (kConv1Scale)
-                }
-            } else {
-                const int kh = g / run_pad, gi = g % run_pad;                 // granule gi of kernel row kh
-                goff[g] = (kh * l.IW * l.CIN + gi * 8) * 2;
-                if (gi >= run) continue;                                      // run padding: next pixel's bytes x zero weights
-                const int c8n = l.CIN / 8, kw = gi / c8n, c8 = gi % c8n;
-                for (int j = 0; j < 8; ++j)
-                    for (int co = 0; co < l.COUT; ++co)
-                        wp[((size_t)g * l.COUT_PAD + co) * 8 + j] = host_f2h(K[((kh * l.KW + kw) * l.CIN + c8 * 8 + j) * l.COUT + co]);
-            }
-        }
-        for (int g = l.G; g < l.G_pad; ++g) goff[g] = goff[l.G - 1];       // padding granule: valid address, zero weights
-        std::vector<float> bias(l.COUT_PAD, 0.0f);
-        for (int co = 0; co < l.COUT; ++co) bias[co] = B[co];
-        std::vector<u4v> wv(wp.size() / 8);
-        std::memcpy(wv.data(), wp.data(), wp.size() * 2);
-        int rc = upload(l.w, wv); if (!rc) rc = upload(l.bias, bias); if (!rc) rc = upload(l.goff, goff);
+        const PackedLayer pk = pack_layer(l, arr[ai], arr[ai + 1]);
+        int rc = upload(cl.w, pk.w); if (!rc) rc = upload(cl.bias, pk.bias); if (!rc) rc = upload(cl.goff, pk.goff);
+        if (!rc && i == 1 && P.head.on) rc = upload(c->w2_parity, conv2_parity_order(l, pk.w));
         if (rc) return rc;
-        c->act_elems[i] = (size_t)l.OH * l.OW * l.COUT;
-        HIPCHK(c->act[i].alloc((size_t)c->n_cap * c->act_elems[i] * (l.out_f32 ? 4 : 2) + 64));
-        if (i < 7) { ih = l.OH; iw = l.OW; }
+        HIPCHK(c->act[i].alloc((size_t)P.n_cap * l.act_elems() * (l.out_f32 ? 4 : 2) + 64));
     }
     auto up = [&](trsim::DevBuf<float>& dst, const float* src, size_t n) -> int { std::vector<float> t(src, src + n); return upload(dst, t); };
-    const int nz = c->arch == TRS_PILOT_FULL_HOUSE ? 1 : 2;                // outputs of the first head
+    const int nz = P.arch == TRS_PILOT_FULL_HOUSE ? 1 : 2;                // outputs of the first head
     int rc = up(c->w2, arr[16], 100 * 50); if (!rc) rc = up(c->b2, arr[17], 50);
     if (!rc) rc = up(c->w3, arr[18], 50 * 25); if (!rc) rc = up(c->b3, arr[19], 25);
     if (!rc) rc = up(c->w4, arr[20], 25 * nz); if (!rc) rc = up(c->b4, arr[21], nz);
     if (rc) return rc;
-    if (c->arch != TRS_PILOT_SPD_CTL) {        // the small fp32 branches of the tail: one blob, offsets by XO_*
-        const int F = (int)c->L[7].CIN;
-        const int f1 = c->arch == TRS_PILOT_SPD_FTR ? 4 : 16, f2 = 2 * f1, f3 = 4 * f1;
+    if (P.arch != TRS_PILOT_SPD_CTL) {        // the small fp32 branches of the tail: one blob, offsets by XO_*
+        const int F = (int)P.L[7].CIN;
+        const int f1 = P.arch == TRS_PILOT_SPD_FTR ? 4 : 16, f2 = 2 * f1, f3 = 4 * f1;
         std::vector<float> blob;
         auto put = [&](int slot, const float* src, size_t n) { c->xo[slot] = (int)blob.size(); blob.insert(blob.end(), src, src + n); };
         put(XO_F1W, arr[22], f1); put(XO_F1B, arr[23], f1); put(XO_F2W, arr[24], (size_t)f1 * f2); put(XO_F2B, arr[25], f2);
@@ -2135,7 +1931,7 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
         put(XO_W1Y, arr[14] + (size_t)F * 100, (size_t)f3 * 100);            // dense1's rows behind the flatten
         put(XO_W2, arr[16], 100 * 50); put(XO_B2, arr[17], 50); put(XO_W3, arr[18], 50 * 25); put(XO_B3, arr[19], 25);
         put(XO_W4, arr[20], 25 * nz); put(XO_B4, arr[21], nz);
-        if (c->arch == TRS_PILOT_FULL_HOUSE) {
+        if (P.arch == TRS_PILOT_FULL_HOUSE) {
             put(XO_C1W, arr[28], f1); put(XO_C1B, arr[29], f1); put(XO_C2W, arr[30], (size_t)f1 * f2); put(XO_C2B, arr[31], f2);
             put(XO_C3W, arr[32], (size_t)f2 * f3); put(XO_C3B, arr[33], f3);
             put(XO_W4Y, arr[34] + (size_t)F * 100, (size_t)2 * f3 * 100);    // dense4's rows for [feature3 | current_spd_3]
@@ -2145,139 +1941,25 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
         rc = upload(c->xblob, blob);
         if (rc) return rc;
     }
-    {   // conv1 -> conv2 fusion: needs the 5x5/2 + 5x5/2 head of Keras_2D_CNN and an LDS tile of 2 R2 + 3 conv1 rows
-        const ConvLayer& l0 = c->L[0]; const ConvLayer& l1 = c->L[1];
-        Fuse12Params& q = c->fuse;
-        q = Fuse12Params{};
-        q.w1 = l0.w.get(); q.b1 = l0.bias.get(); q.w2 = l1.w.get();
-        q.c2 = ConvParams{};
-        q.c2.bias = l1.bias.get(); q.c2.COUT = l1.COUT; q.c2.COUT_PAD = l1.COUT_PAD; q.c2.relu = 1; q.c2.oscale = 1.0f;
+    // ---- the parameter blocks of the two fused kernels, all but their per-call fields ----
+    if (P.head.on) {
+        const PilotLayer& l0 = P.L[0]; const PilotLayer& l1 = P.L[1]; const PilotHead& h = P.head; Fuse12Params& q = c->fuse;
+        q.w1 = c->L[0].w.get(); q.b1 = c->L[0].bias.get(); q.w2 = c->w2_parity.get();
+        q.c2.bias = c->L[1].bias.get(); q.c2.COUT = l1.COUT; q.c2.COUT_PAD = l1.COUT_PAD; q.c2.relu = 1; q.c2.oscale = 1.0f;
         q.IH = l0.IH; q.IW = l0.IW; q.OH1 = l0.OH; q.OW1 = l0.OW; q.OH2 = l1.OH; q.OW2 = l1.OW;
-        {   // can conv1 leave binary16's range?  Its inputs are pixels / 256 <= 1, so |output| <= |bias| + sum |w| (x 256 / 255 and the binary16 rounding of the
-            // weights: 1.01 covers both).  Below 65504 for every output channel the fused head's conv1 epilogue needs no saturation step.
-            const float* K0 = arr[0]; const float* B0 = arr[1];
-            double worst = 0.0;
-            for (int co = 0; co < l0.COUT; ++co) {
-                double sum = std::fabs((double)B0[co]);
-                for (int k = 0; k < l0.KH * l0.KW * l0.CIN; ++k) sum += std::fabs((double)K0[(size_t)k * l0.COUT + co]) * 1.01;
-                worst = std::max(worst, sum);
-            }
-            q.c1_bounded = (worst == worst && worst < 60000.0) ? 1 : 0;      // (NaN weights: not bounded)
-        }
-        const bool shape_ok = l0.G_pad == 12 && l0.COUT_PAD == 32 && l1.G_pad == 80 && l1.COUT_PAD == 32 && l1.COUT == 32 && l1.CIN == 24 && l1.S == 2 && l1.KH == 5;
-        const bool band_ok = l0.OW >= 32 && (2 * 8 + 3) * l0.OW < 65536;   // the band kernels split a tile's first pixel on the scalar unit and let a lane wrap once
-        c->fuse12 = false; c->no_fuse = T.no_fuse != 0;
-        // band form (conv1's input staged once per band as a fp16 image): tile + band image
-        // (measured, 1024 frames of 120x160: R2 = 7 / 6 / 5 -> 129 / 114 / 125 us against 131 for the direct form; 512 frames of
-        // 240x320, where only R2 = 2 fits: 290 against 272 - bands thinner than 4 rows recompute too much of conv1)
-        const int band_r2 = T.fuse_band_r2;                               // 6; 0 = use the direct form
-        for (int r2 = std::min(band_r2, l1.OH); shape_ok && band_ok && r2 >= std::min(4, l1.OH); --r2) {
-            const int rows_in = 2 * (2 * r2 + 3) + 3, row_in = l0.IW * 3;
-            if (row_in % 16 != 0 || rows_in * row_in > kBandPf * 512 * 16) continue;
-            int off = 12 * 32 * 16;
-            q.off_w2 = off; off += 80 * 32 * 16;
-            q.off_b = off; off += 16 * 16;
-            q.off_tile = off; q.tile_bytes = (((2 * r2 + 3) * 2 * ((l0.OW + 1) / 2) * 48 + 128) + 15) & ~15; off += q.tile_bytes;   // two column-parity planes per row
-            q.off_band = off; q.band_bytes = rows_in * row_in * 2 + 64; off += q.band_bytes;
-            if (off <= 160 * 1024) { c->fuse12 = true; c->fuse_r2 = r2; c->fuse_lds = off; q.R2 = r2; q.bands = (l1.OH + r2 - 1) / r2; q.wsplit = 1; break; }
-        }
-        // the band cut in width (240x320: a whole-width band does not fit): parts of w2p conv2 columns, each with its own conv1 tile and
-        // staged frame-row segments (a part re-stages 2 x 3 + 3 input columns and recomputes 3 conv1 columns of its neighbour)
-        const int max_split = T.fuse_wsplit_max;                          // 4; 1 = never cut in width
-        for (int ws = 2; shape_ok && !c->fuse12 && band_r2 > 0 && ws <= max_split; ++ws) {
-            const int w2p = (l1.OW + ws - 1) / ws, w1m = 2 * w2p + 3;          // every part w2p conv2 columns wide (the last one overlaps its neighbour)
-            if (w2p < 15 || w2p > l1.OW || w1m * 19 >= 65536) continue;
-            const int cpr = ((2 * w1m + 3) * 3 + 15) / 16;
-            for (int r2 = std::min(band_r2, l1.OH); r2 >= std::min(4, l1.OH); --r2) {
-                const int rows_in = 2 * (2 * r2 + 3) + 3;
-                if (rows_in * cpr > kBandPf * 512) continue;
-                int off = 12 * 32 * 16;
-                q.off_w2 = off; off += 80 * 32 * 16;
-                q.off_b = off; off += 16 * 16;
-                q.off_tile = off; q.tile_bytes = (((2 * r2 + 3) * 2 * (w2p + 2) * 48 + 128) + 15) & ~15; off += q.tile_bytes;
-                q.off_band = off; q.band_bytes = rows_in * cpr * 32 + 64; off += q.band_bytes;
-                if (off > 160 * 1024) continue;
-                c->fuse12 = true; c->fuse_r2 = r2; c->fuse_lds = off; q.R2 = r2; q.bands = (l1.OH + r2 - 1) / r2;
-                q.wsplit = ws; q.w2p = w2p; q.cpr = cpr;
-                q.magic_full = (unsigned)((0x100000000ull + (unsigned)w1m - 1u) / (unsigned)w1m);
-                q.magic_cpr = (unsigned)((0x100000000ull + (unsigned)cpr - 1u) / (unsigned)cpr);
-                break;
-            }
+        q.R2 = h.R2; q.bands = h.bands; q.wsplit = h.wsplit; q.w2p = h.w2p; q.cpr = h.cpr; q.magic_full = h.magic_full; q.magic_cpr = h.magic_cpr;
+        q.off_w2 = h.off_w2; q.off_b = h.off_b; q.off_tile = h.off_tile; q.tile_bytes = h.tile_bytes; q.off_band = h.off_band; q.band_bytes = h.band_bytes;
+        q.c1_bounded = conv1_bounded(l0, arr[0], arr[1]);
+    }
+    if (P.chain.first >= 0) {
+        const PilotChain& h = P.chain; ChainParams& q = c->chain;
+        q.F = h.F; q.nl = h.nl; q.split_first = h.split_first; q.offA = h.offA; q.offB = h.offB; q.off_bias = h.off_bias;
+        for (int j = 0; j < h.nl; ++j) {
+            const PilotLayer& l = P.L[h.first + j]; const ConvLayer& cl = c->L[h.first + j];
+            q.L[j] = ChainLayer{cl.w.get(), cl.bias.get(), l.IH, l.IW, l.OH, l.OW, l.COUT, l.CIN / 8, l.CIN / 8 == 8 ? 3 : 4, h.nt[j], h.nb[j], h.magic_uout[j], h.magic_ow[j]};
         }
     }
-    if (c->fuse12) {                            // the band kernel reads conv1 columns by parity: conv2's granules in that order
-        const ConvLayer& l1 = c->L[1];
-        std::vector<u4v> orig((size_t)l1.G_pad * l1.COUT_PAD), perm(orig.size());
-        HIPCHK(hipMemcpy(orig.data(), l1.w.get(), orig.size() * sizeof(u4v), hipMemcpyDeviceToHost));
-        for (int kh = 0; kh < 5; ++kh)
-            for (int sl = 0; sl < 16; ++sl) {
-                const int src = sl < 9 ? (2 * (sl / 3)) * 3 + sl % 3 : (sl < 15 ? (2 * ((sl - 9) / 3) + 1) * 3 + (sl - 9) % 3 : 15);   // granule kw * 3 + c8 of the kernel row
-                std::memcpy(&perm[(size_t)(kh * 16 + sl) * l1.COUT_PAD], &orig[(size_t)(kh * 16 + src) * l1.COUT_PAD], (size_t)l1.COUT_PAD * sizeof(u4v));
-            }
-        int rcw = upload(c->w2_parity, perm);
-        if (rcw) return rcw;
-        c->fuse.w2 = c->w2_parity.get();
-    }
-    {   // conv4..conv7 (or conv5..conv7) as one launch when F frames of all their activations fit LDS; TRS_PILOT_CHAIN = 0: off, 3 / 4: layers
-        const int want = T.chain_layers;
-        c->chain_first = -1;
-        for (int nl = std::min(want, 4); nl >= 3 && c->chain_first < 0; --nl) {
-            const int first = 7 - nl;
-            bool ok = true;
-            for (int i = first; i < 7; ++i) {
-                const ConvLayer& l = c->L[i];
-                ok = ok && l.frame && l.COUT == l.COUT_PAD && l.CIN == (i == 6 ? 128 : 64) && (l.COUT == 64 || l.COUT == 128);
-            }
-            if (!ok) continue;
-            auto out_bytes = [&](int i) { return (size_t)c->L[i].OH * c->L[i].OW * c->L[i].COUT * 2; };
-            auto in_bytes_of = [&](int i) { return (size_t)c->L[i].IH * c->L[i].IW * c->L[i].CIN * 2; };
-            for (int f = 4; f >= 2 && c->chain_first < 0; f -= 2) {
-                if (f > 2 && (c->n_cap + f - 1) / f < c->cu_count) continue;          // keep a workgroup per CU
-                const bool split = nl == 4;
-                size_t a, b;
-                if (split) { a = std::max(f * out_bytes(3), f * out_bytes(5)); b = std::max((size_t)(f / 2) * in_bytes_of(3), f * out_bytes(4)); }
-                else { a = std::max(f * in_bytes_of(4), f * out_bytes(5)); b = f * out_bytes(4); }
-                a = (a + 15) & ~(size_t)15; b = (b + 15) & ~(size_t)15;
-                const size_t total = a + b + 4 * 128 * 4;
-                if (total > 158 * 1024) continue;
-                ChainParams& q = c->chain;
-                q = ChainParams{};
-                constexpr int nw = 8;                                               // waves per workgroup, one workgroup per CU
-                q.F = f; q.nl = nl; q.split_first = split ? 1 : 0; q.offA = 0; q.offB = (int)a; q.off_bias = (int)(a + b);
-                for (int j = 0; j < nl; ++j) {
-                    const ConvLayer& l = c->L[first + j];
-                    // item shape per layer: items = ceil(pixels / (32 nt)) x (COUT / (32 nb)), dealt round-robin to 8 waves; waves w and w + 4 share
-                    // a SIMD (one workgroup per CU): the shape that leaves the busiest SIMD the fewest MFMAs per k-step, and among equals the one
-                    // that gives that SIMD two waves (a lone wave per SIMD exposes every LDS and L2 round trip: stamps, profiles/r03_pilot_chain.txt)
-                    const int px = (split && j == 0 ? f / 2 : f) * l.OH * l.OW;
-                    auto busiest = [&](int nt, int nb, int& waves_on_it) {
-                        const int items = ((px + 32 * nt - 1) / (32 * nt)) * (l.COUT / (32 * nb));
-                        int worst = 0; waves_on_it = 0;
-                        for (int sd = 0; sd < 4; ++sd) {
-                            int n_items = 0, n_waves = 0;
-                            for (int w = sd; w < nw; w += 4) { const int mine = items > w ? (items - w + nw - 1) / nw : 0; n_items += mine; n_waves += mine > 0; }
-                            if (n_items * nt * nb > worst) { worst = n_items * nt * nb; waves_on_it = n_waves; }
-                        }
-                        return worst;
-                    };
-                    // the better tile height (2 or 3 tiles of 32 pixels) for items of 64 output channels (items of 32 channels — twice the ring depth,
-                    // two waves on every SIMD — were measured in round 3: the kernel 105 k against 107 k clocks, the closed loop equal; removed in round 4, and measured once
-                    // more for conv7 alone, whose 64-channel items are 6 for 8 waves or 4 lone waves: chain 46.3 -> 47.5 us, for every layer 49.5; conv7 on ten single-tile
-                    // items of 64 channels (three per busy SIMD instead of four lone waves): 43.4 -> 46.5 us — twice the weight stream per MFMA)
-                    int nt = 2, best = 1 << 30, best_waves = 0;
-                    for (int cnt = 3; cnt >= 2; --cnt) {
-                        int wv = 0;
-                        const int m = busiest(cnt, 2, wv);
-                        if (m < best || (m == best && wv > best_waves)) { best = m; best_waves = wv; nt = cnt; }
-                    }
-                    auto magic = [](int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1u) / (unsigned)d); };
-                    q.L[j] = ChainLayer{l.w.get(), l.bias.get(), l.IH, l.IW, l.OH, l.OW, l.COUT, l.CIN / 8, l.CIN / 8 == 8 ? 3 : 4, nt, 2, magic(l.OH * l.OW), magic(l.OW)};
-                }
-                c->chain_first = first; c->chain_lds = (int)total;
-            }
-        }
-    }
-    HIPCHK(c->raw.alloc((size_t)c->n_cap * 2 * sizeof(float)));
+    HIPCHK(c->raw.alloc((size_t)P.n_cap * 2 * sizeof(float)));
     *slot = guard.release();
     return TRS_OK;
 }
@@ -2288,13 +1970,13 @@ TRS_EXPORT int trs_pilot_forward(trs_env* e, const uint8_t* d_frames, int n_imag
     if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
     if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
-    if (n_images < 1 || n_images > c->n_cap) return trs_internal_fail(TRS_ERR_ARG, "n_images must be in [1, n_envs]");
+    if (n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "n_images must be in [1, n_envs]");
     HIPCHK(hipSetDevice(v.device));
     if (!d_frames) {
         if (!v.latest_frame || n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs a rendered step and n_images == n_envs");
         d_frames = v.latest_frame;
     }
-    if (c->arch != TRS_PILOT_SPD_CTL && n_images != v.n)
+    if (c->plan.arch != TRS_PILOT_SPD_CTL && n_images != v.n)
         return trs_internal_fail(TRS_ERR_ARG, "this model type also reads speed (and segment): use trs_pilot_forward_ex, or n_images == n_envs for the env's own");
     return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw.get(), nullptr, false);
 }
@@ -2305,8 +1987,8 @@ TRS_EXPORT int trs_pilot_forward_ex(trs_env* e, const uint8_t* d_frames, const f
     if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
     if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
-    if (n_images < 1 || n_images > c->n_cap) return trs_internal_fail(TRS_ERR_ARG, "n_images must be in [1, n_envs]");
-    if ((!d_speed || (c->arch == TRS_PILOT_FULL_HOUSE && !d_segment)) && n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "the env's own speed / segment need n_images == n_envs");
+    if (n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "n_images must be in [1, n_envs]");
+    if ((!d_speed || (c->plan.arch == TRS_PILOT_FULL_HOUSE && !d_segment)) && n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "the env's own speed / segment need n_images == n_envs");
     HIPCHK(hipSetDevice(v.device));
     if (!d_frames) {
         if (!v.latest_frame || n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs a rendered step and n_images == n_envs");
@@ -2322,10 +2004,10 @@ TRS_EXPORT int trs_pilot_forward_host_ex(trs_env* e, const uint8_t* h_frames, co
     if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
     if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
-    if (!h_frames || !h_out || n_images < 1 || n_images > c->n_cap) return trs_internal_fail(TRS_ERR_ARG, "bad argument (n_images must be in [1, n_envs])");
-    if (c->arch != TRS_PILOT_SPD_CTL && (!h_speed || (c->arch == TRS_PILOT_FULL_HOUSE && !h_segment))) return trs_internal_fail(TRS_ERR_ARG, "this model type needs speed (and segment) arrays");
+    if (!h_frames || !h_out || n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "bad argument (n_images must be in [1, n_envs])");
+    if (c->plan.arch != TRS_PILOT_SPD_CTL && (!h_speed || (c->plan.arch == TRS_PILOT_FULL_HOUSE && !h_segment))) return trs_internal_fail(TRS_ERR_ARG, "this model type needs speed (and segment) arrays");
     HIPCHK(hipSetDevice(v.device));
-    const size_t bytes = (size_t)n_images * c->H * c->W * 3, extra = (size_t)n_images * 8;
+    const size_t bytes = (size_t)n_images * c->plan.H * c->plan.W * 3, extra = (size_t)n_images * 8;
     if (bytes + extra > c->tmp_cap) {
         HIPCHK(hipStreamSynchronize(v.stream));
         c->tmp_cap = 0;
@@ -2337,7 +2019,7 @@ TRS_EXPORT int trs_pilot_forward_host_ex(trs_env* e, const uint8_t* h_frames, co
     HIPCHK(hipMemcpyAsync(c->tmp_frames.get(), h_frames, bytes, hipMemcpyHostToDevice, v.stream));
     if (h_speed) HIPCHK(hipMemcpyAsync(d_spd, h_speed, (size_t)n_images * 4, hipMemcpyHostToDevice, v.stream));
     if (h_segment) HIPCHK(hipMemcpyAsync(d_seg, h_segment, (size_t)n_images * 4, hipMemcpyHostToDevice, v.stream));
-    int rc = c->arch == TRS_PILOT_SPD_CTL ? trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get())
+    int rc = c->plan.arch == TRS_PILOT_SPD_CTL ? trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get())
                                           : trs_pilot_forward_ex(e, c->tmp_frames.get(), h_speed ? d_spd : nullptr, h_segment ? d_seg : nullptr, n_images, c->raw.get());
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
@@ -2352,9 +2034,9 @@ TRS_EXPORT int trs_pilot_forward_host(trs_env* e, const uint8_t* h_frames, int n
     if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
     if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
-    if (!h_frames || !h_out || n_images < 1 || n_images > c->n_cap) return trs_internal_fail(TRS_ERR_ARG, "bad argument (n_images must be in [1, n_envs])");
+    if (!h_frames || !h_out || n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "bad argument (n_images must be in [1, n_envs])");
     HIPCHK(hipSetDevice(v.device));
-    const size_t bytes = (size_t)n_images * c->H * c->W * 3;
+    const size_t bytes = (size_t)n_images * c->plan.H * c->plan.W * 3;
     if (bytes > c->tmp_cap) {
         HIPCHK(hipStreamSynchronize(v.stream));
         c->tmp_cap = 0;
@@ -2365,7 +2047,7 @@ TRS_EXPORT int trs_pilot_forward_host(trs_env* e, const uint8_t* h_frames, int n
     int rc = trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get());
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-    trs_internal_count(e, (uint64_t)n_images * 2 * sizeof(float), (uint64_t)n_images * c->H * c->W * 3);
+    trs_internal_count(e, (uint64_t)n_images * 2 * sizeof(float), (uint64_t)n_images * c->plan.H * c->plan.W * 3);
     HIPCHK(hipStreamSynchronize(v.stream));
     return TRS_OK;
 }
@@ -2377,24 +2059,12 @@ TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t
     PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
     if (!c || !c->last_n) return trs_internal_fail(TRS_ERR_STATE, "no forward pass yet");
     if (layer < 0 || layer > 7 || !h_dst) return trs_internal_fail(TRS_ERR_ARG, "bad layer");
-    const size_t total = (size_t)c->last_n * c->act_elems[layer];
+    const size_t total = (size_t)c->last_n * c->plan.L[layer].act_elems();
     if (n_floats != total) return trs_internal_fail(TRS_ERR_ARG, "size mismatch");
     HIPCHK(hipSetDevice(v.device));
-    if (layer == 0 && !c->act0_valid) {                                     // the fused head never wrote conv1's activation: run the unfused conv1 now
-        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * c->H * c->W * 3, c->act[0].get(), c->last_n, v.stream, c->cu_count);
-        if (rc) return rc;
-        c->act0_valid = true;
-    }
-    if (c->chain_first >= 0 && layer >= c->chain_first && layer < 6 && !c->chain_mid_valid) {   // the chain kept these activations in LDS: run the single layers now
-        for (int j = c->chain_first; j < 6; ++j) {
-            const void* src = j == 0 ? (const void*)c->last_frames : c->act[j - 1].get();
-            int rc = launch_conv(c->L[j], src, (size_t)c->last_n * c->act_elems[j - 1] * 2, c->act[j].get(), c->last_n, v.stream, c->cu_count);
-            if (rc) return rc;
-        }
-        c->chain_mid_valid = true;
-    }
+    { int rc = materialise_layers(c, v, layer, layer); if (rc) return rc; }   // what the fused kernels kept in LDS: only what this layer needs
     HIPCHK(hipStreamSynchronize(v.stream));
-    if (c->L[layer].out_f32) {                                              // dense1: add the K-slice slabs in slice order, then the ReLU (both live in the tail kernel)
+    if (c->plan.L[layer].out_f32) {                                              // dense1: add the K-slice slabs in slice order, then the ReLU (both live in the tail kernel)
         std::vector<float> part(total);
         for (size_t i = 0; i < total; ++i) h_dst[i] = 0.0f;
         for (int sl = 0; sl < c->last_slices; ++sl) {
@@ -2410,24 +2080,6 @@ TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t
     return TRS_OK;
 }
 
-// materialise what the fused kernels of the last forward pass kept in LDS (conv1 behind the fused head, the chain's interior layers)
-static int materialise_layers(PilotCtx* c, const TrsEnvView& v, int upto)
-{
-    if (!c->act0_valid) {
-        int rc = launch_conv(c->L[0], c->last_frames, (size_t)c->last_n * c->H * c->W * 3, c->act[0].get(), c->last_n, v.stream, c->cu_count);
-        if (rc) return rc;
-        c->act0_valid = true;
-    }
-    if (c->chain_first >= 0 && upto >= c->chain_first && !c->chain_mid_valid) {
-        for (int j = c->chain_first; j < 6; ++j) {
-            int rc = launch_conv(c->L[j], c->act[j - 1].get(), (size_t)c->last_n * c->act_elems[j - 1] * 2, c->act[j].get(), c->last_n, v.stream, c->cu_count);
-            if (rc) return rc;
-        }
-        c->chain_mid_valid = true;
-    }
-    return TRS_OK;
-}
-
 TRS_EXPORT int trs_pilot_range_check(trs_env* e, uint64_t h_out[8])
 {
     TrsEnvView v;
@@ -2436,11 +2088,11 @@ TRS_EXPORT int trs_pilot_range_check(trs_env* e, uint64_t h_out[8])
     if (!c || !c->last_n) return trs_internal_fail(TRS_ERR_STATE, "no forward pass yet");
     if (!h_out) return trs_internal_fail(TRS_ERR_ARG, "null output");
     HIPCHK(hipSetDevice(v.device));
-    { int rc = materialise_layers(c, v, 6); if (rc) return rc; }
+    { int rc = materialise_layers(c, v, 0, 6); if (rc) return rc; }
     unsigned long long* const scratch = v.stats + 24;                       // stats[24..30]: this call's per-layer counts; stats[3]: running total
     HIPCHK(hipMemsetAsync(scratch, 0, 8 * sizeof(unsigned long long), v.stream));
     for (int i = 0; i < 7; ++i) {
-        const size_t n = (size_t)c->last_n * c->act_elems[i];
+        const size_t n = (size_t)c->last_n * c->plan.L[i].act_elems();
         const int grid = (int)std::min<size_t>(4096, (n + 255) / 256);
         hipLaunchKernelGGL(trs_pilot_count_sat_kernel, dim3(grid), dim3(256), 0, v.stream, static_cast<const unsigned short*>(c->act[i].get()), n, scratch + i, v.stats + 3);
     }
@@ -2463,8 +2115,8 @@ TRS_EXPORT int trs_pilot_act(trs_env* e, const trs_pilot_config* cfg, const uint
     if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
     if (!cfg || cfg->struct_size != sizeof(trs_pilot_config)) return trs_internal_fail(TRS_ERR_ARG, "trs_pilot_config.struct_size mismatch");
     { int rm = check_model_type(c, cfg); if (rm) return rm; }
-    if (!d_steer || !d_thr || !d_brk || n < 0 || n > c->n_cap) return trs_internal_fail(TRS_ERR_ARG, "null output or n out of range (n <= n_envs)");
-    if ((!d_speed || (c->arch == TRS_PILOT_FULL_HOUSE && !d_segment)) && n != v.n) return trs_internal_fail(TRS_ERR_ARG, "the env's own speed / segment need n == n_envs");
+    if (!d_steer || !d_thr || !d_brk || n < 0 || n > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "null output or n out of range (n <= n_envs)");
+    if ((!d_speed || (c->plan.arch == TRS_PILOT_FULL_HOUSE && !d_segment)) && n != v.n) return trs_internal_fail(TRS_ERR_ARG, "the env's own speed / segment need n == n_envs");
     HIPCHK(hipSetDevice(v.device));
     if (n == 0) return TRS_OK;
     if (!d_frames) {
