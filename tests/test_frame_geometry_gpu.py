@@ -184,6 +184,64 @@ def test_lens_at_geometry(make_env, checker, size, path):
     print(f"[frame geometry] {tag}: largest float difference {_MAXDIFF[tag]:.3g}")
 
 
+DEEP_POSTS = 19                                 # posts without a sync: more than 2 x kSlots (8 posts in flight) and more than 4 x kCamDepth (4 hand-off slots per env)
+DEEP_LENS_W = 48                                # D's 44 is no multiple of 8 (the lens is refused there, below): the next width it takes, as C' is to C
+
+
+@gpu
+@pytest.mark.parametrize("case", list(CASES) + ["lens+depth"])
+def test_variant_resident_deep_queue(make_env, checker, case):
+    """The worker's hand-off where the other tests hardly reach it: size D (five envs per workgroup in batches of 4 + 1, a ragged last workgroup), 19 steps
+    posted without a sync — the slot ring wraps (r >= kCamDepth), the physics team runs into the back-pressure of rread, the deferred rread bump of the
+    LIGHT variants is what frees a slot, and arrivals lag a full `keep` — then three lock-step ticks with per-env host controls and a reset mask on the second.
+    The references and tolerances are test_variant_at_geometry's (test_lens_at_geometry's for the lens), after the posts and after every tick."""
+    lens = case == "lens+depth"
+    H, W = (GEOMETRY["D"][0], DEEP_LENS_W) if lens else (height_of("D", case), width_of("D", case))
+    n = GEOMETRY["D"][2](device_cus())
+    settings, _ = (dict(depth=True), V_LENS | V_DEPTH) if lens else CASES[case]
+    depth, filt, light = settings.get("depth", False), settings.get("filt"), settings.get("light", False)
+    kw = dict(n_envs=n, track=track_points(settings.get("track", "generated")), img_h=H, img_w=W, depth=depth, auto_reset=True)
+    g, o = make_env("hip", **kw), make_env("oracle", **kw)
+    p = params_for(n, 21) if light else None
+    if filt:
+        g.set_frame_filter(filt)
+        if not light:
+            o.set_frame_filter(filt)
+    if light:
+        g.set_lighting(p)
+    if lens:
+        g.set_camera(*LENS)
+    tag = f"geometry/D {H}x{W} n={n}/{case}/deep queue"
+
+    def check(where):
+        if lens:
+            compare(g, o, f"{tag}: {where}", tag)
+            want, want_depth = expected_frames(checker, g, LENS)
+            bad = np.argwhere((g.fetch("img") != want).any(-1))
+            assert bad.size == 0, f"{tag}: {where}: {len(bad)} pixels differ from the checker, first (env, v, u) {bad[:4].tolist()}"
+            bad = np.argwhere(g.fetch("depth").view(np.uint32) != want_depth.view(np.uint32))
+            assert bad.size == 0, f"{tag}: {where}: {len(bad)} depth words differ, first (env, v, u) {bad[:4].tolist()}"
+        elif light:
+            compare(g, o, f"{tag}: {where}", tag)
+            assert_lit(g, o, p, f"{tag}: {where}", depth, cfg=filt)
+        else:
+            compare(g, o, f"{tag}: {where}", tag, frames=True, depth=depth)
+
+    st, th, rs = controls(n, 3, 17)
+    g.set_step_mode(True)
+    for env in (g, o):
+        env.step_synthetic(DEEP_POSTS, 1)
+    check(f"{DEEP_POSTS} posts")
+    for t in range(3):
+        for env in (g, o):
+            env.step(st[t], th[t], 0.0, reset=rs if t == 1 else None)
+        g.sync()
+        check(f"lock-step tick {t}")
+    assert g.step_mode()[0] == "resident"
+    assert int(g.fetch("stats")[2]) == 0        # no layout fault: the worker really ran
+    print(f"[frame geometry] {tag}: largest float difference {_MAXDIFF[tag]:.3g}")
+
+
 @gpu
 @pytest.mark.parametrize("size", ["B", "D"])
 def test_lens_is_refused_where_the_width_is_no_multiple_of_8(make_env, size):

@@ -92,6 +92,9 @@ struct LensBlock {
     int wh;                             // W/2
 };
 __host__ __device__ inline size_t lens_block_offset(int blob_bytes) { return hill_block_offset(blob_bytes) + ((sizeof(HillBlock) + 63) & ~(size_t)63); }
+// the two blocks as a kernel reaches them (a uniform address: scalar loads)
+__device__ __forceinline__ const HillBlock* hill_block(const RParams& p) { return reinterpret_cast<const HillBlock*>(p.blob + hill_block_offset(p.blob_bytes)); }
+__device__ __forceinline__ const LensBlock* lens_block(const RParams& p) { return reinterpret_cast<const LensBlock*>(p.blob + lens_block_offset(p.blob_bytes)); }
 
 struct FParams {                        // ImgPreprocessing with dynamic brightness, evaluated inside the step kernels (their DYN instantiations)
     double baseline;
@@ -696,7 +699,7 @@ __device__ __forceinline__ uint32_t hill_filter_colour(const trsim::HillBlock& h
 // lg (LIGHT instantiations): the env's lighting parameters in LDS, applied to every colour of the row before the static filter (the sky and far colours are raw then)
 __device__ __forceinline__ float hill_row_build(const RParams& p, unsigned char* lds, unsigned tab_off, float P, int v, const float* lg = nullptr)   // returns the row's row_k (0: sky or beyond the far plane)
 {
-    const trsim::HillBlock hb = *reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes));   // (uniform address: scalar loads)
+    const trsim::HillBlock hb = *hill_block(p);   // (uniform address: scalar loads)
     float sp, cp;
     spec_sincos(P, sp, cp);
     const float yn = (hb.hh - ((float)v + 0.5f)) * hb.inv_f;
@@ -816,7 +819,7 @@ __device__ __forceinline__ unsigned light_wave_palette(const RParams& p, unsigne
 {
     const unsigned dst = pal0 + (unsigned)((wave % light_copies(p.gpr)) * p.H * 16);
     const int lo = (64 * wave) / p.gpr, hi = min((64 * wave + 63) / p.gpr, p.rows_per_pass - 1);
-    const trsim::HillBlock& hb = *reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes));
+    const trsim::HillBlock& hb = *hill_block(p);
     float gb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) gb[k] = lg[k];
@@ -1343,7 +1346,7 @@ __device__ __forceinline__ void stage_lds_dma(const unsigned char* blob, int byt
 // the lens palette global -> LDS (raster team, in front of the prologue's barrier)
 __device__ __forceinline__ void lens_stage_palette(const RParams& p, unsigned lds_off, int wave, int lane)
 {
-    const trsim::LensBlock* lb = reinterpret_cast<const trsim::LensBlock*>(p.blob + trsim::lens_block_offset(p.blob_bytes));
+    const trsim::LensBlock* lb = lens_block(p);
     stage_lds_dma(reinterpret_cast<const unsigned char*>(lb->pal), trsim::kLensPalBytes, lds_off, wave, kRasterThreads / 64, lane);
 }
 

@@ -112,6 +112,16 @@ __global__ __launch_bounds__(kPhysBlock) void trs_physics_kernel(const PParams p
     env_store(p, e, st, lane);
 }
 
+// The pose of env j's frame of step sidx (ring: lcam[step][cam_stride], prev: the poses of the step before the launch, staged in the prologue): any step of
+// the launch is there once the physics team has finished it for the env (pprog).  The view pitch of a track with elevation lies the same way (HILLS).
+template <typename T>
+__device__ __forceinline__ T pose_of(const int* pprog, const T* ring, const T* prev, int cam_stride, int sidx, int j)
+{
+    if (sidx < 0) return prev[j];
+    while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
+    return ring[sidx * cam_stride + j];
+}
+
 template <bool DEPTH, bool DYN, bool HILLS = false, bool LENS = false, bool LIGHT = false>   // HILLS: a track with elevation (its own instantiations: the flat kernels' loops do not change for it);
 __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)           // LENS: the lens camera on a flat track (likewise); LIGHT: scene lighting (flat or HILLS)
 {
@@ -141,14 +151,14 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
     const int lds_off_pitch = lds.pitch, lds_off_hill = lds.hill;
     float* const lpitch = reinterpret_cast<float*>(smem + lds_off_pitch);
     int* const hbar = reinterpret_cast<int*>(smem + lds_off_hill + hill_batch(p.H) * hill_table_bytes(p.H));
-    const trsim::HillBlock* const hill = HILLS ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes)) : nullptr;
+    const trsim::HillBlock* const hill = HILLS ? hill_block(p) : nullptr;
     if (HILLS && tid == 0) *hbar = 0;
     // scene lighting (LIGHT): the workgroup's lighting parameters float[cam_stride][8], read once per launch (a call's frames all use the values as they stood when it
     // started), then the raster waves' lit palettes (light_wave_palette) — behind the row tables of a track with elevation, else where those would sit
     const int lds_off_light = lds.light;
     float* const llight = reinterpret_cast<float*>(smem + lds_off_light);
     const unsigned lds_off_lpal = (unsigned)lds_off_light + (unsigned)sp.cam_stride * 32u;
-    const int lfilt = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->filt : 0;   // (once per kernel)
+    const int lfilt = LIGHT ? hill_block(p)->filt : 0;   // (once per kernel)
     if constexpr (DYN) {
         if (tid < 32) reinterpret_cast<int*>(smem + sp.fp.lds_off + 4 * p.H * 16)[tid] = 0;   // esum[2][4][3], dbar
         dyn_stage_tables(smem, sp.fp, p.H, tid, kBlock, reinterpret_cast<const uint32_t*>(p.blob + p.off_pal));                   // OpenCV's reciprocals + the in-range byte masks (behind the prologue's barrier)
@@ -171,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
         }
         if (LENS && raster_team && rendering) lens_stage_palette(p, (unsigned)lds_off_hill, wave, lane);   // the lens palette sits where a hilly track keeps its row tables
         if (LIGHT && raster_team && rendering) {
-            const float* const lsrc = reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->light + (size_t)e_begin * 8;
+            const float* const lsrc = hill_block(p)->light + (size_t)e_begin * 8;
             for (int j = tid; j < (e_end - e_begin) * 8; j += kRasterThreads) llight[j] = lsrc[j];
         }
         if (has_c) lcam_prev[tid] = cv;
@@ -244,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
     trsim::LensBlock lb{};
     LensCacheStep<DEPTH> lcache;
     if constexpr (LENS) {
-        lb = *reinterpret_cast<const trsim::LensBlock*>(p.blob + trsim::lens_block_offset(p.blob_bytes));   // (uniform address: scalar loads)
+        lb = *lens_block(p);   // (uniform address: scalar loads)
         lens_cache_load(p, rth, lb, lcache);                   // this thread's table entries, once for every frame of the kernel
     }
     for (int sidx = sp.r_first; sidx <= sp.r_last; ++sidx) {
@@ -270,11 +280,8 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
                 cams[bi] = make_float4(0.f, 0.f, 0.f, 1.f); Pv[bi] = 0.f;
                 if (bi < nb) {
                     const int j = e - e_begin + bi;
-                    if (sidx < 0) { cams[bi] = lcam_prev[j]; Pv[bi] = lpitch[max(sp.n_phys, 1) * sp.cam_stride + j]; }
-                    else {
-                        while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
-                        cams[bi] = lcam[sidx * sp.cam_stride + j]; Pv[bi] = lpitch[sidx * sp.cam_stride + j];
-                    }
+                    cams[bi] = pose_of(pprog, lcam, lcam_prev, sp.cam_stride, sidx, j);
+                    Pv[bi] = sidx < 0 ? lpitch[max(sp.n_phys, 1) * sp.cam_stride + j] : lpitch[sidx * sp.cam_stride + j];   // (its view pitch lies the same way, behind the same wait)
                 }
             }
             auto never = [](bool) { return false; };                          // (a launch has no abort: every raster wave arrives)
@@ -287,14 +294,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
         }
         if constexpr (LENS) {
             // ---- the lens camera: every row of the frame from the per-pixel table (no uniform rows: sky and far pixels follow the lens per pixel)
-            float4 cam;
-            const int j = e - e_begin;
-            if (sidx < 0) cam = lcam_prev[j];
-            else {
-                while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
-                cam = lcam[sidx * sp.cam_stride + j];
-            }
-            raster_lens_frame(p, rth, lb, lcache, (unsigned)lds_off_hill, frame_desc<DEPTH>(p, img, dep, e), cam);
+            raster_lens_frame(p, rth, lb, lcache, (unsigned)lds_off_hill, frame_desc<DEPTH>(p, img, dep, e), pose_of(pprog, lcam, lcam_prev, sp.cam_stride, sidx, e - e_begin));
             continue;
         }
         if constexpr (DYN) {
@@ -311,14 +311,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
             for (int bi = 0; bi < kDynBatch; ++bi) {
                 const int eb = e + bi;
                 cams[bi] = make_float4(0.f, 0.f, 0.f, 1.f);
-                if (eb < e_end) {
-                    const int j = eb - e_begin;
-                    if (sidx < 0) cams[bi] = lcam_prev[j];
-                    else {
-                        while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
-                        cams[bi] = lcam[sidx * sp.cam_stride + j];
-                    }
-                }
+                if (eb < e_end) cams[bi] = pose_of(pprog, lcam, lcam_prev, sp.cam_stride, sidx, eb - e_begin);
             }
             (void)raster_dyn_batch<DEPTH, LIGHT>(p, sp.fp, rth, smem, cams, min(kDynBatch, e_end - e), img, dep, e, it, tid, lane, [](bool) { return false; },   // a launch has no abort: every raster wave arrives
                                                  LIGHT ? llight + (e - e_begin) * 8 : nullptr, lds_off_lpal);
@@ -331,15 +324,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
         if constexpr (LIGHT && !HILLS && !DYN) rl.pal_off = light_wave_palette(p, lds_off_lpal, llight + (e - e_begin) * 8, lfilt, wave, lane);
         if (!((sp.skip_uniform >> (abs_step & 1u)) & 1)) raster_uniform_rows<DEPTH>(p, rl, fd);
         // -- rows that see the track
-        float4 cam;
-        const int j = e - e_begin;
-        if (sidx < 0) {
-            cam = lcam_prev[j];                                               // written by the previous launch, staged in the prologue
-        } else {                                                              // wait until the physics team has finished this step of env j
-            while (__hip_atomic_load(&pprog[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < sidx + 1) __builtin_amdgcn_s_sleep(2);
-            cam = lcam[sidx * sp.cam_stride + j];
-        }
-        raster_ground_rows<DEPTH>(p, rl, fd, cam);
+        raster_ground_rows<DEPTH>(p, rl, fd, pose_of(pprog, lcam, lcam_prev, sp.cam_stride, sidx, e - e_begin));
     }
     }
     STAMP(5);

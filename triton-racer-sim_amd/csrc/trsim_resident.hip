@@ -522,8 +522,8 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
     const int lds_off_light = worker_lds_light(wp.lds_off_hill, p.H, variant_bits(DEPTH, DYN, HILLS, LENS, LIGHT));   // (worker_lds_layout)
     float* const lring = reinterpret_cast<float*>(smem + lds_off_light);
     const unsigned lds_off_lpal = (unsigned)lds_off_light + (unsigned)(kCamDepth * epw * 32);
-    const float* const light_g = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->light : nullptr;
-    const int lfilt = LIGHT ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes))->filt : 0;   // (once per launch)
+    const float* const light_g = LIGHT ? hill_block(p)->light : nullptr;
+    const int lfilt = LIGHT ? hill_block(p)->filt : 0;   // (once per launch)
     if constexpr (DYN) {
         if (tid < 32) reinterpret_cast<int*>(smem + wp.fp.lds_off + kDynBatch * p.H * 16)[tid] = 0;   // channel sums, team-barrier counter
         dyn_stage_tables(smem, wp.fp, p.H, tid, kBlock, reinterpret_cast<const uint32_t*>(p.blob + p.off_pal));                   // the filter's tables, once per launch: the raster waves' steady state issues no loads
@@ -587,8 +587,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                 // integration goes in front of them (256 envs 3.74 -> 3.52 us per step, 128 envs the same).  With two envs per workgroup it changes nothing (512 envs:
                 // 4.97 against 5.01 us), with four the physics team runs ahead anyway and its priority only displaces raster waves (1024 envs: -5 %; profiles/r05_physics_chain.txt).
                 if (n_loc <= TRS_PHYS_PRIO_MAX_ENVS) __builtin_amdgcn_s_setprio(3);
-                env_advance<true, false>(P, lphys, e, st, (uint32_t)s, synth, steer, thr, brk, rin, lane, o,
-                                         HILLS ? reinterpret_cast<const trsim::HillBlock*>(p.blob + trsim::hill_block_offset(p.blob_bytes)) : nullptr);
+                env_advance<true, false>(P, lphys, e, st, (uint32_t)s, synth, steer, thr, brk, rin, lane, o, HILLS ? hill_block(p) : nullptr);
                 if (n_loc <= TRS_PHYS_PRIO_MAX_ENVS) __builtin_amdgcn_s_setprio(0);
                 if (o.do_reset) lr = epr_before;
                 if constexpr (LIGHT) {                        // this step's lighting parameters of the env, in LDS before the counter moves (drain_lds below)
@@ -642,7 +641,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
     trsim::LensBlock lb{};
     LensCacheWorker<DEPTH> lcache;
     if constexpr (LENS) {
-        lb = *reinterpret_cast<const trsim::LensBlock*>(p.blob + trsim::lens_block_offset(p.blob_bytes));   // (uniform address: scalar loads)
+        lb = *lens_block(p);   // (uniform address: scalar loads)
         lens_cache_load(p, rth, lb, lcache);                   // this thread's table entries, once for every frame of the kernel
     }
     // (the lens camera: the host sets uni_rows = 0, so the counts below are the lens frame's rows, one store instruction each (+1 with depth) as in the
