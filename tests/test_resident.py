@@ -127,6 +127,38 @@ def test_resident_mixed_with_launches_resets_and_idle_exit(make_env):
     assert_frames_equal(g, o, "resident -> launches -> resident")
 
 
+def test_resident_held_host_controls_over_more_steps_than_slots(make_env):
+    """One trs_step_host call holds its host arrays over 19 steps — more than the 8 staging slots: the floats are carried from slot to slot and the
+    call waits for a step's slot inside its loop; the reset mask belongs to the first step alone.  Then 9 held steps without a brake array, then
+    single steps.  The camera worker (37 envs, 60x80) and the physics worker (9 envs, render=False)."""
+    for n, kw in ((37, dict(img_h=60, img_w=80)), (9, dict(render=False))):
+        g, o = make_env("hip", n_envs=n, auto_reset=True, **kw), make_env("oracle", n_envs=n, auto_reset=True, **kw)
+        g.set_step_mode(True)
+        rng = np.random.default_rng(37 + n)
+
+        def check(where):
+            assert_state_equal(g, o, f"{n} envs, {where}")
+            if kw.get("render", True):
+                assert_frames_equal(g, o, f"{n} envs, {where}")
+            assert g.fetch("stats")[2] == 0, where
+
+        st, th, br = controls(rng, n)
+        rs = rng.uniform(0, 1, n) < 0.1
+        rs[n // 2] = True                                        # (at least one env is reset whatever the draw)
+        for env in (g, o):
+            env.step(st, th, br, reset=rs, n_steps=19)
+        check("19 held steps with a reset mask")
+        st2, th2, _ = controls(rng, n)
+        for env in (g, o):
+            env.step(st2, th2, None, n_steps=9)
+        check("9 held steps without a brake array")
+        for k in range(3):
+            st, th, br = controls(rng, n)
+            for env in (g, o):
+                env.step(st, th, br)
+            check(f"single step {k}")
+
+
 @pytest.mark.parametrize("n,h,w,depth", [(2048, 120, 160, False), (24, 240, 320, True), (300, 60, 80, True)])
 def test_resident_shapes(make_env, n, h, w, depth):
     """Several envs per workgroup (state in LDS, step-major physics), the depth frame, ragged last workgroup."""

@@ -33,7 +33,6 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdlib>
-#include <cstddef>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -44,36 +43,9 @@
 #include "trsim_device.hpp"
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
+#include "trsim_post.hpp"
 
 namespace trsim {
-
-constexpr int kSlots = 8;       // posts in flight: ring entries, arrival counters, done flags
-
-struct WEntry {                 // one posted step: ONE 64-B line, so the dispatcher learns of a post and gets it in one PCIe read
-    uint64_t seq_lo;            // step index + 1: the tag of the line's FIRST 32-byte half, written by the host after steer / thr / brk
-    const float* steer; const float* thr; const float* brk;
-    const uint8_t* reset;
-    uint32_t synth, pad0;
-    uint64_t seq;               // step index + 1, written LAST: the tag of the second half.  The line is a valid post for step s iff
-                                // seq_lo == seq == s + 1 — should the device's 64-byte read ever be served as two 32-byte requests, a
-                                // stale half cannot pair with a fresh one (each half carries its own tag, written after its payload)
-    uint64_t pad1;
-};
-static_assert(sizeof(WEntry) == 64, "one entry per 64-B line");
-constexpr int kTagLo = 0, kTagHi = 6;   // u64 word indices of the two tags within a line
-static_assert(offsetof(WEntry, seq_lo) == 8 * kTagLo && offsetof(WEntry, seq) == 8 * kTagHi && offsetof(WEntry, reset) == 32, "tag placement");
-
-struct Mailbox {                // pinned host memory the device reads and writes over PCIe
-    alignas(64) uint64_t close;             // host -> device: leave once everything posted is done
-    uint64_t posted;                        // host bookkeeping: steps [0, posted) have been posted (the device reads the entries' tags)
-    alignas(64) uint64_t exited;            // device -> host: the dispatcher has decided to leave (kExitNormal), or it found the launch NOT co-resident
-                                            //   (kExitNotCoresident: another worker — of another process — holds part of the CUs; nothing was consumed)
-    uint64_t consumed;                      //   ... and every step below this index is processed by the time the kernel ends
-    uint64_t error;                         //   non-zero: a bounded wait gave up (code << 32 | block)
-    uint64_t started;                       //   1 = every workgroup of this launch has reported in: the launch is co-resident and serves posts
-    alignas(64) uint64_t done[kSlots];      // device -> host: done[s % 8] = s + 1 when step s is complete in memory
-    alignas(64) WEntry ring[kSlots];        // host -> device
-};
 
 struct DevCtl {                 // device memory; touched only by sc1 accesses and atomics
     alignas(64) unsigned long long word;    // posted count | kExitBit | kAbortBit, republished by the dispatcher
@@ -108,34 +80,22 @@ constexpr unsigned kDefaultLifeUs = 50000;
 #ifndef TRS_PHYS_PRIO_MAX_ENVS
 #define TRS_PHYS_PRIO_MAX_ENVS 1   /* envs per workgroup up to which a physics wave integrates at raised priority (0 = never: A/B builds) */
 #endif
-constexpr unsigned kRetryMs0 = 100;
 
 struct Resident {
-    bool enabled = false, running = false;
-    bool broken = false;                 // a worker gave up (bounded wait): some workgroups may have taken a step others did not — the env
-                                         // state is undefined until the track is loaded again; every resident call fails meanwhile
+    PostLedger led;                      // what has been posted, launched and seen complete, and which mode the handle is in (trsim_post.hpp)
     PinnedBuf<Mailbox> mb;               // (mapped, coherent: the worker and the host talk through it)
     DevBuf<DevCtl> dc;
     hipStream_t sC = nullptr;            // copies while the worker owns the handle's stream
-    uint64_t base = 0;                   // steps [base, step_count) were handed to the worker since the last quiesce
-    uint64_t seen_done = 0;              // every step below this index has been observed complete
-    bool launched = false;               // steps were LAUNCHED on the handle's stream since the last wait (trs_step_pilot in resident mode): no
-                                         // completion flag will ever be written for them — the stream is what to wait for
-    bool fell_back = false;              // a launch of the worker was found not co-resident (another process's worker on the GPU): the handle went
-                                         // back to TRS_STEP_LAUNCH by itself (trs_last_error() says so); trs_set_step_mode selects resident mode again
     uint64_t gen_start = 0; Variant gen_variant = 0;    // the running (or last) launch of the worker: its first step and its kernel variant (what it rendered: worker_rendered)
     bool dc_ready = false; uint64_t dc_ready_for = 0;   // the device control block has been zeroed and set up for a launch that starts at this step (handle_exit does it for the NEXT launch)
     std::chrono::steady_clock::time_point t_launch{};   // when the running worker was launched (the host gives up on a launch that never reports in)
-    std::chrono::steady_clock::time_point t_fallback{}; // when the handle went back to launches; resident mode is tried again retry_ms later
-    unsigned retry_ms = kRetryMs0;                      //   ... doubling up to 2 s while the GPU stays shared
     unsigned idle_us = 2000;
     unsigned life_us = kDefaultLifeUs;   // a worker leaves after this long whatever happens and the next post (or the one that raced) starts a new one
                                          // (trs_resident_debug_lifetime: tests force many generations).  50 ms since round 5 (0.5 s before): the gap
                                          // between two generations is where ANOTHER process's kernels get CUs — its launches, or its own worker,
                                          // which then holds the GPU for its 50 ms: processes that share a GPU take turns at the reference's tick
                                          // rate (20 Hz, car_templates/manage.py:38) or better, and a worker restart (~35 us) per 50 ms costs 0.1 %
-    PinnedBuf<> hctl;                    // pinned staging for host-array controls: [kSlots] x (3 float[n] + uint8[n])
-    size_t hctl_slot = 0;
+    PinnedBuf<> hctl;                    // pinned staging for host-array controls: kSlots slots (stage_slot_bytes, trsim_post.hpp)
     int lds_bytes = 0, lds_off_ctl = 0, lds_off_dyn = 0, lds_off_hill = 0;
     long long pw_capacity_envs = 0;      // physics-only handles: envs whose workgroups the GPU holds at once (worker_fits)
     int pw_capacity_lds = -1;            //   ... asked for this LDS need
@@ -149,8 +109,6 @@ using namespace trsim;
 using u64 = unsigned long long;
 
 constexpr u64 kExitBit = 1ull << 63, kAbortBit = 1ull << 62, kCountMask = kAbortBit - 1;
-constexpr u64 kExitNormal = 1ull, kExitNotCoresident = 2ull;     // Mailbox::exited
-constexpr u64 kCloseLeave = 1ull, kCloseCancel = 2ull;            // Mailbox::close: leave once everything posted is done / the host has given up on this launch
 constexpr int kFellBack = trsim::kResidentFellBack;               // internal return code (> 0: not an error): the handle has just gone back to launch mode
 
 // ---- one resident worker per GPU (per process) -----------------------------------------------------------------------
@@ -464,7 +422,7 @@ __device__ __forceinline__ int wait_posted(const WParams& wp, const WLds& l, Dut
         if ((spins & 255u) == 255u) {
             const u64 now = (u64)wall_clock64();
             if (t0 == 0) t0 = now;
-            else if (now - t0 > wp.safety_ticks) { worker_abort(wp, l, 1u); return 0; }
+            else if (now - t0 > wp.safety_ticks) { worker_abort(wp, l, kGiveUpPost); return 0; }
         }
     }
 }
@@ -502,7 +460,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
         if (tid == 0) {
             atomicAdd(&p.stats[2], 1ull);
             sys_store64(p.fault, 1ull);
-            sys_store64(&wp.mb->error, (9ull << 32) | (u64)blockIdx.x);
+            sys_store64(&wp.mb->error, ((u64)kGiveUpLdsBase << 32) | (u64)blockIdx.x);
             __hip_atomic_fetch_or(&wp.dc->word, kAbortBit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (blockIdx.x == 0) { sys_store64(&wp.mb->consumed, wp.start); sys_store64(&wp.mb->exited, 1ull); }
         }
@@ -567,7 +525,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
             for (int j = pw - first; j < n_loc; j += nphys) {
                 const int e = e_begin + j;
                 // back-pressure: slot r % kCamDepth is free once every raster wave has read step r - kCamDepth of this env
-                if (r >= kCamDepth && !wait_lds_ge(wp, l, &D, &l.rread[j], (r - kCamDepth + 1) * (kRasterThreads / 64), 2u, lane)) return;
+                if (r >= kCamDepth && !wait_lds_ge(wp, l, &D, &l.rread[j], (r - kCamDepth + 1) * (kRasterThreads / 64), kGiveUpCamRing, lane)) return;
                 float steer = 0.f, thr = 0.f, brk = 0.f;
                 uint8_t rin = 0;
                 if (!synth) {
@@ -621,7 +579,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                 if ((spins & 1023u) == 1023u) {
                     const u64 now = (u64)wall_clock64();
                     if (t0 == 0) t0 = now;
-                    else if (now - t0 > wp.safety_ticks) { worker_abort(wp, l, 4u); break; }
+                    else if (now - t0 > wp.safety_ticks) { worker_abort(wp, l, kGiveUpForward); break; }
                 }
             }
         }
@@ -723,7 +681,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     const int j = b0 + bi;
                     cams[bi] = make_float4(0.f, 0.f, 0.f, 1.f);
                     if (j < n_loc) {
-                        if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, 3u, lane)) return;
+                        if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, kGiveUpPhysics, lane)) return;
                         const float* const sl = l.slot + ((size_t)(r & (kCamDepth - 1)) * epw + j) * kSlotWords;
                         cams[bi] = *reinterpret_cast<const float4*>(sl);
                         if ((j % (kRasterThreads / 64)) == wave) { mine_j = j; tel = __float_as_uint(sl[4 + min(lane, 12)]); }
@@ -737,7 +695,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     if (lds_load64(l.word) & kAbortBit) return true;
                     const u64 now = (u64)wall_clock64();
                     if (first) { t0_bar = now; return false; }
-                    if (now - t0_bar > wp.safety_ticks) { worker_abort(wp, l, 5u); return true; }
+                    if (now - t0_bar > wp.safety_ticks) { worker_abort(wp, l, kGiveUpBarrier); return true; }
                     return false;
                 };
                 if (!raster_dyn_batch<DEPTH, LIGHT>(p, wp.fp, rth, smem, cams, min(kDynBatch, n_loc - b0), img, dep, e_begin + b0, r * nbatch + b0 / kDynBatch, tid, lane, bail,
@@ -772,7 +730,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     cams[bi] = make_float4(0.f, 0.f, 0.f, 1.f); Pv[bi] = 0.f;
                     const int j = b0 + bi;
                     if (bi < nb) {
-                        if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, 3u, lane)) return;
+                        if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, kGiveUpPhysics, lane)) return;
                         const float* const sl = l.slot + ((size_t)(r & (kCamDepth - 1)) * epw + j) * kSlotWords;
                         cams[bi] = *reinterpret_cast<const float4*>(sl);
                         Pv[bi] = sl[17];
@@ -786,7 +744,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     if (lds_load64(l.word) & kAbortBit) return true;
                     const u64 now = (u64)wall_clock64();
                     if (first) { t0_bar = now; return false; }
-                    if (now - t0_bar > wp.safety_ticks) { worker_abort(wp, l, 5u); return true; }
+                    if (now - t0_bar > wp.safety_ticks) { worker_abort(wp, l, kGiveUpBarrier); return true; }
                     return false;
                 };
                 const int done_before = (r * nbatch + b0 / HB) * 2 * (kRasterThreads / 64);
@@ -812,7 +770,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
             // so the counted waits of the arrivals are unchanged.
             for (int j = 0; j < n_loc; ++j) {
                 const FrameDesc fd = frame_desc<DEPTH>(p, img, dep, e_begin + j);
-                if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, 3u, lane)) return;
+                if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, kGiveUpPhysics, lane)) return;
                 const float* const sl = l.slot + ((size_t)(r & (kCamDepth - 1)) * epw + j) * kSlotWords;
                 const float4 cam = *reinterpret_cast<const float4*>(sl);
                 const bool mine = (j % (kRasterThreads / 64)) == wave;
@@ -855,7 +813,7 @@ __global__ __launch_bounds__(kBlock) void trs_worker_kernel(const WParams wp)   
                     raster_arrive(l, owed++, lane);
                 }
             const u64 tq0 = probe ? now_clk() : 0;
-            if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, 3u, lane)) return;
+            if (!wait_lds_ge(wp, l, nullptr, &l.pprog[j], r + 1, kGiveUpPhysics, lane)) return;
             if (probe) t_pose += now_clk() - tq0;
             const float* const sl = l.slot + ((size_t)(r & (kCamDepth - 1)) * epw + j) * kSlotWords;
             const float4 cam = *reinterpret_cast<const float4*>(sl);
@@ -912,7 +870,7 @@ __global__ __launch_bounds__(kPwBlock) void trs_physics_worker_kernel(const WPar
         if (tid == 0) {
             atomicAdd(&P.stats[2], 1ull);
             sys_store64(P.fault, 1ull);
-            sys_store64(&wp.mb->error, (9ull << 32) | (u64)blockIdx.x);
+            sys_store64(&wp.mb->error, ((u64)kGiveUpLdsBase << 32) | (u64)blockIdx.x);
             __hip_atomic_fetch_or(&wp.dc->word, kAbortBit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (blockIdx.x == 0) { sys_store64(&wp.mb->consumed, wp.start); sys_store64(&wp.mb->exited, 1ull); }
         }
@@ -945,7 +903,7 @@ __global__ __launch_bounds__(kPwBlock) void trs_physics_worker_kernel(const WPar
             if ((spins & 1023u) == 1023u) {
                 const u64 now = (u64)wall_clock64();
                 if (t0 == 0) t0 = now;
-                else if (now - t0 > wp.safety_ticks) { worker_abort(wp, l, 4u); break; }
+                else if (now - t0 > wp.safety_ticks) { worker_abort(wp, l, kGiveUpForward); break; }
             }
         }
         return;
@@ -1059,9 +1017,6 @@ __global__ void trs_worker_init_kernel(DevCtl* dc, u64 start)
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-inline uint64_t host_load(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
-inline void host_store(uint64_t* p, uint64_t v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
-
 // the worker's LDS need with the track that is loaded NOW (a larger track may have been loaded since resident mode was selected)
 // and the frame filter that is set NOW (the dynamic-brightness filter adds the per-env palettes of a batch of four envs)
 int worker_fits(trs_env* e)
@@ -1111,7 +1066,7 @@ int worker_launch(trs_env* e, uint64_t start)
     {   // one worker per GPU: the worker of another handle of this process leaves first (the caller holds the device's lock)
         DeviceSlot& D = slot_of(e);
         trs_env* const other = D.owner;
-        if (other && other != e && other->res && other->res->running) (void)evict(other);   // (a worker that gave up is gone all the same: its handle reports it)
+        if (other && other != e && other->res && other->res->led.running) (void)evict(other);   // (a worker that gave up is gone all the same: its handle reports it)
         D.owner = e;
     }
     host_store(&mb->exited, 0); host_store(&mb->consumed, start); host_store(&mb->error, 0);
@@ -1142,7 +1097,7 @@ int worker_launch(trs_env* e, uint64_t start)
         hipLaunchKernelGGL(trs_physics_worker_kernel, dim3(grid), dim3(kPwBlock), R->lds_bytes, e->sP, wp);
     }
     HIPCHK(hipGetLastError());
-    R->running = true;
+    R->led.worker_launched();
     R->t_launch = std::chrono::steady_clock::now();
     return TRS_OK;
 }
@@ -1160,14 +1115,9 @@ int worker_error(trs_env* e)
 {
     const uint64_t err = host_load(&e->res->mb->error);
     if (!err) return TRS_OK;
-    e->res->broken = true;
+    e->res->led.gave_up();
     e->uniform_ok.invalidate();                              // waves left in the middle of frames
-    static const char* const what[] = {"", "waiting for a post", "camera ring back-pressure", "waiting for the physics team", "forwarding the last arrivals",
-                                       "team barrier of the dynamic-brightness batch", "", "abort injected by trs_resident_debug_abort (test hook)", "",
-                                       "dynamic LDS segment not at offset 0"};
-    const unsigned code = (unsigned)(err >> 32);
-    return trs_internal_fail(TRS_ERR_DEVICE, std::string("resident worker gave up (") + (code < 10 ? what[code] : "?") + ") in workgroup " +
-                                                 std::to_string((unsigned)err));
+    return trs_internal_fail(TRS_ERR_DEVICE, std::string("resident worker gave up (") + give_up_text((unsigned)(err >> 32)) + ") in workgroup " + std::to_string((unsigned)err));
 }
 
 // The launch was not co-resident (dispatcher_checkin) or never reported in (wait_done's deadline): the GPU is shared with the worker of another
@@ -1177,41 +1127,35 @@ int worker_error(trs_env* e)
 int fall_back_to_launches(trs_env* e, uint64_t consumed, const char* why)
 {
     Resident* R = e->res;
-    const uint64_t posted = host_load(&R->mb->posted);
-    R->enabled = false;
-    R->fell_back = true;
-    R->t_fallback = std::chrono::steady_clock::now();
-    if (consumed > R->seen_done) R->seen_done = consumed;
-    for (uint64_t s = consumed; s < posted; ++s) {
+    R->led.fall_back(std::chrono::steady_clock::now());
+    R->led.observe(consumed);
+    for (uint64_t s = consumed, posted = host_load(&R->mb->posted); s < posted; ++s) {
         const WEntry& en = R->mb->ring[s & (kSlots - 1)];
-        if (en.seq != s + 1 || en.seq_lo != s + 1)
-            return trs_internal_fail(TRS_ERR_DEVICE, "resident worker: the post of step " + std::to_string(s) + " is no longer in the ring");
-        int rc = trs_internal_replay_launch(e, Controls{en.steer, en.thr, en.brk, en.reset, (int)en.synth, 0}, s);
-        if (rc) return rc;
+        if (!whole_post(en, s)) return trs_internal_fail(TRS_ERR_DEVICE, "resident worker: the post of step " + std::to_string(s) + " is no longer in the ring");
+        { int rc = trs_internal_replay_launch(e, Controls{en.steer, en.thr, en.brk, en.reset, (int)en.synth, 0}, s); if (rc) return rc; }
     }
-    R->launched = true;                                      // these steps have no completion flag: the stream is what to wait for
-    R->base = R->seen_done = e->step_count;
-    for (int k = 0; k < kSlots; ++k) { host_store(&R->mb->ring[k].seq, 0); host_store(&R->mb->ring[k].seq_lo, 0); host_store(&R->mb->done[k], 0); }
+    R->led.note_launch(e->step_count);                       // these steps have no completion flag: the stream is what to wait for
+    forget_ring(R->mb.get());
     trs_internal_note(std::string("resident worker: ") + why + " - another process's worker holds CUs of this GPU; the handle has gone back to TRS_STEP_LAUNCH "
-                      "(resident mode is tried again by itself after " + std::to_string(R->retry_ms) + " ms; trs_get_step_mode tells)");
+                      "(resident mode is tried again by itself after " + std::to_string(R->led.retry_ms) + " ms; trs_get_step_mode tells)");
     return kFellBack;
 }
 
 // the worker has said it leaves (or has been told to): wait for the kernel, restart it if posts raced with its exit.
 // relaunch = false (eviction by another handle): posts that raced stay in the ring, the handle's next call starts a worker from seen_done.
-int handle_exit(trs_env* e, bool relaunch = true)
+// cancelled (give_up_on_launch): whatever the launch says of itself, the handle goes back to launches.
+int handle_exit(trs_env* e, bool relaunch = true, bool cancelled = false)
 {
     Resident* R = e->res;
-    HIPCHK(hipStreamSynchronize(e->sP));
-    R->running = false;
-    int rc = worker_error(e);
-    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(e->sP));                       // (a cancelled launch: bounded by the other worker's lifetime (50 ms) or idle time)
+    R->led.worker_ended();
+    { int rc = worker_error(e); if (rc) return rc; }
     const uint64_t consumed = host_load(&R->mb->consumed), posted = host_load(&R->mb->posted);
     worker_rendered(e, consumed);
-    if (host_load(&R->mb->exited) == kExitNotCoresident)
-        return fall_back_to_launches(e, consumed, "the launch did not get every CU within 2 ms");
-    if (consumed > R->seen_done) R->seen_done = consumed;   // the kernel has ended: everything it consumed is complete
-    if (host_load(&R->mb->started)) R->retry_ms = kRetryMs0;   // this launch had the GPU: the sharing that caused an earlier fallback is over
+    if (cancelled) return fall_back_to_launches(e, consumed, "the launch had not started after 250 ms");
+    if (host_load(&R->mb->exited) == kExitNotCoresident) return fall_back_to_launches(e, consumed, "the launch did not get every CU within 2 ms");
+    R->led.observe(consumed);                               // the kernel has ended: everything it consumed is complete
+    if (host_load(&R->mb->started)) R->led.worker_had_the_gpu();
     if (consumed < posted && relaunch) return worker_launch(e, consumed);
     if (consumed == posted) {                               // nothing left to serve: the next launch of this handle starts here — its control block is set up now
         hipLaunchKernelGGL(trs_worker_init_kernel, dim3(1), dim3(256), 0, e->sP, R->dc.get(), (u64)consumed);
@@ -1223,12 +1167,9 @@ int handle_exit(trs_env* e, bool relaunch = true)
 // another handle of this process wants the GPU for its worker: this one finishes what was posted and leaves
 int evict(trs_env* other)
 {
-    Resident* R = other->res;
-    int rc = TRS_OK;
-    if (R->running) {
-        host_store(&R->mb->close, kCloseLeave);
-        rc = handle_exit(other, false);                      // (kFellBack: it left for launch mode — the GPU is free of it just the same)
-    }
+    if (!other->res->led.running) return TRS_OK;
+    host_store(&other->res->mb->close, kCloseLeave);
+    const int rc = handle_exit(other, false);                // (kFellBack: it left for launch mode — the GPU is free of it just the same)
     return rc < 0 ? rc : TRS_OK;
 }
 
@@ -1236,43 +1177,33 @@ int evict(trs_env* other)
 // process's worker).  Cancel it (the dispatcher leaves at its first look, or serves what it had already begun) and go back to launches.
 int give_up_on_launch(trs_env* e)
 {
-    Resident* R = e->res;
-    host_store(&R->mb->close, kCloseCancel);
-    HIPCHK(hipStreamSynchronize(e->sP));                       // bounded by the other worker's lifetime (50 ms) or idle time
-    R->running = false;
-    int rc = worker_error(e);
-    if (rc) return rc;
-    worker_rendered(e, host_load(&R->mb->consumed));
-    return fall_back_to_launches(e, host_load(&R->mb->consumed), "the launch had not started after 250 ms");
+    host_store(&e->res->mb->close, kCloseCancel);
+    return handle_exit(e, true, true);
 }
+
+// the newest steps are launches on the handle's stream (a fall-back's replay of the posts, resident_note_launch): the stream is what to wait for
+int wait_stream(trs_env* e) { HIPCHK(hipStreamSynchronize(e->sP)); e->res->led.absorb(e->step_count); return TRS_OK; }
 
 int wait_done(trs_env* e, uint64_t s)
 {
     Resident* R = e->res;
-    if (s < R->seen_done) return TRS_OK;
+    PostLedger& L = R->led;
+    if (s < L.seen_done) return TRS_OK;
     Mailbox* mb = R->mb.get();
     const auto t0 = std::chrono::steady_clock::now();
-    auto fell_back = [&]() -> int {                           // the posted steps went onto the stream as launches: wait for the stream
-        HIPCHK(hipStreamSynchronize(e->sP));
-        R->launched = false;
-        R->base = R->seen_done = e->step_count;
-        return TRS_OK;
-    };
     for (unsigned spins = 0;; ++spins) {
-        if (host_load(&mb->done[s & (kSlots - 1)]) >= s + 1) { R->seen_done = s + 1; return TRS_OK; }
+        if (host_load(&mb->done[s & (kSlots - 1)]) >= s + 1) { L.observe(s + 1); return TRS_OK; }
         if ((spins & 63u) == 63u) {
-            if (R->running && host_load(&mb->exited)) {
+            if (L.running && host_load(&mb->exited)) {
                 int rc = handle_exit(e);
-                if (rc == kFellBack) return fell_back();
-                if (rc) return rc;
-                if (s < R->seen_done) return TRS_OK;
-            } else if (!R->running) {
-                if (host_load(&mb->posted) > R->seen_done) { int rc = worker_launch(e, R->seen_done); if (rc) return rc; }
+                if (rc) return rc == kFellBack ? wait_stream(e) : rc;   // (fell back: the posted steps went onto the stream as launches)
+                if (s < L.seen_done) return TRS_OK;
+            } else if (!L.running) {
+                if (host_load(&mb->posted) > L.seen_done) { int rc = worker_launch(e, L.seen_done); if (rc) return rc; }
             } else if ((spins & 4095u) == 4095u && !host_load(&mb->started) &&
                        std::chrono::steady_clock::now() - R->t_launch > std::chrono::milliseconds(250)) {
                 int rc = give_up_on_launch(e);
-                if (rc == kFellBack) return fell_back();
-                if (rc) return rc;
+                if (rc) return rc == kFellBack ? wait_stream(e) : rc;
             }
             if (host_load(&mb->error)) { (void)handle_exit(e); return worker_error(e); }
             if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10))
@@ -1280,6 +1211,15 @@ int wait_done(trs_env* e, uint64_t s)
         }
         __builtin_ia32_pause();
     }
+}
+
+// ring slot, counters, done flag and staging slot of s % kSlots are free: step s - kSlots has been seen done.  kFellBack: the handle went back to
+// launch mode meanwhile and the caller launches the rest of its steps itself.
+int claim_slot(trs_env* e, uint64_t s)
+{
+    if (!e->res->led.must_wait(s)) return TRS_OK;
+    int rc = wait_done(e, s - kSlots);
+    return rc ? rc : e->res->led.enabled ? TRS_OK : kFellBack;
 }
 
 int ensure_resident(trs_env* e)
@@ -1298,8 +1238,7 @@ int ensure_resident(trs_env* e)
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
         HIPCHK(hipStreamCreateWithPriority(&R->sC, hipStreamNonBlocking, greatest));
     }
-    R->hctl_slot = ((size_t)e->n * 13 + 63) & ~(size_t)63;
-    HIPCHK(R->hctl.alloc(R->hctl_slot * kSlots, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(R->hctl.alloc(stage_slot_bytes((size_t)e->n) * kSlots, hipHostMallocMapped | hipHostMallocCoherent));
     return TRS_OK;
 }
 
@@ -1307,8 +1246,8 @@ int ensure_resident(trs_env* e)
 
 namespace trsim {
 
-bool resident_on(const trs_env* e) { return e && e->res && e->res->enabled; }
-bool resident_selected(const trs_env* e) { return e && e->res && (e->res->enabled || e->res->fell_back); }   // (fell back: resident_retry selects it again by itself)
+bool resident_on(const trs_env* e) { return e && e->res && e->res->led.enabled; }
+bool resident_selected(const trs_env* e) { return e && e->res && (e->res->led.enabled || e->res->led.fell_back); }   // (fell back: resident_retry selects it again by itself)
 
 // A handle that went back to launches because the GPU was shared with another process's worker tries resident mode again by itself:
 // called in front of every step call.  The step that follows starts a worker; if the GPU is still shared the launch is called off
@@ -1316,52 +1255,33 @@ bool resident_selected(const trs_env* e) { return e && e->res && (e->res->enable
 void resident_retry(trs_env* e)
 {
     Resident* R = e ? e->res : nullptr;
-    if (!R || R->enabled || !R->fell_back || R->broken || !R->mb.get()) return;
+    if (!R || !R->led.fell_back || !R->mb.get()) return;
     DevLock lock(e);
-    if (std::chrono::steady_clock::now() - R->t_fallback < std::chrono::milliseconds(R->retry_ms)) return;
-    if (worker_fits(e) != TRS_OK) return;
-    R->retry_ms = std::min(R->retry_ms * 2u, 2000u);
-    R->base = R->seen_done = e->step_count;
-    host_store(&R->mb->posted, e->step_count);
-    R->launched = false;
-    R->enabled = true;
-    R->fell_back = false;
+    if (!R->led.retry_due(std::chrono::steady_clock::now()) || worker_fits(e) != TRS_OK) return;
+    if (R->led.reselect(e->step_count)) host_store(&R->mb->posted, e->step_count);
 }
-bool resident_running(const trs_env* e) { return e && e->res && e->res->running; }
-void resident_clear_fault(trs_env* e) { if (e && e->res) e->res->broken = false; }
+bool resident_running(const trs_env* e) { return e && e->res && e->res->led.running; }
+void resident_clear_fault(trs_env* e) { if (e && e->res) e->res->led.clear_fault(); }
 
 int resident_post(trs_env* e, const Controls& c, int n, int* n_done)
 {
     DevLock lock(e);
-    Resident* R = e->res;
-    Mailbox* mb = R->mb.get();
+    PostLedger& L = e->res->led;
+    Mailbox* mb = e->res->mb.get();
     *n_done = 0;
-    if (R->broken) return trs_internal_fail(TRS_ERR_DEVICE, "a resident worker gave up earlier: the env state is undefined, load the track again (trs_load_track)");
+    if (L.broken) return trs_internal_fail(TRS_ERR_DEVICE, "a resident worker gave up earlier: the env state is undefined, load the track again (trs_load_track)");
     for (int k = 0; k < n; ++k) {
         const uint64_t s = e->step_count;
-        if (!R->running) {
-            if (host_load(&mb->posted) > R->seen_done && host_load(&mb->posted) == s) {
-                // posts that raced with the worker's exit while another handle took the GPU over (evict): they are still in the ring
-                int rc = worker_launch(e, R->seen_done);
-                if (rc) return rc;
-            } else { R->base = R->seen_done = s; R->launched = false; }   // no worker: nothing is in flight that a flag will report (the step counter may have moved or restarted since; launched steps are ahead of the worker on the same stream)
+        if (!L.running) {
+            if (!L.orphans(host_load(&mb->posted), s)) L.absorb(s);   // no worker: launched steps are ahead of the next one on the same stream
+            else { int rc = worker_launch(e, L.seen_done); if (rc) return rc; }   // posts that raced with the worker's exit while another handle took the GPU over (evict): still in the ring
         }
-        if (s >= R->base + kSlots) {                                  // ring slot, counters and done flag of s % 8 are free
-            int rc = wait_done(e, s - kSlots);
-            if (rc) return rc;
-            if (!R->enabled) { *n_done = k; return kFellBack; }       // the handle went back to launch mode: the caller launches steps k.. itself
-        }
-        const Controls ck = c.after(k);                           // what step k of the call reads
-        if (!R->running) { int rc = worker_fits(e); if (rc) return rc; }   // nothing is published for a worker that could not be launched
-        WEntry* slot = &mb->ring[s & (kSlots - 1)];
-        slot->steer = ck.steer; slot->thr = ck.thr; slot->brk = ck.brk;
-        host_store(&slot->seq_lo, s + 1);                         // first half: payload, then its tag (x86 keeps the store order)
-        slot->reset = ck.reset; slot->synth = ck.synth ? 1u : 0u;
-        host_store(&slot->seq, s + 1);                            // second half likewise; this tag last: the line is now a valid post
-        host_store(&mb->posted, s + 1);
+        { int rc = claim_slot(e, s); if (rc == kFellBack) *n_done = k; if (rc) return rc; }   // (fell back: the caller launches steps k.. itself)
+        if (!L.running) { int rc = worker_fits(e); if (rc) return rc; }   // nothing is published for a worker that could not be launched
+        write_post(mb, s, c.after(k));                            // what step k of the call reads
         std::atomic_thread_fence(std::memory_order_seq_cst);     // the post is visible before `exited` is read
         e->step_count = s + 1;
-        if (!R->running) { int rc = worker_launch(e, s); if (rc) return rc; }
+        if (!L.running) { int rc = worker_launch(e, s); if (rc) return rc; }
         else if (host_load(&mb->exited)) {
             int rc = handle_exit(e);
             if (rc == kFellBack) { *n_done = k + 1; return kFellBack; }   // (step k was in the ring: it has been launched with the rest)
@@ -1374,28 +1294,20 @@ int resident_post(trs_env* e, const Controls& c, int n, int* n_done)
 
 int resident_wait(trs_env* e)
 {
-    Resident* R = e->res;
-    if (!R) return TRS_OK;
+    if (!e->res) return TRS_OK;
     DevLock lock(e);
-    if (R->launched && !R->running) {                        // the newest steps went through launches (resident_note_launch): wait for the stream
-        HIPCHK(hipStreamSynchronize(e->sP));
-        R->launched = false;
-        R->base = R->seen_done = e->step_count;
-        return TRS_OK;
-    }
-    if (e->step_count <= R->seen_done || e->step_count <= R->base) return TRS_OK;
-    return wait_done(e, e->step_count - 1);
+    const PostLedger& L = e->res->led;
+    if (L.launched && !L.running) return wait_stream(e);
+    return e->step_count <= L.seen_done || e->step_count <= L.base ? TRS_OK : wait_done(e, e->step_count - 1);
 }
 
 // a step was launched on the handle's stream although resident mode is selected (the pilot loop: its kernels need the LDS a worker
 // would hold).  The caller has quiesced the worker; the step has no post and gets no completion flag.
 void resident_note_launch(trs_env* e)
 {
-    Resident* R = e->res;
-    if (!R) return;
+    if (!e->res) return;
     DevLock lock(e);
-    R->launched = true;
-    R->base = R->seen_done = e->step_count;
+    e->res->led.note_launch(e->step_count);
 }
 
 int resident_quiesce(trs_env* e)
@@ -1403,18 +1315,18 @@ int resident_quiesce(trs_env* e)
     Resident* R = e->res;
     if (!R || !R->mb.get()) return TRS_OK;
     DevLock lock(e);
+    PostLedger& L = R->led;
     int rc = TRS_OK;
-    if (!R->running && R->enabled && !R->broken && host_load(&R->mb->posted) > R->seen_done && host_load(&R->mb->posted) == e->step_count)
-        rc = worker_launch(e, R->seen_done);                 // posts an eviction left in the ring (see resident_post): they complete here
-    for (int guard = 0; !rc && R->running && guard < 4; ++guard) {
+    if (!L.running && L.enabled && !L.broken && L.orphans(host_load(&R->mb->posted), e->step_count))
+        rc = worker_launch(e, L.seen_done);                  // posts an eviction left in the ring (see resident_post): they complete here
+    for (int guard = 0; !rc && L.running && guard < 4; ++guard) {
         host_store(&R->mb->close, kCloseLeave);
         rc = handle_exit(e);                                 // waits for the kernel; relaunches (with `close` cleared) if posts raced
         if (rc == kFellBack) { rc = TRS_OK; break; }         // the posted steps are launches on the handle's stream now
     }
-    if (!rc && R->running) rc = trs_internal_fail(TRS_ERR_DEVICE, "resident worker did not leave");
-    R->base = R->seen_done = e->step_count;
-    if (!R->running)                                         // tags and flags of the past must not match a step index that comes round again
-        for (int k = 0; k < kSlots; ++k) { host_store(&R->mb->ring[k].seq, 0); host_store(&R->mb->ring[k].seq_lo, 0); host_store(&R->mb->done[k], 0); }
+    if (!rc && L.running) rc = trs_internal_fail(TRS_ERR_DEVICE, "resident worker did not leave");
+    L.restart(e->step_count);
+    if (!L.running) forget_ring(R->mb.get());
     return rc;
 }
 
@@ -1424,51 +1336,33 @@ void resident_destroy(trs_env* e)
     if (!R) return;
     DevLock lock(e);
     if (slot_of(e).owner == e) slot_of(e).owner = nullptr;
-    if (R->running) { host_store(&R->mb->close, kCloseLeave); (void)hipStreamSynchronize(e->sP); }
+    if (R->led.running) { host_store(&R->mb->close, kCloseLeave); (void)hipStreamSynchronize(e->sP); }
     if (R->sC) (void)hipStreamDestroy(R->sC);
     delete R;                                                // (the worker has left: the mailbox, the staging and the control block go)
     e->res = nullptr;
 }
 
-hipStream_t resident_copy_stream(trs_env* e) { return (e->res && e->res->running) ? e->res->sC : e->sP; }
+hipStream_t resident_copy_stream(trs_env* e) { return (e->res && e->res->led.running) ? e->res->sC : e->sP; }
 
-// controls handed over as host arrays: into this step's slot of the pinned staging buffer, which the device reads over PCIe
+// controls handed over as host arrays: into this step's slot of the pinned staging buffer, which the device reads over PCIe.  Held controls: the steps
+// of the call are posted one by one, each from the slot of its own step (free once claimed), to which the floats are carried over from the step before.
 int resident_post_host(trs_env* e, const Controls& h, int n_steps, int* n_done)
 {
     DevLock lock(e);
     Resident* R = e->res;
-    *n_done = 0;
-    const uint64_t s = e->step_count;
-    if (!R->running && !(host_load(&R->mb->posted) > R->seen_done && host_load(&R->mb->posted) == s)) R->base = R->seen_done = s;
-    if (s >= R->base + kSlots) {                             // the staging slot is free as well
-        int rc = wait_done(e, s - kSlots);
-        if (rc) return rc;
-        if (!R->enabled) return kFellBack;
-    }
-    unsigned char* slot = R->hctl.get() + (s & (kSlots - 1)) * R->hctl_slot;
     const size_t n = (size_t)e->n;
-    float* f = reinterpret_cast<float*>(slot);
-    std::memcpy(f, h.steer, n * 4); std::memcpy(f + n, h.thr, n * 4);
-    if (h.brk) std::memcpy(f + 2 * n, h.brk, n * 4);
-    uint8_t* rsb = slot + n * 12;
-    if (h.reset) std::memcpy(rsb, h.reset, n);
-    // held controls: every step of the call reads the same slot, so the slot must outlive them — post them one by one and
-    // keep the slot until the last is done (n_steps > kSlots would wrap onto it: copy again per step instead)
+    unsigned char* prev = nullptr;
+    *n_done = 0;
     for (int k = 0; k < n_steps; ++k) {
-        if (k > 0) {
-            const uint64_t sk = e->step_count;
-            if (sk >= R->base + kSlots) {
-                int rc = wait_done(e, sk - kSlots);
-                if (rc) return rc;
-                if (!R->enabled) { *n_done = k; return kFellBack; }
-            }
-            unsigned char* sl = R->hctl.get() + (sk & (kSlots - 1)) * R->hctl_slot;
-            if (sl != slot) std::memcpy(sl, slot, n * 12);
-            slot = sl; f = reinterpret_cast<float*>(slot); rsb = slot + n * 12;
-        }
+        const uint64_t s = e->step_count;
+        if (!R->led.running && !R->led.orphans(host_load(&R->mb->posted), s)) R->led.restart(s);   // (resident_post absorbs the launched steps)
+        { int rc = claim_slot(e, s); if (rc == kFellBack) *n_done = k; if (rc) return rc; }
+        unsigned char* slot = stage_slot(R->hctl.get(), s, n);
+        if (k == 0) stage_fill(slot, h, n); else stage_carry(slot, prev, n);
+        prev = slot;
         int one = 0;
-        int rc = resident_post(e, Controls{f, f + n, h.brk ? f + 2 * n : nullptr, (k == 0 && h.reset) ? rsb : nullptr, 0, 0}, 1, &one);
-        if (rc == kFellBack) { *n_done = k + one; return kFellBack; }
+        int rc = resident_post(e, stage_controls(slot, h, n, k == 0), 1, &one);
+        if (rc == kFellBack) *n_done = k + one;
         if (rc) return rc;
     }
     *n_done = n_steps;
@@ -1491,7 +1385,7 @@ TRS_EXPORT int trs_resident_debug_lifetime(trs_env* e, int life_us)
 // error word in the mailbox, by a one-thread kernel on the side stream (the worker owns the handle's stream)
 __global__ void trs_worker_debug_abort_kernel(Mailbox* mb, DevCtl* dc)
 {
-    sys_store64(&mb->error, (7ull << 32));
+    sys_store64(&mb->error, ((u64)kGiveUpInjected << 32));
     __hip_atomic_fetch_or(&dc->word, kAbortBit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -1499,7 +1393,7 @@ TRS_EXPORT int trs_resident_debug_abort(trs_env* e)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     DevLock lock(e);
-    if (!e->res || !e->res->running) return trs_internal_fail(TRS_ERR_STATE, "no resident worker is running on this handle");
+    if (!e->res || !e->res->led.running) return trs_internal_fail(TRS_ERR_STATE, "no resident worker is running on this handle");
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(trs_worker_debug_abort_kernel, dim3(1), dim3(1), 0, e->res->sC, e->res->mb.get(), e->res->dc.get());
     HIPCHK(hipGetLastError());
@@ -1512,8 +1406,8 @@ TRS_EXPORT int trs_get_step_mode(trs_env* e, int* mode, int* fell_back)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     DevLock lock(e);
-    if (mode) *mode = (e->res && e->res->enabled) ? TRS_STEP_RESIDENT : TRS_STEP_LAUNCH;
-    if (fell_back) *fell_back = (e->res && e->res->fell_back) ? 1 : 0;
+    if (mode) *mode = (e->res && e->res->led.enabled) ? TRS_STEP_RESIDENT : TRS_STEP_LAUNCH;
+    if (fell_back) *fell_back = (e->res && e->res->led.fell_back) ? 1 : 0;
     return TRS_OK;
 }
 
@@ -1526,7 +1420,7 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
     if (mode == TRS_STEP_LAUNCH) {
         if (!e->res) return TRS_OK;
         int rc = resident_quiesce(e);
-        e->res->enabled = false;
+        e->res->led.deselect();
         return rc;
     }
     if (!e->track_loaded) return trs_internal_fail(TRS_ERR_STATE, "no track loaded");
@@ -1535,17 +1429,12 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
                                                 "frames over by step parity (trs_set_latency(NULL) first)");
     if (!e->res) e->res = new (std::nothrow) Resident();
     if (!e->res) return trs_internal_fail(TRS_ERR_NOMEM, "out of memory");
-    int rc = ensure_resident(e);
-    if (rc) return rc;
-    Resident* R = e->res;
+    { int rc = ensure_resident(e); if (rc) return rc; }
     { int rf = worker_fits(e); if (rf) return rf; }
     for (const WorkerKernel wk : kWorkerKernels)
         if (wk) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_worker_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (idle_us > 0) R->idle_us = (unsigned)std::min(idle_us, 1000000);
-    if (!R->enabled) { R->base = R->seen_done = e->step_count; host_store(&R->mb->posted, e->step_count); }
-    R->enabled = true;
-    R->fell_back = false;
-    R->retry_ms = kRetryMs0;
+    if (idle_us > 0) e->res->idle_us = (unsigned)std::min(idle_us, 1000000);
+    if (e->res->led.select(e->step_count)) host_store(&e->res->mb->posted, e->step_count);
     return TRS_OK;
 }
