@@ -570,6 +570,48 @@ int trs_pilot_act(trs_env* env, const trs_pilot_config* cfg, const uint8_t* d_fr
  * then one env step with those controls.  Before the first frame exists the controls are (0, 0, 0) (keras_pilot.py:46-47). */
 int trs_step_pilot(trs_env* env, const trs_pilot_config* cfg, int n_steps);
 
+/* ---- scripted expert: the stand-in for the reference's human driver (include/trsim_spec.h, "scripted expert"; HIP library only) ----
+ * The reference's training data comes from a person with a joystick: JoystickController writes 'usr/steering', 'usr/throttle', 'usr/breaking'
+ * (components/controller.py:24).  The expert is a rule on the env's own state (the truth, never a delayed observation): steer against the cross-track
+ * error and the heading error `look` track points ahead, hold a speed.  It exists per handle, on the device, in launch mode.
+ *   trs_set_expert: validates, builds track_yaw from the handle's tangents and uploads the tables; zeroes the driver's tick counter k and its disturbance
+ *     state w.  cfg NULL: the expert is switched off.  h_target: float[n_envs] speed target per env (NULL: cfg.target_speed for all); h_profile:
+ *     float[n_points] speed limit per track point (NULL: none).  TRS_ERR_STATE without a track; a later trs_load_track switches the expert off again.
+ *     TRS_ERR_ARG: struct_size, look outside [0, n_points), a field that is not finite.  The call synchronises the handle.
+ *   trs_expert_act: the pure rule (no disturbance; k and w do not move) for envs 0..n-1 of whatever state the handle is in, into device arrays float[n]
+ *     ('usr/steering', 'usr/throttle', 'usr/breaking'; after trs_step_pilot: DAgger labels).  n <= n_envs.  Asynchronous on the handle's stream.
+ *   trs_step_expert: the closed loop in the shape of trs_step_pilot.  Per tick ONE launch of trs_expert_kernel writes the applied controls (label plus
+ *     the disturbance) into the handle's own control arrays (TRS_F_CTL_*) and, when a capture is due, the record rows; one env step by launch follows.
+ *     Resident mode and latency as for trs_step_pilot: a resident worker is asked to leave, and the truth is stepped.
+ *   Capture (cap NULL: none).  The tick with counter k is captured when k >= skip and (k - skip) % every == 0, until `capacity` slots of THIS call are
+ *     full; a tick is not captured when frames are asked for and no frame exists yet (before the handle's first step).  Slot s: d_rows[s][n_envs][8] =
+ *     (steering label, throttle label, breaking label, applied steering, speed, cte, 'loc/segment' = (float)((double)seg_idx / n_points * 10), done) and,
+ *     with d_frames, d_frames[s][n_envs][H][W][3]: the rendered frame of the state the label was computed on (the truth, not the camera codec's frame:
+ *     put a data set through trs_jpeg_roundtrip afterwards), copied device to device on the handle's stream in front of the step.  No byte of a slot
+ *     that is not captured is written.  *n_captured (may be NULL): slots filled by this call.
+ *     TRS_ERR_ARG: struct_size, every < 1, skip < 0, capacity < 0, capacity > 0 without d_rows, d_frames on a handle without a camera.
+ *     TRS_ERR_STATE: no expert set.  A refused call leaves the handle unchanged. */
+typedef struct trs_expert_config {
+    uint32_t struct_size;
+    int32_t  look;                   /* 6: track points ahead for the heading error */
+    float    k_cte, k_head;          /* 1, 2 */
+    float    thr_hi, thr_lo;         /* 0.6 below the speed target, 0.1 at or above it */
+    float    target_speed;           /* 6 */
+    float    brake_over, brake_val;  /* 1.15, 0.5: brake_val while speed > target * brake_over */
+    float    alpha, sigma;           /* 0.1, 0: the low-pass constant and the amplitude of the steering disturbance */
+    uint64_t seed;                   /* 0: the seed of the disturbance */
+} trs_expert_config;
+typedef struct trs_expert_capture {
+    uint32_t struct_size;
+    int32_t  every, skip, capacity;
+    uint8_t* d_frames_or_null;
+    float*   d_rows;
+} trs_expert_capture;
+void trs_default_expert_config(trs_expert_config* cfg);
+int trs_set_expert(trs_env* env, const trs_expert_config* cfg_or_null, const float* h_target_or_null, const float* h_profile_or_null);
+int trs_expert_act(trs_env* env, float* d_steering, float* d_throttle, float* d_breaking, int n);
+int trs_step_expert(trs_env* env, int n_steps, const trs_expert_capture* cap_or_null, int* n_captured_or_null);
+
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no
  * distributed layer at all; this replaces what a user would otherwise script around N copies of manage.py.

@@ -251,6 +251,28 @@
  *   The result equals what Pillow gives for save(quality = q), then open.  Parity with the closed simulator's own encoder is unpinned: its quality
  *   is unknown.  tests/test_jpeg_codec_cpu.py restates the paragraph in numpy and compares it with decode(encode()) of the two paragraphs above and with
  *   Pillow, byte for byte; csrc/trsim_jpeg_codec.hpp composes the two headers' rules for the kernel and for the host test driver.
+ *
+ * ---- scripted expert (trs_set_expert, trs_expert_act, trs_step_expert; the stand-in for the reference's human driver, components/controller.py:24; HIP library only)
+ *   A rule on the env's own state (the truth of trs_state_view, never a delayed observation).  Every operation rounds to binary32 once (R1: no
+ *   contraction, no fma), so a numpy float32 restatement is bit-exact.  Host, binary64, from the binary32 tangents of TRS_F_TANGENT:
+ *     track_yaw[p] = (float)atan2((double)tx[p], (double)tz[p])
+ *   profile: float[n_points], absent = +inf everywhere;  target: float[n_envs], absent = target_speed for every env.
+ *   per env e:
+ *     j      = (seg_idx + look) mod n_points                          look in [0, n_points)
+ *     herr   = yaw - track_yaw[j];  if herr > PI: herr -= TWO_PI;  if herr < -PI: herr += TWO_PI
+ *     steer  = clamp(-(k_cte*cte + k_head*herr), -1, 1)               (two products, one sum, one negation)
+ *     v_ref  = min(target[e], profile[j])
+ *     thr    = speed < v_ref ? thr_hi : thr_lo                        (strict <)
+ *     brk    = speed > v_ref*brake_over ? brake_val : 0
+ *   (steer, thr, brk) is the LABEL.  Disturbance, only in the closed loop of trs_step_expert, tick counter k since trs_set_expert:
+ *     z  = SplitMix64 as in the synthetic control generator below, seed = the expert's seed, key = (global env id << 32) | k
+ *     u  = (float)(z >> 40) * 2^-24
+ *     w  = w + alpha*(sigma*(u*2 - 1) - w)
+ *     applied_steer = clamp(steer + w, -1, 1);  throttle and brake are applied as labelled
+ *   With sigma == 0, w stays 0 and the applied steering is the label.  w and k belong to the driver: resets of the car do not touch them,
+ *   trs_set_expert zeroes them.  A record row is (steer, thr, brk, applied_steer, speed, cte, (float)((double)seg_idx / n_points * 10), done).
+ *   tests/test_expert_cpu.py restates the paragraph in numpy and drives the CPU oracle with it; tests/test_expert_gpu.py compares the kernel with that
+ *   restatement bit for bit; csrc/trsim_expert.hpp holds the host side (config checks, track_yaw, which ticks are captured).
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H
@@ -335,5 +357,18 @@
 #define TRS_SYNTH_THR_LO    0.2f
 #define TRS_SYNTH_THR_SPAN  0.6f
 #define TRS_START_STRIDE    37                 /* env i starts at track point (37*i) mod n */
+
+/* scripted expert: defaults of trs_expert_config (trs_default_expert_config) */
+#define TRS_EXPERT_LOOK         6
+#define TRS_EXPERT_K_CTE        1.0f
+#define TRS_EXPERT_K_HEAD       2.0f
+#define TRS_EXPERT_THR_HI       0.6f
+#define TRS_EXPERT_THR_LO       0.1f
+#define TRS_EXPERT_TARGET_SPEED 6.0f
+#define TRS_EXPERT_BRAKE_OVER   1.15f
+#define TRS_EXPERT_BRAKE_VAL    0.5f
+#define TRS_EXPERT_ALPHA        0.1f
+#define TRS_EXPERT_SIGMA        0.0f
+#define TRS_EXPERT_SEED         0ull           /* the fixture's (tests/golden/train_pilot_fixture.py: collect(seed=0)) */
 
 #endif /* TRSIM_SPEC_H */

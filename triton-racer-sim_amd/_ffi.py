@@ -121,6 +121,22 @@ class TrsPilotTuning(C.Structure):
     ]
 
 
+class TrsExpertConfig(C.Structure):
+    """``trs_expert_config`` (include/trsim.h): the scripted expert of ``trs_set_expert``."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("look", C.c_int32), ("k_cte", C.c_float), ("k_head", C.c_float), ("thr_hi", C.c_float), ("thr_lo", C.c_float),
+        ("target_speed", C.c_float), ("brake_over", C.c_float), ("brake_val", C.c_float), ("alpha", C.c_float), ("sigma", C.c_float),
+        ("seed", C.c_uint64),
+    ]
+
+
+class TrsExpertCapture(C.Structure):
+    """``trs_expert_capture`` (include/trsim.h): where ``trs_step_expert`` puts the records of the ticks it captures."""
+    _fields_ = [("struct_size", C.c_uint32), ("every", C.c_int32), ("skip", C.c_int32), ("capacity", C.c_int32), ("d_frames", C.c_void_p), ("d_rows", C.c_void_p)]
+
+
+EXPERT_ROW = ("steering", "throttle", "breaking", "applied_steering", "speed", "cte", "segment", "done")   # a record row of trs_step_expert's capture
+
 COMM_ID_BYTES = 128                                                    # TRS_COMM_ID_BYTES
 
 PILOT_MODEL_TYPES = {"cnn_2d_speed_control": 0, "cnn_2d": 1, "cnn_2d_speed_as_feature": 2, "cnn_2d_full_house": 3}   # TRS_PILOT_*; ModelType values (utils/types.py)
@@ -153,9 +169,12 @@ JPEG_DECODE_SYMBOLS = ["decode_jpeg", "decode_jpeg_host"]
 # HIP library only: the camera codec (trs_jpeg_roundtrip, trs_set_camera_codec) — its checker is the restatement of include/trsim_spec.h ("camera codec
 # (JPEG round trip)") in tests/test_jpeg_codec_cpu.py, itself pinned to decode(encode()) of the two restatements above and to Pillow's save and open
 JPEG_CODEC_SYMBOLS = ["jpeg_roundtrip", "jpeg_roundtrip_host", "set_camera_codec", "get_camera_codec"]
+# HIP library only: the scripted expert (trs_set_expert, trs_step_expert) — its checker is the numpy restatement of include/trsim_spec.h ("scripted expert") in
+# tests/test_expert_cpu.py, which drives the oracle with it (tests/test_expert_gpu.py compares the kernel with the restatement bit for bit)
+EXPERT_SYMBOLS = ["default_expert_config", "set_expert", "expert_act", "step_expert"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -259,6 +278,12 @@ class Api:
             "set_camera_codec": (i32, [vp, i32]),
             "get_camera_codec": (i32, [vp, C.POINTER(i32)]),
         }
+        expert = {
+            "default_expert_config": (None, [C.POINTER(TrsExpertConfig)]),
+            "set_expert": (i32, [vp, C.POINTER(TrsExpertConfig), vp, vp]),
+            "expert_act": (i32, [vp, vp, vp, vp, i32]),
+            "step_expert": (i32, [vp, i32, C.POINTER(TrsExpertCapture), C.POINTER(i32)]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -303,6 +328,12 @@ class Api:
         self.has_jpeg_codec = hasattr(cdll, prefix + "jpeg_roundtrip")
         if self.has_jpeg_codec:
             for name, (res, args) in jpeg_codec.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_expert = hasattr(cdll, prefix + "set_expert")
+        if self.has_expert:
+            for name, (res, args) in expert.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

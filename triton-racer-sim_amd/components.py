@@ -382,6 +382,37 @@ class BatchedControlMultiplexer(Component):
         return "Control Multiplexer"
 
 
+DRIVER_OUTPUTS = ["usr/steering", "usr/throttle", "usr/breaking"]                    # controller.py:24 (the joystick's control ports)
+
+
+class HipScriptedDriver(Component):
+    """The scripted expert in the place of the reference's human with a joystick (``components/controller.py:21-33``): no inputs, outputs
+    ``usr/steering``, ``usr/throttle``, ``usr/breaking`` — the expert's answer (``BatchedEnv.expert_act``; include/trsim_spec.h, "scripted expert") to
+    the state the sim is in, read on the device from the sim's own env.  ``gym``: the ``HipGymInterface`` or ``BatchedGymInterface`` it drives (or
+    their ``BatchedEnv``).  One car: Python floats, as the joystick gives them.  N cars: device handles (the multiplexer takes them as they are)
+    or, with ``to_host=True`` (default: what the gym interface was built with), float32 arrays.  Mode, record and reset ports stay with whoever owns
+    them; ``cfg`` / ``target_speed`` / ``profile`` / ``fields`` are ``BatchedEnv.set_expert``'s."""
+
+    def __init__(self, gym, cfg=None, target_speed=None, profile=None, to_host=None, **fields):
+        Component.__init__(self, inputs=[], outputs=list(DRIVER_OUTPUTS), threaded=False)
+        self.env = getattr(gym, "env", gym)
+        self.single = self.env.n == 1 and not isinstance(gym, BatchedGymInterface)
+        self.to_host = (self.single or bool(getattr(gym, "to_host", False))) if to_host is None else bool(to_host)
+        self.env.set_expert(cfg, target_speed=target_speed, profile=profile, **fields)
+
+    def step(self, *args):
+        outs = self.env.expert_act()
+        if not self.to_host:
+            return outs
+        st, th, br = (self.env.to_host(o) for o in outs)
+        if self.single:
+            return float(st[0]), float(th[0]), float(br[0])
+        return st, th, br
+
+    def getName(self):
+        return "Scripted Driver"
+
+
 PILOT_INPUTS = ["cam/img", "gym/speed", "loc/segment", "gym/cte", "usr/mode"]          # keras_pilot.py:18
 PILOT_OUTPUTS = ["ai/steering", "ai/throttle", "ai/breaking"]
 

@@ -78,6 +78,7 @@ struct trs_env {
     int lds_step = 0, lds_off_phys = 0;
     trsim::DevBuf<float> seq_buf;        // device copy of host control sequences (trs_step_sequence_host)
     void* pilot = nullptr;               // trsim_pilot.hip context (cnn_2d_speed_control weights + activations), released by trs_pilot_free
+    void* expert = nullptr;              // trsim_expert.hip context (the scripted expert of trs_set_expert: tables, disturbance state, tick counter), released by trs_expert_free
     trs_pilot_tuning pilot_tuning{}; bool has_pilot_tuning = false;   // trs_pilot_set_tuning: kernel choices of the next trs_pilot_load
     trsim::PinnedBuf<unsigned long long> fault;   // pinned host word the kernels set when they refuse to run (dynamic LDS not at offset 0)
     trsim::DevBuf<float> glue;           // device scratch of the *_host control glue (trs_driver_assist_host, trs_control_mux_host)

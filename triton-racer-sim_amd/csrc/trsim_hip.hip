@@ -843,6 +843,7 @@ TRS_EXPORT int trs_destroy(trs_env* e)
     trsim::comm_destroy(e);
     if (e->ev_order) (void)hipEventDestroy(e->ev_order);
     if (e->pilot) { trs_pilot_free(e->pilot); e->pilot = nullptr; }
+    if (e->expert) { trs_expert_free(e->expert); e->expert = nullptr; }
     for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->sP) (void)hipStreamDestroy(e->sP);
     delete e;                                                // the handle's buffers go with it: the stream was idle above
@@ -1169,6 +1170,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     LensStage ls;
     if ((rc = track_lens_stage(e, T, L, S, ls))) return rc;
     if ((rc = track_commit(e, T, L, S, k, r, ls))) return rc;
+    if (e->expert) { trs_expert_free(e->expert); e->expert = nullptr; }   // the scripted expert's tables were the old track's (the handle is idle: sync_all above)
     if ((rc = track_start_poses(e))) return rc;
     if (e->lat.on() && (rc = latency_restart(e))) return rc;  // the observations of the old track's steps do not reach the new one
     return track_drop_misfits(e, clash);
@@ -1722,6 +1724,7 @@ bool trs_internal_view(trs_env* e, TrsEnvView* v)
     return true;
 }
 void** trs_internal_pilot_slot(trs_env* e) { return e ? &e->pilot : nullptr; }
+void** trs_internal_expert_slot(trs_env* e) { return e ? &e->expert : nullptr; }
 const trs_pilot_tuning* trs_internal_pilot_tuning(trs_env* e) { return e && e->has_pilot_tuning ? &e->pilot_tuning : nullptr; }
 void trs_internal_set_pilot_tuning(trs_env* e, const trs_pilot_tuning* t)
 {

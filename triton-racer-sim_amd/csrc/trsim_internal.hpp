@@ -43,6 +43,7 @@ struct TrsEnvView {
 
 bool trs_internal_view(trs_env* e, TrsEnvView* out);
 void** trs_internal_pilot_slot(trs_env* e);
+void** trs_internal_expert_slot(trs_env* e);   // the scripted expert's context (trsim_expert.hip), nullptr while none is set
 const trs_pilot_tuning* trs_internal_pilot_tuning(trs_env* e);   // what trs_pilot_set_tuning stored, or nullptr (defaults)
 void trs_internal_set_pilot_tuning(trs_env* e, const trs_pilot_tuning* t);
 int trs_internal_fail(int code, const std::string& msg);
@@ -55,3 +56,4 @@ int trs_internal_replay_launch(trs_env* e, const trsim::Controls& c, uint64_t st
 void trs_internal_note(const std::string& msg);            // what trs_last_error() returns, without failing the call
 void trs_internal_count(trs_env* e, uint64_t d2h_bytes, uint64_t h2d_bytes);   // trs_counters bookkeeping for copies made outside trsim_hip.hip
 void trs_pilot_free(void* ctx);       // defined in trsim_pilot.hip, called by trs_destroy
+void trs_expert_free(void* ctx);      // defined in trsim_expert.hip, called by trs_destroy and by trs_load_track (a new track switches the expert off); nullptr is fine

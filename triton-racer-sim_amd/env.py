@@ -80,6 +80,8 @@ SLOT_USR = (4, 5, 6)           # 'usr/steering', 'usr/throttle', 'usr/breaking' 
 SLOT_MUX = (7, 8, 9)           # 'mux/steering', 'mux/throttle', 'mux/breaking'   (BatchedControlMultiplexer)
 SLOT_PILOT_IN = (10, 11)       # 'gym/speed', 'loc/segment' that reached HipKerasPilot as HOST values beside a device frame
 SLOT_JPEG_IN = 12              # host frames handed to BatchedEnv.encode_jpeg                        (uploaded before the encoder reads them)
+SLOT_EXPERT = (13, 14, 15)     # 'usr/steering', 'usr/throttle', 'usr/breaking' of the scripted expert (BatchedEnv.expert_act, HipScriptedDriver)
+SLOT_COLLECT = (16, 17)        # the frames and rows of BatchedEnv.collect
 
 
 def _stream_ptr(stream):
@@ -117,6 +119,30 @@ def lighting_params(n, seed=0, gain=(0.6, 1.4), bias=(-30.0, 30.0), per_channel=
     g = np.broadcast_to(rng.uniform(gain[0], gain[1], (n, k)), (n, 3))
     b = np.broadcast_to(rng.uniform(bias[0], bias[1], (n, k)), (n, 3))
     return lighting_array(g.astype(np.float32), b.astype(np.float32))
+
+
+def corner_speed_profile(track_xyz, a_lat, v_max, span=4, ahead=12):
+    """ONE possible speed profile for ``BatchedEnv.set_expert(profile=...)``: slow down for the corners ahead.  Per raw track point ``i`` of the closed
+    centre line (x, z; indices wrap): the turn between the chords ``P[i-span] -> P[i]`` and ``P[i] -> P[i+span]`` over their mean length is the
+    curvature, ``v_i = min(v_max, sqrt(a_lat / curvature))`` the speed a lateral acceleration ``a_lat`` allows there, and the profile is the minimum
+    of ``v`` over points ``i .. i + ahead``.  float32 ``[n_points]``.  The library holds no curvature model: any array of that shape will do."""
+    pts = np.asarray(track_xyz, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("track must be an (n, 3) array of [x, y, z]")
+    span, ahead = int(span), int(ahead)
+    if span < 1 or ahead < 0 or not a_lat > 0 or not v_max > 0:
+        raise ValueError("span >= 1, ahead >= 0, a_lat > 0 and v_max > 0 are required")
+    xz = pts[:, [0, 2]]
+    back, fwd = xz - np.roll(xz, span, axis=0), np.roll(xz, -span, axis=0) - xz
+    turn = np.arctan2(fwd[:, 0], fwd[:, 1]) - np.arctan2(back[:, 0], back[:, 1])
+    turn = np.abs((turn + np.pi) % (2 * np.pi) - np.pi)
+    dist = 0.5 * (np.hypot(back[:, 0], back[:, 1]) + np.hypot(fwd[:, 0], fwd[:, 1]))
+    curv = np.where(dist > 1e-9, turn / np.maximum(dist, 1e-9), 0.0)
+    v = np.minimum(float(v_max), np.sqrt(float(a_lat) / np.maximum(curv, 1e-12)))
+    out = v.copy()
+    for k in range(1, ahead + 1):
+        out = np.minimum(out, np.roll(v, -k))
+    return np.ascontiguousarray(out, dtype=np.float32)
 
 
 class JpegFrames:
@@ -833,6 +859,113 @@ class BatchedEnv:
         frame it sees has been through the JPEG round trip first."""
         pc = cfg if isinstance(cfg, _ffi.TrsPilotConfig) else self.pilot_config(cfg)
         self.api.check(self.api.step_pilot(self._h, C.byref(pc), int(n_steps)), "step_pilot")
+
+    # -- scripted expert (include/trsim_spec.h, "scripted expert") ----------------------------------------------------------
+    def _need_expert(self):
+        if not getattr(self.api, "has_expert", False):
+            raise RuntimeError("the oracle has no scripted expert (trs_set_expert): its checker is the restatement in tests/test_expert_cpu.py, HIP library only")
+
+    def expert_config(self, **fields):
+        """``trs_expert_config`` with the library's defaults (``trs_default_expert_config``) and ``fields`` over them."""
+        self._need_expert()
+        ec = _ffi.TrsExpertConfig()
+        self.api.default_expert_config(C.byref(ec))
+        names = {f[0] for f in _ffi.TrsExpertConfig._fields_} - {"struct_size"}
+        for k, v in fields.items():
+            if k not in names:
+                raise ValueError(f"trs_expert_config has no field {k!r}")
+            setattr(ec, k, int(v) if k in ("look", "seed") else float(v))
+        return ec
+
+    def set_expert(self, cfg=None, target_speed=None, profile=None, **fields):
+        """The scripted expert, the stand-in for the reference's human driver (``trs_set_expert``): steer against the cross-track error and the heading
+        error ``look`` points ahead, hold a speed.  ``cfg``: ``None`` = the defaults, a ``TrsExpertConfig`` or a dict of its fields; ``fields`` override
+        it (``look``, ``k_cte``, ``k_head``, ``thr_hi``, ``thr_lo``, ``brake_over``, ``brake_val``, ``alpha``, ``sigma``, ``seed``).  ``target_speed``: a
+        number, or one value per env.  ``profile``: a speed limit per track point, float ``[n_points]`` (e.g. ``corner_speed_profile``).
+        ``set_expert(False)`` switches the expert off.  The driver's tick counter and disturbance start from zero; ``load_track`` switches it off."""
+        self._need_expert()
+        if cfg is False:
+            self.api.check(self.api.set_expert(self._h, None, None, None), "set_expert")
+            return
+        if isinstance(cfg, _ffi.TrsExpertConfig):
+            base = {f[0]: getattr(cfg, f[0]) for f in _ffi.TrsExpertConfig._fields_ if f[0] != "struct_size"}
+        else:
+            base = dict(cfg or {})
+        base.update(fields)
+        tg = None
+        if target_speed is not None:
+            t = np.asarray(target_speed, dtype=np.float32)
+            if t.ndim == 0:
+                base["target_speed"] = float(t)
+            else:
+                if t.shape != (self.n,):
+                    raise ValueError(f"target_speed must be a number or have shape ({self.n},)")
+                tg = np.ascontiguousarray(t)
+        pf = None
+        if profile is not None:
+            pf = np.ascontiguousarray(profile, dtype=np.float32)
+            if pf.shape != (self.n_points,):
+                raise ValueError(f"profile must have one value per track point: shape ({self.n_points},)")
+        ec = self.expert_config(**base)
+        self.api.check(self.api.set_expert(self._h, C.byref(ec), None if tg is None else tg.ctypes.data, None if pf is None else pf.ctypes.data), "set_expert")
+
+    def expert_act(self, n=None):
+        """The expert's answer to the state the env is in (``trs_expert_act``): the pure rule, no disturbance, nothing of the driver advances — after
+        ``step_pilot`` these are DAgger labels.  Returns three device handles (scratch slots): 'usr/steering', 'usr/throttle', 'usr/breaking'."""
+        self._need_expert()
+        n = self.n if n is None else int(n)
+        outs = [self.scratch(sl, (n,)) for sl in SLOT_EXPERT]
+        self.api.check(self.api.expert_act(self._h, *[device_ptr(o) for o in outs], n), "expert_act")
+        return tuple(outs)
+
+    def step_expert(self, n_steps=1, capture=None):
+        """Closed loop on the device (``trs_step_expert``): per tick the expert's controls — the label plus its slowly varying steering disturbance
+        (``sigma``) — go into the env's own control arrays (``fetch('ctl_steer')`` ...), then one env step.  ``capture``: a ``TrsExpertCapture`` or a
+        dict ``{every, skip, capacity, rows, frames}`` with ``rows`` a device float32 ``[capacity, n_envs, 8]`` and ``frames`` ``None`` or a device
+        uint8 ``[capacity, n_envs, H, W, 3]``: tick ``k`` of the driver is captured when ``k >= skip`` and ``(k - skip) % every == 0``.  Returns the
+        number of slots this call filled."""
+        self._need_expert()
+        cap = capture
+        if isinstance(capture, dict):
+            cap = _ffi.TrsExpertCapture()
+            cap.struct_size = C.sizeof(_ffi.TrsExpertCapture)
+            cap.every, cap.skip, cap.capacity = int(capture.get("every", 1)), int(capture.get("skip", 0)), int(capture["capacity"])
+            cap.d_frames, cap.d_rows = device_ptr(capture.get("frames")), device_ptr(capture.get("rows"))
+        got = C.c_int(0)
+        self.api.check(self.api.step_expert(self._h, int(n_steps), None if cap is None else C.byref(cap), C.byref(got)), "step_expert")
+        return int(got.value)
+
+    def collect(self, ticks, every=5, skip=20, to_host=False):
+        """A training set from the expert without a byte crossing to the host: ``ticks`` ticks of ``step_expert`` in ONE call, every ``every``-th tick
+        from the driver's tick ``skip`` on captured.  Returns ``(frames uint8[N, H, W, 3], rows float32[N, 8])`` (physics-only envs: ``frames`` is
+        ``None``), N = captured ticks x n_envs in tick order; a row is ``_ffi.EXPERT_ROW``: the expert's label (steering, throttle, breaking), the
+        applied steering, speed, cte, 'loc/segment' and done of the state the frame shows.  Device handles on env-owned memory, valid until the next
+        ``collect`` (``to_host=True``: fresh numpy arrays instead).  Feed them to ``recorder.records_for``; put the frames through
+        ``device_jpeg_roundtrip`` first for what the reference's pilot would have seen."""
+        self._need_expert()
+        ticks, every, skip = int(ticks), int(every), int(skip)
+        if ticks < 1 or every < 1 or skip < 0:
+            raise ValueError("ticks >= 1, every >= 1 and skip >= 0 are required")
+        capacity = (ticks + every - 1) // every                   # no window of `ticks` ticks holds more due ticks
+        render = bool(self.cfg.render)
+        rows = self.scratch(SLOT_COLLECT[1], (capacity, self.n, 8), np.float32)
+        frames = self.scratch(SLOT_COLLECT[0], (capacity, self.n, self.H, self.W, 3), np.uint8) if render else None
+        got = self.step_expert(ticks, {"every": every, "skip": skip, "capacity": capacity, "rows": rows, "frames": frames})
+        rows = _DevicePtr(device_ptr(rows), (got * self.n, 8), np.float32, self)
+        if render:
+            frames = _DevicePtr(device_ptr(frames), (got * self.n, self.H, self.W, 3), np.uint8, self)
+        if not to_host:
+            return frames, rows
+        return (self.to_host(frames) if render else None), self.to_host(rows)
+
+    def to_host(self, handle):
+        """A fresh numpy copy of a device handle of this env (behind everything queued on the env's stream so far)."""
+        cai = handle.__cuda_array_interface__
+        if int(np.prod(cai["shape"], dtype=np.int64)) == 0:
+            return np.zeros(cai["shape"], np.dtype(cai["typestr"]))
+        import torch
+        self.sync()
+        return torch.as_tensor(handle, device=f"cuda:{self.device}").cpu().numpy()
 
     # -- device-resident part graphs (pilot -> mux -> sim without host copies of frames; car_templates/manage.py:46-75) ------
     def scratch(self, slot, shape, dtype=np.float32):

@@ -200,6 +200,33 @@ def load_records(paths, loader="speed_ctl", env=None, batch=1024):
     return np.stack(imgs), np.stack(feats), np.stack(labels)
 
 
+def records_for(loader, frames, rows, label="expert"):
+    """The triple ``load_records`` returns, from records that never were a tub: ``frames`` uint8 ``[n, H, W, 3]`` and ``rows`` float32 ``[n, 8]`` as
+    ``BatchedEnv.collect`` gives them (host arrays; a row is ``_ffi.EXPERT_ROW``).  Each row becomes the record a tub would hold — 'mux/steering' the
+    expert's label (``label="expert"``) or the disturbed steering the car was given (``"applied"``), 'mux/throttle', 'gym/speed', 'loc/segment' —
+    and the labels and features are the ``LOADERS`` entry's, in the reference's binary64 arithmetic like a record read back from JSON.  Frames are
+    taken as they are (``/ 255``): put them through the camera codec first for what a tub's JPEG would have given."""
+    labels_of, features_of = LOADERS[loader]
+    if label not in ("expert", "applied"):
+        raise ValueError("label must be 'expert' or 'applied'")
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 8)
+    frames = np.asarray(frames, dtype=np.uint8)
+    if frames.ndim != 4 or frames.shape[0] != rows.shape[0] or frames.shape[3] != 3:
+        raise ValueError("frames must be uint8[n, H, W, 3] with one frame per row")
+    if rows.shape[0] == 0:
+        return np.zeros((0, 0, 0, 3), np.float32), np.zeros((0, 0), np.float32), np.zeros((0, 2), np.float32)
+    steer = 0 if label == "expert" else 3
+    labels, feats = [], []
+    for r in rows:
+        record = {"mux/steering": float(r[steer]), "mux/throttle": float(r[1]), "mux/breaking": float(r[2]), "gym/speed": float(r[4]),
+                  "gym/cte": float(r[5]), "loc/segment": float(r[6])}
+        labels.append(np.asarray(labels_of(record), dtype=np.float32))
+        feats.append(np.asarray(features_of(record) if features_of else (), dtype=np.float32))
+    imgs = frames.astype(np.float32)
+    imgs /= 255
+    return imgs, np.stack(feats), np.stack(labels)
+
+
 class TrackDataProcessor:
     """Tub -> centre-line file (reference ``components/track_data_process.py:9-39``): walks ``record_1.json, record_2.json, ...``
     (from 1 — ``record_0.json`` is skipped exactly as the reference skips it) until the first missing file, collects
