@@ -612,6 +612,39 @@ int trs_set_expert(trs_env* env, const trs_expert_config* cfg_or_null, const flo
 int trs_expert_act(trs_env* env, float* d_steering, float* d_throttle, float* d_breaking, int n);
 int trs_step_expert(trs_env* env, int n_steps, const trs_expert_capture* cap_or_null, int* n_captured_or_null);
 
+/* ---- training minibatches: DataLoader.load's split, shuffle and batch on the device (include/trsim_spec.h, "training minibatches"; HIP library only) ----
+ * The reference's trainer turns every record into float32 on the host, splits 0.8 / 0.2, shuffles and batches with drop_remainder
+ * (components/keras_train.py:33-69).  Here the set stays where trs_step_expert's capture left it — d_frames uint8[n_records][H][W][3] of the handle's
+ * size, d_rows float[n_records][8] — and a training step asks for one minibatch at a time.
+ *   trs_sample_batch: positions first .. first + batch - 1 of epoch `epoch` of split `split` (TRS_SPLIT_*), gathered by ONE launch of trs_batch_kernel,
+ *     asynchronous on the handle's stream.  Slot k of the batch holds the record at position first + k:
+ *       d_images    [batch][H][W][3] (TRS_LAYOUT_NHWC) or [batch][3][H][W] (TRS_LAYOUT_NCHW) of float, binary16 or uint8 (cfg.dtype)
+ *       d_features  float[batch][F], F = 0, 0, 1, 2 for TRS_LOADER_SPEED_CTL, _DEFAULT, _SPEED_FEATURE, _FULL_HOUSE (may be NULL when F == 0)
+ *       d_labels    float[batch][2]
+ *       d_index     int32[batch], the record numbers (may be NULL)
+ *     A physics-only set has no frames: d_frames and d_images are both NULL.  batch == 0 is accepted and writes nothing.
+ *     TRS_ERR_ARG, nothing written: struct_size, an unknown loader / label / layout / dtype / split, NCHW with uint8, n_records < 0, n_train outside
+ *     [0, n_records], epoch < 0, first < 0, batch < 0, first + batch beyond the split, d_rows or d_labels NULL, d_features NULL with F > 0, exactly
+ *     one of d_frames and d_images NULL, d_images not 16-byte aligned, any other pointer not 4-byte aligned, frames on a handle without a camera
+ *     (cfg.render == 0).  Source and destination must not overlap.  A resident worker leaves the GPU first, as for trs_normalize.
+ *   trs_loader_order: the same record numbers on the host, positions first .. first + count - 1, without a GPU (callable on a machine that has none):
+ *     which records a batch held.  The refusals that concern cfg, split, epoch and the range are the same. */
+enum { TRS_LOADER_SPEED_CTL = 0, TRS_LOADER_DEFAULT = 1, TRS_LOADER_SPEED_FEATURE = 2, TRS_LOADER_FULL_HOUSE = 3 };   /* the order of TRS_PILOT_* */
+enum { TRS_LABEL_EXPERT = 0, TRS_LABEL_APPLIED = 1 };     /* 'mux/steering' = the expert's label, or the disturbed steering the car was given */
+enum { TRS_LAYOUT_NHWC = 0, TRS_LAYOUT_NCHW = 1 };
+enum { TRS_DTYPE_F32 = 0, TRS_DTYPE_F16 = 1, TRS_DTYPE_U8 = 2 };
+enum { TRS_SPLIT_TRAIN = 0, TRS_SPLIT_VAL = 1 };
+typedef struct trs_loader_config {
+    uint32_t struct_size;
+    int32_t  loader, label, layout, dtype;   /* TRS_LOADER_SPEED_CTL, TRS_LABEL_EXPERT, TRS_LAYOUT_NCHW, TRS_DTYPE_F32 */
+    int32_t  n_records, n_train;             /* 0, 0: the caller's set */
+    uint64_t seed;                           /* 0 */
+} trs_loader_config;
+void trs_default_loader_config(trs_loader_config* cfg);
+int trs_sample_batch(trs_env* env, const trs_loader_config* cfg, const uint8_t* d_frames_or_null, const float* d_rows, int split, int epoch, int first,
+                     int batch, void* d_images_or_null, float* d_features_or_null, float* d_labels, int32_t* d_index_or_null);
+int trs_loader_order(const trs_loader_config* cfg, int split, int epoch, int first, int count, int32_t* h_index);
+
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no
  * distributed layer at all; this replaces what a user would otherwise script around N copies of manage.py.

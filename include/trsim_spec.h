@@ -273,6 +273,34 @@
  *   trs_set_expert zeroes them.  A record row is (steer, thr, brk, applied_steer, speed, cte, (float)((double)seg_idx / n_points * 10), done).
  *   tests/test_expert_cpu.py restates the paragraph in numpy and drives the CPU oracle with it; tests/test_expert_gpu.py compares the kernel with that
  *   restatement bit for bit; csrc/trsim_expert.hpp holds the host side (config checks, track_yaw, which ticks are captured).
+ *
+ * ---- training minibatches (trs_sample_batch, trs_loader_order; DataLoader.load of the reference, components/keras_train.py:33-69; HIP library only)
+ *   A set of n records (frame uint8[H][W][3], row float[8] as "scripted expert" defines it) stays where it is; a minibatch is gathered from it in a
+ *   keyed order.  Everything below is unsigned 64-bit integer arithmetic (mod 2^64) or one IEEE operation, so a numpy restatement is bit-exact.
+ *     mix(x):  z = x + 0x9E3779B97F4A7C15;  then the three finaliser lines of the synthetic control generator below
+ *              (z ^= z>>30; z *= 0xBF58476D1CE4E5B9;  z ^= z>>27; z *= 0x94D049BB133111EB;  z ^= z>>31)
+ *   perm(key, n, i), a bijection of [0, n) for n >= 1, computed per index without memory: a balanced Feistel network, cycle-walked.
+ *     b = max(2, bit_length(n - 1)), rounded up to even;  h = b / 2;  mask = 2^h - 1;  x = i
+ *     repeat:  L = x >> h;  R = x & mask
+ *              for r = 0, 1, 2, 3:  (L, R) = (R, L ^ (mix(key ^ ((r << 32) | R)) & mask))
+ *              x = (L << h) | R
+ *     until x < n;  perm = x                         (2^b < 4n for n >= 2: the walk is short; it ends because the network permutes [0, 2^b))
+ *   Split.  K = mix(seed);  sigma(i) = perm(K, n, i).  Split 0 (training) is sigma(0 .. n_train - 1), split 1 (validation) is
+ *     sigma(n_train .. n - 1): off_0 = 0, n_0 = n_train, off_1 = n_train, n_1 = n - n_train.  n_train is given (Python: floor(split * n) in binary64,
+ *     what sklearn's train_test_split computes for train_size = split).
+ *   Epoch order.  K_e,s = mix(K ^ (((s + 1) << 32) | e)), e >= 0 the epoch, s the split.  Position p of epoch e of split s holds record
+ *     sigma(off_s + perm(K_e,s, n_s, p)):  the same (seed, n, n_train, e, s, p) names the same record on every box and in every shard.
+ *   Frames.  Per byte v of the record's frame: float32 (float)v / 255.0f (the one IEEE division of trs_normalize_kernel); binary16: that binary32 value
+ *     rounded to nearest even; uint8: v.  Layouts NHWC [B][H][W][3] (the frame's own order) and, for float32 and binary16, NCHW [B][3][H][W].
+ *   Features and labels of a row, as recorder.LOADERS gives them.  steer = row[0] (label "expert") or row[3] ("applied");
+ *     s20 = (float)((double)row[4] / 20.0)   (the same bits as the one binary32 division row[4] / 20.0f: 53 >= 2 * 24 + 2)
+ *       loader          features            labels
+ *       speed_ctl       -                   (steer, s20)
+ *       default         -                   (steer, row[1])
+ *       speed_feature   (s20)               (steer, row[1])
+ *       full_house      (s20, row[6])       (steer, s20)
+ *   tests/test_loader_cpu.py restates the paragraph in numpy and compares trs_loader_order with it; tests/test_loader_gpu.py compares trs_batch_kernel
+ *   with that restatement bit for bit; csrc/trsim_loader.hpp is the one place the kernel and the host take the rules from.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

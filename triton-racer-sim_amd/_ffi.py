@@ -135,6 +135,21 @@ class TrsExpertCapture(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("every", C.c_int32), ("skip", C.c_int32), ("capacity", C.c_int32), ("d_frames", C.c_void_p), ("d_rows", C.c_void_p)]
 
 
+class TrsLoaderConfig(C.Structure):
+    """``trs_loader_config`` (include/trsim.h): which minibatches ``trs_sample_batch`` gathers from a collected set."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("loader", C.c_int32), ("label", C.c_int32), ("layout", C.c_int32), ("dtype", C.c_int32),
+        ("n_records", C.c_int32), ("n_train", C.c_int32), ("seed", C.c_uint64),
+    ]
+
+
+LOADER_TYPES = {"speed_ctl": 0, "default": 1, "speed_feature": 2, "full_house": 3}   # TRS_LOADER_*; the names of recorder.LOADERS, in the order of TRS_PILOT_*
+LOADER_FEATURES = {"speed_ctl": 0, "default": 0, "speed_feature": 1, "full_house": 2}
+LOADER_LABELS = {"expert": 0, "applied": 1}                             # TRS_LABEL_*
+LOADER_LAYOUTS = {"nhwc": 0, "nchw": 1}                                 # TRS_LAYOUT_*
+LOADER_DTYPES = {"float32": 0, "float16": 1, "uint8": 2}                # TRS_DTYPE_*
+LOADER_SPLITS = {"train": 0, "val": 1}                                  # TRS_SPLIT_*
+
 EXPERT_ROW = ("steering", "throttle", "breaking", "applied_steering", "speed", "cte", "segment", "done")   # a record row of trs_step_expert's capture
 
 COMM_ID_BYTES = 128                                                    # TRS_COMM_ID_BYTES
@@ -172,9 +187,12 @@ JPEG_CODEC_SYMBOLS = ["jpeg_roundtrip", "jpeg_roundtrip_host", "set_camera_codec
 # HIP library only: the scripted expert (trs_set_expert, trs_step_expert) — its checker is the numpy restatement of include/trsim_spec.h ("scripted expert") in
 # tests/test_expert_cpu.py, which drives the oracle with it (tests/test_expert_gpu.py compares the kernel with the restatement bit for bit)
 EXPERT_SYMBOLS = ["default_expert_config", "set_expert", "expert_act", "step_expert"]
+# HIP library only: the training minibatches (trs_sample_batch, trs_loader_order) — their checker is the numpy restatement of include/trsim_spec.h
+# ("training minibatches") in tests/test_loader_cpu.py (tests/test_loader_gpu.py compares the kernel with the restatement bit for bit)
+LOADER_SYMBOLS = ["default_loader_config", "sample_batch", "loader_order"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -284,6 +302,11 @@ class Api:
             "expert_act": (i32, [vp, vp, vp, vp, i32]),
             "step_expert": (i32, [vp, i32, C.POINTER(TrsExpertCapture), C.POINTER(i32)]),
         }
+        loader = {
+            "default_loader_config": (None, [C.POINTER(TrsLoaderConfig)]),
+            "sample_batch": (i32, [vp, C.POINTER(TrsLoaderConfig), vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+            "loader_order": (i32, [C.POINTER(TrsLoaderConfig), i32, i32, i32, i32, vp]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -334,6 +357,12 @@ class Api:
         self.has_expert = hasattr(cdll, prefix + "set_expert")
         if self.has_expert:
             for name, (res, args) in expert.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_loader = hasattr(cdll, prefix + "sample_batch")
+        if self.has_loader:
+            for name, (res, args) in loader.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -967,6 +967,17 @@ class BatchedEnv:
         self.sync()
         return torch.as_tensor(handle, device=f"cuda:{self.device}").cpu().numpy()
 
+    def dataset(self, frames, rows, loader="speed_ctl", label="expert", split=0.8, seed=0, capacity=None, jpeg_quality=None):
+        """A ``DeviceDataset`` (``dataset.py``) holding a COPY of a collection — the handles ``collect`` returns are only valid until the next
+        ``collect`` — in torch device storage of ``capacity`` records (``None``: what the collection needs; it grows on ``append``).  ``loader`` and
+        ``label`` choose the features and labels as ``recorder.records_for`` does, ``split`` the training share (``n_train = floor(split * n)``),
+        ``seed`` the split and every epoch's order.  ``jpeg_quality``: the stored frames go through ``device_jpeg_roundtrip`` once, so the set is what
+        a tub would have held.  ``dataset.batches(...)`` then serves shuffled minibatches from it (``trs_sample_batch``), ``dataset.pilot_loss()``
+        the validation loss of the loaded HIP pilot; ``frames=None`` makes a physics-only set."""
+        from .dataset import DeviceDataset
+        ds = DeviceDataset(self, loader=loader, label=label, split=split, seed=seed, capacity=int(capacity or 0), with_frames=frames is not None)
+        return ds.append(frames, rows, jpeg_quality=jpeg_quality)
+
     # -- device-resident part graphs (pilot -> mux -> sim without host copies of frames; car_templates/manage.py:46-75) ------
     def scratch(self, slot, shape, dtype=np.float32):
         """A handle-owned device buffer (``trs_scratch``) as a zero-copy handle; the same slot returns the same memory."""
