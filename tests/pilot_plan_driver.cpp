@@ -9,9 +9,13 @@
 //       layer 0..7 of the network over an ih x iw input, packed from the float32 Keras arrays in the two files: <prefix>.w (uint16 granules),
 //       <prefix>.goff (int32), <prefix>.bias (float32); conv2 also <prefix>.parity (the granules in the band kernel's order) and a line with the
 //       16 source granules of a kernel row; conv1 also a line with c1_bounded
+//   pilot_plan_driver blob <H> <W> <arrays> <dir> <out prefix>
+//       the tail kernels' blob of small fp32 weights (pack_tail_blob) from the 28 or 42 float32 Keras arrays in <dir>/a<k>.bin, every one on the heap at exactly
+//       its file's size, so that a read past the end of one stops the sanitizer build: <prefix>.blob (float32) and a line with the widths and the XO_* offsets
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -141,6 +145,25 @@ int main(int argc, char** argv)
             std::printf("\n");
         }
         return 0;
+    }
+    if (argc >= 7 && !std::strcmp(argv[1], "blob")) {
+        const int arrays = std::atoi(argv[4]);
+        const PilotPlan P = pilot_plan(std::atoi(argv[2]), std::atoi(argv[3]), 1, 256, arrays, pilot_default_tuning());
+        if (P.err || (arrays != 22 && arrays != 28 && arrays != 42)) return 3;
+        std::vector<std::unique_ptr<float[]>> held;
+        std::vector<const float*> arr;
+        for (int k = 0; k < arrays; ++k) {
+            const std::vector<float> v = read_floats((std::string(argv[5]) + "/a" + std::to_string(k) + ".bin").c_str());
+            if (v.empty()) return 3;
+            held.emplace_back(new float[v.size()]);                    // exactly the array: no capacity beyond it
+            std::copy(v.begin(), v.end(), held.back().get());
+            arr.push_back(held.back().get());
+        }
+        const TailBlob b = pack_tail_blob(P, arr.data());
+        std::printf("blob arch=%d F=%d f1=%d f2=%d f3=%d floats=%zu slots=%d", P.arch, P.L[7].CIN, b.f1, b.f2, b.f3, b.data.size(), (int)XO_COUNT);
+        for (int k = 0; k < XO_COUNT; ++k) std::printf(" xo%d=%d", k, b.xo[k]);
+        std::printf("\n");
+        return write_file(std::string(argv[6]) + ".blob", b.data) ? 0 : 4;
     }
     return 2;
 }

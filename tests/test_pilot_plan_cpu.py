@@ -260,3 +260,61 @@ def test_conv1_bound_for_the_fused_heads_epilogue(driver, tmp_path):
     with_nan = kernel.copy()
     with_nan[2, 3, 1, 17] = np.nan
     assert bounded(with_nan) == 0
+
+
+# ---- (d) the tail's blob of small fp32 weights ---------------------------------------------------------------------------------------------
+
+TAIL_SLOTS = ["feature1.k", "feature1.b", "feature2.k", "feature2.b", "feature3.k", "feature3.b", "dense1.behind", "dense2.k", "dense2.b", "dense3.k", "dense3.b",
+              "out.k", "out.b", "current_spd_1.k", "current_spd_1.b", "current_spd_2.k", "current_spd_2.b", "current_spd_3.k", "current_spd_3.b", "dense4.behind",
+              "dense5.k", "dense5.b", "dense6.k", "dense6.b", "out_steering.k", "out_steering.b"]          # XO_* in order
+
+
+def keras_arrays(rng, h, w, n_arrays):
+    """([(layer name, kernel, bias)] in trs_pilot_load's order, F): every array at its Keras shape (include/trsim.h; keras_train.py:127-174, 184-245)."""
+    ih, iw = h, w
+    layers = []
+    for i, (k, s, cin, cout) in enumerate(SPEC):
+        ih, iw = (ih - k) // s + 1, (iw - k) // s + 1
+        layers.append((f"conv{i + 1}", (k, k, cin, cout)))
+    flat = ih * iw * 128
+    f = {22: None, 28: (4, 8, 16), 42: (16, 32, 64)}[n_arrays]
+    layers += [("dense1", (flat + (f[2] if f else 0), 100)), ("dense2", (100, 50)), ("dense3", (50, 25)), ("out", (25, 1 if n_arrays == 42 else 2))]
+    if f:
+        layers += [("feature1", (1, f[0])), ("feature2", (f[0], f[1])), ("feature3", (f[1], f[2]))]
+    if n_arrays == 42:
+        layers += [("current_spd_1", (1, f[0])), ("current_spd_2", (f[0], f[1])), ("current_spd_3", (f[1], f[2])),
+                   ("dense4", (flat + 2 * f[2], 100)), ("dense5", (100, 50)), ("dense6", (50, 25)), ("out_steering", (25, 1))]
+    assert 2 * len(layers) == n_arrays
+    return [(nm, rng.standard_normal(shape).astype(np.float32), rng.standard_normal(shape[-1]).astype(np.float32)) for nm, shape in layers], flat
+
+
+@pytest.mark.parametrize("h,w", [(120, 160), (100, 132)])
+@pytest.mark.parametrize("n_arrays", [22, 28, 42])
+def test_tail_blob_equals_the_numpy_restatement(driver, tmp_path, h, w, n_arrays):
+    """pack_tail_blob: every slot is one Keras array, whole, or the rows of dense1 / dense4 behind the flatten; slots lie back to back in XO_* order, the ones an
+    architecture lacks at offset 0.  The driver holds every array on the heap at exactly its size under ASan: reading past dense1 or dense4 would stop it."""
+    layers, flat = keras_arrays(np.random.default_rng(n_arrays + h), h, w, n_arrays)
+    for k, a in enumerate(a for _, kern, bias in layers for a in (kern, bias)):
+        (tmp_path / f"a{k}.bin").write_bytes(a.tobytes())
+    (line,) = run_driver(driver, "blob", h, w, n_arrays, tmp_path, tmp_path / "out")
+    rec = parse(line)[1]
+    got = np.fromfile(tmp_path / "out.blob", np.float32)
+    parts = {}
+    for nm, kern, bias in layers:
+        parts[nm + ".k"], parts[nm + ".b"] = kern.reshape(-1), bias
+    for nm in ("dense1", "dense4"):
+        if nm + ".k" in parts:
+            parts[nm + ".behind"] = parts[nm + ".k"].reshape(-1, 100)[flat:].reshape(-1)
+    have = [s for s in TAIL_SLOTS if s in parts and (n_arrays != 22 or not s.endswith(".behind"))]
+    want, offsets, at = [], {}, 0
+    for s in have:
+        offsets[s] = at
+        want.append(parts[s])
+        at += parts[s].size
+    want = np.concatenate(want)
+    widths = {22: (0, 0, 0), 28: (4, 8, 16), 42: (16, 32, 64)}[n_arrays]
+    assert (rec["arch"], rec["F"], rec["slots"]) == ({22: 0, 28: 2, 42: 3}[n_arrays], flat, len(TAIL_SLOTS))
+    assert (rec["f1"], rec["f2"], rec["f3"]) == widths and rec["floats"] == want.size
+    assert [rec[f"xo{k}"] for k in range(len(TAIL_SLOTS))] == [offsets.get(s, 0) for s in TAIL_SLOTS]
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert len(have) == {22: 6, 28: 13, 42: 26}[n_arrays]

@@ -144,3 +144,98 @@ def test_closed_loop_equals_the_loop_done_by_hand(make_env, kind):
     assert a.fetch("speed").max() > 0.05
     with pytest.raises(RuntimeError, match="model_type"):
         a.step_pilot(1, {"model_type": "cnn_2d_speed_control"})       # the loaded weights are another architecture's
+
+
+STEP_RULE_CONFIGS = {"default": {}, "break": {"spd_ctl_break": True}, "smooth": {"smooth_steering_enabled": True, "smooth_steering_threshold": 0.02},
+                     "break+smooth": {"spd_ctl_break": True, "smooth_steering_enabled": True, "smooth_steering_threshold": 0.02}}
+
+
+@pytest.mark.parametrize("kind", ["cnn_2d_speed_control", "cnn_2d", "cnn_2d_speed_as_feature", "cnn_2d_full_house"])
+def test_keras_pilot_step_rule_for_every_model_type(make_env, kind):
+    """KerasPilot.step behind the network (keras_pilot.py:56-118,139-153; mapping.py:23-35) through trs_pilot_act, for every model type, config and mode.
+    The output layers get zero kernels and a chosen bias, so the raw outputs ARE the bias (asserted bit for bit) and everything the rule sees is known here:
+    predicted speed 0.3 x 20 = 6.0, target 6.6 at threshold 1.1.  5 cars of 100x132 frames: four per workgroup, the second workgroup has three idle waves.
+    Speeds 0 / 6.5 / 6.7 / 12 / 25 give full throttle, a small positive one, the (-0.2, 0) dead zone, reverse, and a brake above the 0.4 cut; every one
+    lies >= 1e-3 from every cut-off (checked below), so the 1e-5 on the atan values (tests/test_pilot.py's tolerance for the same quantities) decides no branch."""
+    from triton_racer_sim_amd.env import SLOT_JPEG_IN, SLOT_MODE, SLOT_PILOT_IN
+    h, w, n = 100, 132, 5
+    f32 = np.float32
+    capped = kind in ("cnn_2d", "cnn_2d_speed_as_feature")
+    speeds = np.array([0.0, 6.5, 6.7, 12.0, 25.0], f32)
+    modes = np.array([2, 0, 1, 2, 7], np.uint8)                        # ai, human, ai_steering, ai, no mode at all
+    speed_bias, threshold = f32(0.3), f32(1.1)
+    half_pi = math.pi / 2
+
+    # where the speeds lie relative to the rule's cut-offs, in binary64
+    target = float(speed_bias) * 20 * float(threshold) - speeds.astype(np.float64)
+    thr64, brk64 = np.arctan(target * 2) / half_pi, -np.arctan(target) / half_pi
+    assert min(np.abs(thr64 + 0.2).min(), np.abs(thr64).min(), np.abs(brk64 - 0.4).min(), np.abs(float(speed_bias) * 20 - speeds).min()) >= 1e-3
+    assert thr64[0] > 0.9 and 0 < thr64[1] < 0.2 and -0.2 < thr64[2] < 0 and thr64[3] < -0.9 and brk64[4] > 0.4 and (brk64[:3] < 0.4).all()
+
+    def want(out0, i, cfg, mode):
+        """(steering, throttle, breaking, throttle and breaking are atan values) of car i in float32"""
+        if mode not in (1, 2):
+            return f32(0), f32(0), f32(0), False
+        steer = min(max(f32(out0), f32(-1)), f32(1))
+        if capped:
+            thr, brk, soft = min(max(speed_bias, f32(-1)), f32(1)), f32(0), False
+        else:
+            pred = speed_bias * f32(20)
+            delta = f32(pred * threshold) - speeds[i]
+            thr, brk, soft = f32(math.atan(float(delta * f32(2))) / half_pi), f32(0), True
+            if -0.2 < thr < 0.0:
+                thr = f32(0)
+            if cfg.get("spd_ctl_break"):
+                thr = f32(1) if pred - speeds[i] > 0 else f32(0)
+                brk = f32(-math.atan(float(delta)) / half_pi)
+                if brk < 0.4:
+                    brk = f32(0)
+        if cfg.get("smooth_steering_enabled"):
+            t = f32(cfg["smooth_steering_threshold"])
+            steer = f32(1) if steer > t else (f32(-1) if steer < -t else steer)
+        return steer, thr, brk, soft
+
+    env = make_env("hip", n_envs=n, img_h=h, img_w=w)
+    rng = np.random.default_rng(11)
+    frames = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
+    segment = rng.uniform(0, 10, n).astype(f32)
+    full = kind == "cnn_2d_full_house"
+    d_frames, d_mode = env.scratch(SLOT_JPEG_IN, (n, h, w, 3), np.uint8), env.scratch(SLOT_MODE, (n,), np.uint8)
+    d_speed, d_segment = (env.scratch(s, (n,), f32) for s in SLOT_PILOT_IN)
+    env.upload(d_frames, frames); env.upload(d_mode, modes); env.upload(d_speed, speeds); env.upload(d_segment, segment)
+    bits = lambda a: np.asarray(a, f32).view(np.uint32)
+    for steer_bias in (f32(0.5), f32(-0.01), f32(-1.7)):
+        assert min(abs(abs(float(steer_bias)) - c) for c in (1.0, 0.02)) >= 1e-3
+        if kind in ("cnn_2d_speed_control", "cnn_2d"):
+            named = make_weights(h, w, seed=6)
+            named[20], named[21] = np.zeros_like(named[20]), np.array([steer_bias, speed_bias], f32)
+        else:
+            named, _ = make_named_weights(h, w, kind, seed=6)
+            if full:
+                named["out_steering"] = (np.zeros((25, 1), f32), np.array([steer_bias], f32))
+                named["output_speed"] = (np.zeros((25, 1), f32), np.array([speed_bias], f32))
+            else:
+                named["output_layer"] = (np.zeros((25, 2), f32), np.array([steer_bias, speed_bias], f32))
+        env.pilot_load(named)
+        raw = env.pilot_forward_host(frames, speed=None if kind in ("cnn_2d_speed_control", "cnn_2d") else speeds, segment=segment if full else None)
+        assert np.array_equal(bits(raw), bits(np.tile(np.array([steer_bias, speed_bias], f32), (n, 1))))
+        for name, cfg in STEP_RULE_CONFIGS.items():
+            for masked in (True, False):
+                ai = env.pilot_act_device(frames=d_frames, speed=d_speed, mode=d_mode if masked else None, cfg=dict(cfg, model_type=kind),
+                                          segment=d_segment if full else None)
+                steer, thr, brk = (env.to_host(a) for a in ai)
+                for i in range(n):
+                    case = (kind, float(steer_bias), name, masked, i)
+                    w_steer, w_thr, w_brk, soft = want(steer_bias, i, cfg, int(modes[i]) if masked else 2)
+                    print(case, "got", steer[i], thr[i], brk[i], "want", w_steer, w_thr, w_brk)
+                    assert bits(steer[i]) == bits(w_steer), case
+                    if masked and modes[i] not in (1, 2):
+                        assert not bits([steer[i], thr[i], brk[i]]).any(), case                      # exactly (0, 0, 0)
+                    elif capped:
+                        assert bits(thr[i]) == bits(speed_bias) and bits(brk[i]) == 0, case
+                    else:
+                        exact_thr = cfg.get("spd_ctl_break") or w_thr == 0
+                        assert (bits(thr[i]) == bits(w_thr)) if exact_thr else abs(float(thr[i]) - float(w_thr)) <= 1e-5, case
+                        assert (bits(brk[i]) == 0) if w_brk == 0 else abs(float(brk[i]) - float(w_brk)) <= 1e-5, case
+                        if cfg.get("spd_ctl_break"):
+                            assert thr[i] in (0.0, 1.0), case

@@ -18,6 +18,11 @@
 // The fp32 tail (dense2, dense3, output) and KerasPilot's post-processing (keras_pilot.py:78-95; calcThrottle /
 // calcBreak of utils/mapping.py:23-35) run in one small kernel that writes the env's next controls.
 //
+// This file: the fused convolution kernels and the host side (the context, the launches, the C entry points).  Beside it:
+//   trsim_pilot_plan.hpp    host-only: which kernel serves which layer, the packing of the weights, the layout of the tail's fp32 blob
+//   trsim_pilot_layers.hpp  the single-layer convolution kernels
+//   trsim_pilot_tail.hpp    everything behind conv7: dense1's kernel, the two tail kernels and the one KerasPilot.step rule they share
+//
 // Numerics: binary16 (fp16) operands, fp32 accumulate, activations stored as binary16 (saturating at 65504) — checked against a
 // PyTorch fp32 reference with the same fp16-rounded weights (tests/test_pilot.py, tolerance stated there).  Until round 2 the
 // 16-bit format was bfloat16: the same MFMA rate, but 8 significant bits instead of 11 — measured max |output - fp32| 5.0e-4 against
@@ -1211,432 +1216,7 @@ __global__ __launch_bounds__(1024) void trs_conv12_band_kernel(const Fuse12Param
 #endif
 }
 
-// dense2 -> dense3 -> output in fp32 (keras_train.py:161-168), then KerasPilot.step for CNN_2D_SPD_CTL (keras_pilot.py:78-95)
-struct TailParams {
-    const float* h1;           // dense1 output before ReLU, fp32: h1_slices slabs of [n][100] (split-K partial sums, added here in slice order)
-    int h1_slices; size_t h1_stride;
-    const float *w2, *b2, *w3, *b3, *w4, *b4;    // Keras layouts [IN][OUT]
-    float* raw_out;            // [n][2] or nullptr
-    const float* speed;        // 'gym/speed' or nullptr (no post-processing)
-    const uint8_t* mode;       // 'usr/mode' per car (TRS_MODE_*) or nullptr: a car outside AI / AI_STEERING gets (0, 0, 0) (keras_pilot.py:139)
-    float *steer, *thr, *brk;  // next controls
-    int n, act;
-    float threshold, rev_mult, brk_mult, smooth_thr;
-    int use_break, smooth, direct;   // direct: ModelType.CNN_2D (outputs are steering and throttle)
-};
-
-// raw outputs -> KerasPilot.step's controls for one frame (keras_pilot.py:78-95; ModelType.CNN_2D: :56-62)
-__device__ __forceinline__ void tail_finish(const TailParams& p, int i, float out0, float out1)
-{
-    if (p.raw_out) { p.raw_out[2 * i] = out0; p.raw_out[2 * i + 1] = out1; }
-    if (!p.act) return;
-    if (p.mode && p.mode[i] != TRS_MODE_AI && p.mode[i] != TRS_MODE_AI_STEERING) { p.steer[i] = 0.0f; p.thr[i] = 0.0f; p.brk[i] = 0.0f; return; }
-    float steering = out0 < -1.0f ? -1.0f : (out0 > 1.0f ? 1.0f : out0);           // __cap (keras_pilot.py:142-145)
-    const float predicted = out1 * 20.0f;                                           // :83
-    const float real = p.speed[i];
-    const float kHalfPi = 1.57079632679489661923f;
-    float delta = predicted * p.threshold - real;                                   // calcThrottle (mapping.py:23-28)
-    float throttle = p.rev_mult * atanf(delta * 2.0f) / kHalfPi;
-    if (throttle > -0.2f && throttle < 0.0f) throttle = 0.0f;
-    float breaking = 0.0f;
-    if (p.direct) throttle = out1 < -1.0f ? -1.0f : (out1 > 1.0f ? 1.0f : out1);    // ModelType.CNN_2D: __cap of both outputs (:60)
-    else if (p.use_break) {                                                         // keras_pilot.py:88-90, mapping.py:30-35
-        throttle = (predicted - real > 0.0f) ? 1.0f : 0.0f;
-        breaking = -1.0f * p.brk_mult * atanf(delta * 1.0f) / kHalfPi;
-        if (breaking < 0.4f) breaking = 0.0f;
-    }
-    if (p.smooth) {                                                                 // keras_pilot.py:147-153
-        if (steering > p.smooth_thr) steering = 1.0f;
-        else if (steering < -p.smooth_thr) steering = -1.0f;
-    }
-    p.steer[i] = steering; p.thr[i] = throttle; p.brk[i] = breaking;
-}
-
-__global__ __launch_bounds__(256) void trs_pilot_tail_kernel(const TailParams p)
-{
-    // one wave per frame: lane o owns output neuron o of the current layer; activations travel through LDS
-    __shared__ float s1[4][100], s2[4][50], s3[4][25], s4[4][2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int i = blockIdx.x * 4 + wv;
-    if (i >= p.n) return;
-    // The three small layers are latency chains (100 + 50 + 25 dependent FMAs per lane); what made them slow was a global weight
-    // load in front of every FMA.  All of a lane's weights — column `lane` of each matrix — are requested up front (175 independent
-    // loads, coalesced across lanes) and land while the slab sums run; the FMAs then read registers and LDS only.
-    float wc2[100], wc3[50], wc4[25];
-    {
-        const int o2 = min(lane, 49), o3 = min(lane, 24), o4 = min(lane, 1);
-#pragma unroll
-        for (int k = 0; k < 100; ++k) wc2[k] = p.w2[k * 50 + o2];
-#pragma unroll
-        for (int k = 0; k < 50; ++k) wc3[k] = p.w3[k * 25 + o3];
-#pragma unroll
-        for (int k = 0; k < 25; ++k) wc4[k] = p.w4[k * 2 + o4];
-    }
-    const float bias2 = p.b2[min(lane, 49)], bias3 = p.b3[min(lane, 24)], bias4 = p.b4[min(lane, 1)];
-    {   // dense1's 100 outputs of this frame = the K-slice slabs added in slice order (fixed order: run-to-run identical).  A lane
-        // owns outputs `lane` and `lane + 64`; the phase is pure load latency, so 16 slices x 2 outputs are requested together.
-        const bool two = lane + 64 < 100;
-        const float* src0 = p.h1 + (size_t)i * 100 + lane;
-        const float* src1 = src0 + (two ? 64 : 0);
-        float x0 = 0.0f, x1 = 0.0f;
-        // groups of 16 slices, the last one padded: a slice past the end is read at the last slice's address and added as 0.0f (x + 0.0f == x for
-        // every x that can reach the ReLU's test).  31 slices (240x320) are two load round trips; the ragged tail used to go 4 + 4 + 4 + 1 + 1 + 1
-        // slices at a time: seven dependent round trips, the whole difference between this kernel's 6.0 us at 120x160 and 8.8 us at 240x320.
-        auto add_groups = [&](auto gc) {
-            constexpr int G = decltype(gc)::value;
-            for (int sl = 0; sl < p.h1_slices; sl += G) {
-                float v0[G], v1[G];
-#pragma unroll
-                for (int q = 0; q < G; ++q) {
-                    const int sq = min(sl + q, p.h1_slices - 1);
-                    v0[q] = src0[(size_t)sq * p.h1_stride]; v1[q] = src1[(size_t)sq * p.h1_stride];
-                }
-#pragma unroll
-                for (int q = 0; q < G; ++q) {
-                    const bool in = sl + q < p.h1_slices;
-                    x0 += in ? v0[q] : 0.0f; x1 += in ? v1[q] : 0.0f;
-                }
-            }
-        };
-        if (p.h1_slices <= 8) add_groups(std::integral_constant<int, 8>{});      // (120x160: 8 slices - no padded loads)
-        else add_groups(std::integral_constant<int, 16>{});
-        s1[wv][lane] = x0 > 0.f ? x0 : 0.f;                                 // dense1's ReLU
-        if (two) s1[wv][lane + 64] = x1 > 0.f ? x1 : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 50) {
-        float s = bias2;
-#pragma unroll
-        for (int k = 0; k < 100; ++k) s = fmaf(s1[wv][k], wc2[k], s);
-        s2[wv][lane] = s > 0.f ? s : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 25) {
-        float s = bias3;
-#pragma unroll
-        for (int k = 0; k < 50; ++k) s = fmaf(s2[wv][k], wc3[k], s);
-        s3[wv][lane] = s > 0.f ? s : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 2) {
-        float s = bias4;
-#pragma unroll
-        for (int k = 0; k < 25; ++k) s = fmaf(s3[wv][k], wc4[k], s);
-        s4[wv][lane] = s;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane != 0) return;
-    tail_finish(p, i, s4[wv][0], s4[wv][1]);
-}
-
-// ---- dense1 as its own kernel (round 2) -------------------------------------------------------------------------------------
-// dense1 (4608 -> 100 at 120x160, 83,328 -> 100 at 240x320) is 0.8 % of the network's arithmetic but, as a 1x1 convolution on
-// the chunked kernel, it and the tail were 23 of 267 us: 36 K slices of partial sums written and read back (19 MB against 9.4 MB
-// of activations).  Here a workgroup takes 32 frames x one K slice (8 slices fill the chip at 1024 frames):
-//   * the slice's activations go through LDS (coalesced 16-byte loads of each frame's contiguous run, chunks of 72 granules,
-//     double buffered; row pitch 73 granules = conflict-free ds_read_b128 fragments);
-//   * wave w owns channels 32 w .. 32 w + 31: all 36 k-steps of a chunk on one accumulator, its weight fragments ALL in flight (a
-//     register ring of 36 granules straight from L2, each refilled for the next chunk right behind the MFMA that read it);
-//   * workgroups are numbered so that one XCD works on one K slice: its 1/8 of the weights stays in that XCD's L2;
-//   * the slice's partial sums go to slab [slice][frame][100]; the tail kernel adds the slabs in slice order.
-// 15.5 -> 7.3 us (and the tail 7.5 -> 5.8 with 8 slabs instead of 36); 47 -> 36 us at 512 x 240x320.  Measured and NOT kept
-// (profiles/r02_pilot_dense.txt): the tail in the same launch, run by the last K slice of a frame group to arrive — the hand-over
-// between XCDs costs a write-through drain (2.2 us) and an sc1 read (4 us) and leaves 32 workgroups to do what 256 do in the
-// tail kernel: 17 us in one launch against 7.3 + 5.8 in two.
-struct DenseParams {
-    const u4v* act;            // conv7's output: fp16 [n][G] granules (the NHWC flatten)
-    const u4v* w;              // [G][128] granules
-    const float* bias;         // [128]
-    float* slab;               // [KS][n][100] fp32
-    int n, G, gps, KS, groups;
-};
-
-#ifndef TRS_DENSE_ABLATE
-#define TRS_DENSE_ABLATE 0   /* timing-only diagnostic builds (scripts/r04_dense_ablate.sh), never shipped */
-#endif
-constexpr int kDenseSteps = kDenseChunk / 2;
-constexpr int kDenseStage = 9;             // granules a thread stages per chunk and per 32 frames (32 x 72 / 256)
-
-// NF = frame blocks of 32 per workgroup.  NF = 2 (round 4, long K: 240x320): every weight fragment feeds TWO MFMAs (frames 0..31 and 32..63), so the
-// weight stream — per-lane 16-byte loads straight from L2, 1.18 MB per workgroup at 512 x 240x320, measured as 15 of the kernel's 37 us by a
-// timing-only build (profiles/r04_pilot_dense.txt) — is halved for the same arithmetic; 150 KB of LDS, one workgroup per CU.
-template <int NF>
-__global__ __launch_bounds__(256) void trs_pilot_dense_kernel(const DenseParams p)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int group = idx % p.groups, slice = xcd + 8 * (idx / p.groups);
-    if (slice >= p.KS) return;                                              // the grid is padded to whole rounds of 8 slices
-    u4v* const st = reinterpret_cast<u4v*>(psmem);                          // [2][32 NF][73] granules
-    const int gs = slice * p.gps, ge = min(p.G, gs + p.gps);
-    const int f0 = group * 32 * NF;
-    constexpr int kStage = kDenseStage * NF, kBuf = 32 * NF * kDensePitch;
-
-    // staging: thread t moves granules e = t + 256 i (i < 9 NF) of a chunk: frame e / 72, granule e % 72
-    int sbase[kStage], sdst[kStage];
-#pragma unroll
-    for (int i = 0; i < kStage; ++i) {
-        const int e = tid + 256 * i, f = e / kDenseChunk, gi = e - f * kDenseChunk;
-        sbase[i] = min(f0 + f, p.n - 1) * p.G;
-        sdst[i] = f * kDensePitch + gi;
-    }
-    u4v pf[kStage];
-    auto stage_load = [&](int c0) {
-#pragma unroll
-        for (int i = 0; i < kStage; ++i) {
-            const int e = tid + 256 * i, f = e / kDenseChunk, gi = e - f * kDenseChunk;
-#if TRS_DENSE_ABLATE == 2   /* timing-only: every chunk re-reads the slice's first chunk (cache hits instead of the HBM stream) */
-            pf[i] = p.act[sbase[i] + min(gs + gi, p.G - 1)]; (void)c0;
-#else
-            pf[i] = p.act[sbase[i] + min(c0 + gi, p.G - 1)];
-#endif
-        }
-    };
-    auto stage_write = [&](int buf) {
-        u4v* const sn = st + buf * kBuf;
-#pragma unroll
-        for (int i = 0; i < kStage; ++i) sn[sdst[i]] = pf[i];
-    };
-    // weight ring: granule 2 j + h of the chunk for k-step j, this wave's 32 channels
-    u4v wr[kDenseSteps];
-    const u4v* const wlane = p.w + wave * 32 + r;
-    auto ring_load = [&](int j, int c0) { wr[j] = wlane[(size_t)min(c0 + 2 * j + h, p.G - 1) * 128]; };
-    stage_load(gs);
-#pragma unroll
-    for (int j = 0; j < kDenseSteps; ++j) ring_load(j, gs);
-
-    f32x16 acc[NF];
-#pragma unroll
-    for (int b = 0; b < NF; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[b][i] = slice == 0 ? p.bias[wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * h] : 0.0f;
-    stage_write(0);
-    __syncthreads();
-
-    auto chunk = [&](int c0, int buf, auto prefetch) {
-        const u4v* const sb = st + buf * kBuf + r * kDensePitch + h;
-#pragma unroll
-        for (int j = 0; j < kDenseSteps; ++j) {
-            const bool past = c0 + 2 * j >= ge;                             // ragged last chunk: a zero fragment instead of a branch
-#pragma unroll
-            for (int b = 0; b < NF; ++b) {
-                u4v a = sb[b * 32 * kDensePitch + 2 * j];
-                if (past) a = u4v{0u, 0u, 0u, 0u};
-                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, wr[j]), __builtin_bit_cast(h16x8, a), acc[b], 0, 0, 0);
-            }
-#if TRS_DENSE_ABLATE != 1   /* 1: timing-only, the weights of the first chunk serve every chunk (no weight stream) */
-            if constexpr (decltype(prefetch)::value) ring_load(j, c0 + kDenseChunk);
-#endif
-        }
-    };
-    int c0 = gs, buf = 0;
-    for (; c0 + kDenseChunk < ge; c0 += kDenseChunk, buf ^= 1) {            // every chunk but the last: the next one's operands are requested underneath
-        stage_load(c0 + kDenseChunk);
-        chunk(c0, buf, std::true_type{});
-        stage_write(buf ^ 1);
-        __syncthreads();
-    }
-    chunk(c0, buf, std::false_type{});
-
-    {   // D[cout][frame]: lane = frame r, registers 4 q4 .. + 3 = channels 32 wave + 8 q4 + 4 h .. + 3: one 16-byte store each
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.slab, 0, (int)((size_t)p.KS * p.n * 400), 0x00020000);
-#pragma unroll
-        for (int b = 0; b < NF; ++b) {
-            const int fr = f0 + 32 * b + r;
-            const int row = ((slice * p.n + fr) * 100) * 4;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int c = wave * 32 + 8 * q4 + 4 * h;
-                if (c < 100 && fr < p.n) {
-                    const u4v v = {__float_as_uint(acc[b][4 * q4]), __float_as_uint(acc[b][4 * q4 + 1]), __float_as_uint(acc[b][4 * q4 + 2]), __float_as_uint(acc[b][4 * q4 + 3])};
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rs, row + c * 4, 0, 0);
-                }
-            }
-        }
-    }
-}
-
-// The tail of the model types with extra inputs (components/keras_train.py): cnn_2d_speed_as_feature =
-// Keras_2D_CNN.get_model(num_feature_vectors = 1) (:127-174: speed / 20 -> Dense 4 -> 8 -> 16, concatenated behind the flatten in
-// front of dense1) and cnn_2d_full_house = Keras_2D_FULL_HOUSE.get_model (:184-245: 'loc/segment' -> 16 -> 32 -> 64 joins the
-// flatten for the speed head dense1..3 -> output_speed; speed / 20 -> 16 -> 32 -> 64 joins both for the steering head
-// dense4..6 -> out_steering; output = [steering, speed]).  The rows of dense1 / dense4 that multiply the flatten ran on the
-// matrix cores (split-K slabs, added here in slice order); the rows of the small branches and everything behind are fp32, one
-// wave per frame, a fixed summation order (k ascending) so that two runs agree bit for bit.
-enum { XO_F1W, XO_F1B, XO_F2W, XO_F2B, XO_F3W, XO_F3B, XO_W1Y, XO_W2, XO_B2, XO_W3, XO_B3, XO_W4, XO_B4,
-       XO_C1W, XO_C1B, XO_C2W, XO_C2B, XO_C3W, XO_C3B, XO_W4Y, XO_W5, XO_B5, XO_W6, XO_B6, XO_W7, XO_B7, XO_COUNT };
-
-struct TailExParams {
-    const float* h1; int h1_slices; size_t h1_stride;       // dense1: slabs of [n][100]
-    const float* h4; int h4_slices; size_t h4_stride;       // dense4 (full house) or nullptr
-    const float* blob; int xo[32];
-    int arch, f1, f2, f3;                                    // widths of the small branches (4, 8, 16 or 16, 32, 64)
-    const float* speed; const float* segment; const int32_t* seg_idx; int np;   // 'gym/speed'; 'loc/segment' given, or from the env's index
-    const uint8_t* mode;
-    float* raw_out; float *steer, *thr, *brk;
-    int n, act;
-    float threshold, rev_mult, brk_mult, smooth_thr;
-    int use_break, smooth;
-};
-
-__device__ __forceinline__ void dense_small(const float* in, int nin, const float* w, const float* b, int nout, float* out, int lane, bool relu)
-{   // out[o] = act(b[o] + sum_k in[k] * w[k][o]), lanes over o (nout <= 128).  One FMA chain per output, k ascending; the weights of 16 k
-    // are requested together (a load in front of every FMA made this the slowest kernel of the full-house loop: one L2 round trip per k)
-    for (int o = lane; o < nout; o += 64) {
-        float s = b[o];
-        int k = 0;
-        for (; k + 16 <= nin; k += 16) {
-            float wv[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) wv[j] = w[(k + j) * nout + o];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) s = fmaf(in[k + j], wv[j], s);
-        }
-        for (; k + 4 <= nin; k += 4) {
-            float wv[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wv[j] = w[(k + j) * nout + o];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s = fmaf(in[k + j], wv[j], s);
-        }
-        for (; k < nin; ++k) s = fmaf(in[k], w[k * nout + o], s);
-        out[o] = relu ? (s > 0.f ? s : 0.f) : s;
-    }
-}
-
-__global__ __launch_bounds__(256) void trs_pilot_tail_ex_kernel(const TailExParams p)
-{
-    __shared__ float sy[4][3][64], ss[4][3][64], sh[4][2][100], sa[4][2][50], sb[4][2][25], so[4][2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int i = blockIdx.x * 4 + wv;
-    if (i >= p.n) return;
-    const float* B = p.blob;
-    const float real = p.speed[i];
-    // the small branches
-    float fin = real / 20.0f;                                                      // keras_pilot.py:68,100: speed / 20
-    if (p.arch == TRS_PILOT_FULL_HOUSE)                                            // 'loc/segment' (track_data_process.py:106-107: idx / len * 10, binary64)
-        fin = p.segment ? p.segment[i] : (float)((double)p.seg_idx[i] / (double)p.np * 10.0);
-    if (lane == 0) sy[wv][2][63] = fin;
-    __builtin_amdgcn_wave_barrier();
-    dense_small(&sy[wv][2][63], 1, B + p.xo[XO_F1W], B + p.xo[XO_F1B], p.f1, sy[wv][0], lane, true);
-    __builtin_amdgcn_wave_barrier();
-    dense_small(sy[wv][0], p.f1, B + p.xo[XO_F2W], B + p.xo[XO_F2B], p.f2, sy[wv][1], lane, true);
-    __builtin_amdgcn_wave_barrier();
-    dense_small(sy[wv][1], p.f2, B + p.xo[XO_F3W], B + p.xo[XO_F3B], p.f3, sy[wv][2], lane, true);
-    if (p.arch == TRS_PILOT_FULL_HOUSE) {
-        if (lane == 0) ss[wv][2][63] = real / 20.0f;
-        __builtin_amdgcn_wave_barrier();
-        dense_small(&ss[wv][2][63], 1, B + p.xo[XO_C1W], B + p.xo[XO_C1B], p.f1, ss[wv][0], lane, true);
-        __builtin_amdgcn_wave_barrier();
-        dense_small(ss[wv][0], p.f1, B + p.xo[XO_C2W], B + p.xo[XO_C2B], p.f2, ss[wv][1], lane, true);
-        __builtin_amdgcn_wave_barrier();
-        dense_small(ss[wv][1], p.f2, B + p.xo[XO_C3W], B + p.xo[XO_C3B], p.f3, ss[wv][2], lane, true);
-    }
-    __builtin_amdgcn_wave_barrier();
-    // dense1 (and dense4): slabs in slice order, then the rows of the small branches, then ReLU
-    for (int head = 0; head < (p.arch == TRS_PILOT_FULL_HOUSE ? 2 : 1); ++head) {
-        const float* slab = head ? p.h4 : p.h1;
-        const int slices = head ? p.h4_slices : p.h1_slices;
-        const size_t stride = head ? p.h4_stride : p.h1_stride;
-        const float* wy = B + p.xo[head ? XO_W4Y : XO_W1Y];
-        for (int o = lane; o < 100; o += 64) {
-            float x = 0.0f;
-            {   // the K-slice slabs in slice order, eight loads in flight
-                int sl = 0;
-                for (; sl + 8 <= slices; sl += 8) {
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = slab[(size_t)(sl + j) * stride + (size_t)i * 100 + o];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) x += v[j];
-                }
-                for (; sl < slices; ++sl) x += slab[(size_t)sl * stride + (size_t)i * 100 + o];
-            }
-            for (int k = 0; k < p.f3; k += 4) {                             // f3 is 16 or 64
-                float w4[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) w4[j] = wy[(k + j) * 100 + o];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) x = fmaf(sy[wv][2][k + j], w4[j], x);
-            }
-            if (head) for (int k = 0; k < p.f3; k += 4) {
-                float w4[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) w4[j] = wy[(p.f3 + k + j) * 100 + o];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) x = fmaf(ss[wv][2][k + j], w4[j], x);
-            }
-            sh[wv][head][o] = x > 0.f ? x : 0.f;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int nz = p.arch == TRS_PILOT_FULL_HOUSE ? 1 : 2;                         // outputs of the first head
-    dense_small(sh[wv][0], 100, B + p.xo[XO_W2], B + p.xo[XO_B2], 50, sa[wv][0], lane, true);
-    if (p.arch == TRS_PILOT_FULL_HOUSE) dense_small(sh[wv][1], 100, B + p.xo[XO_W5], B + p.xo[XO_B5], 50, sa[wv][1], lane, true);
-    __builtin_amdgcn_wave_barrier();
-    dense_small(sa[wv][0], 50, B + p.xo[XO_W3], B + p.xo[XO_B3], 25, sb[wv][0], lane, true);
-    if (p.arch == TRS_PILOT_FULL_HOUSE) dense_small(sa[wv][1], 50, B + p.xo[XO_W6], B + p.xo[XO_B6], 25, sb[wv][1], lane, true);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-        auto lin = [&](const float* in, const float* w, const float* b, int nout, int o) {
-            float s = b[o];
-            for (int k = 0; k < 25; ++k) s = fmaf(in[k], w[k * nout + o], s);
-            return s;
-        };
-        if (p.arch == TRS_PILOT_FULL_HOUSE) {                                      // [out_steering, out_speed] (keras_train.py:240)
-            so[wv][0] = lin(sb[wv][1], B + p.xo[XO_W7], B + p.xo[XO_B7], 1, 0);
-            so[wv][1] = lin(sb[wv][0], B + p.xo[XO_W4], B + p.xo[XO_B4], nz, 0);
-        } else {
-            so[wv][0] = lin(sb[wv][0], B + p.xo[XO_W4], B + p.xo[XO_B4], nz, 0);
-            so[wv][1] = lin(sb[wv][0], B + p.xo[XO_W4], B + p.xo[XO_B4], nz, 1);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane != 0) return;
-    const float out[2] = {so[wv][0], so[wv][1]};
-    if (p.raw_out) { p.raw_out[2 * i] = out[0]; p.raw_out[2 * i + 1] = out[1]; }
-    if (!p.act) return;
-    if (p.mode && p.mode[i] != TRS_MODE_AI && p.mode[i] != TRS_MODE_AI_STEERING) { p.steer[i] = 0.0f; p.thr[i] = 0.0f; p.brk[i] = 0.0f; return; }
-    float steering = out[0] < -1.0f ? -1.0f : (out[0] > 1.0f ? 1.0f : out[0]);
-    float throttle, breaking = 0.0f;
-    if (p.arch == TRS_PILOT_SPD_FTR) {                                             // keras_pilot.py:67-76: both outputs capped, breaking 0
-        throttle = out[1] < -1.0f ? -1.0f : (out[1] > 1.0f ? 1.0f : out[1]);
-    } else {                                                                       // full house: the speed controller (:97-118)
-        const float kHalfPi = 1.57079632679489661923f;
-        const float predicted = out[1] * 20.0f;
-        const float delta = predicted * p.threshold - real;
-        throttle = p.rev_mult * atanf(delta * 2.0f) / kHalfPi;
-        if (throttle > -0.2f && throttle < 0.0f) throttle = 0.0f;
-        if (p.use_break) {
-            throttle = (predicted - real > 0.0f) ? 1.0f : 0.0f;
-            breaking = -1.0f * p.brk_mult * atanf(delta * 1.0f) / kHalfPi;
-            if (breaking < 0.4f) breaking = 0.0f;
-        }
-    }
-    if (p.smooth) {
-        if (steering > p.smooth_thr) steering = 1.0f;
-        else if (steering < -p.smooth_thr) steering = -1.0f;
-    }
-    p.steer[i] = steering; p.thr[i] = throttle; p.brk[i] = breaking;
-}
-
-// fp16 range check (trs_pilot_range_check): activations are stored as binary16 and SATURATE at 65504 (v_pk_min_i16 in every epilogue; the
-// reference computes in fp32, components/keras_pilot.py:49-59).  A stored value of exactly 0x7BFF is a saturated one (a sum that lands on
-// 65504 by itself is not a practical case): counted per layer into `per_layer` and into the handle's TRS_F_STATS slot.
-__global__ __launch_bounds__(256) void trs_pilot_count_sat_kernel(const unsigned short* act, size_t n, unsigned long long* per_layer, unsigned long long* total)
-{
-    unsigned cnt = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) cnt += act[i] == 0x7BFFu ? 1u : 0u;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0 && cnt) { atomicAdd(per_layer, (unsigned long long)cnt); atomicAdd(total, (unsigned long long)cnt); }
-}
-
-__global__ void trs_zero_controls_kernel(float* a, float* b, float* c, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { a[i] = 0.f; b[i] = 0.f; c[i] = 0.f; }
-}
+#include "trsim_pilot_tail.hpp"   // everything behind conv7: dense1's kernel, the two tails and KerasPilot.step's one rule, the range check's counter, the zeroed controls
 
 // ---- the host side: the device buffers, the kernels' parameter blocks filled from the plan (trsim_pilot_plan.hpp), and the launches ----
 struct ConvLayer {
@@ -1648,10 +1228,8 @@ struct PilotCtx {
     PilotPlan plan;                       // what trs_pilot_load decided for this frame size, batch capacity, device and tuning
     ConvLayer L[9];                       // conv1..7 + dense1 (1x1 "conv" over frames) [+ dense4: the second head of cnn_2d_full_house]
     trsim::DevBuf<void> act[9];           // outputs of L[i] for n_cap frames (fp16; act[7], act[8] float)
-    trsim::DevBuf<float> xblob;           // small fp32 weights of the extra dense branches (TailExParams offsets)
-    int xo[32] = {};                      // offsets (floats) into xblob
+    trsim::DevBuf<float> xblob; TailLayout tail;   // the small fp32 weights the tail kernel reads, and where each lies (pack_tail_blob)
     trsim::DevBuf<void> slab2; int last_slices2 = 1;   // dense4 partial sums
-    trsim::DevBuf<float> w2, b2, w3, b3, w4, b4;
     trsim::DevBuf<float> raw;             // [n_cap][2]
     trsim::DevBuf<uint8_t> tmp_frames; size_t tmp_cap = 0;   // room for tmp_cap bytes of frames and side inputs (+ the callers' padding)
     int last_n = 0, last_slices = 1;
@@ -1810,54 +1388,107 @@ int check_model_type(const PilotCtx* c, const trs_pilot_config* cfg)
     return TRS_OK;
 }
 
-TailParams make_tail(const PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io)
+// the block both tails share, from the view (a delayed one under an observation latency), the caller's arrays (io; nullptr: the env's own), cfg and act
+StepIo step_io(const PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io)
 {
-    TailParams t{};
-    t.w2 = c->w2.get(); t.b2 = c->b2.get(); t.w3 = c->w3.get(); t.b3 = c->b3.get(); t.w4 = c->w4.get(); t.b4 = c->b4.get();
+    StepIo t{};
     t.raw_out = raw_out; t.n = n; t.act = act ? 1 : 0;
-    if (act) {
-        t.speed = v.speed; t.steer = v.ctl_steer; t.thr = v.ctl_thr; t.brk = v.ctl_brk;
-        if (io) { t.speed = io->speed ? io->speed : v.speed; t.mode = io->mode; t.steer = io->steer; t.thr = io->thr; t.brk = io->brk; }
-        t.threshold = cfg->spd_ctl_threshold; t.rev_mult = cfg->spd_ctl_reverse_multiplier; t.brk_mult = cfg->spd_ctl_break_multiplier;
-        t.use_break = cfg->spd_ctl_break; t.smooth = cfg->smooth_steering_enabled; t.smooth_thr = cfg->smooth_steering_threshold;
-        t.direct = cfg->model_type == TRS_PILOT_CNN_2D;
-    }
+    t.speed = (io && io->speed) ? io->speed : v.speed;
+    if (!act) return t;
+    t.steer = v.ctl_steer; t.thr = v.ctl_thr; t.brk = v.ctl_brk;
+    if (io) { t.mode = io->mode; t.steer = io->steer; t.thr = io->thr; t.brk = io->brk; }
+    t.threshold = cfg->spd_ctl_threshold; t.rev_mult = cfg->spd_ctl_reverse_multiplier; t.brk_mult = cfg->spd_ctl_break_multiplier;
+    t.use_break = cfg->spd_ctl_break; t.smooth = cfg->smooth_steering_enabled; t.smooth_thr = cfg->smooth_steering_threshold;
+    t.capped = cfg->model_type == TRS_PILOT_CNN_2D || c->plan.arch == TRS_PILOT_SPD_FTR;
     return t;
 }
 
-int run_tail(PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io = nullptr)
+int run_tail(PilotCtx* c, const TrsEnvView& v, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io)
 {
-    if (c->plan.arch != TRS_PILOT_SPD_CTL) {
+    const PilotPlan& P = c->plan;
+    const float* const h1 = static_cast<const float*>(c->slab.get());
+    const float* const B = c->xblob.get(); const int* const xo = c->tail.xo;
+    const size_t h1_stride = (size_t)n * P.L[7].act_elems();
+    const StepIo s = step_io(c, v, n, raw_out, cfg, act, io);
+    if (P.arch == TRS_PILOT_SPD_CTL) {
+        const TailParams t{h1, c->last_slices, h1_stride, B + xo[XO_W2], B + xo[XO_B2], B + xo[XO_W3], B + xo[XO_B3], B + xo[XO_W4], B + xo[XO_B4], s};
+        hipLaunchKernelGGL(trs_pilot_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, v.stream, t);
+    } else {
         TailExParams t{};
-        t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->plan.L[7].act_elems();
-        t.h4 = static_cast<const float*>(c->slab2.get()); t.h4_slices = c->last_slices2; t.h4_stride = (size_t)n * c->plan.L[8].act_elems();
-        t.blob = c->xblob.get(); std::memcpy(t.xo, c->xo, sizeof t.xo);
-        t.arch = c->plan.arch; t.f1 = c->plan.arch == TRS_PILOT_SPD_FTR ? 4 : 16; t.f2 = 2 * t.f1; t.f3 = 4 * t.f1;
-        t.speed = (io && io->speed) ? io->speed : v.speed; t.segment = io ? io->segment : nullptr; t.seg_idx = v.seg_idx; t.np = v.n_points > 0 ? v.n_points : 1;
-        t.raw_out = raw_out; t.n = n; t.act = act ? 1 : 0;
-        if (act) {
-            t.steer = v.ctl_steer; t.thr = v.ctl_thr; t.brk = v.ctl_brk;
-            if (io) { t.mode = io->mode; t.steer = io->steer; t.thr = io->thr; t.brk = io->brk; }
-            t.threshold = cfg->spd_ctl_threshold; t.rev_mult = cfg->spd_ctl_reverse_multiplier; t.brk_mult = cfg->spd_ctl_break_multiplier;
-            t.use_break = cfg->spd_ctl_break; t.smooth = cfg->smooth_steering_enabled; t.smooth_thr = cfg->smooth_steering_threshold;
-        }
+        t.h1 = h1; t.h1_slices = c->last_slices; t.h1_stride = h1_stride;
+        t.h4 = static_cast<const float*>(c->slab2.get()); t.h4_slices = c->last_slices2; t.h4_stride = (size_t)n * P.L[8].act_elems();
+        t.blob = B; std::memcpy(t.xo, xo, sizeof t.xo);
+        t.arch = P.arch; t.f1 = c->tail.f1; t.f2 = c->tail.f2; t.f3 = c->tail.f3;
+        t.segment = io ? io->segment : nullptr; t.seg_idx = v.seg_idx; t.np = v.n_points > 0 ? v.n_points : 1;
+        t.io = s;
         hipLaunchKernelGGL(trs_pilot_tail_ex_kernel, dim3((n + 3) / 4), dim3(256), 0, v.stream, t);
-        HIPCHK(hipGetLastError());
-        return TRS_OK;
     }
-    TailParams t = make_tail(c, v, n, raw_out, cfg, act, io);
-    t.h1 = static_cast<const float*>(c->slab.get()); t.h1_slices = c->last_slices; t.h1_stride = (size_t)n * c->plan.L[7].act_elems();
-    hipLaunchKernelGGL(trs_pilot_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, v.stream, t);
     HIPCHK(hipGetLastError());
     return TRS_OK;
 }
 
-// the whole pilot: convolutions, dense1 and the tail
+// the whole pilot: convolutions, dense1 and the tail (raw_out = nullptr: the context's own buffer)
 int forward_and_tail(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n, float* raw_out, const trs_pilot_config* cfg, bool act, const ActIo* io = nullptr)
 {
     int rc = forward(c, v, d_frames, n);
     if (rc) return rc;
-    return run_tail(c, v, n, raw_out, cfg, act, io);
+    return run_tail(c, v, n, raw_out ? raw_out : c->raw.get(), cfg, act, io);
+}
+
+// args[0] is None -> (0.0, 0.0, 0.0) (keras_pilot.py:46-47)
+int zero_controls(const TrsEnvView& v, float* steer, float* thr, float* brk, int n)
+{
+    hipLaunchKernelGGL(trs_zero_controls_kernel, dim3((n + 255) / 256), dim3(256), 0, v.stream, steer, thr, brk, n);
+    HIPCHK(hipGetLastError());
+    return TRS_OK;
+}
+
+// how every entry point behind trs_pilot_load begins: the handle's view and its loaded pilot (need_pass: one that has run a forward pass)
+int enter(trs_env* e, TrsEnvView* v, PilotCtx** c, bool need_pass = false)
+{
+    if (!trs_internal_view(e, v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
+    *c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
+    if (!*c || (need_pass && !(*c)->last_n)) return trs_internal_fail(TRS_ERR_STATE, need_pass ? "no forward pass yet" : "no pilot loaded");
+    return TRS_OK;
+}
+
+// the frames a call reads: the caller's, or the env's latest ones for a call over all its envs; may_be_none: before the first rendered step the answer is nullptr,
+// not a refusal.  `text` is the entry point's own refusal.
+int frames_or_latest(const TrsEnvView& v, const uint8_t** d_frames, int n, bool may_be_none, const char* text)
+{
+    if (*d_frames) return TRS_OK;
+    if ((!may_be_none && !v.latest_frame) || n != v.n) return trs_internal_fail(TRS_ERR_ARG, text);
+    *d_frames = v.latest_frame;
+    return TRS_OK;
+}
+const char* const kLatestNeeds = "latest-frame source needs a rendered step and n_images == n_envs";
+
+// what the two host variants share behind their checks: frames and the side inputs given are staged in the temporary buffer, the pass runs by the rule of the
+// device entry point (with side inputs trs_pilot_forward_ex's; without, and for cnn_2d_speed_control always, trs_pilot_forward's: the env's own speed,
+// n_images == n_envs for the other model types), the outputs are read back
+int forward_staged(trs_env* e, PilotCtx* c, const TrsEnvView& v, const uint8_t* h_frames, const float* h_speed, const float* h_segment, int n, float* h_out)
+{
+    HIPCHK(hipSetDevice(v.device));
+    const size_t bytes = (size_t)n * c->plan.H * c->plan.W * 3, extra = (size_t)n * 8;
+    if (bytes + extra > c->tmp_cap) {
+        HIPCHK(hipStreamSynchronize(v.stream));
+        c->tmp_cap = 0;
+        HIPCHK(c->tmp_frames.alloc(bytes + extra + 128));
+        c->tmp_cap = bytes + extra;
+    }
+    uint8_t* const d_frames = c->tmp_frames.get();
+    float* const d_spd = reinterpret_cast<float*>(d_frames + ((bytes + 63) & ~(size_t)63));
+    float* const d_seg = d_spd + n;
+    HIPCHK(hipMemcpyAsync(d_frames, h_frames, bytes, hipMemcpyHostToDevice, v.stream));
+    if (h_speed) HIPCHK(hipMemcpyAsync(d_spd, h_speed, (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
+    if (h_segment) HIPCHK(hipMemcpyAsync(d_seg, h_segment, (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
+    int rc = (h_speed && c->plan.arch != TRS_PILOT_SPD_CTL) ? trs_pilot_forward_ex(e, d_frames, d_spd, h_segment ? d_seg : nullptr, n, nullptr)
+                                                            : trs_pilot_forward(e, d_frames, n, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
+    trs_internal_count(e, (uint64_t)n * 2 * sizeof(float), (uint64_t)bytes);
+    HIPCHK(hipStreamSynchronize(v.stream));
+    return TRS_OK;
 }
 
 }  // namespace
@@ -1915,31 +1546,10 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
         if (rc) return rc;
         HIPCHK(c->act[i].alloc((size_t)P.n_cap * l.act_elems() * (l.out_f32 ? 4 : 2) + 64));
     }
-    auto up = [&](trsim::DevBuf<float>& dst, const float* src, size_t n) -> int { std::vector<float> t(src, src + n); return upload(dst, t); };
-    const int nz = P.arch == TRS_PILOT_FULL_HOUSE ? 1 : 2;                // outputs of the first head
-    int rc = up(c->w2, arr[16], 100 * 50); if (!rc) rc = up(c->b2, arr[17], 50);
-    if (!rc) rc = up(c->w3, arr[18], 50 * 25); if (!rc) rc = up(c->b3, arr[19], 25);
-    if (!rc) rc = up(c->w4, arr[20], 25 * nz); if (!rc) rc = up(c->b4, arr[21], nz);
-    if (rc) return rc;
-    if (P.arch != TRS_PILOT_SPD_CTL) {        // the small fp32 branches of the tail: one blob, offsets by XO_*
-        const int F = (int)P.L[7].CIN;
-        const int f1 = P.arch == TRS_PILOT_SPD_FTR ? 4 : 16, f2 = 2 * f1, f3 = 4 * f1;
-        std::vector<float> blob;
-        auto put = [&](int slot, const float* src, size_t n) { c->xo[slot] = (int)blob.size(); blob.insert(blob.end(), src, src + n); };
-        put(XO_F1W, arr[22], f1); put(XO_F1B, arr[23], f1); put(XO_F2W, arr[24], (size_t)f1 * f2); put(XO_F2B, arr[25], f2);
-        put(XO_F3W, arr[26], (size_t)f2 * f3); put(XO_F3B, arr[27], f3);
-        put(XO_W1Y, arr[14] + (size_t)F * 100, (size_t)f3 * 100);            // dense1's rows behind the flatten
-        put(XO_W2, arr[16], 100 * 50); put(XO_B2, arr[17], 50); put(XO_W3, arr[18], 50 * 25); put(XO_B3, arr[19], 25);
-        put(XO_W4, arr[20], 25 * nz); put(XO_B4, arr[21], nz);
-        if (P.arch == TRS_PILOT_FULL_HOUSE) {
-            put(XO_C1W, arr[28], f1); put(XO_C1B, arr[29], f1); put(XO_C2W, arr[30], (size_t)f1 * f2); put(XO_C2B, arr[31], f2);
-            put(XO_C3W, arr[32], (size_t)f2 * f3); put(XO_C3B, arr[33], f3);
-            put(XO_W4Y, arr[34] + (size_t)F * 100, (size_t)2 * f3 * 100);    // dense4's rows for [feature3 | current_spd_3]
-            put(XO_W5, arr[36], 100 * 50); put(XO_B5, arr[37], 50); put(XO_W6, arr[38], 50 * 25); put(XO_B6, arr[39], 25);
-            put(XO_W7, arr[40], 25); put(XO_B7, arr[41], 1);
-        }
-        rc = upload(c->xblob, blob);
-        if (rc) return rc;
+    {   // the small fp32 weights behind dense1: one blob, offsets by XO_*
+        const TailBlob blob = pack_tail_blob(P, arr);
+        int rc = upload(c->xblob, blob.data); if (rc) return rc;
+        c->tail = blob;
     }
     // ---- the parameter blocks of the two fused kernels, all but their per-call fields ----
     if (P.head.on) {
@@ -1966,98 +1576,49 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
 
 TRS_EXPORT int trs_pilot_forward(trs_env* e, const uint8_t* d_frames, int n_images, float* d_out)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c)) return rc;
     if (n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "n_images must be in [1, n_envs]");
     HIPCHK(hipSetDevice(v.device));
-    if (!d_frames) {
-        if (!v.latest_frame || n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs a rendered step and n_images == n_envs");
-        d_frames = v.latest_frame;
-    }
+    if (int rc = frames_or_latest(v, &d_frames, n_images, false, kLatestNeeds)) return rc;
     if (c->plan.arch != TRS_PILOT_SPD_CTL && n_images != v.n)
         return trs_internal_fail(TRS_ERR_ARG, "this model type also reads speed (and segment): use trs_pilot_forward_ex, or n_images == n_envs for the env's own");
-    return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw.get(), nullptr, false);
+    return forward_and_tail(c, v, d_frames, n_images, d_out, nullptr, false);
 }
 
 TRS_EXPORT int trs_pilot_forward_ex(trs_env* e, const uint8_t* d_frames, const float* d_speed, const float* d_segment, int n_images, float* d_out)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c)) return rc;
     if (n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "n_images must be in [1, n_envs]");
     if ((!d_speed || (c->plan.arch == TRS_PILOT_FULL_HOUSE && !d_segment)) && n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "the env's own speed / segment need n_images == n_envs");
     HIPCHK(hipSetDevice(v.device));
-    if (!d_frames) {
-        if (!v.latest_frame || n_images != v.n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs a rendered step and n_images == n_envs");
-        d_frames = v.latest_frame;
-    }
+    if (int rc = frames_or_latest(v, &d_frames, n_images, false, kLatestNeeds)) return rc;
     const ActIo io{d_speed, d_segment, nullptr, nullptr, nullptr, nullptr};
-    return forward_and_tail(c, v, d_frames, n_images, d_out ? d_out : c->raw.get(), nullptr, false, &io);
+    return forward_and_tail(c, v, d_frames, n_images, d_out, nullptr, false, &io);
 }
 
 TRS_EXPORT int trs_pilot_forward_host_ex(trs_env* e, const uint8_t* h_frames, const float* h_speed, const float* h_segment, int n_images, float* h_out)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c)) return rc;
     if (!h_frames || !h_out || n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "bad argument (n_images must be in [1, n_envs])");
     if (c->plan.arch != TRS_PILOT_SPD_CTL && (!h_speed || (c->plan.arch == TRS_PILOT_FULL_HOUSE && !h_segment))) return trs_internal_fail(TRS_ERR_ARG, "this model type needs speed (and segment) arrays");
-    HIPCHK(hipSetDevice(v.device));
-    const size_t bytes = (size_t)n_images * c->plan.H * c->plan.W * 3, extra = (size_t)n_images * 8;
-    if (bytes + extra > c->tmp_cap) {
-        HIPCHK(hipStreamSynchronize(v.stream));
-        c->tmp_cap = 0;
-        HIPCHK(c->tmp_frames.alloc(bytes + extra + 128));
-        c->tmp_cap = bytes + extra;
-    }
-    float* d_spd = reinterpret_cast<float*>(c->tmp_frames.get() + ((bytes + 63) & ~(size_t)63));
-    float* d_seg = d_spd + n_images;
-    HIPCHK(hipMemcpyAsync(c->tmp_frames.get(), h_frames, bytes, hipMemcpyHostToDevice, v.stream));
-    if (h_speed) HIPCHK(hipMemcpyAsync(d_spd, h_speed, (size_t)n_images * 4, hipMemcpyHostToDevice, v.stream));
-    if (h_segment) HIPCHK(hipMemcpyAsync(d_seg, h_segment, (size_t)n_images * 4, hipMemcpyHostToDevice, v.stream));
-    int rc = c->plan.arch == TRS_PILOT_SPD_CTL ? trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get())
-                                          : trs_pilot_forward_ex(e, c->tmp_frames.get(), h_speed ? d_spd : nullptr, h_segment ? d_seg : nullptr, n_images, c->raw.get());
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-    trs_internal_count(e, (uint64_t)n_images * 2 * sizeof(float), (uint64_t)bytes);
-    HIPCHK(hipStreamSynchronize(v.stream));
-    return TRS_OK;
+    return forward_staged(e, c, v, h_frames, h_speed, h_segment, n_images, h_out);
 }
 
 TRS_EXPORT int trs_pilot_forward_host(trs_env* e, const uint8_t* h_frames, int n_images, float* h_out)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c)) return rc;
     if (!h_frames || !h_out || n_images < 1 || n_images > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "bad argument (n_images must be in [1, n_envs])");
-    HIPCHK(hipSetDevice(v.device));
-    const size_t bytes = (size_t)n_images * c->plan.H * c->plan.W * 3;
-    if (bytes > c->tmp_cap) {
-        HIPCHK(hipStreamSynchronize(v.stream));
-        c->tmp_cap = 0;
-        HIPCHK(c->tmp_frames.alloc(bytes + 64));
-        c->tmp_cap = bytes;
-    }
-    HIPCHK(hipMemcpyAsync(c->tmp_frames.get(), h_frames, bytes, hipMemcpyHostToDevice, v.stream));
-    int rc = trs_pilot_forward(e, c->tmp_frames.get(), n_images, c->raw.get());
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_out, c->raw.get(), (size_t)n_images * 2 * sizeof(float), hipMemcpyDeviceToHost, v.stream));
-    trs_internal_count(e, (uint64_t)n_images * 2 * sizeof(float), (uint64_t)n_images * c->plan.H * c->plan.W * 3);
-    HIPCHK(hipStreamSynchronize(v.stream));
-    return TRS_OK;
+    return forward_staged(e, c, v, h_frames, nullptr, nullptr, n_images, h_out);
 }
 
 TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t n_floats)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c || !c->last_n) return trs_internal_fail(TRS_ERR_STATE, "no forward pass yet");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c, true)) return rc;
     if (layer < 0 || layer > 7 || !h_dst) return trs_internal_fail(TRS_ERR_ARG, "bad layer");
     const size_t total = (size_t)c->last_n * c->plan.L[layer].act_elems();
     if (n_floats != total) return trs_internal_fail(TRS_ERR_ARG, "size mismatch");
@@ -2082,10 +1643,8 @@ TRS_EXPORT int trs_pilot_debug_layer(trs_env* e, int layer, float* h_dst, size_t
 
 TRS_EXPORT int trs_pilot_range_check(trs_env* e, uint64_t h_out[8])
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c || !c->last_n) return trs_internal_fail(TRS_ERR_STATE, "no forward pass yet");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c, true)) return rc;
     if (!h_out) return trs_internal_fail(TRS_ERR_ARG, "null output");
     HIPCHK(hipSetDevice(v.device));
     { int rc = materialise_layers(c, v, 0, 6); if (rc) return rc; }
@@ -2109,35 +1668,24 @@ TRS_EXPORT int trs_pilot_range_check(trs_env* e, uint64_t h_out[8])
 TRS_EXPORT int trs_pilot_act(trs_env* e, const trs_pilot_config* cfg, const uint8_t* d_frames, const float* d_speed, const float* d_segment,
                              const uint8_t* d_mode, float* d_steer, float* d_thr, float* d_brk, int n)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c)) return rc;
     if (!cfg || cfg->struct_size != sizeof(trs_pilot_config)) return trs_internal_fail(TRS_ERR_ARG, "trs_pilot_config.struct_size mismatch");
     { int rm = check_model_type(c, cfg); if (rm) return rm; }
     if (!d_steer || !d_thr || !d_brk || n < 0 || n > c->plan.n_cap) return trs_internal_fail(TRS_ERR_ARG, "null output or n out of range (n <= n_envs)");
     if ((!d_speed || (c->plan.arch == TRS_PILOT_FULL_HOUSE && !d_segment)) && n != v.n) return trs_internal_fail(TRS_ERR_ARG, "the env's own speed / segment need n == n_envs");
     HIPCHK(hipSetDevice(v.device));
     if (n == 0) return TRS_OK;
-    if (!d_frames) {
-        if (n != v.n) return trs_internal_fail(TRS_ERR_ARG, "latest-frame source needs n == n_envs");
-        d_frames = v.latest_frame;
-    }
-    if (!d_frames) {                                // args[0] is None -> (0.0, 0.0, 0.0) (keras_pilot.py:46-47)
-        hipLaunchKernelGGL(trs_zero_controls_kernel, dim3((n + 255) / 256), dim3(256), 0, v.stream, d_steer, d_thr, d_brk, n);
-        HIPCHK(hipGetLastError());
-        return TRS_OK;
-    }
+    if (int rc = frames_or_latest(v, &d_frames, n, true, "latest-frame source needs n == n_envs")) return rc;
+    if (!d_frames) return zero_controls(v, d_steer, d_thr, d_brk, n);       // no frame rendered yet
     const ActIo io{d_speed, d_segment, d_mode, d_steer, d_thr, d_brk};
-    return forward_and_tail(c, v, d_frames, n, c->raw.get(), cfg, true, &io);
+    return forward_and_tail(c, v, d_frames, n, nullptr, cfg, true, &io);
 }
 
 TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_steps)
 {
-    TrsEnvView v;
-    if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    PilotCtx* c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    TrsEnvView v; PilotCtx* c;
+    if (int rc = enter(e, &v, &c)) return rc;
     if (!cfg || cfg->struct_size != sizeof(trs_pilot_config)) return trs_internal_fail(TRS_ERR_ARG, "trs_pilot_config.struct_size mismatch");
     if (n_steps < 1) return trs_internal_fail(TRS_ERR_ARG, "n_steps < 1");
     { int rm = check_model_type(c, cfg); if (rm) return rm; }
@@ -2150,20 +1698,13 @@ TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_ste
             int rc = trs_internal_camera_codec(e, seen, &seen);
             if (rc) return rc;
         }
-        if (v.obs_on && seen) {                     // an observation latency is set: KerasPilot.step on what each car has been told (frame, speed, segment), and
-            TrsEnvView o = v;                       // (0, 0, 0) for the cars nothing has reached yet (keras_pilot.py:46-47) through the tail's mode mask
-            o.speed = v.obs_speed; o.seg_idx = v.obs_seg_idx;
-            const ActIo io{nullptr, nullptr, v.obs_mode, v.ctl_steer, v.ctl_thr, v.ctl_brk};
-            int rc = forward_and_tail(c, o, seen, v.n, c->raw.get(), cfg, true, &io);
-            if (rc) return rc;
-        } else if (!v.obs_on && seen) {             // KerasPilot.step on the frame of the previous tick
-            int rc = forward_and_tail(c, v, seen, v.n, c->raw.get(), cfg, true);
-            if (rc) return rc;
-        } else {                                    // args[0] is None -> (0.0, 0.0, 0.0) (keras_pilot.py:46-47)
-            hipLaunchKernelGGL(trs_zero_controls_kernel, dim3((v.n + 255) / 256), dim3(256), 0, v.stream, v.ctl_steer, v.ctl_thr, v.ctl_brk, v.n);
-            HIPCHK(hipGetLastError());
-        }
-        int rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
+        // KerasPilot.step on the frame of the previous tick and the env's own speed and segment.  With an observation latency: on what each car has been told
+        // (frame, speed, segment), and (0, 0, 0) for the cars nothing has reached yet (keras_pilot.py:46-47) through the rule's mode mask
+        TrsEnvView o = v;
+        ActIo io{nullptr, nullptr, nullptr, v.ctl_steer, v.ctl_thr, v.ctl_brk};
+        if (v.obs_on) { o.speed = v.obs_speed; o.seg_idx = v.obs_seg_idx; io.mode = v.obs_mode; }
+        int rc = seen ? forward_and_tail(c, o, seen, v.n, nullptr, cfg, true, &io) : zero_controls(v, v.ctl_steer, v.ctl_thr, v.ctl_brk, v.n);
+        if (!rc) rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
         if (rc) return rc;
     }
     return TRS_OK;

@@ -1,6 +1,7 @@
 // trsim_pilot_plan.hpp — which kernel serves which layer of the pilot, and how its weights are packed, as arithmetic a host compiler builds without HIP:
 // the layer geometry of Keras_2D_CNN for a frame size, the kernel of every layer with its LDS layout (pilot_plan), what a call of n frames adds to it
-// (dense_call, head_call, the grids), the constants the plan shares with the kernels, and the packing of the Keras arrays into fp16 granules.
+// (dense_call, head_call, the grids), the constants the plan shares with the kernels, the packing of the Keras arrays into fp16 granules, and the
+// blob of small fp32 weights the tail kernels read (its slots XO_*, the branch widths, pack_tail_blob).
 // No device pointer lives here: trsim_pilot.hip fills its kernel parameter blocks from a PilotPlan.  tests/pilot_plan_driver.cpp runs it on the CPU.
 #pragma once
 #include <algorithm>
@@ -402,6 +403,48 @@ inline int conv1_bounded(const PilotLayer& l0, const float* K0, const float* B0)
         if (!(sum < 60000.0)) return 0;                                   // (a NaN weight: not bounded)
     }
     return 1;
+}
+
+// ---- the small fp32 weights of the tail kernels: one blob per loaded model ----------------------------------------------------------
+// Slot XO_x of the blob = Keras array x, whole and in Keras's [IN][OUT] layout, except the two that are the rows of dense1 / dense4 BEHIND the flatten
+// (XO_W1Y, XO_W4Y: the rows the matrix cores do not take).  F1..3 = feature1..3, C1..3 = current_spd_1..3, W2..B4 = dense2, dense3 and the first head's
+// output, W5..B7 = dense5, dense6, out_steering.  22 arrays fill W2..B4 only (trs_pilot_tail_kernel reads nothing else), 28 all up to B4, 42 every slot.
+enum { XO_F1W, XO_F1B, XO_F2W, XO_F2B, XO_F3W, XO_F3B, XO_W1Y, XO_W2, XO_B2, XO_W3, XO_B3, XO_W4, XO_B4,
+       XO_C1W, XO_C1B, XO_C2W, XO_C2B, XO_C3W, XO_C3B, XO_W4Y, XO_W5, XO_B5, XO_W6, XO_B6, XO_W7, XO_B7, XO_COUNT };
+struct TailLayout {
+    int xo[32] = {};                       // offset (floats) of slot XO_x in the blob; 0 for a slot the architecture does not have
+    int f1 = 0, f2 = 0, f3 = 0;            // widths of the small input branches: 4, 8, 16 (cnn_2d_speed_as_feature) or 16, 32, 64 (cnn_2d_full_house); 0: none
+};
+struct TailBlob : TailLayout { std::vector<float> data; };
+// arr: the Keras arrays in trs_pilot_load's order, each exactly its Keras size (dense1 is [F + f3][100], dense4 [F + 2 f3][100], F = P.L[7].CIN)
+inline TailBlob pack_tail_blob(const PilotPlan& P, const float* const* arr)
+{
+    TailBlob t;
+    const size_t F = (size_t)P.L[7].CIN;
+    const int nz = P.arch == TRS_PILOT_FULL_HOUSE ? 1 : 2;                // outputs of the first head
+    auto put = [&](int slot, const float* src, size_t n) { t.xo[slot] = (int)t.data.size(); t.data.insert(t.data.end(), src, src + n); };
+    // a branch 1 -> f1 -> f2 -> f3 from six consecutive arrays into six consecutive slots
+    auto branch = [&](int slot, int a) {
+        const size_t n[6] = {(size_t)t.f1, (size_t)t.f1, (size_t)t.f1 * t.f2, (size_t)t.f2, (size_t)t.f2 * t.f3, (size_t)t.f3};
+        for (int j = 0; j < 6; ++j) put(slot + j, arr[a + j], n[j]);
+    };
+    // dense(a) -> dense(a + 2) -> an output of nout: 100 -> 50 -> 25 -> nout
+    auto head = [&](int slot, int a, int nout) {
+        const size_t n[6] = {100 * 50, 50, 50 * 25, 25, (size_t)25 * nout, (size_t)nout};
+        for (int j = 0; j < 6; ++j) put(slot + j, arr[a + j], n[j]);
+    };
+    if (P.arch != TRS_PILOT_SPD_CTL) {
+        t.f1 = P.arch == TRS_PILOT_SPD_FTR ? 4 : 16; t.f2 = 2 * t.f1; t.f3 = 4 * t.f1;
+        branch(XO_F1W, 22);
+        put(XO_W1Y, arr[14] + F * 100, (size_t)t.f3 * 100);               // dense1's rows behind the flatten
+    }
+    head(XO_W2, 16, nz);
+    if (P.arch == TRS_PILOT_FULL_HOUSE) {
+        branch(XO_C1W, 28);
+        put(XO_W4Y, arr[34] + F * 100, (size_t)2 * t.f3 * 100);           // dense4's rows for [feature3 | current_spd_3]
+        head(XO_W5, 36, 1);
+    }
+    return t;
 }
 
 }  // namespace trsim
