@@ -1,7 +1,9 @@
-// Test driver (CPU): the slot arithmetic of the observation ring (triton-racer-sim_amd/csrc/trsim_plan.hpp, ObsRing — the header alone) printed for
-// tests/test_latency_cpu.py, which builds it with AddressSanitizer + UBSan and compares it with a deque model.
+// Test driver (CPU): the slot and byte arithmetic of the observation ring (triton-racer-sim_amd/csrc/trsim_plan.hpp, ObsRing and obs_bytes — the header alone)
+// printed for tests/test_latency_cpu.py, which builds it with AddressSanitizer + UBSan and compares it with a deque model and with the same sums in Python.
 //   latency_driver ring <max_ticks> <steps> <L_0> <L_1> ...
 //        "ring <slots>", then per step T = 0..steps: "step <T> <slot of step T> <slot of step T + 1>" and per env "obs <T> <env> <arrived> <slot of the observation>"
+//   latency_driver bytes <n_envs> <H> <W> <depth> <render> <max_ticks>
+//        what trs_set_latency allocates (obs_bytes), one "<name> <bytes>" per line
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,8 +12,22 @@
 
 using namespace trsim;
 
+static int bytes_mode(char** a)
+{
+    ObsRing R;
+    R.max_ticks = std::atoi(a[5]);
+    if (R.max_ticks < 1 || R.max_ticks > kMaxLatencyTicks) return 2;
+    const ObsBytes b = obs_bytes(R, std::atoi(a[0]), std::atoi(a[1]), std::atoi(a[2]), std::atoi(a[4]) != 0, std::atoi(a[3]) != 0);
+    const struct { const char* name; size_t v; } rows[] = {
+        {"img_env", b.img_env}, {"dep_env", b.dep_env}, {"img_stride", b.img_stride}, {"dep_stride", b.dep_stride}, {"ring_img", b.ring_img},
+        {"ring_dep", b.ring_dep}, {"ring_tel", b.ring_tel}, {"tel", b.tel}, {"flag", b.flag}, {"ticks", b.ticks}};
+    for (const auto& r : rows) std::printf("%s %zu\n", r.name, r.v);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 8 && !std::strcmp(argv[1], "bytes")) return bytes_mode(argv + 2);
     if (argc < 5 || std::strcmp(argv[1], "ring")) return 2;
     ObsRing R;
     R.max_ticks = std::atoi(argv[2]);

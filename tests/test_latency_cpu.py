@@ -1,5 +1,5 @@
 """Observation latency without a GPU: the ring arithmetic of triton-racer-sim_amd/csrc/trsim_plan.hpp (ObsRing, through tests/latency_driver.cpp:
-host compiler, AddressSanitizer + UBSan) against a deque model of HipGymInterface's delay line, the ms -> ticks rule of BatchedGymInterface, and the
+host compiler, AddressSanitizer + UBSan) against a deque model of HipGymInterface's delay line, the bytes of the rings (obs_bytes) against the same sums here, the ms -> ticks rule of BatchedGymInterface, and the
 oracle's function table, which has no observation latency."""
 import collections
 import math
@@ -67,6 +67,26 @@ def test_ring_slots_deliver_the_delay_lines_record_and_the_next_step_never_lands
 def test_ring_driver_refuses_a_ring_outside_the_abi(driver):
     for bad in (0, 31):
         assert subprocess.run([driver, "ring", str(bad), "3", "0"], capture_output=True).returncode == 2
+
+
+@pytest.mark.parametrize("n,h,w,depth,render,max_ticks", [(1, 2, 4, 0, 1, 1), (5, 30, 44, 1, 1, 3), (1281, 16, 24, 0, 1, 30), (7, 120, 160, 1, 0, 2),
+                                                          (65536, 240, 320, 1, 1, 30)])     # the last one's frame ring is past 4 GiB: nothing is computed in int
+def test_ring_bytes_are_the_sums_trs_set_latency_allocates(driver, n, h, w, depth, render, max_ticks):
+    out = subprocess.run([driver, "bytes", *[str(v) for v in (n, h, w, depth, render, max_ticks)]], capture_output=True, text=True,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-2000:]
+    got = {k: int(v) for k, v in (line.split(" ") for line in out.stdout.splitlines())}
+    up256 = lambda b: (b + 255) // 256 * 256
+    slots = max_ticks + 2
+    img_env = h * w * 3 if render else 0
+    dep_env = h * w * 4 if render and depth else 0
+    want = {"img_env": img_env, "dep_env": dep_env, "img_stride": up256(n * img_env), "dep_stride": up256(n * dep_env),
+            "ring_img": slots * up256(n * img_env), "ring_dep": slots * up256(n * dep_env),
+            "ring_tel": slots * 6 * n * 4, "tel": 6 * n * 4, "flag": 2 * n, "ticks": n * 4}
+    assert got == want
+    if n == 65536:
+        assert got["ring_img"] > 2**32 and got["img_stride"] > 2**31
 
 
 def test_sim_latency_becomes_ticks_by_the_one_car_rule():

@@ -230,6 +230,36 @@ def test_off_again_the_handle_steps_like_one_that_never_set_a_latency(make_env):
     assert_observation(g, [truth_record(t, depth=True)], ticks, "first step of the new history", depth=True)
 
 
+@pytest.mark.parametrize("render", [True, False])
+def test_a_latency_set_over_a_latency_is_the_setting_alone(make_env, render):
+    """One delay for all (the view into the ring) -> different delays in a larger ring (gathered frames) -> one delay in a smaller ring (the view again) -> off:
+    every setting replaces the buffers of the one before.  After every step the observation is that of a twin that took the same steps without a latency
+    and set only the current setting where it begins; off again, the outputs are those of a twin that never set one.  render=False: telemetry only."""
+    n = 5
+    kw = dict(n_envs=n, img_h=30, img_w=44, depth=render, render=render, track=track_points("generated"), auto_reset=True)
+    g = make_env("hip", **kw)
+    done = 0
+    for ticks, mx in ((2, 2), ([0, 3, 1, 3, 2], 3), ([1, 1, 1, 1, 1], 1)):
+        t = make_env("hip", **kw)
+        if done:
+            t.step_synthetic(done, 1)
+        g.set_latency(ticks, max_ticks=mx); t.set_latency(ticks, max_ticks=mx)
+        assert g.latency()[1] == mx and np.array_equal(g.latency()[0], t.latency()[0])
+        for k in range(mx + 3):
+            g.step_synthetic(1, 1); t.step_synthetic(1, 1); done += 1
+            for i, (a, b) in enumerate(zip(g.observation(image=render), t.observation(image=render))):
+                assert (a is None and b is None) or np.array_equal(bits(a), bits(b)), (ticks, k, i)
+            for name in ("img", "depth") if render else ():
+                assert np.array_equal(bits(dev_np(g.device_observation(name))), bits(dev_np(t.device_observation(name)))), (ticks, k, name)
+    t = make_env("hip", **kw)
+    t.step_synthetic(done, 1)
+    g.set_latency(None)
+    for k in range(3):
+        g.step_synthetic(1, 1); t.step_synthetic(1, 1)
+        for i, (a, b) in enumerate(zip(g.fetch_outputs(image=render), t.fetch_outputs(image=render))):
+            assert (a is None and b is None) or np.array_equal(bits(a), bits(b)), ("off", k, i)
+
+
 def test_load_track_restarts_the_history_and_a_reset_does_not(make_env):
     n = 9
     pts = track_points("generated")

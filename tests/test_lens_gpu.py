@@ -364,3 +364,39 @@ def test_camera_changes_reach_a_running_resident_worker(make_env, checker):
     with pytest.raises(RuntimeError, match="field not available"):
         env.fetch("lens_table")                                        # back to the pinhole: the lens tables are freed
     assert env.step_mode()[0] == "resident"
+
+
+def test_a_lens_set_over_a_lens_renders_like_a_handle_that_set_only_that_camera(make_env):
+    """lens A -> lens B (another offset_x) -> pinhole -> lens A -> a reload with lens A set, two steps each: after every step the frames are those of a twin
+    that took the same steps under the pinhole camera and set only the stage's camera where the stage begins (the camera does not enter the physics),
+    and while a lens is on both handles hold the same table and palette.  Every stage replaces or releases the tables of the one before."""
+    n, H, W = 3, 30, 48
+    pts = track_points("generated")
+    A, B = (1.5, 0.3, 0.4), (0.6, 1.1, -0.7)
+    kw = dict(n_envs=n, img_h=H, img_w=W, depth=True, track=pts, auto_reset=True)
+    env = make_env("hip", **kw)
+
+    def same(a, b, where, lens):
+        for name in ("img", "depth", "pos_x", "pos_z", "yaw", "seg_idx"):
+            assert np.array_equal(a.fetch(name), b.fetch(name)), (where, name)
+        if lens:
+            for name in ("lens_table", "lens_palette"):
+                assert np.array_equal(a.fetch(name).view(np.uint32), b.fetch(name).view(np.uint32)), (where, name)
+
+    t = 0
+    for stage, lens in enumerate((A, B, None, A)):
+        twin = make_env("hip", **kw)
+        for k in range(t):
+            twin.step(*controls(n, k))
+        for e in (env, twin):
+            e.set_camera(*lens) if lens else e.set_camera(None)
+        assert env.camera() == (lens or (0.0, 0.0, 0.0))
+        for _ in range(2):
+            env.step(*controls(n, t)); twin.step(*controls(n, t)); t += 1
+            same(env, twin, (stage, t), lens)
+    env.load_track(pts)                                                # lens A is set: its tables are staged for the new map and replace the old ones
+    twin = make_env("hip", camera=A, **kw)
+    assert env.camera() == A
+    for k in range(2):
+        env.step(*controls(n, k)); twin.step(*controls(n, k))
+        same(env, twin, ("reload", k), A)

@@ -11,10 +11,24 @@
 
 #include "../../include/trsim.h"
 #include "trsim_device.hpp"
+#include "trsim_latency.hpp"
 #include "trsim_mem.hpp"
 #include "trsim_tables.hpp"
 
-namespace trsim { struct Resident; struct Comm; }
+namespace trsim {
+struct Resident; struct Comm;
+// What trs_load_track and trs_set_camera stage beside the handle, check, and then move-assign into it (trsim_hip.hip): the struct a feature is staged in is the
+// member the handle holds, so a commit is one assignment and "none" is the assignment of {}.  The old value's buffers are released by the assignment.
+struct TrackStage {                      // the device buffers of a track
+    DevBuf<> blob_p, blob_r;             // physics LDS image | raster LDS image (+ the constants of a track with elevation and of the lens camera behind it)
+    DevBuf<float> tangent, start_yaw;
+    DevBuf<float> dpitch;                // [n_points] view pitch per raw track point (device: (float)pitch + dpitch[i])
+};
+struct LensStage {                       // the lens tables of a map for a camera
+    DevBuf<> dev; size_t pal_off = 0;    // device: half-width planes F | L | D | M, then the lens palette at byte pal_off (LensBlock points into it)
+    LensTables T;                        // host tables of the map (full frame), built by build_lens_tables
+};
+}  // namespace trsim
 
 struct trs_env {
     trs_config cfg{};
@@ -26,36 +40,20 @@ struct trs_env {
     trsim::DevBuf<uint8_t> img[2];
     trsim::UniformRows uniform_ok;       // which frame buffer holds the present palette's uniform rows (sky, beyond the far plane) of every env: every step path asks it (trsim_plan.hpp)
     trsim::DevBuf<float> depth[2];
-    trsim::DevBuf<> blob_p;              // physics LDS image
-    trsim::DevBuf<> blob_r;              // raster LDS image
-    trsim::DevBuf<float> tangent, start_yaw;
+    trsim::TrackStage trk;               // the loaded track's device buffers (track_commit)
     trsim::DevBuf<float4> cam;           // [kRing][n]
     trsim::DevBuf<float> cam_pitch;      // [kRing][n] the frames' view pitches (tracks with elevation)
-    trsim::DevBuf<float> dpitch;         // [n_points] view pitch per raw track point (device: (float)pitch + dpitch[i])
     bool hilly = false;                       // the loaded track has elevation (include/trsim_spec.h): the HILLS instantiations of the step kernels run
     trsim::HillBlock hill_host{};             // host copy of the block behind the raster image (trs_load_track fills the camera part, upload_palette the frame filter)
     // the lens camera (trs_set_camera; include/trsim_spec.h, "lens camera"): the LENS instantiations of the step kernels run while lens_on
     trs_camera camera{};                      // what trs_set_camera set (all zero: the pinhole)
     bool lens_on = false;
-    trsim::LensTables lens;                   // host tables of the loaded map (full frame), built by lens_build
-    trsim::DevBuf<> lens_dev;                 // device: half-width planes F | L | D | M, then the lens palette (LensBlock points into it)
-    size_t lens_pal_off = 0;                  // byte offset of the palette in lens_dev
+    trsim::LensStage lens;                    // its tables for the loaded map, as lens_stage built them ({}: the pinhole, or no track yet)
     // scene lighting (trs_set_lighting; include/trsim_spec.h, "scene lighting"): the LIGHT instantiations of the step kernels run while light_on
     bool light_on = false;
     const float* light = nullptr;             // view: the registered float[n][8], the caller's or light_own's
     trsim::DevBuf<float> light_own;           // trs_set_lighting_host's copy
-    // observation latency (trs_set_latency; include/trsim_spec.h, "observation latency"): while lat.on() every step renders into a slot of ring_img /
-    // ring_dep, trs_obs_kernel files its telemetry in ring_tel and gathers every env's delayed record; img[] / depth[] then hold the gathered frames
-    // (envs with different delays) or lie idle (one delay for all: the view points into the ring)
-    trsim::ObsRing lat;                       // slot arithmetic (trsim_plan.hpp)
-    uint64_t lat_base = 0;                    // step_count when the history began: T = step_count - lat_base
-    bool lat_uniform = true; int lat_all = 0; // every env has the delay lat_all
-    trsim::DevBuf<int32_t> lat_ticks; std::vector<int32_t> lat_host;   // int32[n]: L_e, device and host
-    trsim::DevBuf<uint8_t> ring_img; size_t ring_img_stride = 0;   // [slots] frames of all envs, stride bytes apart (a multiple of 256)
-    trsim::DevBuf<float> ring_dep; size_t ring_dep_stride = 0;     // [slots] depth frames (cfg.depth), stride bytes apart
-    trsim::DevBuf<float> ring_tel;            // [slots][6][n]: x y z speed cte | seg_idx (int32)
-    trsim::DevBuf<float> obs_tel[2];          // [6][n] the gathered telemetry, by T & 1
-    trsim::DevBuf<uint8_t> obs_flag[2];       // arrived[n] | mode[n] (TRS_MODE_AI where arrived, else TRS_MODE_HUMAN: the pilot tail's mask), by T & 1
+    trsim::ObsHistory obs;                    // observation latency (trs_set_latency; trsim_latency.hpp): while obs.on() every step renders into its ring and trs_obs_kernel runs behind it
     trsim::DevBuf<unsigned long long> stats;
     trsim::DevBuf<double> loc_q; trsim::DevBuf<int32_t> loc_out; int loc_cap = 0;   // trs_locate: room for loc_cap queries
     trsim::DevBuf<uint8_t> pre;          // processed frames of the env (trs_preprocess with d_dst == NULL)
@@ -100,6 +98,13 @@ struct trs_env {
     hipEvent_t ev_order = nullptr;       // trs_stream_wait_external / trs_stream_signal_external
     trsim::Resident* res = nullptr;      // trsim_resident.hip: the resident worker (trs_set_step_mode), nullptr = never used
 };
+
+// ---- trsim_latency.hip (observation latency: the launch behind every step while one is set, and what the car is told) ----
+namespace trsim {
+int launch_obs(trs_env* e);                               // file the step that has just been counted in the ring and gather every env's delayed record
+int latency_restart(trs_env* e);                          // the history begins here (trs_set_latency, trs_load_track); the handle's stream is idle
+void obs_view(const trs_env* e, trs_obs_view* o);         // trs_get_observation's view (obs.on())
+}  // namespace trsim
 
 // ---- trsim_resident.hip (the resident worker: one step per trs_step call without a launch per step) ----
 namespace trsim {

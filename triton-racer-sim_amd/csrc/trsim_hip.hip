@@ -2,11 +2,11 @@
 // and render the envs, and the entry points of include/trsim.h that go with them.  What lives here:
 //   kernels      trs_step_kernel<DEPTH, DYN, HILLS, LENS, LIGHT> (camera on: ONE launch per env step on ONE stream; 768-thread workgroups own a contiguous
 //                range of envs and are wave-specialised — a physics team of one wave per env, a raster team of 8 waves; the variants that are built:
-//                trsim_plan.hpp), trs_physics_kernel (camera off: the same wave-per-env routine, K steps per launch), trs_obs_kernel (observation
-//                latency: files a step's telemetry, gathers every env's delayed record) and trs_locate_kernel (batched LocationTracker).  Their
+//                trsim_plan.hpp), trs_physics_kernel (camera off: the same wave-per-env routine, K steps per launch) and
+//                trs_locate_kernel (batched LocationTracker).  Their
 //                device-side pieces — the spec's arithmetic, the nearest-point search, the raster walk — are in trsim_device.hpp.
 //   host         the step dispatch (step_call: posted to the resident worker or launched), create / destroy, track loading, the lens camera, scene
-//                lighting, the palette upload with the static frame filter (trs_set_frame_filter), observation latency, state, fetch, sync, events,
+//                lighting, the palette upload with the static frame filter (trs_set_frame_filter), state, fetch, sync, events,
 //                scratch, and the internal accessors the other translation units reach the handle through (trsim_internal.hpp, trsim_env.hpp).
 // The rest of the ABI lives in translation units of its own:
 //   trsim_image.hip    trs_preprocess (trim, colour masks, dynamic brightness, Canny) and trs_normalize, kernels and host
@@ -14,6 +14,7 @@
 //   trsim_resident.hip the resident worker (trs_set_step_mode)            trsim_pilot.hip  the pilot network and trs_step_pilot
 //   trsim_jpeg.hip / trsim_jpeg_decode.hip  the tub image codec           trsim_comm.hip   the RCCL communicator
 //   trsim_jpeg_codec.hip  the camera codec (trs_jpeg_roundtrip, trs_set_camera_codec)
+//   trsim_latency.hip  observation latency (trs_set_latency): trs_obs_kernel, the launch behind every step while one is set, and the handle's ObsHistory
 //   trsim_filter.hpp   host only: the static colour filter of ONE colour, OpenCV's reciprocal tables, the check of a trs_pre_config
 //
 // Inside a multi-step call the raster team renders step t-1 while the physics team computes step t; the host opens the call with a physics-only launch
@@ -342,93 +343,6 @@ const std::array<StepKernel, kVariants> kStepKernels = step_kernel_table(std::ma
 
 #undef STAMP_STATS
 
-// ---- observation latency (include/trsim_spec.h, "observation latency"): one launch behind every step while a latency is set ----------------------
-// Workgroups [0, tel_blocks): one thread per env files the step's telemetry in ring slot `slot_now` and gathers the env's delayed record (zeros and
-// arrived = 0 until it exists).  The other workgroups (only when the envs' delays differ) move every env's delayed frame, then depth frame, from its ring
-// slot into the gathered frame: a copy, 16 B per lane, kObsVecs loads in flight per thread, the source slot uniform per workgroup, no LDS.  Source and
-// destination lie at the same offset from a 256-aligned base, so one split serves both: up to three 4-byte pieces in front of the 16-aligned middle
-// (an env's frame is a multiple of 4 bytes, of 16 only for some sizes) and up to three behind it.  Envs that have not arrived get zeros without a read.
-constexpr int kObsBlock = 256, kObsVecs = 4;
-struct ObsFrames { const uint8_t* ring; size_t stride; uint8_t* out; unsigned env_bytes; int blocks_per_env; };
-struct ObsParams {
-    const float* truth[5]; const int32_t* seg;                // x y z speed cte | seg_idx as the step left them
-    float* ring_tel;                                          // [slots][6][n]
-    const int32_t* ticks;                                     // L_e
-    float* out_tel; uint8_t* out_flag;                        // [6][n] | arrived[n], mode[n]
-    int n, slots, slot_now;
-    long long T;                                              // steps of the history so far, this one included
-    int tel_blocks;
-    ObsFrames img, dep;                                       // blocks_per_env == 0: nothing to gather
-};
-// workgroups per env frame: 16 KiB of the middle each, at least one (it also moves the 4-byte pieces)
-inline int obs_blocks_per_env(unsigned env_bytes) { const unsigned per = kObsBlock * kObsVecs; return (int)std::max(1u, (env_bytes / 16u + per - 1) / per); }
-
-__device__ __forceinline__ void obs_move_env(const ObsFrames& f, const ObsParams& p, int env, int blk, int tid)
-{
-    const int L = p.ticks[env];
-    const bool arrived = p.T - (long long)L >= 1;
-    int slot = p.slot_now - L;
-    if (slot < 0) slot += p.slots;
-    const size_t off = (size_t)env * f.env_bytes;
-    const unsigned head = min((16u - (unsigned)(off & 15u)) & 15u, f.env_bytes);
-    const unsigned vecs = (f.env_bytes - head) >> 4, tail = f.env_bytes - head - (vecs << 4);
-    const uint8_t* const src = f.ring + (size_t)slot * f.stride + off;
-    uint8_t* const dst = f.out + off;
-    const uint4* const s4 = reinterpret_cast<const uint4*>(src + head);
-    uint4* const d4 = reinterpret_cast<uint4*>(dst + head);
-    const unsigned v0 = (unsigned)blk * (kObsBlock * kObsVecs) + (unsigned)tid;
-    uint4 r[kObsVecs];
-#pragma unroll
-    for (int k = 0; k < kObsVecs; ++k) {
-        const unsigned i = v0 + k * kObsBlock;
-        r[k] = make_uint4(0u, 0u, 0u, 0u);
-        if (arrived && i < vecs) r[k] = s4[i];
-    }
-#pragma unroll
-    for (int k = 0; k < kObsVecs; ++k) {
-        const unsigned i = v0 + k * kObsBlock;
-        if (i < vecs) d4[i] = r[k];
-    }
-    if (blk == 0) {                                           // the 4-byte pieces: threads 0..2 in front, 64..66 behind
-        const unsigned t = (unsigned)tid;
-        if (t < head / 4u) reinterpret_cast<uint32_t*>(dst)[t] = arrived ? reinterpret_cast<const uint32_t*>(src)[t] : 0u;
-        const unsigned tb = head + (vecs << 4);
-        if (t >= 64u && t - 64u < tail / 4u)
-            reinterpret_cast<uint32_t*>(dst + tb)[t - 64u] = arrived ? reinterpret_cast<const uint32_t*>(src + tb)[t - 64u] : 0u;
-    }
-}
-
-__global__ __launch_bounds__(kObsBlock) void trs_obs_kernel(const ObsParams p)
-{
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    if (b < p.tel_blocks) {
-        const int i = b * kObsBlock + tid;
-        if (i >= p.n) return;
-        const size_t n = (size_t)p.n;
-        float* const now = p.ring_tel + (size_t)p.slot_now * 6 * n;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) now[k * n + i] = p.truth[k][i];
-        reinterpret_cast<int32_t*>(now)[5 * n + i] = p.seg[i];
-        const int L = p.ticks[i];
-        const bool arrived = p.T - (long long)L >= 1;
-        int slot = p.slot_now - L;
-        if (slot < 0) slot += p.slots;
-        const float* const then = p.ring_tel + (size_t)slot * 6 * n;      // (L == 0: what this thread has just stored)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) p.out_tel[k * n + i] = arrived ? (L == 0 ? p.truth[k][i] : then[k * n + i]) : 0.0f;
-        reinterpret_cast<int32_t*>(p.out_tel)[5 * n + i] = arrived ? (L == 0 ? p.seg[i] : reinterpret_cast<const int32_t*>(then)[5 * n + i]) : 0;
-        p.out_flag[i] = arrived ? 1 : 0;
-        p.out_flag[n + i] = arrived ? (uint8_t)TRS_MODE_AI : (uint8_t)TRS_MODE_HUMAN;
-        return;
-    }
-    b -= p.tel_blocks;
-    const int img_blocks = p.n * p.img.blocks_per_env;
-    if (b < img_blocks) { obs_move_env(p.img, p, b / p.img.blocks_per_env, b % p.img.blocks_per_env, tid); return; }
-    b -= img_blocks;
-    if (p.dep.blocks_per_env > 0 && b < p.n * p.dep.blocks_per_env) obs_move_env(p.dep, p, b / p.dep.blocks_per_env, b % p.dep.blocks_per_env, tid);
-}
-
 // Batched LocationTracker.__find_closest (components/track_data_process.py:89-101): one wave per query,
 // track staged in LDS once per workgroup, queries grid-strided.
 __global__ __launch_bounds__(kLocBlock) void trs_locate_kernel(const unsigned char* blob, int stage_bytes, const NearParams g,
@@ -459,19 +373,16 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 
 // the frame buffers written by the last step (nullptr without a camera / without cfg.depth)
-// (with an observation latency set: the ring slot of the last step — every step then renders into the ring, trsim_plan.hpp, ObsRing)
-long long history_steps(const trs_env* e) { return (long long)(e->step_count - e->lat_base); }   // T of "observation latency": steps since the history began
-uint8_t* ring_frame(const trs_env* e, int slot) { return e->ring_img.get() + (size_t)slot * e->ring_img_stride; }
-float* ring_depth(const trs_env* e, int slot) { return reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(e->ring_dep.get()) + (size_t)slot * e->ring_dep_stride); }
+// (with an observation latency set: the ring slot of the last step — every step then renders into the ring, trsim_latency.hpp, ObsHistory)
 const uint8_t* latest_frame(const trs_env* e)
 {
     if (!e->cfg.render) return nullptr;
-    return e->lat.on() ? ring_frame(e, e->lat.slot_of_step(history_steps(e))) : e->img[(e->step_count + 1) & 1].get();
+    return e->obs.on() ? e->obs.frame(e->obs.slot_of_last(e->step_count)) : e->img[(e->step_count + 1) & 1].get();
 }
 const float* latest_depth(const trs_env* e)
 {
     if (!(e->cfg.render && e->cfg.depth)) return nullptr;
-    return e->lat.on() ? ring_depth(e, e->lat.slot_of_step(history_steps(e))) : e->depth[(e->step_count + 1) & 1].get();
+    return e->obs.on() ? e->obs.depth(e->obs.slot_of_last(e->step_count)) : e->depth[(e->step_count + 1) & 1].get();
 }
 
 int grid_of(const trs_env* e) { return (e->n + e->pp.envs_per_wg - 1) / e->pp.envs_per_wg; }
@@ -505,12 +416,12 @@ int launch_step(trs_env* e, const Controls& c, int n_phys, int r_first, int r_la
     sp.ph.ctl_steer = c.steer; sp.ph.ctl_thr = c.thr; sp.ph.ctl_brk = c.brk; sp.ph.ctl_reset = c.reset; sp.ph.ctl_stride = c.stride;
     sp.ph.synth = c.synth; sp.ph.n_steps = n_phys; sp.ph.write_cam = 1; sp.ph.step_off = (uint32_t)step_base;
     sp.ra = e->rp;
-    const bool ring = e->lat.on();                                // an observation latency is set: the one frame of this launch goes to its ring slot
+    const bool ring = e->obs.on();                                // an observation latency is set: the one frame of this launch goes to its ring slot
     if (ring) {
         if (n_phys != 1 || r_first != 0 || r_last != 0) return fail(TRS_ERR_STATE, "internal error: a step with an observation latency set is one launch that renders its own frame");
-        const int slot = e->lat.slot_of_step((long long)(step_base - e->lat_base) + 1);
-        sp.img0 = sp.img1 = ring_frame(e, slot);
-        sp.dep0 = sp.dep1 = e->cfg.depth ? ring_depth(e, slot) : nullptr;
+        const int slot = e->obs.slot_of_last(step_base + 1);      // (the step this launch is: counted once it is on the stream)
+        sp.img0 = sp.img1 = e->obs.frame(slot);
+        sp.dep0 = sp.dep1 = e->cfg.depth ? e->obs.depth(slot) : nullptr;
     } else {
         sp.img0 = e->img[0].get(); sp.img1 = e->img[1].get();
         sp.dep0 = e->depth[0].get(); sp.dep1 = e->depth[1].get();
@@ -532,36 +443,6 @@ int launch_step(trs_env* e, const Controls& c, int n_phys, int r_first, int r_la
     return TRS_OK;
 }
 
-// The launch behind every step while an observation latency is set (trs_obs_kernel): the step that has just been counted is filed in the ring and every
-// env's delayed record gathered.  One delay for all envs: the frame view points into the ring (obs_view) and only the telemetry part runs.
-int launch_obs(trs_env* e)
-{
-    const long long T = history_steps(e);
-    const PParams& k = e->pp;
-    ObsParams p;
-    std::memset(&p, 0, sizeof p);
-    p.truth[0] = k.x; p.truth[1] = k.y; p.truth[2] = k.z; p.truth[3] = k.speed; p.truth[4] = k.cte; p.seg = k.seg_idx;
-    p.ring_tel = e->ring_tel.get(); p.ticks = e->lat_ticks.get();
-    const int b = trsim::ObsRing::gather_buf(T);
-    p.out_tel = e->obs_tel[b].get(); p.out_flag = e->obs_flag[b].get();
-    p.n = e->n; p.slots = e->lat.slots(); p.slot_now = e->lat.slot_of_step(T); p.T = T;
-    p.tel_blocks = (e->n + kObsBlock - 1) / kObsBlock;
-    int grid = p.tel_blocks;
-    if (e->cfg.render && !e->lat_uniform) {
-        p.img = ObsFrames{e->ring_img.get(), e->ring_img_stride, e->img[b].get(), (unsigned)((size_t)e->H * e->W * 3), 0};
-        p.img.blocks_per_env = obs_blocks_per_env(p.img.env_bytes);
-        grid += e->n * p.img.blocks_per_env;
-        if (e->cfg.depth) {
-            p.dep = ObsFrames{reinterpret_cast<const uint8_t*>(e->ring_dep.get()), e->ring_dep_stride, reinterpret_cast<uint8_t*>(e->depth[b].get()), (unsigned)((size_t)e->H * e->W * 4), 0};
-            p.dep.blocks_per_env = obs_blocks_per_env(p.dep.env_bytes);
-            grid += e->n * p.dep.blocks_per_env;
-        }
-    }
-    hipLaunchKernelGGL(trs_obs_kernel, dim3(grid), dim3(kObsBlock), 0, e->sP, p);
-    HIPCHK(hipGetLastError());
-    return TRS_OK;
-}
-
 // n env steps with a camera, K = steps per launch.  n == 1: one launch, the raster team waits for the physics team
 // through the LDS progress counters.  Otherwise a software pipeline over launches: a launch advances K physics steps
 // and renders the previous launch's last step plus its own steps 0..K-2; a raster-only launch closes the call, so on
@@ -570,11 +451,11 @@ int run_camera_steps(trs_env* e, const Controls& c, int n, int per_launch)
 {
     const uint64_t s0 = e->step_count;
     int rc = TRS_OK;
-    if (e->lat.on()) {                                       // an observation latency is set: every step is one launch into its ring slot, and trs_obs_kernel behind it
+    if (e->obs.on()) {                                       // an observation latency is set: every step is one launch into its ring slot, and trs_obs_kernel behind it
         for (int i = 0; i < n; ++i) {
             if ((rc = launch_step(e, c.after(i), 1, 0, 0, s0 + (uint64_t)i))) return rc;
             e->step_count += 1;
-            if ((rc = launch_obs(e))) return rc;
+            if ((rc = trsim::launch_obs(e))) return rc;
         }
         return TRS_OK;
     }
@@ -608,14 +489,14 @@ int launch_physics(trs_env* e, const Controls& c, int n_steps, uint64_t step_off
 // physics-only envs: K steps inside one launch of the physics kernel
 int run_physics_steps(trs_env* e, const Controls& c, int n, int per_launch)
 {
-    if (e->lat.on()) per_launch = 1;                         // an observation latency is set: trs_obs_kernel files every step's telemetry
+    if (e->obs.on()) per_launch = 1;                         // an observation latency is set: trs_obs_kernel files every step's telemetry
     for (int done = 0; done < n;) {
         const int now = std::min(per_launch, n - done);
         int rc = launch_physics(e, c.after(done), now, e->step_count);
         if (rc) return rc;
         e->step_count += (uint64_t)now;
         done += now;
-        if (e->lat.on() && (rc = launch_obs(e))) return rc;
+        if (e->obs.on() && (rc = trsim::launch_obs(e))) return rc;
     }
     return TRS_OK;
 }
@@ -648,44 +529,6 @@ int step_call(trs_env* e, Controls c, int n_steps, PerLaunch per, bool host = fa
         c = Controls{e->ctl_steer, e->ctl_thr, c.brk ? e->ctl_brk : nullptr, c.reset ? e->ctl_reset : nullptr, 0, 0};
     }
     return launch_steps(e, c, n_steps, per);
-}
-
-// The history of observations begins (trs_set_latency, trs_load_track): nothing has arrived, and every slot an observation can point into before a step
-// has written it holds the constructor's state.  The handle's stream is idle when this is called.
-int latency_restart(trs_env* e)
-{
-    e->lat_base = e->step_count;
-    if (e->ring_img.get()) HIPCHK(hipMemsetAsync(e->ring_img.get(), 0, e->ring_img.bytes(), e->sP));
-    if (e->ring_dep.get()) HIPCHK(hipMemsetAsync(e->ring_dep.get(), 0, e->ring_dep.bytes(), e->sP));
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipMemsetAsync(e->obs_tel[b].get(), 0, e->obs_tel[b].bytes(), e->sP));
-        HIPCHK(hipMemsetAsync(e->obs_flag[b].get(), 0, e->obs_flag[b].bytes(), e->sP));
-        if (!e->lat_uniform && e->img[b].get()) HIPCHK(hipMemsetAsync(e->img[b].get(), 0, e->img[b].bytes(), e->sP));        // the gathered frames
-        if (!e->lat_uniform && e->depth[b].get()) HIPCHK(hipMemsetAsync(e->depth[b].get(), 0, e->depth[b].bytes(), e->sP));
-    }
-    HIPCHK(hipStreamSynchronize(e->sP));
-    return TRS_OK;
-}
-
-// what the car is told after the last step (trs_get_observation): device pointers into the gathered telemetry and, for the frames, into the ring (one
-// delay for all envs: no frame byte is moved) or the gathered frames
-void obs_view(const trs_env* e, trs_obs_view* o)
-{
-    const long long T = history_steps(e);
-    const int b = trsim::ObsRing::gather_buf(T);
-    const size_t n = (size_t)e->n;
-    const float* t = e->obs_tel[b].get();
-    o->struct_size = (uint32_t)sizeof *o;
-    o->n_envs = e->n; o->img_h = e->H; o->img_w = e->W;
-    o->img = nullptr; o->depth = nullptr;
-    if (e->cfg.render) {
-        const int slot = e->lat.slot_of_obs(T, e->lat_all);
-        o->img = e->lat_uniform ? ring_frame(e, slot) : e->img[b].get();
-        if (e->cfg.depth) o->depth = e->lat_uniform ? ring_depth(e, slot) : e->depth[b].get();
-    }
-    o->pos_x = t; o->pos_y = t + n; o->pos_z = t + 2 * n; o->speed = t + 3 * n; o->cte = t + 4 * n;
-    o->seg_idx = reinterpret_cast<const int32_t*>(t + 5 * n);
-    o->arrived = e->obs_flag[b].get();
 }
 
 // The staged fetch behind trs_fetch_outputs and trs_fetch_observation: the items asked for (dst non-null) into the pinned staging by copies on stream
@@ -908,12 +751,12 @@ int upload_palette(trs_env* e)
     { int rq = sync_all(e); if (rq) return rq; }               // frames in flight keep the palette they were launched with (a resident worker leaves here and reports what it rendered)
     e->rp.uni_rows = (e->hilly || e->lens_on) ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame;
     e->uniform_ok.invalidate();                                //  the lens camera: on the pixel)  (steps skip uniform rows an earlier step wrote: not across a palette change)
-    HIPCHK(hipMemcpy(e->blob_r.get() + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
-    if (e->lens_on && e->lens_dev.get()) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
-        std::vector<uint32_t> lp(e->lens.palette);
+    HIPCHK(hipMemcpy(e->trk.blob_r.get() + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
+    if (e->lens_on && e->lens.dev.get()) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
+        std::vector<uint32_t> lp(e->lens.T.palette);
         if (e->has_frame_filter && !e->filter_dynamic)
             for (auto& c : lp) c = trsim::filter_colour(e->frame_filter, c);
-        HIPCHK(hipMemcpy(e->lens_dev.get() + e->lens_pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->lens.dev.get() + e->lens.pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
     }
     if (e->hilly || e->light_on) {
         // a track with elevation: the kernels blend a row's ground colours per env and frame and run the static filter on each (hill_filter_colour); the sky colours and
@@ -940,21 +783,19 @@ int upload_palette(trs_env* e)
             }
             hb.hsv_tab = e->hsv_tab.get();
         }
-        if (e->hilly) HIPCHK(hipMemcpy(e->blob_r.get() + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->blob_r.get() + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
+        if (e->hilly) HIPCHK(hipMemcpy(e->trk.blob_r.get() + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->trk.blob_r.get() + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
     }
     return TRS_OK;
 }
 
-struct LensStage {                                           // lens tables built for a map but not yet the handle's (lens_stage / lens_commit)
-    trsim::DevBuf<> dev; size_t pal_off = 0; trsim::LensTables T; bool block_written = false;
-};
+using trsim::LensStage; using trsim::TrackStage;           // what the handle holds as e->lens and e->trk (trsim_env.hpp)
 
 // The lens tables of a map for a camera (include/trsim_spec.h, "lens camera"), STAGED: host tables in binary64, the half-width planes and the palette
 // (static frame filter applied) in a device buffer of their own, and the LensBlock written into the raster image `blob_r` (the new track's, not yet committed,
-// in trs_load_track; the handle's own, with nothing in flight, in trs_set_camera).  Nothing of the handle changes here: lens_commit takes the result.
-// `lds_step` / `cell`: the step kernel's LDS image and the map cell of the track the tables are for.
-int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S)
+// in trs_load_track; the handle's own, with nothing in flight, in trs_set_camera).  Nothing of the handle changes here: the caller moves S into e->lens.
+// `lds_step` / `cell`: the step kernel's LDS image and the map cell of the track the tables are for.  *block_written (optional): the copy into blob_r was begun.
+int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S, bool* block_written = nullptr)
 {
     if (handle_fit(e, variant_bits(e->rp.depth != 0, false, false, true, false), lds_step) == trsim::LdsFit::no_launch)   // (a lens excludes the other variants)
         return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lens camera's palette (" + std::to_string(lds_step) + " B of tables at " +
@@ -992,32 +833,15 @@ int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cel
     lb.M = reinterpret_cast<const uint16_t*>(d + off_M); lb.pal = reinterpret_cast<const uint32_t*>(d + off_pal);
     lb.oc = (float)(cam.offset_x / cell);
     lb.wh = wh;
-    S.block_written = true;                                  // (from here on the slot in blob_r may hold a partial block when the copy fails)
+    if (block_written) *block_written = true;                // (from here on the slot in blob_r may hold a partial block when the copy fails)
     HIPCHK(hipMemcpy(blob_r + trsim::lens_block_offset(blob_bytes), &lb, sizeof lb, hipMemcpyHostToDevice));
     S.pal_off = off_pal;
     return TRS_OK;
 }
 
-// the staged lens tables become the handle's (the old ones are freed)
-void lens_commit(trs_env* e, LensStage& S)
-{
-    e->lens_dev = std::move(S.dev);
-    e->lens_pal_off = S.pal_off; e->lens = std::move(S.T);
-}
-
-// back to the pinhole camera: the lens tables are freed (nothing may be in flight)
-void lens_release(trs_env* e)
-{
-    (void)e->lens_dev.reset();
-    e->lens_pal_off = 0; e->lens = trsim::LensTables{};
-}
-// ---- trs_load_track, step by step.  Transactional: everything is built into copies (tables, layout, parameter blocks, device buffers) and committed only
-// after every check, allocation and copy has succeeded — a failed reload leaves the handle with the track it had (or with none), never with new offsets
-// against old blobs.
-struct TrackStage {                                          // device buffers of the new track; released unless moved into the handle
-    trsim::DevBuf<> blob_p, blob_r;
-    trsim::DevBuf<float> tangent, start_yaw, dpitch;
-};
+// ---- trs_load_track, step by step.  Transactional: everything is built into copies (tables, layout, parameter blocks, device buffers: a TrackStage, released
+// unless moved into the handle) and committed only after every check, allocation and copy has succeeded — a failed reload leaves the handle with the track it
+// had (or with none), never with new offsets against old blobs.
 
 int track_upload(const trsim::TrackTables& T, const std::vector<unsigned char>& hp, const std::vector<unsigned char>& hr, TrackStage& S)
 {
@@ -1078,14 +902,14 @@ int track_lens_stage(const trs_env* e, const trsim::TrackTables& T, const trsim:
 int track_commit(trs_env* e, trsim::TrackTables& T, const trsim::TrackLayout& L, TrackStage& S, const PParams& k, const RParams& r, LensStage& ls)
 {
     e->track_loaded = false;                                 // (until the state arrays are in place: track_start_poses)
-    e->blob_p = std::move(S.blob_p); e->blob_r = std::move(S.blob_r); e->tangent = std::move(S.tangent); e->start_yaw = std::move(S.start_yaw); e->dpitch = std::move(S.dpitch);   // (the old track's are released)
+    e->trk = std::move(S);                                   // (the old track's buffers are released)
     trsim::HillBlock& hb = e->hill_host;                     // (host copy: upload_palette fills in the frame filter and sends the block again)
     hb = trsim::HillBlock{};
-    hb.vpitch = e->dpitch.get(); hb.cam_pitch = e->cam_pitch.get(); hb.off_sky = L.r.off_sky; hb.far_rgb = T.far_rgb;
+    hb.vpitch = e->trk.dpitch.get(); hb.cam_pitch = e->cam_pitch.get(); hb.off_sky = L.r.off_sky; hb.far_rgb = T.far_rgb;
     hb.inv_f = T.inv_f; hb.hh = T.hh; hb.cam_h_f = T.cam_h_f; hb.z_far_f = T.z_far_f; hb.inv_zfar_f = T.inv_zfar_f; hb.fog_f = T.fog_f; hb.inv_cell_f = T.inv_cellf;
     e->hilly = T.hills;
-    HIPCHK(hipMemcpy(e->blob_r.get() + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
-    if (e->lens_on) lens_commit(e, ls);
+    HIPCHK(hipMemcpy(e->trk.blob_r.get() + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
+    if (e->lens_on) e->lens = std::move(ls);                 // (the old map's tables are released)
     e->tab = std::move(T);
     e->pp = k; e->rp = r;
     e->lds_r = L.r.lds_r; e->lds_p = L.p.lds_p; e->lds_step = L.lds_step; e->lds_off_phys = L.lds_off_phys; e->pts_bytes = L.p.pts_bytes;
@@ -1172,7 +996,7 @@ TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
     if ((rc = track_commit(e, T, L, S, k, r, ls))) return rc;
     if (e->expert) { trs_expert_free(e->expert); e->expert = nullptr; }   // the scripted expert's tables were the old track's (the handle is idle: sync_all above)
     if ((rc = track_start_poses(e))) return rc;
-    if (e->lat.on() && (rc = latency_restart(e))) return rc;  // the observations of the old track's steps do not reach the new one
+    if (e->obs.on() && (rc = trsim::latency_restart(e))) return rc;  // the observations of the old track's steps do not reach the new one
     return track_drop_misfits(e, clash);
 }
 
@@ -1285,15 +1109,15 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     case TRS_F_CTL_BRK: src = e->ctl_brk; need = n * 4; break;
     case TRS_F_STATS: src = e->stats.get(); need = 64 * sizeof(unsigned long long); break;
     case TRS_F_DEPTH: src = latest_depth(e); need = n * e->H * e->W * 4; break;
-    case TRS_F_ROWDEPTH: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_depth; need = (size_t)e->H * 4; } break;
+    case TRS_F_ROWDEPTH: if (e->track_loaded) { src = e->trk.blob_r.get() + e->rp.off_depth; need = (size_t)e->H * 4; } break;
     // the tables live on the host exactly as built; their LDS images on the device are re-laid-out (pitched map)
     case TRS_F_MAP: if (e->track_loaded) { src = e->tab.map.data(); need = e->tab.map.size() * 4; host_src = true; } break;
-    case TRS_F_ROWTAB: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_rowtab; need = (size_t)e->H * 8; } break;
-    case TRS_F_PALETTE: if (e->track_loaded) { src = e->blob_r.get() + e->rp.off_pal; need = (size_t)e->H * 16; } break;
-    case TRS_F_TANGENT: if (e->track_loaded) { src = e->tangent.get(); need = (size_t)k.np * 8; } break;
+    case TRS_F_ROWTAB: if (e->track_loaded) { src = e->trk.blob_r.get() + e->rp.off_rowtab; need = (size_t)e->H * 8; } break;
+    case TRS_F_PALETTE: if (e->track_loaded) { src = e->trk.blob_r.get() + e->rp.off_pal; need = (size_t)e->H * 16; } break;
+    case TRS_F_TANGENT: if (e->track_loaded) { src = e->trk.tangent.get(); need = (size_t)k.np * 8; } break;
     case TRS_F_DPITCH: if (e->track_loaded) { src = e->tab.dpitch.data(); need = e->tab.dpitch.size() * 4; host_src = true; } break;
-    case TRS_F_LENS_TABLE: if (e->track_loaded && e->lens_on) { src = e->lens.pix.data(); need = e->lens.pix.size() * 4; host_src = true; } break;
-    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->lens_on && e->lens_dev.get()) { src = e->lens_dev.get() + e->lens_pal_off; need = (size_t)trsim::kLensPalBytes; } break;
+    case TRS_F_LENS_TABLE: if (e->track_loaded && e->lens_on) { src = e->lens.T.pix.data(); need = e->lens.T.pix.size() * 4; host_src = true; } break;
+    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->lens_on && e->lens.dev.get()) { src = e->lens.dev.get() + e->lens.pal_off; need = (size_t)trsim::kLensPalBytes; } break;
     default: return fail(TRS_ERR_ARG, "unknown field");
     }
     if (!src) return fail(TRS_ERR_STATE, "field not available");
@@ -1339,90 +1163,18 @@ TRS_EXPORT int trs_fetch_outputs(trs_env* e, uint8_t* h_img, float* h_x, float* 
     return staged_fetch(e, items, cs);
 }
 
-// ---- observation latency (include/trsim_spec.h, "observation latency") ---------------------------------------------------------------
-TRS_EXPORT int trs_set_latency(trs_env* e, const int32_t* h_ticks, int max_ticks)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    if (h_ticks) {
-        if (max_ticks < 1 || max_ticks > trsim::kMaxLatencyTicks) return fail(TRS_ERR_ARG, "max_ticks must be in [1, " + std::to_string(trsim::kMaxLatencyTicks) + "]");
-        for (int i = 0; i < e->n; ++i)
-            if (h_ticks[i] < 0 || h_ticks[i] > max_ticks) return fail(TRS_ERR_ARG, "the latency of env " + std::to_string(i) + " is " + std::to_string(h_ticks[i]) + " ticks: outside [0, max_ticks = " + std::to_string(max_ticks) + "]");
-        if (trsim::resident_selected(e))
-            return fail(TRS_ERR_STATE, "resident mode is selected (trs_set_step_mode): the worker's frame hand-off is built on two buffers by step parity, an observation latency needs "
-                                       "steps by launches (TRS_STEP_LAUNCH first)");
-    }
-    HIPCHK(hipSetDevice(e->device));
-    int rc = sync_all(e);
-    if (rc) return rc;
-    if (!h_ticks) {                                          // off: back to the two frame buffers; the next step into each stores a whole frame
-        if (!e->lat.on()) return TRS_OK;
-        e->lat = trsim::ObsRing{};
-        e->lat_uniform = true; e->lat_all = 0; e->lat_base = 0; e->lat_host.clear();
-        (void)e->ring_img.reset(); (void)e->ring_dep.reset(); (void)e->ring_tel.reset(); (void)e->lat_ticks.reset();
-        for (int b = 0; b < 2; ++b) { (void)e->obs_tel[b].reset(); (void)e->obs_flag[b].reset(); }
-        e->ring_img_stride = e->ring_dep_stride = 0;
-        e->uniform_ok.invalidate();
-        return TRS_OK;
-    }
-    // everything the new setting needs is allocated first: a failure leaves the handle as it was
-    trsim::ObsRing ring; ring.max_ticks = max_ticks;
-    const size_t n = (size_t)e->n, slots = (size_t)ring.slots();
-    const size_t img_stride = e->cfg.render ? trsim::align_up(e->img_bytes, 256) : 0;
-    const size_t dep_stride = (e->cfg.render && e->cfg.depth) ? trsim::align_up(n * (size_t)e->H * e->W * 4, 256) : 0;
-    trsim::DevBuf<uint8_t> r_img, flag[2]; trsim::DevBuf<float> r_dep, r_tel, tel[2]; trsim::DevBuf<int32_t> ticks;
-    auto want = [&](auto& buf, size_t bytes) -> int {
-        if (!bytes) return TRS_OK;
-        const hipError_t rh = buf.alloc(bytes);
-        if (rh == hipSuccess) return TRS_OK;
-        (void)hipGetLastError();
-        return fail(rh == hipErrorOutOfMemory ? TRS_ERR_NOMEM : TRS_ERR_DEVICE,
-                    "trs_set_latency: the observation ring of " + std::to_string(slots) + " slots wanted " + std::to_string(bytes) + " bytes of device memory (" + hipGetErrorString(rh) + "); the handle is unchanged");
-    };
-    if ((rc = want(r_img, slots * img_stride)) || (rc = want(r_dep, slots * dep_stride)) || (rc = want(r_tel, slots * 6 * n * 4)) || (rc = want(ticks, n * 4))) return rc;
-    for (int b = 0; b < 2; ++b)
-        if ((rc = want(tel[b], 6 * n * 4)) || (rc = want(flag[b], 2 * n))) return rc;
-    HIPCHK(hipMemcpy(ticks.get(), h_ticks, n * 4, hipMemcpyHostToDevice));
-    e->h2d_bytes += n * 4;
-    // commit
-    e->ring_img = std::move(r_img); e->ring_dep = std::move(r_dep); e->ring_tel = std::move(r_tel); e->lat_ticks = std::move(ticks);
-    for (int b = 0; b < 2; ++b) { e->obs_tel[b] = std::move(tel[b]); e->obs_flag[b] = std::move(flag[b]); }
-    e->ring_img_stride = img_stride; e->ring_dep_stride = dep_stride;
-    e->lat = ring;
-    e->lat_host.assign(h_ticks, h_ticks + n);
-    e->lat_all = h_ticks[0];
-    e->lat_uniform = std::all_of(h_ticks, h_ticks + n, [&](int32_t t) { return t == h_ticks[0]; });
-    e->uniform_ok.invalidate();                              // img[] / depth[] become the gathered frames (or lie idle): no step has claimed them when the latency goes off again
-    return latency_restart(e);
-}
-
-TRS_EXPORT int trs_get_latency(trs_env* e, int32_t* h_ticks_out, int* max_ticks_out)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    if (max_ticks_out) *max_ticks_out = e->lat.max_ticks;
-    if (h_ticks_out)
-        for (int i = 0; i < e->n; ++i) h_ticks_out[i] = e->lat.on() ? e->lat_host[(size_t)i] : 0;
-    return TRS_OK;
-}
-
-TRS_EXPORT int trs_get_observation(trs_env* e, trs_obs_view* out)
-{
-    if (!e || !out) return fail(TRS_ERR_ARG, "null argument");
-    if (!e->lat.on()) return fail(TRS_ERR_STATE, "no observation latency is set (trs_set_latency): the observation is the state, trs_get_state");
-    obs_view(e, out);
-    return TRS_OK;
-}
-
+// trs_fetch_outputs as the cars are told it (observation latency: trsim_latency.hip has the rest; this one shares the staging above)
 TRS_EXPORT int trs_fetch_observation(trs_env* e, uint8_t* h_img, float* h_x, float* h_y, float* h_z, float* h_speed, float* h_cte,
                                      int32_t* h_seg, uint8_t* h_arrived)
 {
     if (!e) return fail(TRS_ERR_ARG, "null handle");
-    if (!e->lat.on()) return fail(TRS_ERR_STATE, "no observation latency is set (trs_set_latency): the observation is the state, trs_fetch_outputs");
+    if (!e->obs.on()) return fail(TRS_ERR_STATE, "no observation latency is set (trs_set_latency): the observation is the state, trs_fetch_outputs");
     if (h_img && !e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
     HIPCHK(hipSetDevice(e->device));
     const size_t n = (size_t)e->n, img_b = h_img ? e->img_bytes : 0;
     { int rs = fetch_staging(e, img_b); if (rs) return rs; }
     trs_obs_view v;
-    obs_view(e, &v);
+    trsim::obs_view(e, &v);
     const FetchItem items[trsim::kFetchItems] = {
         {h_img ? v.img : nullptr, h_img, img_b},
         {v.pos_x, h_x, n * 4}, {v.pos_y, h_y, n * 4}, {v.pos_z, h_z, n * 4}, {v.speed, h_speed, n * 4}, {v.cte, h_cte, n * 4},
@@ -1470,7 +1222,7 @@ TRS_EXPORT int trs_locate(trs_env* e, const double* h_xyz, int nq, int32_t* h_id
     const PParams& pk = e->pp;
     const NearParams near{pk.np, pk.off_py, pk.off_pz, pk.off_gstart, pk.off_gpts, pk.grid_nx, pk.grid_nz, pk.grid_x0, pk.grid_z0};
     hipLaunchKernelGGL(trs_locate_kernel, dim3(grid), dim3(kLocBlock), pk.blob_bytes, e->sP,
-                       (const unsigned char*)e->blob_p.get(), pk.blob_bytes, near, (const double*)e->loc_q.get(), nq, e->loc_out.get());
+                       (const unsigned char*)e->trk.blob_p.get(), pk.blob_bytes, near, (const double*)e->loc_q.get(), nq, e->loc_out.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_idx, e->loc_out.get(), (size_t)nq * 4, hipMemcpyDeviceToHost, e->sP));
     HIPCHK(hipStreamSynchronize(e->sP));
@@ -1549,20 +1301,21 @@ TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
     { int rq = sync_all(e); if (rq) return rq; }
     if (on && e->track_loaded) {
         LensStage ls;
-        int rc = lens_stage(e, nc, e->lds_step, e->tab.info.cell, e->blob_r.get(), e->rp.blob_bytes, ls);
+        bool block_written = false;
+        int rc = lens_stage(e, nc, e->lds_step, e->tab.info.cell, e->trk.blob_r.get(), e->rp.blob_bytes, ls, &block_written);
         if (rc) {
-            if (e->lens_on && ls.block_written) {            // the copy of the block failed: the handle's LensBlock may be half written, the old lens cannot stay
+            if (e->lens_on && block_written) {               // the copy of the block failed: the handle's LensBlock may be half written, the old lens cannot stay
                 const std::string why = g_err;
-                lens_release(e); e->lens_on = false; trs_default_camera(&e->camera);
+                e->lens = {}; e->lens_on = false; trs_default_camera(&e->camera);
                 (void)upload_palette(e);
                 return fail(rc, why + " (the lens camera that was set has been removed: the pinhole camera renders)");
             }
             return rc;                                       // (the handle is unchanged: no lens before, whose block slot is never read, or the old block untouched)
         }
-        lens_commit(e, ls);
+        e->lens = std::move(ls);                             // (the old tables are released: nothing is in flight)
     }
     e->camera = nc; e->lens_on = on;
-    if (!on) lens_release(e);                                // back to the pinhole: the tables are not kept
+    if (!on) e->lens = {};                                   // back to the pinhole: the tables are not kept
     return upload_palette(e);                                // uni_rows, the lens palette with the frame filter
 }
 
@@ -1713,12 +1466,12 @@ bool trs_internal_view(trs_env* e, TrsEnvView* v)
     v->ctl_steer = e->ctl_steer; v->ctl_thr = e->ctl_thr; v->ctl_brk = e->ctl_brk;
     v->step_count = e->step_count;
     v->stats = e->stats.get();
-    v->obs_on = e->lat.on();
+    v->obs_on = e->obs.on();
     v->codec_quality = e->codec_quality;
     v->obs_frame = nullptr; v->obs_speed = nullptr; v->obs_seg_idx = nullptr; v->obs_mode = nullptr;
-    if (v->obs_on && history_steps(e) > 0) {                 // what the car is told (trs_get_observation); before the first step of the history: nothing
+    if (v->obs_on && e->obs.steps(e->step_count) > 0) {                 // what the car is told (trs_get_observation); before the first step of the history: nothing
         trs_obs_view o;
-        obs_view(e, &o);
+        trsim::obs_view(e, &o);
         v->obs_frame = o.img; v->obs_speed = o.speed; v->obs_seg_idx = o.seg_idx; v->obs_mode = o.arrived + e->n;
     }
     return true;

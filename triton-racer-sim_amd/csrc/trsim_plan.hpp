@@ -1,7 +1,7 @@
 // trsim_plan.hpp — what a handle is allowed to become and how a call is cut up, as integer arithmetic and string selection a host compiler builds without HIP:
 // the kernel variants and which of them exist, the LDS the kernels keep behind a track's tables (the layouts the hosts size their launches by
 // and the kernels take their offsets from), the layout of a track's two LDS images, the refusals that follow from all three, the frame buffers that hold their
-// uniform rows (UniformRows), the observation ring (ObsRing), the controls of a step call and their slices (Controls) and a fetch's staging (fetch_layout).
+// uniform rows (UniformRows), the observation ring and its bytes (ObsRing, obs_bytes), the controls of a step call and their slices (Controls) and a fetch's staging (fetch_layout).
 // Functions that the kernels call as well carry TRS_HD (trsim_tables.hpp).  tests/plan_driver.cpp and tests/host_tables_driver.cpp run it on the CPU.
 #pragma once
 #include <cstddef>
@@ -186,7 +186,8 @@ inline LdsFit lds_fit(int lds_step, int epw, int H, int W, Variant v, bool resid
 // nor the step.  A frame buffer that a step has rendered into with the present palette holds them for every env, and later steps into that buffer
 // store only the rows that see the track; the consumer still finds a whole frame.  This is the one owner of "does buffer b hold them":
 //   launch_step, worker_launch ask skip_mask();  launch_step and the worker's exit (handle_exit) report what was rendered with rendered();
-//   upload_palette (track, frame filter, camera, lens, lighting), the buffers' allocation and a worker that ended by its abort bit call invalidate().
+//   upload_palette (track, frame filter, camera, lens, lighting), the buffers' allocation, trs_set_latency (on and off: the handle's ObsHistory, trsim_latency.hpp,
+//   takes the steps' frames meanwhile) and a worker that ended by its abort bit call invalidate().
 // DYN, LENS and LIGHT frames have no such rows (the filter follows each frame's mean, the lens decides per pixel, the palette is lit per env): a step
 // of those variants skips nothing and leaves its buffer without them.  HILLS has uni_rows == 0: skipping is a no-op there.
 constexpr bool variant_keeps_uniform(Variant v) { return !(v & (kVDyn | kVLens | kVLight)); }
@@ -239,6 +240,24 @@ struct ObsRing {
     // the gathered observation (telemetry always; frames when the envs' delays differ) is double buffered like the frames of a handle without latency
     static int gather_buf(long long T) { return (int)(T & 1ll); }
 };
+// The bytes behind a ring: a slot's frames (and depth frames) of all envs lie *_stride bytes apart, a multiple of 256; 0 without a camera / without depth.
+// trs_set_latency allocates by it, launch_obs takes an env's frame bytes from it; tests/latency_driver.cpp prints it.  All in size_t.
+struct ObsBytes {
+    size_t img_env, dep_env;                                 // one env's frame, depth frame
+    size_t img_stride, dep_stride, ring_img, ring_dep;       // a slot of every env's frames; all slots
+    size_t ring_tel, tel, flag, ticks;                       // [slots][6][n] | [6][n] | arrived[n], mode[n] | int32[n]
+};
+inline ObsBytes obs_bytes(const ObsRing& r, int n_envs, int H, int W, bool render, bool depth)
+{
+    const size_t n = (size_t)n_envs, slots = (size_t)r.slots(), px = (size_t)H * (size_t)W;
+    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    ObsBytes b{};
+    b.img_env = render ? px * 3 : 0; b.dep_env = render && depth ? px * 4 : 0;
+    b.img_stride = up256(n * b.img_env); b.dep_stride = up256(n * b.dep_env);
+    b.ring_img = slots * b.img_stride; b.ring_dep = slots * b.dep_stride;
+    b.tel = 6 * n * 4; b.ring_tel = slots * b.tel; b.flag = 2 * n; b.ticks = n * 4;
+    return b;
+}
 
 // ---- the controls of a step call, and the slice of them a launch or a post reads ----------------------------------------------------------
 // Control arrays (device pointers, or host arrays on their way to the device; brk and reset optional), or synth: the spec's generator and no arrays.

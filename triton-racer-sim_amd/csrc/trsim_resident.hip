@@ -1424,7 +1424,7 @@ TRS_EXPORT int trs_set_step_mode(trs_env* e, int mode, int idle_us)
         return rc;
     }
     if (!e->track_loaded) return trs_internal_fail(TRS_ERR_STATE, "no track loaded");
-    if (e->lat.on())                                         // (refused before anything of the handle changes)
+    if (e->obs.on())                                         // (refused before anything of the handle changes)
         return trs_internal_fail(TRS_ERR_STATE, "an observation latency is set (trs_set_latency): its ring of frames is filled by launches, one per step, and the resident worker hands "
                                                 "frames over by step parity (trs_set_latency(NULL) first)");
     if (!e->res) e->res = new (std::nothrow) Resident();
