@@ -20,6 +20,9 @@
 //
 // This file: the fused convolution kernels and the host side (the context, the launches, the C entry points).  Beside it:
 //   trsim_pilot_plan.hpp    host-only: which kernel serves which layer, the packing of the weights, the layout of the tail's fp32 blob
+//   trsim_pilot_mma.hpp     the fragment-level pieces every convolution kernel is made of: vector types, fp16 conversions and the packed ReLU, the epilogue
+//                           block (block_groups), the bias start (acc_from_bias), the ONE K loop over a weight ring (ring_k_loop), the 3x3 item and the
+//                           staging that the frame kernel and the chain share (conv3x3_item, stage_run)
 //   trsim_pilot_layers.hpp  the single-layer convolution kernels
 //   trsim_pilot_tail.hpp    everything behind conv7: dense1's kernel, the two tail kernels and the one KerasPilot.step rule they share
 //
@@ -43,10 +46,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;   // 8 binary16 values: one MFMA operand fragment per lane (round 3: binary16 instead of bfloat16 —
-                                                              // the same MFMA rate, 3 more mantissa bits: max |output - fp32| 5e-4 -> 4e-5, profiles/r03_pilot_precision.txt)
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
+#include "trsim_pilot_mma.hpp"      // the fragment-level pieces: vector types, fp16 conversions, the epilogue block, the bias start, the K loop, the shared 3x3 item and its staging
 
 using namespace trsim;   // (trsim_pilot_plan.hpp, trsim_mem.hpp)
 constexpr int kLayers = 11;               // conv1..7, dense1..3, output
@@ -60,99 +60,19 @@ struct ConvParams {
     const u4v* w;              // [G_pad][COUT_PAD] granules of 8 fp16
     const float* bias;         // [COUT_PAD]
     const int* goff;           // [G_pad] byte offset of granule g relative to the output pixel's input base
-    void* out;                 // fp16 NHWC [N][OH][OW][COUT]  or float when out_f32
+    void* out;                 // fp16 NHWC [N][OH][OW][COUT]
     int in_bytes;              // size of `in` (buffer-load bounds)
     int N, IH, IW, CIN, OH, OW, COUT, COUT_PAD, S;
     int G, G_pad, M;           // granules (even-padded), GEMM rows = N*OH*OW
-    int gchunk;                // granules per LDS stage (even)
-    int relu, out_f32, in_px_bytes;   // in_px_bytes: bytes per input pixel (CIN*2, conv1: 3)
-    int ksplit;                // > 1: blockIdx.y owns a slice of the granules and writes its partial sums to slab blockIdx.y of `out` (fp32 [ksplit][M][COUT], no ReLU)
+    int in_px_bytes;           // bytes per input pixel (CIN*2, conv1: 3)
     int nt_out;                // non-temporal activation stores (outputs far larger than L2; measured: conv1 86 -> 80 us, small layers lose)
     int KH, KW, run_pad, cg, span_nl;   // span kernel: kernel rows, granules per kernel row (padded), granules per pixel, load instructions per kernel row
     float oscale;              // the sums are multiplied by this power of two inside the bias FMA: 2^-8 for conv1 (kConv1Scale), 1 elsewhere
 };
 
 extern __shared__ __attribute__((aligned(16))) unsigned char psmem[];
-typedef const __attribute__((address_space(3))) u4v* lds_u4vp;   // an LDS address held as an integer: no "+ psmem" per access
-
-__device__ __forceinline__ unsigned short f2h(float f)
-{   // round to nearest even; beyond binary16's range: 65504 (the activations saturate, they never become infinite)
-    const _Float16 h = (_Float16)__builtin_fminf(__builtin_fmaxf(f, -65504.0f), 65504.0f);
-    return __builtin_bit_cast(unsigned short, h);
-}
-
-typedef __attribute__((ext_vector_type(2))) _Float16 h16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-__device__ __forceinline__ unsigned pack_h16x2(float lo, float hi)
-{   // round to nearest even, two values per dword: v_cvt_pk_f16_f32 on gfx950 (beyond 65504: +-infinity; the ReLU form below saturates)
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, h16x2));
-}
-
-// two uint8 values (already binary32, 0..255: exact in binary16 under any rounding) as a binary16 pair: v_cvt_pkrtz_f16_f32
-__device__ __forceinline__ unsigned u8pair_h16(float f0, float f1) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(f0, f1)); }
-
 constexpr float kConv1Scale = 1.0f / 256.0f;   // conv1's weights carry 256 / 255 (the pilot's / 255 of keras_pilot.py:49-50 x 2^8, so that small weights stay normal
                                                // binary16 numbers); its epilogues multiply the sum by 2^-8 inside the bias FMA: exact, no extra instruction
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-// ReLU on two packed binary16: the sign bit is the int16's, so max(., 0) as int16 zeroes the negatives (and -0).  One v_pk_max_i16
-// for two values instead of a v_max_f32 each in front of the conversion; round-to-nearest keeps the sign, so the bits are the same.
-// Non-negative binary16 values order like their int16 patterns, so min(., 0x7BFF) turns an overflowed +infinity (0x7C00) into 65504:
-// activations saturate instead of poisoning the next layer (one more v_pk_min_i16 per pair).
-// (The epilogues are vector-ALU work between short MFMA runs: conv1's tile of 5 MFMAs carried ~65 VALU instructions.)
-__device__ __forceinline__ unsigned relu_h16x2(unsigned packed)
-{
-    const s16x2 v = __builtin_bit_cast(s16x2, packed), z = {0, 0}, top = {0x7BFF, 0x7BFF};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_elementwise_max(v, z), top));
-}
-__device__ __forceinline__ uint2 relu_pack4(float v0, float v1, float v2, float v3)
-{
-    return make_uint2(relu_h16x2(pack_h16x2(v0, v1)), relu_h16x2(pack_h16x2(v2, v3)));
-}
-// ... without the saturation, for sums that provably stay inside binary16 (conv1 of the fused head: |bias| + sum |w| < 65504 is checked when the weights
-// are loaded — its inputs are pixels / 256 <= 1)
-__device__ __forceinline__ uint2 relu_pack4_bounded(float v0, float v1, float v2, float v3)
-{
-    const s16x2 z = {0, 0};
-    return make_uint2(__builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pack_h16x2(v0, v1)), z)),
-                      __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pack_h16x2(v2, v3)), z)));
-}
-
-// The epilogues' half exchange.  Register quad q of a 32x32 accumulator block holds channels 8q + 4h .. + 3 of pixel r in lane (r, h): the two lanes of a
-// pixel hold the two halves of every 8-channel group.  So that each lane stores whole 16-byte groups — lane h = 0 groups 0 and 1, lane h = 1 groups 2
-// and 3 — lane h = 0 needs its partner's half of groups 0, 1 and lane h = 1 its partner's half of groups 2, 3.  v_permlane32_swap_b32 a, b exchanges
-// the upper 32 lanes of a with the lower 32 lanes of b (gfx950): with a = a word of group q and b = the same word of group q + 2, BOTH halves of the wave
-// end with (own half, partner's half) of the group they store, in (a, b) order — one full-rate VALU instruction per word where rounds 2-3 used a select,
-// a ds_bpermute through the LDS crossbar and two more selects (round 4; the same bytes in the same places).
-__device__ __forceinline__ void half_swap(unsigned& a, unsigned& b)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-__device__ __forceinline__ void quad_groups(const uint2 (&w)[4], u4v& g0, u4v& g1)
-{
-    unsigned a0 = w[0].x, a1 = w[0].y, b0 = w[2].x, b1 = w[2].y, c0 = w[1].x, c1 = w[1].y, d0 = w[3].x, d1 = w[3].y;
-    half_swap(a0, b0); half_swap(a1, b1); half_swap(c0, d0); half_swap(c1, d1);
-    g0 = u4v{a0, a1, b0, b1};                               // h = 0: channels 0..7 of group 0; h = 1: channels 0..7 of group 2
-    g1 = u4v{c0, c1, d0, d1};                               // h = 0: group 1; h = 1: group 3
-}
-// The accumulators of a wave item start at the layer's bias (the MFMA's C operand adds it) instead of at zero with 16 v_add per 32 x 32 block in
-// the epilogue: register 4 q + j of block nb = channel cbase + nb*32 + 8 q + 4 h + j.  (fp32 sum order: bias first — the same fp16 activations up to
-// the last bit of the fp32 sum; tests/test_pilot.py compares against the PyTorch mirror.)
-template <int NT, int NB>
-__device__ __forceinline__ void acc_from_bias(f32x16 (&acc)[NT][NB], const float4* lbias, int cbase, int h)
-{
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 b = lbias[(cbase + nb * 32 + 8 * q + 4 * h) >> 2];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) { acc[nt][nb][4 * q] = b.x; acc[nt][nb][4 * q + 1] = b.y; acc[nt][nb][4 * q + 2] = b.z; acc[nt][nb][4 * q + 3] = b.w; }
-        }
-}
 
 #include "trsim_pilot_layers.hpp"   // the single-layer kernels: conv1 as its own layer, the span kernel (conv2 unfused, conv3 at 240x320), the quad-load fallback
 
@@ -164,12 +84,9 @@ struct FrameConvParams {
     int N, IH, IW, OH, OW, COUT, COUT_PAD, KH, KW;
     int F, cg, cgs;            // units (frames, or row bands of frames) per workgroup; granules per pixel (8 / 16) and log2 of it
     int bands, ohb, ihb;       // a frame whose activation does not fit LDS is cut into `bands` bands of ohb output rows = ohb + KH - 1 input rows
-    int relu;                  // (neighbouring bands re-stage KH - 1 rows); bands == 1: ohb = OH, ihb = IH
+                               // (neighbouring bands re-stage KH - 1 rows); bands == 1: ohb = OH, ihb = IH
     unsigned magic_uout, magic_ow, magic_bands;   // floor(p / d) = umulhi(p, ceil(2^32 / d)), exact for p < 2^32 / d: d = ohb x OW, OW, bands (an item's set-up without divisions)
 };
-// weight prefetch: a register ring of R k-steps (R x NB granules per lane), refilled slot by slot right behind the MFMAs that
-// consumed the slot: R x NT x NB x 32 MFMA clocks of lead time against an L2 round trip of 500-800 (R = 4: one tap at 64 input
-// channels, half a tap at 128; rings of 6 and 8 measured no faster).
 
 #ifndef TRS_FRAME_STAMPS
 #define TRS_FRAME_STAMPS 0   /* diagnostic build, never shipped: workgroup 7 prints the s_memtime ticks of its staging, work and waits */
@@ -180,7 +97,6 @@ struct FrameConvParams {
 #ifndef TRS_FRAME_ABLATE
 #define TRS_FRAME_ABLATE 0   /* timing-only diagnostic builds of trs_conv_frame_kernel, never shipped: 1 = no weight refills, 3 = no stores, 4 = no staging */
 #endif
-__device__ __forceinline__ int frame_swz(int pix, int cgs) { return cgs == 3 ? ((pix >> 1) & 7) : (pix & 15); }
 
 // Round 4: persistent and double-buffered, like trs_conv_frame5_kernel.  Until then a workgroup staged its F units, computed them and ended; its
 // ~150-200 registers allow one 8-wave workgroup per CU, so nothing ran beside the staging: a timing-only build without it (-DTRS_FRAME_ABLATE=4)
@@ -191,7 +107,6 @@ __device__ __forceinline__ int frame_swz(int pix, int cgs) { return cgs == 3 ? (
 template <int NT, int NB, int HALF, int R, int COMPUTE, int LOADERS>
 __global__ __launch_bounds__(64 * (COMPUTE + LOADERS), 1) void trs_conv_frame_kernel(const FrameConvParams p)
 {
-    static_assert(R >= 1 && R <= 9 * HALF, "ring depth in k-steps");
     constexpr int nwaves = COMPUTE + LOADERS, BLOCK = 64 * nwaves;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
@@ -199,46 +114,28 @@ __global__ __launch_bounds__(64 * (COMPUTE + LOADERS), 1) void trs_conv_frame_ke
     const int upix = p.ihb * p.IW, uout = p.ohb * p.OW;                     // input pixels staged / output pixel slots per unit
     const unsigned buf_bytes = (unsigned)((p.F * upix) << p.cgs) * 16u;     // one group of units in LDS
     const unsigned lds_base = (unsigned)(uintptr_t)psmem;
-    // staging of group g into the buffer at byte offset `off` by waves w0 .. w0 + nw - 1 (LDS-DMA: 1 KB per wave instruction; the XOR swizzle goes
-    // on the SOURCE address, the LDS side stays lane-linear)
-    // A unit's input rows are whole rows of one frame: ONE contiguous run of upix x cg granules in memory (the rows a last band asks for below its
-    // frame are never read by a valid pixel: their addresses are clamped into the activation).  So a slot's source is base + slot ^ swizzle — a shift,
-    // a mask and an XOR per DMA instruction (the general (unit, row, column) split of rounds 2-3 cost ~80 instructions per 1 KB: four loader waves
-    // then needed as long for a group as eight compute waves for its MFMAs).
+    // staging of group g into the buffer at byte offset `off` by waves w0 .. w0 + nw - 1.  A unit's input rows are whole rows of one frame: ONE
+    // contiguous run of upix x cg granules in memory (stage_run; what a last band asks for below its frame is clamped into the activation)
     const int last_gran = (int)(((size_t)p.N * p.IH * p.IW) << p.cgs) - 1;
     auto stage = [&](int g, unsigned off, int w0, int nw) {
         const int u0 = g * p.F, nu = min(p.F, n_units - u0);
         const int total = upix << p.cgs;                                    // granule slots of one unit
-        for (int ul = 0; ul < nu; ++ul) {
+        for (int ul = 0; ul < nu && TRS_FRAME_ABLATE != 4; ++ul) {
             const int u = u0 + ul, f = u / p.bands, band = u - f * p.bands;  // (wave-uniform: scalar unit)
             const int base = ((f * p.IH + band * p.ohb) * p.IW) << p.cgs;     // first granule of the unit in the activation (< 2^31: in_bytes fits an int)
-            const unsigned dst = lds_base + off + (unsigned)(ul * total) * 16u;
-            for (int s0 = (wave - w0) * 64; s0 < total; s0 += nw * 64) {
-                const int sl = s0 + lane;
-                if (sl < total && TRS_FRAME_ABLATE != 4) {
-                    const int pix = ul * upix + (sl >> p.cgs), q = sl & (p.cg - 1);   // (the swizzle follows the pixel's index in the GROUP, as the readers compute it)
-                    const int src = min(base + (sl - q) + (q ^ frame_swz(pix, p.cgs)), last_gran);
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.in + src),
-                                                     (__attribute__((address_space(3))) void*)(uintptr_t)(dst + s0 * 16), 16, 0, 0);
-                }
-            }
+            stage_run(p.in + base, total, last_gran - base, ul * upix, p.cgs, lds_base + off + (unsigned)(ul * total) * 16u, wave - w0, nw, lane);
         }
     };
     float* lb = reinterpret_cast<float*>(psmem + 2 * (size_t)buf_bytes);    // the bias behind the two buffers
     const float4* lbias = reinterpret_cast<const float4*>(lb);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4v*>(p.w), 0, 9 * p.cg * p.COUT_PAD * 16, 0x00020000);   // [9 taps x cg granules][COUT_PAD] granules
-#if TRS_FRAME_STAMPS
-    long long fs_t0 = (long long)__builtin_amdgcn_s_memtime(), fs_st = 0, fs_k = 0, fs_w = 0;
-#endif
+    PhaseStamps<TRS_FRAME_STAMPS != 0> stamps;
     int g = blockIdx.x;
     if (g < n_groups) stage(g, 0u, 0, nwaves);                              // the first group: all waves
     for (int i = tid; i < p.COUT_PAD; i += BLOCK) lb[i] = p.bias[i];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#if TRS_FRAME_STAMPS
-    { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); fs_st += t_ - fs_t0; fs_t0 = t_; }
-#endif
-    constexpr int ksteps = 9 * HALF;                                        // k-steps (16 input channels of one tap each) of a 3x3 kernel
+    stamps.mark(stamps.kStaging);
     const int n_cgrp = p.COUT_PAD / (NB * 32);
     for (int it = 0; g < n_groups; ++it, g += gridDim.x) {
         const unsigned cur = (it & 1) ? buf_bytes : 0u;
@@ -266,81 +163,17 @@ __global__ __launch_bounds__(64 * (COMPUTE + LOADERS), 1) void trs_conv_frame_ke
                     lbase[nt] = (ul * p.ihb + oyl) * p.IW + ox;
                     obase[nt] = (m < m_wg && oy < p.OH) ? ((long long)f * p.OH + oy) * p.OW + ox : -1;
                 }
-                // weight granule (2 k + h, cout cbase + nb*32 + r) by buffer load: one lane offset + a scalar per (k-step, block)
-                // (the k-step part of the offset is ONE scalar that runs with the loads — a constant per (k-step, block), 144 of them at 128 input channels, was hoisted
-                // out of the item loop and spilled to vector-register lanes: a v_readlane + wait states in front of every load; the block is the immediate offset)
-                const int wvoff = (h * p.COUT_PAD + cbase + r) * 16;
-                int wso = 0;
-                auto wload = [&](int nb) { return __builtin_bit_cast(u4v, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff + nb * 512, wso, 0)); };
-                auto wnext = [&]() { wso += 2 * p.COUT_PAD * 16; asm volatile("" : "+s"(wso)); };   // the loads are issued in k order
-                u4v ring[R][NB];
-#pragma unroll
-                for (int d = 0; d < R; ++d) {
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) ring[d][nb] = wload(nb);
-                    wnext();
-                }
+                // a 3x3 item of the group's image (conv3x3_item: the weights by buffer load through a register ring, the K loop one basic block)
                 f32x16 acc[NT][NB];
-                acc_from_bias<NT, NB>(acc, lbias, cbase, h);
-                // All ksteps k-steps are unrolled (3 x 12 or 9 x 8 ...): ONE basic block, no back edge — the compiler counts the weight
-                // loads in flight exactly (vmcnt(N) per k-step) instead of draining the queue at a loop head or behind a branch.  The pixel
-                // fragments are software-pipelined by hand: k-step k + 1's ds_reads are issued BEFORE k-step k's MFMAs (the sched_barrier
-                // that keeps "MFMAs of k, then the refill of k's ring slot" in place would otherwise also pin each k-step's LDS reads
-                // right in front of its own MFMAs: one LDS latency per 4 MFMAs).
-                // (Round 4: a second sched_barrier between those reads and the MFMAs — hipcc sinks the reads behind three of a k-step's four MFMAs — was
-                // measured in the frame kernels, the chain and frame5: all slower, chain 46.2 -> 48.4 us, conv7 96.1 -> 100.5: the address arithmetic then runs
-                // as a burst with no MFMA beside it.)
-                // the XOR-swizzled LDS address of a tap's fragment once per tap: granule 2 j + h of k-step j, and (2 j + h) ^ swizzle = (h ^ swizzle) ^ 2 j — the
-                // tap's byte address ^ 32 j, one v_xor per k-step and tile (a K loop is priced by its non-MFMA instructions: profiles/r04_mfma_issue.txt)
-                constexpr int CGS = HALF == 4 ? 3 : 4;                      // (8 granules per input pixel <-> 4 k-steps per tap, 16 <-> 8)
-                unsigned tapb[NT];
-                auto pixels = [&](int k, h16x8 (&x)[NT]) {                  // k is a compile-time constant after unrolling
-                    const int tap = k / HALF, j = k % HALF;
-                    const int tap_off = (tap / 3) * p.IW + tap % 3;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        if (j == 0) {
-                            const int pix = lbase[nt] + tap_off;
-                            tapb[nt] = lds_base + cur + (unsigned)(((pix << CGS) + (h ^ frame_swz(pix, CGS))) << 4);
-                        }
-                        x[nt] = __builtin_bit_cast(h16x8, *(lds_u4vp)(uintptr_t)(tapb[nt] ^ (unsigned)(32 * j)));
-                    }
-                };
-                h16x8 xa[NT], xb[NT];
-                pixels(0, xa);
-#pragma unroll
-                for (int k = 0; k < ksteps; ++k) {
-                    const int d = k % R;
-                    h16x8 (&xc)[NT] = (k & 1) ? xb : xa;
-                    h16x8 (&xn)[NT] = (k & 1) ? xa : xb;
-                    if (k + 1 < ksteps) pixels(k + 1, xn);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc[nt][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ring[d][nb]), xc[nt], acc[nt][nb], 0, 0, 0);
-                    if (k + R < ksteps && TRS_FRAME_ABLATE != 1) {          // (compile-time) refill the slot with the k-step R ahead
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) ring[d][nb] = wload(nb);
-                        wnext();
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // epilogue: register quad q of block nb = channels cbase + nb*32 + 8q + 4h .. +3 of pixel r.  The two lanes of a pixel
-                // (h = 0, 1) hold the two halves of every 8-channel group: they swap half of their quads (v_permlane32_swap_b32) so that
-                // each lane ends with whole 16-byte groups — lane h = 0 stores groups q = 0, 1, lane h = 1 groups 2, 3
+                conv3x3_item<HALF, R, TRS_FRAME_ABLATE == 1 ? 1 : 0>(acc, lds_base + cur, p.IW, rw, p.COUT_PAD, lbias, cbase, lbase, r, h);
+                // epilogue (block_groups): lane h = 0 stores channel groups 0, 1 of a block, lane h = 1 groups 2, 3 — whole 16-byte groups
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     unsigned short* o = p.out + (size_t)(obase[nt] < 0 ? 0 : obase[nt]) * p.COUT + cbase;
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
-                        uint2 w[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            float v0 = acc[nt][nb][4 * q], v1 = acc[nt][nb][4 * q + 1], v2 = acc[nt][nb][4 * q + 2], v3 = acc[nt][nb][4 * q + 3];
-                            w[q] = p.relu ? relu_pack4(v0, v1, v2, v3) : make_uint2(pack_h16x2(v0, v1), pack_h16x2(v2, v3));
-                        }
                         u4v g0, g1;
-                        quad_groups(w, g0, g1);                           // lane h = 0: channel groups 0, 1 of this block, lane h = 1: groups 2, 3 (whole 16-byte groups)
+                        block_groups(acc[nt][nb], g0, g1);
 #if TRS_FRAME_ABLATE == 3
                         asm volatile("" :: "v"(g0), "v"(g1)); (void)o;
 #else
@@ -353,18 +186,14 @@ __global__ __launch_bounds__(64 * (COMPUTE + LOADERS), 1) void trs_conv_frame_ke
                 }
             }
         }
-#if TRS_FRAME_STAMPS
-        { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); fs_k += t_ - fs_t0; fs_t0 = t_; }
-#endif
+        stamps.mark(stamps.kWork);
         __syncthreads();                                                    // the next group is in LDS, this one has been read
-#if TRS_FRAME_STAMPS
-        { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); fs_w += t_ - fs_t0; fs_t0 = t_; }
-#endif
+        stamps.mark(stamps.kWait);
     }
 #if TRS_FRAME_STAMPS
     if (blockIdx.x == 7 && lane == 0 && (wave == 0 || wave == COMPUTE - 1 || wave == COMPUTE))
         printf("frame kernel (cg %d, COUT %d, bands %d, F %d, %d groups), workgroup 7, wave %d [ticks]: first staging %lld | groups: work %lld, wait at the barrier %lld\n",
-               p.cg, p.COUT, p.bands, p.F, n_groups, wave, fs_st, fs_k, fs_w);
+               p.cg, p.COUT, p.bands, p.F, n_groups, wave, stamps.ticks[0], stamps.ticks[1], stamps.ticks[2]);
 #endif
 }
 
@@ -375,7 +204,7 @@ __global__ __launch_bounds__(64 * (COMPUTE + LOADERS), 1) void trs_conv_frame_ke
 //   region A (76.8 KB): conv4's output -> (conv5 reads) -> conv6's output -> (conv7 reads)
 //   region B (53.2 KB): conv4's input, two frames at a time -> conv5's output -> (conv6 reads)
 // conv4 runs in two passes of two frames (its input is the largest tensor of the chain: 26 KB per frame); conv7 stores to global.
-// A layer is trs_conv_frame_kernel's item loop unchanged (2 x 32 pixels x 2 x 32 channels per wave, weights straight from L2
+// A layer is trs_conv_frame_kernel's item (conv3x3_item: 2 x 32 pixels x 2 x 32 channels per wave, weights straight from L2
 // through a register ring, the K loop one basic block); its epilogue writes the next layer's LDS image — 16-byte granules in the
 // same XOR-swizzled slots the staging DMA would have produced.  Layers are separated by a workgroup barrier only.
 struct ChainLayer {
@@ -406,7 +235,6 @@ __device__ __forceinline__ void chain_layer(const ChainLayer& L, const u4v* lin,
     const int uout = L.OH * L.OW, m_wg = nu * uout;
     const int n_tiles = (m_wg + NT * 32 - 1) / (NT * 32), n_cgrp = L.COUT / (NB * 32);
     const float4* lbias = reinterpret_cast<const float4*>(lbias_f);
-    constexpr int ksteps = 9 * HALF, CGS = HALF == 4 ? 3 : 4;              // (8 granules per input pixel <-> 4 k-steps per tap, 16 <-> 8: the host builds the layers so)
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4v*>(L.w), 0, 9 * L.cg * L.COUT * 16, 0x00020000);   // [9 taps x cg granules][COUT] granules
     const unsigned lin_b = (unsigned)(uintptr_t)lin;                                // LDS byte address of the layer's input image
     for (int item = wave; item < n_tiles * n_cgrp; item += nwaves) {
@@ -420,80 +248,14 @@ __device__ __forceinline__ void chain_layer(const ChainLayer& L, const u4v* lin,
             lbase[nt] = (ul * L.IH + oy) * L.IW + ox;
             mo[nt] = m < m_wg ? m : -1;
         }
-        // (round 4, profiles/r04_mfma_issue.txt: inside a wave every vector-ALU instruction between two MFMAs ADDS ~6 ticks to the MFMA's 32, and two waves
-        // per SIMD hide only part of each other's — a K loop is priced by its non-MFMA instructions per MFMA.  So: weights by buffer load (one lane offset
-        // + a scalar per k-step instead of a 64-bit running pointer), and the XOR-swizzled LDS address of a tap's fragment computed ONCE per tap: the
-        // granule of k-step j of the tap is 2 j + h, and (2 j + h) ^ swizzle = (h ^ swizzle) ^ 2 j — the tap's byte address ^ 32 j, one v_xor per k-step.)
-        const int wvoff = (h * L.COUT + cbase + r) * 16;
-        int wso = 0;                                                        // the k-step part of the offset: one scalar that runs with the loads (issued in k order)
-        auto wload = [&](int nb) { return __builtin_bit_cast(u4v, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff + nb * 512, wso, 0)); };
-        auto wnext = [&]() { wso += 2 * L.COUT * 16; asm volatile("" : "+s"(wso)); };
-        u4v ring[R][NB];
-#pragma unroll
-        for (int d = 0; d < R; ++d) {
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) ring[d][nb] = wload(nb);
-            wnext();
-        }
         f32x16 acc[NT][NB];
-        acc_from_bias<NT, NB>(acc, lbias, cbase, h);
-        [[maybe_unused]] h16x8 xkeep[NT];
-        unsigned tapb[NT];                                                  // LDS byte address of this lane's granule h ^ swizzle of the current tap's pixel
-        auto pixels = [&](int k, h16x8 (&x)[NT]) {
-            const int tap = k / HALF, j = k % HALF;
-            const int tap_off = (tap / 3) * L.IW + tap % 3;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                if (j == 0) {
-                    const int pix = lbase[nt] + tap_off;
-                    tapb[nt] = lin_b + (unsigned)(((pix << CGS) + (h ^ frame_swz(pix, CGS))) << 4);
-                }
-                const h16x8 v = __builtin_bit_cast(h16x8, *(lds_u4vp)(uintptr_t)(tapb[nt] ^ (unsigned)(32 * j)));
-#if TRS_CHAIN_ABLATE == 2
-                if (k == 0) xkeep[nt] = v;
-                x[nt] = xkeep[nt];
-#else
-                x[nt] = v;
-#endif
-            }
-        };
-        h16x8 xa[NT], xb[NT];
-        pixels(0, xa);
-#pragma unroll
-        for (int k = 0; k < ksteps; ++k) {
-            const int d = k % R;
-            h16x8 (&xc)[NT] = (k & 1) ? xb : xa;
-            h16x8 (&xn)[NT] = (k & 1) ? xa : xb;
-            if (k + 1 < ksteps) pixels(k + 1, xn);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-#if TRS_CHAIN_ABLATE == 3
-                    asm volatile("" :: "v"(ring[d][nb]), "v"(xc[nt]));
-#else
-                    acc[nt][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ring[d][nb]), xc[nt], acc[nt][nb], 0, 0, 0);
-#endif
-                }
-            if (k + R < ksteps && TRS_CHAIN_ABLATE != 1) {
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) ring[d][nb] = wload(nb);
-                wnext();
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        conv3x3_item<HALF, R, TRS_CHAIN_ABLATE>(acc, lin_b, L.IW, rw, L.COUT, lbias, cbase, lbase, r, h);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                uint2 w[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float v0 = acc[nt][nb][4 * q], v1 = acc[nt][nb][4 * q + 1], v2 = acc[nt][nb][4 * q + 2], v3 = acc[nt][nb][4 * q + 3];
-                    w[q] = relu_pack4(v0, v1, v2, v3);
-                }
                 u4v g0, g1;
-                quad_groups(w, g0, g1);                                   // lane h = 0: channel groups 0, 1 of this block, lane h = 1: groups 2, 3 (whole 16-byte groups)
+                block_groups(acc[nt][nb], g0, g1);                          // lane h = 0: channel groups 0, 1 of this block, lane h = 1: groups 2, 3 (whole 16-byte groups)
                 if (mo[nt] >= 0) {
                     if (lout) {                                               // the next layer's image: pixel slot, granule ^ swizzle
                         const int po = out_pix0 + mo[nt], q0 = (cbase + nb * 32 + 16 * h) >> 3, sw = frame_swz(po, cgs_out);
@@ -534,15 +296,7 @@ __global__ __launch_bounds__(BLOCK, 2) void trs_conv_chain_kernel(const ChainPar
     const unsigned lds0 = (unsigned)(uintptr_t)psmem;
     auto stage = [&](const ChainLayer& L, int fa, int cnt, unsigned lds_byte) {   // frames fa .. fa + cnt - 1 of L's input, whole and contiguous
         const int upix = L.IH * L.IW, total = (cnt * upix) << L.cgs;
-        const u4v* src = p.in + ((size_t)fa * upix << L.cgs);
-        for (int s0 = wave * 64; s0 < total; s0 += nwaves * 64) {
-            const int sl = s0 + lane;
-            if (sl < total) {
-                const int pix = sl >> L.cgs, q = sl & (L.cg - 1);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (pix << L.cgs) + (q ^ frame_swz(pix, L.cgs))),
-                                                 (__attribute__((address_space(3))) void*)(uintptr_t)(lds_byte + s0 * 16), 16, 0, 0);
-            }
-        }
+        stage_run(p.in + ((size_t)fa * upix << L.cgs), total, total - 1, 0, L.cgs, lds_byte, wave, nwaves, lane);
     };
     int li = 0;
     const u4v* cur = A;
@@ -622,7 +376,7 @@ struct Frame5Params {
 template <int NT, int NB, int R, int BLOCK, int COMPUTE>
 __global__ __launch_bounds__(BLOCK, 1) void trs_conv_frame5_kernel(const Frame5Params p)
 {
-    constexpr int KW = 5, ksteps = 50, kCompute = COMPUTE;                  // waves 0 .. COMPUTE - 1 compute, the others stage
+    constexpr int KW = 5, kCompute = COMPUTE;                               // waves 0 .. COMPUTE - 1 compute, the others stage
     const int COUT = p.COUT;                                                // 64 (the host checks)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int nwaves = BLOCK / 64;
@@ -632,9 +386,7 @@ __global__ __launch_bounds__(BLOCK, 1) void trs_conv_frame5_kernel(const Frame5P
     const int upix = p.ihb * p.IW;                                          // input pixels staged per unit
     const unsigned buf_bytes = (unsigned)upix * 64u;                        // one unit in LDS (a multiple of 64)
     const unsigned lds_base = (unsigned)(uintptr_t)psmem;
-#if TRS_F5_STAMPS
-    long long f5_t0 = (long long)__builtin_amdgcn_s_memtime(), f5_st = 0, f5_k = 0, f5_w = 0;
-#endif
+    PhaseStamps<TRS_F5_STAMPS != 0> stamps;
     // staging of unit u into the buffer at byte offset `off` by waves w0 .. w0 + nw - 1: slot sl = 4 * lpix + q holds granule q ^ ((lpix >> 2) & 3) of the
     // pixel that lives in slot lpix
     auto stage = [&](int u, unsigned off, int w0, int nw) {
@@ -662,9 +414,7 @@ __global__ __launch_bounds__(BLOCK, 1) void trs_conv_frame5_kernel(const Frame5P
     for (int i = tid; i < COUT; i += BLOCK) lb[i] = p.bias[i];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#if TRS_F5_STAMPS
-    { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); f5_st += t_ - f5_t0; f5_t0 = t_; }
-#endif
+    stamps.mark(stamps.kStaging);
     for (int it = 0; u < n_units; ++it, u += gridDim.x) {
         const unsigned cur = (it & 1) ? buf_bytes : 0u;
         if (wave >= kCompute) {                                             // loaders: the next unit into the other buffer
@@ -686,22 +436,11 @@ __global__ __launch_bounds__(BLOCK, 1) void trs_conv_frame5_kernel(const Frame5P
                     lbase[nt] = 2 * oyl * p.IW + ox;                        // slot of input pixel (2 oyl, 2 ox) of the unit: even plane, position ox
                     mo[nt] = m < m_wg ? ((long long)f * p.OH + oy) * p.OW + ox : -1;
                 }
-                // weight granule (2 k + h, cout nb*32 + r) by buffer load: ONE lane offset + a scalar per (k-step, block) — a 64-bit address per load
-                // (or a running pointer per ring slot) cost this kernel ~80 registers, and with them a ring deep enough to cover an L2 hit
-                u4v ring[R][NB];
-                int wso = cbase * 16;                                       // the k-step part of the offset: one scalar that runs with the loads (see trs_conv_frame_kernel)
+                // weight granule (2 k + h, cout cbase + nb*32 + r) of k-step k for ring_k_loop
+                int wso = cbase * 16;                                       // the k-step part of the offset: one scalar that runs with the loads
                 auto wload = [&](int nb) { return __builtin_bit_cast(u4v, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff + nb * 512, wso, 0)); };
                 auto wnext = [&]() { wso += 2 * COUT * 16; asm volatile("" : "+s"(wso)); };
-#pragma unroll
-                for (int d = 0; d < R; ++d) {
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) ring[d][nb] = wload(nb);
-                    wnext();
-                }
-                f32x16 acc[NT][NB];
-                acc_from_bias<NT, NB>(acc, lbias, cbase, h);
-                // (the swizzled address once per tap, ^ 32 for its second k-step: see trs_conv_frame_kernel)
-                unsigned tapb[NT];
+                unsigned tapb[NT];                                          // (the swizzled address once per tap, ^ 32 for its second k-step)
                 auto pixels = [&](int k, h16x8 (&x)[NT]) {                  // k is a compile-time constant after unrolling
                     const int tap = k / 2, j = k % 2;
                     const int kh = tap / KW, kw = tap % KW;
@@ -715,38 +454,15 @@ __global__ __launch_bounds__(BLOCK, 1) void trs_conv_frame5_kernel(const Frame5P
                         x[nt] = __builtin_bit_cast(h16x8, *(lds_u4vp)(uintptr_t)(tapb[nt] ^ (unsigned)(32 * j)));
                     }
                 };
-                h16x8 xa[NT], xb[NT];
-                pixels(0, xa);
-#pragma unroll
-                for (int k = 0; k < ksteps; ++k) {
-                    const int d = k % R;
-                    h16x8 (&xc)[NT] = (k & 1) ? xb : xa;
-                    h16x8 (&xn)[NT] = (k & 1) ? xa : xb;
-                    if (k + 1 < ksteps) pixels(k + 1, xn);
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc[nt][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ring[d][nb]), xc[nt], acc[nt][nb], 0, 0, 0);
-                    if (k + R < ksteps) {
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) ring[d][nb] = wload(nb);
-                        wnext();
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                f32x16 acc[NT][NB];
+                ring_k_loop<50, R, 0>(acc, lbias, cbase, h, wload, wnext, pixels);   // 25 taps x 2 halves of the 32 input channels
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     unsigned short* o = p.out + (size_t)(mo[nt] < 0 ? 0 : mo[nt]) * COUT + cbase;
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
-                        uint2 w[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            float v0 = acc[nt][nb][4 * q], v1 = acc[nt][nb][4 * q + 1], v2 = acc[nt][nb][4 * q + 2], v3 = acc[nt][nb][4 * q + 3];
-                            w[q] = relu_pack4(v0, v1, v2, v3);
-                        }
                         u4v g0, g1;
-                        quad_groups(w, g0, g1);                           // lane h = 0: channel groups 0, 1 of this block, lane h = 1: groups 2, 3 (whole 16-byte groups)
+                        block_groups(acc[nt][nb], g0, g1);                // lane h = 0: channel groups 0, 1 of this block, lane h = 1: groups 2, 3 (whole 16-byte groups)
                         if (mo[nt] >= 0) {
                             *reinterpret_cast<u4v*>(o + nb * 32 + 16 * h) = g0;
                             *reinterpret_cast<u4v*>(o + nb * 32 + 16 * h + 8) = g1;
@@ -755,17 +471,13 @@ __global__ __launch_bounds__(BLOCK, 1) void trs_conv_frame5_kernel(const Frame5P
                 }
             }
         }
-#if TRS_F5_STAMPS
-        { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); f5_k += t_ - f5_t0; f5_t0 = t_; }
-#endif
+        stamps.mark(stamps.kWork);
         __syncthreads();                                                    // the next unit is in LDS, this one has been read
-#if TRS_F5_STAMPS
-        { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); f5_w += t_ - f5_t0; f5_t0 = t_; }
-#endif
+        stamps.mark(stamps.kWait);
     }
 #if TRS_F5_STAMPS
     if (blockIdx.x == 7 && lane == 0 && (wave == 0 || wave == kCompute - 1 || wave == kCompute))
-        printf("frame5, workgroup 7, wave %d [clocks]: first staging %lld | units: work %lld, wait at the barrier %lld\n", wave, f5_st, f5_k, f5_w);
+        printf("frame5, workgroup 7, wave %d [clocks]: first staging %lld | units: work %lld, wait at the barrier %lld\n", wave, stamps.ticks[0], stamps.ticks[1], stamps.ticks[2]);
 #endif
 }
 
@@ -804,7 +516,7 @@ struct Fuse12Params {
     const uint8_t* frames; int frames_bytes;
     const u4v* w1; const float* b1;                        // conv1: [12][32] granules, [32]
     const u4v* w2;                                          // conv2: [80][32] granules (kernel rows padded 15 -> 16)
-    ConvParams c2;                                          // conv2's output side (out, COUT, relu, nt_out, bias)
+    ConvParams c2;                                          // conv2's output side (out, M, bias)
     int N, IH, IW, OH1, OW1, OH2, OW2, R2, bands;
     int off_w2, off_b, off_tile;                            // LDS layout
     int tile_bytes;
@@ -1133,14 +845,8 @@ __global__ __launch_bounds__(1024) void trs_conv12_band_kernel(const Fuse12Param
                         moff[j] = px < npx2 ? ((m0 + __mul24(yl2, q.OW2) + x2) * 32 + 16 * h) * 2 : -1;   // this lane's 32 bytes of the pixel in conv2's activation
                     }
                 }
-                // the accumulators start at conv2's bias: register 4 qd + j = cout 8 qd + 4 h + j (read once per item, under the first fragments' latency)
-                f32x16 acc2[kC2Nt];
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    const float4 b = lb2[2 * qd + h];
-#pragma unroll
-                    for (int j = 0; j < kC2Nt; ++j) { acc2[j][4 * qd] = b.x; acc2[j][4 * qd + 1] = b.y; acc2[j][4 * qd + 2] = b.z; acc2[j][4 * qd + 3] = b.w; }
-                }
+                f32x16 acc2[kC2Nt][1];
+                acc_from_bias(acc2, lb2, 0, h);                             // the accumulators start at conv2's bias (read once per item, under the first fragments' latency)
                 u4v fw[kC2Depth], fx[kC2Depth][kC2Nt];
                 unsigned arow[kC2Nt], cur[kC2Nt];
                 auto fetch = [&](int k, int d) {                             // k-step k = kernel row k / 8, window slots 2 (k % 8) + h (compile-time k after unrolling)
@@ -1171,7 +877,7 @@ __global__ __launch_bounds__(1024) void trs_conv12_band_kernel(const Fuse12Param
 #if TRS_C2_ABLATE == 2
                         asm volatile("" :: "v"(w), "v"(fx[d][j]));
 #else
-                        acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, __builtin_bit_cast(h16x8, fx[d][j]), acc2[j], 0, 0, 0);
+                        acc2[j][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, __builtin_bit_cast(h16x8, fx[d][j]), acc2[j][0], 0, 0, 0);
 #endif
                     }
                     if (k + kC2Depth < 40 && TRS_C2_ABLATE != 1) fetch(k + kC2Depth, d);
@@ -1179,7 +885,7 @@ __global__ __launch_bounds__(1024) void trs_conv12_band_kernel(const Fuse12Param
                 }
                 BAND_STAMP(2);                                               // conv2: set-up and K loop (loaders: unpack + request)
 #if TRS_C2_ABLATE == 3
-                asm volatile("" :: "v"(acc2[0]));
+                asm volatile("" :: "v"(acc2[0][0]));
                 continue;
 #endif
                 // Epilogue without LDS: ReLU + fp16, the two lanes of a pixel swap half of their channel quads (v_permlane32_swap_b32) and each stores
@@ -1188,13 +894,8 @@ __global__ __launch_bounds__(1024) void trs_conv12_band_kernel(const Fuse12Param
                 // of phase 2 per tile, profiles/r04_pilot_head_stamps.txt.)
 #pragma unroll
                 for (int j = 0; j < kC2Nt; ++j) {
-                    uint2 w[4];
-#pragma unroll
-                    for (int qd = 0; qd < 4; ++qd)
-                        w[qd] = q.c2.relu ? relu_pack4(acc2[j][4 * qd], acc2[j][4 * qd + 1], acc2[j][4 * qd + 2], acc2[j][4 * qd + 3])
-                                          : make_uint2(pack_h16x2(acc2[j][4 * qd], acc2[j][4 * qd + 1]), pack_h16x2(acc2[j][4 * qd + 2], acc2[j][4 * qd + 3]));
                     u4v g0, g1;
-                    quad_groups(w, g0, g1);
+                    block_groups(acc2[j][0], g0, g1);
                     if (moff[j] >= 0) {
                         __builtin_amdgcn_raw_buffer_store_b128(g0, rout2, moff[j], 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b128(g1, rout2, moff[j] + 16, 0, 0);
@@ -1277,7 +978,7 @@ int launch_conv(const ConvLayer& cl, const void* in, size_t in_bytes, void* out,
         FrameConvParams q{};
         q.in = static_cast<const u4v*>(in); q.w = cl.w.get(); q.bias = cl.bias.get(); q.out = static_cast<unsigned short*>(out);
         q.N = n_img; q.IH = l.IH; q.IW = l.IW; q.OH = l.OH; q.OW = l.OW; q.COUT = l.COUT; q.COUT_PAD = l.COUT_PAD; q.KH = l.KH; q.KW = l.KW;
-        q.F = l.frame_f; q.cg = l.CIN / 8; q.cgs = q.cg == 8 ? 3 : 4; q.relu = l.relu;
+        q.F = l.frame_f; q.cg = l.CIN / 8; q.cgs = q.cg == 8 ? 3 : 4;
         q.bands = l.frame_bands; q.ohb = l.frame_ohb; q.ihb = l.frame_ohb + l.KH - 1;
         q.magic_uout = pilot_magic(q.ohb * q.OW); q.magic_ow = pilot_magic(q.OW); q.magic_bands = q.bands == 1 ? 0u : pilot_magic(q.bands);
         // (wave items of 2 x 32 pixels x 64 channels: the plan cuts the frames into bands so that a group has about 8 of them — items of 3 tiles need
@@ -1290,7 +991,7 @@ int launch_conv(const ConvLayer& cl, const void* in, size_t in_bytes, void* out,
     p.in_bytes = (int)in_bytes;
     p.N = n_img; p.IH = l.IH; p.IW = l.IW; p.CIN = l.CIN; p.OH = l.OH; p.OW = l.OW; p.COUT = l.COUT; p.COUT_PAD = l.COUT_PAD; p.S = l.S;
     p.G = l.G; p.G_pad = l.G_pad; p.M = n_img * l.OH * l.OW;
-    p.relu = l.relu; p.out_f32 = l.out_f32; p.in_px_bytes = l.u8in ? 3 : l.CIN * 2;
+    p.in_px_bytes = l.u8in ? 3 : l.CIN * 2;
     p.oscale = l.u8in ? kConv1Scale : 1.0f;
     // outputs above 128 MB leave non-temporally (measured: conv1's 222 MB -> conv1 88 -> 81 us, conv2 85 -> 82; at 48 MB conv3 loses)
     p.nt_out = (!l.out_f32 && (size_t)p.M * l.COUT * 2 > ((size_t)128 << 20)) ? 1 : 0;
@@ -1555,7 +1256,7 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
     if (P.head.on) {
         const PilotLayer& l0 = P.L[0]; const PilotLayer& l1 = P.L[1]; const PilotHead& h = P.head; Fuse12Params& q = c->fuse;
         q.w1 = c->L[0].w.get(); q.b1 = c->L[0].bias.get(); q.w2 = c->w2_parity.get();
-        q.c2.bias = c->L[1].bias.get(); q.c2.COUT = l1.COUT; q.c2.COUT_PAD = l1.COUT_PAD; q.c2.relu = 1; q.c2.oscale = 1.0f;
+        q.c2.bias = c->L[1].bias.get(); q.c2.COUT = l1.COUT; q.c2.COUT_PAD = l1.COUT_PAD; q.c2.oscale = 1.0f;
         q.IH = l0.IH; q.IW = l0.IW; q.OH1 = l0.OH; q.OW1 = l0.OW; q.OH2 = l1.OH; q.OW2 = l1.OW;
         q.R2 = h.R2; q.bands = h.bands; q.wsplit = h.wsplit; q.w2p = h.w2p; q.cpr = h.cpr; q.magic_full = h.magic_full; q.magic_cpr = h.magic_cpr;
         q.off_w2 = h.off_w2; q.off_b = h.off_b; q.off_tile = h.off_tile; q.tile_bytes = h.tile_bytes; q.off_band = h.off_band; q.band_bytes = h.band_bytes;

@@ -50,7 +50,7 @@ __device__ __forceinline__ void store_tile_at(u4v* stage, const f32x16 (&acc)[NB
                     const float4 b = lbias[nb * 8 + 2 * q + h];
                     const float os = p.oscale;
                     float v0 = __builtin_fmaf(acc[nb][4 * q], os, b.x), v1 = __builtin_fmaf(acc[nb][4 * q + 1], os, b.y), v2 = __builtin_fmaf(acc[nb][4 * q + 2], os, b.z), v3 = __builtin_fmaf(acc[nb][4 * q + 3], os, b.w);
-                    st2[(pr * CR + ((4 * nb + q) ^ f)) * 2 + h] = p.relu ? relu_pack4(v0, v1, v2, v3) : make_uint2(pack_h16x2(v0, v1), pack_h16x2(v2, v3));
+                    st2[(pr * CR + ((4 * nb + q) ^ f)) * 2 + h] = relu_pack4(v0, v1, v2, v3);
                 }
             }
         }
@@ -84,75 +84,22 @@ __device__ __forceinline__ void store_tile(u4v* stage, const f32x16 (&acc)[NB], 
     store_tile_at<NB>(stage, acc, lbias, p, tile * 32, p.M, cbase, lane);
 }
 
-// The epilogue without LDS (round 4; the fused head's conv2 and the frame kernels use the same): the accumulators STARTED at the bias (acc_bias),
-// so what is left is ReLU + fp16, the exchange of channel quads between the two lanes of a pixel (v_permlane32_swap_b32) and two 16-byte
-// stores per lane and 32-channel block (couts cbase + nb*32 + 16 h .. + 15).  The staged epilogue above costs a tile six dependent LDS round
-// trips (four broadcast bias reads + the transpose): 1.4 k clocks in the head (profiles/r04_pilot_head_stamps.txt).  For whole 32-channel blocks
-// (COUT % 32 == 0) and oscale == 1 only: the span kernel's layers.
-template <int NB>
-__device__ __forceinline__ void acc_bias(f32x16 (&acc)[NB], const float4* lbias, int h)
-{
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 b = lbias[nb * 8 + 2 * q + h];
-            acc[nb][4 * q] = b.x; acc[nb][4 * q + 1] = b.y; acc[nb][4 * q + 2] = b.z; acc[nb][4 * q + 3] = b.w;
-        }
-}
+// The epilogue without LDS (round 4; the fused head's conv2 and the frame kernels use the same): the accumulators STARTED at the bias (acc_from_bias),
+// so what is left is block_groups and two 16-byte stores per lane and 32-channel block (couts cbase + nb*32 + 16 h .. + 15).  For whole 32-channel
+// blocks (COUT % 32 == 0) and oscale == 1 only: the span kernel's layers.
 template <int NB>
 __device__ __forceinline__ void store_tile_direct(const f32x16 (&acc)[NB], const ConvParams& p, const __amdgpu_buffer_rsrc_t rout, int tile, int cbase, int lane)
 {
     const int r = lane & 31, h = lane >> 5, m = tile * 32 + r;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        uint2 w[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            w[q] = p.relu ? relu_pack4(acc[nb][4 * q], acc[nb][4 * q + 1], acc[nb][4 * q + 2], acc[nb][4 * q + 3])
-                          : make_uint2(pack_h16x2(acc[nb][4 * q], acc[nb][4 * q + 1]), pack_h16x2(acc[nb][4 * q + 2], acc[nb][4 * q + 3]));
         u4v g0, g1;
-        quad_groups(w, g0, g1);
+        block_groups(acc[nb], g0, g1);
         if (m < p.M) {
             const int off = (m * p.COUT + cbase + nb * 32 + 16 * h) * 2;
             if (p.nt_out == 1) { __builtin_amdgcn_raw_buffer_store_b128(g0, rout, off, 0, 2); __builtin_amdgcn_raw_buffer_store_b128(g1, rout, off + 16, 0, 2); }          // nt
             else if (p.nt_out == 2) { __builtin_amdgcn_raw_buffer_store_b128(g0, rout, off, 0, 17); __builtin_amdgcn_raw_buffer_store_b128(g1, rout, off + 16, 0, 17); }   // sc0 sc1
             else { __builtin_amdgcn_raw_buffer_store_b128(g0, rout, off, 0, 0); __builtin_amdgcn_raw_buffer_store_b128(g1, rout, off + 16, 0, 0); }
-        }
-    }
-}
-
-// The same epilogue for a tile whose 32 pixels are a run of a ROW-SEGMENT grid (the fused head's band cut in width: rows of w2
-// pixels inside an output activation of OW pixels per row): pixel pg of the band part = (row pg / w2, column pg % w2), output
-// pixel m_row0 + row * OW + column.  32 output channels (NB = 1).
-__device__ __forceinline__ void store_tile_rows(u4v* stage, const f32x16 (&acc)[1], const float4* lbias, const ConvParams& p, int pg0, int npx, int w2, float inv_w2,
-                                                int m_row0, int OW, int lane)
-{
-    constexpr int CR = 4;
-    const int r = lane & 31, h = lane >> 5;
-    uint2* st2 = reinterpret_cast<uint2*>(stage);
-    {
-        const int f = (r >> 1) & 3;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 b = lbias[2 * q + h];
-            const float os = p.oscale;
-            float v0 = __builtin_fmaf(acc[0][4 * q], os, b.x), v1 = __builtin_fmaf(acc[0][4 * q + 1], os, b.y), v2 = __builtin_fmaf(acc[0][4 * q + 2], os, b.z), v3 = __builtin_fmaf(acc[0][4 * q + 3], os, b.w);
-            st2[(r * CR + (q ^ f)) * 2 + h] = p.relu ? relu_pack4(v0, v1, v2, v3) : make_uint2(pack_h16x2(v0, v1), pack_h16x2(v2, v3));
-        }
-    }
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<unsigned char*>(p.out), 0, p.M * p.COUT * 2, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int g = i * 64 + lane, pix = g >> 2, c = g & 3;                // 32 pixels x 4 chunks of 8 channels
-        const int pg = pg0 + pix;
-        if (pg < npx) {
-            int row = (int)(((float)pg + 0.5f) * inv_w2), col = pg - row * w2;
-            if (col < 0) { --row; col += w2; } else if (col >= w2) { ++row; col -= w2; }
-            const int f = (pix >> 1) & 3;
-            const u4v v = stage[pix * CR + (c ^ f)];
-            const int off = ((m_row0 + row * OW + col) * p.COUT + 8 * c) * 2;
-            __builtin_amdgcn_raw_buffer_store_b128(v, rout, off, 0, 0);
         }
     }
 }
@@ -455,8 +402,8 @@ __global__ __launch_bounds__(768) void trs_conv_span_kernel(const ConvParams p)
     setup(tile, roff_cur);
     request(0);
     while (true) {
-        f32x16 acc[NB];
-        acc_bias<NB>(acc, lbias, h);                                        // the sums start at the bias
+        f32x16 acc[1][NB];
+        acc_from_bias(acc, lbias, 0, h);                                    // the sums start at the bias
         const int next = tile + stride;                                     // uniform
         for (int kh = 0; kh < p.KH; ++kh) {
 #pragma unroll
@@ -470,11 +417,11 @@ __global__ __launch_bounds__(768) void trs_conv_span_kernel(const ConvParams p)
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     const h16x8 w = __builtin_bit_cast(h16x8, lw[(gbase + t + h) * NBW + nb * 32 + r]);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, acc[nb], 0, 0, 0);
+                    acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, acc[0][nb], 0, 0, 0);
                 }
             }
         }
-        store_tile_direct<NB>(acc, p, rout, tile, cbase, lane);
+        store_tile_direct<NB>(acc[0], p, rout, tile, cbase, lane);
         if (next >= ntiles) break;
         tile = next; roff_cur = roff_next;
     }
