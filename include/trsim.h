@@ -612,6 +612,46 @@ int trs_set_expert(trs_env* env, const trs_expert_config* cfg_or_null, const flo
 int trs_expert_act(trs_env* env, float* d_steering, float* d_throttle, float* d_breaking, int n);
 int trs_step_expert(trs_env* env, int n_steps, const trs_expert_capture* cap_or_null, int* n_captured_or_null);
 
+/* ---- pilot in the loop with the expert's labels: dataset aggregation, DAgger (include/trsim_spec.h, "pilot in the loop with the expert's labels";
+ *      HIP library only) ----
+ * trs_step_expert records states the EXPERT reaches; a trained pilot drifts into states the expert never visits.  Here the loaded pilot drives, or a keyed
+ * mixture of pilot and expert, and the expert's answer to every visited state is the recorded label.  Needs trs_set_expert, trs_pilot_load and a camera.
+ *   trs_step_dagger: the closed loop in the shape of trs_step_pilot, for n_steps ticks.  Per tick: the pilot acts exactly as in trs_step_pilot (same frame
+ *     source: the latest frame, the delayed one under trs_set_latency, the codec's under trs_set_camera_codec; same speed, segment and mode mask; (0, 0, 0)
+ *     before a frame exists) into the handle's control arrays; ONE launch of trs_dagger_kernel computes the expert's pure label on the truth (the
+ *     disturbance state w does NOT move and sigma is ignored — unlike trs_step_expert), draws the gate, overwrites the control arrays (TRS_F_CTL_*) with the
+ *     applied controls, writes the record row when a capture is due and updates the stats; one env step by launch follows.  The driver's tick counter k
+ *     (zeroed by trs_set_expert, shared with trs_step_expert) advances by one per tick.
+ *     Gate: per global env id and per block of `hold` ticks of k, the expert drives iff u < beta, u from SplitMix64 of cfg.seed (beta 0: never, beta 1:
+ *     always); identical in every shard.  Applied steering: the label where the expert drives, else the pilot's.  expert_speed = 1: throttle and brake are
+ *     ALWAYS the labels ("applied as labelled", as in trs_step_expert), so the speed label of the speed_ctl and full_house loaders — the car's own speed /
+ *     20 — shows the expert's speed behaviour.  expert_speed = 0: throttle and brake follow the gate like the steering; those two loaders' speed label is
+ *     then the PILOT's own speed and is not a correction.
+ *   Capture: trs_expert_capture and its rule as for trs_step_expert (every, skip, capacity per call, no byte of an uncaptured slot written, no capture of
+ *     frames while no frame exists).  Row: (steering label, throttle label, breaking label, applied steering, speed, cte, 'loc/segment', done) —
+ *     TRS_LABEL_EXPERT is the correction, TRS_LABEL_APPLIED what the car was given.  Frame: the frame the pilot was FED this tick (the codec's output under a
+ *     camera codec; the delayed frame under a latency, zeros for cars nothing has reached yet; otherwise the latest frame) — unlike trs_step_expert, which
+ *     captures the rendered truth.  It is the pair the pilot is judged on, and the pair the reference's tubs hold under sim_latency.
+ *   trs_dagger_stats: float[n_envs][6] per env, updated on every tick of trs_step_dagger whether captured or not: ticks, ticks the expert drove, sum |cte|,
+ *     max |cte|, sum |pilot steering - label|, ticks with done set (cte and done of the state the label was computed on; binary32 additions in tick order,
+ *     counts exact below 2^24 ticks).  h_out (may be NULL): filled, the call then synchronises; *d_out (may be NULL): the handle-owned device array;
+ *     reset != 0: zeroed behind the read.  trs_set_expert zeroes them too; resets of a car touch neither k nor the stats.
+ *   Refusals (a refused call leaves the handle, k and the stats unchanged).  TRS_ERR_STATE: no expert set, no pilot loaded, no camera; trs_dagger_stats
+ *     without an expert.  TRS_ERR_ARG: either struct_size, beta not finite or outside [0, 1], hold < 1, expert_speed not 0 or 1, n_steps < 1, the pilot
+ *     config's model type not matching the weights (as trs_step_pilot), the capture refusals of trs_step_expert.
+ *   Resident mode as for trs_step_pilot and trs_step_expert: a resident worker is asked to leave. */
+typedef struct trs_dagger_config {
+    uint32_t struct_size;
+    float    beta;                   /* 0.5: the probability that the expert holds the wheel in a block of `hold` ticks */
+    int32_t  hold;                   /* 1: ticks per block of the gate */
+    int32_t  expert_speed;           /* 1: throttle and brake always as labelled; 0: they follow the gate */
+    uint64_t seed;                   /* 0: the seed of the gate */
+} trs_dagger_config;
+void trs_default_dagger_config(trs_dagger_config* cfg);
+int trs_step_dagger(trs_env* env, const trs_pilot_config* pilot_cfg, const trs_dagger_config* cfg, int n_steps, const trs_expert_capture* cap_or_null,
+                    int* n_captured_or_null);
+int trs_dagger_stats(trs_env* env, float* h_out_or_null, const float** d_out_or_null, int reset);
+
 /* ---- training minibatches: DataLoader.load's split, shuffle and batch on the device (include/trsim_spec.h, "training minibatches"; HIP library only) ----
  * The reference's trainer turns every record into float32 on the host, splits 0.8 / 0.2, shuffles and batches with drop_remainder
  * (components/keras_train.py:33-69).  Here the set stays where trs_step_expert's capture left it — d_frames uint8[n_records][H][W][3] of the handle's

@@ -274,7 +274,38 @@
  *   tests/test_expert_cpu.py restates the paragraph in numpy and drives the CPU oracle with it; tests/test_expert_gpu.py compares the kernel with that
  *   restatement bit for bit; csrc/trsim_expert.hpp holds the host side (config checks, track_yaw, which ticks are captured).
  *
- * ---- training minibatches (trs_sample_batch, trs_loader_order; DataLoader.load of the reference, components/keras_train.py:33-69; HIP library only)
+ * ---- pilot in the loop with the expert's labels (trs_step_dagger, trs_dagger_stats; dataset aggregation, DAgger; HIP library only) ----------------------
+ *   The pilot drives, or a keyed mixture of pilot and expert; the expert's answer to every visited state is the label.  Binary32, one rounding per
+ *   operation, no contraction, so a numpy float32 restatement is bit-exact.  Per tick, with the driver's counter k of "scripted expert" (zeroed by
+ *   trs_set_expert, shared with trs_step_expert), per env e with global id gid = env_id_base + e:
+ *     (ps, pt, pb) = the controls trs_step_pilot would apply this tick: KerasPilot.step on the same frame source (the latest frame; the delayed one under
+ *                    "observation latency"; codec(that frame) under "camera codec"), the same speed, segment and mode mask; (0, 0, 0) before a frame exists
+ *     (es, et, eb) = the LABEL of "scripted expert" on the truth.  The disturbance state w does NOT move and sigma is ignored (trs_step_expert moves it).
+ *     z  = SplitMix64 as in the expert's disturbance, seed = trs_dagger_config.seed, key = (gid << 32) | (k / hold)      (integer division, hold >= 1)
+ *     u  = (float)(z >> 40) * 2^-24
+ *     expert drives = (u < beta)           beta = 0: never;  beta = 1: always, since u <= 1 - 2^-24.  Constant over blocks of `hold` ticks, keyed by
+ *                                          the global env id: identical in every shard
+ *     applied steering = expert drives ? es : ps
+ *     expert_speed = 1 (default):  applied throttle, brake = (et, eb) always — "applied as labelled", as in trs_step_expert; the speed label of the
+ *                                  speed_ctl and full_house loaders (the car's own speed / 20) then shows the expert's speed behaviour
+ *     expert_speed = 0:            applied throttle, brake = expert drives ? (et, eb) : (pt, pb); those two loaders' speed label is then the PILOT's own
+ *                                  speed and is not a correction
+ *     row   = (es, et, eb, applied steering, speed, cte, (float)((double)seg_idx / n_points * 10), done), the layout of "scripted expert": the
+ *             expert's label (TRS_LABEL_EXPERT) is the correction, the applied steering (TRS_LABEL_APPLIED) what the car was given
+ *     frame = the frame the pilot was fed this tick: the codec's output under a camera codec, the delayed frame under a latency (zeros for the cars
+ *             nothing has reached yet, as delivered), otherwise the latest frame.  This DIFFERS from trs_step_expert, which captures the rendered truth: it
+ *             is the pair the pilot is judged on, and the pair the reference's tubs hold under sim_latency.
+ *     stats[e], float[6], on every tick whether captured or not, in tick order, each one binary32 operation:
+ *             [0] += 1;  [1] += expert drives ? 1 : 0;  [2] += |cte|;  [3] = max([3], |cte|);  [4] += |ps - es|;  [5] += done ? 1 : 0
+ *             with cte and done of the state the label was computed on (the row's).  Counts are exact below 2^24 ticks.  Zeroed by trs_set_expert and by
+ *             a reset request of trs_dagger_stats.
+ *     k advances by one per tick.  Resets of a car touch neither k nor the stats.  The capture rule (which k is captured, into which slot) is
+ *     trs_step_expert's; a tick whose frame is wanted is not captured while the pilot has no frame.
+ *   tests/test_dagger_cpu.py restates the paragraph in numpy and drives the CPU oracle with it; tests/test_dagger_gpu.py compares trs_step_dagger with
+ *   compositions of the existing calls and that restatement bit for bit; csrc/trsim_expert.hpp holds the defaults, the config check and the gate that the
+ *   kernel and the host both use.
+ *
+ * ---- training minibatches (trs_sample_batch, trs_loader_order;DataLoader.load of the reference, components/keras_train.py:33-69; HIP library only)
  *   A set of n records (frame uint8[H][W][3], row float[8] as "scripted expert" defines it) stays where it is; a minibatch is gathered from it in a
  *   keyed order.  Everything below is unsigned 64-bit integer arithmetic (mod 2^64) or one IEEE operation, so a numpy restatement is bit-exact.
  *     mix(x):  z = x + 0x9E3779B97F4A7C15;  then the three finaliser lines of the synthetic control generator below
@@ -398,5 +429,10 @@
 #define TRS_EXPERT_ALPHA        0.1f
 #define TRS_EXPERT_SIGMA        0.0f
 #define TRS_EXPERT_SEED         0ull           /* the fixture's (tests/golden/train_pilot_fixture.py: collect(seed=0)) */
+/* pilot in the loop with the expert's labels: defaults of trs_dagger_config (trs_default_dagger_config) */
+#define TRS_DAGGER_BETA         0.5f
+#define TRS_DAGGER_HOLD         1
+#define TRS_DAGGER_EXPERT_SPEED 1
+#define TRS_DAGGER_SEED         0ull
 
 #endif /* TRSIM_SPEC_H */

@@ -135,6 +135,11 @@ class TrsExpertCapture(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("every", C.c_int32), ("skip", C.c_int32), ("capacity", C.c_int32), ("d_frames", C.c_void_p), ("d_rows", C.c_void_p)]
 
 
+class TrsDaggerConfig(C.Structure):
+    """``trs_dagger_config`` (include/trsim.h): the gate of ``trs_step_dagger``."""
+    _fields_ = [("struct_size", C.c_uint32), ("beta", C.c_float), ("hold", C.c_int32), ("expert_speed", C.c_int32), ("seed", C.c_uint64)]
+
+
 class TrsLoaderConfig(C.Structure):
     """``trs_loader_config`` (include/trsim.h): which minibatches ``trs_sample_batch`` gathers from a collected set."""
     _fields_ = [
@@ -151,6 +156,7 @@ LOADER_DTYPES = {"float32": 0, "float16": 1, "uint8": 2}                # TRS_DT
 LOADER_SPLITS = {"train": 0, "val": 1}                                  # TRS_SPLIT_*
 
 EXPERT_ROW = ("steering", "throttle", "breaking", "applied_steering", "speed", "cte", "segment", "done")   # a record row of trs_step_expert's capture
+DAGGER_STATS = ("ticks", "expert_ticks", "sum_abs_cte", "max_abs_cte", "sum_abs_steering_diff", "done_ticks")   # a stats row of trs_dagger_stats
 
 COMM_ID_BYTES = 128                                                    # TRS_COMM_ID_BYTES
 
@@ -190,9 +196,12 @@ EXPERT_SYMBOLS = ["default_expert_config", "set_expert", "expert_act", "step_exp
 # HIP library only: the training minibatches (trs_sample_batch, trs_loader_order) — their checker is the numpy restatement of include/trsim_spec.h
 # ("training minibatches") in tests/test_loader_cpu.py (tests/test_loader_gpu.py compares the kernel with the restatement bit for bit)
 LOADER_SYMBOLS = ["default_loader_config", "sample_batch", "loader_order"]
+# HIP library only: the pilot in the loop with the expert's labels (trs_step_dagger) — its checker is the numpy restatement of include/trsim_spec.h ("pilot
+# in the loop with the expert's labels") in tests/test_dagger_cpu.py composed with the existing calls (tests/test_dagger_gpu.py, bit for bit)
+DAGGER_SYMBOLS = ["default_dagger_config", "step_dagger", "dagger_stats"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -307,6 +316,11 @@ class Api:
             "sample_batch": (i32, [vp, C.POINTER(TrsLoaderConfig), vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
             "loader_order": (i32, [C.POINTER(TrsLoaderConfig), i32, i32, i32, i32, vp]),
         }
+        dagger = {
+            "default_dagger_config": (None, [C.POINTER(TrsDaggerConfig)]),
+            "step_dagger": (i32, [vp, C.POINTER(TrsPilotConfig), C.POINTER(TrsDaggerConfig), i32, C.POINTER(TrsExpertCapture), C.POINTER(i32)]),
+            "dagger_stats": (i32, [vp, vp, C.POINTER(vp), i32]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -363,6 +377,12 @@ class Api:
         self.has_loader = hasattr(cdll, prefix + "sample_batch")
         if self.has_loader:
             for name, (res, args) in loader.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_dagger = hasattr(cdll, prefix + "step_dagger")
+        if self.has_dagger:
+            for name, (res, args) in dagger.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -1,9 +1,11 @@
 // trsim_expert.hip — the scripted expert of libtrsim.so (include/trsim_spec.h, "scripted expert"): the device-resident stand-in for the reference's human
-// driver (components/controller.py:24).  One kernel, trs_expert_kernel, evaluates the rule for one env per thread; trs_expert_act hands out the pure
-// labels, trs_step_expert closes the loop in the shape of trs_step_pilot (trsim_pilot.hip) and can capture (frame, label row) records into device memory.
-// The host side of the decisions (config checks, track_yaw, which ticks are captured) is trsim_expert.hpp.  The handle is reached as in the control and
-// JPEG units: trsim_env.hpp and the accessors of trsim_internal.hpp.
-// The kernel is bound by its launch: about 60 B per env, no LDS, no atomics, 256-thread workgroups on a grid of ceil(n / 256).
+// driver (components/controller.py:24).  The rule is one __device__ function, expert_label, evaluated for one env per thread by two kernels:
+// trs_expert_kernel (trs_expert_act hands out the pure labels, trs_step_expert closes the loop in the shape of trs_step_pilot, trsim_pilot.hip) and
+// trs_dagger_kernel (trs_step_dagger, "pilot in the loop with the expert's labels": the pilot has acted, the expert labels the truth, a keyed gate decides
+// per car who holds the wheel).  Both loops can capture (frame, label row) records into device memory.
+// The host side of the decisions (config checks, track_yaw, which ticks are captured, the gate) is trsim_expert.hpp.  The handle is reached as in the
+// control and JPEG units: trsim_env.hpp and the accessors of trsim_internal.hpp.
+// The kernels are bound by their launch: about 60 B (dagger: about 100 B) per env, no LDS, no atomics, 256-thread workgroups on a grid of ceil(n / 256).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,82 +20,143 @@
 
 namespace {
 
+using trsim::kDaggerStatFloats;
 using trsim::kExpertRowFloats;
 
-struct ExpertParams {
-    // the env's state (the truth): views into the handle's slab
+// what the rule reads: the env's state (the truth, views into the handle's slab), the driver's tables and its constants
+struct ExpertRule {
     const int32_t* seg_idx; const float *yaw, *cte, *speed; const uint8_t* done;
     const float *track_yaw, *profile /* nullptr: +inf */, *target;
+    int np, look;
+    float k_cte, k_head, thr_hi, thr_lo, brake_over, brake_val;
+};
+
+struct ExpertParams {
+    ExpertRule rule;
     float* w;                           // the disturbance state per env; nullptr: the pure rule (trs_expert_act)
     float *out_steer, *out_thr, *out_brk;   // the applied controls (the labels when w == nullptr)
     float* rows;                        // float[n][8] of the slot a captured tick goes to, or nullptr
-    int n, np, look, env_id_base;
-    float k_cte, k_head, thr_hi, thr_lo, brake_over, brake_val, alpha, sigma;
+    int n, env_id_base;
+    float alpha, sigma;
     unsigned long long seed;
     uint32_t k;                         // the driver's tick counter
 };
 
+struct DaggerParams {
+    ExpertRule rule;
+    float *ctl_steer, *ctl_thr, *ctl_brk;   // in: the pilot's controls of this tick; out: the applied controls
+    float* rows;                        // float[n][8] of the slot a captured tick goes to, or nullptr
+    float* stats;                       // float[n][6]
+    int n, env_id_base, expert_speed;
+    float beta;
+    unsigned long long seed;
+    uint32_t block;                     // k / hold of the driver's tick counter
+};
+
 __device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
+
+// the label of env i and the state it was computed on
+struct ExpertLabel { float steer, thr, brk, speed, cte; int seg; };
+
+__device__ __forceinline__ ExpertLabel expert_label(const ExpertRule& p, int i)
+{
+    ExpertLabel l;
+    l.seg = p.seg_idx[i];
+    const float yaw = p.yaw[i];
+    l.cte = p.cte[i]; l.speed = p.speed[i];
+    int j = (l.seg + p.look) % p.np;
+    if (j < 0) j += p.np;                                    // (an index is never negative; the table is never read out of bounds either way)
+    float herr = yaw - p.track_yaw[j];
+    if (herr > TRS_PI) herr -= TRS_TWO_PI;
+    if (herr < -TRS_PI) herr += TRS_TWO_PI;
+    const float a = p.k_cte * l.cte, b = p.k_head * herr;
+    l.steer = clamp1(-(a + b));
+    float v_ref = p.target[i];
+    if (p.profile) v_ref = fminf(v_ref, p.profile[j]);
+    l.thr = l.speed < v_ref ? p.thr_hi : p.thr_lo;
+    l.brk = l.speed > v_ref * p.brake_over ? p.brake_val : 0.0f;
+    return l;
+}
+
+// a record row of env i: the label, the steering the car was given and the state the label was computed on
+__device__ __forceinline__ void write_row(float* rows, const ExpertRule& p, int i, const ExpertLabel& l, float applied)
+{
+    const float segment = (float)((double)l.seg / (double)p.np * 10.0);
+    float* r = rows + (size_t)i * kExpertRowFloats;         // (dword stores: the caller's array need not be aligned beyond a float)
+    r[trsim::kExpertRowSteer] = l.steer; r[trsim::kExpertRowThr] = l.thr; r[trsim::kExpertRowBrk] = l.brk; r[trsim::kExpertRowApplied] = applied;
+    r[trsim::kExpertRowSpeed] = l.speed; r[trsim::kExpertRowCte] = l.cte; r[trsim::kExpertRowSegment] = segment;
+    r[trsim::kExpertRowDone] = p.done[i] ? 1.0f : 0.0f;
+}
 
 __global__ __launch_bounds__(256) void trs_expert_kernel(const ExpertParams p)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n) return;
-    const int seg = p.seg_idx[i];
-    const float yaw = p.yaw[i], cte = p.cte[i], speed = p.speed[i];
-    int j = (seg + p.look) % p.np;
-    if (j < 0) j += p.np;                                    // (an index is never negative; the table is never read out of bounds either way)
-    float herr = yaw - p.track_yaw[j];
-    if (herr > TRS_PI) herr -= TRS_TWO_PI;
-    if (herr < -TRS_PI) herr += TRS_TWO_PI;
-    const float a = p.k_cte * cte, b = p.k_head * herr;
-    const float steer = clamp1(-(a + b));
-    float v_ref = p.target[i];
-    if (p.profile) v_ref = fminf(v_ref, p.profile[j]);
-    const float thr = speed < v_ref ? p.thr_hi : p.thr_lo;
-    const float brk = speed > v_ref * p.brake_over ? p.brake_val : 0.0f;
-    float applied = steer;
+    const ExpertLabel l = expert_label(p.rule, i);
+    float applied = l.steer;
     if (p.w) {
-        const unsigned long long gid = (unsigned long long)(unsigned)(p.env_id_base + i);
-        unsigned long long z = p.seed + ((gid << 32) | (unsigned long long)p.k) * 0x9E3779B97F4A7C15ull;
-        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-        z ^= z >> 27; z *= 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        const float u = (float)(z >> 40) * 5.9604644775390625e-08f;        // 2^-24
+        const float u = trsim::unit24(trsim::splitmix64(p.seed, trsim::env_key((uint32_t)(p.env_id_base + i), p.k)));
         const float raw = u * 2.0f - 1.0f;
         float w = p.w[i];
         const float d = p.sigma * raw - w;
         w = w + p.alpha * d;
         p.w[i] = w;
-        applied = clamp1(steer + w);
+        applied = clamp1(l.steer + w);
     }
-    p.out_steer[i] = applied; p.out_thr[i] = thr; p.out_brk[i] = brk;
-    if (p.rows) {
-        const float segment = (float)((double)seg / (double)p.np * 10.0);
-        float* r = p.rows + (size_t)i * kExpertRowFloats;   // (dword stores: the caller's array need not be aligned beyond a float)
-        r[trsim::kExpertRowSteer] = steer; r[trsim::kExpertRowThr] = thr; r[trsim::kExpertRowBrk] = brk; r[trsim::kExpertRowApplied] = applied;
-        r[trsim::kExpertRowSpeed] = speed; r[trsim::kExpertRowCte] = cte; r[trsim::kExpertRowSegment] = segment;
-        r[trsim::kExpertRowDone] = p.done[i] ? 1.0f : 0.0f;
-    }
+    p.out_steer[i] = applied; p.out_thr[i] = l.thr; p.out_brk[i] = l.brk;
+    if (p.rows) write_row(p.rows, p.rule, i, l, applied);
+}
+
+// One tick of "pilot in the loop with the expert's labels" between the pilot's tail and the env step: the control arrays hold the pilot's controls and leave
+// with the applied ones.  block, seed, beta and expert_speed are kernel arguments: uniform over the wave, they stay in scalar registers.
+__global__ __launch_bounds__(256) void trs_dagger_kernel(const DaggerParams p)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n) return;
+    const ExpertLabel l = expert_label(p.rule, i);
+    const float ps = p.ctl_steer[i];
+    const bool expert = trsim::dagger_gate(p.seed, (uint32_t)(p.env_id_base + i), p.block, p.beta);
+    const float applied = expert ? l.steer : ps;
+    p.ctl_steer[i] = applied;
+    if (p.expert_speed || expert) { p.ctl_thr[i] = l.thr; p.ctl_brk[i] = l.brk; }   // else: the pilot's throttle and brake stay where they are
+    if (p.rows) write_row(p.rows, p.rule, i, l, applied);
+    const float acte = fabsf(l.cte);
+    float* s = p.stats + (size_t)i * kDaggerStatFloats;
+    s[trsim::kDaggerStatTicks] = s[trsim::kDaggerStatTicks] + 1.0f;
+    s[trsim::kDaggerStatExpertTicks] = s[trsim::kDaggerStatExpertTicks] + (expert ? 1.0f : 0.0f);
+    s[trsim::kDaggerStatSumAbsCte] = s[trsim::kDaggerStatSumAbsCte] + acte;
+    s[trsim::kDaggerStatMaxAbsCte] = fmaxf(s[trsim::kDaggerStatMaxAbsCte], acte);
+    s[trsim::kDaggerStatSumAbsDiff] = s[trsim::kDaggerStatSumAbsDiff] + fabsf(ps - l.steer);
+    s[trsim::kDaggerStatDone] = s[trsim::kDaggerStatDone] + (p.rule.done[i] ? 1.0f : 0.0f);
 }
 
 // what trs_set_expert keeps per handle (behind trs_internal_expert_slot); its buffers are the project's owning type
 struct ExpertCtx {
     trs_expert_config cfg{};
     trsim::DevBuf<float> track_yaw, profile, target, w;
+    trsim::DevBuf<float> stats;         // float[n][6] of trs_step_dagger (trs_dagger_stats)
     bool has_profile = false;
     int n = 0, n_points = 0;
-    uint32_t k = 0;                     // ticks driven since trs_set_expert
+    uint32_t k = 0;                     // ticks driven since trs_set_expert (trs_step_expert and trs_step_dagger share it)
 };
+
+ExpertRule rule_of(const trs_env* e, const ExpertCtx* c)
+{
+    ExpertRule r{};
+    r.seg_idx = e->pp.seg_idx; r.yaw = e->pp.yaw; r.cte = e->pp.cte; r.speed = e->pp.speed; r.done = e->pp.done;
+    r.track_yaw = c->track_yaw.get(); r.profile = c->has_profile ? c->profile.get() : nullptr; r.target = c->target.get();
+    r.np = c->n_points; r.look = c->cfg.look;
+    r.k_cte = c->cfg.k_cte; r.k_head = c->cfg.k_head; r.thr_hi = c->cfg.thr_hi; r.thr_lo = c->cfg.thr_lo;
+    r.brake_over = c->cfg.brake_over; r.brake_val = c->cfg.brake_val;
+    return r;
+}
 
 ExpertParams params_of(const trs_env* e, const ExpertCtx* c, int n)
 {
     ExpertParams p{};
-    p.seg_idx = e->pp.seg_idx; p.yaw = e->pp.yaw; p.cte = e->pp.cte; p.speed = e->pp.speed; p.done = e->pp.done;
-    p.track_yaw = c->track_yaw.get(); p.profile = c->has_profile ? c->profile.get() : nullptr; p.target = c->target.get();
-    p.n = n; p.np = c->n_points; p.look = c->cfg.look; p.env_id_base = e->cfg.env_id_base;
-    p.k_cte = c->cfg.k_cte; p.k_head = c->cfg.k_head; p.thr_hi = c->cfg.thr_hi; p.thr_lo = c->cfg.thr_lo;
-    p.brake_over = c->cfg.brake_over; p.brake_val = c->cfg.brake_val; p.alpha = c->cfg.alpha; p.sigma = c->cfg.sigma;
+    p.rule = rule_of(e, c);
+    p.n = n; p.env_id_base = e->cfg.env_id_base;
+    p.alpha = c->cfg.alpha; p.sigma = c->cfg.sigma;
     p.seed = c->cfg.seed; p.k = c->k;
     return p;
 }
@@ -142,11 +205,13 @@ TRS_EXPORT int trs_set_expert(trs_env* e, const trs_expert_config* cfg, const fl
     HIPCHK(c->track_yaw.alloc((size_t)np * 4));
     HIPCHK(c->target.alloc((size_t)e->n * 4));
     HIPCHK(c->w.alloc((size_t)e->n * 4));
+    HIPCHK(c->stats.alloc((size_t)e->n * kDaggerStatFloats * 4));
     if (h_profile) HIPCHK(c->profile.alloc((size_t)np * 4));
     HIPCHK(hipMemcpy(c->track_yaw.get(), ty.data(), (size_t)np * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->target.get(), tg.data(), (size_t)e->n * 4, hipMemcpyHostToDevice));
     if (h_profile) HIPCHK(hipMemcpy(c->profile.get(), h_profile, (size_t)np * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(c->w.get(), 0, (size_t)e->n * 4));
+    HIPCHK(hipMemset(c->stats.get(), 0, (size_t)e->n * kDaggerStatFloats * 4));
     trs_internal_count(e, 0, (size_t)np * 4 * (h_profile ? 2 : 1) + (size_t)e->n * 4);
     trs_expert_free(*slot);
     *slot = c;
@@ -199,5 +264,69 @@ TRS_EXPORT int trs_step_expert(trs_env* e, int n_steps, const trs_expert_capture
         rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
         if (rc) return rc;
     }
+    return TRS_OK;
+}
+
+// ---- pilot in the loop with the expert's labels (include/trsim_spec.h) ----
+TRS_EXPORT void trs_default_dagger_config(trs_dagger_config* cfg)
+{
+    if (cfg) trsim::dagger_defaults(cfg);
+}
+
+TRS_EXPORT int trs_step_dagger(trs_env* e, const trs_pilot_config* pilot_cfg, const trs_dagger_config* cfg, int n_steps, const trs_expert_capture* cap, int* n_captured)
+{
+    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
+    ExpertCtx* c = ctx_of(e);
+    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    { int rp = trs_internal_pilot_loop_check(e, pilot_cfg, n_steps); if (rp) return rp; }    // trs_step_pilot's own refusals
+    if (const char* why = trsim::dagger_config_error(cfg)) return trs_internal_fail(TRS_ERR_ARG, why);
+    if (const char* why = trsim::expert_capture_error(cap, e->cfg.render != 0)) return trs_internal_fail(TRS_ERR_ARG, why);
+    HIPCHK(hipSetDevice(e->device));
+    trsim::CapturePlan plan = trsim::CapturePlan::of(cap);
+    if (n_captured) *n_captured = 0;
+    const size_t row_stride = (size_t)e->n * kExpertRowFloats;
+    for (int t = 0; t < n_steps; ++t) {
+        TrsEnvView v;
+        const uint8_t* fed = nullptr;                        // the frame the pilot was fed this tick (nullptr: none exists yet, its controls are zero)
+        int rc = trs_internal_pilot_tick(e, pilot_cfg, &v, &fed);
+        if (rc) return rc;
+        const bool want_frames = cap && cap->d_frames_or_null;
+        const int slot = cap ? plan.slot_for(c->k, !want_frames || fed != nullptr) : -1;
+        DaggerParams p{};
+        p.rule = rule_of(e, c);
+        p.ctl_steer = v.ctl_steer; p.ctl_thr = v.ctl_thr; p.ctl_brk = v.ctl_brk;
+        p.rows = slot >= 0 ? cap->d_rows + (size_t)slot * row_stride : nullptr;
+        p.stats = c->stats.get();
+        p.n = e->n; p.env_id_base = e->cfg.env_id_base; p.expert_speed = cfg->expert_speed;
+        p.beta = cfg->beta; p.seed = cfg->seed; p.block = c->k / (uint32_t)cfg->hold;
+        hipLaunchKernelGGL(trs_dagger_kernel, dim3((p.n + 255) / 256), dim3(256), 0, v.stream, p);
+        HIPCHK(hipGetLastError());
+        c->k += 1;                                           // the stats have moved: the counter moves with them
+        if (slot >= 0 && want_frames)                        // in front of the step: the frame fed is the handle's (latest frame, delay line, codec buffer)
+            HIPCHK(hipMemcpyAsync(cap->d_frames_or_null + (size_t)slot * e->img_bytes, fed, e->img_bytes, hipMemcpyDeviceToDevice, v.stream));
+        if (n_captured) *n_captured = plan.used;
+        rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
+        if (rc) return rc;
+    }
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_dagger_stats(trs_env* e, float* h_out, const float** d_out, int reset)
+{
+    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
+    ExpertCtx* c = ctx_of(e);
+    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    HIPCHK(hipSetDevice(e->device));
+    const size_t bytes = (size_t)c->n * kDaggerStatFloats * sizeof(float);
+    if (d_out) *d_out = c->stats.get();
+    if (!h_out && !reset) return TRS_OK;
+    { int rq = trsim::quiesce_handle(e); if (rq) return rq; }   // the copy and the reset go onto the handle's stream, behind the ticks queued so far
+    if (h_out) {
+        HIPCHK(hipMemcpyAsync(h_out, c->stats.get(), bytes, hipMemcpyDeviceToHost, e->sP));
+        trs_internal_count(e, bytes, 0);
+    }
+    if (reset) HIPCHK(hipMemsetAsync(c->stats.get(), 0, bytes, e->sP));
+    if (h_out) HIPCHK(hipStreamSynchronize(e->sP));
+    trsim::resident_note_launch(e);                          // resident mode selected: stream work without a completion flag, trs_sync waits for the stream
     return TRS_OK;
 }

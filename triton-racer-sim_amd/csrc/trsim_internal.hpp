@@ -56,4 +56,11 @@ int trs_internal_replay_launch(trs_env* e, const trsim::Controls& c, uint64_t st
 void trs_internal_note(const std::string& msg);            // what trs_last_error() returns, without failing the call
 void trs_internal_count(trs_env* e, uint64_t d2h_bytes, uint64_t h2d_bytes);   // trs_counters bookkeeping for copies made outside trsim_hip.hip
 void trs_pilot_free(void* ctx);       // defined in trsim_pilot.hip, called by trs_destroy
+// The two halves of trs_step_pilot that trs_step_dagger (trsim_expert.hip) shares with it, defined in trsim_pilot.hip.
+// trs_internal_pilot_loop_check: what the closed loop refuses before its first tick (no pilot, cfg, n_steps, model type, no camera); TRS_OK or the failed code.
+// trs_internal_pilot_tick: one tick up to, not including, the env step.  Refreshes *v, chooses the frame the pilot reads today (the latest one; the delayed
+// one under an observation latency, with that observation's speed, segment and mode mask), puts it through the camera codec when one is set, and runs the
+// pilot into the handle's control arrays (v->ctl_*) — or writes zero controls when no frame exists yet.  *fed: the frame that was fed (nullptr: none).
+int trs_internal_pilot_loop_check(trs_env* e, const trs_pilot_config* cfg, int n_steps);
+int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView* v, const uint8_t** fed);
 void trs_expert_free(void* ctx);      // defined in trsim_expert.hip, called by trs_destroy and by trs_load_track (a new track switches the expert off); nullptr is fine

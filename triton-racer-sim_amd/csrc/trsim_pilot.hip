@@ -1383,7 +1383,7 @@ TRS_EXPORT int trs_pilot_act(trs_env* e, const trs_pilot_config* cfg, const uint
     return forward_and_tail(c, v, d_frames, n, nullptr, cfg, true, &io);
 }
 
-TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_steps)
+int trs_internal_pilot_loop_check(trs_env* e, const trs_pilot_config* cfg, int n_steps)
 {
     TrsEnvView v; PilotCtx* c;
     if (int rc = enter(e, &v, &c)) return rc;
@@ -1392,19 +1392,34 @@ TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_ste
     { int rm = check_model_type(c, cfg); if (rm) return rm; }
     if (!v.render) return trs_internal_fail(TRS_ERR_STATE, "the pilot needs a camera (render = 1)");
     HIPCHK(hipSetDevice(v.device));
+    return TRS_OK;
+}
+
+int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView* view, const uint8_t** fed)
+{
+    TrsEnvView& v = *view;
+    PilotCtx* const c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
+    trs_internal_view(e, &v);
+    const uint8_t* seen = v.obs_on ? v.obs_frame : v.latest_frame;      // the frame the pilot reads today (nullptr: none yet)
+    if (seen && v.codec_quality) {              // a camera codec is set: the pilot reads codec(that frame), as the reference's pilot reads decoded JPEGs
+        int rc = trs_internal_camera_codec(e, seen, &seen);
+        if (rc) return rc;
+    }
+    // KerasPilot.step on the frame of the previous tick and the env's own speed and segment.  With an observation latency: on what each car has been told
+    // (frame, speed, segment), and (0, 0, 0) for the cars nothing has reached yet (keras_pilot.py:46-47) through the rule's mode mask
+    TrsEnvView o = v;
+    ActIo io{nullptr, nullptr, nullptr, v.ctl_steer, v.ctl_thr, v.ctl_brk};
+    if (v.obs_on) { o.speed = v.obs_speed; o.seg_idx = v.obs_seg_idx; io.mode = v.obs_mode; }
+    *fed = seen;
+    return seen ? forward_and_tail(c, o, seen, v.n, nullptr, cfg, true, &io) : zero_controls(v, v.ctl_steer, v.ctl_thr, v.ctl_brk, v.n);
+}
+
+TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_steps)
+{
+    if (int rc = trs_internal_pilot_loop_check(e, cfg, n_steps)) return rc;
     for (int k = 0; k < n_steps; ++k) {
-        trs_internal_view(e, &v);
-        const uint8_t* seen = v.obs_on ? v.obs_frame : v.latest_frame;      // the frame the pilot reads today (nullptr: none yet)
-        if (seen && v.codec_quality) {              // a camera codec is set: the pilot reads codec(that frame), as the reference's pilot reads decoded JPEGs
-            int rc = trs_internal_camera_codec(e, seen, &seen);
-            if (rc) return rc;
-        }
-        // KerasPilot.step on the frame of the previous tick and the env's own speed and segment.  With an observation latency: on what each car has been told
-        // (frame, speed, segment), and (0, 0, 0) for the cars nothing has reached yet (keras_pilot.py:46-47) through the rule's mode mask
-        TrsEnvView o = v;
-        ActIo io{nullptr, nullptr, nullptr, v.ctl_steer, v.ctl_thr, v.ctl_brk};
-        if (v.obs_on) { o.speed = v.obs_speed; o.seg_idx = v.obs_seg_idx; io.mode = v.obs_mode; }
-        int rc = seen ? forward_and_tail(c, o, seen, v.n, nullptr, cfg, true, &io) : zero_controls(v, v.ctl_steer, v.ctl_thr, v.ctl_brk, v.n);
+        TrsEnvView v; const uint8_t* fed;
+        int rc = trs_internal_pilot_tick(e, cfg, &v, &fed);
         if (!rc) rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
         if (rc) return rc;
     }

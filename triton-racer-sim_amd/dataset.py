@@ -72,7 +72,8 @@ class DeviceDataset:
         """Copy another collection in (device handles as ``BatchedEnv.collect`` returns them, valid only until the next ``collect``; torch tensors
         and host arrays are taken too).  The split is re-derived from the new ``len(self)``: ``n_train = floor(split * n)``, and sigma is a
         permutation of the new ``n``.  ``jpeg_quality``: the new frames go through ``device_jpeg_roundtrip`` once, so that the set holds what a tub's
-        files would have given; a quality outside 1..100 (0 included: ``None`` is the only way to ask for no codec) is refused before anything is copied."""
+        files would have given; a quality outside 1..100 (0 included: ``None`` is the only way to ask for no codec) is refused before anything is copied.
+        This is DAgger's aggregation: append what ``collect(driver="pilot", ...)`` gathered with the pilot in the loop, then retrain on the larger set."""
         torch = self.torch
         if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
             raise ValueError("jpeg_quality must lie in 1..100 (None: no codec)")

@@ -925,24 +925,78 @@ class BatchedEnv:
         uint8 ``[capacity, n_envs, H, W, 3]``: tick ``k`` of the driver is captured when ``k >= skip`` and ``(k - skip) % every == 0``.  Returns the
         number of slots this call filled."""
         self._need_expert()
-        cap = capture
-        if isinstance(capture, dict):
-            cap = _ffi.TrsExpertCapture()
-            cap.struct_size = C.sizeof(_ffi.TrsExpertCapture)
-            cap.every, cap.skip, cap.capacity = int(capture.get("every", 1)), int(capture.get("skip", 0)), int(capture["capacity"])
-            cap.d_frames, cap.d_rows = device_ptr(capture.get("frames")), device_ptr(capture.get("rows"))
+        cap = self._capture(capture)
         got = C.c_int(0)
         self.api.check(self.api.step_expert(self._h, int(n_steps), None if cap is None else C.byref(cap), C.byref(got)), "step_expert")
         return int(got.value)
 
-    def collect(self, ticks, every=5, skip=20, to_host=False):
-        """A training set from the expert without a byte crossing to the host: ``ticks`` ticks of ``step_expert`` in ONE call, every ``every``-th tick
+    @staticmethod
+    def _capture(capture):
+        """A ``TrsExpertCapture`` from a dict ``{every, skip, capacity, rows, frames}`` (anything else is passed through)."""
+        if not isinstance(capture, dict):
+            return capture
+        cap = _ffi.TrsExpertCapture()
+        cap.struct_size = C.sizeof(_ffi.TrsExpertCapture)
+        cap.every, cap.skip, cap.capacity = int(capture.get("every", 1)), int(capture.get("skip", 0)), int(capture["capacity"])
+        cap.d_frames, cap.d_rows = device_ptr(capture.get("frames")), device_ptr(capture.get("rows"))
+        return cap
+
+    # -- pilot in the loop with the expert's labels (include/trsim_spec.h) --------------------------------------------------
+    def _need_dagger(self):
+        if not getattr(self.api, "has_dagger", False):
+            raise RuntimeError("the oracle has no trs_step_dagger: its checker is the restatement in tests/test_dagger_cpu.py, HIP library only")
+
+    def dagger_config(self, beta=0.5, hold=1, expert_speed=True, seed=0):
+        """``trs_dagger_config`` from the library's defaults (``trs_default_dagger_config``) with the four fields set."""
+        self._need_dagger()
+        dc = _ffi.TrsDaggerConfig()
+        self.api.default_dagger_config(C.byref(dc))
+        dc.beta, dc.hold, dc.expert_speed, dc.seed = float(beta), int(hold), int(expert_speed), int(seed)
+        return dc
+
+    def step_dagger(self, n_steps=1, cfg=None, beta=0.5, hold=1, expert_speed=True, seed=0, capture=None):
+        """Closed loop on the device with the pilot in it and the expert's labels (``trs_step_dagger``; DAgger).  Per tick the loaded pilot acts exactly
+        as in ``step_pilot`` (``cfg`` is the pilot config, as there), the expert of ``set_expert`` labels the truth, and a keyed gate decides per car
+        who holds the wheel: the expert with probability ``beta``, constant over blocks of ``hold`` ticks, keyed by ``seed`` and the global env id.
+        ``expert_speed=True``: throttle and brake are always the expert's; ``False``: they follow the gate (the speed label of the ``speed_ctl`` and
+        ``full_house`` loaders is then the pilot's own speed, not a correction).  ``capture`` as for ``step_expert``: a row is the expert's label, the
+        APPLIED steering, speed, cte, segment, done; the frame is the one the pilot was fed (codec's, delayed, or latest).  Returns the slots filled."""
+        self._need_dagger()
+        pc = cfg if isinstance(cfg, _ffi.TrsPilotConfig) else self.pilot_config(cfg)
+        dc = self.dagger_config(beta, hold, expert_speed, seed)
+        cap = self._capture(capture)
+        got = C.c_int(0)
+        self.api.check(self.api.step_dagger(self._h, C.byref(pc), C.byref(dc), int(n_steps), None if cap is None else C.byref(cap), C.byref(got)), "step_dagger")
+        return int(got.value)
+
+    def dagger_stats(self, reset=False, to_host=True):
+        """How the pilot did under ``step_dagger`` since ``set_expert`` or the last ``reset=True`` (``trs_dagger_stats``): a dict of six float32
+        ``[n_envs]`` arrays named by ``_ffi.DAGGER_STATS`` — ticks, ticks the expert drove, sum and max of |cte|, sum of |pilot steering - label|,
+        ticks with done set.  ``to_host=False``: the device handle float32 ``[n_envs, 6]`` instead (env-owned, live)."""
+        self._need_dagger()
+        if not to_host:
+            ptr = C.c_void_p()
+            self.api.check(self.api.dagger_stats(self._h, None, C.byref(ptr), int(bool(reset))), "dagger_stats")
+            return _DevicePtr(ptr.value, (self.n, len(_ffi.DAGGER_STATS)), np.float32, self)
+        out = np.empty((self.n, len(_ffi.DAGGER_STATS)), np.float32)
+        self.api.check(self.api.dagger_stats(self._h, out.ctypes.data, None, int(bool(reset))), "dagger_stats")
+        return {name: np.ascontiguousarray(out[:, i]) for i, name in enumerate(_ffi.DAGGER_STATS)}
+
+    def collect(self, ticks, every=5, skip=20, to_host=False, driver="expert", **dagger):
+        """A training set without a byte crossing to the host: ``ticks`` ticks of ``step_expert`` in ONE call, every ``every``-th tick
         from the driver's tick ``skip`` on captured.  Returns ``(frames uint8[N, H, W, 3], rows float32[N, 8])`` (physics-only envs: ``frames`` is
         ``None``), N = captured ticks x n_envs in tick order; a row is ``_ffi.EXPERT_ROW``: the expert's label (steering, throttle, breaking), the
         applied steering, speed, cte, 'loc/segment' and done of the state the frame shows.  Device handles on env-owned memory, valid until the next
         ``collect`` (``to_host=True``: fresh numpy arrays instead).  Feed them to ``recorder.records_for``; put the frames through
-        ``device_jpeg_roundtrip`` first for what the reference's pilot would have seen."""
+        ``device_jpeg_roundtrip`` first for what the reference's pilot would have seen.
+        ``driver="pilot"``: the ticks are ``step_dagger``'s instead — the loaded pilot (or its keyed mixture with the expert) drives, the rows hold the
+        expert's corrections and the frames are the ones the pilot was fed; ``dagger`` takes ``step_dagger``'s ``cfg``, ``beta``, ``hold``,
+        ``expert_speed`` and ``seed``.  ``DeviceDataset.append`` aggregates such a round into an existing set."""
         self._need_expert()
+        if driver not in ("expert", "pilot"):
+            raise ValueError("driver must be 'expert' or 'pilot'")
+        if dagger and driver != "pilot":
+            raise ValueError(f"{sorted(dagger)} belong to driver='pilot' (step_dagger)")
         ticks, every, skip = int(ticks), int(every), int(skip)
         if ticks < 1 or every < 1 or skip < 0:
             raise ValueError("ticks >= 1, every >= 1 and skip >= 0 are required")
@@ -950,7 +1004,8 @@ class BatchedEnv:
         render = bool(self.cfg.render)
         rows = self.scratch(SLOT_COLLECT[1], (capacity, self.n, 8), np.float32)
         frames = self.scratch(SLOT_COLLECT[0], (capacity, self.n, self.H, self.W, 3), np.uint8) if render else None
-        got = self.step_expert(ticks, {"every": every, "skip": skip, "capacity": capacity, "rows": rows, "frames": frames})
+        capture = {"every": every, "skip": skip, "capacity": capacity, "rows": rows, "frames": frames}
+        got = self.step_expert(ticks, capture) if driver == "expert" else self.step_dagger(ticks, capture=capture, **dagger)
         rows = _DevicePtr(device_ptr(rows), (got * self.n, 8), np.float32, self)
         if render:
             frames = _DevicePtr(device_ptr(frames), (got * self.n, self.H, self.W, 3), np.uint8, self)
