@@ -115,6 +115,116 @@ def test_plan_at_100x132_and_130x300(driver):
     assert p["chain"]["first"] == -1
 
 
+# every layer on its single-layer kernel, and of those the quad-load one wherever it applies: what tests/test_pilot_fallback.py loads its pilots with
+FALLBACK = dict(no_fuse=1, span_layers_mask=0, frame5=0, frame_layers_mask=0, chain_layers=0)
+
+
+def persistent_batch(plan, layer, cus):
+    """The smallest odd batch at which conv(layer + 1)'s single-layer kernel gets more 32-pixel tiles than the waves that are resident: the grid is capped at
+    cus x res_wg_per_cu workgroups (single_grid_x), below the cap it has a wave per tile, so the first such batch is the first past cap x waves x 32 pixels."""
+    l = plan["layers"][layer]
+    waves = cus * l["res_wg_per_cu"] * (l["res_block"] // 64)
+    return (32 * waves // (l["OH"] * l["OW"]) + 1) | 1
+
+
+def tiles_and_waves(plan, call, layer, n):
+    """(32-pixel tiles, resident waves) of conv(layer + 1) launched by itself on n frames"""
+    l = plan["layers"][layer]
+    return (n * l["OH"] * l["OW"] + 31) // 32, call[f"grid{layer}"] * (l["res_block"] // 64)
+
+
+@pytest.mark.parametrize("size,n_cap", [((120, 160), 1), ((120, 160), 5), ((100, 132), 9), ((96, 100), 37)])
+def test_fallback_plan_is_the_quad_load_kernel_on_conv2_to_conv7(driver, size, n_cap):
+    """trs_conv_lt_kernel under FALLBACK: <1> on conv2 (5 waves, 3 workgroups per CU), <2> on conv3..conv7, conv6 and conv7 in two slices of 64 channels,
+    conv7 with 7 waves in 162,624 of the CU's 163,840 bytes.  The K lengths are 80, 100, 72, 72, 72 and 144 granules."""
+    h, w = size
+    p = plan_of(driver, h, w, n_cap, **FALLBACK)
+    assert [l["served_by"] for l in p["layers"]] == ["u8", "lt<1>", "lt<2>", "lt<2>", "lt<2>", "lt<2>", "lt<2>", "dense"]
+    assert p["head"]["runs"] == 0 and p["chain"]["first"] == -1
+    res = lambda i: tuple(p["layers"][i][k] for k in ("res_nb", "res_ysplit", "res_block", "res_lds", "res_wg_per_cu"))
+    assert res(1) == (1, 1, 320, 51648, 3)
+    assert res(2) == (2, 1, 1024, 135824, 1)
+    assert res(3) == res(4) == (2, 1, 1024, 107040, 1)
+    assert res(5) == (2, 2, 1024, 107040, 1)
+    assert res(6) == (2, 2, 448, 162624, 1) and LDS_BYTES - res(6)[3] == 1216
+    assert [l["G_pad"] for l in p["layers"][1:7]] == [80, 100, 72, 72, 72, 144] and p["layers"][1]["run_pad"] == 16
+    ohw = {(120, 160): [999, 204, 150, 104, 66, 36], (100, 132): [660, 117, 77, 45, 21, 5], (96, 100): [462, 81, 49, 25, 9, 1]}[size]
+    assert [l["OH"] * l["OW"] for l in p["layers"][1:7]] == ohw
+    # conv2's padding granule of the last output column is the spare last column of the same conv1 row: a frame is a multiple of 4 wide (trs_create), so conv1's
+    # width W / 2 - 2 is even and conv2's windows end one column short of it
+    l1 = p["layers"][1]
+    assert l1["IW"] == w // 2 - 2 and 2 * (l1["OW"] - 1) + 5 == l1["IW"] - 1
+
+
+def test_default_plans_of_large_frames_reach_the_quad_load_kernel(driver):
+    """360x480 and 480x640 with the default tuning: the head cut in 3 and 4 parts, conv3 in 14 bands of 3 rows and 29 of 2, and trs_conv_lt_kernel<2>
+    where a row band of a 3x3 layer's input does not fit LDS twice over: conv7, and conv4..conv7."""
+    p = plan_of(driver, 360, 480, 3)
+    head, c3 = p["head"], p["layers"][2]
+    assert (head["on"], head["runs"], head["wsplit"], head["w2p"], head["cpr"], head["R2"], head["bands"], head["lds"]) == (1, 1, 3, 39, 31, 6, 15, 139328)
+    assert (c3["frame5"], c3["frame5_bands"], c3["frame5_ohb"], c3["frame5_lds"]) == (1, 14, 3, 135040)
+    assert [(l["frame"], l["frame_bands"], l["frame_ohb"]) for l in p["layers"][3:7]] == [(1, 5, 8), (1, 5, 8), (1, 8, 5), (0, 1, 34)]
+    assert [l["served_by"] for l in p["layers"]] == ["band<split>", "band<split>", "frame5", "frame", "frame", "frame", "lt<2>", "dense"]
+    assert p["chain"]["first"] == -1
+    p = plan_of(driver, 480, 640, 2)
+    head, c3 = p["head"], p["layers"][2]
+    assert (head["on"], head["runs"], head["wsplit"], head["w2p"], head["cpr"], head["R2"], head["bands"], head["lds"]) == (1, 1, 4, 40, 32, 5, 24, 129664)
+    assert (c3["frame5"], c3["frame5_bands"], c3["frame5_ohb"], c3["frame5_lds"]) == (1, 29, 2, 140928)
+    assert [l["frame"] for l in p["layers"][3:7]] == [0, 0, 0, 0]
+    assert [l["served_by"] for l in p["layers"]] == ["band<split>", "band<split>", "frame5", "lt<2>", "lt<2>", "lt<2>", "lt<2>", "dense"]
+    assert p["chain"]["first"] == -1
+    for l in p["layers"][3:7]:
+        assert (l["res_nb"], l["res_block"], l["res_lds"]) == ((2, 448, 162624) if l["i"] == 6 else (2, 1024, 107040))
+
+
+@pytest.mark.parametrize("size,n_cap", [((96, 100), 37), ((96, 100), 1027), ((120, 100), 5), ((120, 96), 5)])
+def test_a_layer_one_pixel_wide_stays_off_the_kernels_that_divide_by_its_width(driver, size, n_cap):
+    """Frames 96 and 100 wide leave conv7 one pixel wide.  trs_conv_frame_kernel and trs_conv_chain_kernel turn a pixel index into (frame, row, column) with
+    pilot_magic(OH x OW) and pilot_magic(OW), and pilot_magic(1) is 2^32 cut to 0: every quotient 0.  The chain at 96x100 gave the second frame of every
+    workgroup the first one's conv7 window (found by tests/test_pilot_fallback.py, A at 96x100).  The plan keeps such a layer on the quad-load kernel, and with
+    conv7 off the frame kernel there is no chain."""
+    h, w = size
+    p = plan_of(driver, h, w, n_cap)
+    c7 = p["layers"][6]
+    assert c7["OW"] == 1 and c7["OH"] == {96: 1, 120: 4}[h] and c7["frame"] == 0
+    assert [l["served_by"] for l in p["layers"][2:]] == ["frame5", "frame", "frame", "frame", "lt<2>", "dense"] and p["chain"]["first"] == -1
+    assert all(l["frame"] == 1 and l["OW"] >= 3 for l in p["layers"][3:6])
+    assert (c7["res_nb"], c7["res_ysplit"], c7["res_block"], c7["res_lds"]) == (2, 2, 448, 162624)
+    assert plan_of(driver, h, w, n_cap, chain_layers=3)["chain"]["first"] == -1
+    wider = plan_of(driver, h, 104, n_cap)                                    # the next legal width: conv7 two pixels wide, the chain as everywhere
+    assert wider["layers"][6]["OW"] == 2 and wider["chain"]["first"] == 3 and [l["served_by"] for l in wider["layers"][3:7]] == ["chain"] * 4
+
+
+def test_no_plan_hands_pilot_magic_a_divisor_of_one(driver):
+    """Every divisor the plan turns into a pilot_magic factor is 2 or more: OW and the unit's pixels of a layer on the frame kernel or in the chain, conv3's OW on
+    trs_conv_frame5_kernel, the head's part width and chunks per row.  All legal widths from 64 to 320, two heights."""
+    for w in range(64, 324, 4):
+        for h in (96, 121):
+            for kind, r in map(parse, run_driver(driver, "plan", h, w, 37, 256, 22)):
+                where = (kind, h, w, r.get("i"))
+                if kind == "layer" and (r["frame"] or r["frame5"]):
+                    assert r["OW"] >= 2 and r["OH"] * r["OW"] >= 2, where
+                elif kind == "head" and r["on"] and r["wsplit"] > 1:
+                    assert r["magic_full"] > 0 and r["magic_cpr"] > 0 and r["cpr"] >= 2 and r["w2p"] >= 2, where
+                elif kind == "chain" and r["first"] >= 0:
+                    assert all(r[f"magic_uout{j}"] > 0 and r[f"magic_ow{j}"] > 0 for j in range(r["nl"])), where
+
+
+@pytest.mark.parametrize("layer,n,tiles,waves", [(1, 267, 3855, 3840), (2, 1619, 4099, 4096)])
+def test_batches_that_make_the_quad_load_kernel_loop(driver, layer, n, tiles, waves):
+    """96x100 under FALLBACK on 256 CUs: 267 frames give conv2 (462 pixels a frame, 768 workgroups of 5 waves) and 1,619 give conv3 (81 pixels a frame,
+    256 workgroups of 16 waves) more tiles than resident waves, so some waves take a second tile; each is the smallest odd batch that does, and its
+    last tile is ragged."""
+    p = plan_of(driver, 96, 100, n, **FALLBACK)
+    assert persistent_batch(p, layer, 256) == n
+    assert tiles_and_waves(p, call_of(driver, 96, 100, n, n, **FALLBACK), layer, n) == (tiles, waves) and tiles > waves
+    assert n * p["layers"][layer]["OH"] * p["layers"][layer]["OW"] % 32 != 0
+    first = 32 * waves // (p["layers"][layer]["OH"] * p["layers"][layer]["OW"]) + 1     # the first batch that loops: n, or the even one in front of it
+    assert first in (n, n - 1)
+    t, w = tiles_and_waves(p, call_of(driver, 96, 100, n, first - 1, **FALLBACK), layer, first - 1)
+    assert t <= w, (first - 1, t, w)
+
+
 def test_refusals_come_back_through_the_plan(driver):
     small = plan_of(driver, 28, 160, 4)
     assert small["refuse"] == {"H": 28, "W": 160, "n_cap": 4, "code": -5, "text": REFUSALS[0]} and not small["layers"]

@@ -28,7 +28,8 @@ constexpr int kDenseChunk = 72;            // granules per LDS chunk of trs_pilo
 constexpr int kDensePitch = 73;            // LDS row pitch in granules (odd: 16 lanes cover all 64 banks)
 constexpr int kDenseLds = 2 * 32 * kDensePitch * 16;   // per 32 frames (NF = 2: twice that)
 constexpr int kFrameBlock = 64 * (8 + TRS_FRAME_LOADERS), kFrame5Block = 64 * (TRS_F5_COMPUTE + 4), kChainBlock = 512;
-// floor(p / d) = umulhi(p, pilot_magic(d)), exact for p < 2^32 / d: the kernels' item set-up without divisions
+// floor(p / d) = umulhi(p, pilot_magic(d)), exact for p < 2^32 / d: the kernels' item set-up without divisions.  d >= 2: for d = 1 the factor would be 2^32,
+// which comes back as 0 (every quotient 0) — the plan keeps a layer whose divisor would be 1 off the kernels that divide this way (plan_frame)
 inline unsigned pilot_magic(int d) { return (unsigned)((0x100000000ull + (unsigned)d - 1u) / (unsigned)d); }
 
 inline trs_pilot_tuning pilot_default_tuning()
@@ -123,7 +124,9 @@ inline bool plan_single(PilotLayer& l, int i, const trs_pilot_tuning& T)
 inline void plan_frame(PilotLayer& l, int n_cap, int cu_count)
 {
     const int cg = l.CIN / 8;
-    const bool shape_ok = l.S == 1 && l.KH == 3 && l.KW == 3 && (cg == 8 || cg == 16) && l.COUT_PAD % 64 == 0 && l.COUT == l.COUT_PAD && l.run_pad == l.KW * cg;
+    // OW >= 2: the frame kernel and the chain divide a pixel index by OW (and by the unit's pixels, a multiple of it) through pilot_magic, which has no
+    // 32-bit value for a divisor of 1.  conv7 is one pixel wide for frames 96 and 100 wide: the quad-load kernel takes it, and no chain is built
+    const bool shape_ok = l.S == 1 && l.KH == 3 && l.KW == 3 && (cg == 8 || cg == 16) && l.COUT_PAD % 64 == 0 && l.COUT == l.COUT_PAD && l.run_pad == l.KW * cg && l.OW >= 2;
     if (!shape_ok) return;
     // Two LDS buffers (the group being computed and the next one), F units each, a unit = a frame or one of `bands` row bands of it (240x320:
     // conv4 128 KB, conv6 97 KB, conv7 167 KB per frame).  Among the (bands, F) that fit, take the one with the fewest MFMA rounds: a group is
