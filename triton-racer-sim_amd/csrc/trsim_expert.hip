@@ -1,10 +1,12 @@
 // trsim_expert.hip — the scripted expert of libtrsim.so (include/trsim_spec.h, "scripted expert"): the device-resident stand-in for the reference's human
 // driver (components/controller.py:24).  The rule is one __device__ function, expert_label, evaluated for one env per thread by two kernels:
-// trs_expert_kernel (trs_expert_act hands out the pure labels, trs_step_expert closes the loop in the shape of trs_step_pilot, trsim_pilot.hip) and
-// trs_dagger_kernel (trs_step_dagger, "pilot in the loop with the expert's labels": the pilot has acted, the expert labels the truth, a keyed gate decides
-// per car who holds the wheel).  Both loops can capture (frame, label row) records into device memory.
-// The host side of the decisions (config checks, track_yaw, which ticks are captured, the gate) is trsim_expert.hpp.  The handle is reached as in the
-// control and JPEG units: trsim_env.hpp and the accessors of trsim_internal.hpp.
+// trs_expert_kernel (trs_expert_act hands out the pure labels, trs_step_expert closes the loop) and trs_dagger_kernel (trs_step_dagger, "pilot in the loop
+// with the expert's labels": the pilot has acted, the expert labels the truth, a keyed gate decides per car who holds the wheel).  Both loops can capture
+// (frame, label row) records into device memory.
+// A closed loop here is its argument checks and an ops object (ExpertOps, DaggerOps: what observes, what labels) handed to trsim::closed_loop of
+// trsim_loop.hpp, which owns the order of a tick, the capture plan and the counter; trs_step_pilot (trsim_pilot.hip) runs through the same loop.
+// The other host-side decisions (config checks, track_yaw, the gate) are trsim_expert.hpp.  The handle is reached as in the control and JPEG units:
+// trsim_env.hpp and the accessors of trsim_internal.hpp.
 // The kernels are bound by their launch: about 60 B (dagger: about 100 B) per env, no LDS, no atomics, 256-thread workgroups on a grid of ceil(n / 256).
 #include <hip/hip_runtime.h>
 
@@ -161,14 +163,60 @@ ExpertParams params_of(const trs_env* e, const ExpertCtx* c, int n)
     return p;
 }
 
-int launch_expert(const trs_env* e, const ExpertParams& p)
+// every launch of the two label kernels: one thread per env, on the view's stream
+template <class P>
+int launch_label(void (*kernel)(P), hipStream_t stream, const P& p)
 {
-    hipLaunchKernelGGL(trs_expert_kernel, dim3((p.n + 255) / 256), dim3(256), 0, e->sP, p);
+    hipLaunchKernelGGL(kernel, dim3((p.n + 255) / 256), dim3(256), 0, stream, p);
     HIPCHK(hipGetLastError());
     return TRS_OK;
 }
 
-ExpertCtx* ctx_of(trs_env* e) { return static_cast<ExpertCtx*>(*trs_internal_expert_slot(e)); }
+// how every entry point behind trs_set_expert begins: the handle's driver
+int enter(trs_env* e, ExpertCtx** c)
+{
+    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
+    *c = static_cast<ExpertCtx*>(*trs_internal_expert_slot(e));
+    if (!*c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    return TRS_OK;
+}
+
+// what the ops of the two labelling loops share (trsim_loop.hpp): the driver, and where the row of a captured tick goes
+struct LabelOps : TrsLoopOps {
+    ExpertCtx* c;
+    float* rows(int slot) const { return slot >= 0 ? cap->d_rows + (size_t)slot * e->n * kExpertRowFloats : nullptr; }
+};
+
+// trs_step_expert: the expert drives.  The frame of a record is the rendered truth of the state the label is computed on, whatever the latency or codec
+struct ExpertOps : LabelOps {
+    int observe(const uint8_t** frame) { int rc = trs_internal_tick_view(e, &v); if (!rc) *frame = v.latest_frame; return rc; }
+    int label(int slot)
+    {
+        ExpertParams p = params_of(e, c, e->n);
+        p.w = c->w.get();                                    // the disturbance state moves: closed_loop moves the counter with it
+        p.out_steer = v.ctl_steer; p.out_thr = v.ctl_thr; p.out_brk = v.ctl_brk;
+        p.rows = rows(slot);
+        return launch_label(trs_expert_kernel, v.stream, p);
+    }
+};
+
+// trs_step_dagger: the pilot acts, the expert labels the truth, the gate decides.  The frame of a record is the one the pilot was fed (the latest frame, the
+// delay line's, the codec buffer's; nullptr: none exists yet, its controls are zero)
+struct DaggerOps : LabelOps {
+    const trs_pilot_config* pilot_cfg; const trs_dagger_config* cfg;
+    int observe(const uint8_t** fed) { return trs_internal_pilot_tick(e, pilot_cfg, &v, fed); }
+    int label(int slot)
+    {
+        DaggerParams p{};
+        p.rule = rule_of(e, c);
+        p.ctl_steer = v.ctl_steer; p.ctl_thr = v.ctl_thr; p.ctl_brk = v.ctl_brk;
+        p.rows = rows(slot);
+        p.stats = c->stats.get();                            // the stats move: closed_loop moves the counter with them
+        p.n = e->n; p.env_id_base = e->cfg.env_id_base; p.expert_speed = cfg->expert_speed;
+        p.beta = cfg->beta; p.seed = cfg->seed; p.block = c->k / (uint32_t)cfg->hold;
+        return launch_label(trs_dagger_kernel, v.stream, p);
+    }
+};
 
 }  // namespace
 
@@ -221,50 +269,28 @@ TRS_EXPORT int trs_set_expert(trs_env* e, const trs_expert_config* cfg, const fl
 
 TRS_EXPORT int trs_expert_act(trs_env* e, float* d_steer, float* d_thr, float* d_brk, int n)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    ExpertCtx* c = ctx_of(e);
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    ExpertCtx* c;
+    if (int rc = enter(e, &c)) return rc;
     if (!d_steer || !d_thr || !d_brk || n < 0 || n > e->n) return trs_internal_fail(TRS_ERR_ARG, "null output or n out of range (n <= n_envs)");
     HIPCHK(hipSetDevice(e->device));
     if (n == 0) return TRS_OK;
     { int rq = trsim::quiesce_handle(e); if (rq) return rq; }   // the kernel goes onto the handle's stream and reads the state behind the posted steps
     ExpertParams p = params_of(e, c, n);
     p.out_steer = d_steer; p.out_thr = d_thr; p.out_brk = d_brk;
-    int rc = launch_expert(e, p);
+    int rc = launch_label(trs_expert_kernel, e->sP, p);
     if (!rc) trsim::resident_note_launch(e);                 // resident mode selected: this kernel has no completion flag, trs_sync waits for the stream
     return rc;
 }
 
 TRS_EXPORT int trs_step_expert(trs_env* e, int n_steps, const trs_expert_capture* cap, int* n_captured)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    ExpertCtx* c = ctx_of(e);
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    ExpertCtx* c;
+    if (int rc = enter(e, &c)) return rc;
     if (n_steps < 1) return trs_internal_fail(TRS_ERR_ARG, "n_steps < 1");
     if (const char* why = trsim::expert_capture_error(cap, e->cfg.render != 0)) return trs_internal_fail(TRS_ERR_ARG, why);
     HIPCHK(hipSetDevice(e->device));
-    trsim::CapturePlan plan = trsim::CapturePlan::of(cap);
-    if (n_captured) *n_captured = 0;
-    const size_t row_stride = (size_t)e->n * kExpertRowFloats;
-    for (int t = 0; t < n_steps; ++t) {
-        TrsEnvView v;
-        if (!trs_internal_view(e, &v)) return trs_internal_fail(TRS_ERR_DEVICE, "the handle's stream could not be taken over from the resident worker");
-        const uint8_t* frame = cap && cap->d_frames_or_null ? v.latest_frame : nullptr;      // the rendered truth of the state the label is computed on
-        const int slot = cap ? plan.slot_for(c->k, !cap->d_frames_or_null || frame != nullptr) : -1;
-        ExpertParams p = params_of(e, c, e->n);
-        p.w = c->w.get();
-        p.out_steer = v.ctl_steer; p.out_thr = v.ctl_thr; p.out_brk = v.ctl_brk;
-        p.rows = slot >= 0 ? cap->d_rows + (size_t)slot * row_stride : nullptr;
-        int rc = launch_expert(e, p);
-        if (rc) return rc;
-        c->k += 1;                                           // the disturbance state has moved: the counter moves with it
-        if (slot >= 0 && frame)                              // in front of the step: the buffer is recycled two steps on
-            HIPCHK(hipMemcpyAsync(cap->d_frames_or_null + (size_t)slot * e->img_bytes, frame, e->img_bytes, hipMemcpyDeviceToDevice, v.stream));
-        if (n_captured) *n_captured = plan.used;
-        rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
-        if (rc) return rc;
-    }
-    return TRS_OK;
+    ExpertOps ops{{{e, cap, {}}, c}};
+    return trsim::closed_loop(ops, n_steps, cap, &c->k, n_captured);
 }
 
 // ---- pilot in the loop with the expert's labels (include/trsim_spec.h) ----
@@ -275,47 +301,20 @@ TRS_EXPORT void trs_default_dagger_config(trs_dagger_config* cfg)
 
 TRS_EXPORT int trs_step_dagger(trs_env* e, const trs_pilot_config* pilot_cfg, const trs_dagger_config* cfg, int n_steps, const trs_expert_capture* cap, int* n_captured)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    ExpertCtx* c = ctx_of(e);
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    ExpertCtx* c;
+    if (int rc = enter(e, &c)) return rc;
     { int rp = trs_internal_pilot_loop_check(e, pilot_cfg, n_steps); if (rp) return rp; }    // trs_step_pilot's own refusals
     if (const char* why = trsim::dagger_config_error(cfg)) return trs_internal_fail(TRS_ERR_ARG, why);
     if (const char* why = trsim::expert_capture_error(cap, e->cfg.render != 0)) return trs_internal_fail(TRS_ERR_ARG, why);
     HIPCHK(hipSetDevice(e->device));
-    trsim::CapturePlan plan = trsim::CapturePlan::of(cap);
-    if (n_captured) *n_captured = 0;
-    const size_t row_stride = (size_t)e->n * kExpertRowFloats;
-    for (int t = 0; t < n_steps; ++t) {
-        TrsEnvView v;
-        const uint8_t* fed = nullptr;                        // the frame the pilot was fed this tick (nullptr: none exists yet, its controls are zero)
-        int rc = trs_internal_pilot_tick(e, pilot_cfg, &v, &fed);
-        if (rc) return rc;
-        const bool want_frames = cap && cap->d_frames_or_null;
-        const int slot = cap ? plan.slot_for(c->k, !want_frames || fed != nullptr) : -1;
-        DaggerParams p{};
-        p.rule = rule_of(e, c);
-        p.ctl_steer = v.ctl_steer; p.ctl_thr = v.ctl_thr; p.ctl_brk = v.ctl_brk;
-        p.rows = slot >= 0 ? cap->d_rows + (size_t)slot * row_stride : nullptr;
-        p.stats = c->stats.get();
-        p.n = e->n; p.env_id_base = e->cfg.env_id_base; p.expert_speed = cfg->expert_speed;
-        p.beta = cfg->beta; p.seed = cfg->seed; p.block = c->k / (uint32_t)cfg->hold;
-        hipLaunchKernelGGL(trs_dagger_kernel, dim3((p.n + 255) / 256), dim3(256), 0, v.stream, p);
-        HIPCHK(hipGetLastError());
-        c->k += 1;                                           // the stats have moved: the counter moves with them
-        if (slot >= 0 && want_frames)                        // in front of the step: the frame fed is the handle's (latest frame, delay line, codec buffer)
-            HIPCHK(hipMemcpyAsync(cap->d_frames_or_null + (size_t)slot * e->img_bytes, fed, e->img_bytes, hipMemcpyDeviceToDevice, v.stream));
-        if (n_captured) *n_captured = plan.used;
-        rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
-        if (rc) return rc;
-    }
-    return TRS_OK;
+    DaggerOps ops{{{e, cap, {}}, c}, pilot_cfg, cfg};
+    return trsim::closed_loop(ops, n_steps, cap, &c->k, n_captured);
 }
 
 TRS_EXPORT int trs_dagger_stats(trs_env* e, float* h_out, const float** d_out, int reset)
 {
-    if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
-    ExpertCtx* c = ctx_of(e);
-    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no expert set (trs_set_expert)");
+    ExpertCtx* c;
+    if (int rc = enter(e, &c)) return rc;
     HIPCHK(hipSetDevice(e->device));
     const size_t bytes = (size_t)c->n * kDaggerStatFloats * sizeof(float);
     if (d_out) *d_out = c->stats.get();

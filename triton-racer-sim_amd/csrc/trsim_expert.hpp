@@ -1,9 +1,10 @@
 // trsim_expert.hpp — the host side of the scripted expert (include/trsim_spec.h, "scripted expert"): what trs_set_expert and trs_step_expert decide
 // before anything reaches the device.  Host-only and free of HIP headers, like trsim_post.hpp and trsim_pilot_plan.hpp: tests/expert_driver.cpp compiles it
 // with a plain host compiler under AddressSanitizer + UBSan.
-//   expert_config_error / expert_capture_error   the refusals of the two calls (nullptr: accepted)
+//   expert_config_error                          the refusals of trs_set_expert (nullptr: accepted)
 //   build_track_yaw                              track_yaw[p] = (float)atan2(tx[p], tz[p]) in binary64 from the binary32 tangents
-//   CapturePlan                                  which ticks of a call are captured, and into which slot
+//   expert_capture_error, CapturePlan            trsim_loop.hpp (included here): the capture's refusals, which ticks of a call are captured and into
+//                                                which slot, and the tick loop that asks
 //   kExpertRow*                                  the layout of a record row
 // and of the pilot in the loop with the expert's labels (include/trsim_spec.h, "pilot in the loop with the expert's labels"; trs_step_dagger):
 //   dagger_defaults / dagger_config_error        the defaults and the refusals of trs_dagger_config (nullptr: accepted)
@@ -17,6 +18,7 @@
 
 #include "../../include/trsim.h"
 #include "../../include/trsim_spec.h"
+#include "trsim_loop.hpp"
 
 #if defined(__HIPCC__)
 #define TRS_HD __host__ __device__
@@ -53,41 +55,10 @@ inline const char* expert_config_error(const trs_expert_config* c, int n_points)
     return nullptr;
 }
 
-// why trs_step_expert refuses this capture on a handle with (render != 0) or without a camera (nullptr: it does not)
-inline const char* expert_capture_error(const trs_expert_capture* c, bool render)
-{
-    if (!c) return nullptr;                                  // no capture
-    if (c->struct_size != sizeof(trs_expert_capture)) return "trs_expert_capture.struct_size mismatch";
-    if (c->every < 1) return "trs_expert_capture.every < 1";
-    if (c->skip < 0) return "trs_expert_capture.skip < 0";
-    if (c->capacity < 0) return "trs_expert_capture.capacity < 0";
-    if (c->capacity > 0 && !c->d_rows) return "trs_expert_capture.d_rows is NULL";
-    if (c->d_frames_or_null && !render) return "frames asked of a handle without a camera (render == 0): only rows can be captured";
-    return nullptr;
-}
-
 inline void build_track_yaw(const float* tangent /* [n][2] (tx, tz) */, int n_points, float* out)
 {
     for (int p = 0; p < n_points; ++p) out[p] = (float)std::atan2((double)tangent[2 * p], (double)tangent[2 * p + 1]);
 }
-
-// The capture plan of ONE trs_step_expert call.  slot_for(k, frame_ready) is asked once per tick, in tick order, with the driver's counter k and whether
-// the frame of the state exists (or no frame is wanted): it returns the slot the tick is captured into and takes it, or -1.
-struct CapturePlan {
-    int every = 1, skip = 0, capacity = 0, used = 0;
-    static CapturePlan of(const trs_expert_capture* c)
-    {
-        CapturePlan p;
-        if (c) { p.every = c->every; p.skip = c->skip; p.capacity = c->capacity; }
-        return p;
-    }
-    bool due(uint32_t k) const { return k >= (uint32_t)skip && (k - (uint32_t)skip) % (uint32_t)every == 0; }
-    int slot_for(uint32_t k, bool frame_ready)
-    {
-        if (used >= capacity || !due(k) || !frame_ready) return -1;
-        return used++;
-    }
-};
 
 // ---- the keyed generator: SplitMix64 of (seed, key), as the synthetic control generator of include/trsim_spec.h states it ----
 TRS_HD inline uint64_t splitmix64(uint64_t seed, uint64_t key)

@@ -1500,6 +1500,12 @@ int trs_internal_step_launch(trs_env* e, const float* d_st, const float* d_th, c
     if (!rc) trsim::resident_note_launch(e);               // resident mode selected: this step has no completion flag, trs_sync / the copies wait for the stream
     return rc;
 }
+// a closed loop keeps the frame of a captured tick: in front of the step, the handle recycles the buffer two steps on
+int TrsLoopOps::keep_frame(int slot, const uint8_t* frame)
+{
+    HIPCHK(hipMemcpyAsync(cap->d_frames_or_null + (size_t)slot * e->img_bytes, frame, e->img_bytes, hipMemcpyDeviceToDevice, v.stream));
+    return TRS_OK;
+}
 int trs_internal_replay_launch(trs_env* e, const trsim::Controls& c, uint64_t step)
 {
     return e->cfg.render ? launch_step(e, c, 1, 0, 0, step) : launch_physics(e, c, 1, step);

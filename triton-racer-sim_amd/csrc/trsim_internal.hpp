@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/trsim.h"
+#include "trsim_loop.hpp"             // the tick loop the closed loops below are run through (host-only)
 
 #define TRS_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -56,11 +57,25 @@ int trs_internal_replay_launch(trs_env* e, const trsim::Controls& c, uint64_t st
 void trs_internal_note(const std::string& msg);            // what trs_last_error() returns, without failing the call
 void trs_internal_count(trs_env* e, uint64_t d2h_bytes, uint64_t h2d_bytes);   // trs_counters bookkeeping for copies made outside trsim_hip.hip
 void trs_pilot_free(void* ctx);       // defined in trsim_pilot.hip, called by trs_destroy
-// The two halves of trs_step_pilot that trs_step_dagger (trsim_expert.hip) shares with it, defined in trsim_pilot.hip.
+// ---- the closed loops: trs_step_pilot (trsim_pilot.hip), trs_step_expert and trs_step_dagger (trsim_expert.hip) ----
+// Each is its argument checks and a small ops object handed to trsim::closed_loop (trsim_loop.hpp), where the order of a tick is written down.
+// The view of one tick: trs_internal_view, which asks a resident worker to leave the handle's stream; at most once per tick.
+inline int trs_internal_tick_view(trs_env* e, TrsEnvView* v)
+{
+    return trs_internal_view(e, v) ? TRS_OK : trs_internal_fail(TRS_ERR_DEVICE, "the handle's stream could not be taken over from the resident worker");
+}
+// what the ops of every loop share: the handle, the call's capture (or nullptr), the view of the current tick (observe refreshes it) and the two ops that
+// do not depend on who drives
+struct TrsLoopOps {
+    trs_env* e; const trs_expert_capture* cap; TrsEnvView v;
+    int keep_frame(int slot, const uint8_t* frame);         // device to device into the capture's slot, on the view's stream (trsim_hip.hip: the size is the handle's)
+    int step() { return trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk); }
+};
+// The pilot's part, defined in trsim_pilot.hip, that trs_step_dagger shares with trs_step_pilot.
 // trs_internal_pilot_loop_check: what the closed loop refuses before its first tick (no pilot, cfg, n_steps, model type, no camera); TRS_OK or the failed code.
-// trs_internal_pilot_tick: one tick up to, not including, the env step.  Refreshes *v, chooses the frame the pilot reads today (the latest one; the delayed
-// one under an observation latency, with that observation's speed, segment and mode mask), puts it through the camera codec when one is set, and runs the
-// pilot into the handle's control arrays (v->ctl_*) — or writes zero controls when no frame exists yet.  *fed: the frame that was fed (nullptr: none).
+// trs_internal_pilot_tick: the `observe` of both loops.  Refreshes *v (trs_internal_tick_view), chooses the frame the pilot reads today (the latest one; the
+// delayed one under an observation latency, with that observation's speed, segment and mode mask), puts it through the camera codec when one is set, and runs
+// the pilot into the handle's control arrays (v->ctl_*) — or writes zero controls when no frame exists yet.  *fed: the frame that was fed (nullptr: none).
 int trs_internal_pilot_loop_check(trs_env* e, const trs_pilot_config* cfg, int n_steps);
 int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView* v, const uint8_t** fed);
 void trs_expert_free(void* ctx);      // defined in trsim_expert.hip, called by trs_destroy and by trs_load_track (a new track switches the expert off); nullptr is fine

@@ -1399,7 +1399,7 @@ int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView*
 {
     TrsEnvView& v = *view;
     PilotCtx* const c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    trs_internal_view(e, &v);
+    if (int rc = trs_internal_tick_view(e, &v)) return rc;
     const uint8_t* seen = v.obs_on ? v.obs_frame : v.latest_frame;      // the frame the pilot reads today (nullptr: none yet)
     if (seen && v.codec_quality) {              // a camera codec is set: the pilot reads codec(that frame), as the reference's pilot reads decoded JPEGs
         int rc = trs_internal_camera_codec(e, seen, &seen);
@@ -1417,11 +1417,10 @@ int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView*
 TRS_EXPORT int trs_step_pilot(trs_env* e, const trs_pilot_config* cfg, int n_steps)
 {
     if (int rc = trs_internal_pilot_loop_check(e, cfg, n_steps)) return rc;
-    for (int k = 0; k < n_steps; ++k) {
-        TrsEnvView v; const uint8_t* fed;
-        int rc = trs_internal_pilot_tick(e, cfg, &v, &fed);
-        if (!rc) rc = trs_internal_step_launch(e, v.ctl_steer, v.ctl_thr, v.ctl_brk);
-        if (rc) return rc;
-    }
-    return TRS_OK;
+    struct Ops : TrsLoopOps {
+        const trs_pilot_config* cfg;
+        int observe(const uint8_t** fed) { return trs_internal_pilot_tick(e, cfg, &v, fed); }
+        int label(int) { return TRS_OK; }                   // the pilot's controls are the applied ones
+    } ops{{e, nullptr, {}}, cfg};
+    return trsim::closed_loop(ops, n_steps, nullptr, nullptr, nullptr);   // no driver, no capture
 }
