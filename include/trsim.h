@@ -685,6 +685,36 @@ int trs_sample_batch(trs_env* env, const trs_loader_config* cfg, const uint8_t* 
                      int batch, void* d_images_or_null, float* d_features_or_null, float* d_labels, int32_t* d_index_or_null);
 int trs_loader_order(const trs_loader_config* cfg, int split, int epoch, int first, int count, int32_t* h_index);
 
+/* ---- training minibatches, augmentation: mirror and colour jitter inside the gather (include/trsim_spec.h, "training minibatches, augmentation") ----
+ * A record is varied between epochs without another pass over the batch: mirrored left to right with its steering label negated, and lit again by the
+ * scene-lighting rule (light_channel, rule R1) with a gain and a bias per record.  The draws are keyed by (aug.seed, epoch, record number), not by the
+ * batch slot: reproducible, the same in every shard, and readable on the host.
+ *   trs_default_augment_config: everything off (mirror_prob, gain_amp, bias_amp = 0).
+ *   trs_sample_batch_aug: trs_sample_batch with the augmentation applied by the same single launch.  It replaces the torch passes a user runs behind the
+ *     plain batch today (flip where flagged, x * gain + bias, clamp, the label's sign).  aug NULL, or a config that is off, launches trs_batch_kernel as
+ *     trs_sample_batch does: the same bytes at the same cost.  Otherwise ONE launch of trs_batch_aug_kernel: every frame byte x becomes
+ *     light_channel(x, gain_c, bias_c) before the conversion of cfg.dtype, a mirrored record has out[y][x] = lit[y][W - 1 - x] in every channel and the
+ *     sign bit of its label[0] flipped; label[1], the features, d_index and the order are trs_sample_batch's.  A physics-only set gets the label rule alone.
+ *     TRS_ERR_ARG, nothing written: every refusal of trs_sample_batch; aug.struct_size; mirror_prob outside [0, 1], gain_amp outside [0, 1), bias_amp
+ *     outside [0, 255] (a NaN is outside); per_channel not 0 or 1; mirror_prob > 0 with TRS_LOADER_FULL_HOUSE (loc/segment is a position on the track as
+ *     driven).
+ *   trs_loader_augment: what positions first .. first + count - 1 of (split, epoch) get, on the host without a GPU or a handle, like trs_loader_order —
+ *     it replaces reading the draws back from a batch: h_index (may be NULL) the record numbers, h_mirror[count] 0 / 1, h_params[count][8] =
+ *     {gR gG gB 0 bR bG bB 0}, the layout of trs_set_lighting.  The refusals of trs_loader_order and those of aug above; aug must not be NULL. */
+typedef struct trs_augment_config {
+    uint32_t struct_size;
+    float    mirror_prob;            /* 0: the probability that a record is mirrored */
+    float    gain_amp, bias_amp;     /* 0, 0: gain_c = 1 + f * gain_amp, bias_c = f * bias_amp, f drawn from [-1, 1) */
+    int32_t  per_channel;            /* 0: one gain and one bias for R, G and B; 1: one per channel */
+    uint64_t seed;                   /* 0: the seed of the draws (independent of trs_loader_config.seed) */
+} trs_augment_config;
+void trs_default_augment_config(trs_augment_config* aug);
+int trs_sample_batch_aug(trs_env* env, const trs_loader_config* cfg, const trs_augment_config* aug_or_null, const uint8_t* d_frames_or_null,
+                         const float* d_rows, int split, int epoch, int first, int batch, void* d_images_or_null, float* d_features_or_null,
+                         float* d_labels, int32_t* d_index_or_null);
+int trs_loader_augment(const trs_loader_config* cfg, const trs_augment_config* aug, int split, int epoch, int first, int count, int32_t* h_index_or_null,
+                       uint8_t* h_mirror, float* h_params);
+
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no
  * distributed layer at all; this replaces what a user would otherwise script around N copies of manage.py.

@@ -332,6 +332,34 @@
  *       full_house      (s20, row[6])       (steer, s20)
  *   tests/test_loader_cpu.py restates the paragraph in numpy and compares trs_loader_order with it; tests/test_loader_gpu.py compares trs_batch_kernel
  *   with that restatement bit for bit; csrc/trsim_loader.hpp is the one place the kernel and the host take the rules from.
+ *
+ * ---- training minibatches, augmentation (trs_sample_batch_aug, trs_loader_augment; HIP library only)
+ *   A record of a minibatch is mirrored left to right and lit again, by draws that are a function of (aug.seed, epoch, record number) alone: not of the
+ *   batch slot, the batch size, `first` or the split the record sits in.  Unsigned 64-bit arithmetic (mod 2^64) and single binary32 IEEE operations only;
+ *   mix is the function of "training minibatches".
+ *     A        = mix(aug.seed ^ 0x6175676D656E7421)
+ *     k(e, r)  = mix(A ^ (((uint64)e << 32) | r))           e >= 0 the epoch, r the record number (what d_index reports)
+ *     d_j      = mix(k + j) >> 40                            j = 0 .. 6, 24 bits each
+ *     mirror   = d_0 < T,  T = (uint32)((double)mirror_prob * 16777216.0)       (mirror_prob 1: always; 0: never)
+ *     f_j      = (float)d_j * 0x1p-23f - 1.0f                exact, in [-1, 1)
+ *     gain_c   = 1.0f + f_(1+c) * gain_amp                   two roundings: the product, then the sum (no fused multiply-add)
+ *     bias_c   = f_(4+c) * bias_amp                          c = 0, 1, 2 = R, G, B
+ *     per_channel == 0:  gain_c = gain_0 and bias_c = bias_0 for every c (draws j = 1 and j = 4 only)
+ *   Pixel.   Every byte x of channel c of the record's frame becomes light_channel(x, gain_c, bias_c) first: rule R1 of "scene lighting", verbatim, the
+ *            one shared function.  The conversion of "training minibatches" (float32, binary16 or the byte) follows.
+ *   Mirror.  On a mirrored record, for every channel, out[y][x] = lit[y][W - 1 - x].  (The class map is a function of the distance to the centre line
+ *            and the arc length, and the pinhole camera has no roll: the mirror image of a frame is the frame of the mirrored track.)
+ *   Label.   On a mirrored record label[0] (whichever steering cfg.label selects) has its sign bit flipped: 0.0f becomes -0.0f.
+ *   label[1], the features, d_index and the order are unchanged; a physics-only set gets the label rule alone.
+ *   Refused: mirror_prob outside [0, 1], gain_amp outside [0, 1) (the gain stays positive), bias_amp outside [0, 255] (a NaN is outside),
+ *   per_channel not 0 or 1, mirror_prob > 0 with the full_house loader (row[6] is a position on the track as driven).
+ *   Off (mirror_prob == 0, gain_amp == 0, bias_amp == 0, or no config): trs_sample_batch itself.
+ *   Test vectors, seed 0, epoch 0, record 0:  d_0..6 = 11521308 2773027 14270921 1147758 4524845 10059823 8999555;  mirror_prob 0.5: not mirrored;
+ *     gain_amp 0.25: gains 3f552812 3f967072 3f48c1b7;  bias_amp 32: biases c16bd34c 40cc0178 40152830 (bit patterns).
+ *     Mirror flags of records 0..11 at mirror_prob 0.5, seed 0:  epoch 0: 0 1 1 0 0 0 0 0 0 1 1 0;  epoch 1: 1 0 1 0 0 1 1 0 1 0 0 0.
+ *     Mirrored among records 0..4095 at 0.5, epochs 0, 1, 7:  seed 0: 2068 1996 2052;  seed 1: 2081 2042 2019;  seed 12345: 1984 2068 2001.
+ *   tests/test_augment_cpu.py restates the paragraph in numpy and compares trs_loader_augment with it; tests/test_augment_gpu.py compares
+ *   trs_batch_aug_kernel with that restatement bit for bit; csrc/trsim_augment.hpp is the one place the kernel and the host take the draw from.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

@@ -5,7 +5,7 @@ Nothing here imports the CPU oracle; without the built HIP extension the env con
 """
 __version__ = "0.1.0"
 
-__all__ = ["BatchedEnv", "HipGymInterface", "BatchedGymInterface", "LocationTracker", "Component", "DataPool", "Car", "Profiler"]
+__all__ = ["BatchedEnv", "HipGymInterface", "BatchedGymInterface", "LocationTracker", "Component", "DataPool", "Car", "Profiler", "Augment", "DeviceDataset"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need numpy/ctypes side effects
@@ -18,4 +18,7 @@ def __getattr__(name):  # lazy: importing the package must not need numpy/ctypes
     if name in ("Component", "DataPool", "Car", "Profiler"):
         from . import core
         return getattr(core, name)
+    if name in ("Augment", "DeviceDataset"):
+        from . import dataset
+        return getattr(dataset, name)
     raise AttributeError(name)

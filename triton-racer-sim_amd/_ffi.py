@@ -148,6 +148,14 @@ class TrsLoaderConfig(C.Structure):
     ]
 
 
+class TrsAugmentConfig(C.Structure):
+    """``trs_augment_config`` (include/trsim.h): the mirror and colour jitter ``trs_sample_batch_aug`` applies inside the gather."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("mirror_prob", C.c_float), ("gain_amp", C.c_float), ("bias_amp", C.c_float), ("per_channel", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
 LOADER_TYPES = {"speed_ctl": 0, "default": 1, "speed_feature": 2, "full_house": 3}   # TRS_LOADER_*; the names of recorder.LOADERS, in the order of TRS_PILOT_*
 LOADER_FEATURES = {"speed_ctl": 0, "default": 0, "speed_feature": 1, "full_house": 2}
 LOADER_LABELS = {"expert": 0, "applied": 1}                             # TRS_LABEL_*
@@ -196,12 +204,15 @@ EXPERT_SYMBOLS = ["default_expert_config", "set_expert", "expert_act", "step_exp
 # HIP library only: the training minibatches (trs_sample_batch, trs_loader_order) — their checker is the numpy restatement of include/trsim_spec.h
 # ("training minibatches") in tests/test_loader_cpu.py (tests/test_loader_gpu.py compares the kernel with the restatement bit for bit)
 LOADER_SYMBOLS = ["default_loader_config", "sample_batch", "loader_order"]
+# HIP library only: the augmented minibatches (trs_sample_batch_aug, trs_loader_augment) — their checker is the numpy restatement of include/trsim_spec.h
+# ("training minibatches, augmentation") in tests/test_augment_cpu.py (tests/test_augment_gpu.py compares the kernel with the restatement bit for bit)
+AUGMENT_SYMBOLS = ["default_augment_config", "sample_batch_aug", "loader_augment"]
 # HIP library only: the pilot in the loop with the expert's labels (trs_step_dagger) — its checker is the numpy restatement of include/trsim_spec.h ("pilot
 # in the loop with the expert's labels") in tests/test_dagger_cpu.py composed with the existing calls (tests/test_dagger_gpu.py, bit for bit)
 DAGGER_SYMBOLS = ["default_dagger_config", "step_dagger", "dagger_stats"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -321,6 +332,11 @@ class Api:
             "step_dagger": (i32, [vp, C.POINTER(TrsPilotConfig), C.POINTER(TrsDaggerConfig), i32, C.POINTER(TrsExpertCapture), C.POINTER(i32)]),
             "dagger_stats": (i32, [vp, vp, C.POINTER(vp), i32]),
         }
+        augment = {
+            "default_augment_config": (None, [C.POINTER(TrsAugmentConfig)]),
+            "sample_batch_aug": (i32, [vp, C.POINTER(TrsLoaderConfig), C.POINTER(TrsAugmentConfig), vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+            "loader_augment": (i32, [C.POINTER(TrsLoaderConfig), C.POINTER(TrsAugmentConfig), i32, i32, i32, i32, vp, vp, vp]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -383,6 +399,12 @@ class Api:
         self.has_dagger = hasattr(cdll, prefix + "step_dagger")
         if self.has_dagger:
             for name, (res, args) in dagger.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_augment = hasattr(cdll, prefix + "sample_batch_aug")
+        if self.has_augment:
+            for name, (res, args) in augment.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -22,46 +22,12 @@
 #include "../../include/trsim.h"
 #include "trsim_env.hpp"
 #include "trsim_internal.hpp"
+#include "trsim_batch.hpp"
 #include "trsim_loader.hpp"
 
 namespace {
 
-constexpr int kBatchBlock = 256, kBatchUnroll = 4, kUnitsPerItem = kBatchBlock * kBatchUnroll;
-
-struct BatchParams {
-    const uint32_t* frames;             // the set's frames as dwords, or nullptr (physics-only set)
-    const float* rows;
-    void* images; float* features; float* labels; int32_t* index;
-    trsim::Order order;
-    uint32_t first, batch;
-    int loader, label, n_feat;
-    uint32_t frame_dwords, quads;       // H * W * 3 / 4 and H * W / 4
-    uint32_t units, chunks;             // units of a frame in this layout, and items per slot
-    uint32_t items;                     // batch * chunks
-};
-
-__device__ __forceinline__ float unit8(uint32_t v) { return trsim::unit255(v); }
-
-// three and four dwords of a frame in one load (and, for uint8 output, one store): the address is a multiple of 4 and no more
-typedef uint32_t dwords3_t __attribute__((ext_vector_type(3)));
-typedef uint32_t dwords4_t __attribute__((ext_vector_type(4)));
-typedef dwords3_t __attribute__((aligned(4))) dwords3_a4;
-typedef dwords4_t __attribute__((aligned(4))) dwords4_a4;
-__device__ __forceinline__ uint32_t byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 255u; }
-__device__ __forceinline__ uint32_t half_bits(float f) { return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)f); }   // round to nearest even
-__device__ __forceinline__ uint2 halves4(float a, float b, float c, float d)
-{
-    return make_uint2(half_bits(a) | (half_bits(b) << 16), half_bits(c) | (half_bits(d) << 16));
-}
-
-// four values of one unit, in output order, to element e of an array of 4-element groups
-template <int DTYPE>
-__device__ __forceinline__ void store4(void* base, size_t e, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3)
-{
-    if (DTYPE == TRS_DTYPE_F32) static_cast<float4*>(base)[e] = make_float4(unit8(b0), unit8(b1), unit8(b2), unit8(b3));
-    else if (DTYPE == TRS_DTYPE_F16) static_cast<uint2*>(base)[e] = halves4(unit8(b0), unit8(b1), unit8(b2), unit8(b3));
-    else static_cast<uint32_t*>(base)[e] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
-}
+using namespace trsim;                 // trsim_batch.hpp: BatchParams, the 4-byte-aligned wide types, store4
 
 template <int LAYOUT, int DTYPE>
 __global__ __launch_bounds__(kBatchBlock) void trs_batch_kernel(const BatchParams p)
@@ -123,17 +89,21 @@ TRS_EXPORT int trs_loader_order(const trs_loader_config* cfg, int split, int epo
     return TRS_OK;
 }
 
-TRS_EXPORT int trs_sample_batch(trs_env* e, const trs_loader_config* cfg, const uint8_t* d_frames, const float* d_rows, int split, int epoch, int first,
-                                int batch, void* d_images, float* d_features, float* d_labels, int32_t* d_index)
+// The one path of trs_sample_batch and trs_sample_batch_aug: the refusals, the work items, one launch.  No augmentation (aug == nullptr or everything
+// off) launches trs_batch_kernel; otherwise trs_batch_aug_kernel (trsim_augment.hip), whose unit is four pixels in every layout.
+int trsim::sample_batch(trs_env* e, const trs_loader_config* cfg, const trs_augment_config* aug, const uint8_t* d_frames, const float* d_rows, int split,
+                        int epoch, int first, int batch, void* d_images, float* d_features, float* d_labels, int32_t* d_index)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     if (const char* why = trsim::loader_config_error(cfg)) return trs_internal_fail(TRS_ERR_ARG, why);
     if (const char* why = trsim::loader_range_error(cfg, split, epoch, first, batch)) return trs_internal_fail(TRS_ERR_ARG, why);
+    if (aug) if (const char* why = trsim::augment_config_error(aug, cfg)) return trs_internal_fail(TRS_ERR_ARG, why);
     const trsim::LoaderCall call{d_frames, d_rows, d_images, d_features, d_labels, d_index, e->cfg.render != 0};
     if (const char* why = trsim::loader_call_error(cfg, call)) return trs_internal_fail(TRS_ERR_ARG, why);
     HIPCHK(hipSetDevice(e->device));
     if (batch == 0) return TRS_OK;
     { int rq = trsim::quiesce_handle(e); if (rq) return rq; }
+    const bool plain = trsim::augment_is_off(aug);
     BatchParams p{};
     p.frames = reinterpret_cast<const uint32_t*>(d_frames); p.rows = d_rows;
     p.images = d_images; p.features = d_features; p.labels = d_labels; p.index = d_index;
@@ -142,13 +112,11 @@ TRS_EXPORT int trs_sample_batch(trs_env* e, const trs_loader_config* cfg, const 
     p.loader = cfg->loader; p.label = cfg->label; p.n_feat = trsim::loader_features(cfg->loader);
     p.quads = (uint32_t)((size_t)e->H * e->W / 4);                        // W % 4 == 0 -> whole groups of four pixels
     p.frame_dwords = 3 * p.quads;
-    p.units = cfg->layout == TRS_LAYOUT_NCHW ? p.quads : cfg->dtype == TRS_DTYPE_U8 ? (p.frame_dwords + 3) / 4 : p.frame_dwords;
-    p.chunks = d_frames ? (p.units + kUnitsPerItem - 1) / kUnitsPerItem : 1;
-    const size_t items = (size_t)batch * p.chunks;
-    if (items > 0x7FFFFFFFu) return trs_internal_fail(TRS_ERR_LIMIT, "batch x frame size beyond 2^31 work items");
-    p.items = (uint32_t)items;
-    const int grid = (int)std::min<size_t>(items, (size_t)e->cu_count * 16);
-    if (cfg->layout == TRS_LAYOUT_NHWC) {
+    const uint32_t units = !plain || cfg->layout == TRS_LAYOUT_NCHW ? p.quads : cfg->dtype == TRS_DTYPE_U8 ? (p.frame_dwords + 3) / 4 : p.frame_dwords;
+    if (!trsim::batch_items(p, units)) return trs_internal_fail(TRS_ERR_LIMIT, "batch x frame size beyond 2^31 work items");
+    const int grid = (int)std::min<size_t>(p.items, (size_t)e->cu_count * 16);
+    if (!plain) trsim::launch_batch_aug(e, p, trsim::AugKey::of(*aug, epoch), (uint32_t)(e->W / 4), cfg->layout, cfg->dtype, grid);
+    else if (cfg->layout == TRS_LAYOUT_NHWC) {
         if (cfg->dtype == TRS_DTYPE_F32) launch_batch<TRS_LAYOUT_NHWC, TRS_DTYPE_F32>(e, p, grid);
         else if (cfg->dtype == TRS_DTYPE_F16) launch_batch<TRS_LAYOUT_NHWC, TRS_DTYPE_F16>(e, p, grid);
         else launch_batch<TRS_LAYOUT_NHWC, TRS_DTYPE_U8>(e, p, grid);
@@ -159,4 +127,10 @@ TRS_EXPORT int trs_sample_batch(trs_env* e, const trs_loader_config* cfg, const 
     HIPCHK(hipGetLastError());
     trsim::resident_note_launch(e);                       // resident mode selected: this kernel has no completion flag, trs_sync waits for the stream
     return TRS_OK;
+}
+
+TRS_EXPORT int trs_sample_batch(trs_env* e, const trs_loader_config* cfg, const uint8_t* d_frames, const float* d_rows, int split, int epoch, int first,
+                                int batch, void* d_images, float* d_features, float* d_labels, int32_t* d_index)
+{
+    return trsim::sample_batch(e, cfg, nullptr, d_frames, d_rows, split, epoch, first, batch, d_images, d_features, d_labels, d_index);
 }

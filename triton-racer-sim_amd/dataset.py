@@ -15,6 +15,56 @@ def _ptr(t):
     return int(t.data_ptr()) or None
 
 
+_HOST_API = []
+
+
+def _host_api():
+    """The library's function table for the calls that need no device and no handle (opened once)."""
+    if not _HOST_API:
+        _HOST_API.append(_ffi.load_hip_library())
+    return _HOST_API[0]
+
+
+class Augment:
+    """Mirror and colour jitter of a training minibatch, applied inside the gather (``trs_sample_batch_aug``; include/trsim_spec.h, "training
+    minibatches, augmentation").  ``mirror``: the probability that a record is mirrored left to right, its steering label negated.  ``gain`` in
+    [0, 1) and ``bias`` in [0, 255]: the record is lit again by the scene-lighting rule with ``gain_c = 1 + f * gain`` and ``bias_c = f * bias``,
+    ``f`` drawn from [-1, 1) — one pair for the three channels, or with ``per_channel`` one per channel.  The draws are keyed by ``(seed, epoch,
+    record number)``: reproducible, and readable on the host (``DeviceDataset.augmentation``).  The library's own refusals validate the values
+    (``trs_loader_augment``: host arithmetic, no GPU); the one about the ``full_house`` loader is made where a dataset is known."""
+
+    __slots__ = ("mirror", "gain", "bias", "per_channel", "seed")
+
+    def __init__(self, mirror=0.0, gain=0.0, bias=0.0, per_channel=False, seed=0, _api=None):
+        for name, value in (("mirror", float(mirror)), ("gain", float(gain)), ("bias", float(bias)), ("per_channel", bool(per_channel)), ("seed", int(seed))):
+            object.__setattr__(self, name, value)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must lie in [0, 2^64)")
+        api = _api if _api is not None else _host_api()
+        cfg = _ffi.TrsLoaderConfig()
+        api.default_loader_config(C.byref(cfg))
+        if api.loader_augment(C.byref(cfg), C.byref(self.config(api)), 0, 0, 0, 0, None, None, None) != 0:
+            raise ValueError((api.last_error() or b"").decode())
+
+    def __setattr__(self, name, value):
+        raise AttributeError("an Augment is a value: make another one")
+
+    def __repr__(self):
+        return f"Augment(mirror={self.mirror}, gain={self.gain}, bias={self.bias}, per_channel={self.per_channel}, seed={self.seed})"
+
+    def __eq__(self, other):
+        return isinstance(other, Augment) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    def config(self, api):
+        a = _ffi.TrsAugmentConfig()
+        api.default_augment_config(C.byref(a))
+        a.mirror_prob, a.gain_amp, a.bias_amp, a.per_channel, a.seed = self.mirror, self.gain, self.bias, int(self.per_channel), self.seed
+        return a
+
+
 class DeviceDataset:
     """``frames uint8[capacity, H, W, 3]`` (``None`` for a physics-only set) and ``rows float32[capacity, 8]`` (``_ffi.EXPERT_ROW``) in torch device
     storage the dataset owns, of which the first ``len(self)`` records are filled.  ``sigma = perm(mix(seed), n, .)`` splits them: ``n_train =
@@ -162,14 +212,31 @@ class DeviceDataset:
         index = torch.empty((batch_size,), dtype=torch.int32, device=self.device)
         return images, feats, labels, index
 
-    def sample(self, cfg, split, epoch, first, batch, images, feats, labels, index=None):
-        """One ``trs_sample_batch`` into torch tensors, asynchronous on the env's stream."""
+    def augmentation(self, augment, split="train", epoch=0, first=0, count=None):
+        """What ``batches(..., augment=augment)`` does to positions ``first .. first + count - 1`` of an epoch of a split (``count=None``: to the end
+        of the split): ``(index int32[count], mirror bool[count], params float32[count, 8])``, the record numbers, the mirror flags and ``{gR gG gB 0
+        bR bG bB 0}`` per record (``trs_loader_augment``: host arithmetic, no GPU work)."""
+        count = self._n_split(split) - int(first) if count is None else int(count)
+        index, mirror, params = np.empty(max(count, 0), np.int32), np.empty(max(count, 0), np.uint8), np.empty((max(count, 0), 8), np.float32)
+        c, a = self.config("nhwc"), augment.config(self.env.api)
+        self.env.api.check(self.env.api.loader_augment(C.byref(c), C.byref(a), _ffi.LOADER_SPLITS[split], int(epoch), int(first), count, index.ctypes.data,
+                                                       mirror.ctypes.data, params.ctypes.data), "loader_augment")
+        return index, mirror.astype(bool), params
+
+    def sample(self, cfg, split, epoch, first, batch, images, feats, labels, index=None, augment=None):
+        """One ``trs_sample_batch`` (``augment``: one ``trs_sample_batch_aug``) into torch tensors, asynchronous on the env's stream."""
+        if augment is not None:
+            self.env.api.check(self.env.api.sample_batch_aug(
+                self.env._h, C.byref(cfg), C.byref(augment.config(self.env.api)), _ptr(self.frames) if self.with_frames else None, _ptr(self.rows),
+                _ffi.LOADER_SPLITS[split], int(epoch), int(first), int(batch), None if images is None else _ptr(images),
+                _ptr(feats) if feats.numel() else None, _ptr(labels), None if index is None else _ptr(index)), "sample_batch_aug")
+            return
         self.env.api.check(self.env.api.sample_batch(
             self.env._h, C.byref(cfg), _ptr(self.frames) if self.with_frames else None, _ptr(self.rows), _ffi.LOADER_SPLITS[split], int(epoch), int(first),
             int(batch), None if images is None else _ptr(images), _ptr(feats) if feats.numel() else None, _ptr(labels), None if index is None else _ptr(index)),
             "sample_batch")
 
-    def batches(self, batch_size, epoch, split="train", layout="nchw", dtype="float32", stream=None):
+    def batches(self, batch_size, epoch, split="train", layout="nchw", dtype="float32", stream=None, augment=None):
         """Iterator over the ``floor(n_split / batch_size)`` minibatches of an epoch (``drop_remainder``): ``(images, features, labels)`` torch
         tensors — ``images`` in ``layout`` / ``dtype`` (``None`` for a physics-only set), ``features float32[B, F]`` (F = 0 for the loaders without
         features), ``labels float32[B, 2]``.  Three sets of buffers rotate: batch t + 1 is gathered while t is consumed, and the request for batch t + 1
@@ -177,8 +244,12 @@ class DeviceDataset:
         read from the host, across the request for t + 1).  Ordering as for ``device_array``: with ``stream=`` (the CONSUMER's stream) that stream
         waits for the gather and the host does not; otherwise the host waits for each batch.  A gather waits for the work the consumer's stream held
         when it was launched, i.e. for everything queued on a batch before the next is requested.  The buffers are allocated on the consumer's
-        stream, so torch's allocator hands them on only behind that stream's reads."""
+        stream, so torch's allocator hands them on only behind that stream's reads.  ``augment``: an ``Augment`` — the records of this split are
+        mirrored and lit again inside the gather, by draws keyed with ``epoch`` and the record number (``augmentation`` reports them); pass it for
+        ``"train"`` only, validation measures the frames as collected.  ``None``: the plain gather."""
         torch = self.torch
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError("augment must be an Augment or None")
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("batch_size >= 1 is required")
@@ -192,7 +263,7 @@ class DeviceDataset:
 
         def gather(t):
             self._env_after_torch(stream)
-            self.sample(cfg, split, epoch, t * batch_size, batch_size, *bufs[t % 3])
+            self.sample(cfg, split, epoch, t * batch_size, batch_size, *bufs[t % 3], augment=augment)
 
         if n_batches:
             gather(0)
@@ -209,7 +280,7 @@ class DeviceDataset:
         """Mean squared error of the loaded HIP pilot (``pilot_load``; ``trs_pilot_forward_ex`` on uint8 minibatches) against the labels, over the
         ``floor(n_split / batch_size)`` batches of the split: the ``val_loss`` the reference's ``ModelCheckpoint`` watches
         (``components/keras_train.py:406-408``), of the fp16 pilot as it will drive.  ``batch_size``: at most ``n_envs``, what the pilot's buffers hold
-        (``None``: ``n_envs``, or the whole split when that is smaller).  Returns a Python float."""
+        (``None``: ``n_envs``, or the whole split when that is smaller).  Never augmented: the loss is of the frames as collected.  Returns a Python float."""
         if not self.with_frames:
             raise RuntimeError("a physics-only set has no frames for the pilot")
         torch = self.torch
