@@ -10,7 +10,9 @@ stores activations as fp16 (round 3; bfloat16 until round 2 — the same MFMA ra
   * "pure": fp32 everywhere (what TensorFlow would compute): tolerance 4e-4 on the two outputs — measured: max |HIP - fp32| 4.4e-5 over
     288 frames x 3 weight sets at both frame sizes (scripts/pilot_precision.py, profiles/r03_pilot_precision.txt; 5.0e-4 with bfloat16).
 The cases here run the default plans of 120x160, 240x320, 100x132 and 130x300 and their tuned-off neighbours.  The generic fallback (trs_conv_lt_kernel, the quad-load
-kernel: never reached by these plans) and the default plans of 360x480, 480x640 and of frames 96 and 100 wide have their tests in tests/test_pilot_fallback.py."""
+kernel: never reached by these plans) and the default plans of 360x480, 480x640 and of frames 96 and 100 wide have their tests in tests/test_pilot_fallback.py.
+The outputs here come from 8 K slices of dense1 (120x160) or 123 (240x320), and test_dense_kernel_against_torch_in_both_frame_groupings reads dense1 through a getter
+that adds the slabs on the host: the other slice counts, through the tail kernels that add the slabs on the device, are in tests/test_pilot_slices.py."""
 import math
 import types
 

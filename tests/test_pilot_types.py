@@ -4,7 +4,10 @@
 of those architectures with seeded random weights (no model file ships; TensorFlow is absent): conv stack as in
 tests/test_pilot.py, the small dense branches and both heads in fp32.  Tolerances as for cnn_2d_speed_control: the two outputs
 within 1e-3 of fp32-everywhere (the fp16 effect of the conv stack; 5e-2 in the bfloat16 rounds), and within 5e-4 of a reference whose conv stack is the
-kernel's own conv7 activation (everything behind it is fp32 on both sides)."""
+kernel's own conv7 activation (everything behind it is fp32 on both sides).
+The forward passes here are 6 frames in 8 K slices: one frame group, whole groups of 8 in trs_pilot_tail_ex_kernel.  Its remainder loop, dense4 with several frame
+groups and 64 frames per workgroup, and a batch change on one handle are in tests/test_pilot_slices.py, which uses make_named_weights and torch_heads from here
+(hence their cnn_2d_speed_control branch and torch_heads' ``flat``)."""
 import math
 
 import numpy as np
@@ -29,7 +32,10 @@ def make_named_weights(h, w, kind, seed=0):
     for k, s, _, _ in SPEC:
         ih, iw = (ih - k) // s + 1, (iw - k) // s + 1
     F = ih * iw * 128
-    if kind == "cnn_2d_speed_as_feature":
+    if kind == "cnn_2d_speed_control":                                # no extra input: tests/test_pilot_slices.py runs all three types through one reference
+        named["dense1"] = dense_init(rng, F, 100)
+        named["dense2"], named["dense3"], named["output_layer"] = dense_init(rng, 100, 50), dense_init(rng, 50, 25), dense_init(rng, 25, 2)
+    elif kind == "cnn_2d_speed_as_feature":
         f = (4, 8, 16)
         named["feature1"], named["feature2"], named["feature3"] = dense_init(rng, 1, f[0]), dense_init(rng, f[0], f[1]), dense_init(rng, f[1], f[2])
         named["dense1"] = dense_init(rng, F + f[2], 100)
@@ -50,22 +56,29 @@ def make_named_weights(h, w, kind, seed=0):
     return named, F
 
 
-def torch_heads(x_flat, speed, segment, named, kind, h16_dense=False):
+def torch_heads(x_flat, speed, segment, named, kind, h16_dense=False, flat=None):
     """Everything behind the flatten, fp32 (with ``h16_dense`` the flatten rows of dense1 / dense4 and x are rounded to fp16, as the
-    matrix-core path does)."""
+    matrix-core path does).  ``flat``: {"dense1": float32[n, 100] (, "dense4": ...)}, the products of the flatten with the flatten rows worked out by the
+    caller (tests/test_pilot_slices.py: in binary64, slice by slice, with a slice left out), used in place of x @ k[:F]; ``x_flat`` is not read then."""
     import torch
     import torch.nn.functional as Fn
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
     lin = lambda z, nm, act=True: (Fn.relu(z @ t(named[nm][0]) + t(named[nm][1])) if act else z @ t(named[nm][0]) + t(named[nm][1]))
-    x = t(x_flat)
-    F = x.shape[1]
+    x = None if flat is not None else t(x_flat)
 
     def big(z_extra, nm):
         k, b = t(named[nm][0]), t(named[nm][1])
-        kx = k[:F].half().float() if h16_dense else k[:F]
-        xx = x.half().float() if h16_dense else x
-        return Fn.relu(xx @ kx + z_extra @ k[F:] + b)
+        F = k.shape[0] - (0 if z_extra is None else z_extra.shape[1])
+        if flat is not None:
+            prod = t(flat[nm])
+        else:
+            kx = k[:F].half().float() if h16_dense else k[:F]
+            xx = x.half().float() if h16_dense else x
+            prod = xx @ kx
+        return Fn.relu(prod + b if z_extra is None else prod + z_extra @ k[F:] + b)
 
+    if kind == "cnn_2d_speed_control":
+        return lin(lin(lin(big(None, "dense1"), "dense2"), "dense3"), "output_layer", act=False).numpy()
     spd = t(speed).reshape(-1, 1) / 20.0
     if kind == "cnn_2d_speed_as_feature":
         y = lin(lin(lin(spd, "feature1"), "feature2"), "feature3")

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void trs_pilot_tail_kernel(const TailParams p)
 }
 
 // ---- dense1 as its own kernel (round 2) -------------------------------------------------------------------------------------
-// dense1 (4608 -> 100 at 120x160, 83,328 -> 100 at 240x320) is 0.8 % of the network's arithmetic but, as a 1x1 convolution on
+// dense1 (4,608 -> 100 at 120x160, 70,528 -> 100 at 240x320) is 0.8 % of the network's arithmetic but, as a 1x1 convolution on
 // the chunked kernel, it and the tail were 23 of 267 us: 36 K slices of partial sums written and read back (19 MB against 9.4 MB
 // of activations).  Here a workgroup takes 32 frames x one K slice (8 slices fill the chip at 1024 frames):
 //   * the slice's activations go through LDS (coalesced 16-byte loads of each frame's contiguous run, chunks of 72 granules,
