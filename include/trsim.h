@@ -715,6 +715,49 @@ int trs_sample_batch_aug(trs_env* env, const trs_loader_config* cfg, const trs_a
 int trs_loader_augment(const trs_loader_config* cfg, const trs_augment_config* aug, int split, int epoch, int first, int count, int32_t* h_index_or_null,
                        uint8_t* h_mirror, float* h_params);
 
+/* ---- training the pilot's tail: dense1 .. output_layer on the device, conv1 .. conv7 frozen (include/trsim_spec.h, "training the pilot's tail") ----
+ * The reference's trainer continues from a saved model (components/keras_train.py:376,400-401) with optimizers.Adam(lr=0.001) on 'mse' (:404).  Here the
+ * loaded pilot of a 22-array model type (cnn_2d_speed_control, cnn_2d) is trained where it drives: a step runs the convolutions and dense1 by the kernels
+ * of trs_pilot_forward, takes the loss and its gradient through the four dense layers, and moves them by Adam, all on the handle's stream and without a
+ * byte crossing to the host.  After a step the handle drives with the updated pilot (trs_pilot_forward, trs_pilot_act, trs_step_pilot, trs_step_dagger).
+ * What stays out: the convolutions' backward pass, dropout, the model types with side inputs (28 and 42 arrays), feature caching across epochs, any
+ * exchange of gradients between GPUs.
+ *   trs_pilot_train_begin: fp32 master weights and Adam's m and v (zero) for the eight arrays dense1 .. output_layer, t = 0.  The handle keeps dense1 as
+ *     binary16 only, so h_tail_arrays[0], dense1's kernel float[F][100] as trs_pilot_load got it, is read from the host; the other seven arrays are taken
+ *     from the device, where the tail kernel reads them (entries 1..7 are not read and may be NULL).  cfg NULL: the defaults.
+ *   trs_pilot_train_step: one step on d_frames uint8[n][H][W][3] and d_labels float[n][2], 1 <= n <= n_envs; d_loss (may be NULL) receives the loss of the
+ *     batch BEFORE the update, sum (out - y)^2 / (2 n).  Asynchronous on the handle's stream.  A resident worker is asked to leave, as for trs_pilot_forward.
+ *   trs_pilot_train_get: the fp32 masters in Keras layouts into h_tail_arrays_out[0..7] (a NULL entry is skipped) and the step count; synchronises.
+ *   trs_pilot_train_debug: item `which` (TRS_TRAIN_DBG_*) of the last step as floats; the sibling of trs_pilot_debug_layer.  Synchronises.
+ *   trs_pilot_train_end: releases the session's buffers; the handle keeps driving with the trained weights.
+ *   Refusals.  TRS_ERR_STATE: no pilot loaded; begin twice; step, get, debug or end without begin; trs_pilot_load or trs_pilot_set_tuning between begin
+ *     and end (end the session first).  TRS_ERR_LIMIT: a pilot of 28 or 42 arrays.  TRS_ERR_ARG: the config (struct_size; lr or eps not positive and
+ *     finite; a beta outside [0, 1); train_mask 0 or with bits beyond 3), a NULL dense1 kernel, n outside [1, n_envs], NULL frames or labels, an unknown
+ *     item or a size that is not the item's. */
+typedef struct trs_train_config {
+    uint32_t struct_size;
+    float    lr, beta1, beta2, eps;  /* 0.001, 0.9, 0.999, 1e-7: optimizers.Adam(lr=0.001) with Keras's defaults */
+    uint32_t train_mask;             /* 0xF: bit l = layer l of dense1, dense2, dense3, output_layer is trained; a masked layer keeps every bit */
+} trs_train_config;
+enum {
+    TRS_TRAIN_DBG_OUT = 0,           /* float[n][2]: the outputs the loss was taken on */
+    TRS_TRAIN_DBG_Z1, TRS_TRAIN_DBG_Z2, TRS_TRAIN_DBG_Z3,                          /* pre-activations [n][100], [n][50], [n][25] */
+    TRS_TRAIN_DBG_DELTA1, TRS_TRAIN_DBG_DELTA2, TRS_TRAIN_DBG_DELTA3, TRS_TRAIN_DBG_DELTA4,   /* [n][100], [n][50], [n][25], [n][2] */
+    TRS_TRAIN_DBG_GW1, TRS_TRAIN_DBG_GW2, TRS_TRAIN_DBG_GW3, TRS_TRAIN_DBG_GW4,    /* [F][100], [100][50], [50][25], [25][2] */
+    TRS_TRAIN_DBG_GB1, TRS_TRAIN_DBG_GB2, TRS_TRAIN_DBG_GB3, TRS_TRAIN_DBG_GB4,
+    TRS_TRAIN_DBG_M = 16,            /* + a (0..7): Adam's m of array a, in the order of trs_pilot_train_begin */
+    TRS_TRAIN_DBG_V = 24,            /* + a: Adam's v */
+    TRS_TRAIN_DBG_SCALE_EXP = 32,    /* 1 float: the exponent s of the batch's scale 2^s */
+    TRS_TRAIN_DBG_LOSS = 33,         /* 1 float */
+    TRS_TRAIN_DBG_PACK1 = 34         /* float[F][100]: dense1's binary16 copy as the dense kernel reads it, widened */
+};
+void trs_default_train_config(trs_train_config* cfg);
+int trs_pilot_train_begin(trs_env* env, const trs_train_config* cfg_or_null, const float* const* h_tail_arrays);
+int trs_pilot_train_step(trs_env* env, const uint8_t* d_frames, const float* d_labels, int n, float* d_loss_or_null);
+int trs_pilot_train_get(trs_env* env, float* const* h_tail_arrays_out, int* t_out_or_null);
+int trs_pilot_train_debug(trs_env* env, int which, float* h_dst, size_t n_floats);
+int trs_pilot_train_end(trs_env* env);
+
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no
  * distributed layer at all; this replaces what a user would otherwise script around N copies of manage.py.

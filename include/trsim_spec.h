@@ -360,6 +360,44 @@
  *     Mirrored among records 0..4095 at 0.5, epochs 0, 1, 7:  seed 0: 2068 1996 2052;  seed 1: 2081 2042 2019;  seed 12345: 1984 2068 2001.
  *   tests/test_augment_cpu.py restates the paragraph in numpy and compares trs_loader_augment with it; tests/test_augment_gpu.py compares
  *   trs_batch_aug_kernel with that restatement bit for bit; csrc/trsim_augment.hpp is the one place the kernel and the host take the draw from.
+ *
+ * ---- training the pilot's tail (trs_pilot_train_begin, trs_pilot_train_step; 22-array model types; HIP library only)
+ *   dense1 -> dense2 -> dense3 -> output_layer of the loaded pilot move by Adam on Keras's 'mse' (components/keras_train.py:400-404); conv1 .. conv7 stay as
+ *   loaded.  Inputs of a step: n frames uint8 NHWC, labels y[n][2] binary32, 1 <= n <= n_envs.  W(l), b(l): kernel [IN][OUT] and bias of layer l = 1..4.
+ *   1. Forward, by the kernels that drive: conv1 .. conv7 and trs_pilot_dense_kernel with the current binary16 copy of W1.  Per frame z1 = the split-K slabs
+ *      added in slice order (binary32, from +0), a1 = relu(z1); z2, z3 and out are one fmaf chain per output from the bias with k ascending,
+ *      s = fmaf(a[k], W[k][o], s), a = relu(z) in between.  out equals trs_pilot_forward's on the same frames bit for bit.
+ *   2. loss = sum_i sum_j (out_ij - y_ij)^2 / (2 n): binary32, s = fmaf(e, e, s) over i ascending, j ascending inside, then one division by (float)(2 n).
+ *      delta4_ij = (out_ij - y_ij) / (float)n: a subtraction and a correctly rounded division.
+ *   3. Backward in binary32, per frame: delta(l)[k] = [z(l)[k] > 0] * sum_o W(l+1)[k][o] delta(l+1)[o] for l = 3, 2, 1; the sum is one fmaf chain from +0 with
+ *      o ascending, s = fmaf(W[k][o], delta[o], s).
+ *   4. Small gradients in binary32, one chain per value over the frames in ascending order: gW(l)[k][o] = sum_i a(l-1)_i[k] delta(l)_i[o] for l = 2, 3, 4 as
+ *      s = fmaf(a, delta, s) from +0; gb(l)[o] = sum_i delta(l)_i[o] for l = 1..4 as s = s + delta.  No floating-point atomics anywhere.
+ *   5. gW1[k][o] = sum_i x7_i[k] delta1_i[o], x7 = conv7's binary16 activation as stored, on the matrix cores with delta1 as binary16 under a power-of-two
+ *      scale per batch.  B = the integer maximum over the batch of the bit patterns of |delta1| (equal to the pattern of the largest value).
+ *        B == 0:                 s = 0
+ *        exponent field of B 0:  E = (position of B's leading one) - 149          (a subnormal)
+ *        otherwise:              E = (B >> 23) - 127                               (Inf and NaN patterns: 128)
+ *        s = 14 - E clamped to [-100, 100];  q = binary16_rn(delta1 * 2^s)  (the product exact in binary32, one rounding to nearest even; the largest
+ *        value lands in [2^14, 2^15));  gW1 = 2^-s * sum_i x7 q, the products exact and the sum accumulated in binary32 by the MFMA, the frames of a k-step of
+ *        16 in the hardware's order, the k-steps ascending; one workgroup owns a feature for the whole batch.  The last factor is one binary32 multiply.
+ *   6. Adam in Keras's form, t counting the steps from 1.  Constants: b1 = beta1, b2 = beta2, e = eps as binary32; c1 = (float)(1 - (double)b1),
+ *      c2 = (float)(1 - (double)b2); alpha_t = (float)((double)lr * sqrt(1 - (double)b2^t) / (1 - (double)b1^t)) (binary64 sqrt and pow, one rounding).
+ *      Per value, plain binary32, every operation rounded by itself, no contraction, sqrt and / correctly rounded:
+ *        m = (b1 * m) + (c1 * g)
+ *        v = (b2 * v) + (c2 * (g * g))
+ *        w = w - ((alpha_t * m) / (sqrt(v) + e))
+ *      on fp32 masters (trs_pilot_train_begin: W1 from the caller's array, the rest from the device), m = v = 0 at the start.  The pass over W1 also writes
+ *      its binary16 granules [G][128][8] with host_f2h's rounding (nearest even, 65504 beyond the range); the other seven arrays are also written where the
+ *      tail kernels read them.  A layer whose bit of train_mask is clear keeps w, m and v; t counts all the same.
+ *   Vectors.  Exponent: B = 0 -> 0; 1.0f -> 14; 1.9999999f -> 14; 2.0f -> 13; 0.5f -> 15; 3e-6f -> 33; 2^14 -> 0; 2^15 -> -1; 2^-86, 2^-87 -> 100;
+ *     B = 1, 0x00400000, 0x007FFFFF -> 100; 2^114, 2^120, 0x7F800000, 0x7FC00000 -> -100.
+ *     alpha_t at the defaults (bit patterns): t = 1: 39a5cb17, t = 2: 3976beef, t = 1000: 3a507326.  c1 = 3dccccd0, c2 = 3a831200.
+ *     One update, g = 1, m = v = 0, w = 1, t = 1: m = 3dccccd0, v = 3a831200, w = 3f7fbe77 (0.99900001: Adam's first step is lr in size).
+ *   Not here: the convolutions' backward pass, dropout (keras_train.py applies 0.1; tests/golden/train_pilot_fixture.py trains without), the model types with
+ *   side inputs (28 and 42 arrays: refused), feature caching across epochs, gradient exchange between GPUs.
+ *   tests/test_train_cpu.py restates steps 2 to 6 in numpy and checks the restatement against torch.autograd in binary64; tests/test_train_gpu.py compares the
+ *   kernels with it (Adam bit for bit from the device's gradient); csrc/trsim_train.hpp holds the rules a host compiler can build.
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Training the pilot's tail (trs_pilot_train_step, include/trsim_spec.h "training the pilot's tail") on one box, at 1024 x 120x160 and 512 x 240x320, the
+legs alternating three times inside one run:
+  step     trs_pilot_train_step against trs_pilot_forward on the same frames (HIP events on the handle's stream): the difference is what training adds behind
+           the forward pass (the forward's own tail kernel, about 6 us, is in trs_pilot_forward and not in the step: it is added back from the trace)
+  torch    the step it replaces, on the same GPU: fp32 nn.Linear layers on conv7's features (already there, fp32), mse_loss, backward(), Adam.step()
+  copies   plain device copies moving the bytes of the gW1 GEMM (n F 2 read, F 400 written) and of the Adam pass (4 fp32 arrays read, 3 written and the
+           binary16 pack): half the total as a torch copy_, which reads and writes it once each.  No pass line: the ratios say what fusing Adam into the
+           GEMM's epilogue could save.
+With --drive N the script only runs N steps per shape: under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/train_bench.py
+--drive 50` that gives the split by kernel, and `python scripts/train_bench.py --stats DIR` prints it.
+Pass line: the part behind conv7 (every trs_train_* kernel) is faster than the torch step.
+Run from the repository root: python scripts/train_bench.py [> profiles/rNN_train_tail.txt]"""
+import csv
+import glob
+import os
+import sys
+sys.path.insert(0, ".")
+import numpy as np
+
+SHAPES = [(1024, 120, 160, 200), (512, 240, 320, 60)]        # (frames, H, W, calls per timing)
+ROUNDS = 3
+SPEC = [(5, 2, 3, 24), (5, 2, 24, 32), (5, 2, 32, 64), (3, 1, 64, 64), (3, 1, 64, 64), (3, 1, 64, 128), (3, 1, 128, 128)]
+
+
+def weights(h, w, seed=0):
+    rng = np.random.default_rng(seed)
+    ws, ih, iw = [], h, w
+    for k, s, cin, cout in SPEC:
+        ws += [(rng.standard_normal((k, k, cin, cout)) * np.sqrt(2.0 / (k * k * cin))).astype(np.float32), rng.uniform(-0.05, 0.05, cout).astype(np.float32)]
+        ih, iw = (ih - k) // s + 1, (iw - k) // s + 1
+    dims = [ih * iw * 128, 100, 50, 25, 2]
+    for a, b in zip(dims[:-1], dims[1:]):
+        lim = np.sqrt(6.0 / (a + b))
+        ws += [rng.uniform(-lim, lim, (a, b)).astype(np.float32), rng.uniform(-0.05, 0.05, b).astype(np.float32)]
+    return ws, dims[0]
+
+
+def stats(directory):
+    rows = {}
+    for path in glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                name = r.get("Name") or r.get("KernelName") or ""
+                if "trs_" in name:
+                    short = name[name.index("trs_"):]
+                    short = short[:short.index("_kernel") + 7] if "_kernel" in short else short.split("(")[0]
+                    calls, total = int(r["Calls"]), float(r["TotalDurationNs"])
+                    c, t = rows.get(short, (0, 0.0))
+                    rows[short] = (c + calls, t + total)
+    print("== kernels by name over both shapes (rocprofv3 --kernel-trace --stats): calls, average us ==")
+    for name, (c, t) in sorted(rows.items()):
+        print(f"  {name:40s} {c:6d} {t / c / 1e3:10.2f}")
+
+
+def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "--stats":
+        return stats(sys.argv[2])
+    drive = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "--drive" else 0
+    import torch
+    from triton_racer_sim_amd.env import BatchedEnv
+
+    def timed(env, calls, fn):
+        env.sync()
+        env.event_record(0)
+        for _ in range(calls):
+            fn()
+        env.event_record(1)
+        env.sync()
+        return env.event_elapsed_ms(0, 1) * 1e3 / calls
+
+    def torch_timed(calls, fn):
+        for _ in range(5):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / calls
+
+    def show(name, runs):
+        print(f"  {name:72s} {min(runs):10.2f} us  (runs: {', '.join(f'{v:.2f}' for v in runs)})", flush=True)
+
+    for n, h, w, calls in SHAPES:
+        ws, F = weights(h, w)
+        env = BatchedEnv(n_envs=n, img_h=h, img_w=w, track=None)
+        env.pilot_load(ws)
+        env.pilot_train_begin()
+        frames = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda")
+        labels = torch.rand((n, 2), device="cuda") * 2 - 1
+        out = torch.empty((n, 2), device="cuda")
+        torch.cuda.synchronize()
+        pf, pl, po = int(frames.data_ptr()), int(labels.data_ptr()), int(out.data_ptr())
+        step = lambda: env.api.pilot_train_step(env._h, pf, pl, n, None)
+        fwd = lambda: env.api.pilot_forward(env._h, pf, n, po)
+        assert step() == 0 and fwd() == 0
+        if drive:
+            timed(env, drive, step)
+            timed(env, drive, fwd)
+            env.close()
+            continue
+        # the torch step on the same features
+        x7 = torch.rand((n, F), device="cuda")
+        model = torch.nn.Sequential(torch.nn.Linear(F, 100), torch.nn.ReLU(), torch.nn.Linear(100, 50), torch.nn.ReLU(), torch.nn.Linear(50, 25), torch.nn.ReLU(),
+                                    torch.nn.Linear(25, 2)).cuda()
+        opt = torch.optim.Adam(model.parameters(), lr=1e-3, eps=1e-7)
+
+        def torch_step():
+            opt.zero_grad(set_to_none=True)
+            torch.nn.functional.mse_loss(model(x7), labels).backward()
+            opt.step()
+
+        gemm_bytes, adam_bytes = n * F * 2 + F * 400, int(7.5 * F * 400)
+        src_g, src_a = torch.empty(gemm_bytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(adam_bytes // 2, dtype=torch.uint8, device="cuda")
+        dst_g, dst_a = torch.empty_like(src_g), torch.empty_like(src_a)
+        res = {}
+        for _ in range(ROUNDS):
+            res.setdefault("fwd", []).append(timed(env, calls, fwd))
+            res.setdefault("step", []).append(timed(env, calls, step))
+            res.setdefault("torch", []).append(torch_timed(calls, torch_step))
+            res.setdefault("copy_g", []).append(torch_timed(calls, lambda: dst_g.copy_(src_g)))
+            res.setdefault("copy_a", []).append(torch_timed(calls, lambda: dst_a.copy_(src_a)))
+        print(f"== {n} frames of {h}x{w}, F = {F}; one MI355X; figures are the minimum of {ROUNDS} alternating runs of {calls} calls ==")
+        show("trs_pilot_forward (conv1..7, dense1, the driving tail)", res["fwd"])
+        show("trs_pilot_train_step (conv1..7, dense1, tail forward + backward, gW1, Adam)", res["step"])
+        show("torch: 4 x nn.Linear fp32 on conv7's features, mse_loss, backward(), Adam.step()", res["torch"])
+        show(f"copy_ of {gemm_bytes // 2 / 1e6:.1f} MB: the gW1 GEMM's {gemm_bytes / 1e6:.1f} MB, read + written", res["copy_g"])
+        show(f"copy_ of {adam_bytes // 2 / 1e6:.1f} MB: the Adam pass's {adam_bytes / 1e6:.1f} MB, read + written", res["copy_a"])
+        added = min(res["step"]) - min(res["fwd"])
+        print(f"  step - forward = {added:.2f} us (the part behind conv7 less the driving tail kernel); torch step / that = {min(res['torch']) / added:.2f} x", flush=True)
+        env.pilot_train_end()
+        env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -156,6 +156,15 @@ class TrsAugmentConfig(C.Structure):
     ]
 
 
+class TrsTrainConfig(C.Structure):
+    """``trs_train_config`` (include/trsim.h): Adam's constants and the layers ``trs_pilot_train_step`` moves."""
+    _fields_ = [("struct_size", C.c_uint32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("train_mask", C.c_uint32)]
+
+
+TRAIN_LAYERS = ("dense1", "dense2", "dense3", "output_layer")           # bit l of trs_train_config.train_mask; their (kernel, bias) pairs are the eight trained arrays
+TRAIN_DEBUG = {"out": 0, "z1": 1, "z2": 2, "z3": 3, "delta1": 4, "delta2": 5, "delta3": 6, "delta4": 7, "gw1": 8, "gw2": 9, "gw3": 10, "gw4": 11,
+               "gb1": 12, "gb2": 13, "gb3": 14, "gb4": 15, "m": 16, "v": 24, "scale_exp": 32, "loss": 33, "pack1": 34}   # TRS_TRAIN_DBG_* ("m", "v": + the array's number 0..7)
+
 LOADER_TYPES = {"speed_ctl": 0, "default": 1, "speed_feature": 2, "full_house": 3}   # TRS_LOADER_*; the names of recorder.LOADERS, in the order of TRS_PILOT_*
 LOADER_FEATURES = {"speed_ctl": 0, "default": 0, "speed_feature": 1, "full_house": 2}
 LOADER_LABELS = {"expert": 0, "applied": 1}                             # TRS_LABEL_*
@@ -210,9 +219,12 @@ AUGMENT_SYMBOLS = ["default_augment_config", "sample_batch_aug", "loader_augment
 # HIP library only: the pilot in the loop with the expert's labels (trs_step_dagger) — its checker is the numpy restatement of include/trsim_spec.h ("pilot
 # in the loop with the expert's labels") in tests/test_dagger_cpu.py composed with the existing calls (tests/test_dagger_gpu.py, bit for bit)
 DAGGER_SYMBOLS = ["default_dagger_config", "step_dagger", "dagger_stats"]
+# HIP library only: training the pilot's tail (trs_pilot_train_*) — its checker is the numpy restatement of include/trsim_spec.h ("training the pilot's
+# tail") in tests/test_train_cpu.py, itself checked against torch.autograd in binary64 (tests/test_train_gpu.py compares the kernels with it)
+TRAIN_SYMBOLS = ["default_train_config", "pilot_train_begin", "pilot_train_step", "pilot_train_get", "pilot_train_debug", "pilot_train_end"]
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -337,6 +349,14 @@ class Api:
             "sample_batch_aug": (i32, [vp, C.POINTER(TrsLoaderConfig), C.POINTER(TrsAugmentConfig), vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
             "loader_augment": (i32, [C.POINTER(TrsLoaderConfig), C.POINTER(TrsAugmentConfig), i32, i32, i32, i32, vp, vp, vp]),
         }
+        train = {
+            "default_train_config": (None, [C.POINTER(TrsTrainConfig)]),
+            "pilot_train_begin": (i32, [vp, C.POINTER(TrsTrainConfig), C.POINTER(C.c_void_p)]),
+            "pilot_train_step": (i32, [vp, vp, vp, i32, vp]),
+            "pilot_train_get": (i32, [vp, C.POINTER(C.c_void_p), C.POINTER(i32)]),
+            "pilot_train_debug": (i32, [vp, i32, vp, C.c_size_t]),
+            "pilot_train_end": (i32, [vp]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -405,6 +425,12 @@ class Api:
         self.has_augment = hasattr(cdll, prefix + "sample_batch_aug")
         if self.has_augment:
             for name, (res, args) in augment.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_train = hasattr(cdll, prefix + "pilot_train_step")
+        if self.has_train:
+            for name, (res, args) in train.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -78,4 +78,17 @@ struct TrsLoopOps {
 // the pilot into the handle's control arrays (v->ctl_*) — or writes zero controls when no frame exists yet.  *fed: the frame that was fed (nullptr: none).
 int trs_internal_pilot_loop_check(trs_env* e, const trs_pilot_config* cfg, int n_steps);
 int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView* v, const uint8_t** fed);
+// ---- training the pilot's tail (trsim_train.hip) ----
+// The loaded pilot behind conv7 as a training step sees it: device pointers into the pilot's own buffers (views), defined in trsim_pilot.hip.
+struct TrsPilotTail {
+    int arch, n_cap, G; size_t F;         // TRS_PILOT_*, the plan's capacity, dense1's granules and the flatten's length F = 8 G
+    const void* x7;                       // conv7's activation of the last pass: binary16 [n][F]
+    const float* slab; int slices; size_t slab_stride;   // dense1's split-K slabs of the last pass: `slices` of [n][100], slab_stride floats apart
+    unsigned short* w1_pack; float* b1;   // dense1 as trs_pilot_dense_kernel reads it: granules [G][128][8] of binary16, bias [128]
+    float *w2, *b2, *w3, *b3, *w4, *b4;   // the small layers where the tail kernel reads them (Keras layouts)
+    void** train;                         // the session's slot in the pilot's context (nullptr in it: none open)
+};
+int trs_internal_pilot_tail(trs_env* e, TrsEnvView* v, TrsPilotTail* t);   // the view and the tail of the loaded pilot, or the refusal of every pilot entry point (no handle, no pilot)
+int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t);   // conv1..7 and dense1 of trs_pilot_forward on the stream; *t refreshed
+void trs_train_free(void* session);   // defined in trsim_train.hip, called by trs_pilot_free; nullptr is fine
 void trs_expert_free(void* ctx);      // defined in trsim_expert.hip, called by trs_destroy and by trs_load_track (a new track switches the expert off); nullptr is fine

@@ -940,6 +940,7 @@ struct PilotCtx {
     ChainParams chain{};                  // conv(plan.chain.first + 1) .. conv7 in one launch (trs_conv_chain_kernel): all but the per-call fields
     bool chain_mid_valid = true;          // act[chain.first .. 5] hold the last pass (the chain never writes them; the debug getter runs the single layers on demand)
     trsim::DevBuf<u4v> w2_parity;         // conv2's granules in the band kernel's order (conv2_parity_order)
+    void* train = nullptr;                // trsim_train.hip's session between trs_pilot_train_begin and _end (released by trs_train_free)
 };
 
 float host_h2f(unsigned short u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; }   // (the debug getter's; packing needs host_f2h only)
@@ -1194,7 +1195,43 @@ int forward_staged(trs_env* e, PilotCtx* c, const TrsEnvView& v, const uint8_t* 
 
 }  // namespace
 
-void trs_pilot_free(void* ctx) { delete static_cast<PilotCtx*>(ctx); }
+void trs_pilot_free(void* ctx)
+{
+    PilotCtx* const c = static_cast<PilotCtx*>(ctx);
+    if (c) trs_train_free(c->train);
+    delete c;
+}
+
+// ---- what trsim_train.hip needs of the loaded pilot (trsim_internal.hpp) ----
+namespace {
+void fill_tail(PilotCtx* c, TrsPilotTail* t)
+{
+    const PilotPlan& P = c->plan;
+    float* const B = c->xblob.get(); const int* const xo = c->tail.xo;
+    t->arch = P.arch; t->n_cap = P.n_cap; t->F = (size_t)P.L[7].CIN; t->G = P.L[7].G;
+    t->x7 = c->act[6].get();
+    t->slab = static_cast<const float*>(c->slab.get()); t->slices = c->last_slices; t->slab_stride = (size_t)c->last_n * P.L[7].act_elems();
+    t->w1_pack = reinterpret_cast<unsigned short*>(c->L[7].w.get()); t->b1 = c->L[7].bias.get();
+    t->w2 = B + xo[XO_W2]; t->b2 = B + xo[XO_B2]; t->w3 = B + xo[XO_W3]; t->b3 = B + xo[XO_B3]; t->w4 = B + xo[XO_W4]; t->b4 = B + xo[XO_B4];
+    t->train = &c->train;
+}
+}  // namespace
+
+int trs_internal_pilot_tail(trs_env* e, TrsEnvView* v, TrsPilotTail* t)
+{
+    PilotCtx* c;
+    if (int rc = enter(e, v, &c)) return rc;
+    fill_tail(c, t);
+    return TRS_OK;
+}
+
+int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t)
+{
+    PilotCtx* const c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
+    if (int rc = forward(c, v, d_frames, n)) return rc;
+    fill_tail(c, t);
+    return TRS_OK;
+}
 
 TRS_EXPORT void trs_default_pilot_config(trs_pilot_config* c)
 {
@@ -1211,6 +1248,8 @@ TRS_EXPORT int trs_pilot_set_tuning(trs_env* e, const trs_pilot_tuning* t)
 {
     if (!e) return trs_internal_fail(TRS_ERR_ARG, "null handle");
     if (t && t->struct_size != sizeof(trs_pilot_tuning)) return trs_internal_fail(TRS_ERR_ARG, "trs_pilot_tuning.struct_size does not match this library (start from trs_default_pilot_tuning)");
+    if (const PilotCtx* c = static_cast<const PilotCtx*>(*trs_internal_pilot_slot(e)); c && c->train)
+        return trs_internal_fail(TRS_ERR_STATE, "a training session is open on this pilot: trs_pilot_train_end first");
     trs_internal_set_pilot_tuning(e, t);
     return TRS_OK;
 }
@@ -1223,8 +1262,10 @@ TRS_EXPORT int trs_pilot_load(trs_env* e, const float* const* arr, int n_arrays)
         return trs_internal_fail(TRS_ERR_ARG, "expected 22 arrays: kernel and bias of conv1..conv7, dense1..dense3, output_layer (28 with feature1..3 for cnn_2d_speed_as_feature; "
                                               "42 for cnn_2d_full_house: ..., output_speed, feature1..3, current_spd_1..3, dense4..6, out_steering)");
     for (int i = 0; i < n_arrays; ++i) if (!arr[i]) return trs_internal_fail(TRS_ERR_ARG, "null weight array");
-    HIPCHK(hipSetDevice(v.device));
     void** slot = trs_internal_pilot_slot(e);
+    if (*slot && static_cast<PilotCtx*>(*slot)->train)
+        return trs_internal_fail(TRS_ERR_STATE, "a training session is open on this pilot: trs_pilot_train_end first");
+    HIPCHK(hipSetDevice(v.device));
     if (*slot) { HIPCHK(hipStreamSynchronize(v.stream)); delete static_cast<PilotCtx*>(*slot); *slot = nullptr; }
     // the context under construction is freed on EVERY early return below (HIPCHK included); released into the handle at the end
     std::unique_ptr<PilotCtx> guard(new PilotCtx());

@@ -1,0 +1,530 @@
+// trsim_train.hip — training the pilot's tail on the device (include/trsim_spec.h, "training the pilot's tail"): dense1 -> dense2 -> dense3 -> output_layer
+// of a loaded 22-array pilot move by Adam on 'mse', conv1 .. conv7 stay as loaded.  A step is the forward pass of trs_pilot_forward up to dense1's split-K
+// slabs (trsim_pilot.hip runs it: the kernels that drive, unchanged) and six kernels of this file, all on the handle's stream:
+//   trs_train_tail_kernel     one wave per frame: the slabs added in slice order, dense2 -> dense3 -> output as trs_pilot_tail_kernel computes them (restated:
+//                             the same chains, so the same bits), delta4 .. delta1 in binary32, the integer maximum of |delta1|'s bit patterns
+//   trs_train_small_kernel    one thread per small weight, bias and the loss: sums over the frames in ascending order (6,478 threads)
+//   trs_train_quant_kernel    delta1 -> binary16 under the batch's power-of-two scale, [n padded to 64][128], zeros in the padding
+//   trs_train_gw1_kernel      dense1's weight gradient on the matrix cores: gW1[k][o] = 2^-s sum_i x7_i[k] q_i[o].  The reduction index is the frame, the slow
+//                             index of both operands as stored, so both tiles go to LDS as they lie in memory ([frame][value], 64 frames per chunk) and
+//                             every MFMA fragment is two ds_read_b64_tr_b16.  A workgroup owns 128 features for the whole batch (wave w: features 32 w ..
+//                             32 w + 31 x the four 32-output blocks: four accumulators), so the order of the sum is fixed.  Row pitch 320 B: rows q = 0..3
+//                             of a transposed read start 16 banks apart, the two 16-lane groups of a half 8 apart, the four lanes of a row 2 apart —
+//                             no two lanes of a 32-lane half on one bank.
+//   trs_train_adam1_kernel    Adam over dense1's kernel: one thread per (granule, output) moves 8 masters and writes the binary16 granule the dense
+//                             kernel reads; trs_train_adam_kernel: the other seven arrays, written to the master and where the tail kernels read them
+// No floating-point atomics: two runs of a step agree bit for bit.  The rules that need no GPU (config, alpha_t, the scale's exponent, the buffers' layout)
+// are trsim_train.hpp.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../../include/trsim.h"
+#include "trsim_internal.hpp"
+#include "trsim_mem.hpp"
+#include "trsim_train.hpp"
+
+namespace {
+
+using namespace trsim;
+
+typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
+typedef __attribute__((ext_vector_type(4))) _Float16 h16x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// ---- forward behind dense1's slabs, and backward through the three small layers: one wave per frame -------------------------------
+struct TailTrainParams {
+    const float* h1; int slices; size_t stride;          // dense1's slabs (bias in slice 0)
+    const float *w2, *b2, *w3, *b3, *w4, *b4;            // Keras layouts [IN][OUT]
+    const float* y; int n;
+    float *out, *z1, *z2, *z3, *d1, *d2, *d3, *d4;
+    unsigned* max_bits;                                  // zeroed before the launch
+};
+
+__global__ __launch_bounds__(256) void trs_train_tail_kernel(const TailTrainParams p)
+{
+    __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i = blockIdx.x * 4 + wv;
+    if (i >= p.n) return;                                // whole waves
+    // z1: the slabs in slice order (what trs_pilot_tail_kernel's padded groups add: x + 0.0f == x), then the ReLU
+    const bool two = lane + 64 < 100;
+    float z1a = 0.0f, z1b = 0.0f;
+    for (int sl = 0; sl < p.slices; ++sl) {
+        const float* src = p.h1 + (size_t)sl * p.stride + (size_t)i * 100 + lane;
+        z1a += src[0];
+        z1b += src[two ? 64 : 0];
+    }
+    p.z1[(size_t)i * 100 + lane] = z1a; s1[wv][lane] = z1a > 0.f ? z1a : 0.f;
+    if (two) { p.z1[(size_t)i * 100 + lane + 64] = z1b; s1[wv][lane + 64] = z1b > 0.f ? z1b : 0.f; }
+    __builtin_amdgcn_wave_barrier();
+    float z2 = 0.0f, z3 = 0.0f;
+    if (lane < 50) {                                     // one fmaf chain per output from the bias, k ascending
+        float s = p.b2[lane];
+        for (int k = 0; k < 100; ++k) s = fmaf(s1[wv][k], p.w2[k * 50 + lane], s);
+        z2 = s; p.z2[(size_t)i * 50 + lane] = s; s2[wv][lane] = s > 0.f ? s : 0.f;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 25) {
+        float s = p.b3[lane];
+        for (int k = 0; k < 50; ++k) s = fmaf(s2[wv][k], p.w3[k * 25 + lane], s);
+        z3 = s; p.z3[(size_t)i * 25 + lane] = s; s3[wv][lane] = s > 0.f ? s : 0.f;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 2) {
+        float s = p.b4[lane];
+        for (int k = 0; k < 25; ++k) s = fmaf(s3[wv][k], p.w4[k * 2 + lane], s);
+        p.out[(size_t)i * 2 + lane] = s;
+        const float d = (s - p.y[(size_t)i * 2 + lane]) / (float)p.n;          // delta4
+        p.d4[(size_t)i * 2 + lane] = d; e4[wv][lane] = d;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // delta(l) = (W(l+1) delta(l+1)) . [z(l) > 0]: lane k owns row k; one fmaf chain from 0, the output index ascending
+    if (lane < 25) {
+        float s = 0.0f;
+        for (int o = 0; o < 2; ++o) s = fmaf(p.w4[lane * 2 + o], e4[wv][o], s);
+        s = z3 > 0.f ? s : 0.0f;
+        p.d3[(size_t)i * 25 + lane] = s; e3[wv][lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 50) {
+        float s = 0.0f;
+        for (int o = 0; o < 25; ++o) s = fmaf(p.w3[lane * 25 + o], e3[wv][o], s);
+        s = z2 > 0.f ? s : 0.0f;
+        p.d2[(size_t)i * 50 + lane] = s; e2[wv][lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float da = 0.0f, db = 0.0f;
+    {
+        const int kb = two ? lane + 64 : lane;
+        for (int o = 0; o < 50; ++o) { da = fmaf(p.w2[lane * 50 + o], e2[wv][o], da); db = fmaf(p.w2[kb * 50 + o], e2[wv][o], db); }
+        da = z1a > 0.f ? da : 0.0f;
+        db = (two && z1b > 0.f) ? db : 0.0f;
+        p.d1[(size_t)i * 100 + lane] = da;
+        if (two) p.d1[(size_t)i * 100 + lane + 64] = db;
+    }
+    // the batch's largest |delta1| as a bit pattern: non-negative binary32 values order like their patterns, and an integer maximum has no order
+    unsigned mx = max(__float_as_uint(da) & 0x7FFFFFFFu, __float_as_uint(db) & 0x7FFFFFFFu);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
+    if (lane == 0 && mx) atomicMax(p.max_bits, mx);
+}
+
+// ---- the small gradients and the loss: one thread per value, the frames in ascending order ----------------------------------------
+struct SmallGradParams {
+    const float *z1, *z2, *z3, *d1, *d2, *d3, *d4, *out, *y;
+    float* g; size_t off[kTrainArrays + 1];              // the gradient buffer and its layout (TrainLayout)
+    float *loss, *loss_user; int n;
+};
+constexpr int kSmallGradThreads = 100 + 5000 + 50 + 1250 + 25 + 50 + 2 + 1;   // gb1, gW2, gb2, gW3, gb3, gW4, gb4, the loss
+
+// The loads of kGradAhead frames are requested together and the additions then run in frame order: the sum is the plain ascending one, but a load's round trip
+// to L2 is paid once per kGradAhead frames and not once per frame (one frame at a time measured 364 us per step at 1024 frames: profiles/r31_train_tail.txt)
+constexpr int kGradAhead = 32;
+__device__ __forceinline__ float grad_w(const float* z, int nin, const float* d, int nout, int t, int n)
+{
+    const int k = t / nout, o = t - k * nout;
+    const float *pz = z + k, *pd = d + o;
+    float s = 0.0f;
+    int i = 0;
+    for (; i + kGradAhead <= n; i += kGradAhead) {
+        float a[kGradAhead], b[kGradAhead];
+#pragma unroll
+        for (int j = 0; j < kGradAhead; ++j) { a[j] = pz[(size_t)(i + j) * nin]; b[j] = pd[(size_t)(i + j) * nout]; }
+#pragma unroll
+        for (int j = 0; j < kGradAhead; ++j) s = fmaf(a[j] > 0.f ? a[j] : 0.f, b[j], s);
+    }
+    for (; i < n; ++i) { const float a = pz[(size_t)i * nin]; s = fmaf(a > 0.f ? a : 0.f, pd[(size_t)i * nout], s); }
+    return s;
+}
+__device__ __forceinline__ float grad_b(const float* d, int nout, int o, int n)
+{
+    const float* pd = d + o;
+    float s = 0.0f;
+    int i = 0;
+    for (; i + kGradAhead <= n; i += kGradAhead) {
+        float b[kGradAhead];
+#pragma unroll
+        for (int j = 0; j < kGradAhead; ++j) b[j] = pd[(size_t)(i + j) * nout];
+#pragma unroll
+        for (int j = 0; j < kGradAhead; ++j) s += b[j];
+    }
+    for (; i < n; ++i) s += pd[(size_t)i * nout];
+    return s;
+}
+
+__global__ __launch_bounds__(64) void trs_train_small_kernel(const SmallGradParams p)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < 100) { p.g[p.off[1] + t] = grad_b(p.d1, 100, t, p.n); return; }
+    t -= 100;
+    if (t < 5000) { p.g[p.off[2] + t] = grad_w(p.z1, 100, p.d2, 50, t, p.n); return; }
+    t -= 5000;
+    if (t < 50) { p.g[p.off[3] + t] = grad_b(p.d2, 50, t, p.n); return; }
+    t -= 50;
+    if (t < 1250) { p.g[p.off[4] + t] = grad_w(p.z2, 50, p.d3, 25, t, p.n); return; }
+    t -= 1250;
+    if (t < 25) { p.g[p.off[5] + t] = grad_b(p.d3, 25, t, p.n); return; }
+    t -= 25;
+    if (t < 50) { p.g[p.off[6] + t] = grad_w(p.z3, 25, p.d4, 2, t, p.n); return; }
+    t -= 50;
+    if (t < 2) { p.g[p.off[7] + t] = grad_b(p.d4, 2, t, p.n); return; }
+    t -= 2;
+    if (t == 0) {                                        // loss = sum_i sum_j (out - y)^2 / (2 n)
+        float s = 0.0f;
+        int i = 0;
+        for (; i + kGradAhead <= 2 * p.n; i += kGradAhead) {
+            float a[kGradAhead], b[kGradAhead];
+#pragma unroll
+            for (int j = 0; j < kGradAhead; ++j) { a[j] = p.out[i + j]; b[j] = p.y[i + j]; }
+#pragma unroll
+            for (int j = 0; j < kGradAhead; ++j) { const float e = a[j] - b[j]; s = fmaf(e, e, s); }
+        }
+        for (; i < 2 * p.n; ++i) { const float e = p.out[i] - p.y[i]; s = fmaf(e, e, s); }
+        s = s / (float)(2 * p.n);
+        *p.loss = s;
+        if (p.loss_user) *p.loss_user = s;
+    }
+}
+
+// ---- delta1 as binary16 under the batch's scale ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(128) void trs_train_quant_kernel(const float* d1, const unsigned* max_bits, unsigned short* q, int* sexp, int n)
+{
+    const int i = blockIdx.x, o = threadIdx.x;           // grid: n padded to 64 frames
+    const int s = train_scale_exponent(*max_bits);
+    if (i == 0 && o == 0) *sexp = s;
+    _Float16 h = (_Float16)0.0f;
+    if (i < n && o < 100) h = (_Float16)(d1[(size_t)i * 100 + o] * __uint_as_float((unsigned)(s + 127) << 23));   // exact scaling, then round to nearest even
+    q[(size_t)i * 128 + o] = __builtin_bit_cast(unsigned short, h);
+}
+
+// ---- dense1's weight gradient on the matrix cores ---------------------------------------------------------------------------------------
+struct Gw1Params {
+    const u4v* x7;             // conv7's activation: binary16 [n][G] granules
+    const u4v* q;              // [n_pad][16] granules: delta1 quantised, 128 values per frame
+    float* gw1;                // [F][100]
+    const int* sexp;
+    int n, n_pad, G;
+};
+constexpr int kGwFrames = 64;              // frames per LDS chunk: four k-steps of 16
+constexpr int kGwPitch = 320;              // bytes per frame row of a tile: 128 values and 64 B that keep the transposed reads off each other's banks
+constexpr int kGwTile = kGwFrames * kGwPitch;
+
+typedef short s16x4 __attribute__((__vector_size__(8)));                   // the builtin's own vector type
+typedef __attribute__((address_space(3))) s16x4* lds_s16x4p;
+
+// the fragment of a 32 x 32 x 16 MFMA whose 32-wide index is `col0 .. col0 + 31` of the tile's rows and whose k index is frames k0 .. k0 + 15: lane l holds
+// column col0 + l % 32, frames k0 + 8 (l / 32) .. + 7.  Per 16-lane group two transposed reads of a 4-frame x 16-column block each: lane 4 q + p of the
+// group points at frame q, columns 4 p .. 4 p + 3 of its block, and receives its own column of the four frames.
+__device__ __forceinline__ h16x8 tr_fragment(const unsigned char* tile, int lane, int col0, int k0)
+{
+    const int i16 = lane & 15, row = k0 + 8 * (lane >> 5) + (i16 >> 2), col = col0 + 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
+    const unsigned char* a = tile + row * kGwPitch + col * 2;
+    const h16x4 lo = __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(a)));
+    const h16x4 hi = __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(a + 4 * kGwPitch)));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__global__ __launch_bounds__(256) void trs_train_gw1_kernel(const Gw1Params p)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char tiles[2 * kGwTile];   // x7's tile, then q's: 40 KB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g0 = blockIdx.x * 16;                                         // the tile's first granule: features 128 blockIdx.x ..
+    // staging: a chunk is 64 frames x 16 granules of each operand; thread t moves granules e = t + 256 i (i < 4): frame e / 16, granule e % 16
+    u4v px[4], pq[4];
+    auto load = [&](int c0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i, fr = c0 + (e >> 4), gi = e & 15;
+            u4v v = p.x7[(size_t)min(fr, p.n - 1) * p.G + g0 + gi];          // a frame past the batch: a valid address, a zero fragment
+            if (fr >= p.n) v = u4v{0u, 0u, 0u, 0u};
+            px[i] = v;
+            pq[i] = p.q[(size_t)fr * 16 + gi];                               // (padded with zeros up to n_pad)
+        }
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i, off = (e >> 4) * kGwPitch + (e & 15) * 16;
+            *reinterpret_cast<u4v*>(tiles + off) = px[i];
+            *reinterpret_cast<u4v*>(tiles + kGwTile + off) = pq[i];
+        }
+    };
+    f32x16 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[b][i] = 0.0f;
+    load(0);
+    for (int c0 = 0; c0 < p.n_pad; c0 += kGwFrames) {
+        __syncthreads();                                                    // the chunk before has been read
+        store();
+        __syncthreads();
+        if (c0 + kGwFrames < p.n_pad) load(c0 + kGwFrames);                 // the next chunk is requested underneath
+        const int steps = min(4, (p.n - c0 + 15) >> 4);                     // k-steps of 16 frames that hold a frame of the batch
+        for (int ks = 0; ks < steps; ++ks) {
+            const h16x8 bx = tr_fragment(tiles, lane, 32 * wave, 16 * ks);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const h16x8 aq = tr_fragment(tiles + kGwTile, lane, 32 * b, 16 * ks);
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bx, acc[b], 0, 0, 0);
+            }
+        }
+    }
+    // D[output][feature]: lane = feature, registers 4 q4 .. + 3 = outputs 32 b + 8 q4 + 4 h .. + 3: one 16-byte store each, scaled back by 2^-s (exact)
+    const float back = __uint_as_float((unsigned)(127 - *p.sexp) << 23);
+    const int h = lane >> 5;
+    float* const row = p.gw1 + ((size_t)g0 * 8 + 32 * wave + (lane & 31)) * 100;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int o = 32 * b + 8 * q4 + 4 * h;
+            if (o < 100) *reinterpret_cast<f4v*>(row + o) = f4v{acc[b][4 * q4] * back, acc[b][4 * q4 + 1] * back, acc[b][4 * q4 + 2] * back, acc[b][4 * q4 + 3] * back};
+        }
+}
+
+// ---- Adam in Keras's form -----------------------------------------------------------------------------------------------------------------
+struct AdamK { float b1, c1, b2, c2, eps, alpha; };      // beta1, 1 - beta1, beta2, 1 - beta2, epsilon, alpha_t
+
+// plain binary32, every operation rounded by itself (the build has no contraction; sqrt and / are correctly rounded)
+__device__ __forceinline__ float adam(float g, float& m, float& v, float w, const AdamK& k)
+{
+    m = k.b1 * m + k.c1 * g;
+    v = k.b2 * v + k.c2 * (g * g);
+    return w - (k.alpha * m) / (sqrtf(v) + k.eps);
+}
+
+// binary32 -> binary16 as host_f2h packs the weights (trsim_pilot_plan.hpp): nearest even, 65504 beyond the range, NaN stays NaN
+__device__ __forceinline__ unsigned short f2h_pack(float f)
+{
+    const unsigned x = __float_as_uint(f), a = x & 0x7FFFFFFFu;
+    if (a >= 0x477FE000u && a <= 0x7F800000u) return (unsigned short)(((x >> 16) & 0x8000u) | 0x7BFFu);
+    return __builtin_bit_cast(unsigned short, (_Float16)f);
+}
+
+// dense1's kernel: thread (granule, output) owns master rows 8 granule .. + 7 of column `output` and the granule [granule][output][8] of the pack
+__global__ __launch_bounds__(256) void trs_train_adam1_kernel(const float* g, float* m, float* v, float* w, unsigned short* pack, int G, const AdamK k)
+{
+    const int gid = blockIdx.x * 256 + threadIdx.x, gr = gid >> 7, co = gid & 127;
+    if (gr >= G || co >= 100) return;                    // columns 100 .. 127 of the pack stay zero
+    unsigned short h[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const size_t e = ((size_t)gr * 8 + j) * 100 + co;
+        float mm = m[e], vv = v[e];
+        const float ww = adam(g[e], mm, vv, w[e], k);
+        m[e] = mm; v[e] = vv; w[e] = ww;
+        h[j] = f2h_pack(ww);
+    }
+    const u4v out = {h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16), h[4] | ((unsigned)h[5] << 16), h[6] | ((unsigned)h[7] << 16)};
+    *reinterpret_cast<u4v*>(pack + ((size_t)gr * 128 + co) * 8) = out;
+}
+
+// arrays 1 .. 7 (dense1's bias, then the small layers): thread per value; the new weight goes to the master and to where the tail kernels read it
+struct AdamSmallParams { size_t off[kTrainArrays + 1]; float* live[kTrainArrays]; unsigned mask; };
+__global__ __launch_bounds__(256) void trs_train_adam_kernel(const float* g, float* m, float* v, float* w, const AdamSmallParams p, const AdamK k)
+{
+    const size_t e = p.off[1] + (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= p.off[kTrainArrays]) return;
+    int a = 1;
+    while (e >= p.off[a + 1]) ++a;
+    if (!((p.mask >> (a >> 1)) & 1u)) return;
+    float mm = m[e], vv = v[e];
+    const float ww = adam(g[e], mm, vv, w[e], k);
+    m[e] = mm; v[e] = vv; w[e] = ww;
+    p.live[a][e - p.off[a]] = ww;
+}
+
+// ---- the session --------------------------------------------------------------------------------------------------------------------------
+struct TrainSession {
+    trs_train_config cfg{};
+    int64_t t = 0;
+    size_t F = 0; int n_cap = 0, last_n = 0;
+    TrainLayout L{};
+    DevBuf<float> master, m, v, g;        // one layout (TrainLayout): the eight arrays in order
+    DevBuf<float> fwd;                    // out | z1 | z2 | z3 | delta1 | delta2 | delta3 | delta4, each for n_cap frames
+    DevBuf<unsigned short> q;             // [n_cap padded to 64][128]
+    DevBuf<unsigned> scal;                // [0] max |delta1| bits, [1] the scale's exponent (int), [2] the loss (float)
+    float* item(int which) const          // TRS_TRAIN_DBG_OUT .. DELTA4
+    {
+        static const int per[8] = {2, 100, 50, 25, 100, 50, 25, 2};
+        size_t o = 0;
+        for (int j = 0; j < which; ++j) o += (size_t)n_cap * per[j];
+        return fwd.get() + o;
+    }
+};
+
+const char* const kNoSession = "no training session on this pilot: trs_pilot_train_begin first";
+
+// how every entry point behind trs_pilot_train_begin begins: the view, the pilot's tail and its open session
+int enter_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrainSession** s)
+{
+    if (int rc = trs_internal_pilot_tail(e, v, t)) return rc;
+    *s = static_cast<TrainSession*>(*t->train);
+    if (!*s) return trs_internal_fail(TRS_ERR_STATE, kNoSession);
+    return TRS_OK;
+}
+
+}  // namespace
+
+void trs_train_free(void* session) { delete static_cast<TrainSession*>(session); }
+
+TRS_EXPORT void trs_default_train_config(trs_train_config* cfg)
+{
+    if (cfg) trsim::train_defaults(cfg);
+}
+
+TRS_EXPORT int trs_pilot_train_begin(trs_env* e, const trs_train_config* cfg_or_null, const float* const* h_tail_arrays)
+{
+    trs_train_config cfg;
+    trsim::train_defaults(&cfg);
+    if (cfg_or_null) {
+        if (const char* why = trsim::train_config_error(cfg_or_null)) return trs_internal_fail(TRS_ERR_ARG, why);
+        cfg = *cfg_or_null;
+    }
+    if (!h_tail_arrays || !h_tail_arrays[0]) return trs_internal_fail(TRS_ERR_ARG, "h_tail_arrays[0], dense1's kernel as trs_pilot_load got it, is NULL");
+    TrsEnvView v; TrsPilotTail t;
+    if (int rc = trs_internal_pilot_tail(e, &v, &t)) return rc;
+    if (t.arch != TRS_PILOT_SPD_CTL)
+        return trs_internal_fail(TRS_ERR_LIMIT, "the tail of a 28- or 42-array pilot (cnn_2d_speed_as_feature, cnn_2d_full_house) is not trained: 22 arrays only");
+    if (*t.train) return trs_internal_fail(TRS_ERR_STATE, "a training session is already open on this pilot: trs_pilot_train_end first");
+    HIPCHK(hipSetDevice(v.device));
+    std::unique_ptr<TrainSession> s(new TrainSession());
+    s->cfg = cfg; s->F = t.F; s->n_cap = t.n_cap; s->L = TrainLayout::of(t.F);
+    const size_t total = s->L.off[kTrainArrays] * sizeof(float), n_pad = trsim::align_up((size_t)t.n_cap, kGwFrames);
+    HIPCHK(s->master.alloc(total)); HIPCHK(s->m.alloc(total)); HIPCHK(s->v.alloc(total)); HIPCHK(s->g.alloc(total));
+    HIPCHK(s->fwd.alloc((size_t)t.n_cap * 354 * sizeof(float)));
+    HIPCHK(s->q.alloc(n_pad * 128 * sizeof(unsigned short)));
+    HIPCHK(s->scal.alloc(4 * sizeof(unsigned)));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    HIPCHK(hipMemcpy(s->master.get(), h_tail_arrays[0], s->L.count(0) * sizeof(float), hipMemcpyHostToDevice));
+    trs_internal_count(e, 0, (uint64_t)(s->L.count(0) * sizeof(float)));
+    const float* const live[kTrainArrays] = {nullptr, t.b1, t.w2, t.b2, t.w3, t.b3, t.w4, t.b4};
+    for (int a = 1; a < kTrainArrays; ++a)
+        HIPCHK(hipMemcpyAsync(s->master.get() + s->L.off[a], live[a], s->L.count(a) * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
+    HIPCHK(hipMemsetAsync(s->m.get(), 0, total, v.stream));
+    HIPCHK(hipMemsetAsync(s->v.get(), 0, total, v.stream));
+    HIPCHK(hipMemsetAsync(s->g.get(), 0, total, v.stream));
+    HIPCHK(hipMemsetAsync(s->scal.get(), 0, 4 * sizeof(unsigned), v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    *t.train = s.release();
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const float* d_labels, int n, float* d_loss_or_null)
+{
+    TrsEnvView v; TrsPilotTail t; TrainSession* s;
+    if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    if (n < 1 || n > s->n_cap) return trs_internal_fail(TRS_ERR_ARG, "n must be in [1, n_envs]");
+    if (!d_frames || !d_labels) return trs_internal_fail(TRS_ERR_ARG, "d_frames or d_labels is NULL");
+    HIPCHK(hipSetDevice(v.device));
+    if (int rc = trs_internal_pilot_dense_forward(e, v, d_frames, n, &t)) return rc;      // conv1 .. conv7 and dense1, by the kernels that drive
+    hipStream_t st = v.stream;
+    unsigned* const scal = s->scal.get();
+    HIPCHK(hipMemsetAsync(scal, 0, sizeof(unsigned), st));
+    TailTrainParams tp{};
+    tp.h1 = t.slab; tp.slices = t.slices; tp.stride = t.slab_stride;
+    tp.w2 = t.w2; tp.b2 = t.b2; tp.w3 = t.w3; tp.b3 = t.b3; tp.w4 = t.w4; tp.b4 = t.b4;
+    tp.y = d_labels; tp.n = n;
+    tp.out = s->item(TRS_TRAIN_DBG_OUT); tp.z1 = s->item(TRS_TRAIN_DBG_Z1); tp.z2 = s->item(TRS_TRAIN_DBG_Z2); tp.z3 = s->item(TRS_TRAIN_DBG_Z3);
+    tp.d1 = s->item(TRS_TRAIN_DBG_DELTA1); tp.d2 = s->item(TRS_TRAIN_DBG_DELTA2); tp.d3 = s->item(TRS_TRAIN_DBG_DELTA3); tp.d4 = s->item(TRS_TRAIN_DBG_DELTA4);
+    tp.max_bits = scal;
+    hipLaunchKernelGGL(trs_train_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp);
+    SmallGradParams sp{};
+    sp.z1 = tp.z1; sp.z2 = tp.z2; sp.z3 = tp.z3; sp.d1 = tp.d1; sp.d2 = tp.d2; sp.d3 = tp.d3; sp.d4 = tp.d4; sp.out = tp.out; sp.y = d_labels;
+    sp.g = s->g.get(); std::memcpy(sp.off, s->L.off, sizeof sp.off);
+    sp.loss = reinterpret_cast<float*>(scal + 2); sp.loss_user = d_loss_or_null; sp.n = n;
+    hipLaunchKernelGGL(trs_train_small_kernel, dim3((kSmallGradThreads + 63) / 64), dim3(64), 0, st, sp);
+    const int n_pad = (int)trsim::align_up((size_t)n, kGwFrames);
+    hipLaunchKernelGGL(trs_train_quant_kernel, dim3(n_pad), dim3(128), 0, st, tp.d1, scal, s->q.get(), reinterpret_cast<int*>(scal + 1), n);
+    Gw1Params gp{};
+    gp.x7 = static_cast<const u4v*>(t.x7); gp.q = reinterpret_cast<const u4v*>(s->q.get()); gp.gw1 = s->g.get(); gp.sexp = reinterpret_cast<const int*>(scal + 1);
+    gp.n = n; gp.n_pad = n_pad; gp.G = t.G;
+    hipLaunchKernelGGL(trs_train_gw1_kernel, dim3(t.G / 16), dim3(256), 0, st, gp);
+    const trs_train_config& c = s->cfg;
+    const AdamK k{c.beta1, trsim::train_one_minus(c.beta1), c.beta2, trsim::train_one_minus(c.beta2), c.eps, trsim::train_alpha(c, s->t + 1)};
+    if (c.train_mask & 1u)
+        hipLaunchKernelGGL(trs_train_adam1_kernel, dim3((t.G * 128 + 255) / 256), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), t.w1_pack, t.G, k);
+    AdamSmallParams ap{};
+    std::memcpy(ap.off, s->L.off, sizeof ap.off);
+    float* const live[kTrainArrays] = {nullptr, t.b1, t.w2, t.b2, t.w3, t.b3, t.w4, t.b4};
+    for (int a = 0; a < kTrainArrays; ++a) ap.live[a] = live[a];
+    ap.mask = c.train_mask;
+    const size_t small = s->L.off[kTrainArrays] - s->L.off[1];
+    hipLaunchKernelGGL(trs_train_adam_kernel, dim3((unsigned)((small + 255) / 256)), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), ap, k);
+    HIPCHK(hipGetLastError());
+    s->t += 1; s->last_n = n;
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_pilot_train_get(trs_env* e, float* const* h_tail_arrays_out, int* t_out_or_null)
+{
+    TrsEnvView v; TrsPilotTail t; TrainSession* s;
+    if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    if (!h_tail_arrays_out) return trs_internal_fail(TRS_ERR_ARG, "h_tail_arrays_out is NULL");
+    HIPCHK(hipSetDevice(v.device));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    for (int a = 0; a < kTrainArrays; ++a) {
+        if (!h_tail_arrays_out[a]) continue;
+        HIPCHK(hipMemcpy(h_tail_arrays_out[a], s->master.get() + s->L.off[a], s->L.count(a) * sizeof(float), hipMemcpyDeviceToHost));
+        trs_internal_count(e, (uint64_t)(s->L.count(a) * sizeof(float)), 0);
+    }
+    if (t_out_or_null) *t_out_or_null = (int)s->t;
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_pilot_train_debug(trs_env* e, int which, float* h_dst, size_t n_floats)
+{
+    TrsEnvView v; TrsPilotTail t; TrainSession* s;
+    if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    if (!s->last_n) return trs_internal_fail(TRS_ERR_STATE, "no training step yet");
+    const size_t want = trsim::train_debug_floats(which, s->last_n, s->F);
+    if (!want || !h_dst) return trs_internal_fail(TRS_ERR_ARG, "unknown item (TRS_TRAIN_DBG_*) or NULL destination");
+    if (n_floats != want) return trs_internal_fail(TRS_ERR_ARG, "size mismatch");
+    HIPCHK(hipSetDevice(v.device));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    const float* src = nullptr;
+    if (which <= TRS_TRAIN_DBG_DELTA4) src = s->item(which);
+    else if (which <= TRS_TRAIN_DBG_GW4) src = s->g.get() + s->L.off[2 * (which - TRS_TRAIN_DBG_GW1)];
+    else if (which <= TRS_TRAIN_DBG_GB4) src = s->g.get() + s->L.off[2 * (which - TRS_TRAIN_DBG_GB1) + 1];
+    else if (which < TRS_TRAIN_DBG_V) src = s->m.get() + s->L.off[which - TRS_TRAIN_DBG_M];
+    else if (which < TRS_TRAIN_DBG_SCALE_EXP) src = s->v.get() + s->L.off[which - TRS_TRAIN_DBG_V];
+    else if (which == TRS_TRAIN_DBG_LOSS) src = reinterpret_cast<const float*>(s->scal.get() + 2);
+    if (src) {
+        HIPCHK(hipMemcpy(h_dst, src, want * sizeof(float), hipMemcpyDeviceToHost));
+        return TRS_OK;
+    }
+    if (which == TRS_TRAIN_DBG_SCALE_EXP) {
+        int sexp = 0;
+        HIPCHK(hipMemcpy(&sexp, s->scal.get() + 1, sizeof sexp, hipMemcpyDeviceToHost));
+        h_dst[0] = (float)sexp;
+        return TRS_OK;
+    }
+    // TRS_TRAIN_DBG_PACK1: granules [G][128][8] -> [F][100]
+    std::vector<unsigned short> pack((size_t)t.G * 128 * 8);
+    HIPCHK(hipMemcpy(pack.data(), t.w1_pack, pack.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < (size_t)t.G; ++g)
+        for (int j = 0; j < 8; ++j)
+            for (int co = 0; co < 100; ++co) {
+                _Float16 h; std::memcpy(&h, &pack[(g * 128 + co) * 8 + j], 2);
+                h_dst[(g * 8 + j) * 100 + co] = (float)h;
+            }
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_pilot_train_end(trs_env* e)
+{
+    TrsEnvView v; TrsPilotTail t; TrainSession* s;
+    if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    HIPCHK(hipSetDevice(v.device));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    trs_train_free(s);
+    *t.train = nullptr;
+    return TRS_OK;
+}

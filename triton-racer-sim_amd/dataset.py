@@ -310,6 +310,56 @@ class DeviceDataset:
             self._torch_after_env()
             return float(torch.mean((out.double() - labels.double()) ** 2).item())
 
+    def fit_tail(self, epochs, batch_size, augment=None, patience=None, val_batch_size=None, **adam):
+        """Train the loaded pilot's dense tail on this set, on the device (``trs_pilot_train_step``; include/trsim_spec.h, "training the pilot's
+        tail"): dense1 .. output_layer move by Adam on 'mse', the convolutions stay as loaded.  What ``model.fit`` is to the reference's trainer
+        for a model continued from a saved one (``components/keras_train.py:376,400-411``), without a second copy of the network in a framework:
+        per epoch the uint8 NHWC batches of ``batches(batch_size, epoch, "train", augment=augment)`` go into one training step each, then
+        ``pilot_loss("val", val_batch_size)`` is taken on the fp16 pilot as it drives.  The best epoch's weights are kept
+        (``ModelCheckpoint(save_best_only=True)``), ``patience`` epochs without a better validation loss stop the run (``None``: all ``epochs``),
+        and at the end the best weights are loaded into the handle.  ``adam``: ``lr``, ``beta1``, ``beta2``, ``eps``, ``layers`` of
+        ``pilot_train_begin``.  Returns the list of ``(train_loss, val_loss)`` per epoch run, ``train_loss`` the mean of the batches' losses.
+        Not here: dropout, the convolutions' backward pass, the model types with side inputs."""
+        if not self.with_frames:
+            raise RuntimeError("a physics-only set has no frames for the pilot")
+        torch, env = self.torch, self.env
+        epochs, batch_size = int(epochs), int(batch_size)
+        if epochs < 1 or not 1 <= batch_size <= env.n:
+            raise ValueError(f"epochs >= 1 and batch_size in [1, n_envs = {env.n}] are required")
+        if self.n_train // batch_size < 1:
+            raise ValueError(f"the 'train' split holds {self.n_train} records: no batch of {batch_size}")
+        if patience is not None and int(patience) < 1:
+            raise ValueError("patience >= 1 is required (None: no early stop)")
+        history, best, best_val, since = [], None, math.inf, 0
+        env.pilot_train_begin(**adam)
+        try:
+            with torch.cuda.device(self.device):
+                stream = self._torch_stream()
+                n_batches = self.n_train // batch_size
+                losses = torch.zeros((n_batches,), dtype=torch.float32, device=self.device)
+                for epoch in range(epochs):
+                    for t, (images, _, labels) in enumerate(self.batches(batch_size, epoch, "train", layout="nhwc", dtype="uint8", stream=stream, augment=augment)):
+                        # the gather and the step run on the env's stream, one behind the other: the torch stream's wait inside batches() is all the order needed
+                        env.pilot_train_step(images, labels, batch_size, loss=losses[t:])
+                    self._torch_after_env()
+                    train_loss = float(losses.double().mean().item())
+                    val_loss = self.pilot_loss("val", val_batch_size)
+                    history.append((train_loss, val_loss))
+                    if val_loss < best_val:
+                        best_val, since = val_loss, 0
+                        best = env.pilot_train_weights()[0]
+                    else:
+                        since += 1
+                        if patience is not None and since >= int(patience):
+                            break
+        finally:
+            env.pilot_train_end()
+        if best is not None:
+            arrs = env.pilot_weights()
+            arrs[14:22] = best
+            env.pilot_load(arrs)
+        return history
+
 
 def _ffi_stream(stream):
     """A torch stream as the pointer value the C ABI takes (0, the legacy default stream, as NULL)."""

@@ -782,6 +782,7 @@ class BatchedEnv:
         arrs = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         self.api.check(self.api.pilot_load(self._h, ptrs, len(arrs)), "pilot_load")
+        self._pilot_arrays = arrs                                    # what pilot_train_begin and pilot_weights start from
 
     def pilot_tuning(self, **choices):
         """Override kernel choices of the NEXT ``pilot_load`` (``trs_pilot_tuning``, include/trsim.h) — tests that compare a kernel
@@ -859,6 +860,92 @@ class BatchedEnv:
         frame it sees has been through the JPEG round trip first."""
         pc = cfg if isinstance(cfg, _ffi.TrsPilotConfig) else self.pilot_config(cfg)
         self.api.check(self.api.step_pilot(self._h, C.byref(pc), int(n_steps)), "step_pilot")
+
+    # -- training the pilot's tail (include/trsim_spec.h, "training the pilot's tail") -----------------------------------------
+    def _need_train(self):
+        if not getattr(self.api, "has_train", False):
+            raise RuntimeError("this library cannot train the pilot's tail (trs_pilot_train_step): HIP library only")
+        if getattr(self, "_pilot_arrays", None) is None:
+            raise RuntimeError("no pilot loaded: pilot_load first")
+
+    def train_config(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None):
+        """``trs_train_config``: Adam's constants (Keras's ``optimizers.Adam(lr=0.001)`` by default) and the layers that move — ``layers``: names
+        out of ``_ffi.TRAIN_LAYERS`` (``None``: all four)."""
+        c = _ffi.TrsTrainConfig()
+        self.api.default_train_config(C.byref(c))
+        c.lr, c.beta1, c.beta2, c.eps = float(lr), float(beta1), float(beta2), float(eps)
+        if layers is not None:
+            unknown = [nm for nm in layers if nm not in _ffi.TRAIN_LAYERS]
+            if unknown:
+                raise ValueError(f"layers must come from {_ffi.TRAIN_LAYERS}: {unknown}")
+            c.train_mask = sum(1 << _ffi.TRAIN_LAYERS.index(nm) for nm in set(layers))
+        return c
+
+    def pilot_train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None):
+        """Open a training session on the loaded pilot's dense tail (``trs_pilot_train_begin``): fp32 master weights from the arrays ``pilot_load``
+        was given, Adam's moments at zero.  22-array model types only; the convolutions stay as loaded.  Until ``pilot_train_end`` the handle
+        refuses ``pilot_load`` and ``pilot_tuning``; it drives with the current weights all along."""
+        self._need_train()
+        cfg = self.train_config(lr, beta1, beta2, eps, layers)
+        tail = self._pilot_arrays[14:22]
+        ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in tail])
+        self.api.check(self.api.pilot_train_begin(self._h, C.byref(cfg), ptrs), "pilot_train_begin")
+
+    def pilot_train_step(self, frames, labels, n=None, loss=None):
+        """One Adam step on ``frames uint8[n, H, W, 3]`` and ``labels float32[n, 2]`` on the device (torch tensors, anything with
+        ``__cuda_array_interface__``, or device pointers with ``n``), ``n <= n_envs``.  Asynchronous on the env's stream.  ``loss``: a device
+        float32 the batch's loss (before the update) is written to, and the call returns ``None``; without it the call waits and returns the loss."""
+        self._need_train()
+        if n is None:
+            n = int(frames.shape[0])
+        self.api.check(self.api.pilot_train_step(self._h, device_ptr(frames), device_ptr(labels), int(n), device_ptr(loss)), "pilot_train_step")
+        self._train_last_n = int(n)
+        if loss is not None:
+            return None
+        return float(self.pilot_train_debug("loss")[0])
+
+    def pilot_train_debug(self, item, array=0):
+        """Item ``item`` (a key of ``_ffi.TRAIN_DEBUG``; ``"m"`` and ``"v"`` take the number of the array, 0..7) of the last training step as a flat
+        float32 array (``trs_pilot_train_debug``); the caller reshapes."""
+        self._need_train()
+        which = _ffi.TRAIN_DEBUG[item] + (int(array) if item in ("m", "v") else 0)
+        F = int(self._pilot_arrays[14].shape[0])
+        n = int(getattr(self, "_train_last_n", 0))
+        sizes = {"out": 2 * n, "z1": 100 * n, "z2": 50 * n, "z3": 25 * n, "delta1": 100 * n, "delta2": 50 * n, "delta3": 25 * n, "delta4": 2 * n,
+                 "gw1": F * 100, "gw2": 5000, "gw3": 1250, "gw4": 50, "gb1": 100, "gb2": 50, "gb3": 25, "gb4": 2, "scale_exp": 1, "loss": 1, "pack1": F * 100}
+        size = self._pilot_arrays[14 + int(array)].size if item in ("m", "v") else sizes[item]
+        out = np.empty(size, np.float32)
+        self.api.check(self.api.pilot_train_debug(self._h, which, out.ctypes.data, out.size), "pilot_train_debug")
+        return out
+
+    def pilot_train_weights(self):
+        """``(arrays, t)``: the eight fp32 master arrays dense1 .. output_layer in Keras layouts and the number of steps taken (``trs_pilot_train_get``)."""
+        self._need_train()
+        outs = [np.empty_like(a) for a in self._pilot_arrays[14:22]]
+        ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in outs])
+        t = C.c_int(0)
+        self.api.check(self.api.pilot_train_get(self._h, ptrs, C.byref(t)), "pilot_train_get")
+        return outs, int(t.value)
+
+    def pilot_train_end(self):
+        """Close the session (``trs_pilot_train_end``).  The arrays ``pilot_weights`` returns keep the trained tail."""
+        self._need_train()
+        tail, _ = self.pilot_train_weights()
+        self.api.check(self.api.pilot_train_end(self._h), "pilot_train_end")
+        self._pilot_arrays = list(self._pilot_arrays[:14]) + tail + list(self._pilot_arrays[22:])
+
+    def pilot_weights(self):
+        """The arrays given to ``pilot_load`` with the trained ones replaced (the masters of an open session, or what the last session left): ready
+        for ``np.savez`` and for ``pilot_load`` of another handle."""
+        if getattr(self, "_pilot_arrays", None) is None:
+            raise RuntimeError("no pilot loaded: pilot_load first")
+        arrs = [a.copy() for a in self._pilot_arrays]
+        if getattr(self.api, "has_train", False) and len(arrs) == 22:
+            outs = [np.empty_like(a) for a in arrs[14:22]]
+            ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in outs])
+            if self.api.pilot_train_get(self._h, ptrs, None) == 0:      # an open session: its masters (refused without one: the arrays as kept)
+                arrs[14:22] = outs
+        return arrs
 
     # -- scripted expert (include/trsim_spec.h, "scripted expert") ----------------------------------------------------------
     def _need_expert(self):
