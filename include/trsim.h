@@ -720,8 +720,8 @@ int trs_loader_augment(const trs_loader_config* cfg, const trs_augment_config* a
  * loaded pilot of a 22-array model type (cnn_2d_speed_control, cnn_2d) is trained where it drives: a step runs the convolutions and dense1 by the kernels
  * of trs_pilot_forward, takes the loss and its gradient through the four dense layers, and moves them by Adam, all on the handle's stream and without a
  * byte crossing to the host.  After a step the handle drives with the updated pilot (trs_pilot_forward, trs_pilot_act, trs_step_pilot, trs_step_dagger).
- * What stays out: the convolutions' backward pass, dropout, the model types with side inputs (28 and 42 arrays), feature caching across epochs, any
- * exchange of gradients between GPUs.
+ * What stays out: conv1 .. conv3 (conv4 .. conv7 can be trained as well: the next section), dropout, the model types with side inputs (28 and 42
+ * arrays), feature caching across epochs, any exchange of gradients between GPUs.
  *   trs_pilot_train_begin: fp32 master weights and Adam's m and v (zero) for the eight arrays dense1 .. output_layer, t = 0.  The handle keeps dense1 as
  *     binary16 only, so h_tail_arrays[0], dense1's kernel float[F][100] as trs_pilot_load got it, is read from the host; the other seven arrays are taken
  *     from the device, where the tail kernel reads them (entries 1..7 are not read and may be NULL).  cfg NULL: the defaults.
@@ -757,6 +757,32 @@ int trs_pilot_train_step(trs_env* env, const uint8_t* d_frames, const float* d_l
 int trs_pilot_train_get(trs_env* env, float* const* h_tail_arrays_out, int* t_out_or_null);
 int trs_pilot_train_debug(trs_env* env, int which, float* h_dst, size_t n_floats);
 int trs_pilot_train_end(trs_env* env);
+
+/* ---- training the pilot's last convolutions: conv4 .. conv7 (include/trsim_spec.h, "training the pilot's last convolutions") ----
+ * Between trs_pilot_train_begin and the session's first step, trs_pilot_train_convs adds conv4 .. conv7 (all 3 x 3, stride 1, valid, 64 or 128 channels)
+ * to what the session trains; conv1 .. conv3 stay as loaded.  Every later step also back-propagates from dense1 down to the lowest layer named, on the
+ * matrix cores, and moves the named layers by the session's Adam (the same alpha_t and t as the tail).  Without the call a session is the tail's alone.
+ *   trs_pilot_train_convs: bit j of conv_mask names conv(4 + j); any non-empty subset.  h_conv_arrays[8]: kernel float[3][3][CIN][COUT] and bias
+ *     float[COUT] of conv4 .. conv7 as trs_pilot_load got them, the source of the fp32 masters (the handle keeps binary16 only); the two entries of a
+ *     layer whose bit is clear may be NULL.
+ *   trs_pilot_train_get_convs: the masters into h_out[0..7] (a NULL entry is skipped); for a layer that is not trained, the arrays as given (untouched
+ *     where they were NULL).  Synchronises.
+ *   trs_pilot_train_debug_conv: item `which` (TRS_CONV_DBG_*) of conv(4 + layer) after the last step as floats.  Synchronises.
+ *   Refusals.  TRS_ERR_STATE: no session, after the session's first step, a second call; get or debug before the call (debug: before a step).
+ *     TRS_ERR_ARG: a zero mask, bits above 3, a NULL array of a named layer, an unknown layer or item, a size that is not the item's, delta of a layer
+ *     below the lowest trained one. */
+enum {
+    TRS_CONV_DBG_DELTA = 0,          /* float[n][OH][OW][COUT]: delta(l), the stored binary16 values times 2^-s_l */
+    TRS_CONV_DBG_GW = 1,             /* float[3][3][CIN][COUT] (zeros for a layer that is not trained, like the five below) */
+    TRS_CONV_DBG_GB = 2,             /* float[COUT] */
+    TRS_CONV_DBG_MW = 3, TRS_CONV_DBG_VW = 4,   /* Adam's m and v of the kernel */
+    TRS_CONV_DBG_MB = 5, TRS_CONV_DBG_VB = 6,   /* and of the bias */
+    TRS_CONV_DBG_SCALE_EXP = 7,      /* 1 float: the exponent s_l of the layer's scale */
+    TRS_CONV_DBG_PACK = 8            /* float[3][3][CIN][COUT]: the binary16 copy the forward kernels read, widened, in Keras layout */
+};
+int trs_pilot_train_convs(trs_env* env, uint32_t conv_mask, const float* const* h_conv_arrays);
+int trs_pilot_train_get_convs(trs_env* env, float* const* h_out);
+int trs_pilot_train_debug_conv(trs_env* env, int layer, int which, float* h_dst, size_t n_floats);
 
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no

@@ -394,10 +394,40 @@
  *     B = 1, 0x00400000, 0x007FFFFF -> 100; 2^114, 2^120, 0x7F800000, 0x7FC00000 -> -100.
  *     alpha_t at the defaults (bit patterns): t = 1: 39a5cb17, t = 2: 3976beef, t = 1000: 3a507326.  c1 = 3dccccd0, c2 = 3a831200.
  *     One update, g = 1, m = v = 0, w = 1, t = 1: m = 3dccccd0, v = 3a831200, w = 3f7fbe77 (0.99900001: Adam's first step is lr in size).
- *   Not here: the convolutions' backward pass, dropout (keras_train.py applies 0.1; tests/golden/train_pilot_fixture.py trains without), the model types with
- *   side inputs (28 and 42 arrays: refused), feature caching across epochs, gradient exchange between GPUs.
+ *   Not here: conv1 .. conv3 (conv4 .. conv7: the next section), dropout (keras_train.py applies 0.1; tests/golden/train_pilot_fixture.py trains without), the
+ *   model types with side inputs (28 and 42 arrays: refused), feature caching across epochs, gradient exchange between GPUs.
  *   tests/test_train_cpu.py restates steps 2 to 6 in numpy and checks the restatement against torch.autograd in binary64; tests/test_train_gpu.py compares the
  *   kernels with it (Adam bit for bit from the device's gradient); csrc/trsim_train.hpp holds the rules a host compiler can build.
+ *
+ * ---- training the pilot's last convolutions (trs_pilot_train_convs; conv4 .. conv7 of a 22-array model type; HIP library only)
+ *   After trs_pilot_train_convs(mask) a step of the tail's session also moves the layers l of conv4 .. conv7 whose bit l - 4 is set; all four are 3 x 3,
+ *   stride 1, valid, (CIN, COUT) = (64, 64), (64, 64), (64, 128), (128, 128).  x(l) = conv_l's stored binary16 activation [n][OH][OW][COUT], W(l)h = its
+ *   binary16 kernel as the forward kernels read it, lo = the lowest layer named.  Without the call a step is the tail's section, bit for bit.
+ *   1. Forward: unchanged, by the kernels that drive; out of a step equals trs_pilot_forward bit for bit.  x3 and x7 are as the pass stored them; x4 .. x6 are
+ *      what the single-layer kernels compute from x3 where the fused chain kept them in LDS (materialise_layers), before any weight moves.  At 96x128 and
+ *      120x160 the single-layer conv7 on the materialised x6 reproduces the chain's x7 bit for bit (tests/test_train_conv_gpu.py).
+ *   2. G7_i[k] = [x7_i[k] > 0] * 2^-s * sum_o W1h[k][o] q1_i[o], k over the flatten: on the matrix cores from the binary16 dense1 copy the forward used (before
+ *      the tail's Adam rewrites it) and the q1 and s of the tail's step 5.  The products are exact in binary32; the 128 outputs (100 and zero padding) are
+ *      added in the MFMA's order, k-steps of 16 ascending; one binary32 multiply by 2^-s.
+ *   3. delta(l) is G(l) stored as binary16 under a per-layer, per-batch scale: B_l = the integer maximum (atomicMax) of the bit patterns of |G(l)|,
+ *      s_l = the tail's exponent rule on B_l (train_scale_exponent), q(l) = binary16_rn(G(l) * 2^s_l), delta(l) = q(l) * 2^-s_l.
+ *   4. For l = 7 .. lo + 1: G(l-1)[f][y][x][ci] = [x(l-1) > 0] * 2^-s_l * sum_{kh,kw,co} q(l)[f][y-kh][x-kw][co] * W(l)h[kh][kw][ci][co], terms outside q's
+ *      extent zero.  Matrix cores, binary32 accumulator, the sum in the order kh, kw ascending, inside a tap the k-steps of 16 co ascending.  Nothing is
+ *      computed below x(lo - 1): in particular nothing for x3.
+ *   5. For every trained l: gW(l)[kh][kw][ci][co] = 2^-s_l * sum_{f,oy,ox} x(l-1)[f][oy+kh][ox+kw][ci] * q(l)[f][oy][ox][co] on the matrix cores, binary32.
+ *      The P = n OH OW output pixels in (f, oy, ox) order are cut into chunks of 64; with want = max(1, min(chunks, (2 CUs + 8) / 9)),
+ *      per_slice = ceil(chunks / want) and slices = ceil(chunks / per_slice), slice s takes chunks s per_slice .. (a function of the geometry, n and the CU
+ *      count alone).  One workgroup per (slice, tap) adds its chunks in order (k-steps of 16 pixels ascending); the slices' sums are added in slice order,
+ *      then one multiply by 2^-s_l.  gb(l)[co] = 2^-s_l * sum q(l)[.][co]: per slice and channel, 256 / COUT running sums over the pixels p with equal
+ *      p mod (256 / COUT), added in that order, then the slices in slice order.  No floating-point atomics anywhere: two runs agree bit for bit.
+ *   6. Adam: the tail's step 6 verbatim, the same alpha_t and t, on fp32 masters of the trained kernels and biases (from the arrays given to
+ *      trs_pilot_train_convs), m = v = 0 at the start.  The pass writes each kernel's binary16 value with host_f2h's rounding at
+ *      ((kh run_pad + kw CIN / 8 + ci / 8) COUT_PAD + co) 8 + ci % 8 of ConvLayer::w (pack_layer's order; run_pad = 3 CIN / 8, COUT_PAD = COUT), into the
+ *      session's own [kh][kw][ci][co] copy that step 4 reads, and the bias where the kernels read it.  Step 4 of layer l runs before layer l's Adam.
+ *   Not here: conv1 .. conv3 (5 x 5, stride 2, the fused head), dropout, the 28- and 42-array model types, feature caching, the multi-GPU exchange.
+ *   tests/test_train_conv_cpu.py restates steps 2 to 5 in numpy, checks the restatement against torch.autograd in binary64 and shows what the reference
+ *   notices; tests/test_train_conv_gpu.py compares the kernels with it within derived bounds (Adam bit for bit from the device's gradient);
+ *   csrc/trsim_train_conv.hpp holds the rules a host compiler can build (tests/train_conv_driver.cpp).
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

@@ -10,7 +10,13 @@ legs alternating three times inside one run:
 With --drive N the script only runs N steps per shape: under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python scripts/train_bench.py
 --drive 50` that gives the split by kernel, and `python scripts/train_bench.py --stats DIR` prints it.
 Pass line: the part behind conv7 (every trs_train_* kernel) is faster than the torch step.
-Run from the repository root: python scripts/train_bench.py [> profiles/rNN_train_tail.txt]"""
+With --convs the session also trains conv4 .. conv7 (trs_pilot_train_convs, "training the pilot's last convolutions") and the torch leg is the step that
+replaces: fp32 nn.Conv2d x 4 and the nn.Linear tail on x3 (already there, fp32), mse_loss, backward(), Adam.step().  Pass line: the step's part behind
+conv3 is faster than that torch step; the script prints the WHOLE device step (conv1 .. conv3 included) beside it, which bounds that part from above, and
+step - forward, what training adds to a forward pass.  --convs combines with --drive for the split by kernel (the data and weight gradients against the
+forward chain kernel trs_conv_chain_kernel, about half their arithmetic); the copy leg moves the bytes of the convolutions' Adam pass (4 fp32 arrays read,
+3 written, two binary16 copies: 32 bytes per weight).  TRS_BENCH_SHAPE=0 or 1 in the environment runs one of the two shapes alone (a trace per shape).
+Run from the repository root: python scripts/train_bench.py [--convs] [> profiles/rNN_train_tail.txt]"""
 import csv
 import glob
 import os
@@ -56,6 +62,9 @@ def stats(directory):
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "--stats":
         return stats(sys.argv[2])
+    convs = "--convs" in sys.argv
+    if convs:
+        sys.argv.remove("--convs")
     drive = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "--drive" else 0
     import torch
     from triton_racer_sim_amd.env import BatchedEnv
@@ -84,11 +93,12 @@ def main():
     def show(name, runs):
         print(f"  {name:72s} {min(runs):10.2f} us  (runs: {', '.join(f'{v:.2f}' for v in runs)})", flush=True)
 
-    for n, h, w, calls in SHAPES:
+    only = os.environ.get("TRS_BENCH_SHAPE")                            # "0" or "1": one shape alone (the split by kernel under the tracer, per shape)
+    for n, h, w, calls in (SHAPES if only is None else [SHAPES[int(only)]]):
         ws, F = weights(h, w)
         env = BatchedEnv(n_envs=n, img_h=h, img_w=w, track=None)
         env.pilot_load(ws)
-        env.pilot_train_begin()
+        env.pilot_train_begin(convs=("conv4", "conv5", "conv6", "conv7") if convs else None)
         frames = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda")
         labels = torch.rand((n, 2), device="cuda") * 2 - 1
         out = torch.empty((n, 2), device="cuda")
@@ -108,12 +118,23 @@ def main():
                                     torch.nn.Linear(25, 2)).cuda()
         opt = torch.optim.Adam(model.parameters(), lr=1e-3, eps=1e-7)
 
+        if convs:                                                       # the torch step from x3 on: conv4 .. conv7 in fp32 NCHW, Keras's Flatten, the tail
+            ih, iw = env.conv_input_size(0)
+            x7 = torch.rand((n, 64, ih, iw), device="cuda")
+            chans, layers = [(64, 64), (64, 64), (64, 128), (128, 128)], []
+            for cin, cout in chans:
+                layers += [torch.nn.Conv2d(cin, cout, 3), torch.nn.ReLU()]
+            model = torch.nn.Sequential(*layers, torch.nn.Flatten(), *list(model.children())).cuda()
+            opt = torch.optim.Adam(model.parameters(), lr=1e-3, eps=1e-7)
+
         def torch_step():
             opt.zero_grad(set_to_none=True)
             torch.nn.functional.mse_loss(model(x7), labels).backward()
             opt.step()
 
         gemm_bytes, adam_bytes = n * F * 2 + F * 400, int(7.5 * F * 400)
+        if convs:
+            adam_bytes = 32 * 295296                                    # conv4 .. conv7: 295,296 weights and biases
         src_g, src_a = torch.empty(gemm_bytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(adam_bytes // 2, dtype=torch.uint8, device="cuda")
         dst_g, dst_a = torch.empty_like(src_g), torch.empty_like(src_a)
         res = {}
@@ -126,11 +147,16 @@ def main():
         print(f"== {n} frames of {h}x{w}, F = {F}; one MI355X; figures are the minimum of {ROUNDS} alternating runs of {calls} calls ==")
         show("trs_pilot_forward (conv1..7, dense1, the driving tail)", res["fwd"])
         show("trs_pilot_train_step (conv1..7, dense1, tail forward + backward, gW1, Adam)", res["step"])
-        show("torch: 4 x nn.Linear fp32 on conv7's features, mse_loss, backward(), Adam.step()", res["torch"])
+        show("torch: 4 x nn.Conv2d + 4 x nn.Linear fp32 on x3, mse_loss, backward(), Adam.step()" if convs else
+             "torch: 4 x nn.Linear fp32 on conv7's features, mse_loss, backward(), Adam.step()", res["torch"])
         show(f"copy_ of {gemm_bytes // 2 / 1e6:.1f} MB: the gW1 GEMM's {gemm_bytes / 1e6:.1f} MB, read + written", res["copy_g"])
         show(f"copy_ of {adam_bytes // 2 / 1e6:.1f} MB: the Adam pass's {adam_bytes / 1e6:.1f} MB, read + written", res["copy_a"])
         added = min(res["step"]) - min(res["fwd"])
-        print(f"  step - forward = {added:.2f} us (the part behind conv7 less the driving tail kernel); torch step / that = {min(res['torch']) / added:.2f} x", flush=True)
+        if convs:
+            print(f"  step - forward = {added:.2f} us (what training conv4 .. conv7 and the tail adds to a forward pass); the whole step, conv1 .. conv3 included, "
+                  f"against the torch step behind conv3: torch / step = {min(res['torch']) / min(res['step']):.2f} x", flush=True)
+        else:
+            print(f"  step - forward = {added:.2f} us (the part behind conv7 less the driving tail kernel); torch step / that = {min(res['torch']) / added:.2f} x", flush=True)
         env.pilot_train_end()
         env.close()
 

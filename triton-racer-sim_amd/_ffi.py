@@ -222,9 +222,14 @@ DAGGER_SYMBOLS = ["default_dagger_config", "step_dagger", "dagger_stats"]
 # HIP library only: training the pilot's tail (trs_pilot_train_*) — its checker is the numpy restatement of include/trsim_spec.h ("training the pilot's
 # tail") in tests/test_train_cpu.py, itself checked against torch.autograd in binary64 (tests/test_train_gpu.py compares the kernels with it)
 TRAIN_SYMBOLS = ["default_train_config", "pilot_train_begin", "pilot_train_step", "pilot_train_get", "pilot_train_debug", "pilot_train_end"]
+# HIP library only: training the pilot's last convolutions (trs_pilot_train_convs) — its checker is the numpy restatement of include/trsim_spec.h
+# ("training the pilot's last convolutions") in tests/test_train_conv_cpu.py, itself checked against torch.autograd in binary64
+TRAIN_CONV_SYMBOLS = ["pilot_train_convs", "pilot_train_get_convs", "pilot_train_debug_conv"]
+TRAIN_CONV_LAYERS = ("conv4", "conv5", "conv6", "conv7")                # bit j of trs_pilot_train_convs' mask; arrays 6 + 2 j, 7 + 2 j of pilot_load
+TRAIN_CONV_DEBUG = {"delta": 0, "gw": 1, "gb": 2, "mw": 3, "vw": 4, "mb": 5, "vb": 6, "scale_exp": 7, "pack": 8}   # TRS_CONV_DBG_*
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + TRAIN_CONV_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -356,6 +361,9 @@ class Api:
             "pilot_train_get": (i32, [vp, C.POINTER(C.c_void_p), C.POINTER(i32)]),
             "pilot_train_debug": (i32, [vp, i32, vp, C.c_size_t]),
             "pilot_train_end": (i32, [vp]),
+            "pilot_train_convs": (i32, [vp, C.c_uint32, C.POINTER(C.c_void_p)]),
+            "pilot_train_get_convs": (i32, [vp, C.POINTER(C.c_void_p)]),
+            "pilot_train_debug_conv": (i32, [vp, i32, i32, vp, C.c_size_t]),
         }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():

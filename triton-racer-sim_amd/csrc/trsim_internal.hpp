@@ -91,4 +91,23 @@ struct TrsPilotTail {
 int trs_internal_pilot_tail(trs_env* e, TrsEnvView* v, TrsPilotTail* t);   // the view and the tail of the loaded pilot, or the refusal of every pilot entry point (no handle, no pilot)
 int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t);   // conv1..7 and dense1 of trs_pilot_forward on the stream; *t refreshed
 void trs_train_free(void* session);   // defined in trsim_train.hip, called by trs_pilot_free; nullptr is fine
+// ---- training the pilot's last convolutions (trsim_train_conv.hip) ----
+// conv4 .. conv7 of the loaded pilot as a training step sees them (views into the pilot's own buffers), defined in trsim_pilot.hip.  With `materialise`
+// the interior activations x4 .. x6 of the last pass are written by the single-layer kernels where the chain kept them in LDS (materialise_layers), on the stream.
+struct TrsPilotConvs {
+    int n_cap, cu_count;
+    struct Layer {
+        int IH, IW, OH, OW, CIN, COUT, COUT_PAD, run_pad;
+        const void* in; const void* out;      // x(l-1) and x(l) of the last pass: binary16 [n][H][W][C]
+        unsigned short* w; float* bias;       // ConvLayer::w (granules, pack_layer's order) and ConvLayer::bias [COUT_PAD]
+    } L[4];
+};
+int trs_internal_pilot_convs(trs_env* e, const TrsEnvView& v, bool materialise, TrsPilotConvs* out);
+// the open session as trsim_train_conv.hip's entry points see it (defined in trsim_train.hip): enter_session's refusals, then the conv part's slot
+struct TrsTrainView { void** conv; int64_t steps; int last_n; };
+int trs_internal_train_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrsTrainView* out);
+// one backward pass and Adam over the trained convolutions, on the stream, from the tail's q1 [n padded to 64][128] and its exponent; before the tail's own Adam.
+struct TrsAdamConsts { float b1, c1, b2, c2, eps, alpha; };   // beta1, 1 - beta1, beta2, 1 - beta2, epsilon, alpha_t of this step: what the tail's Adam uses
+int trs_train_conv_step(void* conv, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n, const TrsAdamConsts& ak);
+void trs_train_conv_free(void* conv);   // nullptr is fine
 void trs_expert_free(void* ctx);      // defined in trsim_expert.hip, called by trs_destroy and by trs_load_track (a new track switches the expert off); nullptr is fine

@@ -1233,6 +1233,21 @@ int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint
     return TRS_OK;
 }
 
+int trs_internal_pilot_convs(trs_env* e, const TrsEnvView& v, bool materialise, TrsPilotConvs* out)
+{
+    PilotCtx* const c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
+    if (!c) return trs_internal_fail(TRS_ERR_STATE, "no pilot loaded");
+    if (materialise) { if (int rc = materialise_layers(c, v, 3, 5)) return rc; }
+    const PilotPlan& P = c->plan;
+    out->n_cap = P.n_cap; out->cu_count = P.cu_count;
+    for (int j = 0; j < 4; ++j) {
+        const PilotLayer& l = P.L[3 + j];
+        out->L[j] = TrsPilotConvs::Layer{l.IH, l.IW, l.OH, l.OW, l.CIN, l.COUT, l.COUT_PAD, l.run_pad, c->act[2 + j].get(), c->act[3 + j].get(),
+                                         reinterpret_cast<unsigned short*>(c->L[3 + j].w.get()), c->L[3 + j].bias.get()};
+    }
+    return TRS_OK;
+}
+
 TRS_EXPORT void trs_default_pilot_config(trs_pilot_config* c)
 {
     if (!c) return;

@@ -26,16 +26,13 @@
 #include "trsim_internal.hpp"
 #include "trsim_mem.hpp"
 #include "trsim_train.hpp"
+#include "trsim_train_dev.hpp"
 
 namespace {
 
 using namespace trsim;
 
-typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
-typedef __attribute__((ext_vector_type(4))) _Float16 h16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef unsigned u4v __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
+using namespace trsim_train_dev;      // the vector types, tr_fragment, Adam's update and the packed rounding: shared with trsim_train_conv.hip
 
 // ---- forward behind dense1's slabs, and backward through the three small layers: one wave per frame -------------------------------
 struct TailTrainParams {
@@ -211,25 +208,7 @@ struct Gw1Params {
     const int* sexp;
     int n, n_pad, G;
 };
-constexpr int kGwFrames = 64;              // frames per LDS chunk: four k-steps of 16
-constexpr int kGwPitch = 320;              // bytes per frame row of a tile: 128 values and 64 B that keep the transposed reads off each other's banks
-constexpr int kGwTile = kGwFrames * kGwPitch;
-
-typedef short s16x4 __attribute__((__vector_size__(8)));                   // the builtin's own vector type
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4p;
-
-// the fragment of a 32 x 32 x 16 MFMA whose 32-wide index is `col0 .. col0 + 31` of the tile's rows and whose k index is frames k0 .. k0 + 15: lane l holds
-// column col0 + l % 32, frames k0 + 8 (l / 32) .. + 7.  Per 16-lane group two transposed reads of a 4-frame x 16-column block each: lane 4 q + p of the
-// group points at frame q, columns 4 p .. 4 p + 3 of its block, and receives its own column of the four frames.
-__device__ __forceinline__ h16x8 tr_fragment(const unsigned char* tile, int lane, int col0, int k0)
-{
-    const int i16 = lane & 15, row = k0 + 8 * (lane >> 5) + (i16 >> 2), col = col0 + 16 * ((lane >> 4) & 1) + 4 * (i16 & 3);
-    const unsigned char* a = tile + row * kGwPitch + col * 2;
-    const h16x4 lo = __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(a)));
-    const h16x4 hi = __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(a + 4 * kGwPitch)));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
+// (the LDS chunk of 64 frames, its row pitch of 320 B and the transposed fragment read tr_fragment: trsim_train_dev.hpp)
 __global__ __launch_bounds__(256) void trs_train_gw1_kernel(const Gw1Params p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char tiles[2 * kGwTile];   // x7's tile, then q's: 40 KB
@@ -290,24 +269,7 @@ __global__ __launch_bounds__(256) void trs_train_gw1_kernel(const Gw1Params p)
 }
 
 // ---- Adam in Keras's form -----------------------------------------------------------------------------------------------------------------
-struct AdamK { float b1, c1, b2, c2, eps, alpha; };      // beta1, 1 - beta1, beta2, 1 - beta2, epsilon, alpha_t
-
-// plain binary32, every operation rounded by itself (the build has no contraction; sqrt and / are correctly rounded)
-__device__ __forceinline__ float adam(float g, float& m, float& v, float w, const AdamK& k)
-{
-    m = k.b1 * m + k.c1 * g;
-    v = k.b2 * v + k.c2 * (g * g);
-    return w - (k.alpha * m) / (sqrtf(v) + k.eps);
-}
-
-// binary32 -> binary16 as host_f2h packs the weights (trsim_pilot_plan.hpp): nearest even, 65504 beyond the range, NaN stays NaN
-__device__ __forceinline__ unsigned short f2h_pack(float f)
-{
-    const unsigned x = __float_as_uint(f), a = x & 0x7FFFFFFFu;
-    if (a >= 0x477FE000u && a <= 0x7F800000u) return (unsigned short)(((x >> 16) & 0x8000u) | 0x7BFFu);
-    return __builtin_bit_cast(unsigned short, (_Float16)f);
-}
-
+// (AdamK, the update `adam` and the packed rounding f2h_pack: trsim_train_dev.hpp)
 // dense1's kernel: thread (granule, output) owns master rows 8 granule .. + 7 of column `output` and the granule [granule][output][8] of the pack
 __global__ __launch_bounds__(256) void trs_train_adam1_kernel(const float* g, float* m, float* v, float* w, unsigned short* pack, int G, const AdamK k)
 {
@@ -351,6 +313,7 @@ struct TrainSession {
     DevBuf<float> fwd;                    // out | z1 | z2 | z3 | delta1 | delta2 | delta3 | delta4, each for n_cap frames
     DevBuf<unsigned short> q;             // [n_cap padded to 64][128]
     DevBuf<unsigned> scal;                // [0] max |delta1| bits, [1] the scale's exponent (int), [2] the loss (float)
+    void* conv = nullptr;                 // trsim_train_conv.hip's part of the session after trs_pilot_train_convs (released by trs_train_conv_free)
     float* item(int which) const          // TRS_TRAIN_DBG_OUT .. DELTA4
     {
         static const int per[8] = {2, 100, 50, 25, 100, 50, 25, 2};
@@ -373,7 +336,20 @@ int enter_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrainSession** s)
 
 }  // namespace
 
-void trs_train_free(void* session) { delete static_cast<TrainSession*>(session); }
+void trs_train_free(void* session)
+{
+    TrainSession* const s = static_cast<TrainSession*>(session);
+    if (s) trs_train_conv_free(s->conv);
+    delete s;
+}
+
+int trs_internal_train_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrsTrainView* out)
+{
+    TrainSession* s;
+    if (int rc = enter_session(e, v, t, &s)) return rc;
+    out->conv = &s->conv; out->steps = s->t; out->last_n = s->last_n;
+    return TRS_OK;
+}
 
 TRS_EXPORT void trs_default_train_config(trs_train_config* cfg)
 {
@@ -449,6 +425,10 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     hipLaunchKernelGGL(trs_train_gw1_kernel, dim3(t.G / 16), dim3(256), 0, st, gp);
     const trs_train_config& c = s->cfg;
     const AdamK k{c.beta1, trsim::train_one_minus(c.beta1), c.beta2, trsim::train_one_minus(c.beta2), c.eps, trsim::train_alpha(c, s->t + 1)};
+    if (s->conv) {                                                          // conv4 .. conv7 from delta1 and the dense1 copy the forward used: before Adam rewrites it
+        const TrsAdamConsts ak{k.b1, k.c1, k.b2, k.c2, k.eps, k.alpha};
+        if (int rc = trs_train_conv_step(s->conv, e, v, t, s->q.get(), reinterpret_cast<const int*>(scal + 1), n, ak)) return rc;
+    }
     if (c.train_mask & 1u)
         hipLaunchKernelGGL(trs_train_adam1_kernel, dim3((t.G * 128 + 255) / 256), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), t.w1_pack, t.G, k);
     AdamSmallParams ap{};

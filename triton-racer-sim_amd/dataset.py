@@ -310,16 +310,17 @@ class DeviceDataset:
             self._torch_after_env()
             return float(torch.mean((out.double() - labels.double()) ** 2).item())
 
-    def fit_tail(self, epochs, batch_size, augment=None, patience=None, val_batch_size=None, **adam):
+    def fit_tail(self, epochs, batch_size, augment=None, patience=None, val_batch_size=None, convs=None, **adam):
         """Train the loaded pilot's dense tail on this set, on the device (``trs_pilot_train_step``; include/trsim_spec.h, "training the pilot's
-        tail"): dense1 .. output_layer move by Adam on 'mse', the convolutions stay as loaded.  What ``model.fit`` is to the reference's trainer
+        tail"): dense1 .. output_layer move by Adam on 'mse'.  ``convs``: names among ``"conv4"`` .. ``"conv7"`` that move with them
+        ("training the pilot's last convolutions"); ``None``: every convolution stays as loaded.  conv1 .. conv3 always do.  What ``model.fit`` is to the reference's trainer
         for a model continued from a saved one (``components/keras_train.py:376,400-411``), without a second copy of the network in a framework:
         per epoch the uint8 NHWC batches of ``batches(batch_size, epoch, "train", augment=augment)`` go into one training step each, then
         ``pilot_loss("val", val_batch_size)`` is taken on the fp16 pilot as it drives.  The best epoch's weights are kept
         (``ModelCheckpoint(save_best_only=True)``), ``patience`` epochs without a better validation loss stop the run (``None``: all ``epochs``),
         and at the end the best weights are loaded into the handle.  ``adam``: ``lr``, ``beta1``, ``beta2``, ``eps``, ``layers`` of
         ``pilot_train_begin``.  Returns the list of ``(train_loss, val_loss)`` per epoch run, ``train_loss`` the mean of the batches' losses.
-        Not here: dropout, the convolutions' backward pass, the model types with side inputs."""
+        Not here: dropout, training conv1 .. conv3, the model types with side inputs."""
         if not self.with_frames:
             raise RuntimeError("a physics-only set has no frames for the pilot")
         torch, env = self.torch, self.env
@@ -331,7 +332,7 @@ class DeviceDataset:
         if patience is not None and int(patience) < 1:
             raise ValueError("patience >= 1 is required (None: no early stop)")
         history, best, best_val, since = [], None, math.inf, 0
-        env.pilot_train_begin(**adam)
+        env.pilot_train_begin(convs=convs, **adam)
         try:
             with torch.cuda.device(self.device):
                 stream = self._torch_stream()
@@ -347,7 +348,7 @@ class DeviceDataset:
                     history.append((train_loss, val_loss))
                     if val_loss < best_val:
                         best_val, since = val_loss, 0
-                        best = env.pilot_train_weights()[0]
+                        best = (env.pilot_train_weights()[0], env.pilot_train_conv_weights() if convs is not None else None)
                     else:
                         since += 1
                         if patience is not None and since >= int(patience):
@@ -356,9 +357,16 @@ class DeviceDataset:
             env.pilot_train_end()
         if best is not None:
             arrs = env.pilot_weights()
-            arrs[14:22] = best
+            arrs[14:22] = best[0]
+            if best[1] is not None:
+                arrs[6:14] = best[1]
             env.pilot_load(arrs)
         return history
+
+    def fit(self, epochs, batch_size, convs=("conv4", "conv5", "conv6", "conv7"), **kwargs):
+        """``fit_tail`` under the name of what it does by default here: dense1 .. output_layer and the convolutions named in ``convs`` (conv4 ..
+        conv7 unless told otherwise) are trained; conv1 .. conv3 stay as loaded, and there is no dropout."""
+        return self.fit_tail(epochs, batch_size, convs=convs, **kwargs)
 
 
 def _ffi_stream(stream):

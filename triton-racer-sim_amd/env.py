@@ -881,15 +881,31 @@ class BatchedEnv:
             c.train_mask = sum(1 << _ffi.TRAIN_LAYERS.index(nm) for nm in set(layers))
         return c
 
-    def pilot_train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None):
+    def pilot_train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None, convs=None):
         """Open a training session on the loaded pilot's dense tail (``trs_pilot_train_begin``): fp32 master weights from the arrays ``pilot_load``
-        was given, Adam's moments at zero.  22-array model types only; the convolutions stay as loaded.  Until ``pilot_train_end`` the handle
-        refuses ``pilot_load`` and ``pilot_tuning``; it drives with the current weights all along."""
+        was given, Adam's moments at zero.  22-array model types only.  ``convs``: names out of ``_ffi.TRAIN_CONV_LAYERS`` (``"conv4"`` ..
+        ``"conv7"``) that are trained as well (``trs_pilot_train_convs``); ``None``: the convolutions stay as loaded.  conv1 .. conv3 always do.
+        Until ``pilot_train_end`` the handle refuses ``pilot_load`` and ``pilot_tuning``; it drives with the current weights all along."""
         self._need_train()
         cfg = self.train_config(lr, beta1, beta2, eps, layers)
+        mask = 0
+        if convs is not None:
+            unknown = [nm for nm in convs if nm not in _ffi.TRAIN_CONV_LAYERS]
+            if unknown:
+                raise ValueError(f"convs must come from {_ffi.TRAIN_CONV_LAYERS}: {unknown}")
+            mask = sum(1 << _ffi.TRAIN_CONV_LAYERS.index(nm) for nm in set(convs))
         tail = self._pilot_arrays[14:22]
         ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in tail])
         self.api.check(self.api.pilot_train_begin(self._h, C.byref(cfg), ptrs), "pilot_train_begin")
+        self._train_convs = False
+        if convs is not None:                                           # (an empty list: the library's refusal of a zero mask)
+            cptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in self._pilot_arrays[6:14]])
+            rc = self.api.pilot_train_convs(self._h, mask, cptrs)
+            if rc != 0:
+                why = self.api.last_error()                             # the refusal's own text, before another call of the library replaces it
+                self.api.pilot_train_end(self._h)                       # no half-open session behind a refusal
+                raise RuntimeError(f"{self.api.prefix}pilot_train_convs failed ({rc}): {why.decode() if why else ''}")
+            self._train_convs = True
 
     def pilot_train_step(self, frames, labels, n=None, loss=None):
         """One Adam step on ``frames uint8[n, H, W, 3]`` and ``labels float32[n, 2]`` on the device (torch tensors, anything with
@@ -927,12 +943,43 @@ class BatchedEnv:
         self.api.check(self.api.pilot_train_get(self._h, ptrs, C.byref(t)), "pilot_train_get")
         return outs, int(t.value)
 
+    def pilot_train_conv_weights(self):
+        """The eight fp32 master arrays of conv4 .. conv7 (kernel ``[3, 3, CIN, COUT]`` and bias each) of a session opened with ``convs``
+        (``trs_pilot_train_get_convs``); a layer that is not trained comes back as it was loaded."""
+        self._need_train()
+        outs = [a.copy() for a in self._pilot_arrays[6:14]]
+        ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in outs])
+        self.api.check(self.api.pilot_train_get_convs(self._h, ptrs), "pilot_train_get_convs")
+        return outs
+
+    def pilot_train_debug_conv(self, layer, item):
+        """Item ``item`` (a key of ``_ffi.TRAIN_CONV_DEBUG``) of ``layer`` (``"conv4"`` .. ``"conv7"``) after the last training step as a flat
+        float32 array (``trs_pilot_train_debug_conv``); the caller reshapes."""
+        self._need_train()
+        j = _ffi.TRAIN_CONV_LAYERS.index(layer)
+        kern, n = self._pilot_arrays[6 + 2 * j], int(getattr(self, "_train_last_n", 0))
+        ih, iw = self.conv_input_size(j)
+        sizes = {"delta": n * (ih - 2) * (iw - 2) * kern.shape[3], "gw": kern.size, "mw": kern.size, "vw": kern.size, "pack": kern.size,
+                 "gb": kern.shape[3], "mb": kern.shape[3], "vb": kern.shape[3], "scale_exp": 1}
+        out = np.empty(sizes[item], np.float32)
+        self.api.check(self.api.pilot_train_debug_conv(self._h, j, _ffi.TRAIN_CONV_DEBUG[item], out.ctypes.data, out.size), "pilot_train_debug_conv")
+        return out
+
+    def conv_input_size(self, j):
+        """``(IH, IW)`` of conv(4 + j)'s input for this handle's frames: three 5 x 5 stride-2 valid layers, then j 3 x 3 stride-1 ones."""
+        h, w = int(self.H), int(self.W)
+        for _ in range(3):
+            h, w = (h - 5) // 2 + 1, (w - 5) // 2 + 1
+        return h - 2 * j, w - 2 * j
+
     def pilot_train_end(self):
-        """Close the session (``trs_pilot_train_end``).  The arrays ``pilot_weights`` returns keep the trained tail."""
+        """Close the session (``trs_pilot_train_end``).  The arrays ``pilot_weights`` returns keep the trained tail and convolutions."""
         self._need_train()
         tail, _ = self.pilot_train_weights()
+        convs = self.pilot_train_conv_weights() if getattr(self, "_train_convs", False) else list(self._pilot_arrays[6:14])
         self.api.check(self.api.pilot_train_end(self._h), "pilot_train_end")
-        self._pilot_arrays = list(self._pilot_arrays[:14]) + tail + list(self._pilot_arrays[22:])
+        self._train_convs = False
+        self._pilot_arrays = list(self._pilot_arrays[:6]) + convs + tail + list(self._pilot_arrays[22:])
 
     def pilot_weights(self):
         """The arrays given to ``pilot_load`` with the trained ones replaced (the masters of an open session, or what the last session left): ready
@@ -945,6 +992,8 @@ class BatchedEnv:
             ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in outs])
             if self.api.pilot_train_get(self._h, ptrs, None) == 0:      # an open session: its masters (refused without one: the arrays as kept)
                 arrs[14:22] = outs
+                if getattr(self, "_train_convs", False):
+                    arrs[6:14] = self.pilot_train_conv_weights()
         return arrs
 
     # -- scripted expert (include/trsim_spec.h, "scripted expert") ----------------------------------------------------------
