@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Are the gfx950 kernels of two source trees the same code?  (CPU only: hipcc cross-compiles to assembly.)
 
-    python scripts/kernel_diff.py <tree A> <tree B> [-j N]
+    python scripts/kernel_diff.py <tree A> <tree B> [-j N] [--rename OLD=NEW]...
 
 A tree is a checkout of this repository (`git archive <rev> | tar -x -C <dir>` gives one of any commit).  Every `*.hip` under its
 triton-racer-sim_amd/csrc is compiled with `-S --cuda-device-only` and the library's flags as that tree states them (HIPCC_FLAGS of its own __graft_entry__.py).  For every
 kernel symbol the instruction text between its label and its `.Lfunc_end` is compared — comments stripped, the function-order index of local labels
 (`.LBB<k>_` -> `.LBB_`) removed — and so is its metadata: register counts, LDS and scratch sizes, spill counts.  A kernel may live in another
-translation unit of the other tree: kernels are matched by name.  Exit status 0: the same set of kernels, each in exactly one unit, text and metadata
+translation unit of the other tree: kernels are matched by name.  `--rename OLD=NEW` (mangled symbols; repeatable) compares kernel OLD of tree A with
+kernel NEW of tree B, for a kernel whose symbol changed only because a parameter's type moved to another namespace: its own name inside the text is
+replaced before the comparison, and it is listed under NEW.  Exit status 0: the same set of kernels, each in exactly one unit, text and metadata
 identical."""
 import argparse
 import concurrent.futures
@@ -72,10 +74,16 @@ def main():
     ap.add_argument("tree_a")
     ap.add_argument("tree_b")
     ap.add_argument("-j", type=int, default=4, help="units compiled at a time")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="kernel OLD of tree A is kernel NEW of tree B (mangled symbols)")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         a = tree_kernels(os.path.abspath(args.tree_a), tmp, "a", args.j)
         b = tree_kernels(os.path.abspath(args.tree_b), tmp, "b", args.j)
+    for pair in args.rename:
+        old, _, new = pair.partition("=")
+        if old not in a or not new or new in a:
+            sys.exit(f"--rename {pair}: tree A has no kernel {old}, or already has {new}")
+        a[new] = [(unit, text.replace(old, new), meta) for unit, text, meta in a.pop(old)]
     bad = 0
     print(f"A = {args.tree_a}: {len(a)} kernels | B = {args.tree_b}: {len(b)} kernels")
     for name in sorted(set(a) | set(b)):

@@ -16,6 +16,10 @@ conv3 is faster than that torch step; the script prints the WHOLE device step (c
 step - forward, what training adds to a forward pass.  --convs combines with --drive for the split by kernel (the data and weight gradients against the
 forward chain kernel trs_conv_chain_kernel, about half their arithmetic); the copy leg moves the bytes of the convolutions' Adam pass (4 fp32 arrays read,
 3 written, two binary16 copies: 32 bytes per weight).  TRS_BENCH_SHAPE=0 or 1 in the environment runs one of the two shapes alone (a trace per shape).
+With --digest the script measures nothing: it prints `name sha256` lines of what three training steps with conv4 .. conv7 leave behind (every debug item of
+the tail and of every layer, the masters, and trs_pilot_forward's output afterwards) on seeded weights, frames and labels, at two small shapes that between
+them reach one and several chunks and slices of both weight-gradient GEMMs and all three channel shapes.  Two builds of the library (TRS_HIP_LIB) that
+compute the same bits print the same lines.
 Run from the repository root: python scripts/train_bench.py [--convs] [> profiles/rNN_train_tail.txt]"""
 import csv
 import glob
@@ -59,9 +63,58 @@ def stats(directory):
         print(f"  {name:40s} {c:6d} {t / c / 1e3:10.2f}")
 
 
+# (H, W, n_envs, the batch sizes in turn, three steps each).  93x100: conv7 is one pixel, F = 128 is one gW1 workgroup, every reduction one partial chunk.
+# 96x128, 70 frames: a second chunk of 6 frames for gW1; the convolutions' pixels in several slices, the last one short; then 3 frames: one partial chunk.
+DIGEST_CASES = [(93, 100, 5, (5,)), (96, 128, 70, (70, 3))]
+
+
+def digest():
+    import hashlib
+    import torch
+    from triton_racer_sim_amd import _ffi
+    from triton_racer_sim_amd.env import BatchedEnv
+
+    def line(name, array):
+        print(f"{name} {hashlib.sha256(np.ascontiguousarray(array).tobytes()).hexdigest()}", flush=True)
+
+    for case, (h, w, n_envs, batches) in enumerate(DIGEST_CASES, 1):
+        ws, _ = weights(h, w)
+        env = BatchedEnv(n_envs=n_envs, img_h=h, img_w=w, track=None)
+        env.pilot_load(ws)
+        env.pilot_train_begin(convs=_ffi.TRAIN_CONV_LAYERS)
+        rng = np.random.default_rng(case)
+        for n in batches:
+            frames = torch.from_numpy(rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)).cuda()
+            labels = torch.from_numpy(rng.uniform(-1, 1, (n, 2)).astype(np.float32)).cuda()
+            for _ in range(3):
+                env.pilot_train_step(frames, labels)
+            tag = f"case{case}.n{n}"
+            for item in _ffi.TRAIN_DEBUG:
+                if item in ("m", "v"):
+                    for a in range(8):
+                        line(f"{tag}.tail.{item}{a}", env.pilot_train_debug(item, a))
+                else:
+                    line(f"{tag}.tail.{item}", env.pilot_train_debug(item))
+            for layer in _ffi.TRAIN_CONV_LAYERS:
+                for item in _ffi.TRAIN_CONV_DEBUG:
+                    line(f"{tag}.{layer}.{item}", env.pilot_train_debug_conv(layer, item))
+            for a, master in enumerate(env.pilot_train_weights()[0]):
+                line(f"{tag}.tail.master{a}", master)
+            for a, master in enumerate(env.pilot_train_conv_weights()):
+                line(f"{tag}.conv.master{a}", master)
+            out = torch.empty((n, 2), device="cuda")
+            assert env.api.pilot_forward(env._h, int(frames.data_ptr()), n, int(out.data_ptr())) == 0
+            env.sync()
+            line(f"{tag}.forward", out.cpu().numpy())
+        env.pilot_train_end()
+        env.close()
+
+
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "--stats":
         return stats(sys.argv[2])
+    if "--digest" in sys.argv:
+        return digest()
     convs = "--convs" in sys.argv
     if convs:
         sys.argv.remove("--convs")

@@ -78,7 +78,7 @@ struct TrsLoopOps {
 // the pilot into the handle's control arrays (v->ctl_*) — or writes zero controls when no frame exists yet.  *fed: the frame that was fed (nullptr: none).
 int trs_internal_pilot_loop_check(trs_env* e, const trs_pilot_config* cfg, int n_steps);
 int trs_internal_pilot_tick(trs_env* e, const trs_pilot_config* cfg, TrsEnvView* v, const uint8_t** fed);
-// ---- training the pilot's tail (trsim_train.hip) ----
+// ---- training the pilot's tail (trsim_train.hip; the session itself is the training units' own: trsim_train_session.hpp) ----
 // The loaded pilot behind conv7 as a training step sees it: device pointers into the pilot's own buffers (views), defined in trsim_pilot.hip.
 struct TrsPilotTail {
     int arch, n_cap, G; size_t F;         // TRS_PILOT_*, the plan's capacity, dense1's granules and the flatten's length F = 8 G
@@ -103,11 +103,4 @@ struct TrsPilotConvs {
     } L[4];
 };
 int trs_internal_pilot_convs(trs_env* e, const TrsEnvView& v, bool materialise, TrsPilotConvs* out);
-// the open session as trsim_train_conv.hip's entry points see it (defined in trsim_train.hip): enter_session's refusals, then the conv part's slot
-struct TrsTrainView { void** conv; int64_t steps; int last_n; };
-int trs_internal_train_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrsTrainView* out);
-// one backward pass and Adam over the trained convolutions, on the stream, from the tail's q1 [n padded to 64][128] and its exponent; before the tail's own Adam.
-struct TrsAdamConsts { float b1, c1, b2, c2, eps, alpha; };   // beta1, 1 - beta1, beta2, 1 - beta2, epsilon, alpha_t of this step: what the tail's Adam uses
-int trs_train_conv_step(void* conv, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n, const TrsAdamConsts& ak);
-void trs_train_conv_free(void* conv);   // nullptr is fine
 void trs_expert_free(void* ctx);      // defined in trsim_expert.hip, called by trs_destroy and by trs_load_track (a new track switches the expert off); nullptr is fine

@@ -10,11 +10,12 @@
 //                             every MFMA fragment is two ds_read_b64_tr_b16.  A workgroup owns 128 features for the whole batch (wave w: features 32 w ..
 //                             32 w + 31 x the four 32-output blocks: four accumulators), so the order of the sum is fixed.  Row pitch 320 B: rows q = 0..3
 //                             of a transposed read start 16 banks apart, the two 16-lane groups of a half 8 apart, the four lanes of a row 2 apart —
-//                             no two lanes of a 32-lane half on one bank.
+//                             no two lanes of a 32-lane half on one bank.  The chunk loop is tr_gemm_chunks (trsim_train_dev.hpp), the one the
+//                             convolutions' weight gradient runs.
 //   trs_train_adam1_kernel    Adam over dense1's kernel: one thread per (granule, output) moves 8 masters and writes the binary16 granule the dense
 //                             kernel reads; trs_train_adam_kernel: the other seven arrays, written to the master and where the tail kernels read them
 // No floating-point atomics: two runs of a step agree bit for bit.  The rules that need no GPU (config, alpha_t, the scale's exponent, the buffers' layout)
-// are trsim_train.hpp.
+// are trsim_train.hpp; the session, which trsim_train_conv.hip's entry points open as well, is trsim_train_session.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -23,16 +24,12 @@
 #include <vector>
 
 #include "../../include/trsim.h"
-#include "trsim_internal.hpp"
-#include "trsim_mem.hpp"
-#include "trsim_train.hpp"
-#include "trsim_train_dev.hpp"
+#include "trsim_train_session.hpp"
 
 namespace {
 
 using namespace trsim;
-
-using namespace trsim_train_dev;      // the vector types, tr_fragment, Adam's update and the packed rounding: shared with trsim_train_conv.hip
+using namespace trsim_train_dev;      // the vector types, the GEMM's chunk loop, Adam's update and the small rules: shared with trsim_train_conv.hip
 
 // ---- forward behind dense1's slabs, and backward through the three small layers: one wave per frame -------------------------------
 struct TailTrainParams {
@@ -105,11 +102,7 @@ __global__ __launch_bounds__(256) void trs_train_tail_kernel(const TailTrainPara
         p.d1[(size_t)i * 100 + lane] = da;
         if (two) p.d1[(size_t)i * 100 + lane + 64] = db;
     }
-    // the batch's largest |delta1| as a bit pattern: non-negative binary32 values order like their patterns, and an integer maximum has no order
-    unsigned mx = max(__float_as_uint(da) & 0x7FFFFFFFu, __float_as_uint(db) & 0x7FFFFFFFu);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
-    if (lane == 0 && mx) atomicMax(p.max_bits, mx);
+    wave_max_bits(max(__float_as_uint(da) & 0x7FFFFFFFu, __float_as_uint(db) & 0x7FFFFFFFu), p.max_bits, lane);   // the batch's largest |delta1|
 }
 
 // ---- the small gradients and the loss: one thread per value, the frames in ascending order ----------------------------------------
@@ -196,7 +189,7 @@ __global__ __launch_bounds__(128) void trs_train_quant_kernel(const float* d1, c
     const int s = train_scale_exponent(*max_bits);
     if (i == 0 && o == 0) *sexp = s;
     _Float16 h = (_Float16)0.0f;
-    if (i < n && o < 100) h = (_Float16)(d1[(size_t)i * 100 + o] * __uint_as_float((unsigned)(s + 127) << 23));   // exact scaling, then round to nearest even
+    if (i < n && o < 100) h = (_Float16)(d1[(size_t)i * 100 + o] * pow2f(s));   // exact scaling, then round to nearest even
     q[(size_t)i * 128 + o] = __builtin_bit_cast(unsigned short, h);
 }
 
@@ -208,55 +201,28 @@ struct Gw1Params {
     const int* sexp;
     int n, n_pad, G;
 };
-// (the LDS chunk of 64 frames, its row pitch of 320 B and the transposed fragment read tr_fragment: trsim_train_dev.hpp)
+// (the LDS chunk of 64 frames, its row pitch of 320 B, the transposed fragment read and the chunk loop tr_gemm_chunks: trsim_train_dev.hpp)
 __global__ __launch_bounds__(256) void trs_train_gw1_kernel(const Gw1Params p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char tiles[2 * kGwTile];   // x7's tile, then q's: 40 KB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g0 = blockIdx.x * 16;                                         // the tile's first granule: features 128 blockIdx.x ..
-    // staging: a chunk is 64 frames x 16 granules of each operand; thread t moves granules e = t + 256 i (i < 4): frame e / 16, granule e % 16
-    u4v px[4], pq[4];
-    auto load = [&](int c0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + 256 * i, fr = c0 + (e >> 4), gi = e & 15;
-            u4v v = p.x7[(size_t)min(fr, p.n - 1) * p.G + g0 + gi];          // a frame past the batch: a valid address, a zero fragment
-            if (fr >= p.n) v = u4v{0u, 0u, 0u, 0u};
-            px[i] = v;
-            pq[i] = p.q[(size_t)fr * 16 + gi];                               // (padded with zeros up to n_pad)
-        }
-    };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int e = tid + 256 * i, off = (e >> 4) * kGwPitch + (e & 15) * 16;
-            *reinterpret_cast<u4v*>(tiles + off) = px[i];
-            *reinterpret_cast<u4v*>(tiles + kGwTile + off) = pq[i];
-        }
-    };
+    // 16 granules per frame of both operands: four staged granules per thread; wave w owns features 32 w .. against the four 32-output blocks
     f32x16 acc[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[b][i] = 0.0f;
-    load(0);
-    for (int c0 = 0; c0 < p.n_pad; c0 += kGwFrames) {
-        __syncthreads();                                                    // the chunk before has been read
-        store();
-        __syncthreads();
-        if (c0 + kGwFrames < p.n_pad) load(c0 + kGwFrames);                 // the next chunk is requested underneath
-        const int steps = min(4, (p.n - c0 + 15) >> 4);                     // k-steps of 16 frames that hold a frame of the batch
-        for (int ks = 0; ks < steps; ++ks) {
-            const h16x8 bx = tr_fragment(tiles, lane, 32 * wave, 16 * ks);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const h16x8 aq = tr_fragment(tiles + kGwTile, lane, 32 * b, 16 * ks);
-                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bx, acc[b], 0, 0, 0);
-            }
-        }
-    }
+    tr_gemm_chunks<4, 4>(tiles, 0, p.n_pad, p.n, wave, 0, acc,
+        [&](int fr, int gi) {
+            u4v v = p.x7[(size_t)min(fr, p.n - 1) * p.G + g0 + gi];          // a frame past the batch: a valid address, a zero fragment
+            if (fr >= p.n) v = u4v{0u, 0u, 0u, 0u};
+            return v;
+        },
+        [&](int fr, int gi) { return p.q[(size_t)fr * 16 + gi]; },           // (padded with zeros up to n_pad)
+        [](int) {});
     // D[output][feature]: lane = feature, registers 4 q4 .. + 3 = outputs 32 b + 8 q4 + 4 h .. + 3: one 16-byte store each, scaled back by 2^-s (exact)
-    const float back = __uint_as_float((unsigned)(127 - *p.sexp) << 23);
+    const float back = pow2f(-*p.sexp);
     const int h = lane >> 5;
     float* const row = p.gw1 + ((size_t)g0 * 8 + 32 * wave + (lane & 31)) * 100;
 #pragma unroll
@@ -303,53 +269,17 @@ __global__ __launch_bounds__(256) void trs_train_adam_kernel(const float* g, flo
     p.live[a][e - p.off[a]] = ww;
 }
 
-// ---- the session --------------------------------------------------------------------------------------------------------------------------
-struct TrainSession {
-    trs_train_config cfg{};
-    int64_t t = 0;
-    size_t F = 0; int n_cap = 0, last_n = 0;
-    TrainLayout L{};
-    DevBuf<float> master, m, v, g;        // one layout (TrainLayout): the eight arrays in order
-    DevBuf<float> fwd;                    // out | z1 | z2 | z3 | delta1 | delta2 | delta3 | delta4, each for n_cap frames
-    DevBuf<unsigned short> q;             // [n_cap padded to 64][128]
-    DevBuf<unsigned> scal;                // [0] max |delta1| bits, [1] the scale's exponent (int), [2] the loss (float)
-    void* conv = nullptr;                 // trsim_train_conv.hip's part of the session after trs_pilot_train_convs (released by trs_train_conv_free)
-    float* item(int which) const          // TRS_TRAIN_DBG_OUT .. DELTA4
-    {
-        static const int per[8] = {2, 100, 50, 25, 100, 50, 25, 2};
-        size_t o = 0;
-        for (int j = 0; j < which; ++j) o += (size_t)n_cap * per[j];
-        return fwd.get() + o;
-    }
-};
-
-const char* const kNoSession = "no training session on this pilot: trs_pilot_train_begin first";
-
-// how every entry point behind trs_pilot_train_begin begins: the view, the pilot's tail and its open session
-int enter_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrainSession** s)
+// ---- the session (trsim_train_session.hpp) ------------------------------------------------------------------------------------------------
+// where the tail kernels read arrays 1 .. 7; dense1's kernel, array 0, is read as the pack
+void tail_live(const TrsPilotTail& t, float* (&live)[kTrainArrays])
 {
-    if (int rc = trs_internal_pilot_tail(e, v, t)) return rc;
-    *s = static_cast<TrainSession*>(*t->train);
-    if (!*s) return trs_internal_fail(TRS_ERR_STATE, kNoSession);
-    return TRS_OK;
+    float* const at[kTrainArrays] = {nullptr, t.b1, t.w2, t.b2, t.w3, t.b3, t.w4, t.b4};
+    std::memcpy(live, at, sizeof at);
 }
 
 }  // namespace
 
-void trs_train_free(void* session)
-{
-    TrainSession* const s = static_cast<TrainSession*>(session);
-    if (s) trs_train_conv_free(s->conv);
-    delete s;
-}
-
-int trs_internal_train_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrsTrainView* out)
-{
-    TrainSession* s;
-    if (int rc = enter_session(e, v, t, &s)) return rc;
-    out->conv = &s->conv; out->steps = s->t; out->last_n = s->last_n;
-    return TRS_OK;
-}
+void trs_train_free(void* session) { delete static_cast<TrainSession*>(session); }
 
 TRS_EXPORT void trs_default_train_config(trs_train_config* cfg)
 {
@@ -375,13 +305,14 @@ TRS_EXPORT int trs_pilot_train_begin(trs_env* e, const trs_train_config* cfg_or_
     s->cfg = cfg; s->F = t.F; s->n_cap = t.n_cap; s->L = TrainLayout::of(t.F);
     const size_t total = s->L.off[kTrainArrays] * sizeof(float), n_pad = trsim::align_up((size_t)t.n_cap, kGwFrames);
     HIPCHK(s->master.alloc(total)); HIPCHK(s->m.alloc(total)); HIPCHK(s->v.alloc(total)); HIPCHK(s->g.alloc(total));
-    HIPCHK(s->fwd.alloc((size_t)t.n_cap * 354 * sizeof(float)));
+    HIPCHK(s->fwd.alloc((size_t)t.n_cap * train_frame_floats() * sizeof(float)));
     HIPCHK(s->q.alloc(n_pad * 128 * sizeof(unsigned short)));
     HIPCHK(s->scal.alloc(4 * sizeof(unsigned)));
     HIPCHK(hipStreamSynchronize(v.stream));
     HIPCHK(hipMemcpy(s->master.get(), h_tail_arrays[0], s->L.count(0) * sizeof(float), hipMemcpyHostToDevice));
     trs_internal_count(e, 0, (uint64_t)(s->L.count(0) * sizeof(float)));
-    const float* const live[kTrainArrays] = {nullptr, t.b1, t.w2, t.b2, t.w3, t.b3, t.w4, t.b4};
+    float* live[kTrainArrays];
+    tail_live(t, live);
     for (int a = 1; a < kTrainArrays; ++a)
         HIPCHK(hipMemcpyAsync(s->master.get() + s->L.off[a], live[a], s->L.count(a) * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
     HIPCHK(hipMemsetAsync(s->m.get(), 0, total, v.stream));
@@ -425,16 +356,13 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     hipLaunchKernelGGL(trs_train_gw1_kernel, dim3(t.G / 16), dim3(256), 0, st, gp);
     const trs_train_config& c = s->cfg;
     const AdamK k{c.beta1, trsim::train_one_minus(c.beta1), c.beta2, trsim::train_one_minus(c.beta2), c.eps, trsim::train_alpha(c, s->t + 1)};
-    if (s->conv) {                                                          // conv4 .. conv7 from delta1 and the dense1 copy the forward used: before Adam rewrites it
-        const TrsAdamConsts ak{k.b1, k.c1, k.b2, k.c2, k.eps, k.alpha};
-        if (int rc = trs_train_conv_step(s->conv, e, v, t, s->q.get(), reinterpret_cast<const int*>(scal + 1), n, ak)) return rc;
-    }
+    if (s->conv)                                                            // conv4 .. conv7 from delta1 and the dense1 copy the forward used: before Adam rewrites it
+        if (int rc = trs_train_conv_step(*s->conv, e, v, t, s->q.get(), reinterpret_cast<const int*>(scal + 1), n, k)) return rc;
     if (c.train_mask & 1u)
         hipLaunchKernelGGL(trs_train_adam1_kernel, dim3((t.G * 128 + 255) / 256), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), t.w1_pack, t.G, k);
     AdamSmallParams ap{};
     std::memcpy(ap.off, s->L.off, sizeof ap.off);
-    float* const live[kTrainArrays] = {nullptr, t.b1, t.w2, t.b2, t.w3, t.b3, t.w4, t.b4};
-    for (int a = 0; a < kTrainArrays; ++a) ap.live[a] = live[a];
+    tail_live(t, ap.live);
     ap.mask = c.train_mask;
     const size_t small = s->L.off[kTrainArrays] - s->L.off[1];
     hipLaunchKernelGGL(trs_train_adam_kernel, dim3((unsigned)((small + 255) / 256)), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), ap, k);
@@ -491,10 +419,7 @@ TRS_EXPORT int trs_pilot_train_debug(trs_env* e, int which, float* h_dst, size_t
     HIPCHK(hipMemcpy(pack.data(), t.w1_pack, pack.size() * 2, hipMemcpyDeviceToHost));
     for (size_t g = 0; g < (size_t)t.G; ++g)
         for (int j = 0; j < 8; ++j)
-            for (int co = 0; co < 100; ++co) {
-                _Float16 h; std::memcpy(&h, &pack[(g * 128 + co) * 8 + j], 2);
-                h_dst[(g * 8 + j) * 100 + co] = (float)h;
-            }
+            for (int co = 0; co < 100; ++co) h_dst[(g * 8 + j) * 100 + co] = widen_h(pack[(g * 128 + co) * 8 + j]);
     return TRS_OK;
 }
 
@@ -504,7 +429,7 @@ TRS_EXPORT int trs_pilot_train_end(trs_env* e)
     if (int rc = enter_session(e, &v, &t, &s)) return rc;
     HIPCHK(hipSetDevice(v.device));
     HIPCHK(hipStreamSynchronize(v.stream));
-    trs_train_free(s);
+    delete s;
     *t.train = nullptr;
     return TRS_OK;
 }

@@ -16,6 +16,16 @@ namespace trsim {
 constexpr int kTrainArrays = 8;
 constexpr int kTailIn[4] = {0, 100, 50, 25}, kTailOut[4] = {100, 50, 25, 2};   // kTailIn[0] is F, the flatten's length: TrainLayout::of fills it in
 constexpr uint32_t kTrainMaskAll = 0xFu;                                       // bit l: layer l of dense1, dense2, dense3, output_layer is trained
+// floats per frame of what a step keeps of its passes, TRS_TRAIN_DBG_OUT .. DELTA4 in order: out, z1 .. z3, delta1 .. delta4
+constexpr int kTrainFrameItems = 8;
+constexpr int kTrainFrameWidth[kTrainFrameItems] = {2, 100, 50, 25, 100, 50, 25, 2};
+// the floats of items 0 .. upto - 1 together: where item `upto` begins in a frame's worth, and with all eight the whole of it
+constexpr size_t train_frame_floats(int upto = kTrainFrameItems)
+{
+    size_t o = 0;
+    for (int j = 0; j < upto; ++j) o += (size_t)kTrainFrameWidth[j];
+    return o;
+}
 
 inline void train_defaults(trs_train_config* c)
 {
@@ -89,9 +99,8 @@ struct TrainLayout {
 // what trs_pilot_train_debug hands out (include/trsim.h, TRS_TRAIN_DBG_*): the number of floats of item `which` after a step of n frames, 0 for an unknown item
 inline size_t train_debug_floats(int which, int n, size_t F)
 {
-    static const int per_frame[8] = {2, 100, 50, 25, 100, 50, 25, 2};        // out, z1..z3, delta1..delta4
     const TrainLayout L = TrainLayout::of(F);
-    if (which >= TRS_TRAIN_DBG_OUT && which <= TRS_TRAIN_DBG_DELTA4) return (size_t)n * per_frame[which];
+    if (which >= TRS_TRAIN_DBG_OUT && which <= TRS_TRAIN_DBG_DELTA4) return (size_t)n * kTrainFrameWidth[which];
     if (which >= TRS_TRAIN_DBG_GW1 && which <= TRS_TRAIN_DBG_GW4) return L.count(2 * (which - TRS_TRAIN_DBG_GW1));
     if (which >= TRS_TRAIN_DBG_GB1 && which <= TRS_TRAIN_DBG_GB4) return L.count(2 * (which - TRS_TRAIN_DBG_GB1) + 1);
     if (which >= TRS_TRAIN_DBG_M && which < TRS_TRAIN_DBG_M + kTrainArrays) return L.count(which - TRS_TRAIN_DBG_M);

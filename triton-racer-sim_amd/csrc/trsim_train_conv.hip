@@ -11,7 +11,8 @@
 //                             copy of the kernel is [kh][kw][ci][co]: co is the fast index of both)
 //   trs_train_wgrad_kernel    the weight gradient's partial sums on the matrix cores: workgroup (slice, tap) stages 64 output pixels of q(l) and the 64
 //                             input pixels of x(l-1) that tap reads, [pixel][channel] as they lie, and reads transposed fragments (the reduction index, the
-//                             pixel, is the slow index of both); wave w owns a quarter of the CIN x COUT blocks of 32 x 32.  The workgroups of tap (0, 0)
+//                             pixel, is the slow index of both): tr_gemm_chunks (trsim_train_dev.hpp), the loop of the tail's gW1 kernel, with this
+//                             kernel's loaders; wave w owns a quarter of the CIN x COUT blocks of 32 x 32.  The workgroups of tap (0, 0)
 //                             also add q(l)'s rows per channel from the staged tile: the bias gradient's partial sums (256 / COUT row classes per chunk,
 //                             each a running sum in pixel order, added in order at the end)
 //   trs_train_cadam_kernel    thread per kernel or bias value: the slices' partial sums in slice order, times 2^-s_l; Adam; the master, the session's
@@ -26,26 +27,12 @@
 #include <vector>
 
 #include "../../include/trsim.h"
-#include "trsim_internal.hpp"
-#include "trsim_mem.hpp"
-#include "trsim_train.hpp"
-#include "trsim_train_conv.hpp"
-#include "trsim_train_dev.hpp"
+#include "trsim_train_session.hpp"
 
 namespace {
 
 using namespace trsim;
-using namespace trsim_train_dev;
-
-__device__ __forceinline__ bool h_positive(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u) > 0.0f; }
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }      // |e| <= 126
-// the wave's largest bit pattern into *dst (an integer maximum has no order)
-__device__ __forceinline__ void wave_max_bits(unsigned mx, unsigned* dst, int lane)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
-    if (lane == 0 && mx) atomicMax(dst, mx);
-}
+using namespace trsim_train_dev;      // the vector types, the GEMM's chunk loop, Adam's update and the small rules: shared with trsim_train.hip
 
 // ---- G7: the gradient at conv7's output ---------------------------------------------------------------------------------------------
 struct G7Params {
@@ -88,10 +75,7 @@ __global__ __launch_bounds__(256) void trs_train_g7_kernel(const G7Params p)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int fr = fb + 8 * (r >> 2) + 4 * h + (r & 3);
-            if (fr >= p.n) continue;
-            const float g = h_positive(p.x7[(size_t)fr * p.F + k]) ? acc[r] * back : 0.0f;
-            p.G[(size_t)fr * p.F + k] = g;
-            mx = max(mx, __float_as_uint(g) & 0x7FFFFFFFu);
+            if (fr < p.n) gated_store(p.G, p.x7, (size_t)fr * p.F + k, acc[r], back, mx);
         }
     }
     wave_max_bits(mx, p.max_bits, lane);
@@ -163,11 +147,7 @@ __global__ __launch_bounds__(256) void trs_train_dgrad_kernel(const DgradParams 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long px = p0 + 8 * (r >> 2) + 4 * h + (r & 3);
-            if (px >= p.M) continue;
-            const size_t at = (size_t)px * CIN + cb * 32 + (lane & 31);
-            const float g = h_positive(p.xin[at]) ? acc[cb][r] * back : 0.0f;
-            p.G[at] = g;
-            mx = max(mx, __float_as_uint(g) & 0x7FFFFFFFu);
+            if (px < p.M) gated_store(p.G, p.xin, (size_t)px * CIN + cb * 32 + (lane & 31), acc[cb][r], back, mx);
         }
     wave_max_bits(mx, p.max_bits, lane);
 }
@@ -184,66 +164,37 @@ struct WgradParams {
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void trs_train_wgrad_kernel(const WgradParams p)
 {
-    constexpr int XG = CIN / 8, QG = COUT / 8, XI = CIN / 32, QI = COUT / 32;       // granules per pixel; staged granules per thread and chunk
-    constexpr int PER = XI * QI / 4;                                                // 32 x 32 blocks per wave: 1, 2 or 4, all in one block row of ci
+    constexpr int XG = CIN / 8, QG = COUT / 8;                                      // granules per pixel: a quarter of them staged per thread and chunk
+    constexpr int PER = (CIN / 32) * (COUT / 32) / 4;                               // 32 x 32 blocks per wave: 1, 2 or 4, all in one block row of ci
+    static_assert(kConvChunk == kGwFrames, "the split's chunk is the loop's");
     __shared__ __attribute__((aligned(16))) unsigned char tiles[2 * kGwTile];       // x's tile, then q's: [pixel][channel], 40 KB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slice = blockIdx.x, tap = blockIdx.y, kh = tap / 3, kw = tap - 3 * kh;
     const long first = (long)slice * p.per_slice * kConvChunk, end = min(p.P, first + (long)p.per_slice * kConvChunk);
-    u4v rx[XI], rq[QI];
-    auto load = [&](long c0) {
-#pragma unroll
-        for (int i = 0; i < XI; ++i) {
-            const int e = tid + 256 * i;
-            const long px = c0 + e / XG;
-            u4v v = u4v{0u, 0u, 0u, 0u};
-            if (px < p.P) {                                                         // a pixel past the batch: a zero row
-                const int f = (int)(px / (p.OH * p.OW)), rem = (int)(px - (long)f * (p.OH * p.OW)), oy = rem / p.OW, ox = rem - oy * p.OW;
-                v = p.x[(((size_t)f * p.IH + oy + kh) * p.IW + ox + kw) * XG + e % XG];
-            }
-            rx[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < QI; ++i) {
-            const int e = tid + 256 * i;
-            const long px = c0 + e / QG;
-            rq[i] = px < p.P ? p.q[(size_t)px * QG + e % QG] : u4v{0u, 0u, 0u, 0u};
-        }
-    };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < XI; ++i) { const int e = tid + 256 * i; *reinterpret_cast<u4v*>(tiles + (e / XG) * kGwPitch + (e % XG) * 16) = rx[i]; }
-#pragma unroll
-        for (int i = 0; i < QI; ++i) { const int e = tid + 256 * i; *reinterpret_cast<u4v*>(tiles + kGwTile + (e / QG) * kGwPitch + (e % QG) * 16) = rq[i]; }
-    };
-    const int b0 = wave * PER, cib = b0 / QI, cob0 = b0 % QI;
+    const int b0 = wave * PER, cib = b0 / (COUT / 32), cob0 = b0 % (COUT / 32);
+    // the bias gradient rides on tap (0, 0): thread (br, bco) adds q's rows br, br + BR, .. of every chunk as they lie in the tile
+    constexpr int BR = 256 / COUT;
+    const int bco = tid % COUT, br = tid / COUT;
+    float bsum = 0.0f;
     f32x16 acc[PER];
 #pragma unroll
     for (int b = 0; b < PER; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[b][i] = 0.0f;
-    // the bias gradient rides on tap (0, 0): thread (br, bco) adds q's rows br, br + BR, .. of every chunk as they lie in the tile
-    constexpr int BR = 256 / COUT;
-    const int bco = tid % COUT, br = tid / COUT;
-    float bsum = 0.0f;
-    load(first);
-    for (long c0 = first; c0 < end; c0 += kConvChunk) {
-        __syncthreads();                                                            // the chunk before has been read
-        store();
-        __syncthreads();
-        if (c0 + kConvChunk < end) load(c0 + kConvChunk);
-        const int steps = (int)min(4L, (p.P - c0 + 15) >> 4);                       // k-steps of 16 pixels that hold a pixel of the batch
-        if (tap == 0)
-            for (int r = br; r < 16 * steps; r += BR) bsum += (float)*reinterpret_cast<const _Float16*>(tiles + kGwTile + r * kGwPitch + bco * 2);
-        for (int ks = 0; ks < steps; ++ks) {
-            const h16x8 bx = tr_fragment(tiles, lane, 32 * cib, 16 * ks);
-#pragma unroll
-            for (int b = 0; b < PER; ++b) {
-                const h16x8 aq = tr_fragment(tiles + kGwTile, lane, 32 * (cob0 + b), 16 * ks);
-                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bx, acc[b], 0, 0, 0);
+    tr_gemm_chunks<CIN / 32, COUT / 32>(tiles, first, end, p.P, cib, cob0, acc,
+        [&](long px, int gi) {
+            u4v v = u4v{0u, 0u, 0u, 0u};
+            if (px < p.P) {                                                         // a pixel past the batch: a zero row
+                const int f = (int)(px / (p.OH * p.OW)), rem = (int)(px - (long)f * (p.OH * p.OW)), oy = rem / p.OW, ox = rem - oy * p.OW;
+                v = p.x[(((size_t)f * p.IH + oy + kh) * p.IW + ox + kw) * XG + gi];
             }
-        }
-    }
+            return v;
+        },
+        [&](long px, int gi) { return px < p.P ? p.q[(size_t)px * QG + gi] : u4v{0u, 0u, 0u, 0u}; },
+        [&](int steps) {
+            if (tap == 0)
+                for (int r = br; r < 16 * steps; r += BR) bsum += (float)*reinterpret_cast<const _Float16*>(tiles + kGwTile + r * kGwPitch + bco * 2);
+        });
     // D[co][ci]: lane = ci, registers 4 q4 .. + 3 = co 32 cob + 8 q4 + 4 h .. + 3: one 16-byte store each
     const int h = lane >> 5;
     float* const row = p.part + (((size_t)slice * 9 + tap) * CIN + 32 * cib + (lane & 31)) * COUT;
@@ -290,60 +241,44 @@ __global__ __launch_bounds__(256) void trs_train_cadam_kernel(const ConvAdamPara
     if (is_bias) { p.bias[e - p.KK] = ww; return; }
     const unsigned short hw = f2h_pack(ww);
     p.wt[e] = hw;
-    const int co = e % p.COUT, t = e / p.COUT, ci = t % p.CIN, tap = t / p.CIN, kh = tap / 3, kw = tap - 3 * kh;
-    p.pack[((size_t)(kh * (3 * p.CIN / 8) + kw * (p.CIN / 8) + ci / 8) * p.COUT + co) * 8 + ci % 8] = hw;   // train_conv_packed_index
+    p.pack[train_conv_packed_index(p.CIN, p.COUT, e)] = hw;
 }
 
 __global__ __launch_bounds__(256) void trs_train_unpack_kernel(const unsigned short* pack, unsigned short* wt, int CIN, int COUT)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= 9 * CIN * COUT) return;
-    const int co = e % COUT, t = e / COUT, ci = t % CIN, tap = t / CIN, kh = tap / 3, kw = tap - 3 * kh;
-    wt[e] = pack[((size_t)(kh * (3 * CIN / 8) + kw * (CIN / 8) + ci / 8) * COUT + co) * 8 + ci % 8];
+    wt[e] = pack[train_conv_packed_index(CIN, COUT, e)];
 }
 
-// ---- the session's conv part ------------------------------------------------------------------------------------------------------------------
-struct ConvSession {
-    uint32_t mask = 0; int lowest = 0, n_cap = 0, cu_count = 0;
-    bool held[kConvTrainArrays] = {};       // the master holds this array (trained, or given all the same)
-    ConvTrainLayout L{};
-    ConvGeom geo[kConvTrainLayers] = {};
-    DevBuf<float> master, m, v, g;          // one layout (ConvTrainLayout)
-    DevBuf<unsigned short> wt;              // W(l)h as [3][3][CIN][COUT], at the kernels' offsets of the layout: the data-gradient kernel's copy
-    DevBuf<float> G, part;                  // G(l) of the layer in hand; the partial sums of the layer in hand (kernel, then bias)
-    DevBuf<unsigned short> q[kConvTrainLayers];
-    DevBuf<unsigned> scal;                  // [2 j] max |G(l)| bits, [2 j + 1] the exponent s_l (int)
-    bool trained(int j) const { return (mask >> j) & 1u; }
-};
-
+// ---- the session's conv part (ConvSession: trsim_train_session.hpp) ---------------------------------------------------------------------------
+// the instance of a kernel for one of train_conv_geom's three channel shapes (trs_pilot_train_convs refuses a pilot with any other)
 template <class P>
-void launch4(int cin, int cout, void (*k64_64)(P), void (*k64_128)(P), void (*k128_64)(P), void (*k128_128)(P), dim3 grid, hipStream_t st, const P& p)
+void launch3(const ConvGeom& g, void (*k64_64)(P), void (*k64_128)(P), void (*k128_128)(P), dim3 grid, hipStream_t st, const P& p)
 {
-    void (*const k)(P) = cin == 64 ? (cout == 64 ? k64_64 : k64_128) : (cout == 64 ? k128_64 : k128_128);
+    void (*const k)(P) = g.CIN == 128 ? k128_128 : (g.COUT == 128 ? k64_128 : k64_64);
     hipLaunchKernelGGL(k, grid, dim3(256), 0, st, p);
 }
 
-int enter_conv(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrsTrainView* tv, ConvSession** s)
+// enter_session, and the session's conv part
+int enter_conv(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrainSession** ts, ConvSession** s)
 {
-    if (int rc = trs_internal_train_session(e, v, t, tv)) return rc;
-    *s = static_cast<ConvSession*>(*tv->conv);
+    if (int rc = enter_session(e, v, t, ts)) return rc;
+    *s = (*ts)->conv.get();
     if (!*s) return trs_internal_fail(TRS_ERR_STATE, "this session trains no convolution: trs_pilot_train_convs first");
     return TRS_OK;
 }
 
 }  // namespace
 
-void trs_train_conv_free(void* conv) { delete static_cast<ConvSession*>(conv); }
-
-int trs_train_conv_step(void* conv, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n, const TrsAdamConsts& ak)
+int trsim::trs_train_conv_step(ConvSession& conv, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n, const AdamK& k)
 {
-    ConvSession* const s = static_cast<ConvSession*>(conv);
+    ConvSession* const s = &conv;
     TrsPilotConvs pc;
     if (int rc = trs_internal_pilot_convs(e, v, true, &pc)) return rc;                  // x4 .. x6 where the chain kept them in LDS
     hipStream_t st = v.stream;
     unsigned* const scal = s->scal.get();
     HIPCHK(hipMemsetAsync(scal, 0, 2 * kConvTrainLayers * sizeof(unsigned), st));
-    const AdamK k{ak.b1, ak.c1, ak.b2, ak.c2, ak.eps, ak.alpha};
     {
         G7Params gp{};
         gp.w1 = reinterpret_cast<const u4v*>(t.w1_pack); gp.q1 = reinterpret_cast<const u4v*>(q1); gp.x7 = static_cast<const unsigned short*>(t.x7);
@@ -361,8 +296,7 @@ int trs_train_conv_step(void* conv, trs_env* e, const TrsEnvView& v, const TrsPi
             dp.q = s->q[j].get(); dp.wt = s->wt.get() + s->L.off[2 * j]; dp.xin = static_cast<const unsigned short*>(pl.in); dp.G = s->G.get();
             dp.sexp = sexp; dp.max_bits = scal + 2 * (j - 1);
             dp.IH = g.IH; dp.IW = g.IW; dp.OH = g.OH; dp.OW = g.OW; dp.M = g.in_pixels(n);
-            launch4(g.CIN, g.COUT, trs_train_dgrad_kernel<64, 64>, trs_train_dgrad_kernel<64, 128>, trs_train_dgrad_kernel<128, 64>, trs_train_dgrad_kernel<128, 128>,
-                    dim3((unsigned)((dp.M + 127) / 128)), st, dp);
+            launch3(g, trs_train_dgrad_kernel<64, 64>, trs_train_dgrad_kernel<64, 128>, trs_train_dgrad_kernel<128, 128>, dim3((unsigned)((dp.M + 127) / 128)), st, dp);
         }
         if (!s->trained(j)) continue;
         const ConvSplit sp = train_conv_split(g, n, s->cu_count);
@@ -373,8 +307,7 @@ int trs_train_conv_step(void* conv, trs_env* e, const TrsEnvView& v, const TrsPi
         WgradParams wp{};
         wp.x = static_cast<const u4v*>(pl.in); wp.q = reinterpret_cast<const u4v*>(s->q[j].get()); wp.part = part; wp.bpart = bpart;
         wp.IH = g.IH; wp.IW = g.IW; wp.OH = g.OH; wp.OW = g.OW; wp.P = sp.P; wp.per_slice = sp.per_slice;
-        launch4(g.CIN, g.COUT, trs_train_wgrad_kernel<64, 64>, trs_train_wgrad_kernel<64, 128>, trs_train_wgrad_kernel<128, 64>, trs_train_wgrad_kernel<128, 128>,
-                dim3(sp.slices, 9), st, wp);
+        launch3(g, trs_train_wgrad_kernel<64, 64>, trs_train_wgrad_kernel<64, 128>, trs_train_wgrad_kernel<128, 128>, dim3(sp.slices, 9), st, wp);
         ConvAdamParams ap{};
         const size_t o = s->L.off[2 * j];
         ap.part = part; ap.bpart = bpart; ap.slices = sp.slices; ap.sexp = sexp;
@@ -389,10 +322,10 @@ int trs_train_conv_step(void* conv, trs_env* e, const TrsEnvView& v, const TrsPi
 
 TRS_EXPORT int trs_pilot_train_convs(trs_env* e, uint32_t conv_mask, const float* const* h_conv_arrays)
 {
-    TrsEnvView v; TrsPilotTail t; TrsTrainView tv;
-    if (int rc = trs_internal_train_session(e, &v, &t, &tv)) return rc;
-    if (*tv.conv) return trs_internal_fail(TRS_ERR_STATE, "trs_pilot_train_convs was already called in this session");
-    if (tv.steps > 0) return trs_internal_fail(TRS_ERR_STATE, "trs_pilot_train_convs comes before the session's first step");
+    TrsEnvView v; TrsPilotTail t; TrainSession* ts;
+    if (int rc = enter_session(e, &v, &t, &ts)) return rc;
+    if (ts->conv) return trs_internal_fail(TRS_ERR_STATE, "trs_pilot_train_convs was already called in this session");
+    if (ts->t > 0) return trs_internal_fail(TRS_ERR_STATE, "trs_pilot_train_convs comes before the session's first step");
     if (const char* why = train_conv_mask_error(conv_mask, h_conv_arrays)) return trs_internal_fail(TRS_ERR_ARG, why);
     HIPCHK(hipSetDevice(v.device));
     TrsPilotConvs pc;
@@ -431,14 +364,14 @@ TRS_EXPORT int trs_pilot_train_convs(trs_env* e, uint32_t conv_mask, const float
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(v.stream));
-    *tv.conv = s.release();
+    ts->conv = std::move(s);
     return TRS_OK;
 }
 
 TRS_EXPORT int trs_pilot_train_get_convs(trs_env* e, float* const* h_out)
 {
-    TrsEnvView v; TrsPilotTail t; TrsTrainView tv; ConvSession* s;
-    if (int rc = enter_conv(e, &v, &t, &tv, &s)) return rc;
+    TrsEnvView v; TrsPilotTail t; TrainSession* ts; ConvSession* s;
+    if (int rc = enter_conv(e, &v, &t, &ts, &s)) return rc;
     if (!h_out) return trs_internal_fail(TRS_ERR_ARG, "h_out is NULL");
     HIPCHK(hipSetDevice(v.device));
     HIPCHK(hipStreamSynchronize(v.stream));
@@ -452,12 +385,12 @@ TRS_EXPORT int trs_pilot_train_get_convs(trs_env* e, float* const* h_out)
 
 TRS_EXPORT int trs_pilot_train_debug_conv(trs_env* e, int layer, int which, float* h_dst, size_t n_floats)
 {
-    TrsEnvView v; TrsPilotTail t; TrsTrainView tv; ConvSession* s;
-    if (int rc = enter_conv(e, &v, &t, &tv, &s)) return rc;
-    if (!tv.last_n) return trs_internal_fail(TRS_ERR_STATE, "no training step yet");
+    TrsEnvView v; TrsPilotTail t; TrainSession* ts; ConvSession* s;
+    if (int rc = enter_conv(e, &v, &t, &ts, &s)) return rc;
+    if (!ts->last_n) return trs_internal_fail(TRS_ERR_STATE, "no training step yet");
     if (layer < 0 || layer >= kConvTrainLayers) return trs_internal_fail(TRS_ERR_ARG, "layer must be 0..3 (conv4 .. conv7)");
     const ConvGeom& g = s->geo[layer];
-    const size_t want = train_conv_debug_floats(g, which, tv.last_n);
+    const size_t want = train_conv_debug_floats(g, which, ts->last_n);
     if (!want || !h_dst) return trs_internal_fail(TRS_ERR_ARG, "unknown item (TRS_CONV_DBG_*) or NULL destination");
     if (n_floats != want) return trs_internal_fail(TRS_ERR_ARG, "size mismatch");
     if ((which == TRS_CONV_DBG_DELTA || which == TRS_CONV_DBG_SCALE_EXP) && layer < s->lowest)
@@ -482,12 +415,11 @@ TRS_EXPORT int trs_pilot_train_debug_conv(trs_env* e, int layer, int which, floa
     int sexp = 0;
     HIPCHK(hipMemcpy(&sexp, s->scal.get() + 2 * layer + 1, sizeof sexp, hipMemcpyDeviceToHost));
     if (which == TRS_CONV_DBG_SCALE_EXP) { h_dst[0] = (float)sexp; return TRS_OK; }
-    auto widen = [](unsigned short u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; };
     if (which == TRS_CONV_DBG_DELTA) {
         std::vector<unsigned short> q(want);
         HIPCHK(hipMemcpy(q.data(), s->q[layer].get(), want * 2, hipMemcpyDeviceToHost));
         const float back = train_pow2(-sexp);
-        for (size_t i = 0; i < want; ++i) h_dst[i] = widen(q[i]) * back;
+        for (size_t i = 0; i < want; ++i) h_dst[i] = widen_h(q[i]) * back;
         return TRS_OK;
     }
     // TRS_CONV_DBG_PACK: the granules the forward kernels read -> [3][3][CIN][COUT]
@@ -499,6 +431,6 @@ TRS_EXPORT int trs_pilot_train_debug_conv(trs_env* e, int layer, int which, floa
         for (int kw = 0; kw < 3; ++kw)
             for (int ci = 0; ci < g.CIN; ++ci)
                 for (int co = 0; co < g.COUT; ++co)
-                    h_dst[((size_t)(kh * 3 + kw) * g.CIN + ci) * g.COUT + co] = widen(pack[train_conv_packed_index(g, kh, kw, ci, co)]);
+                    h_dst[((size_t)(kh * 3 + kw) * g.CIN + ci) * g.COUT + co] = widen_h(pack[train_conv_packed_index(g, kh, kw, ci, co)]);
     return TRS_OK;
 }

@@ -10,6 +10,13 @@
 
 #include "../../include/trsim.h"
 
+// a rule the kernels apply as well: nothing to a plain host compiler
+#ifdef __HIPCC__
+#define TRS_HOST_DEVICE __host__ __device__
+#else
+#define TRS_HOST_DEVICE
+#endif
+
 namespace trsim {
 
 constexpr int kConvTrainLayers = 4;                  // conv4 .. conv7: bit j of the mask, layer j below, row 3 + j of the pilot's plan
@@ -63,10 +70,16 @@ struct ConvTrainLayout {
 
 // K[kh][kw][ci][co] in ConvLayer::w, in binary16 values: granule (kh run_pad + kw CIN / 8 + ci / 8) of output channel co, value ci % 8 of it (pack_layer;
 // run_pad == run == 3 CIN / 8 and COUT_PAD == COUT for these layers)
-inline size_t train_conv_packed_index(const ConvGeom& g, int kh, int kw, int ci, int co)
+TRS_HOST_DEVICE inline size_t train_conv_packed_index(const ConvGeom& g, int kh, int kw, int ci, int co)
 {
     const int run_pad = 3 * g.CIN / 8;
     return ((size_t)(kh * run_pad + kw * (g.CIN / 8) + ci / 8) * g.COUT + co) * 8 + ci % 8;
+}
+// the same for value number e of the Keras kernel [3][3][CIN][COUT]: how the kernels that keep both copies go from one to the other
+TRS_HOST_DEVICE inline size_t train_conv_packed_index(int CIN, int COUT, int e)
+{
+    const int co = e % COUT, t = e / COUT, ci = t % CIN, tap = t / CIN, kh = tap / 3, kw = tap - 3 * kh;
+    return train_conv_packed_index(ConvGeom{0, 0, 0, 0, CIN, COUT}, kh, kw, ci, co);
 }
 
 // The weight gradient reduces over the P = n OH OW output pixels in (frame, row, column) order.  They are cut into chunks of 64; slice s of `slices` takes

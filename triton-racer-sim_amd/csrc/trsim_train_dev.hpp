@@ -1,15 +1,9 @@
 // trsim_train_dev.hpp — the device-side pieces the two training units share (trsim_train.hip: the tail, trsim_train_conv.hip: conv4 .. conv7): the vector
-// types, the transposed LDS fragment read of a GEMM that reduces over the slow index of both operands, Adam's update in Keras's form and the binary16
-// rounding of a packed weight.  HIP only; the rules a host compiler can check are trsim_train.hpp and trsim_train_conv.hpp.
+// types, Adam's constants and update in Keras's form, the binary16 rounding of a packed weight, the small rules of a scaled gradient (2^e, the wave's largest
+// bit pattern, the gated store) and the GEMM that reduces over the slow index of both operands: its transposed LDS fragment read and its staged chunk loop.
+// HIP only; the rules a host compiler can check are trsim_train.hpp and trsim_train_conv.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
-
-// Adam's constants as a kernel parameter: beta1, 1 - beta1, beta2, 1 - beta2, epsilon, alpha_t.  The one definition, in an unnamed namespace on purpose: a
-// kernel's symbol carries its parameter types, and trs_train_adam1_kernel / trs_train_adam_kernel keep the symbols they had while this struct was
-// trsim_train.hip's own (scripts/kernel_diff.py matches kernels by symbol).
-namespace {
-struct AdamK { float b1, c1, b2, c2, eps, alpha; };
-}
 
 namespace trsim_train_dev {
 
@@ -18,6 +12,9 @@ typedef __attribute__((ext_vector_type(4))) _Float16 h16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 typedef float f4v __attribute__((ext_vector_type(4)));
+
+// Adam's constants as a kernel parameter: beta1, 1 - beta1, beta2, 1 - beta2, epsilon, alpha_t of the step
+struct AdamK { float b1, c1, b2, c2, eps, alpha; };
 
 constexpr int kGwFrames = 64;              // rows (frames, or pixels) per LDS chunk: four k-steps of 16
 constexpr int kGwPitch = 320;              // bytes per row of a tile: 128 values and 64 B that keep the transposed reads off each other's banks
@@ -36,6 +33,68 @@ __device__ __forceinline__ h16x8 tr_fragment(const unsigned char* tile, int lane
     const h16x4 lo = __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(a)));
     const h16x4 hi = __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(a + 4 * kGwPitch)));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// The chunk loop of that GEMM, D[q column][x column] += sum over rows first .. end - 1 of q[row][.] x[row][.], for a workgroup of 256 threads: 64 rows of both
+// operands per chunk, [row][value] as they lie in memory, x's tile at `tiles` and q's behind it.  A row of x holds 4 XI granules of 8 values and thread t
+// stages granules t + 256 i (i < XI) of a chunk, row e / (4 XI), granule e % (4 XI); q likewise with QI.  load_x and load_q, (row, granule) -> u4v, do the
+// caller's addressing and give zeros past the operand's end.  The next chunk's loads are requested while this one's MFMAs run.  Of a chunk only the k-steps
+// of 16 rows that hold one of the `rows` rows of the batch are multiplied.  The wave owns x's 32-column block `xb` against q's blocks qb0 .. qb0 + PER - 1:
+// the caller zeroes acc[b], element by element where it declares them (zeroed through a reference the compiler kept them out of the accumulation registers
+// between chunks).  per_chunk(steps) runs once per chunk while the tiles hold it (the weight gradient's bias sums).
+template <int XI, int QI, int PER, class Row, class LoadX, class LoadQ, class PerChunk>
+__device__ __forceinline__ void tr_gemm_chunks(unsigned char* tiles, Row first, Row end, Row rows, int xb, int qb0, f32x16 (&acc)[PER],
+                                               LoadX load_x, LoadQ load_q, PerChunk per_chunk)
+{
+    constexpr int XG = 4 * XI, QG = 4 * QI;
+    const int tid = threadIdx.x, lane = tid & 63;
+    u4v rx[XI], rq[QI];
+    auto load = [&](Row c0) {
+#pragma unroll
+        for (int i = 0; i < XI; ++i) { const int e = tid + 256 * i; rx[i] = load_x(c0 + e / XG, e % XG); }
+#pragma unroll
+        for (int i = 0; i < QI; ++i) { const int e = tid + 256 * i; rq[i] = load_q(c0 + e / QG, e % QG); }
+    };
+    auto store = [&]() {
+#pragma unroll
+        for (int i = 0; i < XI; ++i) { const int e = tid + 256 * i; *reinterpret_cast<u4v*>(tiles + (e / XG) * kGwPitch + (e % XG) * 16) = rx[i]; }
+#pragma unroll
+        for (int i = 0; i < QI; ++i) { const int e = tid + 256 * i; *reinterpret_cast<u4v*>(tiles + kGwTile + (e / QG) * kGwPitch + (e % QG) * 16) = rq[i]; }
+    };
+    load(first);
+    for (Row c0 = first; c0 < end; c0 += kGwFrames) {
+        __syncthreads();                                                            // the chunk before has been read
+        store();
+        __syncthreads();
+        if (c0 + kGwFrames < end) load(c0 + kGwFrames);                             // the next chunk is requested underneath
+        const int steps = (int)min((Row)4, (rows - c0 + 15) >> 4);
+        per_chunk(steps);
+        for (int ks = 0; ks < steps; ++ks) {
+            const h16x8 bx = tr_fragment(tiles, lane, 32 * xb, 16 * ks);
+#pragma unroll
+            for (int b = 0; b < PER; ++b) {
+                const h16x8 aq = tr_fragment(tiles + kGwTile, lane, 32 * (qb0 + b), 16 * ks);
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bx, acc[b], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// 2^e as a binary32 for |e| <= 126 (train_pow2 on the host): a scale and its inverse are exact
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+// The wave's largest bit pattern into *dst.  Non-negative binary32 values order like their patterns, and an integer maximum has no order.
+__device__ __forceinline__ void wave_max_bits(unsigned mx, unsigned* dst, int lane)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
+    if (lane == 0 && mx) atomicMax(dst, mx);
+}
+// how a data gradient leaves its kernel: G[at] = [x[at] > 0] . acc 2^-s, folded into the lane's largest |G| bit pattern
+__device__ __forceinline__ void gated_store(float* G, const unsigned short* x, size_t at, float acc, float back, unsigned& mx)
+{
+    const float g = (float)__builtin_bit_cast(_Float16, x[at]) > 0.0f ? acc * back : 0.0f;
+    G[at] = g;
+    mx = max(mx, __float_as_uint(g) & 0x7FFFFFFFu);
 }
 
 // plain binary32, every operation rounded by itself (the build has no contraction; sqrt and / are correctly rounded)
