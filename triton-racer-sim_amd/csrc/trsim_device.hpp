@@ -11,6 +11,7 @@
 #include "../../include/trsim.h"
 #include "../../include/trsim_spec.h"
 #include "trsim_plan.hpp"
+#include "trsim_scene.hpp"
 #include "trsim_tables.hpp"
 
 #ifndef TRS_ABLATE
@@ -44,27 +45,6 @@ struct PParams {                        // physics kernel
     unsigned long long seed;
 };
 
-// What the kernels need on a track with elevation.  It lives in device memory BEHIND the raster LDS image's bytes (RParams::blob + hill_block_offset): the kernel
-// arguments of the flat-track kernels are exactly what they were before tracks had elevation — arguments sit in scalar registers for the whole kernel, and even one
-// more pointer shifted the flat single-step launch by 2-4 % (profiles/r05_hills.txt).  Only the HILLS instantiations ever form this address.
-struct HillBlock {
-    const float* vpitch;                // [np] the view pitch of a frame whose nearest raw track point is idx: (float)pitch + dpitch[idx], one binary32 addition (host)
-    float* cam_pitch;                   // [kRing][n_envs] ring of the frames' view pitches beside PParams::cam (launch mode: the next launch's first frame)
-    int off_sky;                        // raster LDS image: uint32 sky[H] (the sky colour of every row; filtered by the host when a frame filter is set)
-    unsigned far_rgb;                   // (likewise)
-    float inv_f, hh, cam_h_f, z_far_f, inv_zfar_f, fog_f, inv_cell_f;
-    // the static frame filter (trs_set_frame_filter without dynamic brightness) on a track with elevation: the ground colours of a row are blended per env and
-    // frame, so the filter of ONE colour (img_preprocessing.py:37-74,92-99: the host's filter_colour) runs on each of them in hill_row_build
-    int filt, f_color, f_nfilters;
-    float f_contrast, f_offset;
-    unsigned f_lo[4], f_hi[4];          // packed h | s << 8 | v << 16
-    int f_dst[4];
-    const int* hsv_tab;                 // [512] OpenCV's sdiv | hdiv fixed-point reciprocals (global)
-    // scene lighting (trs_set_lighting; the LIGHT instantiations only, flat tracks included): the caller's float[n_envs][8] {gR gG gB 0 bR bG bB 0}.  With lighting
-    // set, the host keeps the palette, the sky colours and the far colour RAW and fills the static frame filter above: the kernels light, then filter
-    const float* light;
-};
-
 struct RParams {                        // raster side of the step kernel
     const unsigned char* blob;          // raster LDS image: map (pitched rows) @0 | rowtab | palette
     unsigned long long* stats;
@@ -76,38 +56,9 @@ struct RParams {                        // raster side of the step kernel
     int depth;                          // 1 = also write the binary32 z-depth frame
     int uni_rows;                       // leading image rows whose four class colours are equal (sky, beyond the far plane); 0 on a track with elevation
 };
-__host__ __device__ inline size_t hill_block_offset(int blob_bytes) { return ((size_t)blob_bytes + 63) & ~(size_t)63; }
-
-// What the LENS instantiations need (include/trsim_spec.h, "lens camera"): like HillBlock it lives in device memory behind the raster image, so the
-// flat kernels' arguments stay as they are.  The per-pixel table is stored for the RIGHT half of the frame only (u = W/2 + k, k in [0, W/2)): F, depth
-// and the palette row are even in u - W/2 and L is odd, so pixel W-1-u reads entry k with L negated.  Planes of [H][W/2], so that the 4 pixels of a
-// thread's column group are one 16-B load per plane (8 B for the rows).
-struct LensBlock {
-    const float* F;                     // [H][W/2] forward distance, cell units
-    const float* L;                     // [H][W/2] lateral distance, cell units (right half: + = right)
-    const float* D;                     // [H][W/2] z-depth (z_far for sky and far pixels)
-    const uint16_t* M;                  // [H][W/2] lens palette row: 0..255 ground G(q), 256..511 sky S(q), 512 FAR
-    const uint32_t* pal;                // [513][4] the lens palette (static frame filter applied), staged into LDS by the kernels
-    float oc;                           // (float)(offset_x / cell): the lateral mount, cell units
-    int wh;                             // W/2
-};
-__host__ __device__ inline size_t lens_block_offset(int blob_bytes) { return hill_block_offset(blob_bytes) + ((sizeof(HillBlock) + 63) & ~(size_t)63); }
-// the two blocks as a kernel reaches them (a uniform address: scalar loads)
+// The blocks behind the raster image (HillBlock, LensBlock: trsim_scene.hpp, like FParams) as a kernel reaches them (a uniform address: scalar loads)
 __device__ __forceinline__ const HillBlock* hill_block(const RParams& p) { return reinterpret_cast<const HillBlock*>(p.blob + hill_block_offset(p.blob_bytes)); }
 __device__ __forceinline__ const LensBlock* lens_block(const RParams& p) { return reinterpret_cast<const LensBlock*>(p.blob + lens_block_offset(p.blob_bytes)); }
-
-struct FParams {                        // ImgPreprocessing with dynamic brightness, evaluated inside the step kernels (their DYN instantiations)
-    double baseline;
-    float contrast, offset;
-    int color, n_filters;
-    int lo[4], hi[4], dst_ch[4];
-    int w0, w1;                         // brightness window: image rows [w0, w1) = img[40:119] (img_preprocessing.py:88)
-    int lds_off;                        // LDS: uint32 penv[4][H][4] | int esum[2][4][3] | int dbar | (128 B) | dyn tables (kDynTabWords)
-    const unsigned* tabs;               // global, kDynTabWords: int hsv[512] (OpenCV's sdiv | hdiv fixed-point reciprocals) | rngb[768] (byte masks of the
-                                        // in-range tests per component value, range_byte_entry) | sel — staged into LDS once per launch (round 4: the
-                                        // resident worker's raster waves then issue NO loads in their steady state)
-};
-constexpr int kDynCntAt = 512 + 768 + 4;
 
 }  // namespace trsim
 
@@ -128,6 +79,7 @@ using trsim::RParams;
 using trsim::FParams;
 using trsim::kDynTabWords;
 using trsim::kDynCntAt;
+using trsim::range_byte_entry;
 using trsim::Variant;
 using trsim::kVDepth; using trsim::kVDyn; using trsim::kVHills; using trsim::kVLens; using trsim::kVLight; using trsim::kVariants;
 using trsim::variant_bits;
@@ -970,22 +922,6 @@ __device__ __forceinline__ unsigned mask_pixel(unsigned P, const int* tab, const
     h = h < 0 ? h + 180 : h;
     const unsigned m = rngb[min(h, 255)] & rngb[256 + min(sat, 255)] & rngb[512 + v];
     return (m & sel) | (P & ~sel);
-}
-// entry i = c * 256 + x of the table above; *sel_out = the channels that carry a mask
-__host__ __device__ inline unsigned range_byte_entry(const unsigned (&lo)[4], const unsigned (&hi)[4], const int (&dst_ch)[4], int n_filters, int i, unsigned* sel_out)
-{
-    const int c = i >> 8, x = i & 255;
-    int fsel[3] = {-1, -1, -1};
-    for (int f = 0; f < n_filters; ++f) { const int dc = dst_ch[f]; if (dc >= 0 && dc <= 2) fsel[dc] = f; }
-    unsigned word = 0, sel = 0;
-    for (int ch = 0; ch < 3; ++ch) {
-        if (fsel[ch] < 0) continue;
-        const int l = (int)((lo[fsel[ch]] >> (8 * c)) & 255u), u = (int)((hi[fsel[ch]] >> (8 * c)) & 255u);
-        sel |= 0xFFu << (8 * ch);
-        if (x >= l && x <= u) word |= 0xFFu << (8 * ch);
-    }
-    if (sel_out) *sel_out = sel;
-    return word;
 }
 
 // ImgPreprocessing.__process of ONE colour with this frame's brightness delta (img_preprocessing.py:37-74,92-99): the

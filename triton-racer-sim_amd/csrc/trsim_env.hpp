@@ -17,7 +17,7 @@
 
 namespace trsim {
 struct Resident; struct Comm;
-// What trs_load_track and trs_set_camera stage beside the handle, check, and then move-assign into it (trsim_hip.hip): the struct a feature is staged in is the
+// What trs_load_track and trs_set_camera stage beside the handle, check, and then move-assign into it (trsim_scene.hip): the struct a feature is staged in is the
 // member the handle holds, so a commit is one assignment and "none" is the assignment of {}.  The old value's buffers are released by the assignment.
 struct TrackStage {                      // the device buffers of a track
     DevBuf<> blob_p, blob_r;             // physics LDS image | raster LDS image (+ the constants of a track with elevation and of the lens camera behind it)
@@ -43,21 +43,14 @@ struct trs_env {
     trsim::TrackStage trk;               // the loaded track's device buffers (track_commit)
     trsim::DevBuf<float4> cam;           // [kRing][n]
     trsim::DevBuf<float> cam_pitch;      // [kRing][n] the frames' view pitches (tracks with elevation)
-    bool hilly = false;                       // the loaded track has elevation (include/trsim_spec.h): the HILLS instantiations of the step kernels run
-    trsim::HillBlock hill_host{};             // host copy of the block behind the raster image (trs_load_track fills the camera part, upload_palette the frame filter)
-    // the lens camera (trs_set_camera; include/trsim_spec.h, "lens camera"): the LENS instantiations of the step kernels run while lens_on
-    trs_camera camera{};                      // what trs_set_camera set (all zero: the pinhole)
-    bool lens_on = false;
-    trsim::LensStage lens;                    // its tables for the loaded map, as lens_stage built them ({}: the pinhole, or no track yet)
-    // scene lighting (trs_set_lighting; include/trsim_spec.h, "scene lighting"): the LIGHT instantiations of the step kernels run while light_on
-    bool light_on = false;
-    const float* light = nullptr;             // view: the registered float[n][8], the caller's or light_own's
+    trsim::Scene scene;                       // what is rendered besides the track's geometry: the features set, the frame filter, the camera (trsim_scene.hpp)
+    trsim::LensStage lens;                    // the lens camera's tables for the loaded map, as lens_stage built them ({}: the pinhole, or no track yet)
+    const float* light = nullptr;             // view: scene lighting's registered float[n][8], the caller's or light_own's (nullptr unless scene.light_on)
     trsim::DevBuf<float> light_own;           // trs_set_lighting_host's copy
     trsim::ObsHistory obs;                    // observation latency (trs_set_latency; trsim_latency.hpp): while obs.on() every step renders into its ring and trs_obs_kernel runs behind it
     trsim::DevBuf<unsigned long long> stats;
     trsim::DevBuf<double> loc_q; trsim::DevBuf<int32_t> loc_out; int loc_cap = 0;   // trs_locate: room for loc_cap queries
     trsim::DevBuf<uint8_t> pre;          // processed frames of the env (trs_preprocess with d_dst == NULL)
-    trs_pre_config frame_filter{}; bool has_frame_filter = false, filter_dynamic = false;   // trs_set_frame_filter
     trsim::PinnedBuf<> pinned;           // trs_fetch_outputs staging
     trsim::DevBuf<int32_t> mux_state; int mux_tick = 0;   // ControlMultiplexer state per car (trs_control_mux)
     trsim::DevBuf<uint8_t> tmp_in, tmp_out; trsim::DevBuf<float> tmp_f; size_t tmp_cap = 0;   // host-frame staging with room for tmp_cap frames
@@ -130,34 +123,16 @@ void comm_destroy(trs_env* e);
 bool resident_running(const trs_env* e);
 void resident_clear_fault(trs_env* e);                     // trs_load_track puts every env on a defined state again
 int check_fault(trs_env* e);                               // TRS_ERR_DEVICE (sticky) once a kernel has reported a layout fault
-int ensure_hsv_table(trs_env* e);                          // e->hsv_tab holds OpenCV's reciprocal tables (hsv_reciprocals, trsim_filter.hpp); uploaded once (trsim_hip.hip)
+int ensure_hsv_table(trs_env* e);                          // e->hsv_tab holds OpenCV's reciprocal tables (hsv_reciprocals, trsim_filter.hpp); uploaded once (trsim_scene.hip)
 
-// the instantiation of the step kernel and of the resident worker that the handle's state selects (Variant, trsim_device.hpp)
-inline Variant variant_of(const trs_env* e)
-{
-    return variant_bits(e->rp.depth != 0, e->has_frame_filter && e->filter_dynamic, e->hilly, e->lens_on, e->light_on);
-}
-
-// one HSV bound of a colour filter (trs_pre_config::hsv_lo / hsv_hi) as the kernels take it: h | s << 8 | v << 16
-inline int pack_hsv(const uint8_t (&b)[3]) { return b[0] | (b[1] << 8) | (b[2] << 16); }
-
+// the instantiation of the step kernel and of the resident worker that the handle's state selects (Scene::variant, trsim_scene.hpp)
+inline Variant variant_of(const trs_env* e) { return e->scene.variant(e->rp.depth != 0); }
+// ... for the refusals by policy (variant_clash): a handle without a track has no HILLS bit, whatever a failed reload left behind
+inline Variant variant_now(const trs_env* e) { return variant_of(e) & (e->track_loaded ? ~0u : ~kVHills); }
+// The two LDS questions of every refusal, about the variant v the handle would run after the change beside lds_step bytes of tables (trsim_plan.hpp)
+inline LdsFit handle_fit(const trs_env* e, Variant v, int lds_step) { return lds_fit(lds_step, e->pp.envs_per_wg, e->H, e->W, v, resident_on(e)); }
 // the dynamic-brightness frame filter that is set, as the DYN instantiations take it (all zero without one); lds_off: its region in the kernel's LDS layout
-inline FParams fparams_of(const trs_env* e, int lds_off)
-{
-    FParams f;
-    std::memset(&f, 0, sizeof f);
-    if (!(e->has_frame_filter && e->filter_dynamic)) return f;
-    const trs_pre_config& c = e->frame_filter;
-    f.baseline = c.brightness_baseline; f.contrast = c.contrast_ratio; f.offset = c.contrast_offset;
-    f.color = c.color_filter_enabled; f.n_filters = c.n_filters;
-    for (int k = 0; k < 4; ++k) {
-        f.lo[k] = pack_hsv(c.hsv_lo[k]);
-        f.hi[k] = pack_hsv(c.hsv_hi[k]);
-        f.dst_ch[k] = c.dst_channel[k];
-    }
-    f.w0 = dyn_window_lo(e->H); f.w1 = dyn_window_hi(e->H);             // img[40:119] (img_preprocessing.py:88)
-    f.tabs = e->dyn_tab.get();
-    f.lds_off = lds_off;
-    return f;
-}
+inline FParams fparams_of(const trs_env* e, int lds_off) { return dyn_fparams(e->scene, e->H, e->dyn_tab.get(), lds_off); }
+// trsim_hip.hip's part in trs_load_track (trsim_scene.hip): its kernels may use the LDS the new track needs, or the refusal that they cannot
+int track_kernel_attributes(const trs_env* e, const TrackLayout& L, bool hills);
 }  // namespace trsim

@@ -5,10 +5,11 @@
 //                trsim_plan.hpp), trs_physics_kernel (camera off: the same wave-per-env routine, K steps per launch) and
 //                trs_locate_kernel (batched LocationTracker).  Their
 //                device-side pieces — the spec's arithmetic, the nearest-point search, the raster walk — are in trsim_device.hpp.
-//   host         the step dispatch (step_call: posted to the resident worker or launched), create / destroy, track loading, the lens camera, scene
-//                lighting, the palette upload with the static frame filter (trs_set_frame_filter), state, fetch, sync, events,
+//   host         the step dispatch (step_call: posted to the resident worker or launched), create / destroy, reset, pose, locate, state, fetch, sync, events,
 //                scratch, and the internal accessors the other translation units reach the handle through (trsim_internal.hpp, trsim_env.hpp).
 // The rest of the ABI lives in translation units of its own:
+//   trsim_scene.hip    what a handle renders: track loading, the lens camera, scene lighting, the palette upload with the static frame filter
+//                      (trs_set_frame_filter); trsim_scene.hpp, host only, decides and lays out what is uploaded; this unit gives it track_kernel_attributes
 //   trsim_image.hip    trs_preprocess (trim, colour masks, dynamic brightness, Canny) and trs_normalize, kernels and host
 //   trsim_control.hip  trs_driver_assist and trs_control_mux, kernels and host
 //   trsim_resident.hip the resident worker (trs_set_step_mode)            trsim_pilot.hip  the pilot network and trs_step_pilot
@@ -38,7 +39,6 @@
 #include "../../include/trsim_spec.h"
 #include "trsim_device.hpp"
 #include "trsim_env.hpp"
-#include "trsim_filter.hpp"
 #include "trsim_internal.hpp"
 #include "trsim_tables.hpp"
 
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void trs_step_kernel(const SParams sp)     
     STAMP(5);
 }
 
-// trs_step_kernel by variant bits, nullptr where none is built: the launch (launch_step) and the LDS attribute of every instantiation (trs_load_track) go through it
+// trs_step_kernel by variant bits, nullptr where none is built: the launch (launch_step) and the LDS attribute of every instantiation (track_kernel_attributes) go through it
 using StepKernel = void (*)(SParams);
 template <Variant V> StepKernel step_kernel_of()
 {
@@ -386,12 +386,7 @@ const float* latest_depth(const trs_env* e)
 }
 
 int grid_of(const trs_env* e) { return (e->n + e->pp.envs_per_wg - 1) / e->pp.envs_per_wg; }
-
-// The two LDS questions of every refusal, about the variant v the handle would run after the change beside lds_step bytes of tables (trsim_plan.hpp)
-trsim::LdsFit handle_fit(const trs_env* e, Variant v, int lds_step) { return trsim::lds_fit(lds_step, e->pp.envs_per_wg, e->H, e->W, v, trsim::resident_on(e)); }
 int steps_that_fit(const trs_env* e, Variant v, int lds_step) { return trsim::steps_that_fit(lds_step, e->pp.envs_per_wg, e->H, e->W, v); }
-// The variant the handle runs now, for the refusals by policy (variant_clash): a handle without a track has no HILLS bit, whatever a failed reload left behind
-Variant variant_now(const trs_env* e) { return trsim::variant_of(e) & (e->track_loaded ? ~0u : ~kVHills); }
 
 // the handle's stream is idle: a resident worker (trs_set_step_mode) is asked to leave first — it owns the stream while it runs
 int sync_all(trs_env* e)
@@ -693,311 +688,19 @@ TRS_EXPORT int trs_destroy(trs_env* e)
     return TRS_OK;
 }
 
-// OpenCV's reciprocal tables (hsv_reciprocals, trsim_filter.hpp) on the device, uploaded once per handle: trs_preprocess (trsim_image.hip) and the
-// in-kernel static filter of a track with elevation / scene lighting (upload_palette) read them from there
-int trsim::ensure_hsv_table(trs_env* e)
-{
-    if (e->hsv_tab.get()) return TRS_OK;
-    int tab[512];
-    trsim::hsv_reciprocals(tab);
-    HIPCHK(e->hsv_tab.alloc(sizeof tab));
-    HIPCHK(hipMemcpy(e->hsv_tab.get(), tab, sizeof tab, hipMemcpyHostToDevice));
-    return TRS_OK;
-}
-
-namespace {
-// ---- the palette and the lens tables: what trs_load_track and the setters below (frame filter, camera, lighting) upload ----
-int leading_uniform_rows(const std::vector<uint32_t>& pal, int H)
-{
-    int u = 0;
-    while (u < H && pal[4 * u] == pal[4 * u + 1] && pal[4 * u] == pal[4 * u + 2] && pal[4 * u] == pal[4 * u + 3]) ++u;
-    return u;
-}
-
-// the tables the DYN step kernels stage into LDS (FParams::tabs): OpenCV's reciprocals | the in-range byte masks of THIS filter | sel
-int upload_dyn_tables(trs_env* e, const trs_pre_config& c)
-{
-    int rc = trsim::ensure_hsv_table(e);
-    if (rc) return rc;
-    std::vector<unsigned> t(kDynTabWords, 0u);
-    trsim::hsv_reciprocals(reinterpret_cast<int*>(t.data()));     // (the same 512 words the device table holds)
-    unsigned lo[4], hi[4]; int dc[4];
-    for (int k = 0; k < 4; ++k) {
-        lo[k] = (unsigned)trsim::pack_hsv(c.hsv_lo[k]);
-        hi[k] = (unsigned)trsim::pack_hsv(c.hsv_hi[k]);
-        dc[k] = c.dst_channel[k];
-    }
-    unsigned sel = 0;
-    for (int i = 0; i < 768; ++i) t[512 + i] = range_byte_entry(lo, hi, dc, c.n_filters, i, &sel);
-    t[512 + 768] = sel;
-    for (int i = 0; i < 256; ++i) {                                           // class counts of a 4-pixel pack: n0 | n1 << 8 | n2 << 16 | n3 << 24
-        unsigned cnt = 0;
-        for (int k = 0; k < 4; ++k) cnt += 1u << (8 * ((i >> (2 * k)) & 3));
-        t[trsim::kDynCntAt + i] = cnt;
-    }
-    { int rq = quiesce(e); if (rq) return rq; HIPCHK(hipStreamSynchronize(e->sP)); }   // a running kernel may still be staging the old tables
-    HIPCHK(e->dyn_tab.reserve(kDynTabWords * sizeof(unsigned)));   // (allocated once: the size is fixed)
-    HIPCHK(hipMemcpy(e->dyn_tab.get(), t.data(), kDynTabWords * sizeof(unsigned), hipMemcpyHostToDevice));
-    return TRS_OK;
-}
-
-// (re)write the palette of the raster LDS image: raw, or filtered when a frame filter is set
-int upload_palette(trs_env* e)
-{
-    if (!e->track_loaded || !e->cfg.render) return TRS_OK;
-    std::vector<uint32_t> pal(e->tab.palette);
-    if (e->has_frame_filter && !e->filter_dynamic && !e->light_on)   // dynamic brightness: the kernel filters a per-env palette itself; scene lighting: lit, then filtered, in the kernel
-        for (auto& c : pal) c = trsim::filter_colour(e->frame_filter, c);
-    { int rq = sync_all(e); if (rq) return rq; }               // frames in flight keep the palette they were launched with (a resident worker leaves here and reports what it rendered)
-    e->rp.uni_rows = (e->hilly || e->lens_on) ? 0 : leading_uniform_rows(pal, e->H);   // (a track with elevation: which rows are sky depends on the env and the frame;
-    e->uniform_ok.invalidate();                                //  the lens camera: on the pixel)  (steps skip uniform rows an earlier step wrote: not across a palette change)
-    HIPCHK(hipMemcpy(e->trk.blob_r.get() + e->rp.off_pal, pal.data(), pal.size() * 4, hipMemcpyHostToDevice));
-    if (e->lens_on && e->lens.dev.get()) {                           // the lens palette: the static frame filter applied to every entry, as to the flat rows above
-        std::vector<uint32_t> lp(e->lens.T.palette);
-        if (e->has_frame_filter && !e->filter_dynamic)
-            for (auto& c : lp) c = trsim::filter_colour(e->frame_filter, c);
-        HIPCHK(hipMemcpy(e->lens.dev.get() + e->lens.pal_off, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (e->hilly || e->light_on) {
-        // a track with elevation: the kernels blend a row's ground colours per env and frame and run the static filter on each (hill_filter_colour); the sky colours and
-        // the far colour are constants: filtered here — unless scene lighting is set, which comes first (the kernels light, then filter every colour; a flat track's
-        // LIGHT kernels read the filter from this block as well)
-        const bool flt = e->has_frame_filter && !e->filter_dynamic;
-        trsim::HillBlock& hb = e->hill_host;
-        std::vector<uint32_t> sky(e->tab.sky);
-        hb.far_rgb = e->tab.far_rgb;
-        hb.filt = flt ? 1 : 0;
-        hb.light = e->light_on ? e->light : nullptr;
-        if (flt) {
-            const trs_pre_config& c = e->frame_filter;
-            if (!e->light_on) {
-                for (auto& v : sky) v = trsim::filter_colour(c, v);
-                hb.far_rgb = trsim::filter_colour(c, hb.far_rgb);
-            }
-            { int rc = trsim::ensure_hsv_table(e); if (rc) return rc; }
-            hb.f_color = c.color_filter_enabled; hb.f_nfilters = c.n_filters; hb.f_contrast = c.contrast_ratio; hb.f_offset = c.contrast_offset;
-            for (int k = 0; k < 4; ++k) {
-                hb.f_lo[k] = (unsigned)trsim::pack_hsv(c.hsv_lo[k]);
-                hb.f_hi[k] = (unsigned)trsim::pack_hsv(c.hsv_hi[k]);
-                hb.f_dst[k] = c.dst_channel[k];
-            }
-            hb.hsv_tab = e->hsv_tab.get();
-        }
-        if (e->hilly) HIPCHK(hipMemcpy(e->trk.blob_r.get() + hb.off_sky, sky.data(), sky.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->trk.blob_r.get() + trsim::hill_block_offset(e->rp.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
-    }
-    return TRS_OK;
-}
-
-using trsim::LensStage; using trsim::TrackStage;           // what the handle holds as e->lens and e->trk (trsim_env.hpp)
-
-// The lens tables of a map for a camera (include/trsim_spec.h, "lens camera"), STAGED: host tables in binary64, the half-width planes and the palette
-// (static frame filter applied) in a device buffer of their own, and the LensBlock written into the raster image `blob_r` (the new track's, not yet committed,
-// in trs_load_track; the handle's own, with nothing in flight, in trs_set_camera).  Nothing of the handle changes here: the caller moves S into e->lens.
-// `lds_step` / `cell`: the step kernel's LDS image and the map cell of the track the tables are for.  *block_written (optional): the copy into blob_r was begun.
-int lens_stage(const trs_env* e, const trs_camera& cam, int lds_step, double cell, unsigned char* blob_r, int blob_bytes, LensStage& S, bool* block_written = nullptr)
-{
-    if (handle_fit(e, variant_bits(e->rp.depth != 0, false, false, true, false), lds_step) == trsim::LdsFit::no_launch)   // (a lens excludes the other variants)
-        return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lens camera's palette (" + std::to_string(lds_step) + " B of tables at " +
-                                   std::to_string(e->pp.envs_per_wg) + " envs per workgroup): the lens camera needs a shorter track or fewer envs per GPU");
-    std::string err;
-    int rc = trsim::build_lens_tables(e->cfg, cell, cam.fish_eye_x, cam.fish_eye_y, S.T, err);
-    if (rc) return fail(rc, err);
-    const trsim::LensTables& T = S.T;
-    const int H = e->H, W = e->W, wh = W / 2;
-    const size_t plane = trsim::align_up((size_t)H * wh * 4, 256), mplane = trsim::align_up((size_t)H * wh * 2, 256);
-    const size_t off_L = plane, off_D = 2 * plane, off_M = 3 * plane, off_pal = 3 * plane + mplane;
-    const size_t bytes = off_pal + (size_t)trsim::kLensPalBytes;
-    std::vector<unsigned char> h(bytes, 0);
-    for (int v = 0; v < H; ++v)
-        for (int k = 0; k < wh; ++k) {
-            const float* px = &T.pix[((size_t)v * W + wh + k) * 4];
-            const size_t i = (size_t)v * wh + k;
-            uint32_t row;
-            std::memcpy(&row, &px[3], 4);
-            const uint16_t m = (uint16_t)row;
-            std::memcpy(h.data() + i * 4, &px[0], 4);
-            std::memcpy(h.data() + off_L + i * 4, &px[1], 4);
-            std::memcpy(h.data() + off_D + i * 4, &px[2], 4);
-            std::memcpy(h.data() + off_M + i * 2, &m, 2);
-        }
-    std::vector<uint32_t> lp(T.palette);
-    if (e->has_frame_filter && !e->filter_dynamic)
-        for (auto& c : lp) c = trsim::filter_colour(e->frame_filter, c);
-    std::memcpy(h.data() + off_pal, lp.data(), lp.size() * 4);
-    HIPCHK(S.dev.alloc(bytes));
-    HIPCHK(hipMemcpy(S.dev.get(), h.data(), bytes, hipMemcpyHostToDevice));
-    trsim::LensBlock lb{};
-    unsigned char* const d = S.dev.get();
-    lb.F = reinterpret_cast<const float*>(d); lb.L = reinterpret_cast<const float*>(d + off_L); lb.D = reinterpret_cast<const float*>(d + off_D);
-    lb.M = reinterpret_cast<const uint16_t*>(d + off_M); lb.pal = reinterpret_cast<const uint32_t*>(d + off_pal);
-    lb.oc = (float)(cam.offset_x / cell);
-    lb.wh = wh;
-    if (block_written) *block_written = true;                // (from here on the slot in blob_r may hold a partial block when the copy fails)
-    HIPCHK(hipMemcpy(blob_r + trsim::lens_block_offset(blob_bytes), &lb, sizeof lb, hipMemcpyHostToDevice));
-    S.pal_off = off_pal;
-    return TRS_OK;
-}
-
-// ---- trs_load_track, step by step.  Transactional: everything is built into copies (tables, layout, parameter blocks, device buffers: a TrackStage, released
-// unless moved into the handle) and committed only after every check, allocation and copy has succeeded — a failed reload leaves the handle with the track it
-// had (or with none), never with new offsets against old blobs.
-
-int track_upload(const trsim::TrackTables& T, const std::vector<unsigned char>& hp, const std::vector<unsigned char>& hr, TrackStage& S)
-{
-    const size_t n_points = (size_t)T.n_points;
-    HIPCHK(S.blob_p.alloc(hp.size()));
-    HIPCHK(S.blob_r.alloc(trsim::lens_block_offset((int)hr.size()) + sizeof(trsim::LensBlock)));   // (+ the constants of a track with elevation and of the lens camera, behind the image)
-    HIPCHK(S.tangent.alloc(n_points * 8));
-    HIPCHK(S.start_yaw.alloc(n_points * 4));
-    HIPCHK(hipMemcpy(S.blob_p.get(), hp.data(), hp.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(S.blob_r.get(), hr.data(), hr.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(S.tangent.get(), T.tangent.data(), n_points * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(S.start_yaw.get(), T.start_yaw.data(), n_points * 4, hipMemcpyHostToDevice));
-    HIPCHK(S.dpitch.alloc(n_points * 4));
-    // the view pitch of a frame whose nearest raw track point is idx: pitch_f + dpitch[idx], ONE binary32 addition as the spec has it
-    std::vector<float> vp(n_points);
-    for (size_t i = 0; i < n_points; ++i) vp[i] = T.pitch_f + T.dpitch[i];
-    HIPCHK(hipMemcpy(S.dpitch.get(), vp.data(), n_points * 4, hipMemcpyHostToDevice));
-    return TRS_OK;
-}
-
-// the kernels' parameter blocks for the new track: copies of the handle's with the layout, the tables' constants and the staged buffers
-void track_params(const trsim::TrackTables& T, const trsim::TrackLayout& L, const TrackStage& S, PParams& k, RParams& r)
-{
-    k.off_py = L.p.off_py; k.off_pz = L.p.off_pz; k.off_tan = L.p.off_tan; k.tan_in_lds = L.p.tan_in_lds;
-    k.grid_nx = T.grid_nx; k.grid_nz = T.grid_nz; k.grid_x0 = T.grid_x0; k.grid_z0 = T.grid_z0;
-    k.off_gstart = L.p.off_gstart; k.off_gpts = L.p.off_gpts; k.blob_bytes = L.p.blob_bytes; k.off_scratch = L.p.off_scratch;
-    r.map_pitch_b = L.r.map_pitch_b; r.off_rowtab = L.r.off_rowtab; r.off_pal = L.r.off_pal; r.off_depth = L.r.off_depth; r.blob_bytes = L.r.blob_bytes;
-    k.blob = S.blob_p.get(); k.start_yaw = S.start_yaw.get(); k.tangent_g = S.tangent.get();
-    r.blob = S.blob_r.get();
-    k.np = T.n_points; r.map_w = T.info.map_w; r.map_h = T.info.map_h;
-    k.map_x0f = T.map_x0f; k.map_z0f = T.map_z0f; k.inv_cellf = T.inv_cellf;
-}
-
-// the kernels may use the LDS the new track needs — and the fused kernel has room for one step per launch beside it
-int track_kernel_attributes(const trs_env* e, const trsim::TrackLayout& L, bool hills)
+// trs_load_track (trsim_scene.hip) before it commits a track: the kernels may use the LDS the new track needs — and the fused kernel has room for one step
+// per launch beside it
+int trsim::track_kernel_attributes(const trs_env* e, const trsim::TrackLayout& L, bool hills)
 {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_physics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L.p.lds_p));
     // room in the CU's 160 KiB for one step per launch of the camera hand-off ring (on a track with elevation: and the per-env row tables); the frame filter,
     // the lens camera and scene lighting that are set are checked later, each with its own message
-    if (e->cfg.render && handle_fit(e, variant_bits(e->rp.depth != 0, false, hills, false, false), L.lds_step) == trsim::LdsFit::no_launch)
+    if (e->cfg.render && trsim::handle_fit(e, variant_bits(e->rp.depth != 0, false, hills, false, false), L.lds_step) == trsim::LdsFit::no_launch)
         return fail(TRS_ERR_LIMIT, hills ? "no LDS left for the camera hand-off ring and the per-env row tables of a track with elevation" : "no LDS left for the camera hand-off ring");
     for (const StepKernel sk : kStepKernels)
         if (sk) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sk), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(trs_locate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L.p.blob_bytes));
     return TRS_OK;
-}
-
-// the lens camera, when one is set: its tables for the new map (its cell size) and its LensBlock behind the NEW raster image, before anything is committed —
-// a track that leaves no LDS for the lens palette is refused like any other, and the handle keeps its track and its lens
-int track_lens_stage(const trs_env* e, const trsim::TrackTables& T, const trsim::TrackLayout& L, TrackStage& S, LensStage& ls)
-{
-    trsim::LensBlock none{};                                 // (the slot is never read while no lens is set; defined contents all the same)
-    HIPCHK(hipMemcpy(S.blob_r.get() + trsim::lens_block_offset(L.r.blob_bytes), &none, sizeof none, hipMemcpyHostToDevice));
-    return e->lens_on ? lens_stage(e, e->camera, L.lds_step, T.info.cell, S.blob_r.get(), L.r.blob_bytes, ls) : TRS_OK;
-}
-
-// ---- commit: nothing before this has touched the handle ----
-int track_commit(trs_env* e, trsim::TrackTables& T, const trsim::TrackLayout& L, TrackStage& S, const PParams& k, const RParams& r, LensStage& ls)
-{
-    e->track_loaded = false;                                 // (until the state arrays are in place: track_start_poses)
-    e->trk = std::move(S);                                   // (the old track's buffers are released)
-    trsim::HillBlock& hb = e->hill_host;                     // (host copy: upload_palette fills in the frame filter and sends the block again)
-    hb = trsim::HillBlock{};
-    hb.vpitch = e->trk.dpitch.get(); hb.cam_pitch = e->cam_pitch.get(); hb.off_sky = L.r.off_sky; hb.far_rgb = T.far_rgb;
-    hb.inv_f = T.inv_f; hb.hh = T.hh; hb.cam_h_f = T.cam_h_f; hb.z_far_f = T.z_far_f; hb.inv_zfar_f = T.inv_zfar_f; hb.fog_f = T.fog_f; hb.inv_cell_f = T.inv_cellf;
-    e->hilly = T.hills;
-    HIPCHK(hipMemcpy(e->trk.blob_r.get() + trsim::hill_block_offset(r.blob_bytes), &hb, sizeof hb, hipMemcpyHostToDevice));
-    if (e->lens_on) e->lens = std::move(ls);                 // (the old map's tables are released)
-    e->tab = std::move(T);
-    e->pp = k; e->rp = r;
-    e->lds_r = L.r.lds_r; e->lds_p = L.p.lds_p; e->lds_step = L.lds_step; e->lds_off_phys = L.lds_off_phys; e->pts_bytes = L.p.pts_bytes;
-    return TRS_OK;
-}
-
-// start poses (host mirror of the reset branch so that telemetry is meaningful before the first step)
-int track_start_poses(trs_env* e)
-{
-    const trsim::TrackTables& TT = e->tab;
-    const PParams& k = e->pp;
-    const size_t n = (size_t)e->n;
-    std::vector<float> sx(n), sy(n), sz(n), syaw(n);
-    std::vector<int32_t> sidx(n);
-    for (size_t i = 0; i < n; ++i) {
-        const int gid = e->cfg.env_id_base + (int)i;
-        const int si = (int)(((long long)TRS_START_STRIDE * gid) % TT.n_points);
-        sx[i] = (float)TT.px[si]; sy[i] = (float)TT.py[si]; sz[i] = (float)TT.pz[si]; syaw[i] = TT.start_yaw[si]; sidx[i] = si;
-    }
-    HIPCHK(hipMemcpy(k.x, sx.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(k.y, sy.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(k.z, sz.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(k.yaw, syaw.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(k.seg_idx, sidx.data(), n * 4, hipMemcpyHostToDevice));
-    for (float* a : {k.v, k.speed, k.cte, k.ep_return, k.last_return, k.steer_filt}) HIPCHK(hipMemset(a, 0, n * 4));
-    HIPCHK(hipMemset(k.ep_len, 0, n * 4));
-    HIPCHK(hipMemset(k.done, 0, n));
-    HIPCHK(hipMemset(k.pending, 1, n));
-    HIPCHK(hipMemset(e->stats.get(), 0, 64 * sizeof(unsigned long long)));
-    e->step_count = 0;
-    e->track_loaded = true;
-    trsim::resident_clear_fault(e);
-    return TRS_OK;
-}
-
-// The features that were set and that the committed track has no kernel (`clash`: the dynamic-brightness filter on a track with elevation, see
-// variant_refusal) or no LDS for are removed, with an error return; otherwise the palette of the new track goes up
-int track_drop_misfits(trs_env* e, Variant clash)
-{
-    auto drop_filter = [&](int code, const char* why) {
-        e->has_frame_filter = false; e->filter_dynamic = false;
-        (void)upload_palette(e);
-        return fail(code, why);
-    };
-    const Variant v = trsim::variant_of(e);                  // (HILLS, e->lds_step: the new track's)
-    if (clash == kVDyn) return drop_filter(TRS_ERR_STATE, trsim::variant_refusal(kVHills, kVDyn));
-    if ((v & kVDyn) && handle_fit(e, v & ~kVLight, e->lds_step) == trsim::LdsFit::no_launch)   // (the filter alone; with lighting: below)
-        return drop_filter(TRS_ERR_LIMIT, "this track leaves no LDS for the dynamic-brightness frame filter that was set: the filter has been removed");
-    if ((v & kVLight) && handle_fit(e, v, e->lds_step) == trsim::LdsFit::no_launch) {
-        e->light_on = false; e->light = nullptr;
-        (void)upload_palette(e);
-        return fail(TRS_ERR_LIMIT, "this track leaves no LDS for the scene lighting that was set: lighting has been removed");
-    }
-    return upload_palette(e);                 // also sets rp.uni_rows (and applies a frame filter that was set earlier)
-}
-}  // namespace
-
-TRS_EXPORT int trs_load_track(trs_env* e, const double* h_xyz, int n_points)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    HIPCHK(hipSetDevice(e->device));
-    int rc = sync_all(e);
-    if (rc) return rc;
-    std::string err;
-    trsim::TrackTables T;
-    rc = trsim::build_tables(e->cfg, h_xyz, n_points, T, err);
-    if (rc) return fail(rc, err);
-    // the new track's HILLS bit against what is set: a lens camera refuses the track now, the dynamic-brightness filter is removed after the commit
-    const Variant clash = trsim::variant_clash(trsim::variant_of(e) & ~kVHills, T.hills ? kVHills : 0u);
-    if (clash == kVLens) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVHills, clash));
-    trsim::TrackLayout L;
-    rc = trsim::track_layout(T, e->H, e->cfg.render != 0, e->pp.envs_per_wg, L, err);
-    if (rc) return fail(rc, err);
-    std::vector<unsigned char> hp, hr;
-    trsim::pack_track_images(T, e->H, L, hp, hr);
-    TrackStage S;
-    if ((rc = track_upload(T, hp, hr, S))) return rc;
-    PParams k = e->pp;
-    RParams r = e->rp;
-    track_params(T, L, S, k, r);
-    if ((rc = track_kernel_attributes(e, L, T.hills))) return rc;
-    LensStage ls;
-    if ((rc = track_lens_stage(e, T, L, S, ls))) return rc;
-    if ((rc = track_commit(e, T, L, S, k, r, ls))) return rc;
-    if (e->expert) { trs_expert_free(e->expert); e->expert = nullptr; }   // the scripted expert's tables were the old track's (the handle is idle: sync_all above)
-    if ((rc = track_start_poses(e))) return rc;
-    if (e->obs.on() && (rc = trsim::latency_restart(e))) return rc;  // the observations of the old track's steps do not reach the new one
-    return track_drop_misfits(e, clash);
 }
 
 TRS_EXPORT int trs_reset(trs_env* e, const uint8_t* h_mask)
@@ -1116,8 +819,8 @@ TRS_EXPORT int trs_copy_to_host(trs_env* e, int which, void* dst, size_t bytes)
     case TRS_F_PALETTE: if (e->track_loaded) { src = e->trk.blob_r.get() + e->rp.off_pal; need = (size_t)e->H * 16; } break;
     case TRS_F_TANGENT: if (e->track_loaded) { src = e->trk.tangent.get(); need = (size_t)k.np * 8; } break;
     case TRS_F_DPITCH: if (e->track_loaded) { src = e->tab.dpitch.data(); need = e->tab.dpitch.size() * 4; host_src = true; } break;
-    case TRS_F_LENS_TABLE: if (e->track_loaded && e->lens_on) { src = e->lens.T.pix.data(); need = e->lens.T.pix.size() * 4; host_src = true; } break;
-    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->lens_on && e->lens.dev.get()) { src = e->lens.dev.get() + e->lens.pal_off; need = (size_t)trsim::kLensPalBytes; } break;
+    case TRS_F_LENS_TABLE: if (e->track_loaded && e->scene.lens_on) { src = e->lens.T.pix.data(); need = e->lens.T.pix.size() * 4; host_src = true; } break;
+    case TRS_F_LENS_PALETTE: if (e->track_loaded && e->scene.lens_on && e->lens.dev.get()) { src = e->lens.dev.get() + e->lens.pal_off; need = (size_t)trsim::kLensPalBytes; } break;
     default: return fail(TRS_ERR_ARG, "unknown field");
     }
     if (!src) return fail(TRS_ERR_STATE, "field not available");
@@ -1226,155 +929,6 @@ TRS_EXPORT int trs_locate(trs_env* e, const double* h_xyz, int nq, int32_t* h_id
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_idx, e->loc_out.get(), (size_t)nq * 4, hipMemcpyDeviceToHost, e->sP));
     HIPCHK(hipStreamSynchronize(e->sP));
-    return TRS_OK;
-}
-
-
-// ---- frame filter, camera, lighting -----------------------------------------------------------------------
-
-TRS_EXPORT int trs_set_frame_filter(trs_env* e, const trs_pre_config* c)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
-    if (c) {
-        const char* why = nullptr;
-        int rc = trsim::check_pre(c, &why);
-        if (rc) return fail(rc, why);
-        if (e->codec_quality)
-            return fail(TRS_ERR_STATE, "a camera codec is set (trs_set_camera_codec): the fused filter would run in front of it, the reference filters the decoded frame: "
-                                       "use trs_preprocess on the codec's frames");
-        if (c->edge_detection_enabled) return fail(TRS_ERR_ARG, "the Canny layer is a neighbourhood operator: not a palette filter, use trs_preprocess");
-        if (c->dynamic_brightness)
-            if (const Variant set = trsim::variant_clash(variant_now(e), kVDyn)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVDyn, set));
-        if (c->dynamic_brightness) {
-            const int rpp = kRasterThreads / (e->W / 4);
-            if (rpp < 1 || (79 + rpp - 1) / rpp > 16) return fail(TRS_ERR_LIMIT, "image too wide for the in-kernel dynamic-brightness filter (class bits of the brightness rows live in 4 registers), use trs_preprocess");
-            const Variant v = trsim::variant_of(e) | kVDyn;       // what the handle runs with this filter: checked without, then with, its scene lighting
-            if (e->track_loaded && handle_fit(e, v & ~kVLight, e->lds_step) == trsim::LdsFit::no_launch)
-                return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the in-kernel dynamic-brightness palette, use trs_preprocess");
-            const trsim::LdsFit fit = e->track_loaded ? handle_fit(e, v, e->lds_step) : trsim::LdsFit::ok;
-            if (fit == trsim::LdsFit::no_launch)             // (only with scene lighting: the filter alone fits)
-                return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the dynamic-brightness palettes with scene lighting, use trs_preprocess");
-            // resident mode: the worker keeps its env state and hand-off ring in LDS as well — refuse HERE, with the reason, what every later
-            // trs_step would otherwise refuse as "too many envs per workgroup" 
-            if (fit == trsim::LdsFit::no_worker)
-                return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the dynamic-brightness palettes of a batch: "
-                                           "select TRS_STEP_LAUNCH for this filter, or use trs_preprocess");
-        }
-        if (c->dynamic_brightness) { HIPCHK(hipSetDevice(e->device)); rc = upload_dyn_tables(e, *c); if (rc) return rc; }
-        e->frame_filter = *c; e->has_frame_filter = true; e->filter_dynamic = c->dynamic_brightness != 0;
-    } else {
-        e->has_frame_filter = false;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    return upload_palette(e);
-}
-
-TRS_EXPORT void trs_default_camera(trs_camera* c)
-{
-    if (!c) return;
-    std::memset(c, 0, sizeof *c);
-    c->struct_size = (uint32_t)sizeof *c;
-}
-
-TRS_EXPORT int trs_set_camera(trs_env* e, const trs_camera* c)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    trs_camera nc;
-    trs_default_camera(&nc);
-    if (c) {
-        if (c->struct_size != sizeof(trs_camera)) return fail(TRS_ERR_ARG, "trs_camera.struct_size mismatch");
-        if (!(c->fish_eye_x >= 0.0 && c->fish_eye_x <= 2.0)) return fail(TRS_ERR_ARG, "fish_eye_x must lie in [0, 2]");
-        if (!(c->fish_eye_y >= 0.0 && c->fish_eye_y <= 2.0)) return fail(TRS_ERR_ARG, "fish_eye_y must lie in [0, 2]");
-        if (!(c->offset_x >= -2.0 && c->offset_x <= 2.0)) return fail(TRS_ERR_ARG, "offset_x must lie in [-2, 2] world units");
-        nc.fish_eye_x = c->fish_eye_x; nc.fish_eye_y = c->fish_eye_y; nc.offset_x = c->offset_x;
-    }
-    const bool on = nc.fish_eye_x != 0.0 || nc.fish_eye_y != 0.0 || nc.offset_x != 0.0;
-    if (on) {
-        if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
-        if (e->W % 8) return fail(TRS_ERR_LIMIT, "the lens camera needs an image width that is a multiple of 8 (the kernels store half of the mirror-symmetric table)");
-        if (const Variant set = trsim::variant_clash(variant_now(e), kVLens)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVLens, set));
-    }
-    HIPCHK(hipSetDevice(e->device));
-    // nothing may be in flight, and a resident worker leaves, BEFORE anything of the camera changes (the worker's quiesce can still launch for steps
-    // posted earlier: they run with the camera they were posted under)
-    { int rq = sync_all(e); if (rq) return rq; }
-    if (on && e->track_loaded) {
-        LensStage ls;
-        bool block_written = false;
-        int rc = lens_stage(e, nc, e->lds_step, e->tab.info.cell, e->trk.blob_r.get(), e->rp.blob_bytes, ls, &block_written);
-        if (rc) {
-            if (e->lens_on && block_written) {               // the copy of the block failed: the handle's LensBlock may be half written, the old lens cannot stay
-                const std::string why = g_err;
-                e->lens = {}; e->lens_on = false; trs_default_camera(&e->camera);
-                (void)upload_palette(e);
-                return fail(rc, why + " (the lens camera that was set has been removed: the pinhole camera renders)");
-            }
-            return rc;                                       // (the handle is unchanged: no lens before, whose block slot is never read, or the old block untouched)
-        }
-        e->lens = std::move(ls);                             // (the old tables are released: nothing is in flight)
-    }
-    e->camera = nc; e->lens_on = on;
-    if (!on) e->lens = {};                                   // back to the pinhole: the tables are not kept
-    return upload_palette(e);                                // uni_rows, the lens palette with the frame filter
-}
-
-// scene lighting (include/trsim_spec.h, "scene lighting"): register the caller's float[n_envs][8] (NULL: back to the unlit kernels)
-namespace {
-int set_lighting_impl(trs_env* e, const float* d_params, trsim::DevBuf<float> own = {})   // own: the host entry point's copy behind d_params, released on a refusal
-{
-    const bool on = d_params != nullptr;
-    if (on) {
-        if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
-        if (const Variant set = trsim::variant_clash(variant_now(e), kVLight)) return fail(TRS_ERR_STATE, trsim::variant_refusal(kVLight, set));
-        const trsim::LdsFit fit = e->track_loaded ? handle_fit(e, trsim::variant_of(e) | kVLight, e->lds_step) : trsim::LdsFit::ok;   // what the handle runs with lighting
-        if (fit == trsim::LdsFit::no_launch)
-            return fail(TRS_ERR_LIMIT, "no LDS left beside this track's tables for the lit palettes");
-        if (fit == trsim::LdsFit::no_worker)
-            return fail(TRS_ERR_LIMIT, "the resident worker's LDS (tables + env state + hand-off ring) leaves no room for the lighting parameters and lit palettes: select TRS_STEP_LAUNCH");
-    }
-    // nothing may be in flight and a resident worker leaves before the kernels change (upload_palette quiesces too; the old host copy is freed after that)
-    { int rq = sync_all(e); if (rq) return rq; }
-    e->light_own = std::move(own);                         // (the old host copy is released here, after the wait)
-    e->light = d_params; e->light_on = on;
-    return upload_palette(e);                              // raw palette + the filter for the kernels, the parameters' address in the block behind the raster image
-}
-}  // namespace
-
-TRS_EXPORT int trs_set_lighting(trs_env* e, const float* d_params)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    HIPCHK(hipSetDevice(e->device));
-    return set_lighting_impl(e, d_params);
-}
-
-TRS_EXPORT int trs_set_lighting_host(trs_env* e, const float* h_params)
-{
-    if (!e) return fail(TRS_ERR_ARG, "null handle");
-    HIPCHK(hipSetDevice(e->device));
-    if (!h_params) return set_lighting_impl(e, nullptr);
-    if (!e->cfg.render) return fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
-    trsim::DevBuf<float> own;
-    const size_t bytes = (size_t)e->n * 8 * sizeof(float);
-    HIPCHK(own.alloc(bytes));
-    if (hipMemcpy(own.get(), h_params, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(TRS_ERR_DEVICE, "hipMemcpy of the lighting parameters failed");
-    const float* d_params = own.get();
-    return set_lighting_impl(e, d_params, std::move(own));
-}
-
-TRS_EXPORT int trs_get_camera(trs_env* e, trs_camera* out)
-{
-    if (!e || !out) return fail(TRS_ERR_ARG, "null argument");
-    *out = e->camera;
-    out->struct_size = (uint32_t)sizeof *out;
-    return TRS_OK;
-}
-
-TRS_EXPORT int trs_map_info_get(trs_env* e, trs_map_info* o)
-{
-    if (!e || !o || !e->track_loaded) return fail(TRS_ERR_STATE, "no track loaded");
-    *o = e->tab.info;
-    o->lds_bytes = e->cfg.render ? e->lds_step : e->lds_p;
     return TRS_OK;
 }
 

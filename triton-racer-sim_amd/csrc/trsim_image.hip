@@ -640,11 +640,8 @@ TRS_EXPORT int trs_preprocess(trs_env* e, const trs_pre_config* c, const uint8_t
     p.r0 = std::min(40, e->H); p.r1 = std::min(119, e->H);                 // img[40:119] (img_preprocessing.py:88)
     p.dynamic = c->dynamic_brightness; p.color = c->color_filter_enabled; p.n_filters = c->n_filters;
     p.contrast = c->contrast_ratio; p.offset = c->contrast_offset; p.baseline = c->brightness_baseline;
-    for (int f = 0; f < 4; ++f) {
-        p.lo[f] = trsim::pack_hsv(c->hsv_lo[f]);
-        p.hi[f] = trsim::pack_hsv(c->hsv_hi[f]);
-        p.dst_ch[f] = c->dst_channel[f];
-    }
+    const trsim::FilterBounds fb = trsim::filter_bounds(*c);
+    std::memcpy(p.lo, fb.lo, sizeof p.lo); std::memcpy(p.hi, fb.hi, sizeof p.hi); std::memcpy(p.dst_ch, fb.dst, sizeof p.dst_ch);
     if (c->edge_detection_enabled) {
         p.edge = 1; p.edge_ch = c->edge_dst_channel;
         p.edge_low = std::min(c->edge_threshold_a, c->edge_threshold_b);          // cv::Canny swaps the thresholds into order

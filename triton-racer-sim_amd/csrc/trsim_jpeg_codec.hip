@@ -187,7 +187,7 @@ TRS_EXPORT int trs_set_camera_codec(trs_env* e, int quality)
     if (quality < 0 || quality > 100) return trs_internal_fail(TRS_ERR_ARG, "quality must be in [1, 100], or 0 for no codec");
     if (quality == 0) { e->codec_quality = 0; return TRS_OK; }
     if (!e->cfg.render) return trs_internal_fail(TRS_ERR_STATE, "the env has no camera (cfg.render == 0)");
-    if (e->has_frame_filter)
+    if (e->scene.has_filter)
         return trs_internal_fail(TRS_ERR_STATE, "a frame filter is set (trs_set_frame_filter): it would run in front of the codec, the reference filters the decoded frame: "
                                                 "remove it and run trs_preprocess on the codec's frames");
     int rc = check_size(e);

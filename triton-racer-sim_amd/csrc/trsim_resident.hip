@@ -1046,9 +1046,9 @@ int worker_fits(trs_env* e)
     const WorkerLds L = worker_lds_layout(e->lds_step, e->pp.envs_per_wg, e->H, e->W, variant_of(e));   // behind the tables
     R->lds_off_ctl = L.ctl; R->lds_off_dyn = L.dyn; R->lds_off_hill = L.hill; R->lds_bytes = L.total;
     if (R->lds_bytes > 160 * 1024)
-        return trs_internal_fail(TRS_ERR_LIMIT, e->hilly ? "the resident worker's LDS state and the per-env row tables of a track with elevation do not fit beside this track's tables: use TRS_STEP_LAUNCH"
-                                                : e->lens_on ? "the resident worker's LDS state and the lens camera's palette do not fit beside this track's tables: use TRS_STEP_LAUNCH"
-                                                : e->light_on ? "the resident worker's LDS state and the lit palettes of scene lighting do not fit beside this track's tables: use TRS_STEP_LAUNCH"
+        return trs_internal_fail(TRS_ERR_LIMIT, e->scene.hilly ? "the resident worker's LDS state and the per-env row tables of a track with elevation do not fit beside this track's tables: use TRS_STEP_LAUNCH"
+                                                : e->scene.lens_on ? "the resident worker's LDS state and the lens camera's palette do not fit beside this track's tables: use TRS_STEP_LAUNCH"
+                                                : e->scene.light_on ? "the resident worker's LDS state and the lit palettes of scene lighting do not fit beside this track's tables: use TRS_STEP_LAUNCH"
                                                             : "too many envs per workgroup for the resident worker's LDS state");
     return TRS_OK;
 }
