@@ -720,8 +720,9 @@ int trs_loader_augment(const trs_loader_config* cfg, const trs_augment_config* a
  * loaded pilot of a 22-array model type (cnn_2d_speed_control, cnn_2d) is trained where it drives: a step runs the convolutions and dense1 by the kernels
  * of trs_pilot_forward, takes the loss and its gradient through the four dense layers, and moves them by Adam, all on the handle's stream and without a
  * byte crossing to the host.  After a step the handle drives with the updated pilot (trs_pilot_forward, trs_pilot_act, trs_step_pilot, trs_step_dagger).
- * What stays out: conv1 .. conv3 (conv4 .. conv7 can be trained as well: the next section), dropout, the model types with side inputs (28 and 42
- * arrays), feature caching across epochs, any exchange of gradients between GPUs.
+ * What stays out: conv1 .. conv3 (conv4 .. conv7 can be trained as well: the next section), dropout behind conv1 .. conv6 (behind conv7 and the hidden
+ * dense layers: the section after it), the model types with side inputs (28 and 42 arrays), feature caching across epochs, any exchange of gradients
+ * between GPUs.
  *   trs_pilot_train_begin: fp32 master weights and Adam's m and v (zero) for the eight arrays dense1 .. output_layer, t = 0.  The handle keeps dense1 as
  *     binary16 only, so h_tail_arrays[0], dense1's kernel float[F][100] as trs_pilot_load got it, is read from the host; the other seven arrays are taken
  *     from the device, where the tail kernel reads them (entries 1..7 are not read and may be NULL).  cfg NULL: the defaults.
@@ -749,7 +750,10 @@ enum {
     TRS_TRAIN_DBG_V = 24,            /* + a: Adam's v */
     TRS_TRAIN_DBG_SCALE_EXP = 32,    /* 1 float: the exponent s of the batch's scale 2^s */
     TRS_TRAIN_DBG_LOSS = 33,         /* 1 float */
-    TRS_TRAIN_DBG_PACK1 = 34         /* float[F][100]: dense1's binary16 copy as the dense kernel reads it, widened */
+    TRS_TRAIN_DBG_PACK1 = 34,        /* float[F][100]: dense1's binary16 copy as the dense kernel reads it, widened */
+    /* (35 stays unknown) the activations dense2, dense3 and output_layer read, float[n][100], [n][50], [n][25]: relu(z), or a'(l) of "training the pilot's
+     * tail, dropout" where a site is on; valid with or without dropout */
+    TRS_TRAIN_DBG_A1 = 36, TRS_TRAIN_DBG_A2 = 37, TRS_TRAIN_DBG_A3 = 38
 };
 void trs_default_train_config(trs_train_config* cfg);
 int trs_pilot_train_begin(trs_env* env, const trs_train_config* cfg_or_null, const float* const* h_tail_arrays);
@@ -783,6 +787,30 @@ enum {
 int trs_pilot_train_convs(trs_env* env, uint32_t conv_mask, const float* const* h_conv_arrays);
 int trs_pilot_train_get_convs(trs_env* env, float* const* h_out);
 int trs_pilot_train_debug_conv(trs_env* env, int layer, int which, float* h_dst, size_t n_floats);
+
+/* ---- training with dropout behind conv7 (include/trsim_spec.h, "training the pilot's tail, dropout") ----
+ * The reference's trainer puts Dropout(0.1) behind every convolution and every hidden dense layer (components/keras_train.py:131-164).  Between
+ * trs_pilot_train_begin and the session's first step, trs_pilot_train_dropout switches training-mode dropout on at the four sites the session owns:
+ * bit 0 of `sites` conv7's output x7 (the flatten dense1 reads), bits 1 .. 3 relu(z1), relu(z2), relu(z3).  The draws are keyed integers of (seed, the
+ * session's step count, site, the frame's slot in the batch, the unit), so a host restates every mask without a GPU (trs_train_dropout_keep).  out, the
+ * loss and every gradient of a step are those of the dropped network; inference never drops (trs_pilot_forward, trs_pilot_act, trs_step_pilot,
+ * trs_step_dagger are untouched).  The sites behind conv1 .. conv6 stay out: they lie inside the forward kernels that also drive.
+ *   trs_pilot_train_dropout: cfg NULL: the defaults.  rate 0, a clear site bit or no call: that site computes what it computed without this section, bit
+ *     for bit, by the same kernels.
+ *   trs_train_dropout_keep: h_keep[i][k] = 1 when unit k < width of frame slot i < n is kept at step t >= 1 (the first step of a session is 1) at `site`,
+ *     else 0; cfg's sites are not consulted.  Host arithmetic only: no handle, no GPU work; the sibling of trs_loader_order and trs_loader_augment.
+ *   Refusals.  trs_pilot_train_dropout: TRS_ERR_STATE without a session, after the session's first step, on a second call; TRS_ERR_ARG for a struct_size
+ *     mismatch, a rate that is NaN or outside [0, 1), sites with bits above 3.  trs_train_dropout_keep: TRS_ERR_ARG for the config, t < 1, a site outside
+ *     0..3, a negative n or width, a NULL h_keep. */
+typedef struct trs_dropout_config {
+    uint32_t struct_size;
+    float    rate;                   /* 0.1: Dropout(0.1); the effective rate is floor(rate 65536) / 65536 */
+    uint32_t sites;                  /* 0xF: bit 0 = x7, bits 1..3 = relu(z1) .. relu(z3) */
+    uint64_t seed;                   /* 0 (at offset 16: four bytes of padding before it) */
+} trs_dropout_config;
+void trs_default_dropout_config(trs_dropout_config* cfg);
+int trs_pilot_train_dropout(trs_env* env, const trs_dropout_config* cfg_or_null);
+int trs_train_dropout_keep(const trs_dropout_config* cfg_or_null, int64_t t, int site, int n, int64_t width, uint8_t* h_keep);
 
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no

@@ -394,8 +394,9 @@
  *     B = 1, 0x00400000, 0x007FFFFF -> 100; 2^114, 2^120, 0x7F800000, 0x7FC00000 -> -100.
  *     alpha_t at the defaults (bit patterns): t = 1: 39a5cb17, t = 2: 3976beef, t = 1000: 3a507326.  c1 = 3dccccd0, c2 = 3a831200.
  *     One update, g = 1, m = v = 0, w = 1, t = 1: m = 3dccccd0, v = 3a831200, w = 3f7fbe77 (0.99900001: Adam's first step is lr in size).
- *   Not here: conv1 .. conv3 (conv4 .. conv7: the next section), dropout (keras_train.py applies 0.1; tests/golden/train_pilot_fixture.py trains without), the
- *   model types with side inputs (28 and 42 arrays: refused), feature caching across epochs, gradient exchange between GPUs.
+ *   Not here: conv1 .. conv3 (conv4 .. conv7: the next section), dropout behind conv1 .. conv6 (behind conv7 and the hidden dense layers: "training the
+ *   pilot's tail, dropout"; keras_train.py applies 0.1 everywhere; tests/golden/train_pilot_fixture.py trains without), the model types with side inputs
+ *   (28 and 42 arrays: refused), feature caching across epochs, gradient exchange between GPUs.
  *   tests/test_train_cpu.py restates steps 2 to 6 in numpy and checks the restatement against torch.autograd in binary64; tests/test_train_gpu.py compares the
  *   kernels with it (Adam bit for bit from the device's gradient); csrc/trsim_train.hpp holds the rules a host compiler can build.
  *
@@ -424,10 +425,43 @@
  *      trs_pilot_train_convs), m = v = 0 at the start.  The pass writes each kernel's binary16 value with host_f2h's rounding at
  *      ((kh run_pad + kw CIN / 8 + ci / 8) COUT_PAD + co) 8 + ci % 8 of ConvLayer::w (pack_layer's order; run_pad = 3 CIN / 8, COUT_PAD = COUT), into the
  *      session's own [kh][kw][ci][co] copy that step 4 reads, and the bias where the kernels read it.  Step 4 of layer l runs before layer l's Adam.
- *   Not here: conv1 .. conv3 (5 x 5, stride 2, the fused head), dropout, the 28- and 42-array model types, feature caching, the multi-GPU exchange.
+ *   Not here: conv1 .. conv3 (5 x 5, stride 2, the fused head), dropout behind conv1 .. conv6, the 28- and 42-array model types, feature caching, the
+ *   multi-GPU exchange.
  *   tests/test_train_conv_cpu.py restates steps 2 to 5 in numpy, checks the restatement against torch.autograd in binary64 and shows what the reference
  *   notices; tests/test_train_conv_gpu.py compares the kernels with it within derived bounds (Adam bit for bit from the device's gradient);
  *   csrc/trsim_train_conv.hpp holds the rules a host compiler can build (tests/train_conv_driver.cpp).
+ *
+ * ---- training the pilot's tail, dropout (trs_pilot_train_dropout, trs_train_dropout_keep; HIP library only)
+ *   The reference's trainer puts Dropout(0.1) behind every convolution and every hidden dense layer (components/keras_train.py:131-164).  After
+ *   trs_pilot_train_dropout(rate, sites, seed) the steps of a session drop at the four sites the session owns: site 0 (bit 1 of sites) conv7's output x7,
+ *   the flatten dense1 reads, F units per frame; sites 1, 2, 3 (bits 2, 4, 8) relu(z1), relu(z2), relu(z3): 100, 50, 25 units per frame.  The sites behind
+ *   conv1 .. conv6 stay out: they lie inside forward kernels that also drive, and those kernels do not change.  Inference never drops: trs_pilot_forward,
+ *   trs_pilot_act, trs_step_pilot, trs_step_dagger and pilot_loss are untouched, as in Keras.  Unsigned 64-bit arithmetic (mod 2^64) and single binary32
+ *   IEEE operations only; mix is the function of "training minibatches".
+ *     T     = floor((double)rate * 65536)                    rate a binary32 in [0, 1): 0 <= T <= 65535; the effective rate is T / 65536
+ *     s     = (float)(65536.0 / (65536 - T))                 the scale of the EFFECTIVE rate: s (1 - T / 65536) = 1 to one rounding
+ *     D     = mix(seed ^ 0x64726F706F757421)
+ *     Dt    = mix(D ^ t)                                     t >= 1: the session's step count, the t of alpha_t
+ *     key   = mix(Dt ^ (((uint64)site << 32) | i))           i: the frame's slot in the batch
+ *     word  = mix(key + (k >> 2)),  field = (word >> (16 (k & 3))) & 0xFFFF       unit k of the frame: four units per mix
+ *     keep  = field >= T
+ *   The flags are a function of (seed, t, site, i, k) alone: a batch of 70 has the batch of 17 as its prefix.
+ *   Forward.  Sites 1 .. 3: a'(l)[k] = keep ? relu(z(l)[k]) * s : +0, one binary32 rounding; a'(l) replaces relu(z(l)) as the next layer's input (step 1 of
+ *     "training the pilot's tail") and in the weight gradient of layer l + 1 (step 4).  Site 0: x7'[f] = keep ? binary16_rn(min((float)x7[f] * s, 65504)) :
+ *     +0, written where dense1 and the gW1 GEMM (step 5) read x7, before dense1 runs (x7 is finite and not negative: a ReLU's output).  out, the loss
+ *     and every gradient of a step are those of the dropped network.
+ *   Backward.  delta(l) = ((W(l+1) delta(l+1)) * s) . keep . [z(l) > 0] for l = 3, 2, 1: the chain of step 3, then one more binary32 product.  With
+ *     trs_pilot_train_convs, G7 = [x7' > 0] . (s * 2^-s1) (W1h q1): the gate on the dropped x7' carries the mask (a kept positive value stays positive, s >= 1),
+ *     and s * 2^-s1 is one binary32 product, exact, since one factor is a power of two.  Nothing else of the convolutions' backward pass changes: x7 is only a
+ *     gate there.
+ *   Off.  No call, rate 0 (T = 0) or a clear site bit: that site computes what the two sections above state, bit for bit, by the same kernels.
+ *   Refused: a struct_size mismatch, a rate that is NaN or outside [0, 1), sites with bits above 3 (TRS_ERR_ARG); the call without a session, after the
+ *   session's first step, or twice (TRS_ERR_STATE).
+ *   Vectors.  rate 0.1f: T = 6553, s = 3f8e3885;  0.5f: T = 32768, s = 2;  0.999f: T = 65470;  the largest binary32 below 1: T = 65535, s = 65536.
+ *     Kept among the 70 x 4608 units of site 0 at rate 0.1f, seed 0, t = 1: 290315 (0.900034 against 1 - T / 65536 = 0.900009).
+ *   tests/test_dropout_cpu.py restates the paragraph in numpy, compares trs_train_dropout_keep with it bit for bit and checks the dropped passes against
+ *   torch.autograd in binary64 with the masks as constants; tests/test_dropout_gpu.py compares the kernels with it (x7' and a'(l) bit for bit);
+ *   csrc/trsim_dropout.hpp is the one place the kernels and the host take the draw from (tests/dropout_driver.cpp).
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

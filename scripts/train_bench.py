@@ -20,7 +20,11 @@ With --digest the script measures nothing: it prints `name sha256` lines of what
 the tail and of every layer, the masters, and trs_pilot_forward's output afterwards) on seeded weights, frames and labels, at two small shapes that between
 them reach one and several chunks and slices of both weight-gradient GEMMs and all three channel shapes.  Two builds of the library (TRS_HIP_LIB) that
 compute the same bits print the same lines.
-Run from the repository root: python scripts/train_bench.py [--convs] [> profiles/rNN_train_tail.txt]"""
+With --dropout RATE the session drops at all four sites behind conv7 (trs_pilot_train_dropout, "training the pilot's tail, dropout"), the step's median is
+printed beside its minimum, and a further copy leg moves the bytes of the mask pass over x7 (n F 2 read and written), the one part of dropout that moves
+real bytes.  Pass line (profiles/r36_dropout.txt): the step's median with dropout less the median without, on the same box, is at most 1.25 x that copy
+plus the spread of the runs without.
+Run from the repository root: python scripts/train_bench.py [--convs] [--dropout RATE] [> profiles/rNN_train_tail.txt]"""
 import csv
 import glob
 import os
@@ -118,6 +122,11 @@ def main():
     convs = "--convs" in sys.argv
     if convs:
         sys.argv.remove("--convs")
+    dropout = None
+    if "--dropout" in sys.argv:
+        at = sys.argv.index("--dropout")
+        dropout = float(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
     drive = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "--drive" else 0
     import torch
     from triton_racer_sim_amd.env import BatchedEnv
@@ -151,7 +160,7 @@ def main():
         ws, F = weights(h, w)
         env = BatchedEnv(n_envs=n, img_h=h, img_w=w, track=None)
         env.pilot_load(ws)
-        env.pilot_train_begin(convs=("conv4", "conv5", "conv6", "conv7") if convs else None)
+        env.pilot_train_begin(convs=("conv4", "conv5", "conv6", "conv7") if convs else None, **({} if dropout is None else {"dropout": dropout}))
         frames = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda")
         labels = torch.rand((n, 2), device="cuda") * 2 - 1
         out = torch.empty((n, 2), device="cuda")
@@ -190,6 +199,8 @@ def main():
             adam_bytes = 32 * 295296                                    # conv4 .. conv7: 295,296 weights and biases
         src_g, src_a = torch.empty(gemm_bytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(adam_bytes // 2, dtype=torch.uint8, device="cuda")
         dst_g, dst_a = torch.empty_like(src_g), torch.empty_like(src_a)
+        src_x = torch.empty(n * F * 2, dtype=torch.uint8, device="cuda")
+        dst_x = torch.empty_like(src_x)
         res = {}
         for _ in range(ROUNDS):
             res.setdefault("fwd", []).append(timed(env, calls, fwd))
@@ -197,6 +208,7 @@ def main():
             res.setdefault("torch", []).append(torch_timed(calls, torch_step))
             res.setdefault("copy_g", []).append(torch_timed(calls, lambda: dst_g.copy_(src_g)))
             res.setdefault("copy_a", []).append(torch_timed(calls, lambda: dst_a.copy_(src_a)))
+            res.setdefault("copy_x", []).append(torch_timed(calls, lambda: dst_x.copy_(src_x)))
         print(f"== {n} frames of {h}x{w}, F = {F}; one MI355X; figures are the minimum of {ROUNDS} alternating runs of {calls} calls ==")
         show("trs_pilot_forward (conv1..7, dense1, the driving tail)", res["fwd"])
         show("trs_pilot_train_step (conv1..7, dense1, tail forward + backward, gW1, Adam)", res["step"])
@@ -204,6 +216,9 @@ def main():
              "torch: 4 x nn.Linear fp32 on conv7's features, mse_loss, backward(), Adam.step()", res["torch"])
         show(f"copy_ of {gemm_bytes // 2 / 1e6:.1f} MB: the gW1 GEMM's {gemm_bytes / 1e6:.1f} MB, read + written", res["copy_g"])
         show(f"copy_ of {adam_bytes // 2 / 1e6:.1f} MB: the Adam pass's {adam_bytes / 1e6:.1f} MB, read + written", res["copy_a"])
+        show(f"copy_ of {n * F * 2 / 1e6:.1f} MB: x7's bytes, read + written (what dropout's mask pass moves)", res["copy_x"])
+        print(f"  trs_pilot_train_step{'' if dropout is None else f' --dropout {dropout:g}'}: median {sorted(res['step'])[1]:.2f} us, spread {max(res['step']) - min(res['step']):.2f} us; "
+              f"copy of x7: median {sorted(res['copy_x'])[1]:.2f} us", flush=True)
         added = min(res["step"]) - min(res["fwd"])
         if convs:
             print(f"  step - forward = {added:.2f} us (what training conv4 .. conv7 and the tail adds to a forward pass); the whole step, conv1 .. conv3 included, "

@@ -161,9 +161,15 @@ class TrsTrainConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("train_mask", C.c_uint32)]
 
 
+class TrsDropoutConfig(C.Structure):
+    """``trs_dropout_config`` (include/trsim.h): training-mode dropout behind conv7 (``trs_pilot_train_dropout``)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rate", C.c_float), ("sites", C.c_uint32), ("seed", C.c_uint64)]
+
+
 TRAIN_LAYERS = ("dense1", "dense2", "dense3", "output_layer")           # bit l of trs_train_config.train_mask; their (kernel, bias) pairs are the eight trained arrays
 TRAIN_DEBUG = {"out": 0, "z1": 1, "z2": 2, "z3": 3, "delta1": 4, "delta2": 5, "delta3": 6, "delta4": 7, "gw1": 8, "gw2": 9, "gw3": 10, "gw4": 11,
-               "gb1": 12, "gb2": 13, "gb3": 14, "gb4": 15, "m": 16, "v": 24, "scale_exp": 32, "loss": 33, "pack1": 34}   # TRS_TRAIN_DBG_* ("m", "v": + the array's number 0..7)
+               "gb1": 12, "gb2": 13, "gb3": 14, "gb4": 15, "m": 16, "v": 24, "scale_exp": 32, "loss": 33, "pack1": 34,
+               "a1": 36, "a2": 37, "a3": 38}                            # TRS_TRAIN_DBG_* ("m", "v": + the array's number 0..7; 35 is no item)
 
 LOADER_TYPES = {"speed_ctl": 0, "default": 1, "speed_feature": 2, "full_house": 3}   # TRS_LOADER_*; the names of recorder.LOADERS, in the order of TRS_PILOT_*
 LOADER_FEATURES = {"speed_ctl": 0, "default": 0, "speed_feature": 1, "full_house": 2}
@@ -225,11 +231,15 @@ TRAIN_SYMBOLS = ["default_train_config", "pilot_train_begin", "pilot_train_step"
 # HIP library only: training the pilot's last convolutions (trs_pilot_train_convs) — its checker is the numpy restatement of include/trsim_spec.h
 # ("training the pilot's last convolutions") in tests/test_train_conv_cpu.py, itself checked against torch.autograd in binary64
 TRAIN_CONV_SYMBOLS = ["pilot_train_convs", "pilot_train_get_convs", "pilot_train_debug_conv"]
+# HIP library only: dropout behind conv7 (trs_pilot_train_dropout, trs_train_dropout_keep) — its checker is the numpy restatement of include/trsim_spec.h
+# ("training the pilot's tail, dropout") in tests/test_dropout_cpu.py (tests/test_dropout_gpu.py compares the kernels with it, the masks bit for bit)
+DROPOUT_SYMBOLS = ["default_dropout_config", "pilot_train_dropout", "train_dropout_keep"]
+DROPOUT_SITES = ("x7", "a1", "a2", "a3")                                # bit j of trs_dropout_config.sites; units per frame: F, 100, 50, 25
 TRAIN_CONV_LAYERS = ("conv4", "conv5", "conv6", "conv7")                # bit j of trs_pilot_train_convs' mask; arrays 6 + 2 j, 7 + 2 j of pilot_load
 TRAIN_CONV_DEBUG = {"delta": 0, "gw": 1, "gb": 2, "mw": 3, "vw": 4, "mb": 5, "vb": 6, "scale_exp": 7, "pack": 8}   # TRS_CONV_DBG_*
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + TRAIN_CONV_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + TRAIN_CONV_SYMBOLS + DROPOUT_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -365,6 +375,11 @@ class Api:
             "pilot_train_get_convs": (i32, [vp, C.POINTER(C.c_void_p)]),
             "pilot_train_debug_conv": (i32, [vp, i32, i32, vp, C.c_size_t]),
         }
+        dropout = {
+            "default_dropout_config": (None, [C.POINTER(TrsDropoutConfig)]),
+            "pilot_train_dropout": (i32, [vp, C.POINTER(TrsDropoutConfig)]),
+            "train_dropout_keep": (i32, [C.POINTER(TrsDropoutConfig), C.c_int64, i32, i32, C.c_int64, vp]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -439,6 +454,12 @@ class Api:
         self.has_train = hasattr(cdll, prefix + "pilot_train_step")
         if self.has_train:
             for name, (res, args) in train.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_dropout = hasattr(cdll, prefix + "pilot_train_dropout")
+        if self.has_dropout:
+            for name, (res, args) in dropout.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -89,7 +89,10 @@ struct TrsPilotTail {
     void** train;                         // the session's slot in the pilot's context (nullptr in it: none open)
 };
 int trs_internal_pilot_tail(trs_env* e, TrsEnvView* v, TrsPilotTail* t);   // the view and the tail of the loaded pilot, or the refusal of every pilot entry point (no handle, no pilot)
-int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t);   // conv1..7 and dense1 of trs_pilot_forward on the stream; *t refreshed
+// What a training step may put between the two halves of that pass: fn(arg, x7, n) runs after conv7 has been launched and before dense1 is, and launches
+// on the view's stream whatever rewrites conv7's activation in place (dropout at site 0); a non-zero return ends the pass with that code.
+struct TrsPilotX7Hook { int (*fn)(void* arg, void* x7, int n); void* arg; };
+int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t, const TrsPilotX7Hook* between = nullptr);   // conv1..7 and dense1 of trs_pilot_forward on the stream; *t refreshed
 void trs_train_free(void* session);   // defined in trsim_train.hip, called by trs_pilot_free; nullptr is fine
 // ---- training the pilot's last convolutions (trsim_train_conv.hip) ----
 // conv4 .. conv7 of the loaded pilot as a training step sees them (views into the pilot's own buffers), defined in trsim_pilot.hip.  With `materialise`

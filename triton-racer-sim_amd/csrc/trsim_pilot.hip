@@ -1015,7 +1015,8 @@ int launch_dense(const ConvLayer& cl, const DenseCall& d, const void* in, int n,
     return launch_lds(d.nf == 2 ? trs_pilot_dense_kernel<2> : trs_pilot_dense_kernel<1>, dim3(d.grid), dim3(256), d.lds, d.lds, s, q);
 }
 
-int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n)
+// between: what a training step runs on conv7's activation before dense1 reads it (TrsPilotX7Hook, trsim_internal.hpp); nullptr everywhere else
+int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n, const TrsPilotX7Hook* between = nullptr)
 {
     const PilotPlan& P = c->plan;
     const void* in = d_frames;
@@ -1052,6 +1053,7 @@ int forward(PilotCtx* c, const TrsEnvView& v, const uint8_t* d_frames, int n)
     }
     const DenseCall d = dense_call(P.L[7], n, P.cu_count, P.tun);             // dense4 has dense1's shape: one plan for both
     c->last_slices = d.KS;
+    if (between) { if (int rc = between->fn(between->arg, c->act[6].get(), n)) return rc; }
     int rc = launch_dense(c->L[7], d, c->act[6].get(), n, c->slab, v.stream);
     if (!rc && P.arch == TRS_PILOT_FULL_HOUSE) { c->last_slices2 = d.KS; rc = launch_dense(c->L[8], d, c->act[6].get(), n, c->slab2, v.stream); }   // the steering head's dense4 reads conv7's output as well
     if (rc) return rc;
@@ -1225,10 +1227,10 @@ int trs_internal_pilot_tail(trs_env* e, TrsEnvView* v, TrsPilotTail* t)
     return TRS_OK;
 }
 
-int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t)
+int trs_internal_pilot_dense_forward(trs_env* e, const TrsEnvView& v, const uint8_t* d_frames, int n, TrsPilotTail* t, const TrsPilotX7Hook* between)
 {
     PilotCtx* const c = static_cast<PilotCtx*>(*trs_internal_pilot_slot(e));
-    if (int rc = forward(c, v, d_frames, n)) return rc;
+    if (int rc = forward(c, v, d_frames, n, between)) return rc;
     fill_tail(c, t);
     return TRS_OK;
 }

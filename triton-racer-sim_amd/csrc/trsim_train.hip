@@ -14,6 +14,12 @@
 //                             convolutions' weight gradient runs.
 //   trs_train_adam1_kernel    Adam over dense1's kernel: one thread per (granule, output) moves 8 masters and writes the binary16 granule the dense
 //                             kernel reads; trs_train_adam_kernel: the other seven arrays, written to the master and where the tail kernels read them
+// With trs_pilot_train_dropout (include/trsim_spec.h, "training the pilot's tail, dropout"; the draws: trsim_dropout.hpp) a site that drops takes
+//   trs_train_drop7_kernel    site 0: conv7's activation masked and scaled where it lies, between conv7 and dense1 (trsim_pilot.hip calls it through a hook);
+//                             the gW1 GEMM and G7's gate then read the dropped values
+//   trs_train_tail_drop_kernel   sites 1 .. 3: the tail kernel's body with the forward scaling and the backward mask; it stores a'(l), which the small
+//                             kernel reads where it read z(l) (relu(a') is a' bit for bit)
+// and a site that does not keeps the kernels and the bits above.
 // No floating-point atomics: two runs of a step agree bit for bit.  The rules that need no GPU (config, alpha_t, the scale's exponent, the buffers' layout)
 // are trsim_train.hpp; the session, which trsim_train_conv.hip's entry points open as well, is trsim_train_session.hpp.
 #include <hip/hip_runtime.h>
@@ -40,69 +46,46 @@ struct TailTrainParams {
     unsigned* max_bits;                                  // zeroed before the launch
 };
 
+// Dropout at sites 1 .. 3 (include/trsim_spec.h, "training the pilot's tail, dropout"): the step's key Dt, the threshold and scale per site (a site that
+// is off: T = 0, s = 1, which keep every unit and every bit) and where a'(l), what the next layer read, is kept for the small gradients
+struct TailDropParams {
+    uint64_t Dt; uint32_t T[3]; float s[3];
+    float *a1, *a2, *a3;
+};
+
+// The two kernels share their body as text (trsim_train_tail_body.hpp says why); the LDS arrays are each kernel's own
 __global__ __launch_bounds__(256) void trs_train_tail_kernel(const TailTrainParams p)
 {
     __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int i = blockIdx.x * 4 + wv;
-    if (i >= p.n) return;                                // whole waves
-    // z1: the slabs in slice order (what trs_pilot_tail_kernel's padded groups add: x + 0.0f == x), then the ReLU
-    const bool two = lane + 64 < 100;
-    float z1a = 0.0f, z1b = 0.0f;
-    for (int sl = 0; sl < p.slices; ++sl) {
-        const float* src = p.h1 + (size_t)sl * p.stride + (size_t)i * 100 + lane;
-        z1a += src[0];
-        z1b += src[two ? 64 : 0];
+    constexpr bool DROP = false; const TailDropParams dp{};
+#include "trsim_train_tail_body.hpp"
+}
+__global__ __launch_bounds__(256) void trs_train_tail_drop_kernel(const TailTrainParams p, const TailDropParams dp)
+{
+    __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
+    constexpr bool DROP = true;
+#include "trsim_train_tail_body.hpp"
+}
+
+// ---- dropout at site 0: conv7's activation masked and scaled in place, between conv7 and dense1 -------------------------------------
+// x7'[f] = keep ? binary16_rn(min((float)x7[f] s, 65504)) : +0.  One lane per 16-byte unit of 8 features and one wave per workgroup: workgroup (x, y) owns
+// units 64 x .. 64 x + 63 of frames y, y + gridDim.y, .., so a wave's loads and stores cover one contiguous run of 1 KB, the frame's key is the same for the
+// whole wave (no lane divides a flat index by G) and a lane pays the two words of its unit (four fields each).  No LDS, no atomics.
+__global__ __launch_bounds__(64) void trs_train_drop7_kernel(u4v* x7, int n, int G, uint64_t Dt, uint32_t T, float s)
+{
+    const int u = blockIdx.x * 64 + threadIdx.x;
+    if (u >= G) return;
+    for (int i = blockIdx.y; i < n; i += gridDim.y) {
+        const uint64_t key = dropout_frame_key(Dt, 0u, (uint32_t)i);
+        const uint64_t w[2] = {dropout_word(key, 2u * (uint32_t)u), dropout_word(key, 2u * (uint32_t)u + 1u)};
+        u4v* const at = x7 + (size_t)i * (size_t)G + u;
+        const h16x8 x = __builtin_bit_cast(h16x8, *at);
+        h16x8 y;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            y[j] = dropout_keep_field(w[j >> 2], (uint32_t)j, T) ? (_Float16)fminf((float)x[j] * s, 65504.0f) : (_Float16)0.0f;
+        *at = __builtin_bit_cast(u4v, y);
     }
-    p.z1[(size_t)i * 100 + lane] = z1a; s1[wv][lane] = z1a > 0.f ? z1a : 0.f;
-    if (two) { p.z1[(size_t)i * 100 + lane + 64] = z1b; s1[wv][lane + 64] = z1b > 0.f ? z1b : 0.f; }
-    __builtin_amdgcn_wave_barrier();
-    float z2 = 0.0f, z3 = 0.0f;
-    if (lane < 50) {                                     // one fmaf chain per output from the bias, k ascending
-        float s = p.b2[lane];
-        for (int k = 0; k < 100; ++k) s = fmaf(s1[wv][k], p.w2[k * 50 + lane], s);
-        z2 = s; p.z2[(size_t)i * 50 + lane] = s; s2[wv][lane] = s > 0.f ? s : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 25) {
-        float s = p.b3[lane];
-        for (int k = 0; k < 50; ++k) s = fmaf(s2[wv][k], p.w3[k * 25 + lane], s);
-        z3 = s; p.z3[(size_t)i * 25 + lane] = s; s3[wv][lane] = s > 0.f ? s : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 2) {
-        float s = p.b4[lane];
-        for (int k = 0; k < 25; ++k) s = fmaf(s3[wv][k], p.w4[k * 2 + lane], s);
-        p.out[(size_t)i * 2 + lane] = s;
-        const float d = (s - p.y[(size_t)i * 2 + lane]) / (float)p.n;          // delta4
-        p.d4[(size_t)i * 2 + lane] = d; e4[wv][lane] = d;
-    }
-    __builtin_amdgcn_wave_barrier();
-    // delta(l) = (W(l+1) delta(l+1)) . [z(l) > 0]: lane k owns row k; one fmaf chain from 0, the output index ascending
-    if (lane < 25) {
-        float s = 0.0f;
-        for (int o = 0; o < 2; ++o) s = fmaf(p.w4[lane * 2 + o], e4[wv][o], s);
-        s = z3 > 0.f ? s : 0.0f;
-        p.d3[(size_t)i * 25 + lane] = s; e3[wv][lane] = s;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 50) {
-        float s = 0.0f;
-        for (int o = 0; o < 25; ++o) s = fmaf(p.w3[lane * 25 + o], e3[wv][o], s);
-        s = z2 > 0.f ? s : 0.0f;
-        p.d2[(size_t)i * 50 + lane] = s; e2[wv][lane] = s;
-    }
-    __builtin_amdgcn_wave_barrier();
-    float da = 0.0f, db = 0.0f;
-    {
-        const int kb = two ? lane + 64 : lane;
-        for (int o = 0; o < 50; ++o) { da = fmaf(p.w2[lane * 50 + o], e2[wv][o], da); db = fmaf(p.w2[kb * 50 + o], e2[wv][o], db); }
-        da = z1a > 0.f ? da : 0.0f;
-        db = (two && z1b > 0.f) ? db : 0.0f;
-        p.d1[(size_t)i * 100 + lane] = da;
-        if (two) p.d1[(size_t)i * 100 + lane + 64] = db;
-    }
-    wave_max_bits(max(__float_as_uint(da) & 0x7FFFFFFFu, __float_as_uint(db) & 0x7FFFFFFFu), p.max_bits, lane);   // the batch's largest |delta1|
 }
 
 // ---- the small gradients and the loss: one thread per value, the frames in ascending order ----------------------------------------
@@ -331,7 +314,16 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     if (n < 1 || n > s->n_cap) return trs_internal_fail(TRS_ERR_ARG, "n must be in [1, n_envs]");
     if (!d_frames || !d_labels) return trs_internal_fail(TRS_ERR_ARG, "d_frames or d_labels is NULL");
     HIPCHK(hipSetDevice(v.device));
-    if (int rc = trs_internal_pilot_dense_forward(e, v, d_frames, n, &t)) return rc;      // conv1 .. conv7 and dense1, by the kernels that drive
+    const DropSession& dr = s->drop;
+    const uint64_t Dt = dropout_step_key(dr.seed, (uint64_t)(s->t + 1));                  // (read only where a site is on)
+    struct Drop7 { hipStream_t st; int G; uint64_t Dt; uint32_t T; float s; } d7{v.stream, t.G, Dt, dr.T, dr.s};
+    const TrsPilotX7Hook hook{[](void* arg, void* x7, int frames) -> int {
+        const Drop7& d = *static_cast<const Drop7*>(arg);
+        hipLaunchKernelGGL(trs_train_drop7_kernel, dim3((d.G + 63) / 64, std::min(frames, 65535)), dim3(64), 0, d.st, static_cast<u4v*>(x7), frames, d.G, d.Dt, d.T, d.s);
+        return TRS_OK;
+    }, &d7};
+    // conv1 .. conv7 and dense1, by the kernels that drive; with site 0 on, x7 is masked where it lies before dense1 reads it
+    if (int rc = trs_internal_pilot_dense_forward(e, v, d_frames, n, &t, dr.site(0) ? &hook : nullptr)) return rc;
     hipStream_t st = v.stream;
     unsigned* const scal = s->scal.get();
     HIPCHK(hipMemsetAsync(scal, 0, sizeof(unsigned), st));
@@ -342,9 +334,20 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     tp.out = s->item(TRS_TRAIN_DBG_OUT); tp.z1 = s->item(TRS_TRAIN_DBG_Z1); tp.z2 = s->item(TRS_TRAIN_DBG_Z2); tp.z3 = s->item(TRS_TRAIN_DBG_Z3);
     tp.d1 = s->item(TRS_TRAIN_DBG_DELTA1); tp.d2 = s->item(TRS_TRAIN_DBG_DELTA2); tp.d3 = s->item(TRS_TRAIN_DBG_DELTA3); tp.d4 = s->item(TRS_TRAIN_DBG_DELTA4);
     tp.max_bits = scal;
-    hipLaunchKernelGGL(trs_train_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp);
     SmallGradParams sp{};
-    sp.z1 = tp.z1; sp.z2 = tp.z2; sp.z3 = tp.z3; sp.d1 = tp.d1; sp.d2 = tp.d2; sp.d3 = tp.d3; sp.d4 = tp.d4; sp.out = tp.out; sp.y = d_labels;
+    sp.z1 = tp.z1; sp.z2 = tp.z2; sp.z3 = tp.z3;
+    if (dr.tail()) {
+        TailDropParams dp{};
+        dp.Dt = Dt;
+        for (int l = 1; l <= 3; ++l) { dp.T[l - 1] = dr.site(l) ? dr.T : 0u; dp.s[l - 1] = dr.site(l) ? dr.s : 1.0f; }
+        dp.a1 = s->dropped(1); dp.a2 = s->dropped(2); dp.a3 = s->dropped(3);
+        hipLaunchKernelGGL(trs_train_tail_drop_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp, dp);
+        // the small kernel takes relu of what it reads, and relu(a') is a' bit for bit (a' is +0 or a non-negative product): it reads a'(l) where it read z(l)
+        sp.z1 = dp.a1; sp.z2 = dp.a2; sp.z3 = dp.a3;
+    } else {
+        hipLaunchKernelGGL(trs_train_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp);
+    }
+    sp.d1 = tp.d1; sp.d2 = tp.d2; sp.d3 = tp.d3; sp.d4 = tp.d4; sp.out = tp.out; sp.y = d_labels;
     sp.g = s->g.get(); std::memcpy(sp.off, s->L.off, sizeof sp.off);
     sp.loss = reinterpret_cast<float*>(scal + 2); sp.loss_user = d_loss_or_null; sp.n = n;
     hipLaunchKernelGGL(trs_train_small_kernel, dim3((kSmallGradThreads + 63) / 64), dim3(64), 0, st, sp);
@@ -357,7 +360,7 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     const trs_train_config& c = s->cfg;
     const AdamK k{c.beta1, trsim::train_one_minus(c.beta1), c.beta2, trsim::train_one_minus(c.beta2), c.eps, trsim::train_alpha(c, s->t + 1)};
     if (s->conv)                                                            // conv4 .. conv7 from delta1 and the dense1 copy the forward used: before Adam rewrites it
-        if (int rc = trs_train_conv_step(*s->conv, e, v, t, s->q.get(), reinterpret_cast<const int*>(scal + 1), n, k)) return rc;
+        if (int rc = trs_train_conv_step(*s->conv, e, v, t, s->q.get(), reinterpret_cast<const int*>(scal + 1), n, k, dr.site(0) ? dr.s : 0.0f)) return rc;
     if (c.train_mask & 1u)
         hipLaunchKernelGGL(trs_train_adam1_kernel, dim3((t.G * 128 + 255) / 256), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), t.w1_pack, t.G, k);
     AdamSmallParams ap{};
@@ -368,6 +371,50 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     hipLaunchKernelGGL(trs_train_adam_kernel, dim3((unsigned)((small + 255) / 256)), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), ap, k);
     HIPCHK(hipGetLastError());
     s->t += 1; s->last_n = n;
+    return TRS_OK;
+}
+
+// ---- dropout behind conv7 (trsim_dropout.hpp) -------------------------------------------------------------------------------------------
+TRS_EXPORT void trs_default_dropout_config(trs_dropout_config* cfg)
+{
+    if (cfg) trsim::dropout_defaults(cfg);
+}
+
+TRS_EXPORT int trs_train_dropout_keep(const trs_dropout_config* cfg_or_null, int64_t t, int site, int n, int64_t width, uint8_t* h_keep)
+{
+    trs_dropout_config cfg;
+    trsim::dropout_defaults(&cfg);
+    if (cfg_or_null) {
+        if (const char* why = trsim::dropout_config_error(cfg_or_null)) return trs_internal_fail(TRS_ERR_ARG, why);
+        cfg = *cfg_or_null;
+    }
+    if (const char* why = trsim::dropout_keep_error(t, site, n, width, h_keep)) return trs_internal_fail(TRS_ERR_ARG, why);
+    trsim::dropout_keep_host(cfg, t, site, n, width, h_keep);
+    return TRS_OK;
+}
+
+TRS_EXPORT int trs_pilot_train_dropout(trs_env* e, const trs_dropout_config* cfg_or_null)
+{
+    trs_dropout_config cfg;
+    trsim::dropout_defaults(&cfg);
+    if (cfg_or_null) {
+        if (const char* why = trsim::dropout_config_error(cfg_or_null)) return trs_internal_fail(TRS_ERR_ARG, why);
+        cfg = *cfg_or_null;
+    }
+    TrsEnvView v; TrsPilotTail t; TrainSession* s;
+    if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    if (s->drop.called) return trs_internal_fail(TRS_ERR_STATE, "trs_pilot_train_dropout was already called in this session");
+    if (s->t > 0) return trs_internal_fail(TRS_ERR_STATE, "trs_pilot_train_dropout comes before the session's first step");
+    DropSession& d = s->drop;
+    d.T = trsim::dropout_threshold(cfg.rate);
+    d.s = trsim::dropout_scale(d.T);
+    d.seed = cfg.seed;
+    d.on = d.T ? cfg.sites : 0u;                                            // rate 0: every site keeps its kernels and its bits
+    if (d.tail()) {
+        HIPCHK(hipSetDevice(v.device));
+        HIPCHK(d.act.alloc((size_t)s->n_cap * (100 + 50 + 25) * sizeof(float)));
+    }
+    d.called = true;
     return TRS_OK;
 }
 
@@ -406,6 +453,16 @@ TRS_EXPORT int trs_pilot_train_debug(trs_env* e, int which, float* h_dst, size_t
     else if (which == TRS_TRAIN_DBG_LOSS) src = reinterpret_cast<const float*>(s->scal.get() + 2);
     if (src) {
         HIPCHK(hipMemcpy(h_dst, src, want * sizeof(float), hipMemcpyDeviceToHost));
+        return TRS_OK;
+    }
+    if (which >= TRS_TRAIN_DBG_A1 && which <= TRS_TRAIN_DBG_A3) {       // what the next layer read: a'(l) of a step with dropout, else relu(z(l))
+        const int l = which - TRS_TRAIN_DBG_A1 + 1;
+        if (s->drop.tail()) {
+            HIPCHK(hipMemcpy(h_dst, s->dropped(l), want * sizeof(float), hipMemcpyDeviceToHost));
+            return TRS_OK;
+        }
+        HIPCHK(hipMemcpy(h_dst, s->item(TRS_TRAIN_DBG_Z1 + l - 1), want * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < want; ++i) h_dst[i] = h_dst[i] > 0.0f ? h_dst[i] : 0.0f;
         return TRS_OK;
     }
     if (which == TRS_TRAIN_DBG_SCALE_EXP) {

@@ -107,6 +107,7 @@ inline size_t train_debug_floats(int which, int n, size_t F)
     if (which >= TRS_TRAIN_DBG_V && which < TRS_TRAIN_DBG_V + kTrainArrays) return L.count(which - TRS_TRAIN_DBG_V);
     if (which == TRS_TRAIN_DBG_SCALE_EXP || which == TRS_TRAIN_DBG_LOSS) return 1;
     if (which == TRS_TRAIN_DBG_PACK1) return F * 100;
+    if (which >= TRS_TRAIN_DBG_A1 && which <= TRS_TRAIN_DBG_A3) return (size_t)n * kTailIn[which - TRS_TRAIN_DBG_A1 + 1];   // what dense2, dense3, output_layer read
     return 0;
 }
 

@@ -5,6 +5,7 @@
 //   trs_train_g7_kernel       G7 = [x7 > 0] . 2^-s W1h q1 on the matrix cores from dense1's granules as the forward read them.  The reduction index (the
 //                             output o) is the slow index of the granules, so a workgroup's 128 features x 128 outputs go to LDS as they lie and every
 //                             weight fragment is two ds_read_b64_tr_b16 (tr_fragment), read once; q1's fragments come straight from memory.
+//                             trs_train_g7_drop_kernel: the same body with dropout's s as one more factor, for a step that dropped x7
 //   trs_train_cquant_kernel   G(l) -> q(l) = binary16(G(l) 2^s_l), s_l = train_scale_exponent of the integer maximum of |G(l)|'s bit patterns
 //   trs_train_dgrad_kernel    G(l-1) = [x(l-1) > 0] . 2^-s_l sum_{kh,kw,co} q(l)[y-kh][x-kw][co] W(l)h[kh][kw][ci][co]: a wave owns 32 input pixels x all CIN,
 //                             k runs over (kh, kw, co) in that order; both fragments are 16-byte loads (q(l) is [pixel][co]; the session's own binary16
@@ -44,7 +45,10 @@ struct G7Params {
     int n; size_t F;
 };
 
-__global__ __launch_bounds__(256) void trs_train_g7_kernel(const G7Params p)
+// DROP: x7 is the dropped x7' of "training the pilot's tail, dropout" (the gate carries the mask: a kept positive value stays positive) and the factor is
+// s 2^-s1, one exact binary32 product
+template <bool DROP>
+__device__ __forceinline__ void g7_body(const G7Params p, float scale)
 {
     __shared__ __attribute__((aligned(16))) unsigned char tile[128 * kGwPitch];      // [output][feature of the workgroup's 128]: 40 KB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(256) void trs_train_g7_kernel(const G7Params p)
     h16x8 bw[8];                                                                    // the wave's 32 features x all 128 outputs
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) bw[ks] = tr_fragment(tile, lane, 32 * wave, 16 * ks);
-    const float back = pow2f(-*p.sexp1);
+    const float back = DROP ? scale * pow2f(-*p.sexp1) : pow2f(-*p.sexp1);
     const int h = lane >> 5;
     const size_t k = (size_t)g0 * 8 + 32 * wave + (lane & 31);                      // the lane's feature
     unsigned mx = 0;
@@ -80,6 +84,9 @@ __global__ __launch_bounds__(256) void trs_train_g7_kernel(const G7Params p)
     }
     wave_max_bits(mx, p.max_bits, lane);
 }
+
+__global__ __launch_bounds__(256) void trs_train_g7_kernel(const G7Params p) { g7_body<false>(p, 1.0f); }
+__global__ __launch_bounds__(256) void trs_train_g7_drop_kernel(const G7Params p, const float scale) { g7_body<true>(p, scale); }
 
 // ---- G(l) as binary16 under the layer's scale ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void trs_train_cquant_kernel(const float* G, const unsigned* max_bits, unsigned short* q, int* sexp, size_t count)
@@ -271,7 +278,7 @@ int enter_conv(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrainSession** ts, Co
 
 }  // namespace
 
-int trsim::trs_train_conv_step(ConvSession& conv, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n, const AdamK& k)
+int trsim::trs_train_conv_step(ConvSession& conv, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n, const AdamK& k, float x7_scale)
 {
     ConvSession* const s = &conv;
     TrsPilotConvs pc;
@@ -283,7 +290,9 @@ int trsim::trs_train_conv_step(ConvSession& conv, trs_env* e, const TrsEnvView& 
         G7Params gp{};
         gp.w1 = reinterpret_cast<const u4v*>(t.w1_pack); gp.q1 = reinterpret_cast<const u4v*>(q1); gp.x7 = static_cast<const unsigned short*>(t.x7);
         gp.G = s->G.get(); gp.sexp1 = sexp1; gp.max_bits = scal + 2 * 3; gp.n = n; gp.F = t.F;
-        hipLaunchKernelGGL(trs_train_g7_kernel, dim3(t.G / 16, std::min(8, (n + 31) / 32)), dim3(256), 0, st, gp);
+        const dim3 grid(t.G / 16, std::min(8, (n + 31) / 32));
+        if (x7_scale != 0.0f) hipLaunchKernelGGL(trs_train_g7_drop_kernel, grid, dim3(256), 0, st, gp, x7_scale);
+        else hipLaunchKernelGGL(trs_train_g7_kernel, grid, dim3(256), 0, st, gp);
     }
     for (int j = kConvTrainLayers - 1; j >= s->lowest; --j) {
         const ConvGeom& g = s->geo[j];

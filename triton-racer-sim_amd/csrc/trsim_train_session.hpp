@@ -7,6 +7,7 @@
 #include <cstring>
 #include <memory>
 
+#include "trsim_dropout.hpp"
 #include "trsim_internal.hpp"
 #include "trsim_mem.hpp"
 #include "trsim_train.hpp"
@@ -29,8 +30,18 @@ struct ConvSession {
     bool trained(int j) const { return (mask >> j) & 1u; }
 };
 
+// dropout behind conv7 (trs_pilot_train_dropout): `on` holds the bits of the sites that drop at all (none at rate 0, where T = 0)
+struct DropSession {
+    bool called = false;
+    uint32_t on = 0, T = 0; float s = 1.0f; uint64_t seed = 0;
+    DevBuf<float> act;                    // a'1 | a'2 | a'3, each for n_cap frames: allocated when one of sites 1 .. 3 is on
+    bool site(int j) const { return (on >> j) & 1u; }
+    bool tail() const { return (on & 0xEu) != 0; }
+};
+
 struct TrainSession {
     trs_train_config cfg{};
+    DropSession drop;
     int64_t t = 0;
     size_t F = 0; int n_cap = 0, last_n = 0;
     TrainLayout L{};
@@ -40,6 +51,12 @@ struct TrainSession {
     DevBuf<unsigned> scal;                // [0] max |delta1| bits, [1] the scale's exponent (int), [2] the loss (float)
     std::unique_ptr<ConvSession> conv;    // empty: the convolutions stay as loaded
     float* item(int which) const { return fwd.get() + (size_t)n_cap * train_frame_floats(which); }   // TRS_TRAIN_DBG_OUT .. DELTA4
+    float* dropped(int l) const                                                                      // a'(l), l = 1 .. 3
+    {
+        size_t o = 0;
+        for (int j = 1; j < l; ++j) o += (size_t)kDropoutWidth[j];
+        return drop.act.get() + (size_t)n_cap * o;
+    }
 };
 
 // how every entry point behind trs_pilot_train_begin begins: the view, the pilot's tail and its open session
@@ -55,8 +72,9 @@ inline int enter_session(trs_env* e, TrsEnvView* v, TrsPilotTail* t, TrainSessio
 inline float widen_h(unsigned short u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; }
 
 // One backward pass and Adam over the trained convolutions, on the stream, from the tail's q1 [n padded to 64][128] and its exponent; before the tail's own
-// Adam, with that step's constants.  Defined in trsim_train_conv.hip, called by trs_pilot_train_step.
+// Adam, with that step's constants.  x7_scale: dropout's s where the step dropped x7 (G7 takes it as one more factor), 0 where it did not: the plain
+// kernel.  Defined in trsim_train_conv.hip, called by trs_pilot_train_step.
 int trs_train_conv_step(ConvSession& s, trs_env* e, const TrsEnvView& v, const TrsPilotTail& t, const unsigned short* q1, const int* sexp1, int n,
-                        const trsim_train_dev::AdamK& k);
+                        const trsim_train_dev::AdamK& k, float x7_scale);
 
 }  // namespace trsim

@@ -319,8 +319,11 @@ class DeviceDataset:
         ``pilot_loss("val", val_batch_size)`` is taken on the fp16 pilot as it drives.  The best epoch's weights are kept
         (``ModelCheckpoint(save_best_only=True)``), ``patience`` epochs without a better validation loss stop the run (``None``: all ``epochs``),
         and at the end the best weights are loaded into the handle.  ``adam``: ``lr``, ``beta1``, ``beta2``, ``eps``, ``layers`` of
-        ``pilot_train_begin``.  Returns the list of ``(train_loss, val_loss)`` per epoch run, ``train_loss`` the mean of the batches' losses.
-        Not here: dropout, training conv1 .. conv3, the model types with side inputs."""
+        ``pilot_train_begin``, and its ``dropout`` (a rate; the reference's is 0.1), ``dropout_sites``, ``dropout_seed``: training-mode dropout
+        behind conv7 and the hidden dense layers ("training the pilot's tail, dropout"), in the training steps alone — ``train_loss`` is the
+        dropped network's, ``val_loss`` is taken without dropout, as Keras reports them.  Returns the list of ``(train_loss, val_loss)`` per epoch
+        run, ``train_loss`` the mean of the batches' losses.
+        Not here: dropout behind conv1 .. conv6, training conv1 .. conv3, the model types with side inputs."""
         if not self.with_frames:
             raise RuntimeError("a physics-only set has no frames for the pilot")
         torch, env = self.torch, self.env
@@ -365,7 +368,8 @@ class DeviceDataset:
 
     def fit(self, epochs, batch_size, convs=("conv4", "conv5", "conv6", "conv7"), **kwargs):
         """``fit_tail`` under the name of what it does by default here: dense1 .. output_layer and the convolutions named in ``convs`` (conv4 ..
-        conv7 unless told otherwise) are trained; conv1 .. conv3 stay as loaded, and there is no dropout."""
+        conv7 unless told otherwise) are trained; conv1 .. conv3 stay as loaded.  ``dropout=0.1`` adds the reference's dropout behind conv7 and the hidden dense
+        layers (``fit_tail``)."""
         return self.fit_tail(epochs, batch_size, convs=convs, **kwargs)
 
 

@@ -881,13 +881,50 @@ class BatchedEnv:
             c.train_mask = sum(1 << _ffi.TRAIN_LAYERS.index(nm) for nm in set(layers))
         return c
 
-    def pilot_train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None, convs=None):
+    def dropout_config(self, rate=0.1, sites=None, seed=0):
+        """``trs_dropout_config``: the rate, the sites — names out of ``_ffi.DROPOUT_SITES`` (``"x7"``: conv7's output, ``"a1"`` .. ``"a3"``:
+        relu(z1) .. relu(z3)) or the bit mask itself; ``None``: all four — and the seed of the draws."""
+        if not getattr(self.api, "has_dropout", False):
+            raise RuntimeError("this library has no dropout (trs_pilot_train_dropout): HIP library only")
+        c = _ffi.TrsDropoutConfig()
+        self.api.default_dropout_config(C.byref(c))
+        c.rate, c.seed = float(rate), int(seed)
+        if sites is not None:
+            if isinstance(sites, int):
+                c.sites = sites
+            else:
+                unknown = [nm for nm in sites if nm not in _ffi.DROPOUT_SITES]
+                if unknown:
+                    raise ValueError(f"dropout_sites must come from {_ffi.DROPOUT_SITES}: {unknown}")
+                c.sites = sum(1 << _ffi.DROPOUT_SITES.index(nm) for nm in set(sites))
+        return c
+
+    def pilot_train_dropout_keep(self, t, site, n, rate=None, seed=None):
+        """The keep flags of step ``t`` (the session's first step is 1) at ``site`` (0..3 or a name out of ``_ffi.DROPOUT_SITES``) for the first ``n``
+        frame slots of a batch: ``bool[n, width]``, width F, 100, 50, 25 (``trs_train_dropout_keep``: host arithmetic, no GPU work).  ``rate`` and
+        ``seed``: ``None`` takes what the last ``pilot_train_begin(dropout=...)`` of this handle was given."""
+        self._need_train()
+        site = _ffi.DROPOUT_SITES.index(site) if isinstance(site, str) else int(site)
+        last = getattr(self, "_train_dropout", None)
+        if (rate is None or seed is None) and last is None:
+            raise RuntimeError("no session with dropout on this handle: pass rate and seed")
+        cfg = self.dropout_config(last[0] if rate is None else rate, None, last[1] if seed is None else seed)
+        width = int(self._pilot_arrays[14].shape[0]) if site == 0 else (100, 50, 25)[site - 1] if 1 <= site <= 3 else 0
+        keep = np.empty((max(int(n), 0), width), np.uint8)
+        self.api.check(self.api.train_dropout_keep(C.byref(cfg), int(t), site, int(n), width, keep.ctypes.data), "train_dropout_keep")
+        return keep.astype(bool)
+
+    def pilot_train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None, convs=None, dropout=None, dropout_sites=None, dropout_seed=0):
         """Open a training session on the loaded pilot's dense tail (``trs_pilot_train_begin``): fp32 master weights from the arrays ``pilot_load``
         was given, Adam's moments at zero.  22-array model types only.  ``convs``: names out of ``_ffi.TRAIN_CONV_LAYERS`` (``"conv4"`` ..
         ``"conv7"``) that are trained as well (``trs_pilot_train_convs``); ``None``: the convolutions stay as loaded.  conv1 .. conv3 always do.
+        ``dropout``: the rate of training-mode dropout behind conv7 and the three hidden dense layers (``trs_pilot_train_dropout``; the reference's
+        is 0.1), ``dropout_sites`` the sites (``dropout_config``; ``None``: all four), ``dropout_seed`` the seed of the draws; ``None``: no
+        dropout.  Inference never drops.
         Until ``pilot_train_end`` the handle refuses ``pilot_load`` and ``pilot_tuning``; it drives with the current weights all along."""
         self._need_train()
         cfg = self.train_config(lr, beta1, beta2, eps, layers)
+        drop = None if dropout is None else self.dropout_config(dropout, dropout_sites, dropout_seed)
         mask = 0
         if convs is not None:
             unknown = [nm for nm in convs if nm not in _ffi.TRAIN_CONV_LAYERS]
@@ -898,14 +935,21 @@ class BatchedEnv:
         ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in tail])
         self.api.check(self.api.pilot_train_begin(self._h, C.byref(cfg), ptrs), "pilot_train_begin")
         self._train_convs = False
-        if convs is not None:                                           # (an empty list: the library's refusal of a zero mask)
-            cptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in self._pilot_arrays[6:14]])
-            rc = self.api.pilot_train_convs(self._h, mask, cptrs)
+        self._train_dropout = None
+
+        def second(rc, what):
             if rc != 0:
                 why = self.api.last_error()                             # the refusal's own text, before another call of the library replaces it
                 self.api.pilot_train_end(self._h)                       # no half-open session behind a refusal
-                raise RuntimeError(f"{self.api.prefix}pilot_train_convs failed ({rc}): {why.decode() if why else ''}")
+                raise RuntimeError(f"{self.api.prefix}{what} failed ({rc}): {why.decode() if why else ''}")
+
+        if convs is not None:                                           # (an empty list: the library's refusal of a zero mask)
+            cptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in self._pilot_arrays[6:14]])
+            second(self.api.pilot_train_convs(self._h, mask, cptrs), "pilot_train_convs")
             self._train_convs = True
+        if drop is not None:
+            second(self.api.pilot_train_dropout(self._h, C.byref(drop)), "pilot_train_dropout")
+            self._train_dropout = (float(dropout), int(dropout_seed))
 
     def pilot_train_step(self, frames, labels, n=None, loss=None):
         """One Adam step on ``frames uint8[n, H, W, 3]`` and ``labels float32[n, 2]`` on the device (torch tensors, anything with
@@ -928,7 +972,8 @@ class BatchedEnv:
         F = int(self._pilot_arrays[14].shape[0])
         n = int(getattr(self, "_train_last_n", 0))
         sizes = {"out": 2 * n, "z1": 100 * n, "z2": 50 * n, "z3": 25 * n, "delta1": 100 * n, "delta2": 50 * n, "delta3": 25 * n, "delta4": 2 * n,
-                 "gw1": F * 100, "gw2": 5000, "gw3": 1250, "gw4": 50, "gb1": 100, "gb2": 50, "gb3": 25, "gb4": 2, "scale_exp": 1, "loss": 1, "pack1": F * 100}
+                 "gw1": F * 100, "gw2": 5000, "gw3": 1250, "gw4": 50, "gb1": 100, "gb2": 50, "gb3": 25, "gb4": 2, "scale_exp": 1, "loss": 1, "pack1": F * 100,
+                 "a1": 100 * n, "a2": 50 * n, "a3": 25 * n}
         size = self._pilot_arrays[14 + int(array)].size if item in ("m", "v") else sizes[item]
         out = np.empty(size, np.float32)
         self.api.check(self.api.pilot_train_debug(self._h, which, out.ctypes.data, out.size), "pilot_train_debug")
