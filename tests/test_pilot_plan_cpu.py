@@ -56,7 +56,8 @@ def plan_of(exe, h, w, n_cap, cus=256, arrays=22, **tuning):
 
 
 def call_of(exe, h, w, n_cap, n, cus=256, arrays=22, **tuning):
-    (line,) = run_driver(exe, "call", h, w, n_cap, cus, arrays, n, *[f"{k}={v}" for k, v in tuning.items()])
+    """The call line of one batch: dense1's slices, the head's roll and grid, every layer's own grid (the launches and blocks behind it: tests/test_pilot_pass_cpu.py)."""
+    (line,) = run_driver(exe, "call", h, w, n_cap, cus, arrays, n, "show=brief", *[f"{k}={v}" for k, v in tuning.items()])
     return parse(line)[1]
 
 
@@ -267,7 +268,7 @@ def test_every_plan_fits_and_is_aligned(driver, w, n_cap):
 def test_dense1_slices_cover_k_and_frame_groups_cover_the_batch(driver, w):
     pat = re.compile(r" n=(\d+) G=(\d+) nf=(\d+) gps=(\d+) KS=(\d+) groups=(\d+) dense_grid=(\d+) dense_lds=(\d+) ")
     lines = 0
-    for line in run_driver(driver, "call", "29:260", w, 1027, 256, 22, "1:300"):
+    for line in run_driver(driver, "call", "29:260", w, 1027, 256, 22, "1:300", "show=brief"):
         if not line.startswith("call "):
             assert line.startswith("refuse "), line
             continue

@@ -2,7 +2,7 @@
 // the layer geometry of Keras_2D_CNN for a frame size, the kernel of every layer with its LDS layout (pilot_plan), what a call of n frames adds to it
 // (dense_call, head_call, the grids), the constants the plan shares with the kernels, the packing of the Keras arrays into fp16 granules, and the
 // blob of small fp32 weights the tail kernels read (its slots XO_*, the branch widths, pack_tail_blob).
-// No device pointer lives here: trsim_pilot.hip fills its kernel parameter blocks from a PilotPlan.  tests/pilot_plan_driver.cpp runs it on the CPU.
+// No device pointer lives here: trsim_pilot_pass.hpp fills the kernels' parameter blocks and schedules a pass from a PilotPlan.  tests/pilot_plan_driver.cpp runs both on the CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -354,6 +354,20 @@ inline unsigned short host_f2h(float f)
     const uint32_t m = sub ? (a & 0x7FFFFFu) | 0x800000u : a - 0x38000000u, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
     const uint32_t r = (m >> shift) + ((rem > half || (rem == half && ((m >> shift) & 1u))) ? 1u : 0u);
     return (unsigned short)(sign | r);
+}
+// binary16 -> binary32, exact (the debug getter's; packing needs host_f2h only)
+inline float host_h2f(unsigned short u)
+{
+    const uint32_t sign = (uint32_t)(u & 0x8000u) << 16, e = (u >> 10) & 0x1Fu, m = u & 0x3FFu;
+    uint32_t x;
+    if (e == 0x1Fu) x = sign | 0x7F800000u | (m << 13);                     // infinity, NaN
+    else if (e) x = sign | ((e + 112u) << 23) | (m << 13);
+    else {                                                                  // zero or a subnormal: m x 2^-24
+        const float f = (float)m * (1.0f / 16777216.0f);
+        std::memcpy(&x, &f, 4); x |= sign;
+    }
+    float f; std::memcpy(&f, &x, 4);
+    return f;
 }
 // w: granules [G_pad][COUT_PAD][8] of fp16; goff: [G_pad] byte offset of granule g relative to the output pixel's input base; bias: [COUT_PAD]
 struct PackedLayer { std::vector<unsigned short> w; std::vector<int> goff; std::vector<float> bias; };

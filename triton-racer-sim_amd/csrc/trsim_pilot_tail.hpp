@@ -148,15 +148,7 @@ __global__ __launch_bounds__(256) void trs_pilot_tail_kernel(const TailParams p)
 // 15.5 -> 7.3 us (and the tail 7.5 -> 5.8 with 8 slabs instead of 36); 47 -> 36 us at 512 x 240x320.  Measured and NOT kept
 // (profiles/r02_pilot_dense.txt): the tail in the same launch, run by the last K slice of a frame group to arrive — the hand-over
 // between XCDs costs a write-through drain (2.2 us) and an sc1 read (4 us) and leaves 32 workgroups to do what 256 do in the
-// tail kernel: 17 us in one launch against 7.3 + 5.8 in two.
-struct DenseParams {
-    const u4v* act;            // conv7's output: fp16 [n][G] granules (the NHWC flatten)
-    const u4v* w;              // [G][128] granules
-    const float* bias;         // [128]
-    float* slab;               // [KS][n][100] fp32
-    int n, G, gps, KS, groups;
-};
-
+// tail kernel: 17 us in one launch against 7.3 + 5.8 in two.  (DenseParams: trsim_pilot_pass.hpp)
 #ifndef TRS_DENSE_ABLATE
 #define TRS_DENSE_ABLATE 0   /* timing-only diagnostic builds (scripts/r04_dense_ablate.sh), never shipped */
 #endif
