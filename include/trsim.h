@@ -721,8 +721,8 @@ int trs_loader_augment(const trs_loader_config* cfg, const trs_augment_config* a
  * of trs_pilot_forward, takes the loss and its gradient through the four dense layers, and moves them by Adam, all on the handle's stream and without a
  * byte crossing to the host.  After a step the handle drives with the updated pilot (trs_pilot_forward, trs_pilot_act, trs_step_pilot, trs_step_dagger).
  * What stays out: conv1 .. conv3 (conv4 .. conv7 can be trained as well: the next section), dropout behind conv1 .. conv6 (behind conv7 and the hidden
- * dense layers: the section after it), the model types with side inputs (28 and 42 arrays), feature caching across epochs, any exchange of gradients
- * between GPUs.
+ * dense layers: the section after it), cnn_2d_full_house (42 arrays; the 28-array type: "training the speed-as-feature pilot" below), feature caching
+ * across epochs, any exchange of gradients between GPUs.
  *   trs_pilot_train_begin: fp32 master weights and Adam's m and v (zero) for the eight arrays dense1 .. output_layer, t = 0.  The handle keeps dense1 as
  *     binary16 only, so h_tail_arrays[0], dense1's kernel float[F][100] as trs_pilot_load got it, is read from the host; the other seven arrays are taken
  *     from the device, where the tail kernel reads them (entries 1..7 are not read and may be NULL).  cfg NULL: the defaults.
@@ -732,7 +732,7 @@ int trs_loader_augment(const trs_loader_config* cfg, const trs_augment_config* a
  *   trs_pilot_train_debug: item `which` (TRS_TRAIN_DBG_*) of the last step as floats; the sibling of trs_pilot_debug_layer.  Synchronises.
  *   trs_pilot_train_end: releases the session's buffers; the handle keeps driving with the trained weights.
  *   Refusals.  TRS_ERR_STATE: no pilot loaded; begin twice; step, get, debug or end without begin; trs_pilot_load or trs_pilot_set_tuning between begin
- *     and end (end the session first).  TRS_ERR_LIMIT: a pilot of 28 or 42 arrays.  TRS_ERR_ARG: the config (struct_size; lr or eps not positive and
+ *     and end (end the session first).  TRS_ERR_LIMIT: a pilot of 28 or 42 arrays (28: trs_pilot_train_begin_ex).  TRS_ERR_ARG: the config (struct_size; lr or eps not positive and
  *     finite; a beta outside [0, 1); train_mask 0 or with bits beyond 3), a NULL dense1 kernel, n outside [1, n_envs], NULL frames or labels, an unknown
  *     item or a size that is not the item's. */
 typedef struct trs_train_config {
@@ -811,6 +811,37 @@ typedef struct trs_dropout_config {
 void trs_default_dropout_config(trs_dropout_config* cfg);
 int trs_pilot_train_dropout(trs_env* env, const trs_dropout_config* cfg_or_null);
 int trs_train_dropout_keep(const trs_dropout_config* cfg_or_null, int64_t t, int site, int n, int64_t width, uint8_t* h_keep);
+
+/* ---- training the speed-as-feature pilot: side branch and tail (include/trsim_spec.h, "training the pilot's tail, side branch") ----
+ * cnn_2d_speed_as_feature (28 arrays) feeds speed / 20 through feature1 -> feature2 -> feature3 (1 -> 4 -> 8 -> 16, ReLU) and concatenates the result
+ * behind the flatten in front of dense1 (components/keras_train.py:127-174,390-392).  The _ex entry points open the session of either trained model type;
+ * its 14 trained arrays are arrays 14 .. 27 of trs_pilot_load's list: dense1 (kernel float[F + 16][100]) .. output_layer, then feature1 .. feature3.  Bits
+ * 4 .. 6 of trs_train_config.train_mask name feature1 .. feature3 (rows F .. F + 15 of dense1's kernel move with dense1, bit 0); cfg NULL trains all seven
+ * layers.  trs_pilot_train_convs, trs_pilot_train_dropout (site 0 masks x7 alone: the concatenation lies behind that Dropout; the feature layers have
+ * none), trs_pilot_train_debug, trs_pilot_train_end and the conv getters serve either session.  cnn_2d_full_house (42 arrays) stays refused.
+ *   trs_pilot_train_begin_ex: n_arrays = 8 with a 22-array pilot is trs_pilot_train_begin; n_arrays = 14 with a 28-array pilot opens the side session.
+ *     Only h_arrays[0], dense1's whole kernel as trs_pilot_load got it, is read from the host; the rest come from the device.
+ *   trs_pilot_train_step_ex: d_features float[n][1], speed / 20 per frame as trs_sample_batch writes it for TRS_LOADER_SPEED_FEATURE; required for a
+ *     28-array session, ignored for a 22-array one (where the call is trs_pilot_train_step).
+ *   trs_pilot_train_get_ex: the 8 or 14 masters (a NULL entry is skipped) and the step count; synchronises.
+ *   trs_pilot_train_debug_side: item `which` (TRS_TRAIN_SIDE_*) of the last step of a 28-array session as floats.  Synchronises.
+ *   Refusals.  TRS_ERR_LIMIT: a 42-array pilot.  TRS_ERR_ARG: n_arrays that is neither 8 nor 14 or does not match the loaded pilot; the config (bits beyond 6,
+ *     or beyond 3 for 8 arrays); a NULL dense1 kernel; NULL d_features on a 28-array session; trs_pilot_train_step or trs_pilot_train_get on a 28-array
+ *     session (use _ex); an unknown item or a size that is not the item's.  TRS_ERR_STATE: trs_pilot_train_debug_side on a 22-array session, and as above. */
+enum {
+    TRS_TRAIN_SIDE_FIN = 0,          /* float[n][1]: the feature as the step read it */
+    TRS_TRAIN_SIDE_Y1, TRS_TRAIN_SIDE_Y2, TRS_TRAIN_SIDE_Y3,       /* the branch's activations (behind the ReLU) [n][4], [n][8], [n][16] */
+    TRS_TRAIN_SIDE_DY1, TRS_TRAIN_SIDE_DY2, TRS_TRAIN_SIDE_DY3,    /* the loss's gradient by the branch's pre-activations [n][4], [n][8], [n][16] */
+    /* + j (0..6): the side arrays W1Y float[16][100] (rows F .. F + 15 of dense1's kernel), feature1's kernel [1][4] and bias, feature2's [4][8] and bias,
+     * feature3's [8][16] and bias */
+    TRS_TRAIN_SIDE_G = 8,            /* the gradient of side array j */
+    TRS_TRAIN_SIDE_M = 16,           /* Adam's m */
+    TRS_TRAIN_SIDE_V = 24            /* Adam's v */
+};
+int trs_pilot_train_begin_ex(trs_env* env, const trs_train_config* cfg_or_null, const float* const* h_arrays, int n_arrays);
+int trs_pilot_train_step_ex(trs_env* env, const uint8_t* d_frames, const float* d_features, const float* d_labels, int n, float* d_loss_or_null);
+int trs_pilot_train_get_ex(trs_env* env, float* const* h_arrays_out, int n_arrays, int* t_out_or_null);
+int trs_pilot_train_debug_side(trs_env* env, int which, float* h_dst, size_t n_floats);
 
 /* ---- multi-GPU: the one exchange (north_star: "a single RCCL all-gather over xGMI of episode returns") ----
  * One process (or thread) per GPU owns one handle = one shard of envs; shards never exchange state.  The reference has no

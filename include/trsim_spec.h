@@ -395,8 +395,8 @@
  *     alpha_t at the defaults (bit patterns): t = 1: 39a5cb17, t = 2: 3976beef, t = 1000: 3a507326.  c1 = 3dccccd0, c2 = 3a831200.
  *     One update, g = 1, m = v = 0, w = 1, t = 1: m = 3dccccd0, v = 3a831200, w = 3f7fbe77 (0.99900001: Adam's first step is lr in size).
  *   Not here: conv1 .. conv3 (conv4 .. conv7: the next section), dropout behind conv1 .. conv6 (behind conv7 and the hidden dense layers: "training the
- *   pilot's tail, dropout"; keras_train.py applies 0.1 everywhere; tests/golden/train_pilot_fixture.py trains without), the model types with side inputs
- *   (28 and 42 arrays: refused), feature caching across epochs, gradient exchange between GPUs.
+ *   pilot's tail, dropout"; keras_train.py applies 0.1 everywhere; tests/golden/train_pilot_fixture.py trains without), cnn_2d_full_house (42 arrays:
+ *   refused; the 28-array type: "training the pilot's tail, side branch"), feature caching across epochs, gradient exchange between GPUs.
  *   tests/test_train_cpu.py restates steps 2 to 6 in numpy and checks the restatement against torch.autograd in binary64; tests/test_train_gpu.py compares the
  *   kernels with it (Adam bit for bit from the device's gradient); csrc/trsim_train.hpp holds the rules a host compiler can build.
  *
@@ -425,7 +425,7 @@
  *      trs_pilot_train_convs), m = v = 0 at the start.  The pass writes each kernel's binary16 value with host_f2h's rounding at
  *      ((kh run_pad + kw CIN / 8 + ci / 8) COUT_PAD + co) 8 + ci % 8 of ConvLayer::w (pack_layer's order; run_pad = 3 CIN / 8, COUT_PAD = COUT), into the
  *      session's own [kh][kw][ci][co] copy that step 4 reads, and the bias where the kernels read it.  Step 4 of layer l runs before layer l's Adam.
- *   Not here: conv1 .. conv3 (5 x 5, stride 2, the fused head), dropout behind conv1 .. conv6, the 28- and 42-array model types, feature caching, the
+ *   Not here: conv1 .. conv3 (5 x 5, stride 2, the fused head), dropout behind conv1 .. conv6, the 42-array model type, feature caching, the
  *   multi-GPU exchange.
  *   tests/test_train_conv_cpu.py restates steps 2 to 5 in numpy, checks the restatement against torch.autograd in binary64 and shows what the reference
  *   notices; tests/test_train_conv_gpu.py compares the kernels with it within derived bounds (Adam bit for bit from the device's gradient);
@@ -462,6 +462,36 @@
  *   tests/test_dropout_cpu.py restates the paragraph in numpy, compares trs_train_dropout_keep with it bit for bit and checks the dropped passes against
  *   torch.autograd in binary64 with the masks as constants; tests/test_dropout_gpu.py compares the kernels with it (x7' and a'(l) bit for bit);
  *   csrc/trsim_dropout.hpp is the one place the kernels and the host take the draw from (tests/dropout_driver.cpp).
+ *
+ * ---- training the pilot's tail, side branch (trs_pilot_train_begin_ex, trs_pilot_train_step_ex; the 28-array model type; HIP library only)
+ *   cnn_2d_speed_as_feature = Keras_2D_CNN.get_model(num_feature_vectors = 1) (components/keras_train.py:127-174,390-392): the car's speed / 20 goes through
+ *   feature1 -> feature2 -> feature3 (Dense 4, 8, 16, ReLU) and is concatenated behind the flatten in front of dense1.  The session trains 14 arrays, arrays
+ *   14 .. 27 of trs_pilot_load: dense1 .. output_layer as in "training the pilot's tail", with W1 of (F + 16) x 100 values, then F1, bF1, F2, bF2, F3, bF3
+ *   (kernels [IN][OUT]).  W1Y = rows F .. F + 15 of W1, kept in binary32 where trs_pilot_tail_ex_kernel reads them; rows 0 .. F - 1 are the flatten's, as before.
+ *   Inputs of a step: the frames and labels of the tail's section and s20[n][1] binary32, the feature as the speed_feature loader delivers it
+ *   (s20 = row[4] / 20: the same bits as the speed / 20.0f trs_pilot_tail_ex_kernel computes).
+ *   1. Forward.  fin = s20.  y1[j] = relu(fmaf(fin, F1[0][j], bF1[j])), 4 values; y2 = relu(F2^T y1 + bF2), 8 values, and y3 = relu(F3^T y2 + bF3), 16
+ *      values: one fmaf chain per unit from the bias, k ascending, s = fmaf(y[k], F[k][o], s) — what dense_small computes.  z1 = the split-K slabs added in
+ *      slice order (binary32, from +0), then z1 = fmaf(y3[k], W1Y[k][o], z1) for k = 0 .. 15 ascending.  a1 = relu(z1), and dense2 -> dense3 -> output_layer
+ *      follow as in step 1 of the tail's section.  out equals trs_pilot_forward_ex's on the same frames and speeds bit for bit.
+ *   2. The loss and delta4 .. delta1: steps 2 and 3 of the tail's section, unchanged.
+ *   3. Through the branch, binary32, per frame: delta-y3[k] = [y3[k] > 0] * sum_o W1Y[k][o] delta1[o], o = 0 .. 99 ascending; delta-y2[j] = [y2[j] > 0] *
+ *      sum_k F3[j][k] delta-y3[k]; delta-y1[j] = [y1[j] > 0] * sum_k F2[j][k] delta-y2[k]: each one fmaf chain from +0, s = fmaf(W[row][o], delta[o], s).
+ *   4. Gradients, binary32, one chain per value over the frames in ascending order, as step 4 of the tail's section: gW1Y[k][o] = sum_i y3_i[k] delta1_i[o],
+ *      gF3[j][k] = sum_i y2_i[j] delta-y3_i[k], gF2[j][k] = sum_i y1_i[j] delta-y2_i[k] as s = fmaf(y, delta, s) from +0; gbF3, gbF2, gbF1 = sum_i of
+ *      delta-y3, delta-y2, delta-y1 as s = s + delta.  gF1[0][j] = sum_i p_i[j] with p_i[j] = fin_i * delta-y1_i[j], one binary32 product, as s = s + p: the
+ *      feature may be negative, and the chains of the first form gate their first factor.  The rows 0 .. F - 1 of gW1 are step 5 of the tail's section over
+ *      x7 and the quantised delta1: the matrix-core GEMM does not see the branch.
+ *   5. Adam: step 6 of the tail's section over all 14 arrays; W1Y and the six branch arrays are also written where trs_pilot_tail_ex_kernel reads them, so
+ *      the handle drives with the updated pilot.  Bits 0 .. 3 of train_mask are the tail's layers (W1Y moves with dense1), bits 4 .. 6 feature1 .. feature3.
+ *   Dropout (the section above): site 0 masks x7 alone, since Keras concatenates behind the Dropout on x; sites 1 .. 3 are unchanged, and delta-y3 is taken
+ *      from the delta1 that carries site 1's mask and scale.  The feature layers have no dropout in the reference: fin, y1 .. y3 are the same with and without.
+ *   The convolutions (trs_pilot_train_convs): G7 reads q1, the binary16 copy of rows 0 .. F - 1 of W1 and x7 alone, so the section applies as it stands.
+ *   No floating-point atomics anywhere: two runs agree bit for bit.
+ *   Not here: cnn_2d_full_house (42 arrays: its two heads both feed conv7's gradient; refused with TRS_ERR_LIMIT), and what the tail's section leaves out.
+ *   tests/test_train_side_cpu.py restates steps 1 to 4 in numpy and checks the restatement against torch.autograd in binary64; tests/test_train_side_gpu.py
+ *   compares the kernels with it (out, fin, y1 .. y3 and Adam bit for bit); csrc/trsim_train.hpp holds the layout of the 14 arrays and the count and mask rules
+ *   (tests/train_side_driver.cpp).
  */
 #ifndef TRSIM_SPEC_H
 #define TRSIM_SPEC_H

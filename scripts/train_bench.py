@@ -24,7 +24,11 @@ With --dropout RATE the session drops at all four sites behind conv7 (trs_pilot_
 printed beside its minimum, and a further copy leg moves the bytes of the mask pass over x7 (n F 2 read and written), the one part of dropout that moves
 real bytes.  Pass line (profiles/r36_dropout.txt): the step's median with dropout less the median without, on the same box, is at most 1.25 x that copy
 plus the spread of the runs without.
-Run from the repository root: python scripts/train_bench.py [--convs] [--dropout RATE] [> profiles/rNN_train_tail.txt]"""
+With --arch speed_feature the pilot is the 28-array cnn_2d_speed_as_feature ("training the pilot's tail, side branch"): the step is trs_pilot_train_step_ex with
+a feature per frame, the forward leg trs_pilot_forward_ex, and the torch leg the step that replaces: the nn.Linear branch 1 -> 4 -> 8 -> 16 on the feature, its
+output concatenated behind conv7's features, the nn.Linear tail, mse_loss, backward(), Adam.step().  The medians of the three runs are printed beside the minima.
+Pass line: the part behind conv7 is faster than that torch step.
+Run from the repository root: python scripts/train_bench.py [--convs] [--dropout RATE] [--arch speed_feature] [> profiles/rNN_train_tail.txt]"""
 import csv
 import glob
 import os
@@ -37,14 +41,16 @@ ROUNDS = 3
 SPEC = [(5, 2, 3, 24), (5, 2, 24, 32), (5, 2, 32, 64), (3, 1, 64, 64), (3, 1, 64, 64), (3, 1, 64, 128), (3, 1, 128, 128)]
 
 
-def weights(h, w, seed=0):
+def weights(h, w, seed=0, side=False):
+    """22 arrays; side: the 28 of cnn_2d_speed_as_feature (dense1 takes 16 more rows, feature1 .. feature3 follow output_layer)"""
     rng = np.random.default_rng(seed)
     ws, ih, iw = [], h, w
     for k, s, cin, cout in SPEC:
         ws += [(rng.standard_normal((k, k, cin, cout)) * np.sqrt(2.0 / (k * k * cin))).astype(np.float32), rng.uniform(-0.05, 0.05, cout).astype(np.float32)]
         ih, iw = (ih - k) // s + 1, (iw - k) // s + 1
     dims = [ih * iw * 128, 100, 50, 25, 2]
-    for a, b in zip(dims[:-1], dims[1:]):
+    pairs = list(zip([dims[0] + (16 if side else 0)] + dims[1:-1], dims[1:])) + ([(1, 4), (4, 8), (8, 16)] if side else [])
+    for a, b in pairs:
         lim = np.sqrt(6.0 / (a + b))
         ws += [rng.uniform(-lim, lim, (a, b)).astype(np.float32), rng.uniform(-0.05, 0.05, b).astype(np.float32)]
     return ws, dims[0]
@@ -127,6 +133,13 @@ def main():
         at = sys.argv.index("--dropout")
         dropout = float(sys.argv[at + 1])
         del sys.argv[at:at + 2]
+    side = False
+    if "--arch" in sys.argv:
+        at = sys.argv.index("--arch")
+        if sys.argv[at + 1] not in ("speed_ctl", "speed_feature"):
+            sys.exit("--arch takes speed_ctl (22 arrays, the default) or speed_feature (28 arrays)")
+        side = sys.argv[at + 1] == "speed_feature"
+        del sys.argv[at:at + 2]
     drive = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "--drive" else 0
     import torch
     from triton_racer_sim_amd.env import BatchedEnv
@@ -157,7 +170,7 @@ def main():
 
     only = os.environ.get("TRS_BENCH_SHAPE")                            # "0" or "1": one shape alone (the split by kernel under the tracer, per shape)
     for n, h, w, calls in (SHAPES if only is None else [SHAPES[int(only)]]):
-        ws, F = weights(h, w)
+        ws, F = weights(h, w, side=side)
         env = BatchedEnv(n_envs=n, img_h=h, img_w=w, track=None)
         env.pilot_load(ws)
         env.pilot_train_begin(convs=("conv4", "conv5", "conv6", "conv7") if convs else None, **({} if dropout is None else {"dropout": dropout}))
@@ -168,6 +181,13 @@ def main():
         pf, pl, po = int(frames.data_ptr()), int(labels.data_ptr()), int(out.data_ptr())
         step = lambda: env.api.pilot_train_step(env._h, pf, pl, n, None)
         fwd = lambda: env.api.pilot_forward(env._h, pf, n, po)
+        if side:                                                        # a feature per frame: speed / 20 for the step, the speed itself for the forward pass
+            speed = torch.rand((n, 1), device="cuda") * 20
+            feats = speed / 20
+            torch.cuda.synchronize()
+            ps, pq = int(speed.data_ptr()), int(feats.data_ptr())
+            step = lambda: env.api.pilot_train_step_ex(env._h, pf, pq, pl, n, None)
+            fwd = lambda: env.api.pilot_forward_ex(env._h, pf, ps, None, n, po)
         assert step() == 0 and fwd() == 0
         if drive:
             timed(env, drive, step)
@@ -179,6 +199,20 @@ def main():
         model = torch.nn.Sequential(torch.nn.Linear(F, 100), torch.nn.ReLU(), torch.nn.Linear(100, 50), torch.nn.ReLU(), torch.nn.Linear(50, 25), torch.nn.ReLU(),
                                     torch.nn.Linear(25, 2)).cuda()
         opt = torch.optim.Adam(model.parameters(), lr=1e-3, eps=1e-7)
+        if side and not convs:                                          # the branch on the feature, concatenated behind conv7's features in front of dense1
+
+            class SideTail(torch.nn.Module):
+                def __init__(self):
+                    super().__init__()
+                    lin, relu = torch.nn.Linear, torch.nn.ReLU
+                    self.branch = torch.nn.Sequential(lin(1, 4), relu(), lin(4, 8), relu(), lin(8, 16), relu())
+                    self.tail = torch.nn.Sequential(lin(F + 16, 100), relu(), lin(100, 50), relu(), lin(50, 25), relu(), lin(25, 2))
+
+                def forward(self, x):
+                    return self.tail(torch.cat([x, self.branch(feats)], 1))
+
+            model = SideTail().cuda()
+            opt = torch.optim.Adam(model.parameters(), lr=1e-3, eps=1e-7)
 
         if convs:                                                       # the torch step from x3 on: conv4 .. conv7 in fp32 NCHW, Keras's Flatten, the tail
             ih, iw = env.conv_input_size(0)
@@ -225,6 +259,10 @@ def main():
                   f"against the torch step behind conv3: torch / step = {min(res['torch']) / min(res['step']):.2f} x", flush=True)
         else:
             print(f"  step - forward = {added:.2f} us (the part behind conv7 less the driving tail kernel); torch step / that = {min(res['torch']) / added:.2f} x", flush=True)
+        if side:
+            med = {k: sorted(v)[1] for k, v in res.items()}
+            print(f"  --arch speed_feature, medians: forward {med['fwd']:.2f} us, step {med['step']:.2f} us, step - forward {med['step'] - med['fwd']:.2f} us, "
+                  f"torch step {med['torch']:.2f} us; torch step / (step - forward) = {med['torch'] / (med['step'] - med['fwd']):.2f} x", flush=True)
         env.pilot_train_end()
         env.close()
 

@@ -167,9 +167,13 @@ class TrsDropoutConfig(C.Structure):
 
 
 TRAIN_LAYERS = ("dense1", "dense2", "dense3", "output_layer")           # bit l of trs_train_config.train_mask; their (kernel, bias) pairs are the eight trained arrays
+TRAIN_SIDE_LAYERS = TRAIN_LAYERS + ("feature1", "feature2", "feature3")   # a 28-array session: bits 4 .. 6 name the branch's layers; 14 trained arrays
 TRAIN_DEBUG = {"out": 0, "z1": 1, "z2": 2, "z3": 3, "delta1": 4, "delta2": 5, "delta3": 6, "delta4": 7, "gw1": 8, "gw2": 9, "gw3": 10, "gw4": 11,
                "gb1": 12, "gb2": 13, "gb3": 14, "gb4": 15, "m": 16, "v": 24, "scale_exp": 32, "loss": 33, "pack1": 34,
                "a1": 36, "a2": 37, "a3": 38}                            # TRS_TRAIN_DBG_* ("m", "v": + the array's number 0..7; 35 is no item)
+# TRS_TRAIN_SIDE_* (trs_pilot_train_debug_side): name -> (item, floats per frame, or None for an array's size); "g", "m", "v" take the side array's name
+TRAIN_SIDE_DEBUG = {"fin": (0, 1), "y1": (1, 4), "y2": (2, 8), "y3": (3, 16), "dy1": (4, 4), "dy2": (5, 8), "dy3": (6, 16), "g": (8, None), "m": (16, None), "v": (24, None)}
+TRAIN_SIDE_ARRAYS = {"w1y": (0, 1600), "f1w": (1, 4), "f1b": (2, 4), "f2w": (3, 32), "f2b": (4, 8), "f3w": (5, 128), "f3b": (6, 16)}   # side array -> (number, floats)
 
 LOADER_TYPES = {"speed_ctl": 0, "default": 1, "speed_feature": 2, "full_house": 3}   # TRS_LOADER_*; the names of recorder.LOADERS, in the order of TRS_PILOT_*
 LOADER_FEATURES = {"speed_ctl": 0, "default": 0, "speed_feature": 1, "full_house": 2}
@@ -235,11 +239,14 @@ TRAIN_CONV_SYMBOLS = ["pilot_train_convs", "pilot_train_get_convs", "pilot_train
 # ("training the pilot's tail, dropout") in tests/test_dropout_cpu.py (tests/test_dropout_gpu.py compares the kernels with it, the masks bit for bit)
 DROPOUT_SYMBOLS = ["default_dropout_config", "pilot_train_dropout", "train_dropout_keep"]
 DROPOUT_SITES = ("x7", "a1", "a2", "a3")                                # bit j of trs_dropout_config.sites; units per frame: F, 100, 50, 25
+# HIP library only: training the speed-as-feature pilot (trs_pilot_train_*_ex, trs_pilot_train_debug_side) — its checker is the numpy restatement of
+# include/trsim_spec.h ("training the pilot's tail, side branch") in tests/test_train_side_cpu.py, itself checked against torch.autograd in binary64
+TRAIN_SIDE_SYMBOLS = ["pilot_train_begin_ex", "pilot_train_step_ex", "pilot_train_get_ex", "pilot_train_debug_side"]
 TRAIN_CONV_LAYERS = ("conv4", "conv5", "conv6", "conv7")                # bit j of trs_pilot_train_convs' mask; arrays 6 + 2 j, 7 + 2 j of pilot_load
 TRAIN_CONV_DEBUG = {"delta": 0, "gw": 1, "gb": 2, "mw": 3, "vw": 4, "mb": 5, "vb": 6, "scale_exp": 7, "pack": 8}   # TRS_CONV_DBG_*
 # HIP library only: the CNN pilot is a floating-point kernel whose checker is a PyTorch fp32 reference, not the C oracle
 PILOT_SYMBOLS = ["default_pilot_config", "pilot_load", "pilot_forward", "pilot_forward_host", "pilot_forward_ex", "pilot_forward_host_ex",
-                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + TRAIN_CONV_SYMBOLS + DROPOUT_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
+                 "pilot_debug_layer", "pilot_range_check", "pilot_act", "step_pilot", "default_pilot_tuning", "pilot_set_tuning"] + TRAIN_SYMBOLS + TRAIN_CONV_SYMBOLS + DROPOUT_SYMBOLS + TRAIN_SIDE_SYMBOLS + LENS_SYMBOLS + LIGHT_SYMBOLS + LATENCY_SYMBOLS + JPEG_SYMBOLS + JPEG_DECODE_SYMBOLS + JPEG_CODEC_SYMBOLS + EXPERT_SYMBOLS + LOADER_SYMBOLS + DAGGER_SYMBOLS + AUGMENT_SYMBOLS
 # test hooks of the resident worker: only in csrc/libtrsim_testhooks.so (-DTRS_TEST_HOOKS), never in the product library
 HOOK_SYMBOLS = ["resident_debug_lifetime", "resident_debug_abort"]
 HIP_TESTHOOKS_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrsim_testhooks.so")
@@ -380,6 +387,12 @@ class Api:
             "pilot_train_dropout": (i32, [vp, C.POINTER(TrsDropoutConfig)]),
             "train_dropout_keep": (i32, [C.POINTER(TrsDropoutConfig), C.c_int64, i32, i32, C.c_int64, vp]),
         }
+        train_side = {
+            "pilot_train_begin_ex": (i32, [vp, C.POINTER(TrsTrainConfig), C.POINTER(C.c_void_p), i32]),
+            "pilot_train_step_ex": (i32, [vp, vp, vp, vp, i32, vp]),
+            "pilot_train_get_ex": (i32, [vp, C.POINTER(C.c_void_p), i32, C.POINTER(i32)]),
+            "pilot_train_debug_side": (i32, [vp, i32, vp, C.c_size_t]),
+        }
         hooks = {"resident_debug_lifetime": (i32, [vp, i32]), "resident_debug_abort": (i32, [vp])}
         for name, (res, args) in sigs.items():
             fn = getattr(cdll, prefix + name)
@@ -460,6 +473,12 @@ class Api:
         self.has_dropout = hasattr(cdll, prefix + "pilot_train_dropout")
         if self.has_dropout:
             for name, (res, args) in dropout.items():
+                fn = getattr(cdll, prefix + name)
+                fn.restype, fn.argtypes = res, args
+                setattr(self, name, fn)
+        self.has_train_side = hasattr(cdll, prefix + "pilot_train_step_ex")
+        if self.has_train_side:
+            for name, (res, args) in train_side.items():
                 fn = getattr(cdll, prefix + name)
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)

@@ -86,7 +86,10 @@ struct TrsPilotTail {
     const float* slab; int slices; size_t slab_stride;   // dense1's split-K slabs of the last pass: `slices` of [n][100], slab_stride floats apart
     unsigned short* w1_pack; float* b1;   // dense1 as trs_pilot_dense_kernel reads it: granules [G][128][8] of binary16, bias [128]
     float *w2, *b2, *w3, *b3, *w4, *b4;   // the small layers where the tail kernel reads them (Keras layouts)
-    void** train;                         // the session's slot in the pilot's context (nullptr in it: none open)
+    // a 28-array pilot: where trs_pilot_tail_ex_kernel reads dense1's rows behind the flatten (W1Y [16][100]) and kernel and bias of feature1 .. feature3, in
+    // that order (slots XO_W1Y, XO_F1W .. XO_F3B of the tail's blob, which holds w2 .. b4 as well); nullptr each for a 22-array pilot
+    float* side[7];
+    void** train;                        // the session's slot in the pilot's context (nullptr in it: none open)
 };
 int trs_internal_pilot_tail(trs_env* e, TrsEnvView* v, TrsPilotTail* t);   // the view and the tail of the loaded pilot, or the refusal of every pilot entry point (no handle, no pilot)
 // What a training step may put between the two halves of that pass: fn(arg, x7, n) runs after conv7 has been launched and before dense1 is, and launches

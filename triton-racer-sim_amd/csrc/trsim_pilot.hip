@@ -329,6 +329,8 @@ void fill_tail(PilotCtx* c, TrsPilotTail* t)
     t->slab = static_cast<const float*>(c->slab.get()); t->slices = c->last_slices; t->slab_stride = (size_t)c->last_n * P.L[7].act_elems();
     t->w1_pack = reinterpret_cast<unsigned short*>(c->L[7].w.get()); t->b1 = c->L[7].bias.get();
     t->w2 = B + xo[XO_W2]; t->b2 = B + xo[XO_B2]; t->w3 = B + xo[XO_W3]; t->b3 = B + xo[XO_B3]; t->w4 = B + xo[XO_W4]; t->b4 = B + xo[XO_B4];
+    const int side[7] = {XO_W1Y, XO_F1W, XO_F1B, XO_F2W, XO_F2B, XO_F3W, XO_F3B};
+    for (int j = 0; j < 7; ++j) t->side[j] = P.arch == TRS_PILOT_SPD_CTL ? nullptr : B + xo[side[j]];
     t->train = &c->train;
 }
 }  // namespace

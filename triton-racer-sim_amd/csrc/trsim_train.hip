@@ -20,6 +20,16 @@
 //   trs_train_tail_drop_kernel   sites 1 .. 3: the tail kernel's body with the forward scaling and the backward mask; it stores a'(l), which the small
 //                             kernel reads where it read z(l) (relu(a') is a' bit for bit)
 // and a site that does not keeps the kernels and the bits above.
+// The session of a 28-array pilot, cnn_2d_speed_as_feature (include/trsim_spec.h, "training the pilot's tail, side branch"; trs_pilot_train_begin_ex,
+// trs_pilot_train_step_ex), also trains the branch speed / 20 -> feature1 -> feature2 -> feature3 and dense1's 16 rows behind the flatten (W1Y).  It keeps the
+// kernels above for everything they cover — the flatten rows of dense1 and arrays 1 .. 7, which its layout puts where those kernels are told — and adds
+//   trs_train_tail_side_kernel, trs_train_tail_side_drop_kernel   the tail kernel's body with SIDE: the branch on 1 -> 4 -> 8 -> 16 lanes through LDS first,
+//                             W1Y's rows added to z1 behind the slabs as trs_pilot_tail_ex_kernel adds them (the same chains, the same bits), delta-y3 ..
+//                             delta-y1 behind delta1; stored per frame: fin, y1 .. y3, delta-y1 .. delta-y3 and the products fin delta-y1
+//   trs_train_small_side_kernel   behind trs_train_small_kernel: 1,792 values (gW1Y 1,600; feature3 .. feature1: 128 + 32 + 4 weights, 16 + 8 + 4 biases), one
+//                             thread each over the frames in ascending order, by the same grad_w and grad_b
+//   trs_train_adam_side_kernel    the same Adam over those seven arrays, written to the master and to the slots of the tail's blob the ex tail reads
+// A 22-array step launches none of them and its kernels are the code objects they were (scripts/kernel_diff.py).
 // No floating-point atomics: two runs of a step agree bit for bit.  The rules that need no GPU (config, alpha_t, the scale's exponent, the buffers' layout)
 // are trsim_train.hpp; the session, which trsim_train_conv.hip's entry points open as well, is trsim_train_session.hpp.
 #include <hip/hip_runtime.h>
@@ -53,17 +63,112 @@ struct TailDropParams {
     float *a1, *a2, *a3;
 };
 
-// The two kernels share their body as text (trsim_train_tail_body.hpp says why); the LDS arrays are each kernel's own
+// The side branch of a 28-array pilot (include/trsim_spec.h, "training the pilot's tail, side branch"): the feature, the branch's weights and dense1's rows
+// behind the flatten where trs_pilot_tail_ex_kernel reads them, and where fin, y1 .. y3 and delta-y1 .. delta-y3 are kept for the small gradients
+struct TailSideParams {
+    const float* fin;                                    // [n][1]: speed / 20 as the loader delivers it
+    const float *w1y, *f1w, *f1b, *f2w, *f2b, *f3w, *f3b;
+    float *kfin, *y1, *y2, *y3, *dy1, *dy2, *dy3, *pf1;   // pf1 [n][4]: fin delta-y1, the terms of feature1's kernel gradient
+};
+
+// fin -> y1 -> y2 -> y3 on 1, 4, 8, 16 lanes of the frame's wave: each unit one fmaf chain from its bias, k ascending, then the ReLU, which is what dense_small
+// (trsim_pilot_tail.hpp) computes for these widths.  Returns the wave's y1 | y2 | y3 in LDS (y3 at + 12).
+__device__ __forceinline__ float* side_forward(const TailSideParams& sd, int i, int lane, int wv)
+{
+    __shared__ float sy[4][32];                          // y1 at 0, y2 at 4, y3 at 12, fin at 28
+    float* const y = sy[wv];
+    if (lane == 0) { const float f = sd.fin[i]; y[28] = f; sd.kfin[i] = f; }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 4) {
+        float s = fmaf(y[28], sd.f1w[lane], sd.f1b[lane]);
+        s = s > 0.f ? s : 0.f;
+        y[lane] = s; sd.y1[(size_t)i * 4 + lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 8) {
+        float s = sd.f2b[lane];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s = fmaf(y[k], sd.f2w[k * 8 + lane], s);
+        s = s > 0.f ? s : 0.f;
+        y[4 + lane] = s; sd.y2[(size_t)i * 8 + lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 16) {
+        float s = sd.f3b[lane];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s = fmaf(y[4 + k], sd.f3w[k * 16 + lane], s);
+        s = s > 0.f ? s : 0.f;
+        y[12 + lane] = s; sd.y3[(size_t)i * 16 + lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return y;
+}
+
+// delta-y3[k] = [y3[k] > 0] sum_o W1Y[k][o] delta1[o], then delta-y2 and delta-y1 through feature3 and feature2: lane k owns row k, one fmaf chain from 0, the
+// output index ascending, as the tail's own deltas.  delta1 is (da, db) of the lanes; the weights of 25 terms are requested together.
+__device__ __forceinline__ void side_backward(const TailSideParams& sd, const float* y, float da, float db, bool two, int i, int lane, int wv)
+{
+    __shared__ float e1[4][100], ey[4][24];              // delta1; delta-y3 at 0, delta-y2 at 16
+    e1[wv][lane] = da;
+    if (two) e1[wv][lane + 64] = db;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 16) {
+        float s = 0.0f;
+        for (int o0 = 0; o0 < 100; o0 += 25) {
+            float w[25];
+#pragma unroll
+            for (int j = 0; j < 25; ++j) w[j] = sd.w1y[lane * 100 + o0 + j];
+#pragma unroll
+            for (int j = 0; j < 25; ++j) s = fmaf(w[j], e1[wv][o0 + j], s);
+        }
+        s = y[12 + lane] > 0.f ? s : 0.0f;
+        sd.dy3[(size_t)i * 16 + lane] = s; ey[wv][lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 8) {
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) s = fmaf(sd.f3w[lane * 16 + k], ey[wv][k], s);
+        s = y[4 + lane] > 0.f ? s : 0.0f;
+        sd.dy2[(size_t)i * 8 + lane] = s; ey[wv][16 + lane] = s;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 4) {
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s = fmaf(sd.f2w[lane * 8 + k], ey[wv][16 + k], s);
+        s = y[lane] > 0.f ? s : 0.0f;
+        sd.dy1[(size_t)i * 4 + lane] = s; sd.pf1[(size_t)i * 4 + lane] = y[28] * s;
+    }
+}
+
+// The four kernels share their body as text (trsim_train_tail_body.hpp says why); the LDS arrays are each kernel's own
 __global__ __launch_bounds__(256) void trs_train_tail_kernel(const TailTrainParams p)
 {
     __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
     constexpr bool DROP = false; const TailDropParams dp{};
+    constexpr bool SIDE = false; const TailSideParams sd{};
 #include "trsim_train_tail_body.hpp"
 }
 __global__ __launch_bounds__(256) void trs_train_tail_drop_kernel(const TailTrainParams p, const TailDropParams dp)
 {
     __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
     constexpr bool DROP = true;
+    constexpr bool SIDE = false; const TailSideParams sd{};
+#include "trsim_train_tail_body.hpp"
+}
+__global__ __launch_bounds__(256) void trs_train_tail_side_kernel(const TailTrainParams p, const TailSideParams sd)
+{
+    __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
+    constexpr bool DROP = false; const TailDropParams dp{};
+    constexpr bool SIDE = true;
+#include "trsim_train_tail_body.hpp"
+}
+__global__ __launch_bounds__(256) void trs_train_tail_side_drop_kernel(const TailTrainParams p, const TailDropParams dp, const TailSideParams sd)
+{
+    __shared__ float s1[4][100], s2[4][50], s3[4][25], e4[4][2], e3[4][25], e2[4][50];
+    constexpr bool DROP = true;
+    constexpr bool SIDE = true;
 #include "trsim_train_tail_body.hpp"
 }
 
@@ -99,6 +204,9 @@ constexpr int kSmallGradThreads = 100 + 5000 + 50 + 1250 + 25 + 50 + 2 + 1;   //
 // The loads of kGradAhead frames are requested together and the additions then run in frame order: the sum is the plain ascending one, but a load's round trip
 // to L2 is paid once per kGradAhead frames and not once per frame (one frame at a time measured 364 us per step at 1024 frames: profiles/r31_train_tail.txt)
 constexpr int kGradAhead = 32;
+// KERNEL: one instance per kernel that calls them (0: trs_train_small_kernel, 1: trs_train_small_side_kernel).  The compiler propagates the widths its callers
+// pass into a function before it inlines it; with one instance for both kernels the second kernel's widths changed the first one's code object.
+template <int KERNEL = 0>
 __device__ __forceinline__ float grad_w(const float* z, int nin, const float* d, int nout, int t, int n)
 {
     const int k = t / nout, o = t - k * nout;
@@ -115,6 +223,7 @@ __device__ __forceinline__ float grad_w(const float* z, int nin, const float* d,
     for (; i < n; ++i) { const float a = pz[(size_t)i * nin]; s = fmaf(a > 0.f ? a : 0.f, pd[(size_t)i * nout], s); }
     return s;
 }
+template <int KERNEL = 0>
 __device__ __forceinline__ float grad_b(const float* d, int nout, int o, int n)
 {
     const float* pd = d + o;
@@ -163,6 +272,33 @@ __global__ __launch_bounds__(64) void trs_train_small_kernel(const SmallGradPara
         *p.loss = s;
         if (p.loss_user) *p.loss_user = s;
     }
+}
+
+// The side branch's small gradients (a 28-array session), launched behind trs_train_small_kernel: gW1Y[k][o] = sum_i y3_i[k] delta1_i[o] (rows F .. F + 15 of
+// dense1's kernel, which the GEMM over x7 does not reach), kernel and bias of feature1 .. feature3.  One thread per value, the frames in ascending order, by
+// grad_w and grad_b.  feature1's input is the feature itself, which may be negative, and grad_w gates its first operand: the tail kernel stores the products
+// fin_i delta-y1_i[j], each rounded once, and grad_b adds them.
+struct SmallSideParams {
+    const float *pf1, *y1, *y2, *y3, *d1, *dy1, *dy2, *dy3;   // pf1: the products fin delta-y1 [n][4]
+    float* g; size_t at[7];                              // the gradient buffer and where the seven side arrays lie in it (TrainSession::side_array)
+    int n;
+};
+__global__ __launch_bounds__(64) void trs_train_small_side_kernel(const SmallSideParams p)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < kSideRows * 100) { p.g[p.at[0] + t] = grad_w<1>(p.y3, kSideRows, p.d1, 100, t, p.n); return; }
+    t -= kSideRows * 100;
+    if (t < 4) { p.g[p.at[1] + t] = grad_b<1>(p.pf1, 4, t, p.n); return; }
+    t -= 4;
+    if (t < 4) { p.g[p.at[2] + t] = grad_b<1>(p.dy1, 4, t, p.n); return; }
+    t -= 4;
+    if (t < 32) { p.g[p.at[3] + t] = grad_w<1>(p.y1, 4, p.dy2, 8, t, p.n); return; }
+    t -= 32;
+    if (t < 8) { p.g[p.at[4] + t] = grad_b<1>(p.dy2, 8, t, p.n); return; }
+    t -= 8;
+    if (t < 128) { p.g[p.at[5] + t] = grad_w<1>(p.y2, 8, p.dy3, 16, t, p.n); return; }
+    t -= 128;
+    if (t < 16) p.g[p.at[6] + t] = grad_b<1>(p.dy3, 16, t, p.n);
 }
 
 // ---- delta1 as binary16 under the batch's scale ---------------------------------------------------------------------------------------
@@ -252,6 +388,23 @@ __global__ __launch_bounds__(256) void trs_train_adam_kernel(const float* g, flo
     p.live[a][e - p.off[a]] = ww;
 }
 
+// the seven side arrays of a 28-array session (W1Y, then kernel and bias of feature1 .. feature3): thread per value, the same rule; the new weight goes to the
+// master and to the slot of the tail's blob that trs_pilot_tail_ex_kernel and the side tail kernels read.  bit[j]: the train mask's bit that moves array j.
+struct AdamSideParams { size_t at[7]; int first[8]; float* live[7]; int bit[7]; unsigned mask; };
+__global__ __launch_bounds__(256) void trs_train_adam_side_kernel(const float* g, float* m, float* v, float* w, const AdamSideParams p, const AdamK k)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= p.first[7]) return;
+    int j = 0;
+    while (t >= p.first[j + 1]) ++j;
+    if (!((p.mask >> p.bit[j]) & 1u)) return;
+    const size_t e = p.at[j] + (size_t)(t - p.first[j]);
+    float mm = m[e], vv = v[e];
+    const float ww = adam(g[e], mm, vv, w[e], k);
+    m[e] = mm; v[e] = vv; w[e] = ww;
+    p.live[j][t - p.first[j]] = ww;
+}
+
 // ---- the session (trsim_train_session.hpp) ------------------------------------------------------------------------------------------------
 // where the tail kernels read arrays 1 .. 7; dense1's kernel, array 0, is read as the pack
 void tail_live(const TrsPilotTail& t, float* (&live)[kTrainArrays])
@@ -269,50 +422,69 @@ TRS_EXPORT void trs_default_train_config(trs_train_config* cfg)
     if (cfg) trsim::train_defaults(cfg);
 }
 
-TRS_EXPORT int trs_pilot_train_begin(trs_env* e, const trs_train_config* cfg_or_null, const float* const* h_tail_arrays)
+namespace {
+
+// trs_pilot_train_begin (ex false: 8 arrays, 22-array pilots alone) and trs_pilot_train_begin_ex: the session of the loaded pilot over n_arrays trained arrays
+int begin_session(trs_env* e, const trs_train_config* cfg_or_null, const float* const* h_arrays, int n_arrays, bool ex)
 {
+    if (n_arrays != kTrainArrays && n_arrays != kTrainSideArrays) return trs_internal_fail(TRS_ERR_ARG, "n_arrays must be 8 (a 22-array pilot) or 14 (a 28-array pilot)");
     trs_train_config cfg;
     trsim::train_defaults(&cfg);
+    if (n_arrays == kTrainSideArrays) cfg.train_mask = kTrainMaskAllSide;
     if (cfg_or_null) {
-        if (const char* why = trsim::train_config_error(cfg_or_null)) return trs_internal_fail(TRS_ERR_ARG, why);
+        if (const char* why = trsim::train_config_error_ex(cfg_or_null, n_arrays)) return trs_internal_fail(TRS_ERR_ARG, why);
         cfg = *cfg_or_null;
     }
-    if (!h_tail_arrays || !h_tail_arrays[0]) return trs_internal_fail(TRS_ERR_ARG, "h_tail_arrays[0], dense1's kernel as trs_pilot_load got it, is NULL");
+    if (!h_arrays || !h_arrays[0]) return trs_internal_fail(TRS_ERR_ARG, "h_tail_arrays[0], dense1's kernel as trs_pilot_load got it, is NULL");
     TrsEnvView v; TrsPilotTail t;
     if (int rc = trs_internal_pilot_tail(e, &v, &t)) return rc;
-    if (t.arch != TRS_PILOT_SPD_CTL)
-        return trs_internal_fail(TRS_ERR_LIMIT, "the tail of a 28- or 42-array pilot (cnn_2d_speed_as_feature, cnn_2d_full_house) is not trained: 22 arrays only");
+    if (!ex && t.arch != TRS_PILOT_SPD_CTL)
+        return trs_internal_fail(TRS_ERR_LIMIT, "the tail of a 28- or 42-array pilot (cnn_2d_speed_as_feature, cnn_2d_full_house) is not trained by this call: 22 arrays only "
+                                                "(trs_pilot_train_begin_ex opens the session of a 28-array pilot)");
+    bool limit = false;
+    if (const char* why = trsim::train_count_error(t.arch == TRS_PILOT_SPD_CTL ? 22 : (t.arch == TRS_PILOT_SPD_FTR ? 28 : 42), n_arrays, &limit))
+        return trs_internal_fail(limit ? TRS_ERR_LIMIT : TRS_ERR_ARG, why);
     if (*t.train) return trs_internal_fail(TRS_ERR_STATE, "a training session is already open on this pilot: trs_pilot_train_end first");
     HIPCHK(hipSetDevice(v.device));
     std::unique_ptr<TrainSession> s(new TrainSession());
-    s->cfg = cfg; s->F = t.F; s->n_cap = t.n_cap; s->L = TrainLayout::of(t.F);
-    const size_t total = s->L.off[kTrainArrays] * sizeof(float), n_pad = trsim::align_up((size_t)t.n_cap, kGwFrames);
+    s->cfg = cfg; s->F = t.F; s->n_cap = t.n_cap; s->L = TrainLayout::of(t.F); s->n_arrays = n_arrays;
+    if (s->has_side()) {
+        s->SL = TrainSideLayout::of(t.F); s->L = s->SL.tail();
+        HIPCHK(s->side.alloc((size_t)t.n_cap * side_frame_floats() * sizeof(float)));
+    }
+    const size_t total = s->total() * sizeof(float), n_pad = trsim::align_up((size_t)t.n_cap, kGwFrames);
     HIPCHK(s->master.alloc(total)); HIPCHK(s->m.alloc(total)); HIPCHK(s->v.alloc(total)); HIPCHK(s->g.alloc(total));
     HIPCHK(s->fwd.alloc((size_t)t.n_cap * train_frame_floats() * sizeof(float)));
     HIPCHK(s->q.alloc(n_pad * 128 * sizeof(unsigned short)));
     HIPCHK(s->scal.alloc(4 * sizeof(unsigned)));
     HIPCHK(hipStreamSynchronize(v.stream));
-    HIPCHK(hipMemcpy(s->master.get(), h_tail_arrays[0], s->L.count(0) * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->master.get(), h_arrays[0], s->L.count(0) * sizeof(float), hipMemcpyHostToDevice));
     trs_internal_count(e, 0, (uint64_t)(s->L.count(0) * sizeof(float)));
     float* live[kTrainArrays];
     tail_live(t, live);
     for (int a = 1; a < kTrainArrays; ++a)
         HIPCHK(hipMemcpyAsync(s->master.get() + s->L.off[a], live[a], s->L.count(a) * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
+    for (int j = 1; s->has_side() && j < 7; ++j)                               // feature1 .. feature3 (W1Y came with dense1's kernel)
+        HIPCHK(hipMemcpyAsync(s->master.get() + s->side_array(j), t.side[j], kSideArrayCount[j] * sizeof(float), hipMemcpyDeviceToDevice, v.stream));
     HIPCHK(hipMemsetAsync(s->m.get(), 0, total, v.stream));
     HIPCHK(hipMemsetAsync(s->v.get(), 0, total, v.stream));
     HIPCHK(hipMemsetAsync(s->g.get(), 0, total, v.stream));
+    if (s->has_side()) HIPCHK(hipMemsetAsync(s->side.get(), 0, s->side.bytes(), v.stream));
     HIPCHK(hipMemsetAsync(s->scal.get(), 0, 4 * sizeof(unsigned), v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
     *t.train = s.release();
     return TRS_OK;
 }
 
-TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const float* d_labels, int n, float* d_loss_or_null)
+// trs_pilot_train_step (ex false: no features, 22-array sessions alone) and trs_pilot_train_step_ex
+int train_step(trs_env* e, const uint8_t* d_frames, const float* d_features, const float* d_labels, int n, float* d_loss_or_null, bool ex)
 {
     TrsEnvView v; TrsPilotTail t; TrainSession* s;
     if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    if (!ex && s->has_side()) return trs_internal_fail(TRS_ERR_ARG, "a 28-array session also reads the feature: use trs_pilot_train_step_ex");
     if (n < 1 || n > s->n_cap) return trs_internal_fail(TRS_ERR_ARG, "n must be in [1, n_envs]");
     if (!d_frames || !d_labels) return trs_internal_fail(TRS_ERR_ARG, "d_frames or d_labels is NULL");
+    if (s->has_side() && !d_features) return trs_internal_fail(TRS_ERR_ARG, "d_features is NULL: a 28-array session reads float[n][1], speed / 20 per frame");
     HIPCHK(hipSetDevice(v.device));
     const DropSession& dr = s->drop;
     const uint64_t Dt = dropout_step_key(dr.seed, (uint64_t)(s->t + 1));                  // (read only where a site is on)
@@ -336,14 +508,25 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     tp.max_bits = scal;
     SmallGradParams sp{};
     sp.z1 = tp.z1; sp.z2 = tp.z2; sp.z3 = tp.z3;
+    TailSideParams sd{};
+    if (s->has_side()) {
+        sd.fin = d_features;
+        sd.w1y = t.side[0]; sd.f1w = t.side[1]; sd.f1b = t.side[2]; sd.f2w = t.side[3]; sd.f2b = t.side[4]; sd.f3w = t.side[5]; sd.f3b = t.side[6];
+        sd.kfin = s->side_item(TRS_TRAIN_SIDE_FIN); sd.y1 = s->side_item(TRS_TRAIN_SIDE_Y1); sd.y2 = s->side_item(TRS_TRAIN_SIDE_Y2); sd.y3 = s->side_item(TRS_TRAIN_SIDE_Y3);
+        sd.dy1 = s->side_item(TRS_TRAIN_SIDE_DY1); sd.dy2 = s->side_item(TRS_TRAIN_SIDE_DY2); sd.dy3 = s->side_item(TRS_TRAIN_SIDE_DY3); sd.pf1 = s->side_item(TRS_TRAIN_SIDE_DY3 + 1);
+    }
     if (dr.tail()) {
         TailDropParams dp{};
         dp.Dt = Dt;
         for (int l = 1; l <= 3; ++l) { dp.T[l - 1] = dr.site(l) ? dr.T : 0u; dp.s[l - 1] = dr.site(l) ? dr.s : 1.0f; }
         dp.a1 = s->dropped(1); dp.a2 = s->dropped(2); dp.a3 = s->dropped(3);
+        if (s->has_side()) hipLaunchKernelGGL(trs_train_tail_side_drop_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp, dp, sd);
+        else
         hipLaunchKernelGGL(trs_train_tail_drop_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp, dp);
         // the small kernel takes relu of what it reads, and relu(a') is a' bit for bit (a' is +0 or a non-negative product): it reads a'(l) where it read z(l)
         sp.z1 = dp.a1; sp.z2 = dp.a2; sp.z3 = dp.a3;
+    } else if (s->has_side()) {
+        hipLaunchKernelGGL(trs_train_tail_side_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp, sd);
     } else {
         hipLaunchKernelGGL(trs_train_tail_kernel, dim3((n + 3) / 4), dim3(256), 0, st, tp);
     }
@@ -351,6 +534,13 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     sp.g = s->g.get(); std::memcpy(sp.off, s->L.off, sizeof sp.off);
     sp.loss = reinterpret_cast<float*>(scal + 2); sp.loss_user = d_loss_or_null; sp.n = n;
     hipLaunchKernelGGL(trs_train_small_kernel, dim3((kSmallGradThreads + 63) / 64), dim3(64), 0, st, sp);
+    if (s->has_side()) {
+        SmallSideParams ssp{};
+        ssp.pf1 = sd.pf1; ssp.y1 = sd.y1; ssp.y2 = sd.y2; ssp.y3 = sd.y3; ssp.d1 = tp.d1; ssp.dy1 = sd.dy1; ssp.dy2 = sd.dy2; ssp.dy3 = sd.dy3;
+        ssp.g = s->g.get(); ssp.n = n;
+        for (int j = 0; j < 7; ++j) ssp.at[j] = s->side_array(j);
+        hipLaunchKernelGGL(trs_train_small_side_kernel, dim3((kSideValues + 63) / 64), dim3(64), 0, st, ssp);
+    }
     const int n_pad = (int)trsim::align_up((size_t)n, kGwFrames);
     hipLaunchKernelGGL(trs_train_quant_kernel, dim3(n_pad), dim3(128), 0, st, tp.d1, scal, s->q.get(), reinterpret_cast<int*>(scal + 1), n);
     Gw1Params gp{};
@@ -369,9 +559,60 @@ TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const f
     ap.mask = c.train_mask;
     const size_t small = s->L.off[kTrainArrays] - s->L.off[1];
     hipLaunchKernelGGL(trs_train_adam_kernel, dim3((unsigned)((small + 255) / 256)), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), ap, k);
+    if (s->has_side()) {
+        AdamSideParams asp{};
+        for (int j = 0; j < 7; ++j) {
+            asp.at[j] = s->side_array(j); asp.first[j + 1] = asp.first[j] + (int)kSideArrayCount[j]; asp.live[j] = t.side[j];
+            asp.bit[j] = j == 0 ? 0 : train_mask_bit(kTrainArrays + j - 1);
+        }
+        asp.mask = c.train_mask;
+        hipLaunchKernelGGL(trs_train_adam_side_kernel, dim3((kSideValues + 255) / 256), dim3(256), 0, st, s->g.get(), s->m.get(), s->v.get(), s->master.get(), asp, k);
+    }
     HIPCHK(hipGetLastError());
     s->t += 1; s->last_n = n;
     return TRS_OK;
+}
+
+// trs_pilot_train_get (n_arrays 0: eight arrays, 22-array sessions alone) and trs_pilot_train_get_ex
+int get_masters(trs_env* e, float* const* h_out, int n_arrays, int* t_out_or_null)
+{
+    TrsEnvView v; TrsPilotTail t; TrainSession* s;
+    if (int rc = enter_session(e, &v, &t, &s)) return rc;
+    if (!h_out) return trs_internal_fail(TRS_ERR_ARG, "h_tail_arrays_out is NULL");
+    if (!n_arrays && s->has_side()) return trs_internal_fail(TRS_ERR_ARG, "a 28-array session holds 14 arrays: use trs_pilot_train_get_ex");
+    if (n_arrays && n_arrays != s->n_arrays) return trs_internal_fail(TRS_ERR_ARG, "n_arrays does not match the session: 8 for a 22-array pilot, 14 for a 28-array one");
+    HIPCHK(hipSetDevice(v.device));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    for (int a = 0; a < s->n_arrays; ++a) {
+        if (!h_out[a]) continue;
+        const size_t at = a < kTrainArrays ? s->L.off[a] : s->SL.off[a], count = a < kTrainArrays ? s->L.count(a) : s->SL.count(a);
+        HIPCHK(hipMemcpy(h_out[a], s->master.get() + at, count * sizeof(float), hipMemcpyDeviceToHost));
+        trs_internal_count(e, (uint64_t)(count * sizeof(float)), 0);
+    }
+    if (t_out_or_null) *t_out_or_null = (int)s->t;
+    return TRS_OK;
+}
+
+}  // namespace
+
+TRS_EXPORT int trs_pilot_train_begin(trs_env* e, const trs_train_config* cfg_or_null, const float* const* h_tail_arrays)
+{
+    return begin_session(e, cfg_or_null, h_tail_arrays, kTrainArrays, false);
+}
+
+TRS_EXPORT int trs_pilot_train_begin_ex(trs_env* e, const trs_train_config* cfg_or_null, const float* const* h_arrays, int n_arrays)
+{
+    return begin_session(e, cfg_or_null, h_arrays, n_arrays, true);
+}
+
+TRS_EXPORT int trs_pilot_train_step(trs_env* e, const uint8_t* d_frames, const float* d_labels, int n, float* d_loss_or_null)
+{
+    return train_step(e, d_frames, nullptr, d_labels, n, d_loss_or_null, false);
+}
+
+TRS_EXPORT int trs_pilot_train_step_ex(trs_env* e, const uint8_t* d_frames, const float* d_features, const float* d_labels, int n, float* d_loss_or_null)
+{
+    return train_step(e, d_frames, d_features, d_labels, n, d_loss_or_null, true);
 }
 
 // ---- dropout behind conv7 (trsim_dropout.hpp) -------------------------------------------------------------------------------------------
@@ -420,17 +661,32 @@ TRS_EXPORT int trs_pilot_train_dropout(trs_env* e, const trs_dropout_config* cfg
 
 TRS_EXPORT int trs_pilot_train_get(trs_env* e, float* const* h_tail_arrays_out, int* t_out_or_null)
 {
+    return get_masters(e, h_tail_arrays_out, 0, t_out_or_null);
+}
+
+TRS_EXPORT int trs_pilot_train_get_ex(trs_env* e, float* const* h_arrays_out, int n_arrays, int* t_out_or_null)
+{
+    if (n_arrays != kTrainArrays && n_arrays != kTrainSideArrays) return trs_internal_fail(TRS_ERR_ARG, "n_arrays must be 8 (a 22-array pilot) or 14 (a 28-array pilot)");
+    return get_masters(e, h_arrays_out, n_arrays, t_out_or_null);
+}
+
+TRS_EXPORT int trs_pilot_train_debug_side(trs_env* e, int which, float* h_dst, size_t n_floats)
+{
     TrsEnvView v; TrsPilotTail t; TrainSession* s;
     if (int rc = enter_session(e, &v, &t, &s)) return rc;
-    if (!h_tail_arrays_out) return trs_internal_fail(TRS_ERR_ARG, "h_tail_arrays_out is NULL");
+    if (!s->has_side()) return trs_internal_fail(TRS_ERR_STATE, "the session has no side branch: a 28-array pilot's alone has (trs_pilot_train_begin_ex)");
+    if (!s->last_n) return trs_internal_fail(TRS_ERR_STATE, "no training step yet");
+    const size_t want = trsim::train_side_debug_floats(which, s->last_n);
+    if (!want || !h_dst) return trs_internal_fail(TRS_ERR_ARG, "unknown item (TRS_TRAIN_SIDE_*) or NULL destination");
+    if (n_floats != want) return trs_internal_fail(TRS_ERR_ARG, "size mismatch");
     HIPCHK(hipSetDevice(v.device));
     HIPCHK(hipStreamSynchronize(v.stream));
-    for (int a = 0; a < kTrainArrays; ++a) {
-        if (!h_tail_arrays_out[a]) continue;
-        HIPCHK(hipMemcpy(h_tail_arrays_out[a], s->master.get() + s->L.off[a], s->L.count(a) * sizeof(float), hipMemcpyDeviceToHost));
-        trs_internal_count(e, (uint64_t)(s->L.count(a) * sizeof(float)), 0);
-    }
-    if (t_out_or_null) *t_out_or_null = (int)s->t;
+    const float* src;
+    if (which <= TRS_TRAIN_SIDE_DY3) src = s->side_item(which);
+    else if (which < TRS_TRAIN_SIDE_M) src = s->g.get() + s->side_array(which - TRS_TRAIN_SIDE_G);
+    else if (which < TRS_TRAIN_SIDE_V) src = s->m.get() + s->side_array(which - TRS_TRAIN_SIDE_M);
+    else src = s->v.get() + s->side_array(which - TRS_TRAIN_SIDE_V);
+    HIPCHK(hipMemcpy(h_dst, src, want * sizeof(float), hipMemcpyDeviceToHost));
     return TRS_OK;
 }
 

@@ -50,6 +50,15 @@ struct TrainSession {
     DevBuf<unsigned short> q;             // [n_cap padded to 64][128]
     DevBuf<unsigned> scal;                // [0] max |delta1| bits, [1] the scale's exponent (int), [2] the loss (float)
     std::unique_ptr<ConvSession> conv;    // empty: the convolutions stay as loaded
+    // a 28-array session (n_arrays 14): master, m, v and g hold SL's 14 arrays, of which L names the first eight; `side` is fin | y1 | y2 | y3 | delta-y1 |
+    // delta-y2 | delta-y3 | fin delta-y1 (kSideFrameWidth), each for n_cap frames
+    int n_arrays = kTrainArrays;
+    TrainSideLayout SL{};
+    DevBuf<float> side;
+    bool has_side() const { return n_arrays == kTrainSideArrays; }
+    size_t total() const { return has_side() ? SL.off[kTrainSideArrays] : L.off[kTrainArrays]; }
+    float* side_item(int which) const { return side.get() + (size_t)n_cap * side_frame_floats(which); }   // TRS_TRAIN_SIDE_FIN .. DY3
+    size_t side_array(int j) const { return j == 0 ? SL.w1y() : SL.off[kTrainArrays + j - 1]; }             // where side array j (0..6) lies in the four buffers
     float* item(int which) const { return fwd.get() + (size_t)n_cap * train_frame_floats(which); }   // TRS_TRAIN_DBG_OUT .. DELTA4
     float* dropped(int l) const                                                                      // a'(l), l = 1 .. 3
     {

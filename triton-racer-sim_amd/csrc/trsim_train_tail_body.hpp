@@ -1,9 +1,13 @@
-// trsim_train_tail_body.hpp — the body of trs_train_tail_kernel and trs_train_tail_drop_kernel (trsim_train.hip), included once in each: no include guard.
-// The including kernel declares `p` (TailTrainParams), `dp` (TailDropParams), `constexpr bool DROP` and the six LDS arrays s1, s2, s3, e4, e3, e2.  The two
+// trsim_train_tail_body.hpp — the body of trs_train_tail_kernel, trs_train_tail_drop_kernel and their two SIDE siblings (trsim_train.hip), included once in
+// each: no include guard.  The including kernel declares `p` (TailTrainParams), `dp` (TailDropParams), `sd` (TailSideParams), `constexpr bool DROP`,
+// `constexpr bool SIDE` and the six LDS arrays s1, s2, s3, e4, e3, e2.  The
 // kernels share this text and not a function: inlined from a function template, the plain kernel's code object was no longer the one it is (registers
 // allocated otherwise); expanded in place it is, instruction for instruction (scripts/kernel_diff.py).
 // DROP (include/trsim_spec.h, "training the pilot's tail, dropout"): a'(l) = keep ? relu(z(l)) s : +0 replaces relu(z(l)) and is stored; delta(l) =
 // keep and z(l) > 0 ? (W(l+1) delta(l+1)) s : +0.  Lane k draws the units it owns: the frame's key per site, then one mix per unit (trsim_dropout.hpp).
+// SIDE (include/trsim_spec.h, "training the pilot's tail, side branch"): the branch fin -> y1 -> y2 -> y3 runs first (side_forward), the rows W1Y of dense1
+// behind the flatten are added to z1 behind the slabs, k ascending, as trs_pilot_tail_ex_kernel adds them, and delta1 goes on through W1Y and the branch
+// (side_backward).  The LDS of both is theirs, so the plain kernels declare none of it.
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wv;
     if (i >= p.n) return;                                // whole waves
@@ -15,11 +19,20 @@
         k1a = dropout_keep(key1, (uint32_t)lane, dp.T[0]); k1b = dropout_keep(key1, (uint32_t)lane + 64u, dp.T[0]);
         k2 = dropout_keep(key2, (uint32_t)lane, dp.T[1]); k3 = dropout_keep(key3, (uint32_t)lane, dp.T[2]);
     }
+    float* ys = nullptr;                                 // SIDE: the wave's y1 | y2 | y3 in LDS
+    if constexpr (SIDE) ys = side_forward(sd, i, lane, wv);
     float z1a = 0.0f, z1b = 0.0f;
     for (int sl = 0; sl < p.slices; ++sl) {
         const float* src = p.h1 + (size_t)sl * p.stride + (size_t)i * 100 + lane;
         z1a += src[0];
         z1b += src[two ? 64 : 0];
+    }
+    if constexpr (SIDE) {
+        float wa[kSideRows], wb[kSideRows];
+#pragma unroll
+        for (int k = 0; k < kSideRows; ++k) { wa[k] = sd.w1y[k * 100 + lane]; wb[k] = sd.w1y[k * 100 + lane + (two ? 64 : 0)]; }
+#pragma unroll
+        for (int k = 0; k < kSideRows; ++k) { z1a = fmaf(ys[12 + k], wa[k], z1a); z1b = fmaf(ys[12 + k], wb[k], z1b); }
     }
     if constexpr (DROP) {
         const float aa = k1a ? (z1a > 0.f ? z1a : 0.f) * dp.s[0] : 0.f, ab = k1b ? (z1b > 0.f ? z1b : 0.f) * dp.s[0] : 0.f;
@@ -86,4 +99,5 @@
         p.d1[(size_t)i * 100 + lane] = da;
         if (two) p.d1[(size_t)i * 100 + lane + 64] = db;
     }
+    if constexpr (SIDE) side_backward(sd, ys, da, db, two, i, lane, wv);
     wave_max_bits(max(__float_as_uint(da) & 0x7FFFFFFFu, __float_as_uint(db) & 0x7FFFFFFFu), p.max_bits, lane);   // the batch's largest |delta1|

@@ -323,10 +323,16 @@ class DeviceDataset:
         behind conv7 and the hidden dense layers ("training the pilot's tail, dropout"), in the training steps alone — ``train_loss`` is the
         dropped network's, ``val_loss`` is taken without dropout, as Keras reports them.  Returns the list of ``(train_loss, val_loss)`` per epoch
         run, ``train_loss`` the mean of the batches' losses.
-        Not here: dropout behind conv1 .. conv6, training conv1 .. conv3, the model types with side inputs."""
+        With a 28-array pilot loaded (``cnn_2d_speed_as_feature``) the set must come from the ``speed_feature`` loader: each batch's feature, speed / 20,
+        goes into the step with its frames, and feature1 .. feature3 move with the tail ("training the pilot's tail, side branch"; ``layers`` also takes
+        their names); the best epoch's 14 arrays are kept and restored.
+        Not here: dropout behind conv1 .. conv6, training conv1 .. conv3, ``cnn_2d_full_house``."""
         if not self.with_frames:
             raise RuntimeError("a physics-only set has no frames for the pilot")
         torch, env = self.torch, self.env
+        side = len(getattr(env, "_pilot_arrays", None) or ()) == 28
+        if side and self.loader != "speed_feature":
+            raise ValueError(f"a 28-array pilot (cnn_2d_speed_as_feature) trains on the 'speed_feature' loader's batches: this set's loader is {self.loader!r}")
         epochs, batch_size = int(epochs), int(batch_size)
         if epochs < 1 or not 1 <= batch_size <= env.n:
             raise ValueError(f"epochs >= 1 and batch_size in [1, n_envs = {env.n}] are required")
@@ -342,9 +348,9 @@ class DeviceDataset:
                 n_batches = self.n_train // batch_size
                 losses = torch.zeros((n_batches,), dtype=torch.float32, device=self.device)
                 for epoch in range(epochs):
-                    for t, (images, _, labels) in enumerate(self.batches(batch_size, epoch, "train", layout="nhwc", dtype="uint8", stream=stream, augment=augment)):
+                    for t, (images, feats, labels) in enumerate(self.batches(batch_size, epoch, "train", layout="nhwc", dtype="uint8", stream=stream, augment=augment)):
                         # the gather and the step run on the env's stream, one behind the other: the torch stream's wait inside batches() is all the order needed
-                        env.pilot_train_step(images, labels, batch_size, loss=losses[t:])
+                        env.pilot_train_step(images, labels, batch_size, loss=losses[t:], features=feats if side else None)
                     self._torch_after_env()
                     train_loss = float(losses.double().mean().item())
                     val_loss = self.pilot_loss("val", val_batch_size)
@@ -360,7 +366,7 @@ class DeviceDataset:
             env.pilot_train_end()
         if best is not None:
             arrs = env.pilot_weights()
-            arrs[14:22] = best[0]
+            arrs[14:14 + len(best[0])] = best[0]
             if best[1] is not None:
                 arrs[6:14] = best[1]
             env.pilot_load(arrs)

@@ -868,17 +868,29 @@ class BatchedEnv:
         if getattr(self, "_pilot_arrays", None) is None:
             raise RuntimeError("no pilot loaded: pilot_load first")
 
+    def _train_side(self):
+        """True when the loaded pilot is the 28-array type (``cnn_2d_speed_as_feature``): 14 trained arrays, a feature per frame."""
+        return len(self._pilot_arrays) == 28
+
+    def _train_arrays(self):
+        """The trained arrays' places in ``pilot_load``'s list: 14 .. 21 for a 22-array pilot, 14 .. 27 for a 28-array one."""
+        return slice(14, 28 if self._train_side() else 22)
+
     def train_config(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None):
         """``trs_train_config``: Adam's constants (Keras's ``optimizers.Adam(lr=0.001)`` by default) and the layers that move — ``layers``: names
-        out of ``_ffi.TRAIN_LAYERS`` (``None``: all four)."""
+        out of ``_ffi.TRAIN_LAYERS`` (``None``: all four); with a 28-array pilot loaded, out of ``_ffi.TRAIN_SIDE_LAYERS``, which adds
+        ``"feature1"`` .. ``"feature3"`` (``None``: all seven)."""
         c = _ffi.TrsTrainConfig()
         self.api.default_train_config(C.byref(c))
         c.lr, c.beta1, c.beta2, c.eps = float(lr), float(beta1), float(beta2), float(eps)
+        names = _ffi.TRAIN_SIDE_LAYERS if getattr(self, "_pilot_arrays", None) is not None and self._train_side() else _ffi.TRAIN_LAYERS
         if layers is not None:
-            unknown = [nm for nm in layers if nm not in _ffi.TRAIN_LAYERS]
+            unknown = [nm for nm in layers if nm not in names]
             if unknown:
-                raise ValueError(f"layers must come from {_ffi.TRAIN_LAYERS}: {unknown}")
-            c.train_mask = sum(1 << _ffi.TRAIN_LAYERS.index(nm) for nm in set(layers))
+                raise ValueError(f"layers must come from {names}: {unknown}")
+            c.train_mask = sum(1 << names.index(nm) for nm in set(layers))
+        else:
+            c.train_mask = (1 << len(names)) - 1
         return c
 
     def dropout_config(self, rate=0.1, sites=None, seed=0):
@@ -909,14 +921,16 @@ class BatchedEnv:
         if (rate is None or seed is None) and last is None:
             raise RuntimeError("no session with dropout on this handle: pass rate and seed")
         cfg = self.dropout_config(last[0] if rate is None else rate, None, last[1] if seed is None else seed)
-        width = int(self._pilot_arrays[14].shape[0]) if site == 0 else (100, 50, 25)[site - 1] if 1 <= site <= 3 else 0
+        flatten = int(self._pilot_arrays[14].shape[0]) - (16 if self._train_side() else 0)    # site 0 masks x7 alone: the branch joins behind that Dropout
+        width = flatten if site == 0 else (100, 50, 25)[site - 1] if 1 <= site <= 3 else 0
         keep = np.empty((max(int(n), 0), width), np.uint8)
         self.api.check(self.api.train_dropout_keep(C.byref(cfg), int(t), site, int(n), width, keep.ctypes.data), "train_dropout_keep")
         return keep.astype(bool)
 
     def pilot_train_begin(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, layers=None, convs=None, dropout=None, dropout_sites=None, dropout_seed=0):
         """Open a training session on the loaded pilot's dense tail (``trs_pilot_train_begin``): fp32 master weights from the arrays ``pilot_load``
-        was given, Adam's moments at zero.  22-array model types only.  ``convs``: names out of ``_ffi.TRAIN_CONV_LAYERS`` (``"conv4"`` ..
+        was given, Adam's moments at zero.  With a 28-array pilot (``cnn_2d_speed_as_feature``) the session also trains feature1 .. feature3 and
+        dense1's rows behind the flatten (``trs_pilot_train_begin_ex``), and every step takes the feature; ``cnn_2d_full_house`` is refused.  ``convs``: names out of ``_ffi.TRAIN_CONV_LAYERS`` (``"conv4"`` ..
         ``"conv7"``) that are trained as well (``trs_pilot_train_convs``); ``None``: the convolutions stay as loaded.  conv1 .. conv3 always do.
         ``dropout``: the rate of training-mode dropout behind conv7 and the three hidden dense layers (``trs_pilot_train_dropout``; the reference's
         is 0.1), ``dropout_sites`` the sites (``dropout_config``; ``None``: all four), ``dropout_seed`` the seed of the draws; ``None``: no
@@ -931,9 +945,12 @@ class BatchedEnv:
             if unknown:
                 raise ValueError(f"convs must come from {_ffi.TRAIN_CONV_LAYERS}: {unknown}")
             mask = sum(1 << _ffi.TRAIN_CONV_LAYERS.index(nm) for nm in set(convs))
-        tail = self._pilot_arrays[14:22]
-        ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in tail])
-        self.api.check(self.api.pilot_train_begin(self._h, C.byref(cfg), ptrs), "pilot_train_begin")
+        tail = self._pilot_arrays[self._train_arrays()]
+        ptrs = (C.c_void_p * len(tail))(*[a.ctypes.data for a in tail])
+        if len(self._pilot_arrays) == 22:
+            self.api.check(self.api.pilot_train_begin(self._h, C.byref(cfg), ptrs), "pilot_train_begin")
+        else:                                                           # (a 42-array pilot: the library's refusal)
+            self.api.check(self.api.pilot_train_begin_ex(self._h, C.byref(cfg), ptrs, len(tail)), "pilot_train_begin_ex")
         self._train_convs = False
         self._train_dropout = None
 
@@ -951,14 +968,20 @@ class BatchedEnv:
             second(self.api.pilot_train_dropout(self._h, C.byref(drop)), "pilot_train_dropout")
             self._train_dropout = (float(dropout), int(dropout_seed))
 
-    def pilot_train_step(self, frames, labels, n=None, loss=None):
+    def pilot_train_step(self, frames, labels, n=None, loss=None, features=None):
         """One Adam step on ``frames uint8[n, H, W, 3]`` and ``labels float32[n, 2]`` on the device (torch tensors, anything with
         ``__cuda_array_interface__``, or device pointers with ``n``), ``n <= n_envs``.  Asynchronous on the env's stream.  ``loss``: a device
-        float32 the batch's loss (before the update) is written to, and the call returns ``None``; without it the call waits and returns the loss."""
+        float32 the batch's loss (before the update) is written to, and the call returns ``None``; without it the call waits and returns the loss.
+        ``features``: ``float32[n, 1]`` on the device, speed / 20 per frame as the ``speed_feature`` loader delivers it: required by the session of a
+        28-array pilot (``trs_pilot_train_step_ex``), not read by a 22-array one."""
         self._need_train()
         if n is None:
             n = int(frames.shape[0])
-        self.api.check(self.api.pilot_train_step(self._h, device_ptr(frames), device_ptr(labels), int(n), device_ptr(loss)), "pilot_train_step")
+        if features is None and not self._train_side():
+            self.api.check(self.api.pilot_train_step(self._h, device_ptr(frames), device_ptr(labels), int(n), device_ptr(loss)), "pilot_train_step")
+        else:
+            self.api.check(self.api.pilot_train_step_ex(self._h, device_ptr(frames), device_ptr(features), device_ptr(labels), int(n), device_ptr(loss)),
+                           "pilot_train_step_ex")
         self._train_last_n = int(n)
         if loss is not None:
             return None
@@ -969,23 +992,42 @@ class BatchedEnv:
         float32 array (``trs_pilot_train_debug``); the caller reshapes."""
         self._need_train()
         which = _ffi.TRAIN_DEBUG[item] + (int(array) if item in ("m", "v") else 0)
-        F = int(self._pilot_arrays[14].shape[0])
+        F = int(self._pilot_arrays[14].shape[0]) - (16 if self._train_side() else 0)     # the flatten's length: the items of dense1's kernel cover its rows
         n = int(getattr(self, "_train_last_n", 0))
         sizes = {"out": 2 * n, "z1": 100 * n, "z2": 50 * n, "z3": 25 * n, "delta1": 100 * n, "delta2": 50 * n, "delta3": 25 * n, "delta4": 2 * n,
                  "gw1": F * 100, "gw2": 5000, "gw3": 1250, "gw4": 50, "gb1": 100, "gb2": 50, "gb3": 25, "gb4": 2, "scale_exp": 1, "loss": 1, "pack1": F * 100,
                  "a1": 100 * n, "a2": 50 * n, "a3": 25 * n}
-        size = self._pilot_arrays[14 + int(array)].size if item in ("m", "v") else sizes[item]
+        size = sizes["gw1"] if item in ("m", "v") and int(array) == 0 else self._pilot_arrays[14 + int(array)].size if item in ("m", "v") else sizes[item]
         out = np.empty(size, np.float32)
         self.api.check(self.api.pilot_train_debug(self._h, which, out.ctypes.data, out.size), "pilot_train_debug")
         return out
 
-    def pilot_train_weights(self):
-        """``(arrays, t)``: the eight fp32 master arrays dense1 .. output_layer in Keras layouts and the number of steps taken (``trs_pilot_train_get``)."""
+    def pilot_train_debug_side(self, item, array=None):
+        """Item ``item`` (a key of ``_ffi.TRAIN_SIDE_DEBUG``) of the last training step of a 28-array session as a flat float32 array
+        (``trs_pilot_train_debug_side``); ``"g"``, ``"m"`` and ``"v"`` take the side array's name, a key of ``_ffi.TRAIN_SIDE_ARRAYS`` (``"w1y"``: rows
+        F .. F + 15 of dense1's kernel)."""
         self._need_train()
-        outs = [np.empty_like(a) for a in self._pilot_arrays[14:22]]
-        ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in outs])
+        which, per_frame = _ffi.TRAIN_SIDE_DEBUG[item]
+        if per_frame is None:
+            j, size = _ffi.TRAIN_SIDE_ARRAYS[array]
+            which += j
+        else:
+            size = per_frame * int(getattr(self, "_train_last_n", 0))
+        out = np.empty(size, np.float32)
+        self.api.check(self.api.pilot_train_debug_side(self._h, which, out.ctypes.data, out.size), "pilot_train_debug_side")
+        return out
+
+    def pilot_train_weights(self):
+        """``(arrays, t)``: the fp32 master arrays in Keras layouts — the eight of dense1 .. output_layer, and behind them the six of feature1 ..
+        feature3 for a 28-array pilot — and the number of steps taken (``trs_pilot_train_get``, ``trs_pilot_train_get_ex``)."""
+        self._need_train()
+        outs = [np.empty_like(a) for a in self._pilot_arrays[self._train_arrays()]]
+        ptrs = (C.c_void_p * len(outs))(*[a.ctypes.data for a in outs])
         t = C.c_int(0)
-        self.api.check(self.api.pilot_train_get(self._h, ptrs, C.byref(t)), "pilot_train_get")
+        if len(outs) == 8:
+            self.api.check(self.api.pilot_train_get(self._h, ptrs, C.byref(t)), "pilot_train_get")
+        else:
+            self.api.check(self.api.pilot_train_get_ex(self._h, ptrs, len(outs), C.byref(t)), "pilot_train_get_ex")
         return outs, int(t.value)
 
     def pilot_train_conv_weights(self):
@@ -1024,7 +1066,7 @@ class BatchedEnv:
         convs = self.pilot_train_conv_weights() if getattr(self, "_train_convs", False) else list(self._pilot_arrays[6:14])
         self.api.check(self.api.pilot_train_end(self._h), "pilot_train_end")
         self._train_convs = False
-        self._pilot_arrays = list(self._pilot_arrays[:6]) + convs + tail + list(self._pilot_arrays[22:])
+        self._pilot_arrays = list(self._pilot_arrays[:6]) + convs + tail + list(self._pilot_arrays[14 + len(tail):])
 
     def pilot_weights(self):
         """The arrays given to ``pilot_load`` with the trained ones replaced (the masters of an open session, or what the last session left): ready
@@ -1032,11 +1074,13 @@ class BatchedEnv:
         if getattr(self, "_pilot_arrays", None) is None:
             raise RuntimeError("no pilot loaded: pilot_load first")
         arrs = [a.copy() for a in self._pilot_arrays]
-        if getattr(self.api, "has_train", False) and len(arrs) == 22:
-            outs = [np.empty_like(a) for a in arrs[14:22]]
-            ptrs = (C.c_void_p * 8)(*[a.ctypes.data for a in outs])
-            if self.api.pilot_train_get(self._h, ptrs, None) == 0:      # an open session: its masters (refused without one: the arrays as kept)
-                arrs[14:22] = outs
+        if getattr(self.api, "has_train", False) and len(arrs) in (22, 28):
+            where = self._train_arrays()
+            outs = [np.empty_like(a) for a in arrs[where]]
+            ptrs = (C.c_void_p * len(outs))(*[a.ctypes.data for a in outs])
+            rc = self.api.pilot_train_get(self._h, ptrs, None) if len(outs) == 8 else self.api.pilot_train_get_ex(self._h, ptrs, len(outs), None)
+            if rc == 0:                                                 # an open session: its masters (refused without one: the arrays as kept)
+                arrs[where] = outs
                 if getattr(self, "_train_convs", False):
                     arrs[6:14] = self.pilot_train_conv_weights()
         return arrs
